@@ -7,6 +7,11 @@ N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ..
 (one rank per GPU over RCCL), or -- when WORLD_SIZE is not set -- this process starts exactly that command as a
 CHILD (before any HIP call of its own) and relays rank 0's JSON line and the exit code.
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").
+
+A plain run only sets up, warms up, times the K steps and prints the line (`ms_per_step` = one timed step).  `--full` adds
+what needs passes of its own: the per-kernel roofline, the `alt_*` precisions, the CPU baseline, the exposed all-reduce
+time at N > 1.  `--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy (seeded inputs: same arguments,
+same inputs, so two builds compare output for output).
 """
 import argparse
 import json
@@ -99,7 +104,20 @@ def parse():
     ap.add_argument("--dp-selftest", action="store_true",
                     help="N=1: price the data-parallel machinery on ONE GPU -- the same step plain and with the 4 gradient "
                          "buckets all-reduced over a single-rank RCCL group (BucketAllReducer(force=True)); one JSON line")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="headline workload: also run what takes passes of its own after the timed steps -- the per-kernel "
+                         "roofline (HIP-event passes), the f32x3 / bf16 alt_* figures, the CPU oracle baseline and, at N > 1, "
+                         "the exposed all-reduce time.  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline workload: after the timed steps write what the last timed step gave its caller -- the "
+                         "loss, the parameters and gradients (seeded fixed sample), the BatchNorm running statistics -- as "
+                         "DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.dump_outputs is not None and (args.workload != "denoiser" or args.dp_selftest):
+        ap.error("--dump-outputs: the headline workload only (--workload denoiser, no --dp-selftest)")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def log(msg):
@@ -711,6 +729,35 @@ def dp_selftest(args):
         raise SystemExit("dp-selftest: bucketed gradients differ from the plain pass")
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of a larger dumped array (16 MB of float32): 3 such arrays stay under 64 MB
+
+
+def dump_outputs(out_dir, model, loss):
+    """What one optimiser step hands back to its caller: the loss, the model's parameters and gradients after it (in
+    named_parameters() order; a fixed, seeded sample of DUMP_SAMPLE elements when larger) and the BatchNorm running
+    statistics.  Same arguments -> same inputs, so two builds can be compared file by file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    arrays = {"loss": loss.detach().reshape(-1),
+              "parameters": torch.cat([p.detach().reshape(-1) for p in params])}
+    if all(p.grad is not None for p in params):
+        arrays["gradients"] = torch.cat([p.grad.detach().reshape(-1) for p in params])
+    elif model.flat_grads is not None:  # (gradients not published as .grad: the flat buffer, same order)
+        arrays["gradients"] = model.flat_grads.detach().reshape(-1)
+    arrays["bn_running_stats"] = torch.cat([b.detach().reshape(-1) for n, b in model.named_buffers()
+                                            if n.endswith((".running_mean", ".running_var"))])
+    index = None
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            if index is None or index[1] != a.size:
+                index = (np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False)), a.size)
+            a = a[index[0]]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(n + '.npy' for n in arrays)}")
+
+
 def self_launch(args):
     """`python bench.py --gpus N` (N > 1) with no launcher around it: start
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>` as a CHILD process
@@ -864,7 +911,7 @@ def main():
         if i == 0:
             torch.cuda.synchronize()
             log("first step done")
-    use_events = not args.no_kernel_events
+    use_events = args.full and not args.no_kernel_events
     # N > 1: the exchange configuration is MEASURED on this job, not assumed (no N > 1 box existed while this was
     # written): every rank times every candidate over the same steps, one all_reduce(MAX) per candidate gives all ranks
     # the same table, the first minimum runs the timed region.  N = 1: nothing happens here.
@@ -896,10 +943,12 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     log(f"timed region done: {dt:.3f}s for {args.steps} steps")
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, lit.model, loss)
     # N > 1: what the exchange still costs the optimiser's stream -- the stall inside reducer.wait(), bracketed by HIP
-    # events on that stream, in a pass of its own right after the timed region (an event pair taxes the stream)
+    # events on that stream, in a pass of its own right after the timed region (an event pair taxes the stream); --full only
     exposed_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         dp.reducer.timing = True
         for i in range(min(args.steps, 5)):
             loss = step(args.warmup + args.steps + i)
@@ -908,7 +957,7 @@ def main():
         ex = torch.tensor([mine if mine is not None else -1.0], dtype=torch.float64, device=dev)
         dist.all_reduce(ex, op=dist.ReduceOp.MAX)
         exposed_ms = round(float(ex.item()), 4) if nwaits else None
-    # Kernel-level roofline figures: HIP events around every launch of a kernel class, in two passes of `diag` steps
+    # Kernel-level roofline figures (--full): HIP events around every launch of a kernel class, in two passes of `diag` steps
     # RIGHT AFTER the timed region (same process, same resident batches, same clocks) -- not inside it: an event pair
     # costs ~8 us of stream time (its marker packets drain the queue), 97 pairs per step would tax `value` by ~2 %.
     # Pass 1: the roofline kernel conv_igemm_kernel (+ its LDS-patch forms), 47 forward + ~50 data-gradient launches
@@ -1037,13 +1086,13 @@ def main():
     else:
         out["roofline"] = {"bound": "mfma", "achieved": None, "peak": peak, "unit": "TFLOP/s", "frac": None,
                            "traffic": None}
-    if world == 1 and args.dtype == "f32" and not args.no_alt:
+    if args.full and world == 1 and args.dtype == "f32" and not args.no_alt:
         del lit, opt, data, step  # free the fp32 run's 2 GB workspace before building the next model
         for alt in ("f32x3", "bf16"):
             torch.cuda.empty_cache()
             out["alt_" + alt] = alt_dtype(args, dev, alt)
             log(f"alt {alt}: {out['alt_' + alt]['value']} images/s")
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.size, args.batch, args.cpu_steps)
     print(json.dumps(out), flush=True)
     if world > 1:

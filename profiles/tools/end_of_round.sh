@@ -25,11 +25,11 @@ else
   bash profiles/tools/kernel_stats.sh ${TAG}_end > $O/ks.log 2>&1; tail -1 $O/ks.log
   bash profiles/tools/kernel_stats.sh ${TAG}_end_bf16 --dtype bf16 > $O/ks_bf16.log 2>&1; tail -1 $O/ks_bf16.log
   bash profiles/tools/kernel_stats.sh ${TAG}_end_128 --size 128 > $O/ks_128.log 2>&1; tail -1 $O/ks_128.log
-  python bench.py > $O/bench.json 2> $O/bench.err
-  python bench.py --dtype bf16 --no-cpu-baseline > $O/bench_bf16.json 2>/dev/null
-  python bench.py --size 128 --no-cpu-baseline --no-alt > $O/bench_128.json 2>/dev/null
-  python bench.py --size 128 --dtype bf16 --no-cpu-baseline > $O/bench_128_bf16.json 2>/dev/null
-  python bench.py --size 448 --batch 14 --no-cpu-baseline --no-alt > $O/bench_448.json 2>/dev/null
+  python bench.py --full > $O/bench.json 2> $O/bench.err
+  python bench.py --full --dtype bf16 --no-cpu-baseline > $O/bench_bf16.json 2>/dev/null
+  python bench.py --full --size 128 --no-cpu-baseline --no-alt > $O/bench_128.json 2>/dev/null
+  python bench.py --full --size 128 --dtype bf16 --no-cpu-baseline > $O/bench_128_bf16.json 2>/dev/null
+  python bench.py --full --size 448 --batch 14 --no-cpu-baseline --no-alt > $O/bench_448.json 2>/dev/null
   python bench.py --workload deepfake > $O/workload_deepfake.json 2>/dev/null
   python bench.py --workload deepfake --pair-fused off > $O/workload_deepfake_sequential.json 2>/dev/null
   python bench.py --workload deepfake --dtype bf16 > $O/workload_deepfake_bf16.json 2>/dev/null

@@ -362,3 +362,21 @@ def test_unet_pair_host_protocol():
     with pytest.raises(ValueError):
         a.set_plan_nets(3)
     assert a.set_plan_nets(2) is a and a.plan_nets == 2 and copy.deepcopy(a).plan_nets == 2
+
+
+def test_bench_dump_outputs_is_the_headline_workloads(monkeypatch, capsys):
+    """--dump-outputs writes what the headline step computed: any other workload is refused before anything runs."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("d3f_bench", str(ROOT / "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    for argv in (["--workload", "deepfake"], ["--dp-selftest"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", "out"] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2 and "--dump-outputs" in capsys.readouterr().err
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "4", "--warmup", "2", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.steps == 4 and args.warmup == 2 and args.dump_outputs == "out" and args.full is False
+    assert not torch.cuda.is_initialized()

@@ -223,7 +223,7 @@ def test_bench_self_launch_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(D3F_FORCE_DEVICE="0", D3F_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--batch", "4",
-           "--size", "64", "--dp-buckets", "2"]
+           "--size", "64", "--dp-buckets", "2", "--full"]   # --full: the kernel-event roofline and the exposed exchange time
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -330,7 +330,7 @@ def test_bench_self_launch_four_ranks_replicas_identical():
     # scaling run: 2 and 4 buckets timed behind the warm-up, one all_reduce(MAX) per candidate, the faster one runs the
     # timed region (the agreement logic itself: tests/test_cpu_distributed.py, gloo world 4)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1", "--batch", "4",
-           "--size", "64", "--dp-autotune-steps", "2", "--dist-timeout", "120"]
+           "--size", "64", "--dp-autotune-steps", "2", "--dist-timeout", "120", "--full"]   # (--full: exposed exchange time)
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -779,3 +779,39 @@ def test_fit_on_an_image_list_uint8_batches_equal_float_batches(tmp_path):
     assert len(l_f32) == 6 and l_f32 == l_u8 and torch.equal(p_f32, p_u8)
     l_w, p_w = run(True, 2)   # spawned workers + pinned staging: same batches (the sampler's permutation is seeded), same result
     assert l_w == l_f32 and torch.equal(p_w, p_f32)
+
+
+def test_bench_plain_run_full_run_and_dumped_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` as the headline is measured: exactly K timed steps, the result line with
+    `ms_per_step`, none of the extra passes; `--dump-outputs DIR` writes the last timed step's loss, parameters, gradients
+    and BatchNorm statistics as float32 .npy files (64 MB at most).  `--full` adds the per-kernel roofline and the alt_*
+    figures (CPU baseline left out here: it is minutes of host time at any size)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+            "--size", "64"]
+
+    def run(*extra):
+        out = subprocess.run(base + list(extra), capture_output=True, text=True, timeout=240, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        return json.loads(lines[0])
+    res = run("--dump-outputs", str(tmp_path / "dump"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in res, k
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["dtype"] == "f32" and res["ms_per_step"] > 0
+    assert res["value"] > 0 and res["unit"] == "images/sec" and res["higher_is_better"] is True
+    assert "cpu_baseline" not in res and "alt_f32x3" not in res and res["roofline"]["achieved"] is None
+    files = {f: np.load(tmp_path / "dump" / f) for f in sorted(os.listdir(tmp_path / "dump"))}
+    assert set(files) == {"loss.npy", "parameters.npy", "gradients.npy", "bn_running_stats.npy"}
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert files["parameters.npy"].shape == files["gradients.npy"].shape and files["gradients.npy"].any()
+    assert round(float(files["loss.npy"][0]), 5) == res["config"]["final_loss"]
+    full = run("--full", "--no-cpu-baseline")
+    assert full["steps"] == 3 and full["roofline"]["achieved"] > 0 and full["roofline"]["launches"] > 0
+    assert full["alt_f32x3"]["value"] > 0 and full["alt_bf16"]["value"] > 0 and "cpu_baseline" not in full
