@@ -214,16 +214,7 @@ const char* d3f_last_error(void) { return g_err; }
 // ---- whole network ------------------------------------------------------------------------
 int d3f_unet_create(const char* encoder_name, int in_channels, int classes, int B, int H, int W,
                     int dtype, d3f_unet_t* out) {
-  D3F_CHECK(out != nullptr && encoder_name != nullptr, "unet_create: null argument");
-  d3f_unet* h = new (std::nothrow) d3f_unet();
-  D3F_CHECK(h != nullptr, "unet_create: out of host memory");
-  const int rc = h->e.build(encoder_name, in_channels, classes, B, H, W, dtype);
-  if (rc != 0) {
-    delete h;
-    return rc;
-  }
-  *out = h;
-  return 0;
+  return d3f_unet_create_nets(encoder_name, in_channels, classes, B, H, W, dtype, 1, 1, out);
 }
 int d3f_unet_create_nets(const char* encoder_name, int in_channels, int classes, int B, int H, int W, int dtype,
                          int nets, int plan_nets, d3f_unet_t* out) {
@@ -236,6 +227,12 @@ int d3f_unet_create_nets(const char* encoder_name, int in_channels, int classes,
     return rc;
   }
   *out = h;
+  return 0;
+}
+// the single-network entry points on a pair handle (d3f_unet_create_nets(..., nets = 2, ...)): refused before anything is
+// enqueued; `instead` says what a pair runs in its place
+static int single_net(d3f_unet_t h, const char* fn, const char* instead) {
+  D3F_CHECK(h->e.nets == 1, "%s: a pair handle %s", fn, instead);
   return 0;
 }
 int d3f_unet_destroy(d3f_unet_t h) {
@@ -317,23 +314,25 @@ double d3f_unet_backward_flops(d3f_unet_t h) { return h ? h->e.bwd_flops : 0.0; 
 
 int d3f_unet_pack_weights(d3f_unet_t h, const float* params, void* workspace, void* stream) {
   D3F_CHECK(h && params && workspace, "pack_weights: null argument");
-  D3F_CHECK(h->e.nets == 1, "pack_weights: a pair handle takes d3f_unet_pair_pack_weights");
+  if (int rc = single_net(h, "pack_weights", "takes d3f_unet_pair_pack_weights")) return rc;
   return h->e.pack_weights(params, workspace, (hipStream_t)stream);
 }
 int d3f_unet_forward(d3f_unet_t h, const float* params, float* bnstats, const float* x, float* out,
                      void* workspace, int training, void* stream) {
   D3F_CHECK(h && params && bnstats && x && out && workspace, "unet_forward: null argument");
-  D3F_CHECK(h->e.nets == 1, "unet_forward: a pair handle takes d3f_unet_pair_forward");
+  if (int rc = single_net(h, "unet_forward", "takes d3f_unet_pair_forward")) return rc;
   return h->e.forward(params, bnstats, x, out, workspace, training, (hipStream_t)stream);
 }
 int d3f_unet_forward_graph(d3f_unet_t h, const float* params, float* bnstats, const float* x, float* out,
                            void* workspace, void* stream) {
   D3F_CHECK(h && params && bnstats && x && out && workspace, "unet_forward_graph: null argument");
+  if (int rc = single_net(h, "unet_forward_graph", "has no eval-mode forward (run each network alone)")) return rc;
   return h->e.forward_graph(params, bnstats, x, out, workspace, (hipStream_t)stream);
 }
 int d3f_unet_predict_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* bgr_in, uint8_t* bgr_out,
                         const float mean[3], const float std[3], void* workspace, int use_graph, void* stream) {
   D3F_CHECK(h && params && bnstats && bgr_in && bgr_out && mean && std && workspace, "predict_u8: null argument");
+  if (int rc = single_net(h, "predict_u8", "has no eval-mode forward (run each network alone)")) return rc;
   return h->e.predict_u8(params, bnstats, bgr_in, bgr_out, mean, std, workspace, use_graph, (hipStream_t)stream);
 }
 
@@ -365,7 +364,7 @@ int d3f_unet_segment_range(d3f_unet_t h, int segment, int64_t* begin, int64_t* e
 int d3f_unet_backward(d3f_unet_t h, const float* params, const float* grad_out, float* grads,
                       void* workspace, int seg_begin, int seg_end, void* stream) {
   D3F_CHECK(h && params && grad_out && grads && workspace, "unet_backward: null argument");
-  D3F_CHECK(h->e.nets == 1, "unet_backward: a pair handle takes d3f_unet_pair_backward");
+  if (int rc = single_net(h, "unet_backward", "takes d3f_unet_pair_backward")) return rc;
   D3F_CHECK(seg_begin >= 0 && seg_end <= h->e.num_segments && seg_begin <= seg_end,
             "unet_backward: segments [%d,%d)", seg_begin, seg_end);
   return h->e.backward(params, grad_out, grads, workspace, seg_begin, seg_end, (hipStream_t)stream);
@@ -373,7 +372,7 @@ int d3f_unet_backward(d3f_unet_t h, const float* params, const float* grad_out, 
 int d3f_unet_backward_nojoin(d3f_unet_t h, const float* params, const float* grad_out, float* grads,
                              void* workspace, int seg_begin, int seg_end, void* stream) {
   D3F_CHECK(h && params && grad_out && grads && workspace, "unet_backward_nojoin: null argument");
-  D3F_CHECK(h->e.nets == 1, "unet_backward_nojoin: a pair handle takes d3f_unet_pair_backward(join = 0)");
+  if (int rc = single_net(h, "unet_backward_nojoin", "takes d3f_unet_pair_backward(join = 0)")) return rc;
   D3F_CHECK(seg_begin >= 0 && seg_end <= h->e.num_segments && seg_begin <= seg_end,
             "unet_backward_nojoin: segments [%d,%d)", seg_begin, seg_end);
   return h->e.backward(params, grad_out, grads, workspace, seg_begin, seg_end, (hipStream_t)stream, 0);
@@ -395,6 +394,8 @@ int d3f_adam_coefficients(float lr, float beta1, float beta2, float eps, int ste
 int d3f_unet_train_step(d3f_unet_t h, const d3f_step_buffers* b, float lam, float input_min, float input_max,
                         void* workspace, int use_graph, void* stream) {
   D3F_CHECK(h && b && workspace, "unet_train_step: null argument");
+  if (int rc = single_net(h, "unet_train_step", "has no captured step (d3f_unet_pair_forward / _backward, then per network)"))
+    return rc;
   D3F_CHECK(b->params && b->bnstats && b->grads && b->exp_avg && b->exp_avg_sq && b->image && b->noise && b->y_uniform &&
                 b->noisy && b->pred && b->grad_pred && b->loss_out && b->loss_workspace && b->adam_coef,
             "unet_train_step: null buffer");
@@ -413,6 +414,9 @@ int d3f_unet_train_step(d3f_unet_t h, const d3f_step_buffers* b, float lam, floa
 }
 int d3f_unet_set_bn_sync(d3f_unet_t h, d3f_allreduce_fn fn, void* ctx, int world_size) {
   D3F_CHECK(h && (fn == nullptr || world_size >= 1), "unet_set_bn_sync: arguments");
+  if (fn != nullptr) {  // (removing a callback is always allowed)
+    if (int rc = single_net(h, "unet_set_bn_sync", "keeps per-GPU BatchNorm statistics")) return rc;
+  }
   h->e.set_bn_sync(fn, ctx, world_size);
   return 0;
 }

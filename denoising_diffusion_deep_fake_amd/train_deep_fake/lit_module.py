@@ -239,9 +239,7 @@ class LitModule(LightningModule):
             with torch.no_grad():
                 noisy.append(self.blend_random_amount_of_noise_with_each_sample(x))
             reals.append(x)
-        if self._pair is None:
-            self.__dict__["_pair"] = UnetPair(self.model_a, self.model_b)
-        predictions = self._pair(noisy[0], noisy[1])
+        predictions = self._unet_pair()(noisy[0], noisy[1])
         losses = []
         for name, prediction, real in zip("ab", predictions, reals):
             loss = self.criterion(prediction, real)
@@ -249,6 +247,14 @@ class LitModule(LightningModule):
             losses.append(loss)
         self.log("epoch", float(self.current_epoch))
         return tuple(losses)
+
+    def _unet_pair(self):
+        """UnetPair(model_a, model_b), made on first use and made anew once either module was replaced (loading into a new
+        module, say): a pair bound to the old modules would go on stepping them"""
+        pair = self._pair
+        if pair is None or pair.nets[0] is not self.model_a or pair.nets[1] is not self.model_b:
+            pair = self.__dict__["_pair"] = UnetPair(self.model_a, self.model_b)
+        return pair
 
     def training_step_for_one_model(self, name, real, real_model, fake_model):
         p = self.hparams

@@ -96,14 +96,12 @@ _ENCODERS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}
 class _Engine:
     """one libd3f_hip whole-network plan + its workspace, for a fixed (B, H, W, dtype)."""
 
-    def __init__(self, encoder_name, in_channels, classes, B, H, W, dtype, device, nets=1, plan_nets=1):
+    def __init__(self, encoder_name, in_channels, classes, B, H, W, dtype, device, nets, plan_nets):
+        # nets = 2: a pair, B images PER network; plan_nets = 2 with nets = 1: one network planned like the pair
         L = _lib.lib()
         self.h = C.c_void_p()
-        if nets == 1 and plan_nets == 1:
-            check(L.d3f_unet_create(encoder_name.encode(), in_channels, classes, B, H, W, dtype, C.byref(self.h)))
-        else:  # a pair (nets = 2: B images PER network), or one network planned like the pair (plan_nets = 2)
-            check(L.d3f_unet_create_nets(encoder_name.encode(), in_channels, classes, B, H, W, dtype, nets, plan_nets,
-                                         C.byref(self.h)))
+        check(L.d3f_unet_create_nets(encoder_name.encode(), in_channels, classes, B, H, W, dtype, nets, plan_nets,
+                                     C.byref(self.h)))
         self.nets = nets
         self.net_stride = L.d3f_unet_net_workspace_stride(self.h)
         self.shape = (B, H, W)
@@ -154,6 +152,14 @@ class _Engine:
                 return -3
         self._bn_cb = _lib.ALLREDUCE_FN(allreduce)  # kept alive with the engine
         check(L.d3f_unet_set_bn_sync(self.h, C.cast(self._bn_cb, C.c_void_p), None, int(world_size)))
+
+    def flat_range(self, s0, s1, what):
+        """[lo, hi): the flat gradient range that backward segments [s0, s1) write; refused unless it is one range"""
+        segs = self.seg_ranges[s0:s1]
+        lo, hi = min(b for b, _ in segs), max(e for _, e in segs)
+        if sum(e - b for b, e in segs) != hi - lo:
+            raise D3FError(f"{what}: segments {s0}..{s1 - 1} are not one contiguous flat range")
+        return lo, hi
 
     def side_stream(self, device):
         """the engine's weight-gradient stream as a torch stream (None when the engine runs everything on the caller's
@@ -210,37 +216,191 @@ class _Lease:
     __del__ = release
 
 
-class _UnetFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, module, engine, anchor):
-        # `anchor`: ONE parameter that requires grad -- enough for autograd to record the node and call backward, which
-        # writes every parameter's .grad itself; handing all 143 parameters to apply() cost ~0.15 ms of host time per step
-        ctx.module, ctx.engine = module, engine
-        out = module._run_forward(engine, x, training=True)
-        ctx.serial = engine.serial
-        ctx.lease = _Lease(engine)
-        return out
+def _ptrs(ts):
+    """a buffer argument of the C entry points: one network's pointer (d3f_unet_*) or the two networks' `T* const x[2]`
+    array (d3f_unet_pair_*)"""
+    return ptr(ts[0]) if len(ts) == 1 else ptr2(*ts)
+
+
+class _NetsFunction(torch.autograd.Function):
+    """the autograd node of one recorded forward pass of `owner` (a Unet, or a UnetPair: one output per network)"""
 
     @staticmethod
-    def backward(ctx, grad_out):
+    def forward(ctx, owner, engine, xs, *anchors):
+        # `anchors`: ONE parameter per network that requires grad -- enough for autograd to record the node and call
+        # backward, which writes every parameter's .grad itself; handing all 143 parameters to apply() cost ~0.15 ms of
+        # host time per step
+        ctx.owner, ctx.engine = owner, engine
+        outs = owner._run_forward(engine, xs, training=True)
+        ctx.serial = engine.serial
+        ctx.lease = _Lease(engine)
+        return outs
+
+    @staticmethod
+    def backward(ctx, *grad_outs):
         eng = ctx.engine
         if ctx.lease.engine is None:
-            raise D3FError("backward through the d3f Unet a second time: the activations were released by the first "
-                           "backward (retain_graph is not supported by the HIP path)")
+            raise D3FError(f"backward through the d3f {type(ctx.owner).__name__} a second time: the activations were "
+                           "released by the first backward (retain_graph is not supported by the HIP path)")
         if ctx.serial != eng.serial:
-            # cannot happen through Unet.forward (a leased workspace is never handed out again); guards direct
+            # cannot happen through forward (a leased workspace is never handed out again); guards direct
             # _run_forward callers: silently using another forward's activations would give wrong gradients
             raise D3FError("the workspace of this forward pass was overwritten by a later forward before backward ran")
-        ctx.module._run_backward(eng, grad_out)
+        # (autograd materialises the gradient of an output the loss does not depend on as zeros: that network's
+        # parameter gradients then come out as exact zeros)
+        ctx.owner._run_backward(eng, grad_outs)
         ctx.lease.release()
-        return (None, None, None, None)  # every .grad was set by _run_backward (views of the flat gradient buffer)
+        return (None,) * len(ctx.needs_input_grad)  # every .grad was set by _run_backward (views of the flat gradient buffer)
+
+
+class _NetsRuntime:
+    """What runs a tuple of networks of one architecture as ONE set of launches -- `_nets`: (self,) for a Unet, (net_a,
+    net_b) for a UnetPair: a pool of plans + workspaces per shape with their leases, the packed-weight stamp, the forward
+    and backward enqueue with the data-parallel gradient buckets, and activation export.  The owner's `_rt` dict holds
+    "engines" and "last_engine".  The number of networks only picks the C entry point: d3f_unet_* with one pointer per
+    buffer, or d3f_unet_pair_* with two."""
+
+    MAX_LIVE_GRAPHS = 4  # workspaces (2 GB each at bs 16, 256x256) per shape that may hold un-backwarded graphs
+
+    def _engine(self, B, H, W, device):
+        """a plan + workspace for this shape whose activations no live autograd graph still needs.  smp.Unet allows
+        `crit(net(x1)) + crit(net(x2))` and a no_grad forward between forward and backward: each recorded forward
+        leases its workspace until its backward has run, and a further forward of the same shape gets another one."""
+        nets = self._nets
+        a = nets[0]
+        plan_nets = max(len(nets), getattr(a, "plan_nets", 1))  # (a pair plans for two networks whatever its nets say)
+        key = (B, H, W, a.compute_dtype, device.index, plan_nets)
+        pool = self._rt["engines"].setdefault(key, [])
+        for eng in pool:
+            if not eng.in_use:
+                return eng
+        if len(pool) >= self.MAX_LIVE_GRAPHS:
+            raise D3FError(f"{len(pool)} forward passes of shape {(B, H, W)} are waiting for their backward pass; "
+                           f"run inference-only forwards under torch.no_grad()")
+        eng = _Engine(a.encoder_name, a.in_channels, a.classes, B, H, W, a.compute_dtype, device, len(nets), plan_nets)
+        if a._rt.get("bn_sync"):  # (a UnetPair refuses synchronised statistics before it gets here)
+            eng.set_bn_sync(*a._rt["bn_sync"])
+        pool.append(eng)
+        return eng
+
+    def _pack_if_needed(self, eng):
+        # `p.data = view` keeps every parameter's OWN version counter, so in-place updates by
+        # torch optimizers / load_state_dict show up on the parameters, not on the flat buffer
+        nets = self._nets
+        ver = tuple(n._weights_version() for n in nets)
+        if eng.packed_version != ver:
+            L = _lib.lib()
+            args = (eng.h, _ptrs([n._rt["flat"] for n in nets]), ptr(eng.workspace), stream_ptr())
+            check(L.d3f_unet_pack_weights(*args) if len(nets) == 1 else L.d3f_unet_pair_pack_weights(*args))
+            eng.packed_version = ver
+
+    def _forward_nets(self, xs):
+        """the forward pass of the networks on xs (one input each, checked by the caller), recorded for autograd when a
+        gradient is wanted"""
+        nets = self._nets
+        for net in nets:
+            net._ensure_flat(xs[0].device)
+        need = [torch.is_grad_enabled() and any(p.requires_grad for p in net._param_list) for net in nets]
+        if any(need):
+            if not all(need):
+                raise D3FError("UnetPair: both networks (or neither) must require gradients")
+            if not nets[0].training:
+                raise D3FError("backward through an eval-mode Unet is not supported (BatchNorm is folded)")
+            if any(x.requires_grad for x in xs):
+                raise D3FError("gradient w.r.t. the network input is not computed by the HIP path")
+        xs = tuple(x.detach().contiguous().float() for x in xs)
+        eng = self._engine(xs[0].shape[0], xs[0].shape[2], xs[0].shape[3], xs[0].device)
+        if not any(need):
+            return self._run_forward(eng, xs, training=nets[0].training)
+        return _NetsFunction.apply(self, eng, xs, *[next(p for p in net._param_list if p.requires_grad) for net in nets])
+
+    def _run_forward(self, eng, xs, training):
+        nets = self._nets
+        self._pack_if_needed(eng)
+        x = xs[0]
+        outs = tuple(torch.empty((x.shape[0], nets[0].classes, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device)
+                     for _ in nets)
+        eng.serial += 1
+        self._rt["last_engine"] = eng
+        L = _lib.lib()
+        args = (eng.h, _ptrs([n._rt["flat"] for n in nets]), _ptrs([n._rt["flat_bn"] for n in nets]), _ptrs(xs),
+                _ptrs(outs), ptr(eng.workspace))
+        if len(nets) == 1:
+            check(L.d3f_unet_forward(*args, 1 if training else 0, stream_ptr()))
+        else:  # train mode only (UnetPair checks it)
+            check(L.d3f_unet_pair_forward(*args, stream_ptr()))
+        if training:
+            for net in nets:
+                net._rt["flat_nbt"] += 1
+        return outs
+
+    def _backward_launch(self, eng, grad_outs, targets, s0, s1, join):
+        """backward segments [s0, s1); join = 0: their gradients are final on the engine's side stream, not on this one"""
+        nets = self._nets
+        L = _lib.lib()
+        args = (eng.h, _ptrs([n._rt["flat"] for n in nets]), _ptrs(grad_outs), _ptrs(targets), ptr(eng.workspace), s0, s1)
+        if len(nets) == 1:
+            check((L.d3f_unet_backward if join else L.d3f_unet_backward_nojoin)(*args, stream_ptr()))
+        else:
+            check(L.d3f_unet_pair_backward(*args, join, stream_ptr()))
+
+    def _run_backward(self, eng, grad_outs):
+        nets = self._nets
+        grad_outs = [g.contiguous().float() for g in grad_outs]
+        targets, directs = zip(*[net._backward_target() for net in nets])
+        self._enqueue_backward(eng, grad_outs, targets, directs)
+        for net, target, direct in zip(nets, targets, directs):
+            net._publish_grads(target, direct)
+
+    def _enqueue_backward(self, eng, grad_outs, targets, directs):
+        nets = self._nets
+        syncs = [net._rt["grad_sync"] for net in nets]
+        if all(sync is None for sync in syncs):
+            self._backward_launch(eng, grad_outs, targets, 0, eng.nseg, join=1)
+            return
+        # Data parallel: bucket k's collectives (one per network, each module's own reducer) must wait for bucket k's
+        # gradients -- and nothing else may wait for anything.  The gradients become final on the engine's SIDE stream
+        # (weight gradients run there; it also waits for this stream at the end of each bucket), so the hooks are called
+        # with the side stream current: torch.distributed orders a collective behind the current stream at the time of
+        # the call.  This stream (the dependent BatchNorm-backward -> data-gradient chain, the critical path) goes
+        # straight on with bucket k+1; one join after the last bucket orders the optimiser behind the weight gradients.
+        if any(sync is None for sync in syncs):
+            raise D3FError("UnetPair: attach the data-parallel reducer to both networks or to neither")
+        buckets = nets[0]._rt.get("grad_buckets")
+        if any(net._rt.get("grad_buckets") != buckets for net in nets):
+            raise D3FError("UnetPair: the two networks' gradient bucket settings differ")
+        side = eng.side_stream(grad_outs[0].device)
+        for k, (s0, s1) in enumerate(nets[0]._bucket_groups(buckets, eng.nseg)):
+            self._backward_launch(eng, grad_outs, targets, s0, s1, join=0)
+            lo, hi = eng.flat_range(s0, s1, f"gradient bucket {k}")
+            with torch.cuda.stream(side):  # (a no-op for None, D3F_SERIAL_BACKWARD: everything is on this stream)
+                for sync, target in zip(syncs, targets):
+                    sync(k, target[lo:hi])
+        check(_lib.lib().d3f_unet_backward_join(eng.h, stream_ptr()))
+
+    def export_activation_shape(self, name):
+        eng = self._rt.get("last_engine")
+        if eng is None:
+            raise D3FError("export_activation_shape() before any forward pass")
+        dims = (C.c_int32 * 3)()
+        check(_lib.lib().d3f_unet_export_shape(eng.h, name.encode(), dims))
+        return (eng.shape[0], dims[0], dims[1], dims[2])
+
+    def _export(self, net_index, name):
+        eng = self._rt.get("last_engine")
+        if eng is None:
+            raise D3FError("export_activation() before any forward pass")
+        out = torch.empty(self.export_activation_shape(name), dtype=torch.float32, device=eng.workspace.device)
+        ws = C.c_void_p(eng.workspace.data_ptr() + int(net_index) * eng.net_stride)  # network 1: the pair's second copy
+        check(_lib.lib().d3f_unet_export(eng.h, name.encode(), ws, ptr(out), stream_ptr()))
+        return out
 
 
 def _views_unverified(module, incompatible_keys):
     module._rt["verified"] = False
 
 
-class Unet(nn.Module):
+class Unet(nn.Module, _NetsRuntime):
     def __init__(self, encoder_name="resnet34", encoder_weights=None, in_channels=3, classes=3,
                  activation=None, compute_dtype="f32"):
         super().__init__()
@@ -473,35 +633,7 @@ class Unet(nn.Module):
         self._rt["early_update"] = fn
 
     # -- engine -------------------------------------------------------------------------------------
-    MAX_LIVE_GRAPHS = 4  # workspaces (2 GB each at bs 16, 256x256) per shape that may hold un-backwarded graphs
-
-    def _engine(self, B, H, W, device):
-        """a plan + workspace for this shape whose activations no live autograd graph still needs.  smp.Unet allows
-        `crit(net(x1)) + crit(net(x2))` and a no_grad forward between forward and backward: each recorded forward
-        leases its workspace until its backward has run, and a further forward of the same shape gets another one."""
-        key = (B, H, W, self.compute_dtype, device.index, getattr(self, "plan_nets", 1))
-        pool = self._rt["engines"].setdefault(key, [])
-        for eng in pool:
-            if not eng.in_use:
-                return eng
-        if len(pool) >= self.MAX_LIVE_GRAPHS:
-            raise D3FError(f"{len(pool)} forward passes of shape {(B, H, W)} are waiting for their backward pass; "
-                           f"run inference-only forwards under torch.no_grad()")
-        eng = _Engine(self.encoder_name, self.in_channels, self.classes, B, H, W, self.compute_dtype, device,
-                      plan_nets=getattr(self, "plan_nets", 1))
-        if self._rt.get("bn_sync"):
-            eng.set_bn_sync(*self._rt["bn_sync"])
-        pool.append(eng)
-        return eng
-
-    def _pack_if_needed(self, eng):
-        rt = self._rt
-        # `p.data = view` keeps every parameter's OWN version counter, so in-place updates by
-        # torch optimizers / load_state_dict show up on the parameters, not on the flat buffer
-        ver = self._weights_version()
-        if eng.packed_version != ver:
-            check(_lib.lib().d3f_unet_pack_weights(eng.h, ptr(rt["flat"]), ptr(eng.workspace), stream_ptr()))
-            eng.packed_version = ver
+    _nets = property(lambda self: (self,))
 
     def _weights_version(self):
         """stamp of the current parameter values: torch's version counters (in-place torch updates, load_state_dict) and the
@@ -509,66 +641,23 @@ class Unet(nn.Module):
         rt = self._rt
         return (sum(p._version for p in rt["params"]) + rt["flat"]._version, rt.get("gen", 0))
 
-    def _run_forward(self, eng, x, training):
-        rt = self._rt
-        self._pack_if_needed(eng)
-        out = torch.empty((x.shape[0], self.classes, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device)
-        eng.serial += 1
-        rt["last_engine"] = eng
-        check(_lib.lib().d3f_unet_forward(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), ptr(out),
-                                          ptr(eng.workspace), 1 if training else 0, stream_ptr()))
-        if training:
-            rt["flat_nbt"] += 1
-        return out
-
-    def _run_backward(self, eng, grad_out):
-        rt = self._rt
-        L = _lib.lib()
-        grad_out = grad_out.contiguous().float()
-        target, direct = self._backward_target()
-        sync = rt["grad_sync"]
-        early = rt.get("early_update") if (sync is None and direct and eng.nseg > 1) else None
-        side = eng.side_stream(grad_out.device) if early is not None else None
-        if early is not None and side is not None:
-            # every bucket is enqueued without a join; the leading buckets' gradients are final on the side stream at the
-            # event, and the hook's update runs on THIS stream behind the chain's last kernel -- next to the last bucket's
-            # weight gradients, which are still running on the side stream -- before the join that step() would wait for
-            last = eng.nseg - 1
-            lo, hi = min(b for b, _ in eng.seg_ranges[:last]), max(e for _, e in eng.seg_ranges[:last])
-            if sum(e - b for b, e in eng.seg_ranges[:last]) != hi - lo:
-                raise D3FError("early update: the leading gradient buckets are not one contiguous range")
-            check(L.d3f_unet_backward_nojoin(eng.h, ptr(rt["flat"]), ptr(grad_out), ptr(target), ptr(eng.workspace),
-                                             0, last, stream_ptr()))
-            final = side.record_event()
-            check(L.d3f_unet_backward_nojoin(eng.h, ptr(rt["flat"]), ptr(grad_out), ptr(target), ptr(eng.workspace),
-                                             last, eng.nseg, stream_ptr()))
-            torch.cuda.current_stream().wait_event(final)
-            early(target, lo, hi)
-            check(L.d3f_unet_backward_join(eng.h, stream_ptr()))
-        elif sync is None:
-            check(L.d3f_unet_backward(eng.h, ptr(rt["flat"]), ptr(grad_out), ptr(target), ptr(eng.workspace),
-                                      0, eng.nseg, stream_ptr()))
-        else:
-            # Data parallel: bucket k's collective must wait for bucket k's gradients -- and nothing else may wait for
-            # anything.  The gradients become final on the engine's SIDE stream (weight gradients run there; it also
-            # waits for this stream at the end of each bucket), so the hook is called with the side stream current:
-            # torch.distributed orders a collective behind the current stream at the time of the call.  This stream
-            # (the dependent BatchNorm-backward -> data-gradient chain, the critical path) goes straight on with bucket
-            # k+1; one join after the last bucket orders the optimiser behind the weight gradients.
-            side = eng.side_stream(grad_out.device)
-            for k, (s0, s1) in enumerate(self._bucket_groups(rt.get("grad_buckets"), eng.nseg)):
-                check(L.d3f_unet_backward_nojoin(eng.h, ptr(rt["flat"]), ptr(grad_out), ptr(target),
-                                                 ptr(eng.workspace), s0, s1, stream_ptr()))
-                b, e = min(r[0] for r in eng.seg_ranges[s0:s1]), max(r[1] for r in eng.seg_ranges[s0:s1])
-                if sum(r[1] - r[0] for r in eng.seg_ranges[s0:s1]) != e - b:
-                    raise D3FError(f"gradient bucket {k}: segments {s0}..{s1 - 1} are not one contiguous flat range")
-                if side is None:  # D3F_SERIAL_BACKWARD: everything is on this stream
-                    sync(k, target[b:e])
-                else:
-                    with torch.cuda.stream(side):
-                        sync(k, target[b:e])
-            check(L.d3f_unet_backward_join(eng.h, stream_ptr()))
-        self._publish_grads(target, direct)
+    def _enqueue_backward(self, eng, grad_outs, targets, directs):
+        early = self._rt.get("early_update")
+        side = eng.side_stream(grad_outs[0].device) if (early is not None and self._rt["grad_sync"] is None and directs[0]
+                                                       and eng.nseg > 1) else None
+        if side is None:
+            return super()._enqueue_backward(eng, grad_outs, targets, directs)
+        # every bucket is enqueued without a join; the leading buckets' gradients are final on the side stream at the
+        # event, and the hook's update runs on THIS stream behind the chain's last kernel -- next to the last bucket's
+        # weight gradients, which are still running on the side stream -- before the join that step() would wait for
+        last = eng.nseg - 1
+        lo, hi = eng.flat_range(0, last, "early update")
+        self._backward_launch(eng, grad_outs, targets, 0, last, join=0)
+        final = side.record_event()
+        self._backward_launch(eng, grad_outs, targets, last, eng.nseg, join=0)
+        torch.cuda.current_stream().wait_event(final)
+        early(targets[0], lo, hi)
+        check(_lib.lib().d3f_unet_backward_join(eng.h, stream_ptr()))
 
     def _backward_target(self):
         """(flat buffer the engine writes this pass's gradients into, direct): direct = every .grad is None, the gradients
@@ -620,18 +709,7 @@ class Unet(nn.Module):
         if x.device.type != "cuda":
             raise D3FError("d3f Unet runs on an MI355X (HIP) device only; there is no CPU fallback "
                            "(input tensor is on %s)" % x.device)
-        self._ensure_flat(x.device)
-        xin = x.detach().contiguous().float()
-        eng = self._engine(x.shape[0], x.shape[2], x.shape[3], x.device)
-        params = self._param_list
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        if need_grad:
-            if not self.training:
-                raise D3FError("backward through an eval-mode Unet is not supported (BatchNorm is folded)")
-            if x.requires_grad:
-                raise D3FError("gradient w.r.t. the network input is not computed by the HIP path")
-            return _UnetFunction.apply(xin, self, eng, next(p for p in params if p.requires_grad))
-        return self._run_forward(eng, xin, training=self.training)
+        return self._forward_nets((x,))[0]
 
     @torch.no_grad()
     def forward_graph(self, x, out=None):
@@ -703,20 +781,7 @@ class Unet(nn.Module):
         """debugging / parity tests: an internal tensor of the MOST RECENT forward (+ backward) as NCHW f32 --
         "<conv name>:y" raw conv output, ":a" post BatchNorm(+residual)+ReLU activation, ":da" gradient w.r.t. that
         activation (d3f_unet_export).  Channels beyond the real count (vector padding) are cut off by the caller."""
-        eng = self._rt.get("last_engine")
-        if eng is None:
-            raise D3FError("export_activation() before any forward pass")
-        out = torch.empty(self.export_activation_shape(name), dtype=torch.float32, device=eng.workspace.device)
-        check(_lib.lib().d3f_unet_export(eng.h, name.encode(), ptr(eng.workspace), ptr(out), stream_ptr()))
-        return out
-
-    def export_activation_shape(self, name):
-        eng = self._rt.get("last_engine")
-        if eng is None:
-            raise D3FError("export_activation_shape() before any forward pass")
-        dims = (C.c_int32 * 3)()
-        check(_lib.lib().d3f_unet_export_shape(eng.h, name.encode(), dims))
-        return (eng.shape[0], dims[0], dims[1], dims[2])
+        return self._export(0, name)
 
     # flops of the conv contractions of one call (2*MAC), for roofline reporting
     def conv_flops(self, B, H, W, device=None):
@@ -730,31 +795,7 @@ class Unet(nn.Module):
 # ---------------------------------------------------------------------------------------------
 # two networks, one set of launches
 # ---------------------------------------------------------------------------------------------
-class _UnetPairFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, xa, xb, pair, engine, anchor_a, anchor_b):
-        ctx.pair, ctx.engine = pair, engine
-        out = pair._run_forward(engine, xa, xb)
-        ctx.serial = engine.serial
-        ctx.lease = _Lease(engine)
-        return out
-
-    @staticmethod
-    def backward(ctx, ga, gb):
-        eng = ctx.engine
-        if ctx.lease.engine is None:
-            raise D3FError("backward through the d3f UnetPair a second time: the activations were released by the first "
-                           "backward (retain_graph is not supported by the HIP path)")
-        if ctx.serial != eng.serial:
-            raise D3FError("the workspace of this pair forward was overwritten by a later forward before backward ran")
-        # (autograd materialises the gradient of an output the loss does not depend on as zeros: that network's
-        # parameter gradients then come out as exact zeros)
-        ctx.pair._run_backward(eng, ga, gb)
-        ctx.lease.release()
-        return (None,) * 6
-
-
-class UnetPair:
+class UnetPair(_NetsRuntime):
     """Two `Unet`s of identical architecture stepped as ONE set of kernel launches.
 
     train_deep_fake's `mode: "denoise"` trains model_a on domain a and model_b on domain b with nothing shared
@@ -773,8 +814,11 @@ class UnetPair:
             if getattr(net_a, attr) != getattr(net_b, attr):
                 raise ValueError(f"UnetPair: the two networks differ in {attr}")
         self.nets = (net_a, net_b)
-        self._engines = {}
-        self.last_engine = None
+        self._rt = {"engines": {}}
+
+    _nets = property(lambda self: self.nets)
+    _engines = property(lambda self: self._rt["engines"])  # plans + workspaces per shape (what tests and tools read)
+    last_engine = property(lambda self: self._rt.get("last_engine"))  # the plan of the most recent pair pass
 
     # plans and workspaces are runtime state (C handles): a copy / pickle of whatever holds the pair starts without them
     def __deepcopy__(self, memo):
@@ -786,73 +830,7 @@ class UnetPair:
 
     def __setstate__(self, st):
         self.nets = st["nets"]
-        self._engines = {}
-        self.last_engine = None
-
-    def _engine(self, B, H, W, device):
-        a = self.nets[0]
-        key = (B, H, W, a.compute_dtype, device.index)
-        pool = self._engines.setdefault(key, [])
-        for eng in pool:
-            if not eng.in_use:
-                return eng
-        if len(pool) >= Unet.MAX_LIVE_GRAPHS:
-            raise D3FError(f"{len(pool)} pair forward passes of shape {(B, H, W)} are waiting for their backward pass")
-        eng = _Engine(a.encoder_name, a.in_channels, a.classes, B, H, W, a.compute_dtype, device, nets=2, plan_nets=2)
-        pool.append(eng)
-        return eng
-
-    def _pack_if_needed(self, eng):
-        ver = (self.nets[0]._weights_version(), self.nets[1]._weights_version())
-        if eng.packed_version != ver:
-            a, b = self.nets
-            check(_lib.lib().d3f_unet_pair_pack_weights(eng.h, ptr2(a._rt["flat"], b._rt["flat"]), ptr(eng.workspace),
-                                                        stream_ptr()))
-            eng.packed_version = ver
-
-    def _run_forward(self, eng, xa, xb):
-        a, b = self.nets
-        self._pack_if_needed(eng)
-        shape = (xa.shape[0], a.classes, xa.shape[2], xa.shape[3])
-        oa = torch.empty(shape, dtype=torch.float32, device=xa.device)
-        ob = torch.empty(shape, dtype=torch.float32, device=xa.device)
-        eng.serial += 1
-        self.last_engine = eng
-        check(_lib.lib().d3f_unet_pair_forward(eng.h, ptr2(a._rt["flat"], b._rt["flat"]),
-                                               ptr2(a._rt["flat_bn"], b._rt["flat_bn"]), ptr2(xa, xb), ptr2(oa, ob),
-                                               ptr(eng.workspace), stream_ptr()))
-        for net in self.nets:
-            net._rt["flat_nbt"] += 1
-        return oa, ob
-
-    def _run_backward(self, eng, ga, gb):
-        a, b = self.nets
-        L = _lib.lib()
-        ga, gb = ga.contiguous().float(), gb.contiguous().float()
-        (ta, da), (tb, db) = a._backward_target(), b._backward_target()
-        params, douts, grads = ptr2(a._rt["flat"], b._rt["flat"]), ptr2(ga, gb), ptr2(ta, tb)
-        syncs = (a._rt["grad_sync"], b._rt["grad_sync"])
-        if syncs[0] is None and syncs[1] is None:
-            check(L.d3f_unet_pair_backward(eng.h, params, douts, grads, ptr(eng.workspace), 0, eng.nseg, 1, stream_ptr()))
-        else:
-            # data parallel (as Unet._run_backward): bucket k's collectives -- one per network, each module's own reducer
-            # -- wait for bucket k's gradients on the engine's side stream, the chain goes straight on with bucket k + 1
-            if syncs[0] is None or syncs[1] is None:
-                raise D3FError("UnetPair: attach the data-parallel reducer to both networks or to neither")
-            if a._rt.get("grad_buckets") != b._rt.get("grad_buckets"):
-                raise D3FError("UnetPair: the two networks' gradient bucket settings differ")
-            side = eng.side_stream(ga.device)
-            for k, (s0, s1) in enumerate(Unet._bucket_groups(a._rt.get("grad_buckets"), eng.nseg)):
-                check(L.d3f_unet_pair_backward(eng.h, params, douts, grads, ptr(eng.workspace), s0, s1, 0, stream_ptr()))
-                lo, hi = min(r[0] for r in eng.seg_ranges[s0:s1]), max(r[1] for r in eng.seg_ranges[s0:s1])
-                if sum(r[1] - r[0] for r in eng.seg_ranges[s0:s1]) != hi - lo:
-                    raise D3FError(f"gradient bucket {k}: segments {s0}..{s1 - 1} are not one contiguous flat range")
-                with (torch.cuda.stream(side) if side is not None else _nullcontext()):
-                    syncs[0](k, ta[lo:hi])
-                    syncs[1](k, tb[lo:hi])
-            check(L.d3f_unet_backward_join(eng.h, stream_ptr()))
-        a._publish_grads(ta, da)
-        b._publish_grads(tb, db)
+        self._rt = {"engines": {}}
 
     def usable(self, xa, xb):
         """can this batch go through the pair?  Same shape, both networks training on one HIP device, and neither with
@@ -874,36 +852,8 @@ class UnetPair:
                            "goes through each Unet")
         if a._rt.get("bn_sync") or b._rt.get("bn_sync"):
             raise D3FError("UnetPair keeps per-GPU BatchNorm statistics; switch set_sync_batchnorm off or step the networks alone")
-        for net in self.nets:
-            net._ensure_flat(xa.device)
-        xa, xb = xa.detach().contiguous().float(), xb.detach().contiguous().float()
-        eng = self._engine(xa.shape[0], xa.shape[2], xa.shape[3], xa.device)
-        need = [any(p.requires_grad for p in net._param_list) for net in self.nets]
-        if torch.is_grad_enabled() and any(need):
-            if not all(need):
-                raise D3FError("UnetPair: both networks (or neither) must require gradients")
-            if xa.requires_grad or xb.requires_grad:
-                raise D3FError("gradient w.r.t. the network input is not computed by the HIP path")
-            anchors = [next(p for p in net._param_list if p.requires_grad) for net in self.nets]
-            return _UnetPairFunction.apply(xa, xb, self, eng, anchors[0], anchors[1])
-        return self._run_forward(eng, xa, xb)
+        return self._forward_nets((xa, xb))
 
     def export_activation(self, net_index, name):
         """`Unet.export_activation` for network 0 / 1 of the most recent pair pass"""
-        eng = self.last_engine
-        if eng is None:
-            raise D3FError("export_activation() before any pair forward pass")
-        dims = (C.c_int32 * 3)()
-        check(_lib.lib().d3f_unet_export_shape(eng.h, name.encode(), dims))
-        out = torch.empty((eng.shape[0], dims[0], dims[1], dims[2]), dtype=torch.float32, device=eng.workspace.device)
-        ws = C.c_void_p(eng.workspace.data_ptr() + int(net_index) * eng.net_stride)
-        check(_lib.lib().d3f_unet_export(eng.h, name.encode(), ws, ptr(out), stream_ptr()))
-        return out
-
-
-class _nullcontext:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
+        return self._export(net_index, name)

@@ -85,9 +85,12 @@ int d3f_unet_destroy(d3f_unet_t h);
  * Workspace of a pair: ONE buffer of d3f_unet_workspace_bytes(h) bytes = two copies of the single-network layout,
  *           d3f_unet_net_workspace_stride(h) bytes apart (d3f_unet_export on network 1: pass workspace + stride).
  * The pair entry points take the two networks' buffers as arrays of two pointers (any two allocations); train-mode
- *           forward only, per-GPU BatchNorm statistics only (d3f_unet_set_bn_sync is refused).  Packing, forward and
- *           backward of a pair handle go through these three calls; everything per network (noise blend, loss, Adam,
- *           EMA) stays the single-network entry points, called once per network.
+ *           forward only, per-GPU BatchNorm statistics only.  Packing, forward and backward of a pair handle go through
+ *           these three calls; everything per network (noise blend, loss, Adam, EMA) stays the single-network entry
+ *           points, called once per network.  On a pair handle d3f_unet_pack_weights, _forward, _forward_graph,
+ *           _predict_u8, _backward, _backward_nojoin, _train_step and d3f_unet_set_bn_sync with a callback (fn != NULL)
+ *           return an error before anything is enqueued; the queries, d3f_unet_set_bn_sync(h, NULL, ...), the side
+ *           stream, d3f_unet_backward_join and d3f_unet_export / _export_shape take either kind of handle.
  * ------------------------------------------------------------------------------------- */
 int d3f_unet_create_nets(const char* encoder_name, int in_channels, int classes, int B, int H, int W, int dtype,
                          int nets, int plan_nets, d3f_unet_t* out);

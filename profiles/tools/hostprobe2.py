@@ -54,9 +54,9 @@ for i in range(N):
     noisy = timed("py: noise draws + blend", lambda: lit.blend_random_amount_of_noise_with_each_sample(x))
     eng = net._engine(BATCH, SIZE, SIZE, dev)
     timed("py: weight-version check + pack call", lambda: net._pack_if_needed(eng))
-    pred = timed("C: d3f_unet_forward (one call)", lambda: net._run_forward(eng, noisy, True))
+    pred = timed("C: d3f_unet_forward (one call)", lambda: net._run_forward(eng, (noisy,), True)[0])
     lossv, gout = timed("py+C: loss op", lambda: ops.mse_ssim_loss(pred, x))
-    timed("C: d3f_unet_backward (one call) + .grad views", lambda: net._run_backward(eng, gout))
+    timed("C: d3f_unet_backward (one call) + .grad views", lambda: net._run_backward(eng, (gout,)))
     timed("py+C: optimizer step", lambda: opt.step())
     timed("py: whole training_step + backward + step, for comparison", lambda: full_step(i))
 print(f"[{DTYPE} {SIZE}x{SIZE} bs{BATCH}] host ms per step, GPU idle at the start of each phase:")

@@ -364,6 +364,23 @@ def test_unet_pair_host_protocol():
     assert a.set_plan_nets(2) is a and a.plan_nets == 2 and copy.deepcopy(a).plan_nets == 2
 
 
+def test_trainer_pair_follows_replaced_models():
+    """train_deep_fake's fused route steps the UnetPair its LitModule keeps: the same pair while model_a / model_b stay,
+    a new one bound to the new modules once either is replaced (a pair of the old modules would go on stepping them)"""
+    from denoising_diffusion_deep_fake_amd.train_deep_fake.lit_module import LitModule
+    lit = LitModule(mode="denoise", encoder_name="resnet18", batch_size=2, learning_rate=0.01, adam_b1=0.5, adam_b2=0.999,
+                    cosine_scheduler_max_epoch=1, noise_exponential_sampling_lambda=3, mean_a=[0.5] * 3, std_a=[0.5] * 3,
+                    mean_b=[0.5] * 3, std_b=[0.5] * 3, synthetic=True, image_size=64, augment=False)
+    pair = lit._unet_pair()
+    assert pair.nets == (lit.model_a, lit.model_b) and lit._unet_pair() is pair and lit._pair is pair
+    lit.model_a = lit.create_model_instance()
+    new = lit._unet_pair()
+    assert new is not pair and new.nets[0] is lit.model_a and new.nets[1] is lit.model_b and lit._pair is new
+    assert lit._unet_pair() is new
+    lit.model_b = lit.create_model_instance()
+    assert lit._unet_pair().nets == (lit.model_a, lit.model_b)
+
+
 def test_bench_dump_outputs_is_the_headline_workloads(monkeypatch, capsys):
     """--dump-outputs writes what the headline step computed: any other workload is refused before anything runs."""
     import importlib.util

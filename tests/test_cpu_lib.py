@@ -56,6 +56,35 @@ def test_plan_errors_mirror_smp():
     assert b"Wrong encoder name" in lib.d3f_last_error()
 
 
+def test_pair_handle_refuses_the_single_network_calls():
+    """a pair handle (d3f_unet_create_nets(..., nets = 2, ...)) is refused by predict_u8, forward_graph, train_step and
+    set_bn_sync with a callback before anything reaches a device -- the dummy pointers below are never dereferenced;
+    removing a callback still succeeds.  Host only: with a device visible, a library without the guard would launch."""
+    if torch.cuda.is_available():
+        pytest.skip("host-only check of the C ABI guards (dummy device pointers)")
+    from denoising_diffusion_deep_fake_amd.graph_step import StepBuffers
+    lib = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(lib.d3f_unet_create_nets(b"resnet18", 3, 3, 1, 64, 64, _lib.F32, 2, 2, C.byref(h)))
+    try:
+        d = C.c_void_p(0x1000)
+        mean_std = (C.c_float * 3)(0.5, 0.5, 0.5)
+        buffers = StepBuffers(*[0x1000] * len(StepBuffers._fields_))
+        callback = _lib.ALLREDUCE_FN(lambda ctx, data, count, stream: 0)
+        calls = {
+            "predict_u8": lambda: lib.d3f_unet_predict_u8(h, d, d, d, d, mean_std, mean_std, d, 0, None),
+            "forward_graph": lambda: lib.d3f_unet_forward_graph(h, d, d, d, d, d, None),
+            "train_step": lambda: lib.d3f_unet_train_step(h, C.byref(buffers), 5.0, -1.0, 1.0, d, 0, None),
+            "set_bn_sync": lambda: lib.d3f_unet_set_bn_sync(h, C.cast(callback, C.c_void_p), None, 2),
+        }
+        for name, call in calls.items():
+            assert call() != 0, name
+            assert b"pair" in lib.d3f_last_error(), (name, lib.d3f_last_error())
+        assert lib.d3f_unet_set_bn_sync(h, None, None, 1) == 0
+    finally:
+        lib.d3f_unet_destroy(h)
+
+
 def test_module_tree_matches_engine_table_and_oracle_keys():
     import oracle
     from denoising_diffusion_deep_fake_amd import Unet
