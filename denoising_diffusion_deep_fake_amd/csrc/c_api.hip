@@ -53,118 +53,21 @@ struct d3f_unet {
 // storage dtype of a compute dtype (D3F_F32X3 keeps fp32 tensors)
 static inline int sdt(int dtype) { return dtype == D3F_F32X3 ? D3F_F32 : dtype; }
 
-static int desc_check(int dtype, const d3f_conv_desc* d) {
+// describe -> plan: the layer a descriptor describes (conv_plan.hip), with the launches `what` asks for
+enum { PLAN_FWD = 1, PLAN_DGRAD = 2, PLAN_WGRAD = 4, PLAN_SPLITK = 8, PLAN_SUM2 = 16 };
+static int plan(ConvLayer& L, int dtype, const d3f_conv_desc* d, int what) {
   D3F_CHECK(d != nullptr, "conv: null descriptor");
-  D3F_CHECK(dtype == D3F_F32 || dtype == D3F_BF16 || dtype == D3F_F32X3, "conv: dtype %d", dtype);
-  const int ve = sdt(dtype) == D3F_F32 ? 4 : 8;
-  D3F_CHECK(d->B >= 0 && d->H > 0 && d->W > 0 && d->C0 > 0 && d->C1 >= 0 && d->Cout > 0, "conv: extent");
-  D3F_CHECK(d->C0 % ve == 0 && d->C1 % ve == 0, "conv: channels must be multiples of %d", ve);
-  D3F_CHECK(d->KH == d->KW && d->KH >= 1 && d->KH <= 7, "conv: kernel %dx%d", d->KH, d->KW);
-  D3F_CHECK(d->stride == 1 || d->stride == 2, "conv: stride %d", d->stride);
-  D3F_CHECK(!d->upsample0 || (d->H % 2 == 0 && d->W % 2 == 0), "conv: up-sampled extent must be even");
-  D3F_CHECK(d->CinReal > 0 && d->CinReal <= d->C0 + d->C1, "conv: CinReal");
-  return 0;
-}
-
-struct Geo {
-  int Cin, Ho, Wo, CoutPad, Kpad, CoutD, KpadD, CinRows;
-};
-static Geo geo(int dtype, const d3f_conv_desc* d) {
-  const int ve = sdt(dtype) == D3F_F32 ? 4 : 8, bke = sdt(dtype) == D3F_F32 ? 32 : 64;
-  Geo g;
-  g.Cin = d->C0 + d->C1;
-  g.Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1;
-  g.Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-  g.CoutPad = (int)round_up(d->Cout, 16);
-  g.Kpad = (int)round_up((long)d->KH * d->KW * g.Cin, bke);
-  g.CoutD = (int)round_up(d->Cout, ve);
-  g.KpadD = (int)round_up((long)d->KH * d->KW * g.CoutD, bke);
-  g.CinRows = (int)round_up(g.Cin, 16);
-  return g;
-}
-
-static bool desc_upfold(int dtype, const d3f_conv_desc* d) {
-  return upfold_applies(sdt(dtype), d->upsample0, d->KH, d->stride, d->pad, d->C0, d->C1);
-}
-
-static int fwd_params(int dtype, const d3f_conv_desc* d, ConvParams& p, bool allow_splitk = false) {
-  if (int rc = desc_check(dtype, d)) return rc;
-  const Geo g = geo(dtype, d);
-  std::memset(&p, 0, sizeof(p));
-  p.B = d->B; p.Hv = d->H; p.Wv = d->W; p.C0 = d->C0; p.C1 = d->C1; p.cin_real = d->CinReal;
-  p.shift0 = d->upsample0 ? 1 : 0;
-  p.H0s = d->H >> p.shift0; p.W0s = d->W >> p.shift0;
-  p.Ho = g.Ho; p.Wo = g.Wo; p.Cout = d->Cout; p.CoutPad = g.CoutPad; p.Kpad = g.Kpad;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-  p.M = d->B * g.Ho * g.Wo;
-  p.mode = CONV_RAW_STATS;
-  if (desc_upfold(dtype, d)) {  // up-sampling folded into pre-summed weights: rows = one output-parity class
-    p.par = 3;
-    p.shift0 = 0;
-    p.Ho = p.H0s; p.Wo = p.W0s;
-    p.M = d->B * p.H0s * p.W0s;
-    p.Kpad = 4 * d->C0 + 9 * d->C1;
-  }
-  return conv_igemm_plan(p, dtype, allow_splitk);
-}
-
-// data gradient of an up-sample-folded layer: (lo) 4x4 stride-2 convolution over dY -> gradient of the LOW-resolution
-// source [B][H/2][W/2][C0]; (skip) ordinary 3x3 data gradient -> gradient of the skip tensor [B][H][W][C1]
-static int upfold_dgrad_params(int dtype, const d3f_conv_desc* d, ConvParams& lo, ConvParams& sk, bool allow_splitk) {
-  const Geo g = geo(dtype, d);
-  std::memset(&lo, 0, sizeof(lo));
-  std::memset(&sk, 0, sizeof(sk));
-  lo.B = d->B; lo.C0 = g.CoutD; lo.C1 = 0;
-  lo.Hv = lo.H0s = d->H; lo.Wv = lo.W0s = d->W;
-  lo.Ho = d->H / 2; lo.Wo = d->W / 2;
-  lo.Cout = d->C0; lo.CoutPad = (int)round_up(d->C0, 16); lo.Kpad = 16 * g.CoutD;
-  lo.KH = lo.KW = 4; lo.stride = 2; lo.pad = 1;
-  lo.M = d->B * lo.Ho * lo.Wo;
-  lo.mode = CONV_DGRAD;
-  lo.out_c0 = d->C0;
-  if (int rc = conv_igemm_plan(lo, dtype, allow_splitk)) return rc;
-  if (d->C1 > 0) {
-    sk.B = d->B; sk.C0 = g.CoutD; sk.C1 = 0;
-    sk.Hv = sk.H0s = sk.Ho = d->H; sk.Wv = sk.W0s = sk.Wo = d->W;
-    sk.Cout = d->C1; sk.CoutPad = (int)round_up(d->C1, 16); sk.Kpad = g.KpadD;
-    sk.KH = sk.KW = 3; sk.stride = 1; sk.pad = 1;
-    sk.M = d->B * d->H * d->W;
-    sk.mode = CONV_DGRAD;
-    sk.out_c0 = d->C1;
-    if (int rc = conv_igemm_plan(sk, dtype, allow_splitk)) return rc;
-  }
-  return 0;
-}
-
-// want_sum2: the caller takes dx0 of an up-sampled single source at the source's LOW resolution where a launch can sum the
-// 2x2 blocks itself (d3f_conv_desc::upsample0 == 2, or the availability query d3f_conv_upsample_summed)
-static int dgrad_params(int dtype, const d3f_conv_desc* d, ConvParams& p, bool allow_splitk, bool want_sum2) {
-  if (int rc = desc_check(dtype, d)) return rc;
-  const Geo g = geo(dtype, d);
-  const int s2 = d->stride == 2;
-  D3F_CHECK(s2 ? (g.Ho * 2 == d->H && g.Wo * 2 == d->W) : (g.Ho == d->H && g.Wo == d->W),
-            "conv_backward_data: needs a 'same' (stride 1) or exactly halving (stride 2) conv");
-  std::memset(&p, 0, sizeof(p));
-  p.mode = CONV_DGRAD;
-  p.out_c0 = d->C1 > 0 ? d->C0 : g.Cin;
-  p.Cout = g.Cin; p.CoutPad = g.CinRows; p.Kpad = g.KpadD; p.C0 = g.CoutD; p.C1 = 0; p.B = d->B;
-  if (parity_dgrad_applies(dtype, d->stride, d->KH, d->pad, g.CoutD, d->C1)) {
-    // stride 2: four plain sub-convolutions over dY, one per output-parity class (conv_igemm.hip)
-    p.par = d->KH == 3 ? 1 : 2;
-    p.Hv = p.Ho = p.H0s = g.Ho; p.Wv = p.Wo = p.W0s = g.Wo;
-    p.KH = p.KW = d->KH == 3 ? 2 : 1; p.stride = 1; p.pad = 0;
-    p.M = d->B * g.Ho * g.Wo;
-    return conv_igemm_plan(p, dtype, false);
-  }
-  p.Hv = d->H; p.Wv = d->W;
-  p.H0s = g.Ho; p.W0s = g.Wo; p.shift0 = s2; p.zi = s2;
-  p.Ho = d->H; p.Wo = d->W;
-  p.KH = d->KH; p.KW = d->KW; p.stride = 1; p.pad = d->KH - 1 - d->pad;
-  p.M = d->B * d->H * d->W;
-  // an up-sampled single source without folded weights: ask for the 2x2-summed gradient at the source's own resolution
-  // (kept by the plan only where a patch kernel serves it: d3f_conv_upsample_summed) -- only for a caller that said so
-  p.sum2 = (want_sum2 && d->upsample0 && d->C1 == 0) ? 1 : 0;
-  return conv_igemm_plan(p, dtype, allow_splitk);
+  L.B = d->B; L.Hv = d->H; L.Wv = d->W; L.C0 = d->C0; L.C1 = d->C1; L.up0 = d->upsample0 ? 1 : 0;
+  L.CinReal = d->CinReal; L.Cout = d->Cout; L.KH = d->KH; L.KW = d->KW; L.stride = d->stride; L.pad = d->pad;
+  L.dtype = dtype;
+  L.need_fwd = what & PLAN_FWD;
+  L.need_dgrad = what & PLAN_DGRAD;
+  L.need_wgrad = what & PLAN_WGRAD;
+  L.allow_splitk = what & PLAN_SPLITK;
+  // want_sum2: the caller takes dx0 of an up-sampled single source at the source's LOW resolution where a launch can sum
+  // the 2x2 blocks itself (d3f_conv_desc::upsample0 == 2, or the availability query d3f_conv_upsample_summed)
+  L.want_sum2 = what & PLAN_SUM2;
+  return conv_layer_plan(L);
 }
 
 extern "C" {
@@ -429,188 +332,147 @@ int d3f_unet_export_shape(d3f_unet_t h, const char* name, int32_t dims[3]) {
   return h->e.export_shape(name, dims);
 }
 
-// ---- single operators -----------------------------------------------------------------------
+// ---- single operators ----------------------------------------------------------------------
 size_t d3f_conv_packed_bytes(int dtype, const d3f_conv_desc* d, int which) {
-  if (desc_check(dtype, d) != 0) return 0;
-  const Geo g = geo(dtype, d);
-  const size_t es = dtype == D3F_F32X3 ? 6 : (dtype == D3F_F32 ? 4 : 2);  // x3: three bf16 planes
-  if (desc_upfold(dtype, d)) {
-    // forward: four per-class matrices; data gradient: [wd4 (low-resolution source) | wds (skip tensor)]
-    const size_t c0r = (size_t)round_up(d->C0, 16), c1r = (size_t)round_up(d->C1, 16);
-    return which == 0 ? (size_t)4 * g.CoutPad * (4 * d->C0 + 9 * d->C1) * es
-                      : (c0r * 16 * g.CoutD + c1r * g.KpadD) * es;
-  }
-  return which == 0 ? (size_t)g.CoutPad * g.Kpad * es : (size_t)g.CinRows * g.KpadD * es;
+  ConvLayer L;
+  if (plan(L, dtype, d, 0) != 0) return 0;
+  if (L.upfold) return which == 0 ? L.wfc : L.wd4 + L.wds;  // data gradient: [wd4 (low-resolution source) | wds (skip)]
+  return which == 0 ? L.wf : L.wd;
 }
 int d3f_conv_pack_weights(int dtype, const d3f_conv_desc* d, const float* w, void* w_fwd, void* w_dgrad,
                           void* stream) {
-  if (int rc = desc_check(dtype, d)) return rc;
-  const Geo g = geo(dtype, d);
-  if (desc_upfold(dtype, d)) {
-    const size_t es = dtype == D3F_F32X3 ? 6 : (dtype == D3F_F32 ? 4 : 2);
-    const int c0r = (int)round_up(d->C0, 16), c1r = (int)round_up(d->C1, 16);
+  ConvLayer L;
+  if (int rc = plan(L, dtype, d, 0)) return rc;
+  if (L.upfold) {
     D3F_CHECK(w_fwd != nullptr && d->CinReal == d->C0 + d->C1, "conv_pack_weights: up-sample folded layer");
-    char* wds = w_dgrad ? reinterpret_cast<char*>(w_dgrad) + (size_t)c0r * 16 * g.CoutD * es : nullptr;
-    return pack_up_launch(dtype, w, d->Cout, d->C0, d->C1, w_fwd, g.CoutPad, w_dgrad, c0r,
-                          d->C1 > 0 ? wds : nullptr, c1r, (hipStream_t)stream);
+    char* wds = w_dgrad && d->C1 > 0 ? reinterpret_cast<char*>(w_dgrad) + L.wd4 : nullptr;
+    return pack_up_launch(dtype, w, d->Cout, d->C0, d->C1, w_fwd, L.CoutPad, w_dgrad, L.C0Rows, wds, L.C1Rows,
+                          (hipStream_t)stream);
   }
-  return pack_weights_launch(dtype, w, d->Cout, d->CinReal, g.Cin, d->KH, d->KW, w_fwd, g.CoutPad, g.Kpad,
-                             w_dgrad, g.CinRows, g.KpadD,
-                             parity_dgrad_applies(dtype, d->stride, d->KH, d->pad, g.CoutD, d->C1) ? 2 : 1,
-                             (hipStream_t)stream);
+  return pack_weights_launch(dtype, w, d->Cout, d->CinReal, L.Cin, d->KH, d->KW, w_fwd, L.CoutPad, L.Kpad, w_dgrad,
+                             L.CinRows, L.KpadD, L.parity ? 2 : 1, (hipStream_t)stream);
 }
 int d3f_conv_upsample_folded(int dtype, const d3f_conv_desc* d) {
-  return (d != nullptr && desc_check(dtype, d) == 0 && desc_upfold(dtype, d)) ? 1 : 0;
+  ConvLayer L;
+  return (d != nullptr && plan(L, dtype, d, 0) == 0 && L.upfold) ? 1 : 0;
 }
 int d3f_conv_upsample_summed(int dtype, const d3f_conv_desc* d) {
-  ConvParams p;
-  if (d == nullptr || !d->upsample0 || desc_check(dtype, d) != 0 || desc_upfold(dtype, d)) return 0;
-  if (dgrad_params(dtype, d, p, false, true) != 0) return 0;
-  return p.sum2 ? 1 : 0;
+  ConvLayer L, D;  // (a folded layer plans no data-gradient launch for the question)
+  if (d == nullptr || !d->upsample0 || plan(L, dtype, d, 0) != 0 || L.upfold) return 0;
+  return (plan(D, dtype, d, PLAN_DGRAD | PLAN_SUM2) == 0 && D.dgrad.sum2) ? 1 : 0;
 }
 size_t d3f_conv_workspace_bytes(int dtype, const d3f_conv_desc* d, int which) {
-  ConvParams p;
-  if (which != 0 && desc_check(dtype, d) == 0 && desc_upfold(dtype, d)) {
-    ConvParams lo, sk;
-    if (upfold_dgrad_params(dtype, d, lo, sk, true) != 0) return 0;
-    return std::max(conv_splitk_floats(lo), d->C1 > 0 ? conv_splitk_floats(sk) : (size_t)0) * sizeof(float);
-  }
-  const int rc = which == 0 ? fwd_params(dtype, d, p, true) : dgrad_params(dtype, d, p, true, d != nullptr && d->upsample0 == 2);
-  return rc != 0 ? 0 : conv_splitk_floats(p) * sizeof(float);
+  ConvLayer L;
+  const int what = which == 0 ? PLAN_FWD : PLAN_DGRAD | (d != nullptr && d->upsample0 == 2 ? PLAN_SUM2 : 0);
+  return plan(L, dtype, d, what | PLAN_SPLITK) != 0 ? 0 : L.splitk_floats * sizeof(float);
 }
 size_t d3f_conv_stats_floats(int dtype, const d3f_conv_desc* d, int with_workspace, int* tiles) {
-  ConvParams p;
-  if (fwd_params(dtype, d, p, with_workspace != 0) != 0) return 0;
-  if (tiles) *tiles = p.stat_rows;
-  return (size_t)p.stat_rows * p.CoutPad * 2;
+  ConvLayer L;
+  if (plan(L, dtype, d, PLAN_FWD | (with_workspace ? PLAN_SPLITK : 0)) != 0) return 0;
+  if (tiles) *tiles = L.fwd.stat_rows;
+  return (size_t)L.fwd.stat_rows * L.CoutPad * 2;
 }
 int d3f_conv_forward(int dtype, const d3f_conv_desc* d, const void* src0, const void* src1,
                      const void* w_fwd, void* y, float* stats, void* workspace, void* stream) {
-  ConvParams p;
-  if (int rc = fwd_params(dtype, d, p, workspace != nullptr)) return rc;
-  if (d && d->B == 0) return 0;  // empty batch: nothing to compute (an empty tensor has a null data pointer)
+  ConvLayer L;
+  if (int rc = plan(L, dtype, d, PLAN_FWD | (workspace ? PLAN_SPLITK : 0))) return rc;
+  if (d->B == 0) return 0;  // empty batch: nothing to compute (an empty tensor has a null data pointer)
   D3F_CHECK(src0 && w_fwd && y && (d->C1 == 0 || src1), "conv_forward: null argument");
-  p.src0 = src0; p.src1 = src1; p.w = w_fwd; p.out0 = y; p.stats = stats; p.mode = CONV_RAW_STATS;
+  ConvParams p = L.fwd;
+  p.src0 = src0; p.src1 = src1; p.w = w_fwd; p.out0 = y; p.stats = stats;
   p.partial = p.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
   return conv_igemm_launch(p, dtype, (hipStream_t)stream);
 }
 // ---- Winograd F(2x2, 3x3) form of a stride-1 3x3 fp32 layer on its own (conv_winograd.hip) ----
-static int wino_params(const d3f_conv_desc* d, ConvParams& p) {
-  if (int rc = fwd_params(D3F_F32, d, p, false)) return rc;
-  D3F_CHECK(conv_winograd_fits(p, D3F_F32),
+// (the layer planned as fp32 with its Winograd sizes filled, i.e. the kernel fits it)
+static int wino_plan(ConvLayer& L, const d3f_conv_desc* d) {
+  if (int rc = plan(L, D3F_F32, d, PLAN_FWD)) return rc;
+  D3F_CHECK(L.wu != 0,
             "conv_winograd: needs 3x3 / stride 1 / pad 1, one source, H and W multiples of 16, channels a multiple of 16, "
             "filters a multiple of 64 (got %dx%d k%d s%d p%d C0=%d C1=%d up=%d Cout=%d)",
             d->H, d->W, d->KH, d->stride, d->pad, d->C0, d->C1, d->upsample0, d->Cout);
   return 0;
 }
 int d3f_conv_winograd_applies(int dtype, const d3f_conv_desc* d) {
-  ConvParams p;
-  if (d == nullptr || desc_check(dtype, d) != 0 || fwd_params(dtype, d, p, false) != 0) return 0;
-  return conv_winograd_applies(p, dtype) ? 1 : 0;
+  ConvLayer L;
+  return (d != nullptr && plan(L, dtype, d, PLAN_FWD) == 0 && L.wino) ? 1 : 0;
 }
 size_t d3f_conv_winograd_filter_bytes(const d3f_conv_desc* d) {
-  ConvParams p;
-  return (d == nullptr || desc_check(D3F_F32, d) != 0 || fwd_params(D3F_F32, d, p, false) != 0 || !conv_winograd_fits(p, D3F_F32))
-             ? 0 : conv_winograd_filter_floats(p) * sizeof(float);
+  ConvLayer L;
+  return (d == nullptr || plan(L, D3F_F32, d, PLAN_FWD) != 0) ? 0 : L.wu;
 }
 size_t d3f_conv_winograd_stats_floats(const d3f_conv_desc* d, int* tiles) {
-  ConvParams p;
-  if (d == nullptr || desc_check(D3F_F32, d) != 0 || fwd_params(D3F_F32, d, p, false) != 0 || !conv_winograd_fits(p, D3F_F32))
-    return 0;
-  const int rows = conv_winograd_stat_rows(p);
-  if (tiles) *tiles = rows;
-  return (size_t)rows * p.CoutPad * 2;
+  ConvLayer L;
+  if (d == nullptr || plan(L, D3F_F32, d, PLAN_FWD) != 0 || L.wu == 0) return 0;
+  if (tiles) *tiles = L.wino_rows;
+  return (size_t)L.wino_rows * L.CoutPad * 2;
 }
 int d3f_conv_winograd_pack(const d3f_conv_desc* d, const float* w, void* u, void* stream) {
-  ConvParams p;
-  if (int rc = wino_params(d, p)) return rc;
+  ConvLayer L;
+  if (int rc = wino_plan(L, d)) return rc;
   D3F_CHECK(w && u && d->CinReal == d->C0, "conv_winograd_pack: null argument or padded input channels");
   return conv_winograd_pack_launch(w, reinterpret_cast<float*>(u), d->Cout, d->C0, (hipStream_t)stream);
 }
 int d3f_conv_winograd_forward(const d3f_conv_desc* d, const void* src0, const void* u, void* y, float* stats,
                               const float* scale, const float* shift, const void* residual, int relu, void* stream) {
-  ConvParams p;
-  if (int rc = wino_params(d, p)) return rc;
+  ConvLayer L;
+  if (int rc = wino_plan(L, d)) return rc;
   if (d->B == 0) return 0;
   D3F_CHECK(src0 && u && y && ((scale == nullptr) == (shift == nullptr)), "conv_winograd_forward: null argument");
   D3F_CHECK(scale != nullptr || (residual == nullptr && relu == 0),
             "conv_winograd_forward: residual / ReLU belong to the eval epilogue (scale and shift)");
+  ConvParams p = L.fwd;
   p.src0 = src0; p.w = u; p.out0 = y;
   if (scale != nullptr) {
     p.mode = CONV_EVAL_FUSED; p.scale = scale; p.shift = shift; p.res = residual; p.relu = relu ? 1 : 0;
   } else {
-    p.mode = CONV_RAW_STATS; p.stats = stats; p.stat_rows = conv_winograd_stat_rows(p);
+    p.stats = stats; p.stat_rows = L.wino_rows;
   }
   return conv_winograd_launch(p, (hipStream_t)stream);
 }
 int d3f_conv_backward_data(int dtype, const d3f_conv_desc* d, const void* dy, const void* w_dgrad,
                            void* dx0, void* dx1, int acc0, int acc1, void* workspace, void* stream) {
-  ConvParams p;
-  if (desc_check(dtype, d) == 0 && desc_upfold(dtype, d)) {
+  ConvLayer L;
+  const int sum2 = d != nullptr && d->upsample0 == 2 ? PLAN_SUM2 : 0;
+  if (int rc = plan(L, dtype, d, PLAN_DGRAD | sum2 | (workspace ? PLAN_SPLITK : 0))) return rc;
+  if (d->B == 0) return 0;
+  D3F_CHECK(dy && w_dgrad && dx0 && (d->C1 == 0 || dx1), "conv_backward_data: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  if (L.upfold) {
     // dx0 = gradient of the LOW-resolution source [B][H/2][W/2][C0], dx1 = gradient of the skip tensor
-    ConvParams lo, sk;
-    if (int rc = upfold_dgrad_params(dtype, d, lo, sk, workspace != nullptr)) return rc;
-    if (d->B == 0) return 0;
-    D3F_CHECK(dy && w_dgrad && dx0 && (d->C1 == 0 || dx1), "conv_backward_data: null argument");
-    const Geo g = geo(dtype, d);
-    const size_t es = dtype == D3F_F32X3 ? 6 : (dtype == D3F_F32 ? 4 : 2);
+    ConvParams lo = L.dgrad_lo;
     lo.src0 = dy; lo.w = w_dgrad; lo.out0 = dx0; lo.acc0 = acc0;
     lo.partial = lo.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
-    if (int rc = conv_igemm_launch(lo, dtype, (hipStream_t)stream)) return rc;
-    if (d->C1 > 0) {
-      sk.src0 = dy;
-      sk.w = reinterpret_cast<const char*>(w_dgrad) + (size_t)round_up(d->C0, 16) * 16 * g.CoutD * es;
-      sk.out0 = dx1; sk.acc0 = acc1;
-      sk.partial = sk.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
-      if (int rc = conv_igemm_launch(sk, dtype, (hipStream_t)stream)) return rc;
-    }
-    return 0;
+    if (int rc = conv_igemm_launch(lo, dtype, s)) return rc;
+    if (d->C1 == 0) return 0;
+    ConvParams sk = L.dgrad;
+    sk.src0 = dy; sk.w = reinterpret_cast<const char*>(w_dgrad) + L.wd4; sk.out0 = dx1; sk.acc0 = acc1;
+    sk.partial = sk.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
+    return conv_igemm_launch(sk, dtype, s);
   }
-  if (int rc = dgrad_params(dtype, d, p, workspace != nullptr, d != nullptr && d->upsample0 == 2)) return rc;
-  if (d && d->B == 0) return 0;
-  D3F_CHECK(dy && w_dgrad && dx0 && (d->C1 == 0 || dx1), "conv_backward_data: null argument");
+  ConvParams p = L.dgrad;
   p.src0 = dy; p.w = w_dgrad; p.out0 = dx0; p.out1 = dx1; p.acc0 = acc0; p.acc1 = acc1;
   p.partial = p.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
-  if (p.par == 2 && !acc0) {  // 1x1 stride 2: only even pixels receive a gradient; the others are zero
-    const size_t es = sdt(dtype) == D3F_F32 ? 4 : 2;
-    D3F_HIP(hipMemsetAsync(dx0, 0, (size_t)4 * p.M * p.Cout * es, (hipStream_t)stream));
-  }
-  return conv_igemm_launch(p, dtype, (hipStream_t)stream);
-}
-static int wgrad_params(int dtype, const d3f_conv_desc* d, WgradParams& w) {
-  if (int rc = desc_check(dtype, d)) return rc;
-  const Geo g = geo(dtype, d);
-  std::memset(&w, 0, sizeof(w));
-  w.B = d->B; w.Hv = d->H; w.Wv = d->W; w.C0 = d->C0; w.C1 = d->C1;
-  w.shift0 = d->upsample0 ? 1 : 0;
-  w.H0s = d->H >> w.shift0; w.W0s = d->W >> w.shift0;
-  w.Ho = g.Ho; w.Wo = g.Wo; w.Cout = g.CoutD;
-  w.KH = d->KH; w.KW = d->KW; w.stride = d->stride; w.pad = d->pad;
-  w.M = d->B * g.Ho * g.Wo;
-  w.cin_real = d->CinReal;
-  return wgrad_plan(w, sdt(dtype));
+  if (p.par == 2 && !acc0)  // 1x1 stride 2: only even pixels receive a gradient; the others are zero
+    D3F_HIP(hipMemsetAsync(dx0, 0, (size_t)4 * p.M * p.Cout * (L.sdtype == D3F_F32 ? 4 : 2), s));
+  return conv_igemm_launch(p, dtype, s);
 }
 size_t d3f_conv_backward_weight_workspace_bytes(int dtype, const d3f_conv_desc* d) {
-  WgradParams w;
-  if (wgrad_params(dtype, d, w) != 0) return 0;
-  WgradLayer L;
-  if (wgrad_layer_plan(L, w, sdt(dtype)) != 0) return 0;
-  return wgrad_layer_partial_floats(L) * sizeof(float);
+  ConvLayer L;
+  return plan(L, dtype, d, PLAN_WGRAD) != 0 ? 0 : L.wslab_bytes;
 }
 int d3f_conv_backward_weight(int dtype, const d3f_conv_desc* d, const void* dy, const void* src0,
                              const void* src1, void* workspace, float* dw, void* stream) {
-  WgradParams w;
-  if (int rc = wgrad_params(dtype, d, w)) return rc;
-  if (d && d->B == 0) {  // empty batch: the gradient is zero
+  ConvLayer L;
+  if (int rc = plan(L, dtype, d, PLAN_WGRAD)) return rc;
+  if (d->B == 0) {  // empty batch: the gradient is zero
     D3F_CHECK(dw, "conv_backward_weight: null argument");
     D3F_HIP(hipMemsetAsync(dw, 0, (size_t)d->Cout * d->CinReal * d->KH * d->KW * sizeof(float), (hipStream_t)stream));
     return 0;
   }
   D3F_CHECK(dy && src0 && workspace && dw && (d->C1 == 0 || src1), "conv_backward_weight: null argument");
   // the passes the engine runs for this layer (class form behind an up-sampling where it applies), then its slab reduce
-  WgradLayer L;
-  if (int rc = wgrad_layer_plan(L, w, sdt(dtype))) return rc;
-  return wgrad_layer_launch(L, dy, src0, src1, reinterpret_cast<float*>(workspace), dw, d->Cout, d->CinReal, dtype,
+  return wgrad_layer_launch(L.wl, dy, src0, src1, reinterpret_cast<float*>(workspace), dw, d->Cout, d->CinReal, dtype,
                             (hipStream_t)stream);
 }
 

@@ -255,6 +255,7 @@ struct ConvParams {
   // workgroups of plan_nets networks, so that a single engine planned with plan_nets = 2 runs exactly the pair's kernels.
   int nets, plan_nets;
   long net_ws, net_out0, net_scale;
+  int tile_bm, tile_bn;  // conv_igemm_kernel's tile (filled by the plan; patch kernels: unused)
 };
 // the launch description as net `net` (blockIdx.z / nz) sees it
 __device__ __forceinline__ ConvParams conv_params_of_net(const ConvParams& pin, int net) {
@@ -272,20 +273,7 @@ __device__ __forceinline__ ConvParams conv_params_of_net(const ConvParams& pin, 
 struct ConvTile {
   int BM, BN;
 };
-// Does conv(cat(upsample2x(x0), x1)) run with the up-sampling folded into pre-summed weights (ConvParams::par == 3
-// forward, 4x4 stride-2 data gradient)?  Needs whole k-tiles per tap in both sources.
-static inline bool upfold_applies(int dtype, int upsample0, int k, int stride, int pad, int C0, int C1) {
-  static const bool off = prof_knob("D3F_NO_UPFOLD") != nullptr;  // debugging knob: gather through the up-sampling
-  const int bke = dtype == D3F_BF16 ? 64 : 32;
-  return !off && upsample0 && k == 3 && stride == 1 && pad == 1 && C0 > 0 && (C0 % bke) == 0 && (C1 % bke) == 0;
-}
-// Does the data gradient of this convolution run as the parity-class decomposition (ConvParams::par)?  The weight
-// packers (pointwise.hip) store the flipped taps class by class exactly when it does, so both ask this one function.
-static inline bool parity_dgrad_applies(int dtype, int stride, int k, int pad, int CoutD, int C1) {
-  const int bke = dtype == D3F_BF16 ? 64 : 32;
-  return stride == 2 && C1 == 0 && (CoutD % bke) == 0 && ((k == 3 && pad == 1) || (k == 1 && pad == 0));
-}
-// chooses the tile configuration for a problem; tiles_m/tiles_n are filled in p.
+// chooses the tile configuration for a problem; tile_bm/tile_bn and tiles_m/tiles_n are filled in p.
 // allow_splitk: the caller can provide `partial` (conv_splitk_floats(p) floats) -- deep layers
 // whose M x Cout yields too few workgroups then split the K loop over grid.y.
 int conv_igemm_plan(ConvParams& p, int dtype, bool allow_splitk = false);
@@ -396,5 +384,38 @@ int wgrad_layer_launch(const WgradLayer& L, const void* dy, const void* src0, co
 int wgrad_layer_launch_deferred(const WgradLayer& L, const void* dy, const void* src0, const void* src1, float* partial,
                                 float* dw, int CoutReal, int CinReal, int dtype, WgradReduceBatch& tb,
                                 hipStream_t stream, const NetSplit* ns = nullptr);
+
+// ---------------------------------------------------------------------------------------
+// One convolution layer y = conv(cat(upsample2x?(src0), src1)), planned once (conv_plan.hip) for both the whole-network
+// engine and the single-operator C API
+// ---------------------------------------------------------------------------------------
+struct ConvLayer {
+  // ---- description (set by the caller) ----
+  int B = 0, Hv = 0, Wv = 0;   // input extent after the optional up-sampling
+  int C0 = 0, C1 = 0, up0 = 0; // channels of src0 / src1 (vector multiples); up0: src0 is read through nearest x2
+  int CinReal = 0, Cout = 0, KH = 0, KW = 0, stride = 1, pad = 0;
+  int dtype = 0;               // compute dtype
+  bool head = false;           // forward: + bias, NCHW store (segmentation head) instead of raw output + statistics
+  bool need_fwd = false, need_dgrad = false, need_wgrad = false;  // launches to plan (geometry and sizes: always)
+  bool want_sum2 = false;      // an up-sampled source's data gradient may come back 2x2-summed (ConvParams::sum2)
+  bool allow_splitk = false;   // the caller provides split-K slabs (splitk_floats)
+  int plan_nets = 0;           // ConvParams::plan_nets / WgradParams::plan_nets
+  // ---- plan (filled by conv_layer_plan) ----
+  int sdtype = 0;              // storage dtype
+  int Cin = 0, Ho = 0, Wo = 0, CoutPad = 0, Kpad = 0, CoutD = 0, KpadD = 0, CinRows = 0, C0Rows = 0, C1Rows = 0;
+  bool upfold = false;         // up-sampling folded into pre-summed weights: fwd.par == 3, dgrad_lo + dgrad (skip tensor)
+  bool parity = false;         // stride-2 data gradient as output-parity classes (dgrad.par 1 / 2; packed class by class)
+  bool wino = false;           // the train-mode forward runs as Winograd F(2x2, 3x3)
+  ConvParams fwd{}, dgrad{}, dgrad_lo{};
+  WgradLayer wl{};
+  int wino_rows = 0;           // Winograd statistics rows (where its kernel fits the layer, as wu)
+  size_t wf = 0, wd = 0;       // packed weight bytes: forward / data-gradient layouts
+  size_t wfc = 0, wd4 = 0, wds = 0;  // ... of an up-folded layer: per-class forward, low-resolution source, skip tensor
+  size_t wu = 0;               // ... Winograd filters, where its kernel fits the layer (else 0)
+  size_t splitk_floats = 0;    // the planned launches' largest split-K slab set
+  size_t wslab_bytes = 0;      // weight-gradient slabs
+  double macs = 0;             // algorithmic multiply-adds (unpadded channels)
+};
+int conv_layer_plan(ConvLayer& L);
 
 }  // namespace d3f

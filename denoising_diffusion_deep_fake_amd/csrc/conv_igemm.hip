@@ -1535,6 +1535,8 @@ int conv_igemm_plan(ConvParams& p, int dtype, bool allow_splitk) {
   }
   p.sum2 = 0;  // (a request the implicit GEMM does not serve: full-resolution output, the caller sums the 2x2 blocks)
   const ConvTile t = pick_tile(p, dtype == D3F_F32X3, dtype == D3F_BF16);
+  p.tile_bm = t.BM;
+  p.tile_bn = t.BN;
   p.tiles_m = cdiv(p.M, t.BM);
   p.tiles_n = cdiv(p.Cout, t.BN);
   p.splitk = 1;
@@ -1580,8 +1582,8 @@ static int launch_cfg(const ConvParams& p, bool smallc, hipStream_t stream) {
 }
 
 template <typename T, bool X3> static int launch_t(const ConvParams& p, bool smallc, hipStream_t stream) {
-  const ConvTile t = pick_tile(p, X3, sizeof(T) == 2 && !X3);
-  D3F_CHECK(p.tiles_m == cdiv(p.M, t.BM) && p.tiles_n == cdiv(p.Cout, t.BN),
+  const ConvTile t{p.tile_bm, p.tile_bn};  // the plan's choice
+  D3F_CHECK(t.BM > 0 && t.BN > 0 && p.tiles_m == cdiv(p.M, t.BM) && p.tiles_n == cdiv(p.Cout, t.BN),
             "conv: params were not planned (tiles %d,%d)", p.tiles_m, p.tiles_n);
   if (t.BM == 256 && t.BN == 16) return launch_cfg<T, 256, 16, 4, 1, 16, X3>(p, smallc, stream);
   if (t.BM == 256 && t.BN == 32) return launch_cfg<T, 256, 32, 4, 1, 32, X3>(p, smallc, stream);

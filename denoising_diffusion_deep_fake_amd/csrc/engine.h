@@ -32,37 +32,24 @@ struct BnInfo {
   long rm_off, rv_off;  // floats into the flat BN-statistics buffer
 };
 
-struct Unit {
+// one convolution layer of the network: its plan (common.h, ConvLayer: description, geometry, launches, packed sizes)
+// plus its place in the network -- tensors, parameters, BatchNorm, workspace regions
+struct Unit : ConvLayer {
   std::string conv_name, bn_name;
-  int Cout = 0, CinReal = 0, C0 = 0, C1 = 0, KH = 0, KW = 0, stride = 1, pad = 0, up0 = 0;
-  int Hv = 0, Wv = 0, Ho = 0, Wo = 0;
   int in0 = -1, in1 = -1, y = -1, a = -1;
-  bool bn = true, bias = false, relu = true, apply = true, need_dgrad = true;
+  bool bn = true, bias = false, relu = true, apply = true;
   int res_tensor = -1, res_unit = -1;
   long w_off = -1, bias_off = -1, g_off = -1, b_off = -1, rm_off = -1, rv_off = -1;
   size_t wf_off = 0, wd_off = 0;  // packed weights (bytes into workspace)
-  int CoutPad = 0, Kpad = 0, CinRows = 0, KpadD = 0, CoutD = 0;
   size_t coef_off = 0;  // bytes: mean[C] invstd[C] scale[C] shift[C] k[3C]
   int segment = 0;      // backward bucket this unit belongs to
   size_t dy_off = 0;    // this unit's own dY buffer (kept until its weight-gradient group has run)
   // decoder conv(cat(upsample2x(in0), in1)) with the up-sampling folded into pre-summed weights (pointwise.hip,
   // pack_up_kernel): per-class forward matrices, the 4x4 stride-2 data gradient w.r.t. in0 (written at in0's own
   // resolution: no full-resolution scratch, no 2x2 sum) and the skip tensor's 3x3 data gradient as its own launch
-  bool upfold = false;
   size_t wfc_off = 0, wd4_off = 0, wds_off = 0;
-  // train-mode forward as Winograd F(2x2, 3x3) (conv_winograd.hip): transformed filters, statistics rows
-  bool wino = false;
-  size_t wu_off = 0;
-  int wino_rows = 0;
-  int C0Rows = 0, C1Rows = 0;
-  ConvParams dgrad_lo{};
-  ConvParams fwd{}, dgrad{};
-  // weight gradient as WG_CLASS + WG_SKIP passes (conv_wgrad.hip): the decoder layers behind an up-sampling whose
-  // gradient runs on the tap-parallel kernel -- 4/9 of the MACs on the up-sampled channels
-  bool wclass = false;
-  WgradLayer wl{};
-  size_t wslab_off = 0;  // this unit's own slab region
-  int Cin() const { return C0 + C1; }
+  size_t wu_off = 0;     // Winograd F(2x2, 3x3) filters (conv_winograd.hip) of a layer whose forward runs as Winograd
+  size_t wslab_off = 0;  // this unit's own weight-gradient slab region
 };
 
 enum BwdKind { BW_HEAD, BW_UNIT, BW_SUM2X2, BW_POOL };
@@ -163,7 +150,6 @@ class UnetEngine {
   int esize() const { return dtype == D3F_F32 ? 4 : 2; }
   int wsize() const { return cdtype == D3F_F32X3 ? 6 : esize(); }  // bytes per packed weight (x3: three bf16 planes)
   int ve() const { return dtype == D3F_F32 ? 4 : 8; }
-  int bke() const { return dtype == D3F_F32 ? 32 : 64; }
   const TensorD* find_export(const char* name) const;
   int new_tensor(int H_, int W_, int C_);
   int new_grad(int tensor_id);
@@ -171,7 +157,6 @@ class UnetEngine {
   int add_unit(const std::string& conv_name, const std::string& bn_name, int in0, int in1, int up0,
                int Cout, int k, int stride, int pad, bool bn, bool bias, bool relu, bool apply,
                int segment);
-  int plan_unit(Unit& u);
 
   std::vector<TensorD> tensors;   // activations
   std::vector<TensorD> gtensors;  // activation gradients

@@ -126,20 +126,22 @@ int UnetEngine::add_unit(const std::string& conv_name, const std::string& bn_nam
   Unit u;
   u.conv_name = conv_name;
   u.bn_name = bn_name;
-  u.in0 = in0; u.in1 = in1; u.up0 = up0;
-  u.Cout = Cout; u.KH = u.KW = k; u.stride = stride; u.pad = pad;
+  u.in0 = in0; u.in1 = in1;
   u.bn = bn; u.bias = bias; u.relu = relu; u.apply = apply; u.segment = segment;
   const TensorD& t0 = tensors[in0];
-  u.C0 = t0.C;
-  u.Hv = t0.H << up0;
-  u.Wv = t0.W << up0;
-  u.C1 = in1 >= 0 ? tensors[in1].C : 0;
+  u.B = B; u.Hv = t0.H << up0; u.Wv = t0.W << up0;
+  u.C0 = t0.C; u.C1 = in1 >= 0 ? tensors[in1].C : 0; u.up0 = up0;
   D3F_CHECK(in1 < 0 || (tensors[in1].H == u.Hv && tensors[in1].W == u.Wv),
             "unit %s: skip extent mismatch", conv_name.c_str());
-  u.CinReal = (in0 == t_x) ? in_channels : u.Cin();
-  u.Ho = (u.Hv + 2 * pad - k) / stride + 1;
-  u.Wo = (u.Wv + 2 * pad - k) / stride + 1;
+  u.CinReal = (in0 == t_x) ? in_channels : u.C0 + u.C1;
+  u.Cout = Cout; u.KH = u.KW = k; u.stride = stride; u.pad = pad;
+  u.dtype = cdtype;
+  u.head = !bn;
+  u.need_fwd = u.need_wgrad = true;
   u.need_dgrad = (in0 != t_x);
+  u.want_sum2 = u.allow_splitk = true;
+  u.plan_nets = plan_nets;
+  if (int rc = conv_layer_plan(u)) return rc;
   D3F_CHECK(stride == 1 || (u.Hv % 2 == 0 && u.Wv % 2 == 0 && u.Ho * 2 == u.Hv && u.Wo * 2 == u.Wv),
             "unit %s: stride-2 conv needs an even extent", conv_name.c_str());
 
@@ -161,151 +163,15 @@ int UnetEngine::add_unit(const std::string& conv_name, const std::string& bn_nam
     u.a = apply ? new_tensor(u.Ho, u.Wo, Cout) : -1;
     u.coef_off = alloc((size_t)7 * Cout * sizeof(float));
   }
-  u.CoutPad = (int)round_up(Cout, 16);
-  u.Kpad = (int)round_up((long)k * k * u.Cin(), bke());
-  u.wf_off = alloc((size_t)u.CoutPad * u.Kpad * wsize());
-  u.CoutD = (int)round_up(Cout, ve());
-  if (u.need_dgrad) {
-    u.KpadD = (int)round_up((long)k * k * u.CoutD, bke());
-    u.CinRows = (int)round_up(u.Cin(), 16);
-    u.wd_off = alloc((size_t)u.CinRows * u.KpadD * wsize());
-  }
-  u.upfold = upfold_applies(dtype, up0, k, stride, pad, u.C0, u.C1);
+  u.wf_off = alloc(u.wf);
+  if (u.need_dgrad) u.wd_off = alloc(u.wd);
   if (u.upfold) {
-    u.C0Rows = (int)round_up(u.C0, 16);
-    u.C1Rows = (int)round_up(u.C1, 16);
-    u.wfc_off = alloc((size_t)4 * u.CoutPad * (4 * u.C0 + 9 * u.C1) * wsize());
-    u.wd4_off = alloc((size_t)u.C0Rows * 16 * u.CoutD * wsize());
-    u.wds_off = alloc((size_t)std::max(1, u.C1Rows) * round_up(9L * u.CoutD, bke()) * wsize());
+    u.wfc_off = alloc(u.wfc);
+    u.wd4_off = alloc(u.wd4);
+    u.wds_off = alloc(std::max(u.wds, (size_t)u.KpadD * wsize()));  // (one row even without a skip tensor)
   }
   units.push_back(u);
   return (int)units.size() - 1;
-}
-
-int UnetEngine::plan_unit(Unit& u) {
-  ConvParams& f = u.fwd;
-  std::memset(&f, 0, sizeof(f));
-  f.B = B; f.Hv = u.Hv; f.Wv = u.Wv; f.C0 = u.C0; f.C1 = u.C1; f.cin_real = u.CinReal;
-  f.H0s = u.Hv >> u.up0; f.W0s = u.Wv >> u.up0; f.shift0 = u.up0; f.zi = 0;
-  f.Ho = u.Ho; f.Wo = u.Wo; f.Cout = u.Cout; f.CoutPad = u.CoutPad; f.Kpad = u.Kpad;
-  f.KH = u.KH; f.KW = u.KW; f.stride = u.stride; f.pad = u.pad;
-  f.M = B * u.Ho * u.Wo;
-  f.mode = u.bn ? CONV_RAW_STATS : CONV_HEAD_NCHW;
-  f.plan_nets = plan_nets;
-  const long rows_full = (long)B * u.Ho * u.Wo;
-  if (u.upfold) {  // rows = one output-parity class; src0 described at its own (low) resolution
-    f.par = 3;
-    f.shift0 = 0;
-    f.Ho = f.H0s; f.Wo = f.W0s;
-    f.M = B * f.H0s * f.W0s;
-    f.Kpad = 4 * u.C0 + 9 * u.C1;
-  }
-  if (int rc = conv_igemm_plan(f, cdtype, true)) return rc;
-  if (conv_splitk_floats(f) * sizeof(float) > splitk_bytes) splitk_bytes = conv_splitk_floats(f) * sizeof(float);
-  const double macs = (double)rows_full * u.Cout * u.KH * u.KW * u.CinReal;  // algorithmic
-  f.flops = 2.0 * macs;
-  fwd_flops += 2.0 * macs;
-  bwd_flops += 2.0 * macs;  // weight gradient
-  u.wino = u.bn && !u.upfold && cdtype == D3F_F32 && conv_winograd_applies(f, cdtype);
-  if (u.wino) {
-    u.wino_rows = conv_winograd_stat_rows(f);
-    u.wu_off = alloc(conv_winograd_filter_floats(f) * sizeof(float));
-  }
-  if (u.bn) {
-    const size_t sb = (size_t)std::max(f.stat_rows, u.wino_rows) * u.CoutPad * 2 * sizeof(float);
-    if (sb > stats_bytes) stats_bytes = sb;
-    const size_t pb = (size_t)bn_bwd_reduce_blocks(rows_full, u.Cout, dtype) * u.Cout * 2 * sizeof(float);
-    if (pb > bnpart_bytes) bnpart_bytes = pb;
-  }
-  const size_t dyb = (size_t)rows_full * u.CoutD * esize();
-  if (dyb > dy_bytes) dy_bytes = dyb;
-  if (!u.apply && u.bn && dyb > dz_bytes) dz_bytes = dyb;
-
-  WgradParams g;
-  std::memset(&g, 0, sizeof(g));
-  g.B = B; g.Hv = u.Hv; g.Wv = u.Wv; g.C0 = u.C0; g.C1 = u.C1;
-  g.H0s = u.Hv >> u.up0; g.W0s = u.Wv >> u.up0; g.shift0 = u.up0;
-  g.Ho = u.Ho; g.Wo = u.Wo; g.Cout = u.CoutD;
-  g.KH = u.KH; g.KW = u.KW; g.stride = u.stride; g.pad = u.pad; g.M = (int)rows_full;
-  g.cin_real = u.CinReal;
-  g.flops = 2.0 * macs;
-  g.plan_nets = plan_nets;
-  if (int rc = wgrad_layer_plan(u.wl, g, dtype)) return rc;
-  u.wclass = u.wl.part[0].part != WG_WHOLE;
-  u.wslab_off = alloc(wgrad_layer_partial_floats(u.wl) * sizeof(float));
-  u.dy_off = alloc(dyb);
-
-  if (u.need_dgrad && u.upfold) {
-    // (1) gradient w.r.t. the low-resolution source: 4x4 stride-2 pad-1 convolution over dY with pre-summed weights
-    ConvParams& l = u.dgrad_lo;
-    std::memset(&l, 0, sizeof(l));
-    l.B = B; l.C0 = u.CoutD; l.C1 = 0;
-    l.Hv = l.H0s = u.Hv; l.Wv = l.W0s = u.Wv;
-    l.Ho = u.Hv / 2; l.Wo = u.Wv / 2;
-    l.Cout = u.C0; l.CoutPad = u.C0Rows; l.Kpad = 16 * u.CoutD;
-    l.KH = l.KW = 4; l.stride = 2; l.pad = 1;
-    l.M = B * l.Ho * l.Wo;
-    l.mode = CONV_DGRAD;
-    l.out_c0 = u.C0;
-    l.plan_nets = plan_nets;
-    if (int rc = conv_igemm_plan(l, cdtype, true)) return rc;
-    if (conv_splitk_floats(l) * sizeof(float) > splitk_bytes) splitk_bytes = conv_splitk_floats(l) * sizeof(float);
-    l.flops = 2.0 * macs * u.C0 / u.Cin();
-    // (2) gradient w.r.t. the skip tensor: an ordinary 3x3 data gradient with C1 outputs
-    ConvParams& d = u.dgrad;
-    std::memset(&d, 0, sizeof(d));
-    if (u.C1 > 0) {
-      d.B = B; d.C0 = u.CoutD; d.C1 = 0;
-      d.Hv = d.H0s = d.Ho = u.Hv; d.Wv = d.W0s = d.Wo = u.Wv;
-      d.Cout = u.C1; d.CoutPad = u.C1Rows; d.Kpad = u.KpadD;
-      d.KH = d.KW = 3; d.stride = 1; d.pad = 1;
-      d.M = (int)rows_full;
-      d.mode = CONV_DGRAD;
-      d.out_c0 = u.C1;
-      d.plan_nets = plan_nets;
-      if (int rc = conv_igemm_plan(d, cdtype, true)) return rc;
-      if (conv_splitk_floats(d) * sizeof(float) > splitk_bytes) splitk_bytes = conv_splitk_floats(d) * sizeof(float);
-      d.flops = 2.0 * macs * u.C1 / u.Cin();
-    }
-    bwd_flops += 2.0 * macs;
-  } else if (u.need_dgrad) {
-    ConvParams& d = u.dgrad;
-    std::memset(&d, 0, sizeof(d));
-    const int s2 = u.stride == 2 ? 1 : 0;
-    D3F_CHECK(s2 || (u.Ho == u.Hv && u.Wo == u.Wv), "unit %s: dgrad expects a 'same' conv",
-              u.conv_name.c_str());
-    d.B = B; d.C0 = u.CoutD; d.C1 = 0;
-    d.Cout = u.Cin(); d.CoutPad = u.CinRows; d.Kpad = u.KpadD;
-    d.mode = CONV_DGRAD;
-    d.plan_nets = plan_nets;
-    d.out_c0 = u.C1 > 0 ? u.C0 : u.Cin();
-    if (parity_dgrad_applies(dtype, u.stride, u.KH, u.pad, u.CoutD, u.C1)) {
-      // stride 2: four plain sub-convolutions over dY, one per output-parity class (conv_igemm.hip)
-      d.par = u.KH == 3 ? 1 : 2;
-      d.Hv = d.Ho = d.H0s = u.Ho; d.Wv = d.Wo = d.W0s = u.Wo;
-      d.KH = d.KW = u.KH == 3 ? 2 : 1; d.stride = 1; d.pad = 0;
-      d.M = B * u.Ho * u.Wo;
-    } else {
-      d.Hv = u.Hv; d.Wv = u.Wv;  // extent of the (zero-inserted) dY == extent of dX
-      d.H0s = u.Ho; d.W0s = u.Wo; d.shift0 = s2; d.zi = s2;
-      d.Ho = u.Hv; d.Wo = u.Wv;
-      d.KH = u.KH; d.KW = u.KW; d.stride = 1; d.pad = u.KH - 1 - u.pad;
-      d.M = B * u.Hv * u.Wv;
-      // a source read through the up-sampling without folded weights (bf16: decoder block 4 conv1): ask for the gradient
-      // at the source's own resolution, 2x2 blocks summed in the epilogue; the plan keeps the request only when a patch
-      // kernel takes the launch (conv_patch.hip), otherwise full-resolution scratch + sum2x2 as before
-      d.sum2 = (u.up0 && u.C1 == 0) ? 1 : 0;
-    }
-    if (int rc = conv_igemm_plan(d, cdtype, true)) return rc;
-    if (conv_splitk_floats(d) * sizeof(float) > splitk_bytes) splitk_bytes = conv_splitk_floats(d) * sizeof(float);
-    d.flops = 2.0 * macs;
-    bwd_flops += 2.0 * macs;
-    if (u.up0 && !d.sum2) {
-      const size_t fb = (size_t)d.M * u.C0 * esize();
-      if (fb > dfull_bytes) dfull_bytes = fb;
-    }
-  }
-  return 0;
 }
 
 int UnetEngine::build(const char* encoder, int in_channels_, int classes_, int B_, int H_, int W_,
@@ -382,8 +248,28 @@ int UnetEngine::build(const char* encoder, int in_channels_, int classes_, int B
   head = add_unit("segmentation_head.0", "", x, -1, 0, classes, 3, 1, 1, false, true, false, false, 0);
   if (head < 0) return head;
 
-  for (auto& u : units)
-    if (int rc = plan_unit(u)) return rc;
+  // the rest of every unit's workspace (behind all the packed weights), FLOP totals and the scratch every unit shares
+  for (Unit& u : units) {
+    const long rows = (long)B * u.Ho * u.Wo;
+    fwd_flops += 2.0 * u.macs;
+    bwd_flops += 2.0 * u.macs;  // weight gradient
+    if (u.need_dgrad) bwd_flops += 2.0 * u.macs;
+    splitk_bytes = std::max(splitk_bytes, u.splitk_floats * sizeof(float));
+    if (u.wino) u.wu_off = alloc(u.wu);
+    if (u.bn) {
+      const int stat_rows = std::max(u.fwd.stat_rows, u.wino ? u.wino_rows : 0);
+      stats_bytes = std::max(stats_bytes, (size_t)stat_rows * u.CoutPad * 2 * sizeof(float));
+      bnpart_bytes = std::max(bnpart_bytes, (size_t)bn_bwd_reduce_blocks(rows, u.Cout, dtype) * u.Cout * 2 * sizeof(float));
+    }
+    const size_t dyb = (size_t)rows * u.CoutD * esize();
+    dy_bytes = std::max(dy_bytes, dyb);
+    if (!u.apply && u.bn) dz_bytes = std::max(dz_bytes, dyb);
+    u.wslab_off = alloc(u.wslab_bytes);
+    u.dy_off = alloc(dyb);
+    // an up-sampled source whose data gradient comes back at full resolution: scratch for the 2x2 sum
+    if (u.need_dgrad && !u.upfold && u.up0 && !u.dgrad.sum2)
+      dfull_bytes = std::max(dfull_bytes, (size_t)u.dgrad.M * u.C0 * esize());
+  }
   for (int ui = 0; ui < (int)units.size() && first_late_unit_ < 0; ++ui)
     if (units[ui].conv_name.rfind("encoder.layer3.", 0) == 0) first_late_unit_ = ui;
   for (int ui = 0; ui < (int)units.size() && first_mid_unit_ < 0; ++ui)
@@ -585,7 +471,6 @@ bool UnetEngine::make_split(const NetIO* io, long in_delta, NetSplit* ns) const 
 int UnetEngine::pack_weights(const float* params0_, void* ws0_, hipStream_t s, const NetIO* io) const {
   D3F_CHECK((int)units.size() <= PACK_MAX_LAYERS, "pack_weights: %d layers exceed the table", (int)units.size());
   D3F_CHECK(nets == 1 || io != nullptr, "pack_weights: a pair engine needs the second network's offsets");
-  const int ve = dtype == D3F_F32 ? 4 : 8;
   static const bool sync_pack = getenv("D3F_NO_ASYNC_PACK") != nullptr;  // debugging knob: everything on the caller's stream
   const bool async = !sync_pack && first_late_unit_ > 0;
   const int mid = async ? first_mid_unit_ : -1;
@@ -607,9 +492,8 @@ int UnetEngine::pack_weights(const float* params0_, void* ws0_, hipStream_t s, c
       if (first_late_unit_ <= 0 && part != 0) continue;
       if (u.upfold) continue;  // packed by pack_up_launch below (none of the plain layouts is read for these layers)
       PackEntry& e = t.e[t.n++];
-      const int CoutD = (int)round_up(u.Cout, ve);
       const long nf = (long)u.CoutPad * u.Kpad, nd = u.need_dgrad ? (long)u.CinRows * u.KpadD : 0;
-      D3F_CHECK(u.Kpad >= u.KH * u.KW * u.Cin() && (!u.need_dgrad || u.KpadD >= u.KH * u.KW * CoutD),
+      D3F_CHECK(u.Kpad >= u.KH * u.KW * u.Cin && (!u.need_dgrad || u.KpadD >= u.KH * u.KW * u.CoutD),
                 "pack_weights: padded K too small");
       D3F_CHECK(u.wf_off % 16 == 0 && u.wd_off % 16 == 0 && (u.wf_off >> 4) < 0xffffffffull &&
                     (u.wd_off >> 4) < 0xffffffffull && nf + nd < 0x7fffffffl && u.Kpad < 65536 && u.KpadD < 65536,
@@ -618,17 +502,17 @@ int UnetEngine::pack_weights(const float* params0_, void* ws0_, hipStream_t s, c
       e.wf_off16 = (uint32_t)(u.wf_off >> 4);
       e.wd_off16 = (uint32_t)(u.wd_off >> 4);
       e.block0 = blocks;
-      e.Cout = (uint16_t)u.Cout; e.CinReal = (uint16_t)u.CinReal; e.Cin = (uint16_t)u.Cin();
+      e.Cout = (uint16_t)u.Cout; e.CinReal = (uint16_t)u.CinReal; e.Cin = (uint16_t)u.Cin;
       e.taps = (uint16_t)(u.KH * u.KW); e.CoutPad = (uint16_t)u.CoutPad; e.Kpad = (uint16_t)u.Kpad;
-      e.CinRows = (uint16_t)u.CinRows; e.CoutD = (uint16_t)CoutD; e.KpadD = (uint16_t)u.KpadD;
+      e.CinRows = (uint16_t)u.CinRows; e.CoutD = (uint16_t)u.CoutD; e.KpadD = (uint16_t)u.KpadD;
       e.has_d = u.need_dgrad ? 1 : 0;
-      e.conv_stride = (u.need_dgrad && u.dgrad.par) ? 2 : 1;
+      e.conv_stride = (u.need_dgrad && u.parity) ? 2 : 1;
       const int taps = u.KH * u.KW;
       D3F_CHECK(taps <= PACK_LDS_ROW, "pack_weights: %d taps exceed the tile", taps);
       int CT = 32;
       while (CT * taps > PACK_LDS_ROW) CT >>= 1;
-      const int crows = std::max(u.Cin(), u.need_dgrad ? u.CinRows : 0);
-      const int nrows = std::max(u.CoutPad, u.need_dgrad ? CoutD : 0);
+      const int crows = std::max(u.Cin, u.need_dgrad ? u.CinRows : 0);
+      const int nrows = std::max(u.CoutPad, u.need_dgrad ? u.CoutD : 0);
       e.CT = (uint16_t)CT;
       {
         unsigned mul, shr;
@@ -659,7 +543,7 @@ int UnetEngine::pack_weights(const float* params0_, void* ws0_, hipStream_t s, c
         const Unit& u = units[ui];
         if (!u.wino) continue;
         if (first_late_unit_ > 0 ? part_of(ui) != part : part != 0) continue;
-        if (int rc = conv_winograd_pack_launch(params_ + u.w_off, reinterpret_cast<float*>(ws + u.wu_off), u.Cout, u.Cin(), ps))
+        if (int rc = conv_winograd_pack_launch(params_ + u.w_off, reinterpret_cast<float*>(ws + u.wu_off), u.Cout, u.Cin, ps))
           return rc;
       }
     }

@@ -180,3 +180,30 @@ def test_plan_counts_at_the_headline_shapes():
     for B, S in ((16, 128), (2, 448)):
         f, d, w = plan(_lib.BF16, B, S)
         assert sum(f[9:13]) == 0 and sum(d[9:13]) == 0 and f[8] == 1 and w[7] == 22
+
+
+def test_plan_counts_and_workspace_of_the_pair_and_f32x3_plans():
+    """The pair plan (two networks, planned together: nets 2, plan_nets 2) at 8x256x256 in fp32 and bf16, and the f32x3
+    single-network plan at 16x256x256: every kernel choice (d3f_unet_plan_counts) and the workspace layout's size and
+    per-network stride, as recorded before the engine and the C API shared one convolution-layer planner."""
+    L = _lib.lib()
+
+    def plan(dtype, B, nets):
+        h = C.c_void_p()
+        assert L.d3f_unet_create_nets(b"resnet34", 3, 3, B, 256, 256, dtype, nets, nets, C.byref(h)) == 0, L.d3f_last_error()
+        f, d, w = (C.c_int32 * 16)(), (C.c_int32 * 16)(), (C.c_int32 * 16)()
+        try:
+            assert L.d3f_unet_plan_counts(h, f, d, w) == 0
+            return list(f), list(d), list(w), L.d3f_unet_workspace_bytes(h), L.d3f_unet_net_workspace_stride(h)
+        finally:
+            L.d3f_unet_destroy(h)
+
+    assert plan(_lib.F32, 8, 2) == ([37, 2, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 7],
+                                    [48, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0],
+                                    [44, 1, 2, 3, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0], 3_620_552_704, 1_810_276_352)
+    assert plan(_lib.BF16, 8, 2) == ([10, 0, 0, 2, 1, 1, 0, 0, 1, 7, 8, 12, 5, 0, 0, 0],
+                                     [10, 0, 0, 1, 2, 0, 1, 1, 0, 8, 9, 13, 5, 0, 0, 0],
+                                     [25, 0, 0, 0, 0, 0, 1, 22, 0, 0, 0, 0, 0, 0, 0, 0], 2_090_164_224, 1_045_082_112)
+    assert plan(_lib.F32X3, 16, 1) == ([47, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0],
+                                       [50, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0],
+                                       [44, 1, 2, 3, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0], 3_479_396_608, 0)
