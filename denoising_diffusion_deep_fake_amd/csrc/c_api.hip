@@ -349,8 +349,18 @@ int d3f_conv_pack_weights(int dtype, const d3f_conv_desc* d, const float* w, voi
     return pack_up_launch(dtype, w, d->Cout, d->C0, d->C1, w_fwd, L.CoutPad, w_dgrad, L.C0Rows, wds, L.C1Rows,
                           (hipStream_t)stream);
   }
-  return pack_weights_launch(dtype, w, d->Cout, d->CinReal, L.Cin, d->KH, d->KW, w_fwd, L.CoutPad, L.Kpad, w_dgrad,
-                             L.CinRows, L.KpadD, L.parity ? 2 : 1, (hipStream_t)stream);
+  // the network's packing kernel, one launch per layout given (each its own buffer); every table entry is filled and
+  // range-checked before the first launch
+  void* const dst[2] = {w_fwd, w_dgrad};
+  PackTable t[2];
+  int blocks[2] = {0, 0};
+  for (int k = 0; k < 2; ++k) {
+    t[k].n = dst[k] != nullptr ? 1 : 0;
+    if (t[k].n && (blocks[k] = conv_pack_entry(L, 0, 0, 0, k == 0, k == 1, 0, t[k].e[0])) < 0) return blocks[k];
+  }
+  for (int k = 0; k < 2; ++k)
+    if (int rc = pack_all_launch(dtype, w, dst[k], t[k], blocks[k], (hipStream_t)stream)) return rc;
+  return 0;
 }
 int d3f_conv_upsample_folded(int dtype, const d3f_conv_desc* d) {
   ConvLayer L;
@@ -378,10 +388,10 @@ int d3f_conv_forward(int dtype, const d3f_conv_desc* d, const void* src0, const 
   if (int rc = plan(L, dtype, d, PLAN_FWD | (workspace ? PLAN_SPLITK : 0))) return rc;
   if (d->B == 0) return 0;  // empty batch: nothing to compute (an empty tensor has a null data pointer)
   D3F_CHECK(src0 && w_fwd && y && (d->C1 == 0 || src1), "conv_forward: null argument");
-  ConvParams p = L.fwd;
-  p.src0 = src0; p.src1 = src1; p.w = w_fwd; p.out0 = y; p.stats = stats;
-  p.partial = p.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
-  return conv_igemm_launch(p, dtype, (hipStream_t)stream);
+  ConvFwdBufs b;
+  b.src0 = src0; b.src1 = src1; b.w = w_fwd; b.out = y; b.stats = stats;
+  b.slabs = reinterpret_cast<float*>(workspace);
+  return conv_layer_forward(L, b, false, (hipStream_t)stream);
 }
 // ---- Winograd F(2x2, 3x3) form of a stride-1 3x3 fp32 layer on its own (conv_winograd.hip) ----
 // (the layer planned as fp32 with its Winograd sizes filled, i.e. the kernel fits it)
@@ -421,14 +431,14 @@ int d3f_conv_winograd_forward(const d3f_conv_desc* d, const void* src0, const vo
   D3F_CHECK(src0 && u && y && ((scale == nullptr) == (shift == nullptr)), "conv_winograd_forward: null argument");
   D3F_CHECK(scale != nullptr || (residual == nullptr && relu == 0),
             "conv_winograd_forward: residual / ReLU belong to the eval epilogue (scale and shift)");
-  ConvParams p = L.fwd;
-  p.src0 = src0; p.w = u; p.out0 = y;
+  ConvFwdBufs b;
+  b.src0 = src0; b.w = u; b.out = y;
   if (scale != nullptr) {
-    p.mode = CONV_EVAL_FUSED; p.scale = scale; p.shift = shift; p.res = residual; p.relu = relu ? 1 : 0;
+    b.scale = scale; b.shift = shift; b.res = residual; b.relu = relu ? 1 : 0;
   } else {
-    p.stats = stats; p.stat_rows = L.wino_rows;
+    b.stats = stats;
   }
-  return conv_winograd_launch(p, (hipStream_t)stream);
+  return conv_layer_forward(L, b, true, (hipStream_t)stream);
 }
 int d3f_conv_backward_data(int dtype, const d3f_conv_desc* d, const void* dy, const void* w_dgrad,
                            void* dx0, void* dx1, int acc0, int acc1, void* workspace, void* stream) {
@@ -437,25 +447,12 @@ int d3f_conv_backward_data(int dtype, const d3f_conv_desc* d, const void* dy, co
   if (int rc = plan(L, dtype, d, PLAN_DGRAD | sum2 | (workspace ? PLAN_SPLITK : 0))) return rc;
   if (d->B == 0) return 0;
   D3F_CHECK(dy && w_dgrad && dx0 && (d->C1 == 0 || dx1), "conv_backward_data: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  if (L.upfold) {
-    // dx0 = gradient of the LOW-resolution source [B][H/2][W/2][C0], dx1 = gradient of the skip tensor
-    ConvParams lo = L.dgrad_lo;
-    lo.src0 = dy; lo.w = w_dgrad; lo.out0 = dx0; lo.acc0 = acc0;
-    lo.partial = lo.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
-    if (int rc = conv_igemm_launch(lo, dtype, s)) return rc;
-    if (d->C1 == 0) return 0;
-    ConvParams sk = L.dgrad;
-    sk.src0 = dy; sk.w = reinterpret_cast<const char*>(w_dgrad) + L.wd4; sk.out0 = dx1; sk.acc0 = acc1;
-    sk.partial = sk.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
-    return conv_igemm_launch(sk, dtype, s);
-  }
-  ConvParams p = L.dgrad;
-  p.src0 = dy; p.w = w_dgrad; p.out0 = dx0; p.out1 = dx1; p.acc0 = acc0; p.acc1 = acc1;
-  p.partial = p.splitk > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
-  if (p.par == 2 && !acc0)  // 1x1 stride 2: only even pixels receive a gradient; the others are zero
-    D3F_HIP(hipMemsetAsync(dx0, 0, (size_t)4 * p.M * p.Cout * (L.sdtype == D3F_F32 ? 4 : 2), s));
-  return conv_igemm_launch(p, dtype, s);
+  // an up-folded layer: dx0 = gradient of the LOW-resolution source [B][H/2][W/2][C0], w_dgrad = [wd4 | wds]
+  ConvDgradBufs b;
+  b.dy = dy; b.w = w_dgrad; b.dx0 = dx0; b.dx1 = dx1; b.acc0 = acc0; b.acc1 = acc1;
+  b.w_skip = L.upfold ? reinterpret_cast<const char*>(w_dgrad) + L.wd4 : nullptr;
+  b.slabs = reinterpret_cast<float*>(workspace);
+  return conv_layer_dgrad(L, b, (hipStream_t)stream);
 }
 size_t d3f_conv_backward_weight_workspace_bytes(int dtype, const d3f_conv_desc* d) {
   ConvLayer L;

@@ -418,4 +418,45 @@ struct ConvLayer {
 };
 int conv_layer_plan(ConvLayer& L);
 
+// The launches of a planned layer (conv_plan.hip), issued the same way for the engine and the C API.  The buffers are net
+// 0's; ns (two networks in one launch) makes net 1 shift them (ConvParams::net_*).
+struct ConvFwdBufs {
+  const void* src0 = nullptr;
+  const void* src1 = nullptr;
+  const void* w = nullptr;       // packed forward weights, or the Winograd filters (wino)
+  void* out = nullptr;           // NHWC output; the head: the NCHW fp32 prediction
+  float* stats = nullptr;        // train mode: (sum, sum of squares) rows, or null
+  const float* bias = nullptr;   // the head
+  const float* scale = nullptr;  // eval mode (scale given): y * scale + shift (+ res) (ReLU), the BatchNorm folded in
+  const float* shift = nullptr;
+  const void* res = nullptr;
+  int relu = 0;
+  float* slabs = nullptr;        // split-K slabs (splitk_floats): train and eval mode
+};
+// head: CONV_HEAD_NCHW + bias; eval: CONV_EVAL_FUSED; train: CONV_RAW_STATS.  wino: as Winograd F(2x2, 3x3) (the train
+// mode then writes wino_rows statistics rows)
+int conv_layer_forward(const ConvLayer& L, const ConvFwdBufs& b, bool wino, hipStream_t s, const NetSplit* ns = nullptr);
+struct ConvDgradBufs {
+  const void* dy = nullptr;      // [B][Ho][Wo][CoutD]
+  const void* w = nullptr;       // packed data-gradient weights (an up-folded layer: wd4)
+  const void* w_skip = nullptr;  // an up-folded layer's skip-tensor weights (wds)
+  void* dx0 = nullptr;           // gradient of src0 (an up-folded layer: at src0's own low resolution)
+  void* dx1 = nullptr;           // gradient of src1
+  int acc0 = 0, acc1 = 0;        // accumulate into dx0 / dx1
+  float* slabs = nullptr;
+  // optional: the BatchNorm-backward reduction of the layer that consumes dx0, fused into the epilogue (ConvParams::bn_*)
+  const void* bn_y = nullptr;
+  const float* bn_coef = nullptr;
+  float* bn_partial = nullptr;
+  const void* bn_a = nullptr;
+};
+// a plain or parity layer: one launch; an up-folded layer: dgrad_lo (dx0), then dgrad (dx1) when it has a skip tensor
+int conv_layer_dgrad(const ConvLayer& L, const ConvDgradBufs& b, hipStream_t s, const NetSplit* ns = nullptr);
+// Fills the pack_all_launch table entry (pointwise.h) of a planned layer's plain layouts: forward (fwd) at wf_off, data
+// gradient (dgrad) at wd_off, bytes into the launch's workspace; w_off: floats into its parameters; block0: the entry's
+// first block.  Returns the entry's block count, or < 0 for a layer beyond the table's range.
+struct PackEntry;
+int conv_pack_entry(const ConvLayer& L, long w_off, size_t wf_off, size_t wd_off, bool fwd, bool dgrad, uint32_t block0,
+                    PackEntry& e);
+
 }  // namespace d3f

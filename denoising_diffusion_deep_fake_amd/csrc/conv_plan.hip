@@ -1,8 +1,9 @@
 // One convolution layer planned once (host only): the geometry, the kernel-form decisions, the launch descriptions and the
-// packed sizes that the whole-network engine (engine.hip) and the single-operator C API (c_api.hip) both read.  Which
-// dtype each rule sees is decided here and nowhere else: the layouts, the folding and the parity rule follow the storage
-// dtype, the contraction plans and Winograd the compute dtype (D3F_F32X3 keeps fp32 storage).
-#include "common.h"
+// packed sizes that the whole-network engine (engine.hip) and the single-operator C API (c_api.hip) both read -- and the
+// launches of the planned layer, which both issue through this file too.  Which dtype each rule sees is decided here and
+// nowhere else: the layouts, the folding and the parity rule follow the storage dtype, the contraction plans and Winograd
+// the compute dtype (D3F_F32X3 keeps fp32 storage).
+#include "pointwise.h"
 
 #include <algorithm>
 
@@ -142,6 +143,105 @@ int conv_layer_plan(ConvLayer& L) {
     d.sum2 = (L.want_sum2 && L.up0 && L.C1 == 0) ? 1 : 0;
   }
   return plan(d, 2.0 * L.macs);
+}
+
+// two networks in one launch: every pointer of net 1 lies net_ws further on (the head's exceptions: conv_layer_forward)
+static void net_conv(ConvParams& p, const NetSplit* ns) {
+  if (ns != nullptr) {
+    p.nets = ns->nets;
+    p.net_ws = p.net_out0 = p.net_scale = ns->ws;
+  }
+}
+
+int conv_layer_forward(const ConvLayer& L, const ConvFwdBufs& b, bool wino, hipStream_t s, const NetSplit* ns) {
+  ConvParams p = L.fwd;
+  p.src0 = b.src0; p.src1 = b.src1; p.w = b.w; p.out0 = b.out;
+  net_conv(p, ns);
+  if (L.head) {
+    p.mode = CONV_HEAD_NCHW;
+    p.scale = b.bias;
+    if (ns != nullptr) {  // the prediction and the bias live outside the workspace
+      p.net_out0 = ns->out;
+      p.net_scale = ns->par;
+    }
+    return conv_igemm_launch(p, L.dtype, s);
+  }
+  p.partial = p.splitk > 1 ? b.slabs : nullptr;
+  if (b.scale != nullptr) {
+    p.mode = CONV_EVAL_FUSED;
+    p.scale = b.scale; p.shift = b.shift; p.res = b.res; p.relu = b.relu;
+  } else {
+    p.mode = CONV_RAW_STATS;
+    p.stats = b.stats;
+    if (wino) p.stat_rows = L.wino_rows;  // one statistics row per workgroup
+  }
+  return wino ? conv_winograd_launch(p, s) : conv_igemm_launch(p, L.dtype, s);
+}
+
+int conv_layer_dgrad(const ConvLayer& L, const ConvDgradBufs& b, hipStream_t s, const NetSplit* ns) {
+  // the launch that writes dx0 (it alone carries the fused reduction)
+  ConvParams p = L.upfold ? L.dgrad_lo : L.dgrad;
+  p.src0 = b.dy; p.w = b.w; p.out0 = b.dx0; p.acc0 = b.acc0;
+  if (!L.upfold) {
+    p.out1 = b.dx1;
+    p.acc1 = b.acc1;
+  }
+  p.partial = p.splitk > 1 ? b.slabs : nullptr;
+  p.bn_y = b.bn_y; p.bn_coef = b.bn_coef; p.bn_partial = b.bn_partial; p.bn_a = b.bn_a;
+  net_conv(p, ns);
+  if (p.par == 2 && !p.acc0) {  // 1x1 stride 2: only even pixels receive a gradient; the others are zero
+    const NetSplit nv = net_split_or_single(ns);
+    for (int n = 0; n < nv.nets; ++n)
+      D3F_HIP(hipMemsetAsync(reinterpret_cast<char*>(b.dx0) + (size_t)n * nv.ws, 0,
+                             (size_t)4 * p.M * p.Cout * (L.sdtype == D3F_F32 ? 4 : 2), s));
+  }
+  if (int rc = conv_igemm_launch(p, L.dtype, s)) return rc;
+  if (!L.upfold || L.C1 == 0) return 0;
+  // an up-folded layer's skip tensor: an ordinary 3x3 data gradient of its own
+  ConvParams k = L.dgrad;
+  k.src0 = b.dy; k.w = b.w_skip; k.out0 = b.dx1; k.acc0 = b.acc1;
+  k.partial = k.splitk > 1 ? b.slabs : nullptr;
+  net_conv(k, ns);
+  return conv_igemm_launch(k, L.dtype, s);
+}
+
+int conv_pack_entry(const ConvLayer& L, long w_off, size_t wf_off, size_t wd_off, bool fwd, bool dgrad, uint32_t block0,
+                    PackEntry& e) {
+  const int taps = L.KH * L.KW;
+  const long nf = fwd ? (long)L.CoutPad * L.Kpad : 0, nd = dgrad ? (long)L.CinRows * L.KpadD : 0;
+  D3F_CHECK((!fwd || L.Kpad >= taps * L.Cin) && (!dgrad || L.KpadD >= taps * L.CoutD), "pack_weights: padded K too small");
+  // 16-bit extents, 32-bit element indices (pack_all_kernel)
+  const int extent = std::max({L.Cout, L.CinReal, L.Cin, L.CoutPad, L.Kpad, L.CinRows, L.CoutD, L.KpadD});
+  D3F_CHECK(extent < 65536 && nf + nd < 0x7fffffffL,
+            "pack_weights: the layer exceeds the packing table (extents below 65536, fewer than 2^31 packed elements): "
+            "extent %d, %ld elements", extent, nf + nd);
+  D3F_CHECK(w_off >= 0 && w_off <= 0xffffffffL && wf_off % 16 == 0 && wd_off % 16 == 0 && (wf_off >> 4) < 0xffffffffull &&
+                (wd_off >> 4) < 0xffffffffull,
+            "pack_weights: layer out of table range");
+  D3F_CHECK(taps <= PACK_LDS_ROW, "pack_weights: %d taps exceed the tile", taps);
+  int CT = 32;
+  while (CT * taps > PACK_LDS_ROW) CT >>= 1;
+  const int crows = std::max(fwd ? L.Cin : 0, dgrad ? L.CinRows : 0);
+  const int nrows = std::max(fwd ? L.CoutPad : 0, dgrad ? L.CoutD : 0);
+  unsigned mul, shr;
+  fast_div_setup((unsigned)taps, &mul, &shr);
+  e = PackEntry{};
+  e.w_off = (uint32_t)w_off;
+  e.wf_off16 = (uint32_t)(wf_off >> 4);
+  e.wd_off16 = (uint32_t)(wd_off >> 4);
+  e.block0 = block0;
+  e.Cout = (uint16_t)L.Cout; e.CinReal = (uint16_t)L.CinReal; e.Cin = (uint16_t)L.Cin;
+  e.taps = (uint16_t)taps; e.CoutPad = (uint16_t)L.CoutPad; e.Kpad = (uint16_t)L.Kpad;
+  e.CinRows = (uint16_t)L.CinRows; e.CoutD = (uint16_t)L.CoutD; e.KpadD = (uint16_t)L.KpadD;
+  e.has_f = fwd ? 1 : 0;
+  e.has_d = dgrad ? 1 : 0;
+  e.conv_stride = (dgrad && L.parity) ? 2 : 1;
+  e.CT = (uint16_t)CT;
+  e.ctiles = (uint16_t)((crows + CT - 1) / CT);
+  e.taps_mul = mul;
+  e.taps_shr = (uint16_t)shr;
+  e.ct_log2 = (uint16_t)__builtin_ctz((unsigned)CT);
+  return e.ctiles * ((nrows + PACK_NT - 1) / PACK_NT);
 }
 
 }  // namespace d3f

@@ -187,12 +187,6 @@ class UnetEngine {
                    const NetSplit* ns = nullptr) const;
   // what a launch of this engine hands to the kernels: null for a single network
   bool make_split(const NetIO* io, long in_delta, NetSplit* ns) const;
-  static void net_conv(ConvParams& p, const NetSplit* ns) {
-    if (ns != nullptr) {
-      p.nets = ns->nets;
-      p.net_ws = p.net_out0 = p.net_scale = ns->ws;
-    }
-  }
   int predict_u8_launches(const float* params, float* bnstats, const uint8_t* bgr_in, uint8_t* bgr_out,
                           const float mean255[3], const float std255[3], char* ws, hipStream_t s) const;
   // captured graphs: one slot per entry point; a slot is re-captured when the pointers / constants it baked in change

@@ -491,38 +491,9 @@ int UnetEngine::pack_weights(const float* params0_, void* ws0_, hipStream_t s, c
       if (first_late_unit_ > 0 && part_of(ui) != part) continue;
       if (first_late_unit_ <= 0 && part != 0) continue;
       if (u.upfold) continue;  // packed by pack_up_launch below (none of the plain layouts is read for these layers)
-      PackEntry& e = t.e[t.n++];
-      const long nf = (long)u.CoutPad * u.Kpad, nd = u.need_dgrad ? (long)u.CinRows * u.KpadD : 0;
-      D3F_CHECK(u.Kpad >= u.KH * u.KW * u.Cin && (!u.need_dgrad || u.KpadD >= u.KH * u.KW * u.CoutD),
-                "pack_weights: padded K too small");
-      D3F_CHECK(u.wf_off % 16 == 0 && u.wd_off % 16 == 0 && (u.wf_off >> 4) < 0xffffffffull &&
-                    (u.wd_off >> 4) < 0xffffffffull && nf + nd < 0x7fffffffl && u.Kpad < 65536 && u.KpadD < 65536,
-                "pack_weights: layer out of table range");
-      e.w_off = (uint32_t)u.w_off;
-      e.wf_off16 = (uint32_t)(u.wf_off >> 4);
-      e.wd_off16 = (uint32_t)(u.wd_off >> 4);
-      e.block0 = blocks;
-      e.Cout = (uint16_t)u.Cout; e.CinReal = (uint16_t)u.CinReal; e.Cin = (uint16_t)u.Cin;
-      e.taps = (uint16_t)(u.KH * u.KW); e.CoutPad = (uint16_t)u.CoutPad; e.Kpad = (uint16_t)u.Kpad;
-      e.CinRows = (uint16_t)u.CinRows; e.CoutD = (uint16_t)u.CoutD; e.KpadD = (uint16_t)u.KpadD;
-      e.has_d = u.need_dgrad ? 1 : 0;
-      e.conv_stride = (u.need_dgrad && u.parity) ? 2 : 1;
-      const int taps = u.KH * u.KW;
-      D3F_CHECK(taps <= PACK_LDS_ROW, "pack_weights: %d taps exceed the tile", taps);
-      int CT = 32;
-      while (CT * taps > PACK_LDS_ROW) CT >>= 1;
-      const int crows = std::max(u.Cin, u.need_dgrad ? u.CinRows : 0);
-      const int nrows = std::max(u.CoutPad, u.need_dgrad ? u.CoutD : 0);
-      e.CT = (uint16_t)CT;
-      {
-        unsigned mul, shr;
-        fast_div_setup((unsigned)taps, &mul, &shr);
-        e.taps_mul = mul;
-        e.taps_shr = (uint16_t)shr;
-        e.ct_log2 = (uint16_t)__builtin_ctz((unsigned)CT);
-      }
-      e.ctiles = (uint16_t)((crows + CT - 1) / CT);
-      blocks += (uint32_t)e.ctiles * (uint32_t)((nrows + PACK_NT - 1) / PACK_NT);
+      const int nb = conv_pack_entry(u, u.w_off, u.wf_off, u.wd_off, true, u.need_dgrad, blocks, t.e[t.n++]);
+      if (nb < 0) return nb;
+      blocks += (uint32_t)nb;
     }
     hipStream_t ps = s;
     if (part >= 1 && async) {
@@ -625,39 +596,29 @@ int UnetEngine::forward_body(const float* params_, float* bnstats, float* out, c
       D3F_HIP(hipStreamWaitEvent(s, ev_pack_done_, 0));
       pack_pending_ = false;
     }
-    ConvParams p = u.fwd;
-    p.src0 = T(u.in0);
-    p.src1 = u.in1 >= 0 ? T(u.in1) : nullptr;
-    p.w = ws + (u.upfold ? u.wfc_off : u.wf_off);
-    net_conv(p, ns);
+    ConvFwdBufs b;
+    b.src0 = T(u.in0);
+    b.src1 = u.in1 >= 0 ? T(u.in1) : nullptr;
+    // Winograd F(2x2, 3x3): its own filter layout
+    b.w = ws + (u.wino ? u.wu_off : u.upfold ? u.wfc_off : u.wf_off);
+    b.slabs = reinterpret_cast<float*>(ws + splitk_off);
     if (!u.bn) {  // segmentation head
-      p.mode = CONV_HEAD_NCHW;
-      p.out0 = out;
-      p.scale = params_ + u.bias_off;
-      if (ns != nullptr) {  // the prediction and the bias live outside the workspace
-        p.net_out0 = ns->out;
-        p.net_scale = ns->par;
-      }
-      if (int rc = conv_igemm_launch(p, cdtype, s)) return rc;
+      b.out = out;
+      b.bias = params_ + u.bias_off;
+      if (int rc = conv_layer_forward(u, b, false, s, ns)) return rc;
       continue;
     }
     const Unit* ds = u.res_unit >= 0 ? &units[u.res_unit] : nullptr;
     if (training) {
-      p.mode = CONV_RAW_STATS;
-      p.out0 = T(u.y);
-      p.stats = reinterpret_cast<float*>(ws + stats_off);
-      p.partial = p.splitk > 1 ? reinterpret_cast<float*>(ws + splitk_off) : nullptr;
-      if (u.wino) {  // Winograd F(2x2, 3x3): its own filter layout and one statistics row per workgroup
-        p.w = ws + u.wu_off;
-        p.stat_rows = u.wino_rows;
-        if (int rc = conv_winograd_launch(p, s)) return rc;
-      } else if (int rc = conv_igemm_launch(p, cdtype, s)) {
-        return rc;
-      }
-      const long rows = (long)B * u.Ho * u.Wo;  // (p.M counts one output-parity class for a folded layer)
+      float* stats = reinterpret_cast<float*>(ws + stats_off);
+      const int stat_rows = u.wino ? u.wino_rows : u.fwd.stat_rows;  // (Winograd: one per workgroup)
+      b.out = T(u.y);
+      b.stats = stats;
+      if (int rc = conv_layer_forward(u, b, u.wino, s, ns)) return rc;
+      const long rows = (long)B * u.Ho * u.Wo;  // (fwd.M counts one output-parity class for a folded layer)
       const bool sync = bn_sync_fn_ != nullptr;
       if (sync) {  // statistics over every rank's batch: the partial rows are summed across ranks in place
-        if (int rc = bn_sync_fn_(bn_sync_ctx_, p.stats, (int64_t)p.stat_rows * u.CoutPad * 2, (void*)s))
+        if (int rc = bn_sync_fn_(bn_sync_ctx_, stats, (int64_t)stat_rows * u.CoutPad * 2, (void*)s))
           return set_error(rc, "BatchNorm statistics all-reduce failed in the forward pass (%s)", u.bn_name.c_str());
       }
       const long count = rows * (sync ? bn_sync_world_ : 1);
@@ -667,16 +628,16 @@ int UnetEngine::forward_body(const float* params_, float* bnstats, float* out, c
       // of "apply the two coefficients in the consumer's patch staging instead"  before any consumer cost
       static const bool abl_fbn = getenv("D3F_ABLATE_FWD_BN") != nullptr;
       if (abl_fbn && !sync && u.apply && u.res_tensor < 0 && ds == nullptr) {
-        if (int rc = bn_finalize_launch(p.stats, p.stat_rows, u.Cout, u.CoutPad, count, params_ + u.g_off, params_ + u.b_off,
+        if (int rc = bn_finalize_launch(stats, stat_rows, u.Cout, u.CoutPad, count, params_ + u.g_off, params_ + u.b_off,
                                         1e-5f, 0.1f, bnstats + u.rm_off, bnstats + u.rv_off, coef_ptr(ws, u, 0),
                                         coef_ptr(ws, u, 1), coef_ptr(ws, u, 2), coef_ptr(ws, u, 3), s, ns))
           return rc;
         continue;
       }
 #endif
-      if (!sync && u.apply && bn_fused_finalize_ok(dtype, p.stat_rows, u.Cout)) {
+      if (!sync && u.apply && bn_fused_finalize_ok(dtype, stat_rows, u.Cout)) {
         // finalize folded into the streaming pass (bn_fused.hip): one launch instead of two
-        if (int rc = bn_finalize_apply_launch(dtype, p.stats, p.stat_rows, u.Cout, u.CoutPad, rows, params_ + u.g_off,
+        if (int rc = bn_finalize_apply_launch(dtype, stats, stat_rows, u.Cout, u.CoutPad, rows, params_ + u.g_off,
                                               params_ + u.b_off, 1e-5f, 0.1f, bnstats + u.rm_off, bnstats + u.rv_off,
                                               coef_ptr(ws, u, 0), coef_ptr(ws, u, 1), coef_ptr(ws, u, 2),
                                               coef_ptr(ws, u, 3), T(u.y),
@@ -686,7 +647,7 @@ int UnetEngine::forward_body(const float* params_, float* bnstats, float* out, c
           return rc;
         continue;
       }
-      if (int rc = bn_finalize_launch(p.stats, p.stat_rows, u.Cout, u.CoutPad, count,
+      if (int rc = bn_finalize_launch(stats, stat_rows, u.Cout, u.CoutPad, count,
                                       params_ + u.g_off, params_ + u.b_off, 1e-5f, 0.1f,
                                       bnstats + u.rm_off, bnstats + u.rv_off, coef_ptr(ws, u, 0),
                                       coef_ptr(ws, u, 1), coef_ptr(ws, u, 2), coef_ptr(ws, u, 3), s, ns))
@@ -700,24 +661,16 @@ int UnetEngine::forward_body(const float* params_, float* bnstats, float* out, c
           return rc;
       }
     } else {
-      p.mode = CONV_EVAL_FUSED;
-      p.scale = coef_ptr(ws, u, 2);
-      p.shift = coef_ptr(ws, u, 3);
-      p.relu = u.relu ? 1 : 0;
-      p.partial = p.splitk > 1 ? reinterpret_cast<float*>(ws + splitk_off) : nullptr;  // small batches: split K
+      b.scale = coef_ptr(ws, u, 2);
+      b.shift = coef_ptr(ws, u, 3);
+      b.relu = u.relu ? 1 : 0;
       if (u.apply) {
-        p.out0 = T(u.a);
-        p.res = u.res_tensor >= 0 ? T(u.res_tensor) : (ds ? T(ds->y) : nullptr);
+        b.out = T(u.a);
+        b.res = u.res_tensor >= 0 ? T(u.res_tensor) : (ds ? T(ds->y) : nullptr);
       } else {
-        p.out0 = T(u.y);  // downsample branch: bn(conv(x)) lands in its y slot
-        p.res = nullptr;
+        b.out = T(u.y);  // downsample branch: bn(conv(x)) lands in its y slot
       }
-      if (u.wino) {
-        p.w = ws + u.wu_off;
-        if (int rc = conv_winograd_launch(p, s)) return rc;
-      } else if (int rc = conv_igemm_launch(p, cdtype, s)) {
-        return rc;
-      }
+      if (int rc = conv_layer_forward(u, b, u.wino, s, ns)) return rc;
     }
   }
   return 0;
@@ -1072,57 +1025,24 @@ int UnetEngine::backward(const float* params_, const float* dout, float* grads, 
       if ((int)pending.size() >= defer)
         if (int rc = flush_pending()) return rc;
     }
-    // data gradient (main stream)
-    if (u.need_dgrad && !skip_d && u.upfold) {
-      // up-sampling folded into the weights: the gradient of the low-resolution source is a 4x4 stride-2 convolution
-      // over dY written at its own resolution (it feeds the next BatchNorm backward: first), the skip tensor's
-      // gradient an ordinary 3x3 data gradient
-      ConvParams l = u.dgrad_lo;
-      l.src0 = dy;
-      l.w = ws + u.wd4_off;
-      l.out0 = G(op.dst0);
-      l.acc0 = op.acc0 ? 1 : 0;
-      l.partial = l.splitk > 1 ? reinterpret_cast<float*>(ws + splitk_off) : nullptr;
-      net_conv(l, ns);
-      if (op.fuse_for_unit >= 0) {
-        const Unit& uc = units[op.fuse_for_unit];
-        l.bn_y = T(uc.y);
-        l.bn_coef = coef_ptr(ws, uc, 0);
-        l.bn_partial = reinterpret_cast<float*>(ws + bnpart_off);
-        l.bn_a = (uc.res_tensor >= 0 || uc.res_unit >= 0) ? T(uc.a) : nullptr;
-      }
-      if (int rc = conv_igemm_launch(l, cdtype, s)) return rc;
-      if (op.dst1 >= 0) {
-        // the skip tensor's gradient (not read before the encoder stages; a third stream for these launches was measured
-        // 1 % slower -- MFMA-bound work next to the chain's own kernels -- profiles/README.md round 2)
-        ConvParams d = u.dgrad;
-        d.src0 = dy;
-        d.w = ws + u.wds_off;
-        d.out0 = G(op.dst1);
-        d.acc0 = op.acc1 ? 1 : 0;
-        d.partial = d.splitk > 1 ? reinterpret_cast<float*>(ws + splitk_off) : nullptr;
-        net_conv(d, ns);
-        if (int rc = conv_igemm_launch(d, cdtype, s)) return rc;
-      }
-    } else if (u.need_dgrad && !skip_d) {
-      ConvParams d = u.dgrad;
-      d.src0 = dy;
-      d.w = ws + u.wd_off;
+    // data gradient (main stream).  An up-folded layer: the gradient of the low-resolution source is a 4x4 stride-2
+    // convolution over dY written at its own resolution (it feeds the next BatchNorm backward: first), then the skip
+    // tensor's (not read before the encoder stages; a third stream for these launches was measured 1 % slower --
+    // MFMA-bound work next to the chain's own kernels -- profiles/README.md round 2)
+    if (u.need_dgrad && !skip_d) {
+      ConvDgradBufs d;
+      d.dy = dy;
+      d.w = ws + (u.upfold ? u.wd4_off : u.wd_off);
+      d.w_skip = ws + u.wds_off;
       if (op.dst0_is_full_scratch) {
-        d.out0 = ws + dfull_off;
-        d.acc0 = 0;
+        d.dx0 = ws + dfull_off;
       } else {
-        d.out0 = G(op.dst0);
+        d.dx0 = G(op.dst0);
         d.acc0 = op.acc0 ? 1 : 0;
       }
-      d.out1 = op.dst1 >= 0 ? G(op.dst1) : nullptr;
+      d.dx1 = op.dst1 >= 0 ? G(op.dst1) : nullptr;
       d.acc1 = op.acc1 ? 1 : 0;
-      d.partial = d.splitk > 1 ? reinterpret_cast<float*>(ws + splitk_off) : nullptr;
-      net_conv(d, ns);
-      if (d.par == 2 && !d.acc0)  // 1x1 stride 2: only even pixels receive a gradient; the others are zero
-        for (int n = 0; n < nets; ++n)
-          D3F_HIP(hipMemsetAsync(reinterpret_cast<char*>(d.out0) + (size_t)n * net_ws_stride, 0,
-                                 (size_t)4 * d.M * d.Cout * esize(), s));
+      d.slabs = reinterpret_cast<float*>(ws + splitk_off);
       if (op.fuse_for_unit >= 0) {
         const Unit& uc = units[op.fuse_for_unit];
         d.bn_y = T(uc.y);
@@ -1130,7 +1050,7 @@ int UnetEngine::backward(const float* params_, const float* dout, float* grads, 
         d.bn_partial = reinterpret_cast<float*>(ws + bnpart_off);
         d.bn_a = (uc.res_tensor >= 0 || uc.res_unit >= 0) ? T(uc.a) : nullptr;
       }
-      if (int rc = conv_igemm_launch(d, cdtype, s)) return rc;
+      if (int rc = conv_layer_dgrad(u, d, s, ns)) return rc;
     }
   }
   if (int rc = flush_pending()) return rc;

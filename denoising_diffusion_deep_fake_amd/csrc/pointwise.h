@@ -14,11 +14,8 @@ int bn_finalize_launch(const float* stats, int tiles, int C, int Cpad, long coun
                        const float* gamma, const float* beta, float eps, float momentum,
                        float* running_mean, float* running_var, float* mean, float* invstd,
                        float* scale, float* shift, hipStream_t stream, const NetSplit* ns = nullptr);
-// eval mode: scale/shift from the running statistics
-int bn_eval_coeff_launch(const float* gamma, const float* beta, const float* running_mean,
-                         const float* running_var, float eps, int C, float* scale, float* shift,
-                         hipStream_t stream);
-// the same for every BatchNorm of a network in one launch: scale -> coef[2*C..], shift -> coef[3*C..]
+// eval mode: scale / shift from the running statistics, every BatchNorm of a network in one launch: scale -> coef[2*C..],
+// shift -> coef[3*C..]
 struct BnEvalEntry {
   uint32_t g_off, b_off, rm_off, rv_off;  // floats into params / bnstats
   uint32_t coef_off16;                     // 16-byte units into the workspace
@@ -93,19 +90,15 @@ int affine_warp_launch(const float* in, const float* theta, float* out, int B, i
                        hipStream_t stream);
 
 // ---- weights -------------------------------------------------------------------------------
-// PyTorch [Cout][CinReal][KH][KW] fp32 -> forward pack [CoutPad][Kpad] (k = tap*Cin + c) and/or
-// data-gradient pack [CinPadRows][KpadD] (k = flipped tap*Cout + co); T = dtype.
-int pack_weights_launch(int dtype, const float* w, int Cout, int CinReal, int Cin, int KH, int KW,
-                        void* wf, int CoutPad, int Kpad, void* wd, int CinRows, int KpadD, int stride,
-                        hipStream_t stream);
-
 // conv(cat(upsample2x(x), skip)) with the up-sampling folded into pre-summed weights (pointwise.hip): per-class
 // forward matrices wfc [4][CoutPad][4*C0 + 9*C1], the 4x4 stride-2 data-gradient matrix wd4 [C0Rows][16*CoutD]
 // (gradient w.r.t. the low-resolution source) and the skip tensor's 3x3 data-gradient matrix wds [C1Rows][9*CoutD]
 int pack_up_launch(int dtype, const float* w, int Cout, int C0, int C1, void* wfc, int CoutPad, void* wd4,
                    int C0Rows, void* wds, int C1Rows, hipStream_t stream);
 
-// every layer of a network in one launch (engine): table passed by value as a kernel argument
+// PyTorch [Cout][CinReal][KH][KW] fp32 -> forward layout [CoutPad][Kpad] (k = tap*Cin + c) and / or data-gradient layout
+// [CinRows][KpadD] (k = flipped tap*CoutD + co), T = dtype: every layer of a network in one launch (engine), or one layout
+// of one layer (C API).  The table is passed by value as a kernel argument; conv_pack_entry (conv_plan.hip) fills entries.
 constexpr int PACK_NT = 32;        // filters per tile
 constexpr int PACK_LDS_ROW = 288;  // floats per filter in a tile: CT channels x taps  (32 x 9)
 struct PackEntry {
@@ -114,7 +107,7 @@ struct PackEntry {
   uint32_t block0;              // first block of this layer; blocks are (filter tile, channel tile)
   uint16_t Cout, CinReal, Cin, taps, CoutPad, Kpad, CinRows, CoutD, KpadD, has_d, CT, ctiles;
   uint16_t conv_stride;         // 2: data-gradient taps stored parity class by class (dgrad_tap_slot_to_flipped)
-  uint16_t pad0;
+  uint16_t has_f;               // write the forward layout (has_d: the data-gradient layout)
   uint16_t taps_shr, ct_log2;   // index arithmetic without divisions: q / taps = umulhi(q, taps_mul) >> taps_shr
   uint32_t taps_mul;            // (fast_div_setup, common.h; 0 = one tap), CT = 1 << ct_log2
 };
@@ -122,6 +115,7 @@ struct PackTable {
   int n;
   PackEntry e[PACK_MAX_LAYERS];
 };
+static_assert(sizeof(PackEntry) == 52, "PackTable travels as a kernel argument: keep its entries small");
 int pack_all_launch(int dtype, const float* params, void* ws, const PackTable& t, int blocks,
                     hipStream_t stream);
 

@@ -118,18 +118,6 @@ int bn_finalize_launch(const float* stats, int tiles, int C, int Cpad, long coun
   return 0;
 }
 
-__global__ void bn_eval_coeff_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
-                                     const float* __restrict__ rm, const float* __restrict__ rv,
-                                     float eps, int C, float* __restrict__ scale,
-                                     float* __restrict__ shift) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const float invstd = 1.0f / sqrtf(rv[c] + eps);
-  const float sc = gamma[c] * invstd;
-  scale[c] = sc;
-  shift[c] = beta[c] - rm[c] * sc;
-}
-
 // every BatchNorm of the network in one launch (eval forward): block = layer, table as kernel argument
 __global__ __launch_bounds__(256) void bn_eval_coeff_all_kernel(const float* __restrict__ params,
                                                                 const float* __restrict__ bnstats,
@@ -148,15 +136,6 @@ int bn_eval_coeff_all_launch(const float* params, const float* bnstats, void* ws
                              hipStream_t stream) {
   if (t.n == 0) return 0;
   hipLaunchKernelGGL(bn_eval_coeff_all_kernel, dim3(t.n), dim3(256), 0, stream, params, bnstats, (char*)ws, eps, t);
-  D3F_HIP(hipGetLastError());
-  return 0;
-}
-
-int bn_eval_coeff_launch(const float* gamma, const float* beta, const float* running_mean,
-                         const float* running_var, float eps, int C, float* scale, float* shift,
-                         hipStream_t stream) {
-  hipLaunchKernelGGL(bn_eval_coeff_kernel, dim3(cdiv(C, 256)), dim3(256), 0, stream, gamma, beta,
-                     running_mean, running_var, eps, C, scale, shift);
   D3F_HIP(hipGetLastError());
   return 0;
 }
@@ -885,56 +864,6 @@ __device__ __forceinline__ void pack_store(T* __restrict__ base, long idx, long 
   }
 }
 
-template <typename T, bool X3>
-__global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restrict__ w, int Cout,
-                                                           int CinReal, int Cin, int KH, int KW,
-                                                           T* __restrict__ wf, int CoutPad, int Kpad,
-                                                           T* __restrict__ wd, int CinRows, int CoutD,
-                                                           int KpadD, int stride) {
-  const int taps = KH * KW;
-  const long nf = wf ? (long)CoutPad * Kpad : 0;
-  const long nd = wd ? (long)CinRows * KpadD : 0;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nf + nd; i += (long)gridDim.x * 256) {
-    if (i < nf) {
-      const int n = (int)(i / Kpad), k = (int)(i % Kpad);
-      const int tap = k / Cin, c = k % Cin;
-      float v = 0.f;
-      if (n < Cout && tap < taps && c < CinReal) v = w[((long)n * CinReal + c) * taps + tap];
-      pack_store<T, X3>(wf, i, nf, v);
-    } else {
-      const long j = i - nf;
-      const int c = (int)(j / KpadD), k = (int)(j % KpadD);
-      const int slot = k / CoutD, n = k % CoutD;
-      float v = 0.f;
-      if (c < CinReal && slot < taps && n < Cout)
-        v = w[((long)n * CinReal + c) * taps + (taps - 1 - dgrad_tap_slot_to_flipped(slot, taps, stride))];
-      pack_store<T, X3>(wd, j, nd, v);
-    }
-  }
-}
-
-int pack_weights_launch(int dtype, const float* w, int Cout, int CinReal, int Cin, int KH, int KW,
-                        void* wf, int CoutPad, int Kpad, void* wd, int CinRows, int KpadD, int stride,
-                        hipStream_t stream) {
-  const int ve = dtype == D3F_BF16 ? 8 : 4;
-  const int CoutD = (int)round_up(Cout, ve);
-  const long total = (wf ? (long)CoutPad * Kpad : 0) + (wd ? (long)CinRows * KpadD : 0);
-  if (total == 0) return 0;
-  D3F_CHECK(!wf || Kpad >= KH * KW * Cin, "pack: Kpad");
-  D3F_CHECK(!wd || KpadD >= KH * KW * CoutD, "pack: KpadD");
-  if (dtype == D3F_F32)
-    hipLaunchKernelGGL((pack_weights_kernel<float, false>), dim3(grid_for(total)), dim3(256), 0, stream, w, Cout,
-                       CinReal, Cin, KH, KW, (float*)wf, CoutPad, Kpad, (float*)wd, CinRows, CoutD, KpadD, stride);
-  else if (dtype == D3F_F32X3)
-    hipLaunchKernelGGL((pack_weights_kernel<bf16_t, true>), dim3(grid_for(total)), dim3(256), 0, stream, w, Cout,
-                       CinReal, Cin, KH, KW, (bf16_t*)wf, CoutPad, Kpad, (bf16_t*)wd, CinRows, CoutD, KpadD, stride);
-  else
-    hipLaunchKernelGGL((pack_weights_kernel<bf16_t, false>), dim3(grid_for(total)), dim3(256), 0, stream, w, Cout,
-                       CinReal, Cin, KH, KW, (bf16_t*)wf, CoutPad, Kpad, (bf16_t*)wd, CinRows, CoutD, KpadD, stride);
-  D3F_HIP(hipGetLastError());
-  return 0;
-}
-
 // ------------------------------------------------------------------------------------------
 // "Up-sample folded into the weights" layouts for the decoder's conv(cat(upsample2x(x), skip)), 3x3 pad 1:
 // nearest x2 up-sampling repeats every low-resolution pixel 2x2 times, so inside an output-parity class (py, px)
@@ -1052,9 +981,10 @@ int pack_up_launch(int dtype, const float* w, int Cout, int C0, int C1, void* wf
 
 // All layers of a network in one launch: the table travels as a kernel argument (no device-side state) and a
 // block looks its layer up by its first block index.  A block transposes one [32 filters][CT channels][taps]
-// tile through LDS: the torch layout [n][c][tap] is read in contiguous runs of CT*taps floats and both packed
-// layouts ([n][tap][c] and [c][flipped tap][n]) are written in contiguous runs; padding rows/columns of the
-// packed matrices are (re)written as zeros by the edge tiles, so the workspace needs no initialisation.
+// tile through LDS: the torch layout [n][c][tap] is read in contiguous runs of CT*taps floats and the packed
+// layouts the entry asks for ([n][tap][c] and / or [c][flipped tap][n]) are written in contiguous runs; padding
+// rows/columns of the packed matrices are (re)written as zeros by the edge tiles, so the workspace needs no
+// initialisation.
 template <typename T, bool X3>
 __global__ __launch_bounds__(256) void pack_all_kernel(const float* __restrict__ params, char* __restrict__ ws,
                                                        PackTable t) {
@@ -1085,19 +1015,20 @@ __global__ __launch_bounds__(256) void pack_all_kernel(const float* __restrict__
   }
   __syncthreads();
   // ---- forward layout wf[n][tap*Cin + c] ----
-  if (true)
-  for (int i = threadIdx.x; i < PACK_NT * run; i += 256) {
-    const int cl = i & (CT - 1), q = i >> lgct;
-    const int nl = fast_div(q, tmul, tshr), tap = q - nl * taps;
-    const int n = n0 + nl, c = c0 + cl;
-    if (n < CoutPad && c < Cin)
-      pack_store<T, X3>(wf, (long)(unsigned)(n * Kpad + tap * Cin + c), (long)CoutPad * Kpad, tile[nl * stride + cl * taps + tap]);
-  }
-  if (ct == 0) {  // zero tail of each row: k in [taps*Cin, Kpad)
-    const int k0 = taps * Cin, tail = Kpad - k0;
-    for (int i = threadIdx.x; i < PACK_NT * tail; i += 256) {
-      const int n = n0 + i / tail;
-      if (n < CoutPad) pack_store<T, X3>(wf, (long)n * Kpad + k0 + i % tail, (long)CoutPad * Kpad, 0.f);
+  if (e.has_f) {
+    for (int i = threadIdx.x; i < PACK_NT * run; i += 256) {
+      const int cl = i & (CT - 1), q = i >> lgct;
+      const int nl = fast_div(q, tmul, tshr), tap = q - nl * taps;
+      const int n = n0 + nl, c = c0 + cl;
+      if (n < CoutPad && c < Cin)
+        pack_store<T, X3>(wf, (long)(unsigned)(n * Kpad + tap * Cin + c), (long)CoutPad * Kpad, tile[nl * stride + cl * taps + tap]);
+    }
+    if (ct == 0) {  // zero tail of each row: k in [taps*Cin, Kpad)
+      const int k0 = taps * Cin, tail = Kpad - k0;
+      for (int i = threadIdx.x; i < PACK_NT * tail; i += 256) {
+        const int n = n0 + i / tail;
+        if (n < CoutPad) pack_store<T, X3>(wf, (long)n * Kpad + k0 + i % tail, (long)CoutPad * Kpad, 0.f);
+      }
     }
   }
   // ---- data-gradient layout wd[c][tapf*CoutD + n], taps flipped ----

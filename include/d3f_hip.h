@@ -219,7 +219,12 @@ typedef struct d3f_conv_desc {
   int32_t CinReal;    /* unpadded input channels of the f32 master weight [Cout][CinReal][KH][KW] */
 } d3f_conv_desc;
 
-/* torch.nn.Conv2d weight -> packed forward (which=0) / data-gradient (which=1) operand */
+/* torch.nn.Conv2d weight -> packed forward (which=0) / data-gradient (which=1) operand.  d3f_conv_pack_weights packs
+ * with the whole-network packing kernel, whose table holds 16-bit extents and 32-bit element indices: a layer whose
+ * padded extents (Cout, Cin, their padded row counts, KH*KW*Cin and KH*KW*Cout rounded up to whole k-tiles) reach 65536,
+ * or one of whose requested layouts reaches 2^31 elements, is refused with an error naming that limit (an up-sampled
+ * layer that runs folded, d3f_conv_upsample_folded, is packed by a kernel of its own, as before).
+ * d3f_conv_packed_bytes still sizes such a layer. */
 size_t d3f_conv_packed_bytes(int dtype, const d3f_conv_desc* d, int which);
 int d3f_conv_pack_weights(int dtype, const d3f_conv_desc* d, const float* w, void* w_fwd, void* w_dgrad,
                           void* stream);

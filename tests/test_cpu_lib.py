@@ -122,6 +122,24 @@ def test_conv_descriptor_validation_on_host():
     assert lib.d3f_conv_workspace_bytes(_lib.F32, C.byref(d), 0) > 0  # 128 rows x 128 channels: split-K
 
 
+def test_conv_pack_weights_refuses_a_layer_beyond_the_packing_table():
+    """d3f_conv_pack_weights packs through the network's table-driven kernel (16-bit extents, 32-bit element indices): a
+    layer beyond that range is refused with an error that names the limit before anything is launched -- the dummy
+    pointers below are never dereferenced -- while d3f_conv_packed_bytes still sizes it."""
+    if torch.cuda.is_available():
+        pytest.skip("host-only check of the C ABI guard (dummy device pointers)")
+    lib = _lib.lib()
+    d = _lib.ConvDesc(1, 8, 8, 8192, 0, 0, 64, 3, 3, 1, 1, 8192)  # Kpad = 9 x 8192 = 73728
+    p = C.c_void_p(0x1000)
+    for dtype, wsz in ((_lib.F32, 4), (_lib.BF16, 2), (_lib.F32X3, 6)):
+        assert lib.d3f_conv_packed_bytes(dtype, C.byref(d), 0) == 64 * 73728 * wsz
+        assert lib.d3f_conv_packed_bytes(dtype, C.byref(d), 1) == 8192 * 576 * wsz
+        for w_fwd, w_dgrad in ((p, p), (p, None), (None, p)):
+            assert lib.d3f_conv_pack_weights(dtype, C.byref(d), p, w_fwd, w_dgrad, None) != 0
+            err = lib.d3f_last_error()
+            assert b"packing table" in err and b"65536" in err, err
+
+
 def test_library_digest_matches_sources_and_a_stale_library_is_refused(tmp_path):
     """The loaded library carries the digest of the sources it was built from (Makefile -> d3f_source_digest); a library
     sitting next to sources it was NOT built from must not load silently (VERDICT r3 weak #11)."""
