@@ -473,36 +473,50 @@ int d3f_conv_backward_weight(int dtype, const d3f_conv_desc* d, const void* dy, 
                             (hipStream_t)stream);
 }
 
+// describe -> plan: a BatchNorm layer of the single-operator entry points (the split form)
+static BnLayer bn_layer(int dtype, int C, int64_t rows, int fwd_rows = 0) {
+  BnLayer L;
+  L.C = C; L.Cpad = (int)round_up(C, 16); L.rows = (long)rows; L.dtype = sdt(dtype); L.fwd_rows = fwd_rows;
+  L.allow_fused = false;
+  bn_layer_plan(L);
+  return L;
+}
 int d3f_bn_finalize(const float* stats, int tiles, int C, int64_t count, const float* gamma,
                     const float* beta, float* running_mean, float* running_var, float* coef, void* stream) {
   D3F_CHECK(stats && gamma && beta && coef && C > 0 && tiles > 0 && count > 0, "bn_finalize: argument");
-  return bn_finalize_launch(stats, tiles, C, (int)round_up(C, 16), (long)count, gamma, beta, 1e-5f, 0.1f,
-                            running_mean, running_var, coef, coef + C, coef + 2 * C, coef + 3 * C,
-                            (hipStream_t)stream);
+  const BnLayer L = bn_layer(D3F_F32, C, count, tiles);
+  BnBufs b;
+  b.stats = const_cast<float*>(stats);  // (read only)
+  b.gamma = gamma; b.beta = beta; b.running_mean = running_mean; b.running_var = running_var; b.coef = coef;
+  return bn_layer_finalize(L, b, (long)count, (hipStream_t)stream);
 }
 int d3f_bn_apply(int dtype, const void* y, const float* coef, int C, int64_t rows, const void* residual,
                  int relu, void* out, void* stream) {
   D3F_CHECK(y && coef && out, "bn_apply: null argument");
-  return bn_apply_launch(sdt(dtype), y, coef + 2 * C, coef + 3 * C, residual, nullptr, nullptr, nullptr, relu,
-                         out, (long)rows, C, (hipStream_t)stream);
+  BnLayer L = bn_layer(dtype, C, rows);
+  L.relu = relu != 0;
+  L.res = residual ? BN_RES_TENSOR : BN_RES_NONE;
+  BnBufs b;
+  b.coef = const_cast<float*>(coef);  // (the forward's scale / shift rows: read only)
+  b.y = y; b.res = residual; b.a = out;
+  return bn_layer_apply(L, b, (hipStream_t)stream);
 }
 size_t d3f_bn_backward_workspace_bytes(int dtype, int C, int64_t rows) {
-  return ((size_t)bn_bwd_reduce_blocks((long)rows, C, sdt(dtype)) * C * 2 + 3 * (size_t)C) * sizeof(float) + 256;
+  return ((size_t)bn_layer(dtype, C, rows).reduce_blocks * C * 2 + 3 * (size_t)C) * sizeof(float) + 256;
 }
 int d3f_bn_backward(int dtype, const void* dA, const void* a_or_null, const void* y, const float* coef,
                     const float* gamma, int C, int64_t rows, void* dy, void* dres, float* dgamma,
                     float* dbeta, void* workspace, void* stream) {
   D3F_CHECK(dA && y && coef && gamma && dy && dgamma && dbeta && workspace, "bn_backward: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  float* part = reinterpret_cast<float*>(workspace);
-  const int blocks = bn_bwd_reduce_blocks((long)rows, C, sdt(dtype));
-  float* k = part + (size_t)round_up((long)blocks * C * 2, 4);
-  int nb = 0;
-  if (int rc = bn_bwd_reduce_launch(sdt(dtype), dA, a_or_null, y, coef, coef + C, part, &nb, (long)rows, C, s))
-    return rc;
-  if (int rc = bn_bwd_finalize_launch(part, nb, C, (long)rows, gamma, coef + C, dgamma, dbeta, 0, k, s))
-    return rc;
-  return bn_bwd_apply_launch(sdt(dtype), dA, a_or_null, y, coef, coef + C, k, dy, dres, 0, (long)rows, C, s);
+  BnLayer L = bn_layer(dtype, C, rows);
+  L.mask = a_or_null ? BN_MASK_FROM_A : BN_MASK_NONE;
+  BnBufs b;
+  b.stats = reinterpret_cast<float*>(workspace);  // the partial sums, then k (this workspace holds it: coef has 4 rows)
+  b.k = b.stats + (size_t)round_up((long)L.reduce_blocks * C * 2, 4);
+  b.coef = const_cast<float*>(coef);  // (mean / invstd rows: read only)
+  b.gamma = gamma; b.y = y; b.a = const_cast<void*>(a_or_null);
+  b.dA = dA; b.dy = dy; b.dres = dres; b.dgamma = dgamma; b.dbeta = dbeta;
+  return bn_layer_backward(L, b, nullptr, (hipStream_t)stream);
 }
 
 int d3f_maxpool3x3s2_forward(int dtype, const void* in, void* out, uint8_t* idx, int B, int H, int W,

@@ -35,13 +35,14 @@ struct BnInfo {
 // one convolution layer of the network: its plan (common.h, ConvLayer: description, geometry, launches, packed sizes)
 // plus its place in the network -- tensors, parameters, BatchNorm, workspace regions
 struct Unit : ConvLayer {
-  std::string conv_name, bn_name;
+  std::string conv_name;
   int in0 = -1, in1 = -1, y = -1, a = -1;
-  bool bn = true, bias = false, relu = true, apply = true;
+  bool bn = true, bias = false;
+  BnLayer norm;  // bn: its BatchNorm (pointwise.h: description and plan, ReLU and residual included)
   int res_tensor = -1, res_unit = -1;
   long w_off = -1, bias_off = -1, g_off = -1, b_off = -1, rm_off = -1, rv_off = -1;
   size_t wf_off = 0, wd_off = 0;  // packed weights (bytes into workspace)
-  size_t coef_off = 0;  // bytes: mean[C] invstd[C] scale[C] shift[C] k[3C]
+  size_t coef_off = 0;  // bytes: the BatchNorm's coefficient block (pointwise.h, bn_coef)
   int segment = 0;      // backward bucket this unit belongs to
   size_t dy_off = 0;    // this unit's own dY buffer (kept until its weight-gradient group has run)
   // decoder conv(cat(upsample2x(in0), in1)) with the up-sampling folded into pre-summed weights (pointwise.hip,
@@ -128,8 +129,8 @@ class UnetEngine {
   // partials) and once in the backward pass (the (sum dz, sum dz*xhat) partials); the finalize kernels then divide by
   // rows * world.  dgamma / dbeta stay LOCAL sums (the gradient all-reduce adds them up like every other gradient).
   typedef int (*AllReduceFn)(void* ctx, float* data, int64_t count, void* stream);
-  bool bn_sync_installed() const { return bn_sync_fn_ != nullptr; }
-  void set_bn_sync(AllReduceFn fn, void* ctx, int world) { bn_sync_fn_ = fn; bn_sync_ctx_ = ctx; bn_sync_world_ = world > 0 ? world : 1; }
+  bool bn_sync_installed() const { return bn_sync_.fn != nullptr; }
+  void set_bn_sync(AllReduceFn fn, void* ctx, int world) { bn_sync_ = BnSync{fn, ctx, world > 0 ? world : 1}; }
   int export_tensor(const char* name, const void* ws, float* out_nchw, hipStream_t s) const;
   int export_shape(const char* name, int32_t dims[3]) const;
 
@@ -200,9 +201,8 @@ class UnetEngine {
   int wait_for_packed_weights(hipStream_t s) const;
   mutable hipStream_t gstream_ = nullptr;
   mutable GraphSlot g_predict_, g_eval_;
-  AllReduceFn bn_sync_fn_ = nullptr;
-  void* bn_sync_ctx_ = nullptr;
-  int bn_sync_world_ = 1;
+  BnSync bn_sync_{nullptr, nullptr, 1};
+  const BnSync* bn_sync() const { return bn_sync_.fn != nullptr ? &bn_sync_ : nullptr; }
   int train_step_launches(const StepArgs& a, void* ws, hipStream_t s) const;
   mutable hipGraphExec_t g_step_ = nullptr;
   mutable StepArgs g_step_key_{};

@@ -125,9 +125,8 @@ int UnetEngine::add_unit(const std::string& conv_name, const std::string& bn_nam
                          bool apply, int segment) {
   Unit u;
   u.conv_name = conv_name;
-  u.bn_name = bn_name;
   u.in0 = in0; u.in1 = in1;
-  u.bn = bn; u.bias = bias; u.relu = relu; u.apply = apply; u.segment = segment;
+  u.bn = bn; u.bias = bias; u.segment = segment;
   const TensorD& t0 = tensors[in0];
   u.B = B; u.Hv = t0.H << up0; u.Wv = t0.W << up0;
   u.C0 = t0.C; u.C1 = in1 >= 0 ? tensors[in1].C : 0; u.up0 = up0;
@@ -161,7 +160,14 @@ int UnetEngine::add_unit(const std::string& conv_name, const std::string& bn_nam
     bns.push_back(bi);
     u.y = new_tensor(u.Ho, u.Wo, Cout);
     u.a = apply ? new_tensor(u.Ho, u.Wo, Cout) : -1;
-    u.coef_off = alloc((size_t)7 * Cout * sizeof(float));
+    u.coef_off = alloc((size_t)BN_COEF_ROWS * Cout * sizeof(float));
+    BnLayer& n = u.norm;  // (residual, mask and the backward's partial rows: once the schedule is known)
+    n.name = bn_name;
+    n.C = Cout; n.Cpad = u.CoutPad; n.rows = (long)B * u.Ho * u.Wo;  // (fwd.M counts one output-parity class for a folded layer)
+    n.dtype = dtype; n.plan_nets = plan_nets;
+    n.apply = apply; n.relu = relu;
+    n.fwd_rows = u.wino ? u.wino_rows : u.fwd.stat_rows;  // (Winograd: one per workgroup)
+    n.allow_fused = true;
   }
   u.wf_off = alloc(u.wf);
   if (u.need_dgrad) u.wd_off = alloc(u.wd);
@@ -256,14 +262,9 @@ int UnetEngine::build(const char* encoder, int in_channels_, int classes_, int B
     if (u.need_dgrad) bwd_flops += 2.0 * u.macs;
     splitk_bytes = std::max(splitk_bytes, u.splitk_floats * sizeof(float));
     if (u.wino) u.wu_off = alloc(u.wu);
-    if (u.bn) {
-      const int stat_rows = std::max(u.fwd.stat_rows, u.wino ? u.wino_rows : 0);
-      stats_bytes = std::max(stats_bytes, (size_t)stat_rows * u.CoutPad * 2 * sizeof(float));
-      bnpart_bytes = std::max(bnpart_bytes, (size_t)bn_bwd_reduce_blocks(rows, u.Cout, dtype) * u.Cout * 2 * sizeof(float));
-    }
     const size_t dyb = (size_t)rows * u.CoutD * esize();
     dy_bytes = std::max(dy_bytes, dyb);
-    if (!u.apply && u.bn) dz_bytes = std::max(dz_bytes, dyb);
+    if (u.bn && !u.norm.apply) dz_bytes = std::max(dz_bytes, dyb);
     u.wslab_off = alloc(u.wslab_bytes);
     u.dy_off = alloc(dyb);
     // an up-sampled source whose data gradient comes back at full resolution: scratch for the 2x2 sum
@@ -375,8 +376,23 @@ int UnetEngine::build(const char* encoder, int in_channels_, int classes_, int B
                 "plan: fused BatchNorm reduce shape mismatch (%s -> %s)", up.conv_name.c_str(), uc.conv_name.c_str());
       pj.fuse_for_unit = ck.unit;
       ck.fused_rows = pd.splitk > 1 ? pd.stat_rows : pd.tiles_m;
-      bnpart_bytes = std::max(bnpart_bytes, (size_t)ck.fused_rows * uc.Cout * 2 * sizeof(float));
     }
+  }
+
+  // ---- BatchNorm: the rest of each layer's description, from the graph and the schedule; then its plan ----------
+  for (const BwdOp& op : bwd_ops) {
+    if (op.kind != BW_UNIT) continue;
+    Unit& u = units[op.unit];
+    u.norm.res = u.res_tensor >= 0 ? BN_RES_TENSOR : u.res_unit >= 0 ? BN_RES_LAYER : BN_RES_NONE;
+    // ReLU mask: recomputed from y without a residual (bn_layer_backward), read from the activation with one
+    u.norm.mask = !op.mask ? BN_MASK_NONE : u.norm.res == BN_RES_NONE ? BN_MASK_FROM_Y : BN_MASK_FROM_A;
+    u.norm.fused_rows = op.fused_rows;
+  }
+  for (Unit& u : units) {
+    if (!u.bn) continue;
+    bn_layer_plan(u.norm);
+    stats_bytes = std::max(stats_bytes, u.norm.stat_floats * sizeof(float));
+    bnpart_bytes = std::max(bnpart_bytes, u.norm.part_floats * sizeof(float));
   }
 
   // ---- scratch ------------------------------------------------------------------------
@@ -542,10 +558,6 @@ int UnetEngine::pack_weights(const float* params0_, void* ws0_, hipStream_t s, c
   return 0;
 }
 
-static inline float* coef_ptr(char* ws, const Unit& u, int which) {
-  return reinterpret_cast<float*>(ws + u.coef_off) + (long)which * u.Cout;
-}
-
 int UnetEngine::forward(const float* params_, float* bnstats, const float* x, float* out, void* ws_,
                         int training, hipStream_t s, const NetIO* io) const {
   char* ws = reinterpret_cast<char*>(ws_);
@@ -562,7 +574,8 @@ int UnetEngine::forward(const float* params_, float* bnstats, const float* x, fl
 int UnetEngine::forward_body(const float* params_, float* bnstats, float* out, char* ws, int training,
                              hipStream_t s, const NetSplit* ns) const {
   auto T = [&](int tid) { return ws + tensors[tid].off; };
-  D3F_CHECK(ns == nullptr || (training && bn_sync_fn_ == nullptr), "unet: the pair engine runs train-mode passes with "
+  auto coef = [&](const Unit& u) { return reinterpret_cast<float*>(ws + u.coef_off); };
+  D3F_CHECK(ns == nullptr || (training && bn_sync() == nullptr), "unet: the pair engine runs train-mode passes with "
             "per-GPU BatchNorm statistics");
   if (!training) {  // folded BatchNorm coefficients of all layers: one launch
     BnEvalTable t;
@@ -576,7 +589,7 @@ int UnetEngine::forward_body(const float* params_, float* bnstats, float* out, c
         e.coef_off16 = (uint32_t)(u.coef_off >> 4);
         e.C = u.Cout;
       }
-    if (int rc = bn_eval_coeff_all_launch(params_, bnstats, ws, 1e-5f, t, s)) return rc;
+    if (int rc = bn_eval_coeff_all_launch(params_, bnstats, ws, t, s)) return rc;
   }
   for (int ui : fwd_order_) {
     if (ui < 0) {
@@ -610,61 +623,23 @@ int UnetEngine::forward_body(const float* params_, float* bnstats, float* out, c
     }
     const Unit* ds = u.res_unit >= 0 ? &units[u.res_unit] : nullptr;
     if (training) {
-      float* stats = reinterpret_cast<float*>(ws + stats_off);
-      const int stat_rows = u.wino ? u.wino_rows : u.fwd.stat_rows;  // (Winograd: one per workgroup)
       b.out = T(u.y);
-      b.stats = stats;
+      b.stats = reinterpret_cast<float*>(ws + stats_off);
       if (int rc = conv_layer_forward(u, b, u.wino, s, ns)) return rc;
-      const long rows = (long)B * u.Ho * u.Wo;  // (fwd.M counts one output-parity class for a folded layer)
-      const bool sync = bn_sync_fn_ != nullptr;
-      if (sync) {  // statistics over every rank's batch: the partial rows are summed across ranks in place
-        if (int rc = bn_sync_fn_(bn_sync_ctx_, stats, (int64_t)stat_rows * u.CoutPad * 2, (void*)s))
-          return set_error(rc, "BatchNorm statistics all-reduce failed in the forward pass (%s)", u.bn_name.c_str());
-      }
-      const long count = rows * (sync ? bn_sync_world_ : 1);
-#ifdef D3F_PROFILING
-      // timing-only ablation (wrong activations; profiling builds only): D3F_ABLATE_FWD_BN=1 replaces the streaming
-      // BatchNorm + ReLU pass of every layer WITHOUT a residual add by the coefficient-only finalize launch -- the ceiling
-      // of "apply the two coefficients in the consumer's patch staging instead"  before any consumer cost
-      static const bool abl_fbn = getenv("D3F_ABLATE_FWD_BN") != nullptr;
-      if (abl_fbn && !sync && u.apply && u.res_tensor < 0 && ds == nullptr) {
-        if (int rc = bn_finalize_launch(stats, stat_rows, u.Cout, u.CoutPad, count, params_ + u.g_off, params_ + u.b_off,
-                                        1e-5f, 0.1f, bnstats + u.rm_off, bnstats + u.rv_off, coef_ptr(ws, u, 0),
-                                        coef_ptr(ws, u, 1), coef_ptr(ws, u, 2), coef_ptr(ws, u, 3), s, ns))
-          return rc;
-        continue;
-      }
-#endif
-      if (!sync && u.apply && bn_fused_finalize_ok(dtype, stat_rows, u.Cout)) {
-        // finalize folded into the streaming pass (bn_fused.hip): one launch instead of two
-        if (int rc = bn_finalize_apply_launch(dtype, stats, stat_rows, u.Cout, u.CoutPad, rows, params_ + u.g_off,
-                                              params_ + u.b_off, 1e-5f, 0.1f, bnstats + u.rm_off, bnstats + u.rv_off,
-                                              coef_ptr(ws, u, 0), coef_ptr(ws, u, 1), coef_ptr(ws, u, 2),
-                                              coef_ptr(ws, u, 3), T(u.y),
-                                              u.res_tensor >= 0 ? T(u.res_tensor) : nullptr, ds ? T(ds->y) : nullptr,
-                                              ds ? coef_ptr(ws, *ds, 2) : nullptr, ds ? coef_ptr(ws, *ds, 3) : nullptr,
-                                              u.relu ? 1 : 0, T(u.a), rows, s, ns, plan_nets))
-          return rc;
-        continue;
-      }
-      if (int rc = bn_finalize_launch(stats, stat_rows, u.Cout, u.CoutPad, count,
-                                      params_ + u.g_off, params_ + u.b_off, 1e-5f, 0.1f,
-                                      bnstats + u.rm_off, bnstats + u.rv_off, coef_ptr(ws, u, 0),
-                                      coef_ptr(ws, u, 1), coef_ptr(ws, u, 2), coef_ptr(ws, u, 3), s, ns))
-        return rc;
-      if (u.apply) {
-        if (int rc = bn_apply_launch(dtype, T(u.y), coef_ptr(ws, u, 2), coef_ptr(ws, u, 3),
-                                     u.res_tensor >= 0 ? T(u.res_tensor) : nullptr,
-                                     ds ? T(ds->y) : nullptr, ds ? coef_ptr(ws, *ds, 2) : nullptr,
-                                     ds ? coef_ptr(ws, *ds, 3) : nullptr, u.relu ? 1 : 0, T(u.a),
-                                     rows, u.Cout, s, ns))
-          return rc;
-      }
+      BnBufs n;
+      n.stats = b.stats;
+      n.gamma = params_ + u.g_off; n.beta = params_ + u.b_off;
+      n.running_mean = bnstats + u.rm_off; n.running_var = bnstats + u.rv_off;
+      n.coef = coef(u);
+      n.y = T(u.y); n.a = u.a >= 0 ? T(u.a) : nullptr;
+      n.res = u.res_tensor >= 0 ? T(u.res_tensor) : (ds ? T(ds->y) : nullptr);
+      n.res_coef = ds ? coef(*ds) : nullptr;
+      if (int rc = bn_layer_forward(u.norm, n, bn_sync(), s, ns)) return rc;
     } else {
-      b.scale = coef_ptr(ws, u, 2);
-      b.shift = coef_ptr(ws, u, 3);
-      b.relu = u.relu ? 1 : 0;
-      if (u.apply) {
+      b.scale = bn_coef(coef(u), u.Cout, BN_SCALE);
+      b.shift = bn_coef(coef(u), u.Cout, BN_SHIFT);
+      b.relu = u.norm.relu ? 1 : 0;
+      if (u.norm.apply) {
         b.out = T(u.a);
         b.res = u.res_tensor >= 0 ? T(u.res_tensor) : (ds ? T(ds->y) : nullptr);
       } else {
@@ -863,12 +838,13 @@ int UnetEngine::backward_join(hipStream_t s) const {
 int UnetEngine::backward(const float* params_, const float* dout, float* grads, void* ws_,
                          int seg_begin, int seg_end, hipStream_t s, int join, const NetIO* io) const {
   char* ws = reinterpret_cast<char*>(ws_);
-  D3F_CHECK(nets == 1 || (io != nullptr && bn_sync_fn_ == nullptr), "unet: the pair engine needs the second network's "
+  D3F_CHECK(nets == 1 || (io != nullptr && bn_sync() == nullptr), "unet: the pair engine needs the second network's "
             "offsets and runs with per-GPU BatchNorm statistics");
   NetSplit split{};
   const NetSplit* ns = make_split(io, io ? io->dout : 0, &split) ? &split : nullptr;
   auto T = [&](int tid) { return ws + tensors[tid].off; };
   auto G = [&](int gid) { return gid == -2 ? ws + dz_off : ws + gtensors[gid].off; };
+  auto coef = [&](const Unit& u) { return reinterpret_cast<float*>(ws + u.coef_off); };
   const bool serial = serial_backward();
 #ifdef D3F_PROFILING
   // timing-only ablation (wrong gradients; profiling builds only): D3F_ABLATE_BACKWARD contains w (skip weight
@@ -946,7 +922,6 @@ int UnetEngine::backward(const float* params_, const float* dout, float* grads, 
       continue;
     }
     const Unit& u = units[op.unit];
-    const long rows = (long)B * u.Ho * u.Wo;
     char* dy = ws + u.dy_off;
     if (op.kind == BW_HEAD) {
       if (int rc = nchw_to_nhwc_launch(dtype, dout, dy, B, u.Cout, u.Ho, u.Wo, u.CoutD, s, ns)) return rc;
@@ -957,67 +932,16 @@ int UnetEngine::backward(const float* params_, const float* dout, float* grads, 
       } else {
         head_bias_pending = true;  // with the head's weight gradient, on the weight-gradient stream (flush_pending)
       }
-    } else {
-      int nb = 0;
-      float* mean = coef_ptr(ws, u, 0);
-      float* invstd = coef_ptr(ws, u, 1);
-      float* k = coef_ptr(ws, u, 4);
-      float* bnpart = reinterpret_cast<float*>(ws + bnpart_off);
-      // ReLU mask: layers without a residual recompute it from y (identical to a > 0: the forward apply used the
-      // same fp32 y*scale + shift on the same stored y, and rounding a positive fp32 value to bf16 never gives
-      // zero); residual layers read the saved activation
-      const bool from_y = op.mask && u.res_tensor < 0 && u.res_unit < 0;
-      const void* amask = (op.mask && !from_y) ? T(u.a) : nullptr;
-      const float* msc = from_y ? coef_ptr(ws, u, 2) : nullptr;
-      const float* msf = from_y ? coef_ptr(ws, u, 3) : nullptr;
-      if (skip_b) {
-        nb = 1;
-      } else if (op.fused_rows > 0) {
-        nb = op.fused_rows;  // the producing data gradient already left the partial sums in bnpart
-      } else if (int rc = bn_bwd_reduce_launch(dtype, G(op.dA), amask, T(u.y), mean, invstd, bnpart, &nb, rows,
-                                               u.Cout, s, msc, msf, ns)) {
-        return rc;
-      }
-      const bool sync = bn_sync_fn_ != nullptr && !skip_b;
-      if (sync) {
-        // synchronised statistics: dgamma / dbeta from the LOCAL sums (they are summed over ranks with the other
-        // gradients), the coefficients of dy from the sums over every rank's batch
-        if (int rc = bn_bwd_finalize_launch(bnpart, nb, u.Cout, rows, params_ + u.g_off, invstd, grads + u.g_off,
-                                            grads + u.b_off, 0, k, s))
-          return rc;
-        if (int rc = bn_sync_fn_(bn_sync_ctx_, bnpart, (int64_t)nb * u.Cout * 2, (void*)s))
-          return set_error(rc, "BatchNorm statistics all-reduce failed in the backward pass (%s)", u.bn_name.c_str());
-        if (int rc = bn_bwd_finalize_launch(bnpart, nb, u.Cout, rows * bn_sync_world_, params_ + u.g_off, invstd, nullptr,
-                                            nullptr, 0, k, s))
-          return rc;
-        if (int rc = bn_bwd_apply_launch(dtype, G(op.dA), amask, T(u.y), mean, invstd, k, dy,
-                                         op.dres == -1 ? nullptr : G(op.dres), op.dres_acc ? 1 : 0, rows,
-                                         u.Cout, s, msc, msf))
-          return rc;
-#ifdef D3F_PROFILING
-      } else if (!skip_b && getenv("D3F_ABLATE_BWD_BN") != nullptr && op.dres == -1 && from_y) {
-        // timing-only ablation (wrong gradients): the backward streaming pass of the layers without a residual replaced by
-        // the coefficient-only finalize launch -- the ceiling of VERDICT r5 item 4b (dy made in the data gradient's staging)
-        if (int rc = bn_bwd_finalize_launch(bnpart, nb, u.Cout, rows, params_ + u.g_off, invstd, grads + u.g_off,
-                                            grads + u.b_off, 0, k, s, ns))
-          return rc;
-#endif
-      } else if (!skip_b && bn_fused_finalize_ok(dtype, nb, u.Cout)) {
-        // finalize folded into the streaming pass (bn_fused.hip)
-        if (int rc = bn_bwd_finalize_apply_launch(dtype, bnpart, nb, u.Cout, rows, params_ + u.g_off, mean, invstd,
-                                                  grads + u.g_off, grads + u.b_off, 0, k, G(op.dA), amask, T(u.y), dy,
-                                                  op.dres == -1 ? nullptr : G(op.dres), op.dres_acc ? 1 : 0, rows, s,
-                                                  msc, msf, ns, plan_nets))
-          return rc;
-      } else if (!skip_b) {
-        if (int rc = bn_bwd_finalize_launch(bnpart, nb, u.Cout, rows, params_ + u.g_off, invstd,
-                                            grads + u.g_off, grads + u.b_off, 0, k, s, ns))
-          return rc;
-        if (int rc = bn_bwd_apply_launch(dtype, G(op.dA), amask, T(u.y), mean, invstd, k, dy,
-                                         op.dres == -1 ? nullptr : G(op.dres), op.dres_acc ? 1 : 0, rows,
-                                         u.Cout, s, msc, msf, ns))
-          return rc;
-      }
+    } else if (!skip_b) {
+      BnBufs n;
+      n.stats = reinterpret_cast<float*>(ws + bnpart_off);
+      n.gamma = params_ + u.g_off;
+      n.coef = coef(u);
+      n.y = T(u.y); n.a = u.a >= 0 ? T(u.a) : nullptr;
+      n.dA = G(op.dA); n.dy = dy;
+      n.dres = op.dres == -1 ? nullptr : G(op.dres); n.dres_acc = op.dres_acc ? 1 : 0;
+      n.dgamma = grads + u.g_off; n.dbeta = grads + u.b_off;
+      if (int rc = bn_layer_backward(u.norm, n, bn_sync(), s, ns)) return rc;
     }
     // weight gradient (side stream), once the unit's dY exists
     if (!skip_w) {
@@ -1046,9 +970,9 @@ int UnetEngine::backward(const float* params_, const float* dout, float* grads, 
       if (op.fuse_for_unit >= 0) {
         const Unit& uc = units[op.fuse_for_unit];
         d.bn_y = T(uc.y);
-        d.bn_coef = coef_ptr(ws, uc, 0);
+        d.bn_coef = bn_coef(coef(uc), uc.Cout, BN_MEAN);  // (the epilogue reads the mean and invstd rows)
         d.bn_partial = reinterpret_cast<float*>(ws + bnpart_off);
-        d.bn_a = (uc.res_tensor >= 0 || uc.res_unit >= 0) ? T(uc.a) : nullptr;
+        d.bn_a = uc.norm.mask == BN_MASK_FROM_A ? T(uc.a) : nullptr;
       }
       if (int rc = conv_layer_dgrad(u, d, s, ns)) return rc;
     }

@@ -1,65 +1,96 @@
-// HBM-bound kernels of the U-Net hot path (pointwise.hip, loss.hip, optim.hip).
+// HBM-bound kernels of the U-Net hot path (pointwise.hip, batchnorm.hip, loss.hip, optim.hip).
 #pragma once
+#include <string>
+
 #include "common.h"
 
 namespace d3f {
 
 constexpr int PACK_MAX_LAYERS = 64;  // layers per kernel-argument table
 
-// ---- BatchNorm, train mode (K5/K7) ------------------------------------------------------
-// stats: per-m-tile partial (sum, sumsq) written by the conv epilogue.
-// Produces mean / invstd (saved for backward), folded scale / shift, and updates the
-// running statistics (momentum, unbiased variance) like torch.nn.BatchNorm2d.
-int bn_finalize_launch(const float* stats, int tiles, int C, int Cpad, long count,
-                       const float* gamma, const float* beta, float eps, float momentum,
-                       float* running_mean, float* running_var, float* mean, float* invstd,
-                       float* scale, float* shift, hipStream_t stream, const NetSplit* ns = nullptr);
-// eval mode: scale / shift from the running statistics, every BatchNorm of a network in one launch: scale -> coef[2*C..],
-// shift -> coef[3*C..]
+// ---- BatchNorm (K5/K7, batchnorm.hip) ----------------------------------------------------
+// A layer's coefficient block: BN_COEF_ROWS rows of C floats, mean invstd scale shift (the forward folds the affine
+// transform into y*scale + shift) and k[3] (the backward's k0 k1 k2).  The conv kernels' fused BatchNorm backward reads
+// it as well (ConvParams::bn_coef).
+enum BnCoefRow { BN_MEAN, BN_INVSTD, BN_SCALE, BN_SHIFT, BN_K, BN_COEF_ROWS = BN_K + 3 };
+inline float* bn_coef(float* block, int C, BnCoefRow row) { return block + (long)row * C; }
+inline const float* bn_coef(const float* block, int C, BnCoefRow row) { return block + (long)row * C; }
+
+// eval mode: scale / shift from the running statistics, every BatchNorm of a network in one launch: the scale and shift
+// rows of each coefficient block
 struct BnEvalEntry {
   uint32_t g_off, b_off, rm_off, rv_off;  // floats into params / bnstats
-  uint32_t coef_off16;                     // 16-byte units into the workspace
+  uint32_t coef_off16;                     // the coefficient block: 16-byte units into the workspace
   int32_t C;
 };
 struct BnEvalTable {
   int n;
   BnEvalEntry e[PACK_MAX_LAYERS];
 };
-int bn_eval_coeff_all_launch(const float* params, const float* bnstats, void* ws, float eps, const BnEvalTable& t,
+int bn_eval_coeff_all_launch(const float* params, const float* bnstats, void* ws, const BnEvalTable& t,
                              hipStream_t stream);
-// a = act(y*scale + shift + residual),  residual = res (activation) or yr*scale_r + shift_r
-int bn_apply_launch(int dtype, const void* y, const float* scale, const float* shift,
-                    const void* res, const void* yr, const float* scale_r, const float* shift_r,
-                    int relu, void* out, long rows, int C, hipStream_t stream, const NetSplit* ns = nullptr);
-// backward: dz = dA * (a > 0 if a given);  partial sums of dz and dz*xhat
-int bn_bwd_reduce_launch(int dtype, const void* dA, const void* a, const void* y,
-                         const float* mean, const float* invstd, float* partial, int* nblocks,
-                         long rows, int C, hipStream_t stream, const float* mask_scale = nullptr,
-                         const float* mask_shift = nullptr, const NetSplit* ns = nullptr);
-int bn_bwd_reduce_blocks(long rows, int C, int dtype);
-int bn_bwd_finalize_launch(const float* partial, int nblocks, int C, long count,
-                           const float* gamma, const float* invstd, float* dgamma, float* dbeta,
-                           int accumulate, float* coef /*[3][C]*/, hipStream_t stream, const NetSplit* ns = nullptr);
-// dy = k1*(dz - k2 - xhat*k3); optionally dz -> dres (+= if dres_acc)
-int bn_bwd_apply_launch(int dtype, const void* dA, const void* a, const void* y, const float* mean,
-                        const float* invstd, const float* coef, void* dy, void* dres, int dres_acc,
-                        long rows, int C, hipStream_t stream, const float* mask_scale = nullptr,
-                        const float* mask_shift = nullptr, const NetSplit* ns = nullptr);
 
-// bn_fused.hip: the finalize step folded into the streaming pass (fp32 tensors, C % 32 == 0, few partial rows)
-bool bn_fused_finalize_ok(int dtype, int stat_rows, int C);
-int bn_finalize_apply_launch(int dtype, const float* stats, int stat_rows, int C, int Cpad, long count, const float* gamma,
-                             const float* beta, float eps, float momentum, float* running_mean,
-                             float* running_var, float* mean, float* invstd, float* scale, float* shift,
-                             const void* y, const void* res, const void* yr, const float* scale_r,
-                             const float* shift_r, int relu, void* out, long rows, hipStream_t stream,
-                             const NetSplit* ns = nullptr, int plan_nets = 1);
-int bn_bwd_finalize_apply_launch(int dtype, const float* partial, int nblocks, int C, long count, const float* gamma,
-                                 const float* mean, const float* invstd, float* dgamma, float* dbeta,
-                                 int accumulate, float* coef, const void* dA, const void* a, const void* y, void* dy,
-                                 void* dres, int dres_acc, long rows, hipStream_t stream,
-                                 const float* mask_scale = nullptr, const float* mask_shift = nullptr,
-                                 const NetSplit* ns = nullptr, int plan_nets = 1);
+// Train mode.  Forward: the conv epilogue's per-tile (sum, sum of squares) rows -> mean / invstd (saved for backward),
+// folded scale / shift and the running statistics (momentum, unbiased variance, like torch.nn.BatchNorm2d), then
+// a = act(y*scale + shift + residual).  Backward: partial sums of dz = dA*[mask] and dz*xhat -> dgamma, dbeta and
+// k -> dy = k0*(dz - k1 - xhat*k2), dz -> the residual's gradient.
+enum BnResidual { BN_RES_NONE, BN_RES_TENSOR, BN_RES_LAYER };  // + an activation, or + another layer's y*scale + shift
+enum BnMask { BN_MASK_NONE, BN_MASK_FROM_Y, BN_MASK_FROM_A };    // the backward's ReLU mask: y*scale+shift > 0, a > 0
+struct BnLayer {
+  // ---- description ----
+  std::string name;          // module path (error messages)
+  int C = 0, Cpad = 0;       // channels; the forward statistics rows' stride (the conv's CoutPad)
+  long rows = 0;             // rows (pixels) per network
+  int dtype = D3F_F32;       // storage dtype
+  int plan_nets = 1;         // networks whose workgroups the fused passes count (ConvLayer::plan_nets)
+  bool apply = true, relu = true;  // apply false: a downsample branch, only finalized (its consumer applies it)
+  BnResidual res = BN_RES_NONE;
+  BnMask mask = BN_MASK_NONE;
+  int fwd_rows = 0;          // forward partial rows: the conv's fwd.stat_rows, or wino_rows for a Winograd layer
+  int fused_rows = 0;        // > 0: backward partial rows already written by the producing data gradient
+  bool allow_fused = false;  // the finalize may fold into the streaming pass (the engine, not the C API)
+  // ---- plan (bn_layer_plan) ----
+  bool fwd_fused = false, bwd_fused = false;  // finalize folded into the streaming pass (fp32 / bf16, C % 32, few rows)
+  int reduce_blocks = 0;     // bn_bwd_reduce's workgroups = its partial rows
+  int bwd_rows = 0;          // the backward's partial rows: fused_rows, or reduce_blocks
+  long rows_per_block = 0;   // the fused passes' rows per workgroup
+  size_t stat_floats = 0;    // scratch: forward statistics rows, fwd_rows x Cpad x 2
+  size_t part_floats = 0;    // scratch: backward partial sums (as many rows as the reduce writes, at least)
+};
+void bn_layer_plan(BnLayer& L);
+// Buffers of one call, net 0's (ns: two networks in one launch, common.h NetSplit).
+struct BnBufs {
+  float* stats = nullptr;     // forward: the statistics rows; backward: the partial sums
+  const float *gamma = nullptr, *beta = nullptr;
+  float *running_mean = nullptr, *running_var = nullptr;  // updated by the forward pass (null: not tracked)
+  float* coef = nullptr;      // the layer's coefficient block
+  float* k = nullptr;         // the backward's k rows when not the block's own (the C API's workspace)
+  const void* y = nullptr;    // raw conv output
+  void* a = nullptr;          // forward: written; backward: the ReLU mask of BN_MASK_FROM_A
+  const void* res = nullptr;  // residual: the activation (BN_RES_TENSOR) or the other layer's y (BN_RES_LAYER)
+  const float* res_coef = nullptr;  // BN_RES_LAYER: the other layer's coefficient block
+  const void* dA = nullptr;   // backward: gradient w.r.t. a
+  void* dy = nullptr;         // backward: gradient w.r.t. y
+  void* dres = nullptr;       // backward, optional: dz for the residual branch, added to it with dres_acc
+  int dres_acc = 0;
+  float *dgamma = nullptr, *dbeta = nullptr;
+};
+// synchronised statistics across data-parallel ranks: fn sum-all-reduces `count` floats in place, ordered on `stream`
+struct BnSync {
+  int (*fn)(void* ctx, float* data, int64_t count, void* stream);
+  void* ctx;
+  int world;
+};
+// The planned form, or with sync: the split form over the all-reduced sums (count = rows x world; dgamma / dbeta stay
+// the LOCAL sums, summed over ranks with the other gradients).
+int bn_layer_forward(const BnLayer& L, const BnBufs& b, const BnSync* sync, hipStream_t stream,
+                     const NetSplit* ns = nullptr);
+int bn_layer_backward(const BnLayer& L, const BnBufs& b, const BnSync* sync, hipStream_t stream,
+                      const NetSplit* ns = nullptr);
+// the split forward's two steps on their own: statistics over `count` rows -> coefficients (+ running statistics), and
+// the streaming pass
+int bn_layer_finalize(const BnLayer& L, const BnBufs& b, long count, hipStream_t stream, const NetSplit* ns = nullptr);
+int bn_layer_apply(const BnLayer& L, const BnBufs& b, hipStream_t stream, const NetSplit* ns = nullptr);
 
 // ---- pooling / resampling / layout (K6, K8 backward, boundary) ---------------------------
 int maxpool3x3s2_fwd_launch(int dtype, const void* in, void* out, uint8_t* idx, int B, int H, int W,

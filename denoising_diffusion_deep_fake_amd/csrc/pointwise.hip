@@ -1,440 +1,15 @@
-// HBM-bound kernels of the U-Net hot path: BatchNorm (train / eval, forward / backward),
-// ReLU + residual add, 3x3/s2 max-pool, 2x2 sum (backward of nearest up-sampling), layout
-// conversion at the NCHW boundary and weight packing.  All activations NHWC, every access a
-// 16-byte vector per lane, grid-stride over at most 2048 workgroups.
+// HBM-bound kernels of the U-Net hot path: 3x3/s2 max-pool, 2x2 sum (backward of nearest
+// up-sampling), layout conversion at the NCHW boundary and weight packing (BatchNorm, ReLU and
+// the residual add: batchnorm.hip).  All activations NHWC, every access a 16-byte vector per
+// lane, grid-stride over at most 2048 workgroups.
 //
-// These replace the ATen batch_norm / relu / add / max_pool2d / upsample_nearest2d / cat
-// kernels (forward and autograd backward) the reference's U-Net dispatches
-// (semantics: SURVEY.md Appendix A.1).
+// These replace the ATen max_pool2d / upsample_nearest2d / cat kernels (forward and autograd
+// backward) the reference's U-Net dispatches (semantics: SURVEY.md
+// Appendix A.1).
 #include "pointwise.h"
+#include "vec16.h"
 
 namespace d3f {
-
-template <typename T> struct V16;
-template <> struct V16<float> {
-  static constexpr int N = 4;
-  static __device__ __forceinline__ void load(const float* p, float (&o)[4]) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&o)[4]) {
-    *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
-  }
-};
-template <> struct V16<bf16_t> {
-  static constexpr int N = 8;
-  static __device__ __forceinline__ void load(const bf16_t* p, float (&o)[8]) {
-    const uint4 t = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      o[2 * i] = __uint_as_float(w[i] << 16);
-      o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ void store(bf16_t* p, const float (&o)[8]) {
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      w[i] = (uint32_t)f32_to_bf16(o[2 * i]) | ((uint32_t)f32_to_bf16(o[2 * i + 1]) << 16);
-    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-};
-
-static inline int grid_for(long work_items, int per_block = 256, int cap = 2048) {
-  long b = (work_items + per_block - 1) / per_block;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-// ------------------------------------------------------------------------------------------
-// BatchNorm forward
-// ------------------------------------------------------------------------------------------
-// one workgroup per channel: 256 lanes stride over the m-tile partials (up to 8192 of them for the
-// 256x16 tiles), f64 accumulation, wave shuffle + LDS tree
-__device__ __forceinline__ void block_sum2(double& s1, double& s2) {
-  __shared__ double red[2][4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s1 += __shfl_xor(s1, o);
-    s2 += __shfl_xor(s2, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = s1;
-    red[1][threadIdx.x >> 6] = s2;
-  }
-  __syncthreads();
-  s1 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-  s2 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-}
-
-__global__ __launch_bounds__(256) void bn_finalize_kernel(
-    const float* __restrict__ stats, int tiles, int C, int Cpad, double count,
-    const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float momentum,
-    float* __restrict__ running_mean, float* __restrict__ running_var, float* __restrict__ mean_o,
-    float* __restrict__ invstd_o, float* __restrict__ scale_o, float* __restrict__ shift_o, NetSplit ns) {
-  chain_priority();
-  if (blockIdx.z != 0) {  // two networks in one launch (common.h, NetSplit): blockIdx.z = net
-    net_shift(stats, ns.ws); net_shift(gamma, ns.par); net_shift(beta, ns.par);
-    net_shift(running_mean, ns.bn); net_shift(running_var, ns.bn);
-    net_shift(mean_o, ns.ws); net_shift(invstd_o, ns.ws); net_shift(scale_o, ns.ws); net_shift(shift_o, ns.ws);
-  }
-  const int c = blockIdx.x;
-  double s1 = 0.0, s2 = 0.0;
-  for (int t = threadIdx.x; t < tiles; t += 256) {
-    const float2 v = *reinterpret_cast<const float2*>(stats + ((long)t * Cpad + c) * 2);
-    s1 += (double)v.x;
-    s2 += (double)v.y;
-  }
-  block_sum2(s1, s2);
-  if (threadIdx.x == 0) {
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double invstd = 1.0 / sqrt(var + (double)eps);
-    const float g = gamma[c], b = beta[c];
-    mean_o[c] = (float)mean;
-    invstd_o[c] = (float)invstd;
-    scale_o[c] = (float)((double)g * invstd);
-    shift_o[c] = (float)((double)b - mean * (double)g * invstd);
-    if (running_mean != nullptr) {
-      const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-      running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * mean);
-      running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * unbiased);
-    }
-  }
-}
-
-int bn_finalize_launch(const float* stats, int tiles, int C, int Cpad, long count,
-                       const float* gamma, const float* beta, float eps, float momentum,
-                       float* running_mean, float* running_var, float* mean, float* invstd,
-                       float* scale, float* shift, hipStream_t stream, const NetSplit* ns) {
-  const NetSplit nv = net_split_or_single(ns);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C, 1, nv.nets), dim3(256), 0, stream, stats, tiles, C,
-                     Cpad, (double)count, gamma, beta, eps, momentum, running_mean, running_var, mean,
-                     invstd, scale, shift, nv);
-  D3F_HIP(hipGetLastError());
-  return 0;
-}
-
-// every BatchNorm of the network in one launch (eval forward): block = layer, table as kernel argument
-__global__ __launch_bounds__(256) void bn_eval_coeff_all_kernel(const float* __restrict__ params,
-                                                                const float* __restrict__ bnstats,
-                                                                char* __restrict__ ws, float eps, BnEvalTable t) {
-  const BnEvalEntry e = t.e[blockIdx.x];
-  float* __restrict__ coef = reinterpret_cast<float*>(ws + (size_t)e.coef_off16 * 16);
-  for (int c = threadIdx.x; c < e.C; c += 256) {
-    const float invstd = 1.0f / sqrtf(bnstats[e.rv_off + c] + eps);
-    const float sc = params[e.g_off + c] * invstd;
-    coef[2 * e.C + c] = sc;
-    coef[3 * e.C + c] = params[e.b_off + c] - bnstats[e.rm_off + c] * sc;
-  }
-}
-
-int bn_eval_coeff_all_launch(const float* params, const float* bnstats, void* ws, float eps, const BnEvalTable& t,
-                             hipStream_t stream) {
-  if (t.n == 0) return 0;
-  hipLaunchKernelGGL(bn_eval_coeff_all_kernel, dim3(t.n), dim3(256), 0, stream, params, bnstats, (char*)ws, eps, t);
-  D3F_HIP(hipGetLastError());
-  return 0;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void bn_apply_kernel(
-    const T* __restrict__ y, const float* __restrict__ scale, const float* __restrict__ shift,
-    const T* __restrict__ res, const T* __restrict__ yr, const float* __restrict__ scale_r,
-    const float* __restrict__ shift_r, int relu, T* __restrict__ out, long nvec, int C, long net_ws) {
-  chain_priority();
-  if (blockIdx.z != 0) {  // two networks in one launch (common.h, NetSplit): every operand lives in the workspace
-    net_shift(y, net_ws); net_shift(scale, net_ws); net_shift(shift, net_ws); net_shift(res, net_ws); net_shift(yr, net_ws);
-    net_shift(scale_r, net_ws); net_shift(shift_r, net_ws); net_shift(out, net_ws);
-  }
-  constexpr int N = V16<T>::N;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-    const int c0 = (int)((i * N) % C);
-    float v[N], sc[N], sf[N];
-    V16<T>::load(y + i * N, v);
-#pragma unroll
-    for (int k = 0; k < N; k += 4) {
-      const float4 a = *reinterpret_cast<const float4*>(scale + c0 + k);
-      const float4 b = *reinterpret_cast<const float4*>(shift + c0 + k);
-      sc[k] = a.x; sc[k + 1] = a.y; sc[k + 2] = a.z; sc[k + 3] = a.w;
-      sf[k] = b.x; sf[k + 1] = b.y; sf[k + 2] = b.z; sf[k + 3] = b.w;
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = v[k] * sc[k] + sf[k];
-    if (res != nullptr) {
-      float r[N];
-      V16<T>::load(res + i * N, r);
-#pragma unroll
-      for (int k = 0; k < N; ++k) v[k] += r[k];
-    } else if (yr != nullptr) {
-      float r[N];
-      V16<T>::load(yr + i * N, r);
-#pragma unroll
-      for (int k = 0; k < N; ++k) v[k] += r[k] * scale_r[c0 + k] + shift_r[c0 + k];
-    }
-    if (relu) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) v[k] = fmaxf(v[k], 0.f);
-    }
-    V16<T>::store(out + i * N, v);
-  }
-}
-
-int bn_apply_launch(int dtype, const void* y, const float* scale, const float* shift,
-                    const void* res, const void* yr, const float* scale_r, const float* shift_r,
-                    int relu, void* out, long rows, int C, hipStream_t stream, const NetSplit* ns) {
-  const int ve = dtype == D3F_F32 ? 4 : 8;
-  D3F_CHECK(C % ve == 0 && (256 * ve) % C == 0, "bn_apply: C=%d must divide %d", C, 256 * ve);
-  const long nvec = rows * C / ve;
-  if (nvec == 0) return 0;
-  const NetSplit nv = net_split_or_single(ns);
-  const dim3 grid(grid_for(nvec), 1, nv.nets);
-  if (dtype == D3F_F32)
-    hipLaunchKernelGGL(bn_apply_kernel<float>, grid, dim3(256), 0, stream, (const float*)y, scale,
-                       shift, (const float*)res, (const float*)yr, scale_r, shift_r, relu, (float*)out,
-                       nvec, C, nv.ws);
-  else
-    hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)y,
-                       scale, shift, (const bf16_t*)res, (const bf16_t*)yr, scale_r, shift_r, relu,
-                       (bf16_t*)out, nvec, C, nv.ws);
-  D3F_HIP(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// BatchNorm backward.  dz = dA * [a > 0];  dbeta = sum dz;  dgamma = sum dz * xhat;
-// dy = gamma*invstd * (dz - dbeta/N - xhat * dgamma/N)
-// ------------------------------------------------------------------------------------------
-int bn_bwd_reduce_blocks(long rows, int C, int dtype) {
-  // a block covers at least one unrolled trip (4 passes of 256 threads) and 16 rows; small tensors then
-  // still spread over enough CUs to hide the load latency
-  const int ve = dtype == D3F_F32 ? 4 : 8;
-  const long per_trip = 4L * (256 / std::max(1, std::min(256, C / ve)));
-  const long min_rows = std::max(16L, per_trip);
-  long b = (rows + min_rows - 1) / min_rows;
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-// ReLU mask: from the saved activation `a` (a > 0), or -- for layers without a residual, mask_scale !=
-// null -- recomputed from y with the forward's own arithmetic (y*scale + shift > 0), which saves reading `a`.
-template <typename T>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
-    const T* __restrict__ dA, const T* __restrict__ a, const T* __restrict__ y,
-    const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ partial,
-    long rows, int C, const float* __restrict__ mask_scale, const float* __restrict__ mask_shift, long net_ws) {
-  chain_priority();
-  if (blockIdx.z != 0) {  // two networks in one launch (common.h, NetSplit): every operand lives in the workspace
-    net_shift(dA, net_ws); net_shift(a, net_ws); net_shift(y, net_ws); net_shift(mean, net_ws); net_shift(invstd, net_ws);
-    net_shift(partial, net_ws); net_shift(mask_scale, net_ws); net_shift(mask_shift, net_ws);
-  }
-  constexpr int N = V16<T>::N;
-  __shared__ float red[256 * N * 2];
-  const int VC = C / N;        // vectors per row (power of two, <= 256)
-  const int RP = 256 / VC;     // rows per pass
-  const int cv = threadIdx.x % VC, r0 = threadIdx.x / VC;
-  const long rows_per_block = (rows + gridDim.x - 1) / gridDim.x;
-  const long rbeg = (long)blockIdx.x * rows_per_block;
-  long rend = rbeg + rows_per_block;
-  if (rend > rows) rend = rows;
-  float mu[N], is[N], s1[N], s2[N], msc[N], msf[N];
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    mu[k] = mean[cv * N + k];
-    is[k] = invstd[cv * N + k];
-    msc[k] = mask_scale ? mask_scale[cv * N + k] : 0.f;
-    msf[k] = mask_scale ? mask_shift[cv * N + k] : 0.f;
-    s1[k] = 0.f;
-    s2[k] = 0.f;
-  }
-  // U rows per trip: all loads of a trip are issued before any arithmetic (memory-level parallelism)
-  constexpr int U = 4;
-  const bool from_y = mask_scale != nullptr, from_a = !from_y && a != nullptr;
-  long r = rbeg + r0;
-  for (; r + (U - 1) * RP < rend; r += U * RP) {
-    float g[U][N], yy[U][N], aa[U][N];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long off = (r + u * RP) * C + cv * N;
-      V16<T>::load(dA + off, g[u]);
-      V16<T>::load(y + off, yy[u]);
-      if (from_a) V16<T>::load(a + off, aa[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) {
-        const float keep = from_y ? yy[u][k] * msc[k] + msf[k] : (from_a ? aa[u][k] : 1.f);
-        const float gz = keep > 0.f ? g[u][k] : 0.f;
-        s1[k] += gz;
-        s2[k] += gz * ((yy[u][k] - mu[k]) * is[k]);
-      }
-    }
-  }
-  for (; r < rend; r += RP) {
-    const long off = r * C + cv * N;
-    float g[N], yy[N], aa[N];
-    V16<T>::load(dA + off, g);
-    V16<T>::load(y + off, yy);
-    if (from_a) V16<T>::load(a + off, aa);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      const float keep = from_y ? yy[k] * msc[k] + msf[k] : (from_a ? aa[k] : 1.f);
-      const float gz = keep > 0.f ? g[k] : 0.f;
-      s1[k] += gz;
-      s2[k] += gz * ((yy[k] - mu[k]) * is[k]);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    red[(threadIdx.x * N + k) * 2 + 0] = s1[k];
-    red[(threadIdx.x * N + k) * 2 + 1] = s2[k];
-  }
-  __syncthreads();
-  // thread t < 2*C sums column t over the RP row groups
-  for (int t = threadIdx.x; t < 2 * C; t += 256) {
-    const int c = t >> 1, which = t & 1;
-    const int v = c / N, k = c % N;
-    float s = 0.f;
-    for (int rr = 0; rr < RP; ++rr) s += red[((rr * VC + v) * N + k) * 2 + which];
-    partial[((long)blockIdx.x * C + c) * 2 + which] = s;
-  }
-}
-
-int bn_bwd_reduce_launch(int dtype, const void* dA, const void* a, const void* y,
-                         const float* mean, const float* invstd, float* partial, int* nblocks,
-                         long rows, int C, hipStream_t stream, const float* mask_scale,
-                         const float* mask_shift, const NetSplit* ns) {
-  const int ve = dtype == D3F_F32 ? 4 : 8;
-  const int vc = C / ve;
-  D3F_CHECK(C % ve == 0 && vc >= 1 && vc <= 256 && (256 % vc) == 0,
-            "bn_bwd_reduce: unsupported channel count %d", C);
-  const int blocks = bn_bwd_reduce_blocks(rows, C, dtype);
-  *nblocks = blocks;
-  const NetSplit nv = net_split_or_single(ns);
-  const dim3 grid(blocks, 1, nv.nets);
-  if (dtype == D3F_F32)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, grid, dim3(256), 0, stream,
-                       (const float*)dA, (const float*)a, (const float*)y, mean, invstd, partial, rows, C,
-                       mask_scale, mask_shift, nv.ws);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, grid, dim3(256), 0, stream,
-                       (const bf16_t*)dA, (const bf16_t*)a, (const bf16_t*)y, mean, invstd, partial, rows, C,
-                       mask_scale, mask_shift, nv.ws);
-  D3F_HIP(hipGetLastError());
-  return 0;
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(
-    const float* __restrict__ partial, int nblocks, int C, double count,
-    const float* __restrict__ gamma, const float* __restrict__ invstd, float* __restrict__ dgamma,
-    float* __restrict__ dbeta, int accumulate, float* __restrict__ coef, NetSplit ns) {
-  chain_priority();
-  if (blockIdx.z != 0) {  // two networks in one launch (common.h, NetSplit)
-    net_shift(partial, ns.ws); net_shift(gamma, ns.par); net_shift(invstd, ns.ws);
-    net_shift(dgamma, ns.grad); net_shift(dbeta, ns.grad); net_shift(coef, ns.ws);
-  }
-  const int c = blockIdx.x;
-  double s1 = 0.0, s2 = 0.0;
-  for (int t = threadIdx.x; t < nblocks; t += 256) {
-    const float2 v = *reinterpret_cast<const float2*>(partial + ((long)t * C + c) * 2);
-    s1 += (double)v.x;
-    s2 += (double)v.y;
-  }
-  block_sum2(s1, s2);
-  if (threadIdx.x == 0) {
-    const float db = (float)s1, dg = (float)s2;
-    if (dgamma != nullptr) {
-      dgamma[c] = accumulate ? dgamma[c] + dg : dg;
-      dbeta[c] = accumulate ? dbeta[c] + db : db;
-    }
-    coef[c] = gamma[c] * invstd[c];
-    coef[C + c] = (float)(s1 / count);
-    coef[2 * C + c] = (float)(s2 / count);
-  }
-}
-
-int bn_bwd_finalize_launch(const float* partial, int nblocks, int C, long count,
-                           const float* gamma, const float* invstd, float* dgamma, float* dbeta,
-                           int accumulate, float* coef, hipStream_t stream, const NetSplit* ns) {
-  const NetSplit nv = net_split_or_single(ns);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C, 1, nv.nets), dim3(256), 0, stream, partial, nblocks,
-                     C, (double)count, gamma, invstd, dgamma, dbeta, accumulate, coef, nv);
-  D3F_HIP(hipGetLastError());
-  return 0;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
-    const T* __restrict__ dA, const T* __restrict__ a, const T* __restrict__ y,
-    const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ coef,
-    T* __restrict__ dy, T* __restrict__ dres, int dres_acc, long nvec, int C,
-    const float* __restrict__ mask_scale, const float* __restrict__ mask_shift, long net_ws) {
-  chain_priority();
-  if (blockIdx.z != 0) {  // two networks in one launch (common.h, NetSplit): every operand lives in the workspace
-    net_shift(dA, net_ws); net_shift(a, net_ws); net_shift(y, net_ws); net_shift(mean, net_ws); net_shift(invstd, net_ws);
-    net_shift(coef, net_ws); net_shift(dy, net_ws); net_shift(dres, net_ws); net_shift(mask_scale, net_ws);
-    net_shift(mask_shift, net_ws);
-  }
-  constexpr int N = V16<T>::N;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-    const int c0 = (int)((i * N) % C);
-    float g[N], yy[N], o[N];
-    V16<T>::load(dA + i * N, g);
-    V16<T>::load(y + i * N, yy);
-    if (mask_scale != nullptr) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) g[k] = (yy[k] * mask_scale[c0 + k] + mask_shift[c0 + k]) > 0.f ? g[k] : 0.f;
-    } else if (a != nullptr) {
-      float aa[N];
-      V16<T>::load(a + i * N, aa);
-#pragma unroll
-      for (int k = 0; k < N; ++k) g[k] = aa[k] > 0.f ? g[k] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      const int c = c0 + k;
-      const float xhat = (yy[k] - mean[c]) * invstd[c];
-      o[k] = coef[c] * (g[k] - coef[C + c] - xhat * coef[2 * C + c]);
-    }
-    V16<T>::store(dy + i * N, o);
-    if (dres != nullptr) {
-      if (dres_acc) {
-        float d[N];
-        V16<T>::load(dres + i * N, d);
-#pragma unroll
-        for (int k = 0; k < N; ++k) g[k] += d[k];
-      }
-      V16<T>::store(dres + i * N, g);
-    }
-  }
-}
-
-int bn_bwd_apply_launch(int dtype, const void* dA, const void* a, const void* y, const float* mean,
-                        const float* invstd, const float* coef, void* dy, void* dres, int dres_acc,
-                        long rows, int C, hipStream_t stream, const float* mask_scale,
-                        const float* mask_shift, const NetSplit* ns) {
-  const int ve = dtype == D3F_F32 ? 4 : 8;
-  D3F_CHECK(C % ve == 0 && (256 * ve) % C == 0, "bn_bwd_apply: C=%d must divide %d", C, 256 * ve);
-  const long nvec = rows * C / ve;
-  if (nvec == 0) return 0;
-  const NetSplit nv = net_split_or_single(ns);
-  const dim3 grid(grid_for(nvec), 1, nv.nets);
-  if (dtype == D3F_F32)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, dim3(256), 0, stream, (const float*)dA,
-                       (const float*)a, (const float*)y, mean, invstd, coef, (float*)dy, (float*)dres,
-                       dres_acc, nvec, C, mask_scale, mask_shift, nv.ws);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)dA,
-                       (const bf16_t*)a, (const bf16_t*)y, mean, invstd, coef, (bf16_t*)dy, (bf16_t*)dres,
-                       dres_acc, nvec, C, mask_scale, mask_shift, nv.ws);
-  D3F_HIP(hipGetLastError());
-  return 0;
-}
 
 // ------------------------------------------------------------------------------------------
 // MaxPool2d(3, stride 2, padding 1): first maximum in (kh, kw) scan order wins, like ATen.
