@@ -25,6 +25,7 @@ class ConvDesc(C.Structure):
 
 
 _p, _i, _i64, _f, _sz, _dbl = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_double
+_u64, _u32p = C.c_uint64, C.POINTER(C.c_uint32)
 _desc = C.POINTER(ConvDesc)
 
 # name -> (restype, argtypes); must list every symbol include/d3f_hip.h declares
@@ -102,6 +103,12 @@ PROTOTYPES = {
     "d3f_mse_ssim_loss": (_i, [_p, _p, _f, _f, _p, _p, _p, _i, _i, _i, _p]),
     "d3f_adam_step": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _i, _f, _p]),
     "d3f_ema_lerp": (_i, [_p, _p, _i64, _f, _p]),
+    "d3f_philox4x32_10": (_i, [_u32p, _u32p, _u32p]),
+    "d3f_noise_blend_rng": (_i, [_p, _u64, _u64, _f, _p, _p, _i, _i64, _p]),
+    "d3f_noise_blend_fixed_rng": (_i, [_p, _u64, _u64, _p, _p, _i, _i64, _p]),
+    "d3f_noise_draw": (_i, [_u64, _u64, _p, _p, _i, _i64, _p]),
+    "d3f_affine_warp_rng": (_i, [_p, _p, _u64, _u64, _i, C.POINTER(_f), _i, _i, _i, _i, _p]),
+    "d3f_affine_theta_draw": (_i, [_u64, _u64, _i, C.POINTER(_f), _p, _p, _i, _i, _i, _p]),
 }
 
 # d3f_allreduce_fn: int (*)(void* ctx, float* data, int64_t count, void* stream)

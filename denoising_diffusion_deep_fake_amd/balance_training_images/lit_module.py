@@ -11,11 +11,13 @@ Device work is HIP: ops.noise_blend_fixed, the Unet engine, the fused loss, ops.
 reference, on purpose: TensorBoard image / histogram logging is dropped (no tensorboard / matplotlib on the box);
 the reference accepts `--output_list` but never writes it (dead option) -- here the classes ARE written, one
 "<relative image path>\\t<class>" line per image, when `output_image_list_path` is set.
+`device_rng: true` (off by default; optional `rng_seed`): the noise is drawn inside the blend kernel by the counter-based
+generator (rng.py, csrc/philox.h), a function of (seed, global_step or validation batch index, rank).
 """
 import torch
 from torch.utils.data import DataLoader
 
-from .. import ops
+from .. import ops, rng
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset
 from ..lightning import LightningModule
 from ..loss_functions import MseStructuralSimilarityLoss
@@ -73,7 +75,10 @@ class LitModule(LightningModule):
         return loss
 
     @torch.no_grad()
-    def blend_fixed_amount_of_noise_with_each_sample(self, batch):
+    def blend_fixed_amount_of_noise_with_each_sample(self, batch, step=None):
+        if self.hparams.get("device_rng", False):  # the normals are drawn inside the blend kernel (rng.py, csrc/philox.h)
+            seed, offset = rng.module_stream(self, 0, step)
+            return ops.noise_blend_fixed_rng(batch, seed, offset, float(self.hparams.ratio_of_noise))
         noise = torch.randn_like(batch)
         return ops.noise_blend_fixed(batch, noise, float(self.hparams.ratio_of_noise))
 
@@ -81,7 +86,8 @@ class LitModule(LightningModule):
     def validation_step(self, batch, batch_idx):
         image = batch["image"]
         image_index = batch["index"]
-        image_noisy = self.blend_fixed_amount_of_noise_with_each_sample(image)
+        # (device_rng: validation has no optimiser step to count -- the batch index names the draws)
+        image_noisy = self.blend_fixed_amount_of_noise_with_each_sample(image, step=batch_idx)
         image_prediction = self.model(image_noisy)
         difficulty_loss = self.compute_difficulty_loss(image_prediction, image)
         return {"index": torch.as_tensor(image_index).cpu(), "loss": difficulty_loss.cpu()}

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "philox.h"
 
 namespace d3f {
 static thread_local char g_err[1024] = "";
@@ -550,6 +551,25 @@ int d3f_affine_warp(const float* in, const float* theta, float* out, int B, int 
   return affine_warp_launch(in, theta, out, B, C, H, W, (hipStream_t)stream);
 }
 
+int d3f_affine_warp_rng(const float* in, float* out, uint64_t seed, uint64_t offset, int kind, const float params[5],
+                        int B, int C, int H, int W, void* stream) {
+  if (B == 0) return 0;
+  D3F_CHECK(in && out && params && in != out, "affine_warp_rng: null or aliased argument");
+  D3F_CHECK(B >= 0 && C > 0 && H > 0 && W > 0, "affine_warp_rng: bad shape");
+  AffineRngParams q;
+  if (int rc = affine_rng_params(kind, params, H, W, q)) return rc;
+  return affine_warp_rng_launch(in, out, seed, offset, q, B, C, H, W, (hipStream_t)stream);
+}
+int d3f_affine_theta_draw(uint64_t seed, uint64_t offset, int kind, const float params[5], float* theta, uint8_t* apply,
+                          int B, int H, int W, void* stream) {
+  if (B == 0) return 0;
+  D3F_CHECK(params && theta && apply, "affine_theta_draw: null argument");
+  D3F_CHECK(B >= 0, "affine_theta_draw: bad shape");
+  AffineRngParams q;
+  if (int rc = affine_rng_params(kind, params, H, W, q)) return rc;
+  return affine_theta_draw_launch(seed, offset, q, theta, apply, B, (hipStream_t)stream);
+}
+
 int d3f_nchw_to_nhwc(int dtype, const float* in, void* out, int B, int C, int H, int W, int Cpad, void* stream) {
   D3F_CHECK(in && out && Cpad >= C, "nchw_to_nhwc: argument");
   return nchw_to_nhwc_launch(sdt(dtype), in, out, B, C, H, W, Cpad, (hipStream_t)stream);
@@ -572,6 +592,32 @@ int d3f_noise_blend_fixed(const float* x, const float* noise, const float* r, fl
   if (B == 0 || per_image == 0) return 0;
   D3F_CHECK(x && noise && r && out, "noise_blend_fixed: null argument");
   return noise_blend_fixed_launch(x, noise, r, out, B, (long)per_image, (hipStream_t)stream);
+}
+int d3f_philox4x32_10(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]) {
+  D3F_CHECK(counter && key && out, "philox4x32_10: null argument");
+  const Philox4 p = philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1]);
+  for (int i = 0; i < 4; ++i) out[i] = p.x[i];
+  return 0;
+}
+int d3f_noise_blend_rng(const float* x, uint64_t seed, uint64_t offset, float lam, float* out, float* r_out_or_null,
+                        int B, int64_t per_image, void* stream) {
+  if (B == 0 || per_image == 0) return 0;
+  D3F_CHECK(x && out && x != out, "noise_blend_rng: null or aliased argument");
+  D3F_CHECK(B > 0 && per_image > 0, "noise_blend_rng: bad shape");
+  return noise_blend_rng_launch(x, seed, offset, lam, out, r_out_or_null, B, (long)per_image, (hipStream_t)stream);
+}
+int d3f_noise_blend_fixed_rng(const float* x, uint64_t seed, uint64_t offset, const float* r, float* out, int B,
+                              int64_t per_image, void* stream) {
+  if (B == 0 || per_image == 0) return 0;
+  D3F_CHECK(x && r && out && x != out, "noise_blend_fixed_rng: null or aliased argument");
+  D3F_CHECK(B > 0 && per_image > 0, "noise_blend_fixed_rng: bad shape");
+  return noise_blend_fixed_rng_launch(x, seed, offset, r, out, B, (long)per_image, (hipStream_t)stream);
+}
+int d3f_noise_draw(uint64_t seed, uint64_t offset, float* noise_or_null, float* y_or_null, int B, int64_t per_image,
+                   void* stream) {
+  if (B == 0) return 0;
+  D3F_CHECK(B > 0 && per_image >= 0, "noise_draw: bad shape");
+  return noise_draw_launch(seed, offset, noise_or_null, y_or_null, B, (long)per_image, (hipStream_t)stream);
 }
 size_t d3f_l1_per_image_workspace_bytes(int B) { return l1_per_image_workspace_bytes(B); }
 int d3f_l1_per_image(const float* prediction, const float* target, float* out, void* workspace, int B,

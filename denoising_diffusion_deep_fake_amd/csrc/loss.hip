@@ -13,6 +13,7 @@
 // maps with the adjoint (zero-padded) Gaussian and adds the MSE gradient, so the loss and
 // d loss / d prediction cost 2 stencil passes over the images instead of ~15 torch kernels.
 #include "pointwise.h"
+#include "philox.h"
 
 namespace d3f {
 
@@ -328,6 +329,30 @@ int mse_ssim_loss_launch(const float* pred, const float* target, float in_min, f
 }
 
 // ------------------------------------------------------------------------------------------
+// the blend's per-image coefficients and its four-element body: ONE expression for the kernel that loads its draws and
+// for the ones that draw inside (noise_blend_rng_kernel), so that the same z and y give the same bits
+struct BlendCoef {
+  float r, sa, sb;
+};
+__device__ __forceinline__ BlendCoef blend_coef(float y, float c, float one_minus_c, float inv_lam) {
+  // x = 1/lam * log(1 / (y*(1-c) + c))   -- every step rounded to f32 like the torch expression
+  const float t = __fadd_rn(__fmul_rn(y, one_minus_c), c);
+  // log / sqrt evaluated in double and rounded once: correctly rounded f32 results (the device's
+  // f32 logf / sqrtf are 1-2 ulp off the host libm the reference's CPU path uses); 3 ops per image
+  // inv_lam <= 0: fixed-ratio mode (balance_training_images), y holds r itself
+  const float r = inv_lam > 0.f ? __fmul_rn(inv_lam, (float)log((double)__fdiv_rn(1.0f, t))) : y;
+  // __fsqrt_rn: IEEE correctly rounded f32 square root
+  return BlendCoef{r, __fsqrt_rn(__fsub_rn(1.0f, r)), __fsqrt_rn(r)};
+}
+__device__ __forceinline__ float4 blend4(const BlendCoef k, const float4 a, const float4 n) {
+  float4 o;
+  o.x = __fadd_rn(__fmul_rn(k.sa, a.x), __fmul_rn(k.sb, n.x));
+  o.y = __fadd_rn(__fmul_rn(k.sa, a.y), __fmul_rn(k.sb, n.y));
+  o.z = __fadd_rn(__fmul_rn(k.sa, a.z), __fmul_rn(k.sb, n.z));
+  o.w = __fadd_rn(__fmul_rn(k.sa, a.w), __fmul_rn(k.sb, n.w));
+  return o;
+}
+
 __global__ __launch_bounds__(256) void noise_blend_kernel(const float* __restrict__ x,
                                                           const float* __restrict__ noise,
                                                           const float* __restrict__ y_uniform,
@@ -335,28 +360,13 @@ __global__ __launch_bounds__(256) void noise_blend_kernel(const float* __restric
                                                           float* __restrict__ out,
                                                           float* __restrict__ r_out, long per_image) {
   const int b = blockIdx.y;
-  // x = 1/lam * log(1 / (y*(1-c) + c))   -- every step rounded to f32 like the torch expression
-  const float t = __fadd_rn(__fmul_rn(y_uniform[b], one_minus_c), c);
-  // log / sqrt evaluated in double and rounded once: correctly rounded f32 results (the device's
-  // f32 logf / sqrtf are 1-2 ulp off the host libm the reference's CPU path uses); 3 ops per image
-  // inv_lam <= 0: fixed-ratio mode (balance_training_images), y_uniform holds r itself
-  const float r = inv_lam > 0.f ? __fmul_rn(inv_lam, (float)log((double)__fdiv_rn(1.0f, t))) : y_uniform[b];
-  // __fsqrt_rn: IEEE correctly rounded f32 square root
-  const float sa = __fsqrt_rn(__fsub_rn(1.0f, r)), sb = __fsqrt_rn(r);
-  if (r_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) r_out[b] = r;
+  const BlendCoef k = blend_coef(y_uniform[b], c, one_minus_c, inv_lam);
+  if (r_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) r_out[b] = k.r;
   const long nvec = per_image / 4;
   const float4* __restrict__ xv = reinterpret_cast<const float4*>(x + (long)b * per_image);
   const float4* __restrict__ nv = reinterpret_cast<const float4*>(noise + (long)b * per_image);
   float4* __restrict__ ov = reinterpret_cast<float4*>(out + (long)b * per_image);
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-    const float4 a = xv[i], n = nv[i];
-    float4 o;
-    o.x = __fadd_rn(__fmul_rn(sa, a.x), __fmul_rn(sb, n.x));
-    o.y = __fadd_rn(__fmul_rn(sa, a.y), __fmul_rn(sb, n.y));
-    o.z = __fadd_rn(__fmul_rn(sa, a.z), __fmul_rn(sb, n.z));
-    o.w = __fadd_rn(__fmul_rn(sa, a.w), __fmul_rn(sb, n.w));
-    ov[i] = o;
-  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) ov[i] = blend4(k, xv[i], nv[i]);
 }
 
 int noise_blend_launch(const float* x, const float* noise, const float* y_uniform, float lam,
@@ -383,6 +393,84 @@ int noise_blend_fixed_launch(const float* x, const float* noise, const float* r,
   if (bx > 256) bx = 256;
   hipLaunchKernelGGL(noise_blend_kernel, dim3((unsigned)bx, (unsigned)B), dim3(256), 0, stream, x, noise, r, 0.f, 0.f,
                      -1.f, out, (float*)nullptr, per_image);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- K12 with its draws made inside (philox.h: the draw layout) ------------------------------------------------------
+// d3f/train_denoiser/lit_module.py:128-153 == d3f/train_deep_fake/lit_module.py:208-233 (randn_like + rand + blend) and
+// d3f/balance_training_images/lit_module.py:109-121 (randn_like + fixed-ratio blend) as ONE kernel: block g of image b
+// gives the four normals of float4 g, the image's y comes from block 0xFFFFFFFF; no noise tensor goes through HBM.
+// y_or_r == nullptr: y is drawn (exponential sampler); otherwise y_or_r[b] is the fixed ratio r (inv_lam <= 0).
+__global__ __launch_bounds__(256) void noise_blend_rng_kernel(const float* __restrict__ x, uint64_t seed, uint64_t offset,
+                                                              const float* __restrict__ y_or_r, float c,
+                                                              float one_minus_c, float inv_lam, float* __restrict__ out,
+                                                              float* __restrict__ r_out, long per_image) {
+  chain_priority();
+  const int b = blockIdx.y;
+  const BlendCoef k = blend_coef(y_or_r != nullptr ? y_or_r[b] : rng_y(seed, offset, b), c, one_minus_c, inv_lam);
+  if (r_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) r_out[b] = k.r;
+  const long nvec = per_image / 4;
+  const float4* __restrict__ xv = reinterpret_cast<const float4*>(x + (long)b * per_image);
+  float4* __restrict__ ov = reinterpret_cast<float4*>(out + (long)b * per_image);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256)
+    ov[i] = blend4(k, xv[i], rng_normal4(seed, offset, b, (uint32_t)i));
+}
+
+// the draws of noise_blend_rng_kernel written out (either pointer may be null): the same device functions
+__global__ __launch_bounds__(256) void noise_draw_kernel(uint64_t seed, uint64_t offset, float* __restrict__ noise,
+                                                         float* __restrict__ y, long per_image) {
+  const int b = blockIdx.y;
+  if (y != nullptr && blockIdx.x == 0 && threadIdx.x == 0) y[b] = rng_y(seed, offset, b);
+  if (noise == nullptr) return;
+  const long nvec = per_image / 4;
+  float4* __restrict__ nv = reinterpret_cast<float4*>(noise + (long)b * per_image);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256)
+    nv[i] = rng_normal4(seed, offset, b, (uint32_t)i);
+}
+
+static int rng_shape_check(const char* what, long per_image) {
+  D3F_CHECK(per_image % 4 == 0, "%s: per-image element count %ld not a multiple of 4", what, per_image);
+  // groups 0xFFFFFFFD .. 0xFFFFFFFF of every image hold the augmentation draws and y
+  D3F_CHECK(per_image / 4 < (long)RNG_G_APPLY, "%s: per-image element count %ld leaves no room for the reserved groups",
+            what, per_image);
+  return 0;
+}
+static unsigned rng_blocks(long per_image) {
+  const long bx = (per_image / 4 + 255) / 256;
+  return (unsigned)(bx > 256 ? 256 : (bx < 1 ? 1 : bx));
+}
+
+int noise_blend_rng_launch(const float* x, uint64_t seed, uint64_t offset, float lam, float* out, float* r_out, int B,
+                           long per_image, hipStream_t stream) {
+  if (int rc = rng_shape_check("noise_blend_rng", per_image)) return rc;
+  D3F_CHECK(lam > 0.f, "noise_blend_rng: lambda must be positive");
+  if (B == 0 || per_image == 0) return 0;
+  const double c = 1.0 / exp((double)lam);
+  hipLaunchKernelGGL(noise_blend_rng_kernel, dim3(rng_blocks(per_image), (unsigned)B), dim3(256), 0, stream, x, seed,
+                     offset, (const float*)nullptr, (float)c, (float)(1.0 - c), (float)(1.0 / (double)lam), out, r_out,
+                     per_image);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+int noise_blend_fixed_rng_launch(const float* x, uint64_t seed, uint64_t offset, const float* r, float* out, int B,
+                                 long per_image, hipStream_t stream) {
+  if (int rc = rng_shape_check("noise_blend_fixed_rng", per_image)) return rc;
+  if (B == 0 || per_image == 0) return 0;
+  hipLaunchKernelGGL(noise_blend_rng_kernel, dim3(rng_blocks(per_image), (unsigned)B), dim3(256), 0, stream, x, seed,
+                     offset, r, 0.f, 0.f, -1.f, out, (float*)nullptr, per_image);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+int noise_draw_launch(uint64_t seed, uint64_t offset, float* noise, float* y, int B, long per_image,
+                      hipStream_t stream) {
+  if (int rc = rng_shape_check("noise_draw", per_image)) return rc;
+  if (B == 0 || (noise == nullptr && y == nullptr)) return 0;
+  const unsigned bx = (noise != nullptr && per_image > 0) ? rng_blocks(per_image) : 1u;
+  hipLaunchKernelGGL(noise_draw_kernel, dim3(bx, (unsigned)B), dim3(256), 0, stream, seed, offset,
+                     per_image > 0 ? noise : (float*)nullptr, y, per_image);
   D3F_HIP(hipGetLastError());
   return 0;
 }

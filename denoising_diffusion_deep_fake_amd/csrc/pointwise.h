@@ -119,6 +119,22 @@ int u8rgb_to_nchw_launch(const uint8_t* in, float* out, int B, long HW, const fl
 // K17: affine_grid + grid_sample(bilinear, zeros, align_corners=False) on NCHW fp32, theta [B][2][3]
 int affine_warp_launch(const float* in, const float* theta, float* out, int B, int C, int H, int W,
                        hipStream_t stream);
+// K17 with theta drawn inside (philox.h): the ranges of RandomAffine (kind 0) / ShiftScaleRotate (kind 1) as the kernels
+// take them -- python-side double constants rounded to fp32 once, like a python scalar meeting a float tensor
+struct AffineRngParams {
+  int kind;
+  float angle_unit;          // kind 0: radians(degrees); kind 1: rotate_limit (degrees)
+  float deg2rad;             // pi / 180
+  float scale_lo, scale_span;  // kind 0: scale_lo, scale_hi - scale_lo; kind 1: -, scale_limit
+  float shift_x, shift_y;    // kind 0: translate_x, translate_y; kind 1: shift_limit twice
+  float p;                   // probability that an image is warped at all
+  float h_over_w, w_over_h;
+};
+int affine_rng_params(int kind, const float params[5], int H, int W, AffineRngParams& q);
+int affine_warp_rng_launch(const float* in, float* out, uint64_t seed, uint64_t offset, const AffineRngParams& q, int B,
+                           int C, int H, int W, hipStream_t stream);
+int affine_theta_draw_launch(uint64_t seed, uint64_t offset, const AffineRngParams& q, float* theta, uint8_t* apply, int B,
+                             hipStream_t stream);
 
 // ---- weights -------------------------------------------------------------------------------
 // conv(cat(upsample2x(x), skip)) with the up-sampling folded into pre-summed weights (pointwise.hip): per-class
@@ -155,6 +171,13 @@ int noise_blend_launch(const float* x, const float* noise, const float* y_unifor
                        float* out, float* r_out, int B, long per_image, hipStream_t stream);
 int noise_blend_fixed_launch(const float* x, const float* noise, const float* r, float* out, int B, long per_image,
                              hipStream_t stream);
+// the same with the draws made inside the kernel, and the draws alone (philox.h: the layout)
+int noise_blend_rng_launch(const float* x, uint64_t seed, uint64_t offset, float lam, float* out, float* r_out, int B,
+                           long per_image, hipStream_t stream);
+int noise_blend_fixed_rng_launch(const float* x, uint64_t seed, uint64_t offset, const float* r, float* out, int B,
+                                 long per_image, hipStream_t stream);
+int noise_draw_launch(uint64_t seed, uint64_t offset, float* noise, float* y, int B, long per_image,
+                      hipStream_t stream);
 size_t l1_per_image_workspace_bytes(int B);
 int l1_per_image_launch(const float* pred, const float* target, float* out, void* workspace, int B, long per_image,
                         hipStream_t stream);

@@ -218,6 +218,43 @@ def affine_warp(x, theta):
     return out
 
 
+def _affine_rng_params(kind, params):
+    kinds = {"random_affine": 0, "shift_scale_rotate": 1}
+    kind = kinds.get(kind, kind)
+    if kind not in (0, 1):
+        raise ValueError(f"kind must be one of {sorted(kinds)} (or 0 / 1), got {kind!r}")
+    params = [float(v) for v in params]
+    if len(params) != (5 if kind == 0 else 4):
+        raise ValueError("params: (degrees, translate_x, translate_y, scale_lo, scale_hi) for random_affine, "
+                         "(shift_limit, scale_limit, rotate_limit, p) for shift_scale_rotate")
+    return kind, (C.c_float * 5)(*(params + [0.0] * (5 - len(params))))
+
+
+def affine_warp_rng(x, seed, offset, kind, params):
+    """affine_warp with its per-image parameters drawn inside the kernel (d3f_affine_warp_rng; csrc/philox.h has the draw
+    layout).  kind "random_affine": params (degrees, translate_x, translate_y, scale_lo, scale_hi), every image warped;
+    kind "shift_scale_rotate": params (shift_limit, scale_limit, rotate_limit, p), an image is warped with probability p
+    and copied otherwise."""
+    x = x.contiguous().float()
+    B, Cc, H, W = x.shape
+    kind, cparams = _affine_rng_params(kind, params)
+    out = torch.empty_like(x)
+    check(_lib.lib().d3f_affine_warp_rng(ptr(x), ptr(out), int(seed), int(offset), kind, cparams, B, Cc, H, W,
+                                         stream_ptr()))
+    return out
+
+
+def affine_theta_draw(seed, offset, kind, params, B, H, W, device="cuda"):
+    """the (theta [B, 2, 3] f32, apply [B] bool) affine_warp_rng uses for the same arguments"""
+    kind, cparams = _affine_rng_params(kind, params)
+    theta = torch.empty((B, 2, 3), dtype=torch.float32, device=device)
+    apply = torch.empty(B, dtype=torch.uint8, device=device)
+    _dev(theta)
+    check(_lib.lib().d3f_affine_theta_draw(int(seed), int(offset), kind, cparams, ptr(theta), ptr(apply), B, H, W,
+                                           stream_ptr()))
+    return theta, apply.bool()
+
+
 def u8rgb_normalise(frames, mean, std):
     """uint8 RGB [B, H, W, 3] on the HIP device -> normalised NCHW float32 ((u8 / 255 - mean) / std per channel): the
     host transform NormalizeToTensor bit for bit (d3f_u8rgb_normalise)"""
@@ -252,6 +289,53 @@ def noise_blend_fixed(x, noise, ratio):
     check(_lib.lib().d3f_noise_blend_fixed(ptr(x), ptr(noise.contiguous().float()), ptr(r), ptr(out), B,
                                            x.numel() // max(B, 1), stream_ptr()))
     return out
+
+
+def noise_blend_rng(x, seed, offset, lam, return_r=False):
+    """noise_blend with its normals and its per-image uniform drawn inside the kernel: no noise tensor exists"""
+    x = x.contiguous().float()
+    out = torch.empty_like(x)
+    B = x.shape[0]
+    r = torch.empty(B, dtype=torch.float32, device=_dev(x)) if return_r else None
+    check(_lib.lib().d3f_noise_blend_rng(ptr(x), int(seed), int(offset), float(lam), ptr(out), ptr(r), B,
+                                         x.numel() // max(B, 1), stream_ptr()))
+    return (out, r) if return_r else out
+
+
+def noise_blend_fixed_rng(x, seed, offset, ratio):
+    """noise_blend_fixed with its normals drawn inside the kernel"""
+    x = x.contiguous().float()
+    B = x.shape[0]
+    r = ratio if torch.is_tensor(ratio) else torch.ones(B, device=_dev(x)) * float(ratio)
+    r = r.to(device=_dev(x), dtype=torch.float32).reshape(-1).contiguous()
+    out = torch.empty_like(x)
+    check(_lib.lib().d3f_noise_blend_fixed_rng(ptr(x), int(seed), int(offset), ptr(r), ptr(out), B,
+                                               x.numel() // max(B, 1), stream_ptr()))
+    return out
+
+
+def noise_draw(seed, offset, shape, device="cuda", noise=True, y=True):
+    """the draws noise_blend_rng / noise_blend_fixed_rng make for a batch of this shape: (noise [shape] or None, y [B] or
+    None)"""
+    shape = tuple(int(v) for v in shape)
+    B = shape[0]
+    per_image = 1
+    for v in shape[1:]:
+        per_image *= v
+    n = torch.empty(shape, dtype=torch.float32, device=device) if noise else None
+    yy = torch.empty(B, dtype=torch.float32, device=device) if y else None
+    _dev(n if n is not None else yy)
+    check(_lib.lib().d3f_noise_draw(int(seed), int(offset), ptr(n), ptr(yy), B, per_image, stream_ptr()))
+    return n, yy
+
+
+def philox4x32_10(counter, key):
+    """one Philox4x32-10 block on the host: counter 4 and key 2 uint32 words -> 4 uint32 words"""
+    c = (C.c_uint32 * 4)(*[int(v) & 0xFFFFFFFF for v in counter])
+    k = (C.c_uint32 * 2)(*[int(v) & 0xFFFFFFFF for v in key])
+    out = (C.c_uint32 * 4)()
+    check(_lib.lib().d3f_philox4x32_10(c, k, out))
+    return tuple(int(v) for v in out)
 
 
 def l1_per_image(pred, target):

@@ -15,6 +15,11 @@ parameter ranges drawn with torch RNG, one HIP warp kernel (ops.affine_warp, K17
 units -- inside `training_step`, before the noise blend, so that 8 GPUs are not fed by 8 CPU warps.
 `augment: false` switches it off (benchmarks, parity tests).
 
+`device_rng: true` (off by default; optional `rng_seed`): the noise, y and augmentation draws come from the counter-based
+generator inside the kernels that consume them (rng.py, csrc/philox.h) -- a function of (seed, global_step, rank, domain:
+stream 0 for a, 1 for b), so the fused two-network step equals the sequential loop whatever the order of the draws and a
+resumed run continues the interrupted one.
+
 Reference quirks kept on purpose: the dataloaders receive `mean_x` as BOTH
 mean and std (lit_module.py:75-76); `predict_fake("a")` uses model_a with B's mean/std (:253-257);
 de-normalisation truncates with `.int()` BEFORE clamping (:293-294).
@@ -29,7 +34,7 @@ import torch.nn as nn
 import torch.optim.lr_scheduler as schedulers
 from torch.utils.data import DataLoader
 
-from .. import ops
+from .. import ops, rng
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset, ToUint8Tensor
 from ..lightning import LightningModule
 from ..loss_functions import MseStructuralSimilarityLoss
@@ -66,7 +71,10 @@ class ShiftScaleRotate(nn.Module):
                 "scale": 1.0 + u(self.scale_limit), "dx": u(self.shift_limit), "dy": u(self.shift_limit)}
 
     @torch.no_grad()
-    def forward(self, x, draws=None):
+    def forward(self, x, draws=None, seed_offset=None):
+        if seed_offset is not None:  # device_rng: (seed, offset) -- draws, theta, warp and pass-through in one kernel
+            return ops.affine_warp_rng(x, seed_offset[0], seed_offset[1], "shift_scale_rotate",
+                                       (self.shift_limit, self.scale_limit, self.rotate_limit, self.p))
         d = self.draw(x.shape[0], x.device) if draws is None else draws
         th = self.theta(d["angle"], d["scale"], d["dx"], d["dy"], x.shape[2], x.shape[3])
         warped = ops.affine_warp(x, th)
@@ -191,15 +199,20 @@ class LitModule(LightningModule):
             # the reference augments in the dataset; each image of a combined batch is consumed by exactly one of the
             # two optimiser steps (a by 0, b by 1), so warping the half a step uses is the same thing
             if optimizer_idx == 0:
-                batch_a = self.augmentation(batch_a)
+                batch_a = self.augment(batch_a, 0)
             else:
-                batch_b = self.augmentation(batch_b)
+                batch_b = self.augment(batch_b, 1)
         if optimizer_idx == 0:
             loss = self.training_step_for_one_model("a", batch_a, self.model_a, self.ema_model_b)
         if optimizer_idx == 1:
             loss = self.training_step_for_one_model("b", batch_b, self.model_b, self.ema_model_a)
         self.log("epoch", float(self.current_epoch))
         return loss
+
+    def augment(self, x, stream):
+        if self.hparams.get("device_rng", False):
+            return self.augmentation(x, seed_offset=rng.module_stream(self, stream))
+        return self.augmentation(x)
 
     # ---- the two optimizer steps of a denoise-mode batch as one set of launches ------------------------------------
     def pair_fused_active(self, batch=None, optimizers=None):
@@ -225,19 +238,20 @@ class LitModule(LightningModule):
 
     def training_step_pair(self, batch, batch_idx):
         """training_step(batch, batch_idx, 0) and training_step(batch, batch_idx, 1) of a denoise-mode batch as one pass:
-        the same preparation and the same random draws in the same order (a's augmentation and noise, then b's), ONE
+        the same preparation and the same random draws in the same order (a's augmentation and noise, then b's; with
+        `device_rng` the same streams 0 / 1, whatever the order), ONE
         forward of UnetPair(model_a, model_b), the two losses.  Returns (loss_a, loss_b); the caller runs ONE backward,
         torch.autograd.backward([loss_a, loss_b]), then both optimizer steps."""
         p = self.hparams
         reals, noisy = [], []
-        for key, mean in (("a", p.mean_a), ("b", p.mean_b)):
+        for stream, (key, mean) in enumerate((("a", p.mean_a), ("b", p.mean_b))):
             x = batch[key]["image"]
             if x.dtype == torch.uint8:
                 x = ops.u8rgb_normalise(x, mean, mean)
             if self.augmentation is not None:
-                x = self.augmentation(x)
+                x = self.augment(x, stream)
             with torch.no_grad():
-                noisy.append(self.blend_random_amount_of_noise_with_each_sample(x))
+                noisy.append(self.blend_random_amount_of_noise_with_each_sample(x, stream))
             reals.append(x)
         predictions = self._unet_pair()(noisy[0], noisy[1])
         losses = []
@@ -266,7 +280,7 @@ class LitModule(LightningModule):
 
     def training_denoise_step_for_one_model(self, name, real, real_model):
         with torch.no_grad():
-            noisy_real = self.blend_random_amount_of_noise_with_each_sample(real)
+            noisy_real = self.blend_random_amount_of_noise_with_each_sample(real, "ab".index(name))
         real_prediction = real_model(noisy_real)
         loss = self.criterion(real_prediction, real)
         self.log(f"loss_denoise/train_{name}", loss)
@@ -277,7 +291,7 @@ class LitModule(LightningModule):
         with torch.no_grad():
             fake = fake_model(real)  # train-mode BatchNorm: the EMA wrapper is a registered sub-module
             swap_diff = nn.functional.mse_loss(real, fake)
-            noisy_fake = self.blend_random_amount_of_noise_with_each_sample(fake)
+            noisy_fake = self.blend_random_amount_of_noise_with_each_sample(fake, "ab".index(name))
         real_prediction = real_model(noisy_fake)
         loss = self.criterion(real_prediction, real)
         self.log(f"swap_difference/{name}", swap_diff)
@@ -285,8 +299,12 @@ class LitModule(LightningModule):
         return loss
 
     @torch.no_grad()
-    def blend_random_amount_of_noise_with_each_sample(self, batch):
+    def blend_random_amount_of_noise_with_each_sample(self, batch, stream=0):
+        """stream: the domain whose step this is (0: a, 1: b) -- names the draws of `device_rng`, otherwise unused"""
         p = self.hparams
+        if p.get("device_rng", False):  # K12 as one kernel: the draws are a function of (seed, step, rank, domain)
+            seed, offset = rng.module_stream(self, stream)
+            return ops.noise_blend_rng(batch, seed, offset, p.noise_exponential_sampling_lambda)
         noise = torch.randn_like(batch)  # reference RNG order: randn_like first, then rand
         y = torch.rand(size=(batch.shape[0], 1, 1, 1), device=batch.device)
         return ops.noise_blend(batch, noise, y.reshape(-1), p.noise_exponential_sampling_lambda)

@@ -10,7 +10,10 @@ Differences, all outside the parity-checked arithmetic
     command actually runs; `synthetic: true` swaps in the synthetic face-crop dataset;
   * kornia's RandomAffine is replaced by the same parameter ranges drawn with torch RNG and one HIP warp
     kernel (ops.affine_warp = affine_grid + grid_sample(bilinear, zeros), parity-tested against torch on CPU);
-    the random draws themselves are not part of the numerics contract; off in benchmarks (`augment: false`).
+    the random draws themselves are not part of the numerics contract; off in benchmarks (`augment: false`);
+  * `device_rng: true` (off by default; optional `rng_seed`): the noise, y and augmentation draws come from the
+    counter-based generator inside the kernels that consume them (rng.py, csrc/philox.h) -- a function of (seed,
+    global_step, rank), so a resumed run continues the interrupted one.  Not together with `graph_step`.
 """
 import math
 
@@ -18,7 +21,7 @@ import torch
 import torch.optim.lr_scheduler as schedulers
 from torch.utils.data import DataLoader
 
-from .. import ops
+from .. import ops, rng
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset, ToUint8Tensor
 from ..lightning import LightningModule
 from ..loss_functions import MseStructuralSimilarityLoss
@@ -34,7 +37,10 @@ class RandomAffine(torch.nn.Module):
         super().__init__()
         self.degrees, self.translate, self.scale = degrees, translate, scale
 
-    def forward(self, x):
+    def forward(self, x, seed_offset=None):
+        if seed_offset is not None:  # device_rng: (seed, offset) -- the draws and theta happen inside the warp kernel
+            return ops.affine_warp_rng(x, seed_offset[0], seed_offset[1], "random_affine",
+                                       (self.degrees, self.translate[0], self.translate[1], self.scale[0], self.scale[1]))
         B = x.shape[0]
         dev = x.device
         ang = (torch.rand(B, device=dev) * 2 - 1) * math.radians(self.degrees)
@@ -58,6 +64,7 @@ class LitModule(LightningModule):
         # Single GPU only.  Measured on ROCm 7.0 / MI355X (profiles/README.md, round 3): bit-identical and SLOWER than the
         # eager step (the replay of a graph spanning the engine's three streams costs ~30 us per node), so it is off
         # unless asked for.
+        rng.refuse_graph_step(self.hparams)
         self.automatic_optimization = not self.hparams.get("graph_step", False)
         self.__dict__["_graph_step"] = None
 
@@ -129,7 +136,10 @@ class LitModule(LightningModule):
             image = self.normalise_on_device(image)
         if self.hparams.get("augment", True):
             with torch.no_grad():
-                image = self.shared_augmentation_sequence(image)
+                if self.hparams.get("device_rng", False):
+                    image = self.shared_augmentation_sequence(image, rng.module_stream(self))
+                else:
+                    image = self.shared_augmentation_sequence(image)
         if not self.automatic_optimization:
             if self._graph_step is None:
                 from ..graph_step import GraphTrainStep
@@ -149,6 +159,9 @@ class LitModule(LightningModule):
     @torch.no_grad()
     def blend_random_amount_of_noise_with_each_sample(self, batch):
         p = self.hparams
+        if p.get("device_rng", False):  # K12 as one kernel: the step's draws are a function of (seed, step, rank)
+            seed, offset = rng.module_stream(self)
+            return ops.noise_blend_rng(batch, seed, offset, p.noise_exponential_sampling_lambda)
         # RNG call order of the reference: randn_like(batch) first, then rand(B,1,1,1)
         noise = torch.randn_like(batch)
         y = torch.rand(size=(batch.shape[0], 1, 1, 1), device=batch.device)

@@ -302,6 +302,40 @@ int d3f_u8rgb_normalise(const uint8_t* in_hwc, float* out_nchw, int B, int H, in
 int d3f_affine_warp(const float* in, const float* theta, float* out, int B, int C, int H, int W, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Counter-based random numbers (Philox4x32-10, Random123 / cuRAND definition) made inside the kernels that consume
+ * them.  The draw layout every entry below shares:
+ *   key     = (seed & 0xffffffff, seed >> 32)                    seed, offset: caller-given uint64
+ *   counter = (g, b, offset & 0xffffffff, offset >> 32)          b: image index inside the call
+ *   normals  g = index of a group of four consecutive elements of image b (per_image % 4 == 0, per_image / 4 < 0xFFFFFFFD);
+ *            words x0..x3: ua = ((x0 >> 9) + 0.5) * 2^-23, ub = (x1 >> 8) * 2^-24, R = sqrt(-2 ln ua),
+ *            z0 = R cos(2 pi ub), z1 = R sin(2 pi ub); x2, x3 give z2, z3 the same way (fp32, accurate ln / sqrt / sincospi)
+ *   y        word 0 of g = 0xFFFFFFFF: y = (x0 >> 8) * 2^-24 in [0,1)
+ *   u0..u3   the four words of g = 0xFFFFFFFE, u4 = word 0 of g = 0xFFFFFFFD (augmentation; same conversion as y)
+ * A value depends on (seed, offset, b, element) only: not on B, the grid, or per_image beyond the element's own index.
+ * Every consumer has a twin that writes out exactly the draws it uses, from the same device functions.
+ * ------------------------------------------------------------------------------------- */
+/* host: one Philox4x32-10 block (tests, tools; no device needed) */
+int d3f_philox4x32_10(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
+
+/* GPU-side augmentation with its parameters drawn inside: replaces the draws + theta + warp (+ where) of RandomAffine
+ * (d3f/train_denoiser/lit_module.py:55-65, applied at :113; kind 0, params = degrees, translate_x, translate_y, scale_lo,
+ * scale_hi; always applied) and of A.ShiftScaleRotate (d3f/train_deep_fake/lit_module.py:99-111; kind 1, params =
+ * shift_limit, scale_limit, rotate_limit, p, unused).  Draw layout above: u0..u3 of image b from g = 0xFFFFFFFE, u4 from
+ * g = 0xFFFFFFFD.
+ *   kind 0: ang = (2 u0 - 1) radians(degrees), sc = u1 (scale_hi - scale_lo) + scale_lo, tx = (2 u2 - 1) translate_x 2,
+ *           ty = (2 u3 - 1) translate_y 2;  theta = [[cos/sc, -sin/sc, tx], [sin/sc, cos/sc, ty]]
+ *   kind 1: angle = (2 u0 - 1) rotate_limit (degrees), scale = 1 + (2 u1 - 1) scale_limit, dx = (2 u2 - 1) shift_limit,
+ *           dy = (2 u3 - 1) shift_limit, apply = u4 < p;  theta of cv2.warpAffine(getRotationMatrix2D(centre, angle, scale)
+ *           + (dx W, dy H)) in affine_grid form
+ * then the sampling of d3f_affine_warp.  An image whose `apply` draw fails passes through as a copy.  in and out must
+ * not alias. */
+int d3f_affine_warp_rng(const float* in, float* out, uint64_t seed, uint64_t offset, int kind,
+                        const float params[5], int B, int C, int H, int W, void* stream);
+/* the theta [B][2][3] and apply [B] (uint8) that call uses (same layout, same device functions) */
+int d3f_affine_theta_draw(uint64_t seed, uint64_t offset, int kind, const float params[5],
+                          float* theta, uint8_t* apply, int B, int H, int W, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training-step arithmetic around the network
  * ------------------------------------------------------------------------------------- */
 /* blend_random_amount_of_noise_with_each_sample + sample_random_number_from_exponential_distribution
@@ -314,6 +348,20 @@ int d3f_noise_blend(const float* x, const float* noise, const float* y_uniform, 
  * caller's noise and the per-image ratios r [B] (device): out = sqrt(1-r)*x + sqrt(r)*noise */
 int d3f_noise_blend_fixed(const float* x, const float* noise, const float* r, float* out, int B, int64_t per_image,
                           void* stream);
+/* d3f_noise_blend with z and y drawn inside, K12 as one kernel (d3f/train_denoiser/lit_module.py:128-153 ==
+ * d3f/train_deep_fake/lit_module.py:208-233: randn_like + rand + blend): out = sqrt(1-r) x + sqrt(r) z.  Draw layout above:
+ * the four normals of elements 4g .. 4g+3 of image b from counter g, y from g = 0xFFFFFFFF.  Given the same z and y the
+ * result is d3f_noise_blend's bit for bit.  out must not alias x (the callers never do). */
+int d3f_noise_blend_rng(const float* x, uint64_t seed, uint64_t offset, float lam, float* out,
+                        float* r_out_or_null, int B, int64_t per_image, void* stream);
+/* d3f_noise_blend_fixed with z drawn inside (d3f/balance_training_images/lit_module.py:109-121): fixed ratios r [B] on
+ * the device; normals as above, no y.  out must not alias x. */
+int d3f_noise_blend_fixed_rng(const float* x, uint64_t seed, uint64_t offset, const float* r, float* out, int B,
+                              int64_t per_image, void* stream);
+/* the draws of the two calls above, written out: noise [B][per_image] (normals of counter g = element / 4), y [B]
+ * (g = 0xFFFFFFFF); either may be NULL */
+int d3f_noise_draw(uint64_t seed, uint64_t offset, float* noise_or_null, float* y_or_null, int B, int64_t per_image,
+                   void* stream);
 /* compute_difficulty_loss (d3f/balance_training_images/lit_module.py:139-142): out[b] = mean |prediction - target|
  * over image b; deterministic two-pass sum (f64 partials in the workspace) */
 size_t d3f_l1_per_image_workspace_bytes(int B);
