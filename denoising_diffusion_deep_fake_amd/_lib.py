@@ -24,9 +24,25 @@ class ConvDesc(C.Structure):
                 ("B", "H", "W", "C0", "C1", "upsample0", "Cout", "KH", "KW", "stride", "pad", "CinReal")]
 
 
+class BnDesc(C.Structure):
+    """d3f_bn_desc: one BatchNorm layer as the engine describes it"""
+    _fields_ = [("dtype", C.c_int32), ("C", C.c_int32), ("Cpad", C.c_int32), ("rows", C.c_int64),
+                ("apply", C.c_int32), ("relu", C.c_int32), ("res", C.c_int32), ("mask", C.c_int32),
+                ("fwd_rows", C.c_int32), ("fused_rows", C.c_int32), ("allow_fused", C.c_int32), ("plan_nets", C.c_int32)]
+
+
+class BnPlan(C.Structure):
+    """d3f_bn_plan: what bn_layer_plan made of a BnDesc"""
+    _fields_ = [("fwd_fused", C.c_int32), ("bwd_fused", C.c_int32), ("reduce_blocks", C.c_int32), ("bwd_rows", C.c_int32),
+                ("rows_per_block", C.c_int64), ("stat_floats", C.c_uint64), ("part_floats", C.c_uint64)]
+
+
+BN_COEF_ROWS = 7  # D3F_BN_COEF_ROWS: mean invstd scale shift k0 k1 k2
+
 _p, _i, _i64, _f, _sz, _dbl = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_double
 _u64, _u32p = C.c_uint64, C.POINTER(C.c_uint32)
 _desc = C.POINTER(ConvDesc)
+_bnd, _bnp = C.POINTER(BnDesc), C.POINTER(BnPlan)
 
 # name -> (restype, argtypes); must list every symbol include/d3f_hip.h declares
 PROTOTYPES = {
@@ -93,6 +109,10 @@ PROTOTYPES = {
     "d3f_bn_apply": (_i, [_i, _p, _p, _i, _i64, _p, _i, _p, _p]),
     "d3f_bn_backward_workspace_bytes": (_sz, [_i, _i, _i64]),
     "d3f_bn_backward": (_i, [_i, _p, _p, _p, _p, _p, _i, _i64, _p, _p, _p, _p, _p, _p]),
+    "d3f_bn_layer_plan": (_i, [_bnd, _bnp]),
+    "d3f_bn_layer_forward": (_i, [_bnd, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "d3f_bn_layer_backward": (_i, [_bnd, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "d3f_unet_bn_layer": (_i, [_p, _i, _bnd, _bnp]),
     "d3f_maxpool3x3s2_forward": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _p]),
     "d3f_maxpool3x3s2_backward": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "d3f_upsample2x_backward": (_i, [_i, _p, _p, _i, _i, _i, _i, _p]),

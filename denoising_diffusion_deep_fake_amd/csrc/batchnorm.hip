@@ -711,7 +711,8 @@ static int bn_bwd_finalize_apply_launch(const BnLayer& L, const BnBufs& b, const
 // the layer: planned once, one call per pass
 // ------------------------------------------------------------------------------------------
 void bn_layer_plan(BnLayer& L) {
-  static const bool no_fused = prof_knob("D3F_NO_BN_FUSED_FINALIZE") != nullptr;  // debugging knob: separate launches
+  // fallback knob, read by the shipped library too (the suite runs the network with it): separate launches everywhere
+  static const bool no_fused = getenv("D3F_NO_BN_FUSED_FINALIZE") != nullptr;
   auto fused_ok = [&](int rows) {  // fp32 / bf16 tensors, whole slabs, at most BNF_MAX_ROWS partial rows
     return L.allow_fused && !no_fused && (L.dtype == D3F_F32 || L.dtype == D3F_BF16) && L.C % BNF_SC == 0 && rows >= 1 &&
            rows <= BNF_MAX_ROWS;

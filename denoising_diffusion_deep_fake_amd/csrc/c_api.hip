@@ -520,6 +520,102 @@ int d3f_bn_backward(int dtype, const void* dA, const void* a_or_null, const void
   return bn_layer_backward(L, b, nullptr, (hipStream_t)stream);
 }
 
+// describe -> plan: the layer a d3f_bn_desc describes, as the engine would hold it
+static_assert(D3F_BN_COEF_ROWS == BN_COEF_ROWS, "d3f_hip.h states the coefficient block's rows");
+static int bn_plan(BnLayer& L, const d3f_bn_desc* d) {
+  D3F_CHECK(d != nullptr, "bn_layer: null descriptor");
+  D3F_CHECK(d->dtype == D3F_F32 || d->dtype == D3F_BF16 || d->dtype == D3F_F32X3, "bn_layer: dtype %d", d->dtype);
+  D3F_CHECK(d->C > 0 && d->Cpad >= d->C && d->rows >= 0, "bn_layer: C=%d Cpad=%d rows=%lld", d->C, d->Cpad,
+            (long long)d->rows);
+  D3F_CHECK(d->res >= BN_RES_NONE && d->res <= BN_RES_LAYER && d->mask >= BN_MASK_NONE && d->mask <= BN_MASK_FROM_A,
+            "bn_layer: res=%d mask=%d", d->res, d->mask);
+  D3F_CHECK(d->fwd_rows >= 0 && d->fused_rows >= 0, "bn_layer: fwd_rows=%d fused_rows=%d", d->fwd_rows, d->fused_rows);
+  D3F_CHECK(d->plan_nets == 1 || d->plan_nets == 2, "bn_layer: plan_nets=%d", d->plan_nets);
+  L.name = "bn_layer";
+  L.C = d->C; L.Cpad = d->Cpad; L.rows = (long)d->rows; L.dtype = sdt(d->dtype); L.plan_nets = d->plan_nets;
+  L.apply = d->apply != 0; L.relu = d->relu != 0;
+  L.res = (BnResidual)d->res; L.mask = (BnMask)d->mask;
+  L.fwd_rows = d->fwd_rows; L.fused_rows = d->fused_rows; L.allow_fused = d->allow_fused != 0;
+  bn_layer_plan(L);
+  return 0;
+}
+static void bn_plan_out(const BnLayer& L, d3f_bn_plan* p) {
+  p->fwd_fused = L.fwd_fused; p->bwd_fused = L.bwd_fused; p->reduce_blocks = L.reduce_blocks; p->bwd_rows = L.bwd_rows;
+  p->rows_per_block = L.rows_per_block; p->stat_floats = L.stat_floats; p->part_floats = L.part_floats;
+}
+// the streaming kernels of the split form take whole 16-byte vectors per thread and a row pattern that repeats within a
+// workgroup; bn_bwd_reduce one row per group of C / ve threads
+static bool bn_split_channels_ok(const BnLayer& L) {
+  const int ve = L.dtype == D3F_F32 ? 4 : 8;
+  return L.C % ve == 0 && (256 * ve) % L.C == 0;
+}
+int d3f_bn_layer_plan(const d3f_bn_desc* d, d3f_bn_plan* plan) {
+  D3F_CHECK(plan != nullptr, "bn_layer_plan: null argument");
+  BnLayer L;
+  if (int rc = bn_plan(L, d)) return rc;
+  bn_plan_out(L, plan);
+  return 0;
+}
+int d3f_bn_layer_forward(const d3f_bn_desc* d, float* stats, const float* gamma, const float* beta, float* running_mean,
+                         float* running_var, float* coef, const void* y, const void* res, const float* res_coef, void* a,
+                         void* stream) {
+  BnLayer L;
+  if (int rc = bn_plan(L, d)) return rc;
+  if (L.rows == 0) return 0;
+  D3F_CHECK(L.fwd_rows >= 1, "bn_layer_forward: the forward pass reads fwd_rows >= 1 partial rows (fwd_rows=%d)", L.fwd_rows);
+  D3F_CHECK(stats && gamma && beta && coef && y, "bn_layer_forward: null argument");
+  D3F_CHECK((running_mean == nullptr) == (running_var == nullptr), "bn_layer_forward: one running statistic without the other");
+  if (L.apply) {
+    D3F_CHECK(a != nullptr, "bn_layer_forward: apply needs the output tensor");
+    D3F_CHECK(L.res == BN_RES_NONE || res != nullptr, "bn_layer_forward: res=%d needs the residual tensor", (int)L.res);
+    D3F_CHECK(L.res != BN_RES_LAYER || res_coef != nullptr, "bn_layer_forward: res=2 needs res_coef, the other layer's coefficient block");
+  }
+  if (L.fwd_fused)  // (16-byte loads of the statistics rows)
+    D3F_CHECK(L.Cpad % 2 == 0, "bn_layer_forward: the fused form needs an even Cpad (Cpad=%d)", L.Cpad);
+  else if (L.apply)
+    D3F_CHECK(bn_split_channels_ok(L), "bn_layer_forward: the split form needs C to divide %d (C=%d)",
+              256 * (L.dtype == D3F_F32 ? 4 : 8), L.C);
+  BnBufs b;
+  b.stats = stats; b.gamma = gamma; b.beta = beta; b.running_mean = running_mean; b.running_var = running_var;
+  b.coef = coef; b.y = y; b.a = a; b.res = res; b.res_coef = res_coef;
+  return bn_layer_forward(L, b, nullptr, (hipStream_t)stream);
+}
+int d3f_bn_layer_backward(const d3f_bn_desc* d, float* partial, const float* gamma, float* coef, const void* y,
+                          const void* a, const void* dA, void* dy, void* dres, int dres_acc, float* dgamma, float* dbeta,
+                          void* stream) {
+  BnLayer L;
+  if (int rc = bn_plan(L, d)) return rc;
+  if (L.rows == 0) return 0;
+  D3F_CHECK(partial != nullptr, "bn_layer_backward: null partial rows (fused_rows=%d: %s)", L.fused_rows,
+            L.fused_rows > 0 ? "the caller's sums" : "scratch of part_floats floats");
+  D3F_CHECK(gamma && coef && y && dA && dy, "bn_layer_backward: null argument");
+  D3F_CHECK(L.mask != BN_MASK_FROM_A || a != nullptr, "bn_layer_backward: mask=2 needs the activation a");
+  D3F_CHECK((dgamma == nullptr) == (dbeta == nullptr), "bn_layer_backward: dgamma without dbeta or the reverse");
+  if (L.fused_rows == 0 || !L.bwd_fused)
+    D3F_CHECK(bn_split_channels_ok(L), "bn_layer_backward: the split kernels need C to divide %d (C=%d)",
+              256 * (L.dtype == D3F_F32 ? 4 : 8), L.C);
+  BnBufs b;
+  b.stats = partial; b.gamma = gamma; b.coef = coef; b.y = y;
+  b.a = const_cast<void*>(a);  // (the ReLU mask: read only)
+  b.dA = dA; b.dy = dy; b.dres = dres; b.dres_acc = dres != nullptr && dres_acc ? 1 : 0;
+  b.dgamma = dgamma; b.dbeta = dbeta;
+  return bn_layer_backward(L, b, nullptr, (hipStream_t)stream);
+}
+int d3f_unet_bn_layer(d3f_unet_t h, int i, d3f_bn_desc* d, d3f_bn_plan* plan) {
+  D3F_CHECK(h && d && plan && i >= 0 && i < (int)h->e.bns.size(), "bn_layer: index %d", i);
+  int k = -1;
+  for (const Unit& u : h->e.units) {  // (bns lists the units with a BatchNorm, in order)
+    if (!u.bn || ++k != i) continue;
+    const BnLayer& L = u.norm;
+    d->dtype = L.dtype; d->C = L.C; d->Cpad = L.Cpad; d->rows = L.rows; d->apply = L.apply; d->relu = L.relu;
+    d->res = L.res; d->mask = L.mask; d->fwd_rows = L.fwd_rows; d->fused_rows = L.fused_rows;
+    d->allow_fused = L.allow_fused; d->plan_nets = L.plan_nets;
+    bn_plan_out(L, plan);
+    return 0;
+  }
+  return set_error(-1, "bn_layer: index %d", i);
+}
+
 int d3f_maxpool3x3s2_forward(int dtype, const void* in, void* out, uint8_t* idx, int B, int H, int W,
                              int C, void* stream) {
   D3F_CHECK(in && out && idx, "maxpool: null argument");

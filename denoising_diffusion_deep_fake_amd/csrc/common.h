@@ -28,6 +28,8 @@ namespace d3f {
 
 // Debugging / sweep knobs whose verdict is recorded (profiles/README.md) exist only in profiling builds
 // (make EXTRA=-DD3F_PROFILING, loaded through D3F_LIB): the shipped library does not read them.
+// (The fallback knobs that tests/ runs the network with -- D3F_SERIAL_BACKWARD, D3F_NO_ASYNC_PACK, D3F_NO_BN_FUSED_FINALIZE,
+// D3F_NO_FUSED_BN_REDUCE -- are read with getenv by every build.)
 static inline const char* prof_knob(const char* name) {
 #ifdef D3F_PROFILING
   return getenv(name);

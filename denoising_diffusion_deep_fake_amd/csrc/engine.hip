@@ -350,7 +350,8 @@ int UnetEngine::build(const char* encoder, int in_channels_, int classes_, int B
   // gradient also emits the (dbeta, dgamma) partial sums of the unit that consumes it -- when that unit is the very
   // next op (bnpart is one stream-ordered scratch).  The producer may accumulate (it sums first, then reduces the
   // final values); a consumer with a residual add takes its ReLU mask from its activation instead of from y.
-  static const bool no_fused_reduce = prof_knob("D3F_NO_FUSED_BN_REDUCE") != nullptr;  // debugging knob: separate reduce launches
+  // fallback knob, read by the shipped library too (the suite runs the network with it): separate reduce launches
+  static const bool no_fused_reduce = getenv("D3F_NO_FUSED_BN_REDUCE") != nullptr;
   if (!no_fused_reduce) {
     auto writes = [&](const BwdOp& o, int gid) {
       if (o.kind == BW_UNIT || o.kind == BW_HEAD) {

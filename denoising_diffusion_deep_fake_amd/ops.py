@@ -182,6 +182,35 @@ def bn_backward(dA, a, y, coef, gamma, want_dres=False, dtype=F32):
     return dy, dres, dgamma, dbeta
 
 
+def bn_desc(C_, rows, dtype=F32, cpad=None, apply=True, relu=True, res=0, mask=0, fwd_rows=0, fused_rows=0,
+            allow_fused=True, plan_nets=1):
+    """a BatchNorm layer description (d3f_bn_desc).  res: 0 none, 1 a tensor, 2 another layer's y with its coefficient
+    block; mask: 0 none, 1 recomputed from y, 2 read from a"""
+    return _lib.BnDesc(dtype, C_, C_ if cpad is None else cpad, rows, int(apply), int(relu), res, mask, fwd_rows,
+                       fused_rows, int(allow_fused), plan_nets)
+
+
+def bn_layer_plan(d):
+    """the plan of a description (host only: needs no GPU)"""
+    p = _lib.BnPlan()
+    check(_lib.lib().d3f_bn_layer_plan(C.byref(d), C.byref(p)))
+    return p
+
+
+def bn_layer_forward(d, stats, gamma, beta, coef, y, a=None, res=None, res_coef=None, running_mean=None,
+                     running_var=None):
+    """one forward pass of the layer in its planned form, on the caller's buffers (nothing is allocated here)"""
+    check(_lib.lib().d3f_bn_layer_forward(C.byref(d), ptr(stats), ptr(gamma), ptr(beta), ptr(running_mean),
+                                          ptr(running_var), ptr(coef), ptr(y), ptr(res), ptr(res_coef), ptr(a),
+                                          stream_ptr()))
+
+
+def bn_layer_backward(d, partial, gamma, coef, y, dA, dy, a=None, dres=None, dres_acc=False, dgamma=None, dbeta=None):
+    """one backward pass of the layer in its planned form, on the caller's buffers"""
+    check(_lib.lib().d3f_bn_layer_backward(C.byref(d), ptr(partial), ptr(gamma), ptr(coef), ptr(y), ptr(a), ptr(dA),
+                                           ptr(dy), ptr(dres), int(dres_acc), ptr(dgamma), ptr(dbeta), stream_ptr()))
+
+
 def maxpool_forward(x, dtype=F32):
     B, H, W, Cc = x.shape
     out = torch.empty((B, H // 2, W // 2, Cc), dtype=x.dtype, device=_dev(x))

@@ -283,6 +283,47 @@ int d3f_bn_backward(int dtype, const void* dA, const void* a_or_null, const void
                     const float* gamma, int C, int64_t rows, void* dy, void* dres, float* dgamma,
                     float* dbeta, void* workspace, void* stream);
 
+/* One BatchNorm layer as the engine describes, plans and launches it: the description below is planned into the fused
+ * form (the finalize step folded into the streaming pass: fp32 / bf16, C a multiple of 32, 1..1024 partial rows,
+ * allow_fused) or the split form, and a pass is ONE call that runs the planned form -- the same two calls the network
+ * makes.  The three entry points above keep building the split form only. */
+typedef struct d3f_bn_desc {
+  int32_t dtype, C, Cpad; /* storage dtype; channels; stride (channels) of the forward statistics rows, >= C */
+  int64_t rows;           /* rows (pixels) of y */
+  int32_t apply, relu;    /* apply 0: coefficients and running statistics only (a downsample branch; `a` is not written) */
+  int32_t res;            /* 0 none, 1 + a tensor, 2 + another layer's y * scale + shift (its coefficient block) */
+  int32_t mask;           /* backward ReLU mask: 0 none, 1 recomputed as y * scale + shift > 0, 2 read as a > 0 */
+  int32_t fwd_rows;       /* forward partial rows the caller hands in: (sum, sum of squares) per channel, [fwd_rows][Cpad][2] */
+  int32_t fused_rows;     /* > 0: backward partial rows the caller hands in: (sum dz, sum dz * xhat), [fused_rows][C][2];
+                           * 0: the backward pass reduces dz itself into `partial` */
+  int32_t allow_fused, plan_nets; /* plan_nets 1 or 2: networks whose workgroups the fused passes count */
+} d3f_bn_desc;
+typedef struct d3f_bn_plan {
+  int32_t fwd_fused, bwd_fused; /* finalize folded into the streaming pass */
+  int32_t reduce_blocks;        /* partial rows the backward's own reduce writes (1..1024) */
+  int32_t bwd_rows;             /* partial rows the backward reads: fused_rows, or reduce_blocks */
+  int64_t rows_per_block;       /* rows per workgroup of the fused passes (0: neither pass is fused) */
+  uint64_t stat_floats;         /* floats the forward reads from `stats` */
+  uint64_t part_floats;         /* floats `partial` must hold */
+} d3f_bn_plan;
+#define D3F_BN_COEF_ROWS 7 /* a coefficient block: mean invstd scale shift k0 k1 k2, C floats each */
+/* host only (no GPU): validates the description and plans it */
+int d3f_bn_layer_plan(const d3f_bn_desc* d, d3f_bn_plan* plan);
+/* stats -> rows 0..3 of coef, running statistics (both NULL: not tracked), and with apply
+ * a = relu?(y * scale + shift [+ res | + res * scale_r + shift_r]).  res_coef: the other layer's block (res == 2).
+ * rows == 0: nothing is launched.  A description the planned form's kernels cannot run is D3F_EINVAL (-1). */
+int d3f_bn_layer_forward(const d3f_bn_desc* d, float* stats, const float* gamma, const float* beta, float* running_mean,
+                         float* running_var, float* coef, const void* y, const void* res, const float* res_coef, void* a,
+                         void* stream);
+/* dz = dA * mask; partial (part_floats floats: read with fused_rows > 0, else scratch) -> dgamma, dbeta (both NULL: not
+ * wanted), rows 4..6 of coef, dy, and dres (NULL: not wanted) = dz, or += dz with dres_acc.  coef: the block the forward
+ * pass filled; a: the activation (mask == 2). */
+int d3f_bn_layer_backward(const d3f_bn_desc* d, float* partial, const float* gamma, float* coef, const void* y,
+                          const void* a, const void* dA, void* dy, void* dres, int dres_acc, float* dgamma, float* dbeta,
+                          void* stream);
+/* the description and plan the engine holds for BatchNorm layer i (d3f_unet_bn_info's order); host only */
+int d3f_unet_bn_layer(d3f_unet_t h, int i, d3f_bn_desc* d, d3f_bn_plan* plan);
+
 int d3f_maxpool3x3s2_forward(int dtype, const void* in, void* out, uint8_t* idx, int B, int H, int W, int C, void* stream);
 int d3f_maxpool3x3s2_backward(int dtype, const void* dout, const uint8_t* idx, void* din, int accumulate,
                               int B, int H, int W, int C, void* stream);

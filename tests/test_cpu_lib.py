@@ -225,3 +225,113 @@ def test_plan_counts_and_workspace_of_the_pair_and_f32x3_plans():
     assert plan(_lib.F32X3, 16, 1) == ([47, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0],
                                        [50, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0],
                                        [44, 1, 2, 3, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0], 3_479_396_608, 0)
+
+
+def _bn_plan(**kw):
+    """d3f_bn_layer_plan of a description (host only); None when the description is refused"""
+    L = _lib.lib()
+    f = dict(dtype=_lib.F32, C=64, Cpad=None, rows=1000, apply=1, relu=1, res=0, mask=0, fwd_rows=8, fused_rows=0,
+             allow_fused=1, plan_nets=1)
+    f.update(kw)
+    if f["Cpad"] is None:
+        f["Cpad"] = f["C"]
+    d = _lib.BnDesc(*[f[n] for n, _ in _lib.BnDesc._fields_])
+    p = _lib.BnPlan()
+    return p if L.d3f_bn_layer_plan(C.byref(d), C.byref(p)) == 0 else None
+
+
+def test_bn_layer_plan_picks_the_fused_form_inside_its_limits_only():
+    """fused only with allow_fused, fp32 / bf16 storage, whole 32-channel slabs and 1..1024 partial rows -- each
+    boundary from both sides, forward (fwd_rows) and backward (fused_rows, else the reduce's own rows)"""
+    for dtype in (_lib.F32, _lib.BF16):
+        for rows_in, want in ((0, False), (1, True), (2, True), (1023, True), (1024, True), (1025, False)):
+            p = _bn_plan(dtype=dtype, fwd_rows=rows_in, fused_rows=rows_in, rows=4096)
+            assert bool(p.fwd_fused) == want, (dtype, rows_in)
+            # (fused_rows = 0: the backward reads bn_bwd_reduce's rows, 1..1024 of them: fused)
+            assert bool(p.bwd_fused) == (want or rows_in == 0) and p.bwd_rows == (rows_in or p.reduce_blocks)
+        for Cn, want in ((16, False), (32, True), (48, False), (64, True), (96, True), (100, False)):
+            p = _bn_plan(dtype=dtype, C=Cn)
+            assert (bool(p.fwd_fused), bool(p.bwd_fused)) == (want, want), (dtype, Cn)
+            assert (p.rows_per_block > 0) == want
+        p = _bn_plan(dtype=dtype, allow_fused=0)
+        assert not p.fwd_fused and not p.bwd_fused and p.rows_per_block == 0
+        p = _bn_plan(dtype=dtype, apply=0)  # a downsample branch has no streaming pass to fold the finalize into
+        assert not p.fwd_fused and p.bwd_fused
+    # refused descriptions
+    for bad in (dict(C=0), dict(C=64, Cpad=32), dict(rows=-1), dict(res=3), dict(mask=-1), dict(plan_nets=3),
+                dict(dtype=7), dict(fwd_rows=-1), dict(fused_rows=-2)):
+        assert _bn_plan(**bad) is None, bad
+        assert b"bn_layer" in _lib.lib().d3f_last_error()
+
+
+def test_bn_layer_plan_sizes_cover_what_the_kernels_index():
+    """rows_per_block: whole passes of 32 rows, ~256 (fp32) / ~512 (bf16) workgroups in all, half of that per network for
+    plan_nets = 2; reduce_blocks in 1..1024; the scratch sizes reach the largest index the kernels read
+    (statistics: ((fwd_rows - 1) * Cpad + C - 1) * 2 + 1, partial sums: ((rows - 1) * C + C - 1) * 2 + 1 for the rows
+    the reduce writes and for the rows a producer hands in); d3f_bn_backward_workspace_bytes holds the split plan's
+    partial rows, three k rows and its alignment slack"""
+    L = _lib.lib()
+    for dtype, target in ((_lib.F32, 256), (_lib.BF16, 512)):
+        for Cn in (32, 64, 128, 512):
+            for rows in (1, 2, 31, 32, 33, 1000, 4097, 65536, 262144, 1048576):
+                for nets in (1, 2):
+                    for fused_rows in (0, 7, 1024, 4096):
+                        p = _bn_plan(dtype=dtype, C=Cn, Cpad=Cn + 16, rows=rows, fwd_rows=9, fused_rows=fused_rows,
+                                     plan_nets=nets)
+                        slabs, T = Cn // 32, target // nets
+                        rb = max(1, T // slabs)
+                        assert p.rows_per_block % 32 == 0 and p.rows_per_block >= 32
+                        blocks = -(-rows // p.rows_per_block)
+                        assert blocks * slabs <= max(T, slabs), (dtype, Cn, rows, nets)
+                        if rows >= 64 * rb:  # (whole passes of 32 rows cost at most a third of the workgroups then)
+                            assert blocks * slabs >= T // 2, (dtype, Cn, rows, nets, blocks)
+                        assert 1 <= p.reduce_blocks <= 1024
+                        assert p.bwd_rows == (fused_rows or p.reduce_blocks)
+                        assert p.stat_floats == 9 * (Cn + 16) * 2 > (8 * (Cn + 16) + Cn - 1) * 2 + 1
+                        assert p.part_floats > ((max(p.reduce_blocks, fused_rows) - 1) * Cn + Cn - 1) * 2 + 1
+                split = _bn_plan(dtype=dtype, C=Cn, rows=rows, allow_fused=0)
+                assert L.d3f_bn_backward_workspace_bytes(dtype, Cn, rows) == \
+                    (split.reduce_blocks * Cn * 2 + 3 * Cn) * 4 + 256 >= split.part_floats * 4 + 3 * Cn * 4
+    one, two = _bn_plan(rows=65536, plan_nets=1), _bn_plan(rows=65536, plan_nets=2)
+    assert two.rows_per_block == 2 * one.rows_per_block and two.reduce_blocks == one.reduce_blocks
+
+
+def test_bn_layers_of_the_headline_plan():
+    """d3f_unet_bn_layer: the description and plan the engine holds for every BatchNorm layer (host only).  The headline
+    plan (16 x 256 x 256 fp32, DESIGN.md "BatchNorm (train mode)"): 46 layers; 41 run the fused forward -- all but the
+    three downsample branches (apply = 0: only finalized) and the two 16-channel layers of decoder block 4; 44 the fused
+    backward (all but decoder block 4), 39 of them on partial rows their producing data gradient wrote; the stem's 1024
+    statistics rows are the most the fused form takes.  The same description through d3f_bn_layer_plan gives the same plan."""
+    L = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(L.d3f_unet_create(b"resnet34", 3, 3, 16, 256, 256, _lib.F32, C.byref(h)))
+    try:
+        assert L.d3f_unet_num_bn(h) == 46
+        layers = []
+        for i in range(46):
+            d, p, q = _lib.BnDesc(), _lib.BnPlan(), _lib.BnPlan()
+            _lib.check(L.d3f_unet_bn_layer(h, i, C.byref(d), C.byref(p)))
+            _lib.check(L.d3f_bn_layer_plan(C.byref(d), C.byref(q)))
+            assert bytes(p) == bytes(q), i
+            c = C.c_int()
+            rm, rv = C.c_int64(), C.c_int64()
+            _lib.check(L.d3f_unet_bn_info(h, i, None, 0, C.byref(c), C.byref(rm), C.byref(rv)))
+            assert c.value == d.C and d.dtype == _lib.F32 and d.allow_fused == 1 and d.plan_nets == 1
+            layers.append((d, p))
+        d = _lib.BnDesc()
+        assert L.d3f_unet_bn_layer(h, 46, C.byref(d), C.byref(p)) != 0 and L.d3f_unet_bn_layer(h, -1, C.byref(d), C.byref(p)) != 0
+    finally:
+        L.d3f_unet_destroy(h)
+    assert sum(p.fwd_fused for _, p in layers) == 41
+    assert sum(p.bwd_fused for _, p in layers) == 44
+    assert sum(d.fused_rows > 0 for d, _ in layers) == 39
+    split_fwd = [i for i, (_, p) in enumerate(layers) if not p.fwd_fused]
+    assert [layers[i][0].apply for i in split_fwd] == [0, 0, 0, 1, 1]
+    assert [layers[i][0].C for i in split_fwd] == [128, 256, 512, 16, 16]
+    assert [i for i, (_, p) in enumerate(layers) if not p.bwd_fused] == [44, 45]
+    stem_d, stem_p = layers[0]
+    assert (stem_d.C, stem_d.rows, stem_d.fwd_rows, stem_d.mask, stem_d.res) == (64, 16 * 128 * 128, 1024, 1, 0)
+    assert stem_p.fwd_fused and stem_p.bwd_fused and stem_p.rows_per_block == 2048
+    # residual / mask: 16 BasicBlocks end in a residual add (13 identity, 3 downsample branches), masks follow
+    assert sum(d.res == 1 for d, _ in layers) == 13 and sum(d.res == 2 for d, _ in layers) == 3
+    assert all(d.mask == (0 if not d.apply else 2 if d.res else 1) for d, _ in layers)
