@@ -240,6 +240,15 @@ int d3f_unet_predict_u8(d3f_unet_t h, const float* params, float* bnstats, const
   return h->e.predict_u8(params, bnstats, bgr_in, bgr_out, mean, std, workspace, use_graph, (hipStream_t)stream);
 }
 
+int d3f_unet_predict_frames_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
+                               int src_w, int x1, int y1, int cw, int ch, uint8_t* pair_out, const float mean[3],
+                               const float std[3], void* workspace, int use_graph, void* stream) {
+  D3F_CHECK(h && params && bnstats && raw_in && pair_out && mean && std && workspace, "predict_frames_u8: null argument");
+  if (int rc = single_net(h, "predict_frames_u8", "has no eval-mode forward (run each network alone)")) return rc;
+  return h->e.predict_frames_u8(params, bnstats, raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, mean, std, workspace,
+                                use_graph, (hipStream_t)stream);
+}
+
 int d3f_unet_num_segments(d3f_unet_t h) { return h ? h->e.num_segments : -1; }
 int d3f_unet_plan_counts(d3f_unet_t h, int32_t fwd[16], int32_t dgrad[16], int32_t wgrad[16]) {
   D3F_CHECK(h && fwd && dgrad && wgrad, "unet_plan_counts: null argument");
@@ -638,6 +647,13 @@ int d3f_u8rgb_normalise(const uint8_t* in_hwc, float* out_nchw, int B, int H, in
   D3F_CHECK(B > 0 && H > 0 && W > 0, "u8rgb_normalise: bad shape");
   D3F_CHECK(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "u8rgb_normalise: zero std");
   return u8rgb_to_nchw_launch(in_hwc, out_nchw, B, (long)H * W, mean, std, (hipStream_t)stream);
+}
+
+int d3f_crop_resize_cubic_u8(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch, uint8_t* dst,
+                             int H, int W, int64_t dst_row_stride_bytes, void* stream) {
+  D3F_CHECK(src && dst, "crop_resize_cubic_u8: null argument");
+  return crop_resize_cubic_u8_launch(src, B, src_h, src_w, x1, y1, cw, ch, dst, H, W, (long)dst_row_stride_bytes,
+                                     (hipStream_t)stream);
 }
 
 int d3f_affine_warp(const float* in, const float* theta, float* out, int B, int C, int H, int W, void* stream) {

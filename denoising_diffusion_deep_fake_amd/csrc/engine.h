@@ -108,6 +108,13 @@ class UnetEngine {
   // use_graph: the launch sequence is captured once per set of pointers into a hipGraph and replayed
   int predict_u8(const float* params, float* bnstats, const uint8_t* bgr_in, uint8_t* bgr_out,
                  const float mean[3], const float stdv[3], void* ws, int use_graph, hipStream_t s) const;
+  // the frame loop of d3f/script_tools/put_video_through_fake_model.py:111-119, 64-68 on raw frames: crop box
+  // (x1, y1, cw, ch) of uint8 BGR frames [B][src_h][src_w][3] -> bicubic resize to the plan's H x W (resize.hip), written
+  // both as the left half of pair_out [B][H][2W][3] and, normalised, as the network input -> eval-mode forward -> the
+  // fake frame into the right half.  use_graph: captured once per set of pointers, frame size and crop box
+  int predict_frames_u8(const float* params, float* bnstats, const uint8_t* raw_in, int src_h, int src_w, int x1, int y1,
+                        int cw, int ch, uint8_t* pair_out, const float mean[3], const float stdv[3], void* ws,
+                        int use_graph, hipStream_t s) const;
   // eval-mode forward (f32 NCHW in / out) replayed from a hipGraph captured once per set of pointers -- the
   // "hipGraph-captured denoise step" of BASELINE.json configs[4]; bit-identical to forward(training = 0)
   int forward_graph(const float* params, float* bnstats, const float* x, float* out, void* ws, hipStream_t s) const;
@@ -190,17 +197,25 @@ class UnetEngine {
   bool make_split(const NetIO* io, long in_delta, NetSplit* ns) const;
   int predict_u8_launches(const float* params, float* bnstats, const uint8_t* bgr_in, uint8_t* bgr_out,
                           const float mean255[3], const float std255[3], char* ws, hipStream_t s) const;
-  // captured graphs: one slot per entry point; a slot is re-captured when the pointers / constants it baked in change
+  int predict_frames_u8_launches(const float* params, float* bnstats, const uint8_t* raw_in, const int geo[6],
+                                 uint8_t* pair_out, const float mean255[3], const float std255[3], char* ws,
+                                 hipStream_t s) const;
+  // captured graphs: one slot per entry point; a slot is re-captured when what it baked in changes -- the pointers, the
+  // constants and (predict_frames_u8) the raw frame size and crop box
+  struct GraphKey {
+    const void* ptr[5];
+    float cst[6];
+    int geo[6];
+  };
   struct GraphSlot {
     hipGraphExec_t exec = nullptr;
-    const void* key[5] = {};
-    float cst[6] = {};
+    GraphKey key = {};
   };
   template <typename F>
-  int graph_replay(GraphSlot& slot, const void* const key[5], const float cst[6], hipStream_t s, F&& launches) const;
+  int graph_replay(GraphSlot& slot, const GraphKey& key, hipStream_t s, F&& launches) const;
   int wait_for_packed_weights(hipStream_t s) const;
   mutable hipStream_t gstream_ = nullptr;
-  mutable GraphSlot g_predict_, g_eval_;
+  mutable GraphSlot g_predict_, g_eval_, g_frames_;
   BnSync bn_sync_{nullptr, nullptr, 1};
   const BnSync* bn_sync() const { return bn_sync_.fn != nullptr ? &bn_sync_ : nullptr; }
   int train_step_launches(const StepArgs& a, void* ws, hipStream_t s) const;

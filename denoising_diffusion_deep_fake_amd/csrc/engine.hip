@@ -659,7 +659,7 @@ int UnetEngine::predict_u8_launches(const float* params_, float* bnstats, const 
     return rc;
   float* head_out = reinterpret_cast<float*>(ws + head_nchw_off);
   if (int rc = forward_body(params_, bnstats, head_out, ws, 0, s)) return rc;
-  return nchw_to_u8bgr_launch(head_out, bgr_out, B, (long)H * W, mean255, std255, s);
+  return nchw_to_u8bgr_launch(head_out, bgr_out, B, H, W, 3L * W, mean255, std255, s);
 }
 
 int UnetEngine::predict_u8(const float* params_, float* bnstats, const uint8_t* bgr_in, uint8_t* bgr_out,
@@ -674,18 +674,50 @@ int UnetEngine::predict_u8(const float* params_, float* bnstats, const uint8_t* 
   }
   if (!use_graph) return predict_u8_launches(params_, bnstats, bgr_in, bgr_out, m255, s255, ws, s);
   // hipGraph path: at B = 1 the ~100 launches of an eval forward are launch-bound; capture them once
-  const void* key[5] = {params_, bnstats, bgr_in, bgr_out, ws_};
-  const float cst[6] = {m255[0], m255[1], m255[2], s255[0], s255[1], s255[2]};
-  return graph_replay(g_predict_, key, cst, s, [&](hipStream_t gs) {
+  const GraphKey key = {{params_, bnstats, bgr_in, bgr_out, ws_}, {m255[0], m255[1], m255[2], s255[0], s255[1], s255[2]}, {}};
+  return graph_replay(g_predict_, key, s, [&](hipStream_t gs) {
     return predict_u8_launches(params_, bnstats, bgr_in, bgr_out, m255, s255, ws, gs);
+  });
+}
+
+int UnetEngine::predict_frames_u8_launches(const float* params_, float* bnstats, const uint8_t* raw_in, const int geo[6],
+                                           uint8_t* pair_out, const float mean255[3], const float std255[3], char* ws,
+                                           hipStream_t s) const {
+  // one launch writes the real half of the pair and, from the same rounded bytes, the network input
+  if (int rc = crop_resize_cubic_u8_nhwc_launch(dtype, raw_in, B, geo[0], geo[1], geo[2], geo[3], geo[4], geo[5], pair_out,
+                                                H, W, 6L * W, ws + tensors[t_x].off, tensors[t_x].C, mean255, std255, s))
+    return rc;
+  float* head_out = reinterpret_cast<float*>(ws + head_nchw_off);
+  if (int rc = forward_body(params_, bnstats, head_out, ws, 0, s)) return rc;
+  return nchw_to_u8bgr_launch(head_out, pair_out + 3L * W, B, H, W, 6L * W, mean255, std255, s);
+}
+
+int UnetEngine::predict_frames_u8(const float* params_, float* bnstats, const uint8_t* raw_in, int src_h, int src_w, int x1,
+                                  int y1, int cw, int ch, uint8_t* pair_out, const float mean[3], const float stdv[3],
+                                  void* ws_, int use_graph, hipStream_t s) const {
+  D3F_CHECK(in_channels == 3 && classes == 3, "predict_frames_u8: 3-channel frames only (in %d, out %d)", in_channels,
+            classes);
+  char* ws = reinterpret_cast<char*>(ws_);
+  float m255[3], s255[3];
+  for (int c = 0; c < 3; ++c) {  // as predict_u8
+    m255[c] = mean[c] * 255.0f;
+    s255[c] = stdv[c] * 255.0f;
+  }
+  if (int rc = crop_resize_cubic_check(B, src_h, src_w, x1, y1, cw, ch, H, W, 6L * W)) return rc;
+  const int geo[6] = {src_h, src_w, x1, y1, cw, ch};
+  if (!use_graph) return predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, s);
+  const GraphKey key = {{params_, bnstats, raw_in, pair_out, ws_},
+                        {m255[0], m255[1], m255[2], s255[0], s255[1], s255[2]},
+                        {src_h, src_w, x1, y1, cw, ch}};
+  return graph_replay(g_frames_, key, s, [&](hipStream_t gs) {
+    return predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, gs);
   });
 }
 
 int UnetEngine::forward_graph(const float* params_, float* bnstats, const float* x, float* out, void* ws_,
                               hipStream_t s) const {
-  const void* key[5] = {params_, bnstats, x, out, ws_};
-  const float cst[6] = {0, 0, 0, 0, 0, 0};
-  return graph_replay(g_eval_, key, cst, s, [&](hipStream_t gs) { return forward(params_, bnstats, x, out, ws_, 0, gs); });
+  const GraphKey key = {{params_, bnstats, x, out, ws_}, {}, {}};
+  return graph_replay(g_eval_, key, s, [&](hipStream_t gs) { return forward(params_, bnstats, x, out, ws_, 0, gs); });
 }
 
 int UnetEngine::train_step_launches(const StepArgs& a, void* ws_, hipStream_t s) const {
@@ -754,16 +786,16 @@ int UnetEngine::wait_for_packed_weights(hipStream_t s) const {
 }
 
 template <typename F>
-int UnetEngine::graph_replay(GraphSlot& slot, const void* const key[5], const float cst[6], hipStream_t s,
-                             F&& launches) const {
+int UnetEngine::graph_replay(GraphSlot& slot, const GraphKey& key, hipStream_t s, F&& launches) const {
   if (int rc = wait_for_packed_weights(s)) return rc;
   if (gstream_ == nullptr) {
     D3F_HIP(hipStreamCreateWithFlags(&gstream_, hipStreamNonBlocking));
     D3F_HIP(hipEventCreateWithFlags(&ev_gin_, hipEventDisableTiming));
     D3F_HIP(hipEventCreateWithFlags(&ev_gout_, hipEventDisableTiming));
   }
-  const bool same = slot.exec != nullptr && memcmp(key, slot.key, sizeof(slot.key)) == 0 &&
-                    memcmp(cst, slot.cst, sizeof(slot.cst)) == 0;
+  // (GraphKey has no padding: pointers, then 4-byte fields filling whole 8-byte units)
+  static_assert(sizeof(GraphKey) == 5 * sizeof(void*) + 6 * sizeof(float) + 6 * sizeof(int), "GraphKey is compared bytewise");
+  const bool same = slot.exec != nullptr && memcmp(&key, &slot.key, sizeof(GraphKey)) == 0;
   if (!same) {
     if (slot.exec) {
       (void)hipGraphExecDestroy(slot.exec);
@@ -781,8 +813,7 @@ int UnetEngine::graph_replay(GraphSlot& slot, const void* const key[5], const fl
     const hipError_t ei = hipGraphInstantiate(&slot.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     D3F_HIP(ei);
-    memcpy(slot.key, key, sizeof(slot.key));
-    memcpy(slot.cst, cst, sizeof(slot.cst));
+    slot.key = key;
   }
   // order the replay after the caller's stream (input, packed weights) and the caller after the replay
   D3F_HIP(hipEventRecord(ev_gin_, s));
@@ -796,6 +827,7 @@ int UnetEngine::graph_replay(GraphSlot& slot, const void* const key[5], const fl
 UnetEngine::~UnetEngine() {
   if (g_predict_.exec) (void)hipGraphExecDestroy(g_predict_.exec);
   if (g_eval_.exec) (void)hipGraphExecDestroy(g_eval_.exec);
+  if (g_frames_.exec) (void)hipGraphExecDestroy(g_frames_.exec);
   if (g_step_) (void)hipGraphExecDestroy(g_step_);
   if (ev_gin_) (void)hipEventDestroy(ev_gin_);
   if (ev_gout_) (void)hipEventDestroy(ev_gout_);

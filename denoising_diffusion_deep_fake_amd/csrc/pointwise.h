@@ -109,8 +109,20 @@ int nhwc_to_nchw_launch(int dtype, const void* in, float* out, int B, int C, int
 // K16: uint8 BGR frames <-> normalised activations (mean255 = mean*255, std255 = std*255, RGB order)
 int u8bgr_to_nhwc_launch(int dtype, const uint8_t* in, void* out, long npix, int Cpad, const float mean255[3],
                          const float std255[3], hipStream_t stream);
-int nchw_to_u8bgr_launch(const float* in, uint8_t* out, int B, long HW, const float mean255[3],
+// out: rows of W pixels, out_row_stride bytes apart (3 * W: packed frames; 6 * W: the right half of a real|fake pair)
+int nchw_to_u8bgr_launch(const float* in, uint8_t* out, int B, int H, int W, long out_row_stride, const float mean255[3],
                          const float std255[3], hipStream_t stream);
+
+// script_tools frame path (resize.hip): crop box (x1, y1, cw, ch) of uint8 BGR frames [B][src_h][src_w][3] -> bicubic
+// (cv2.INTER_CUBIC in float arithmetic) -> [B][H][W][3] with rows dst_row_stride bytes apart; the _nhwc form also writes
+// the K16 normalisation of the rounded bytes, [B][H][W][Cpad] in RGB order, as u8bgr_to_nhwc_launch would
+// (the host-side argument check of both, for a caller that must refuse before it starts a capture)
+int crop_resize_cubic_check(int B, int src_h, int src_w, int x1, int y1, int cw, int ch, int H, int W, long dst_row_stride);
+int crop_resize_cubic_u8_launch(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch,
+                                uint8_t* dst, int H, int W, long dst_row_stride, hipStream_t stream);
+int crop_resize_cubic_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw,
+                                     int ch, uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
+                                     const float mean255[3], const float std255[3], hipStream_t stream);
 
 // input pipeline: uint8 RGB [B][H][W][3] -> NCHW fp32, ((float)u8 / 255 - mean[c]) / std[c]
 int u8rgb_to_nchw_launch(const uint8_t* in, float* out, int B, long HW, const float mean[3], const float stdv[3],

@@ -272,9 +272,9 @@ __global__ __launch_bounds__(256) void u8bgr_to_nhwc_kernel(const uint8_t* __res
 }
 
 __global__ __launch_bounds__(256) void nchw_to_u8bgr_kernel(const float* __restrict__ in, uint8_t* __restrict__ out,
-                                                            int B, long HW, float m0, float m1, float m2, float s0,
-                                                            float s1, float s2) {
-  const long total = (long)B * HW;
+                                                            int B, long HW, int W, long out_row_stride, float m0,
+                                                            float m1, float m2, float s0, float s1, float s2) {
+  const long total = (long)B * HW, H = HW / W;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long b = i / HW, pix = i - b * HW;
     const float* src = in + b * 3 * HW + pix;
@@ -284,7 +284,8 @@ __global__ __launch_bounds__(256) void nchw_to_u8bgr_kernel(const float* __restr
       t = t < 0 ? 0 : (t > 255 ? 255 : t);
       return (uint8_t)t;
     };
-    uint8_t* o = out + i * 3;
+    const long y = pix / W, x = pix - y * W;
+    uint8_t* o = out + (b * H + y) * out_row_stride + x * 3;
     o[2] = q(src[0], s0, m0);
     o[1] = q(src[HW], s1, m1);
     o[0] = q(src[2 * HW], s2, m2);
@@ -500,11 +501,12 @@ int u8rgb_to_nchw_launch(const uint8_t* in, float* out, int B, long HW, const fl
   return 0;
 }
 
-int nchw_to_u8bgr_launch(const float* in, uint8_t* out, int B, long HW, const float mean255[3],
+int nchw_to_u8bgr_launch(const float* in, uint8_t* out, int B, int H, int W, long out_row_stride, const float mean255[3],
                          const float std255[3], hipStream_t stream) {
+  const long HW = (long)H * W;
   if ((long)B * HW == 0) return 0;
-  hipLaunchKernelGGL(nchw_to_u8bgr_kernel, dim3(grid_for((long)B * HW)), dim3(256), 0, stream, in, out, B, HW,
-                     mean255[0], mean255[1], mean255[2], std255[0], std255[1], std255[2]);
+  hipLaunchKernelGGL(nchw_to_u8bgr_kernel, dim3(grid_for((long)B * HW)), dim3(256), 0, stream, in, out, B, HW, W,
+                     out_row_stride, mean255[0], mean255[1], mean255[2], std255[0], std255[1], std255[2]);
   D3F_HIP(hipGetLastError());
   return 0;
 }

@@ -401,3 +401,40 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
 
 def ema_lerp(ema, online, weight):
     check(_lib.lib().d3f_ema_lerp(ptr(ema), ptr(online), ema.numel(), float(weight), stream_ptr()))
+
+
+def center_crop_box(h, w, width, height):
+    """crop_image_at_center of the script tools (d3f/script_tools/put_video_through_fake_model.py:121-138): the largest
+    centred box of the target aspect inside an h x w frame, as (x1, y1, crop_width, crop_height) -- the reference's float
+    division and int() truncation, kept in Python"""
+    width_scale = w / width
+    height_scale = h / height
+    scale = min(width_scale, height_scale)
+    crop_width = int(width * scale)
+    crop_height = int(height * scale)
+    x1 = (w - crop_width) // 2
+    y1 = (h - crop_height) // 2
+    return x1, y1, crop_width, crop_height
+
+
+def crop_resize_cubic_u8(frames, size, box=None, out=None):
+    """uint8 frames [h, w, 3] or [B, h, w, 3] on the HIP device -> the crop box (x1, y1, cw, ch) resized to size = (H, W)
+    as cv2.resize(..., INTER_CUBIC) defines it in float arithmetic (include/d3f_hip.h: d3f_crop_resize_cubic_u8).
+    box=None: the reference's centre crop to the target aspect.  out: a uint8 tensor [B, H, W, 3] whose pixels are packed
+    and whose rows may be strided -- the left half of a [B, H, 2W, 3] side-by-side buffer, for one."""
+    if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
+        raise ValueError("crop_resize_cubic_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3]")
+    dev = _dev(frames)
+    single = frames.dim() == 3
+    x = (frames.unsqueeze(0) if single else frames).contiguous()
+    B, h, w, _ = x.shape
+    H, W = int(size[0]), int(size[1])
+    x1, y1, cw, ch = center_crop_box(h, w, W, H) if box is None else [int(v) for v in box]
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+    elif (tuple(out.shape) != (B, H, W, 3) or out.dtype != torch.uint8 or out.device != dev or out.stride(3) != 1
+          or out.stride(2) != 3 or (B > 1 and out.stride(0) != H * out.stride(1))):
+        raise ValueError(f"out must be a uint8 tensor of shape {(B, H, W, 3)} on the input's device with packed pixels "
+                         f"and frames H rows apart")
+    check(_lib.lib().d3f_crop_resize_cubic_u8(ptr(x), B, h, w, x1, y1, cw, ch, ptr(out), H, W, out.stride(1), stream_ptr()))
+    return out[0] if single else out

@@ -1,0 +1,104 @@
+"""Render a video through a trained face-swap model as real|fake frames side by side
+(d3f/script_tools/put_video_through_fake_model.py).  Per frame the reference crops at the centre, cv2.resize()s,
+predicts and concatenates on the host; here all of that is one device call per batch of frames
+(LitModule.predict_fake_frames -> Unet.predict_frames_u8), and cv2 only decodes and encodes."""
+import argparse
+import datetime
+from contextlib import nullcontext
+from pathlib import Path
+
+from ..train_deep_fake.lit_module import LitModule
+from .video_writer_context_manager import VideoWriter, batches, import_cv2, open_video_as_generator, video_fps
+
+
+def main():
+
+    args = parse_command_line_arguments()
+
+    RenderFakeVideo(
+        args.video_path,
+        args.checkpoint_path,
+        args.model_a_or_b,
+        args.width,
+        args.height,
+        batch_frames=args.batch_frames,
+        )
+
+
+def parse_command_line_arguments(argv=None):
+    parser = argparse.ArgumentParser()
+
+    parser.add_argument("video_path", help="Video file you want to fake")
+    parser.add_argument("checkpoint_path", help="Model checkpoint path")
+    parser.add_argument("model_a_or_b", choices=["a", "b"], help="Use model A or B to fake image")
+    parser.add_argument("width", help="desired video width")
+    parser.add_argument("height", help="desired video height")
+    parser.add_argument("--batch-frames", type=int, default=1, help="frames per device call")
+
+    return parser.parse_args(argv)
+
+
+class RenderFakeVideo():
+    """frames=: an iterable of decoded BGR frames instead of the video file; sink=: a callable that takes each real|fake
+    frame instead of the .mp4 writer; model=: a loaded LitModule instead of the checkpoint.  With both hooks no video
+    file is touched and cv2 is not needed."""
+
+    def __init__(self, video_path, checkpoint_path, model_a_or_b, image_width, image_height, batch_frames=1,
+                 frames=None, sink=None, model=None):
+
+        self.video_path = Path(video_path)
+        self.checkpoint_path = Path(checkpoint_path) if checkpoint_path is not None else None
+        self.model_a_or_b = model_a_or_b
+        self.image_width = int(image_width)
+        self.image_height = int(image_height)
+        self.batch_frames = int(batch_frames)
+        if self.batch_frames < 1:
+            raise ValueError("batch_frames is at least 1")
+        self.frames = frames
+        self.sink = sink
+
+        if frames is None or sink is None:
+            import_cv2()  # a video file is read or written: fail before the checkpoint is loaded
+
+        self.model = model if model is not None else self.load_model_from_checkpoint()
+
+        self.render_real_fake_video()
+
+    def load_model_from_checkpoint(self):
+        model = LitModule.load_from_checkpoint(self.checkpoint_path)
+        model.cuda()
+        model.eval()
+        return model
+
+    def render_real_fake_video(self):
+        w = 2 * self.image_width
+        h = self.image_height
+
+        if self.sink is not None:
+            writer = nullcontext(None)
+        else:
+            writer = VideoWriter(str(self.get_output_video_path()), w, h, self.get_input_video_properties())
+        frames = self.frames if self.frames is not None else open_video_as_generator(self.video_path)
+
+        with writer as video_writer:
+            write = self.sink if self.sink is not None else video_writer.write
+            for batch, real_frames in batches(frames, self.batch_frames):
+                real_and_fake = self.model.predict_fake_frames(batch, self.model_a_or_b, self.image_width,
+                                                               self.image_height)
+                for frame in real_and_fake[:real_frames]:  # the padding of a short last batch is dropped
+                    write(frame)
+
+    def get_output_video_path(self):
+
+        datetime_str = datetime.datetime.now().strftime("%Y%m%d_%a_%H%M%S")
+
+        output_name = f"{self.video_path.stem}_model_{self.model_a_or_b}_{datetime_str}.mp4"
+        output_path = self.video_path.with_name(output_name)
+        return output_path
+
+    def get_input_video_properties(self):
+        return video_fps(self.video_path)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,72 @@
+"""cv2.VideoWriter as a context manager (d3f/script_tools/video_writer_context_manager.py) and the matching reader.
+cv2 is imported only when a file is opened: the frame path itself runs without it through the `frames=` / `sink=` hooks
+of RenderFakeVideo and VideoToImages."""
+
+NO_CV2 = ("OpenCV (cv2) is not installed, and it is only needed to decode / encode video files: pass decoded BGR frames "
+          "through the frames= hook (an iterable of [h, w, 3] uint8 arrays) and take the output frames through the "
+          "sink= hook (a callable per frame) instead")
+
+
+def import_cv2():
+    try:
+        import cv2
+    except ImportError as e:
+        raise ImportError(NO_CV2) from e
+    return cv2
+
+
+class VideoWriter():
+
+    def __init__(self, output_path, w, h, fps):
+        self.output_path = output_path
+        self.w = w
+        self.h = h
+        self.fps = fps
+
+    def __enter__(self):
+        cv2 = import_cv2()
+        four_cc = cv2.VideoWriter_fourcc(*"mp4v")
+        self.video_writer = cv2.VideoWriter(filename=self.output_path, fourcc=four_cc, fps=self.fps,
+                                            frameSize=(self.w, self.h))
+        return self.video_writer
+
+    def __exit__(self, *args):
+        self.video_writer.release()
+
+
+def video_fps(video_path):
+    cv2 = import_cv2()
+    video_reader = cv2.VideoCapture(str(video_path.resolve()))
+    fps = video_reader.get(cv2.CAP_PROP_FPS)
+    video_reader.release()
+    return fps
+
+
+def open_video_as_generator(video_path):
+    """decoded BGR frames of a video file, one [h, w, 3] uint8 array at a time"""
+    cv2 = import_cv2()
+    video_reader = cv2.VideoCapture(str(video_path.resolve()))
+    try:
+        while video_reader.isOpened():
+            frame_ok, frame = video_reader.read()
+            if not frame_ok:
+                break
+            yield frame
+    finally:
+        video_reader.release()
+
+
+def batches(frames, n):
+    """(stacked [n, h, w, 3] batch, number of real frames in it): frames n at a time; a short last batch is padded by
+    repeating its last frame, so every batch has the shape the first one planned (and captured) for"""
+    import numpy as np
+    chunk = []
+    for frame in frames:
+        chunk.append(np.asarray(frame))
+        if len(chunk) == n:
+            yield np.stack(chunk), n
+            chunk = []
+    if chunk:
+        real = len(chunk)
+        chunk += [chunk[-1]] * (n - real)
+        yield np.stack(chunk), real

@@ -342,6 +342,46 @@ class LitModule(LightningModule):
         output_tensor = model(input_tensor)
         return self.tensor_cv2_to_denormalised(output_tensor, mean, std)
 
+    # ---- raw frames to real|fake frames (script_tools/put_video_through_fake_model.py:111-119, 68) ----
+    @torch.no_grad()
+    def predict_fake_frames(self, raw_bgr_batch, model_a_or_b, width, height):
+        """host frames [B, h, w, 3] (uint8 BGR, any size) -> host real|fake frames [B, height, 2 * width, 3]: centre crop,
+        bicubic resize, `predict_fake` and the side-by-side concatenate of the reference's frame loop in one device call
+        (`Unet.predict_frames_u8`).  Mean / std as in `predict_fake`: a model is fed the other domain's statistics.
+        Pinned and device staging buffers are kept per shape, so a frame loop allocates nothing after its first batch."""
+        p = self.hparams
+        if model_a_or_b == "a":
+            model, mean, std = self.model_a, p.mean_b, p.std_b
+        elif model_a_or_b == "b":
+            model, mean, std = self.model_b, p.mean_a, p.std_a
+        else:
+            raise ValueError("model_a_or_b is 'a' or 'b'")
+        if model.training:
+            raise RuntimeError("predict_fake_frames is the eval-mode frame path: call .eval() first")
+        raw = np.ascontiguousarray(raw_bgr_batch)
+        if raw.dtype != np.uint8 or raw.ndim != 4 or raw.shape[-1] != 3:
+            raise ValueError("predict_fake_frames expects uint8 frames [B, h, w, 3] in BGR order")
+        width, height = int(width), int(height)
+        key = (raw.shape, id(model), width, height)
+        if not hasattr(self, "_frames_buffers"):
+            self._frames_buffers = {}
+        bufs = self._frames_buffers.get(key)
+        if bufs is None:
+            pair = (raw.shape[0], height, 2 * width, 3)
+            bufs = (torch.empty(raw.shape, dtype=torch.uint8).pin_memory(),
+                    torch.empty(raw.shape, dtype=torch.uint8, device=self.device),
+                    torch.empty(pair, dtype=torch.uint8, device=self.device),
+                    torch.empty(pair, dtype=torch.uint8).pin_memory())
+            self._frames_buffers[key] = bufs
+        host_in, dev_in, dev_out, host_out = bufs
+        host_in.copy_(torch.from_numpy(raw))
+        dev_in.copy_(host_in, non_blocking=True)
+        model.predict_frames_u8(dev_in, (height, width), mean, std, graph=bool(p.get("inference_graph", False)),
+                                out=dev_out)
+        host_out.copy_(dev_out, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return host_out.numpy().copy()
+
     def cv2_to_tensor_normalised(self, image_bgr, mean, std):
         image_rgb = np.ascontiguousarray(image_bgr[:, :, ::-1])  # cv2.COLOR_BGR2RGB
         tensor = torch.from_numpy(image_rgb).float().to(self.device)

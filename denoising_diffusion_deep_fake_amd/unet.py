@@ -777,6 +777,45 @@ class Unet(nn.Module, _NetsRuntime):
         eng.keep = (x, out)  # the captured graph bakes these pointers in: keep them alive with the engine
         return out[0] if single else out
 
+    @torch.no_grad()
+    def predict_frames_u8(self, raw_bgr, size, mean, std, graph=True, out=None):
+        """The frame path of d3f/script_tools/put_video_through_fake_model.py:111-119, 68 on decoded frames of any
+        size: uint8 BGR frames [h,w,3] or [B,h,w,3] on the HIP device -> centre crop to the aspect of size = (H, W)
+        (`ops.center_crop_box`) -> bicubic resize (`ops.crop_resize_cubic_u8`) -> `predict_u8` -> the real|fake frames
+        [B,H,2W,3] ([H,2W,3] for a single frame), all in one C call.  The left half is byte for byte
+        `ops.crop_resize_cubic_u8`, the right half `predict_u8` of the left half at the same batch size.  `graph=True`
+        replays a hipGraph captured per (input, output) buffer pair, raw frame size and crop box: pass the same buffers
+        again (`out=`) in a frame loop."""
+        from . import ops
+        if raw_bgr.dtype != torch.uint8 or raw_bgr.shape[-1] != 3 or raw_bgr.dim() not in (3, 4):
+            raise ValueError("predict_frames_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3] in BGR order")
+        if raw_bgr.device.type != "cuda":
+            raise D3FError("predict_frames_u8 needs frames on the HIP device (no CPU fallback)")
+        single = raw_bgr.dim() == 3
+        x = raw_bgr.unsqueeze(0) if single else raw_bgr
+        x = x.contiguous()
+        B, h, w, _ = x.shape
+        H, W = int(size[0]), int(size[1])
+        if H % 32 or W % 32:
+            raise RuntimeError(f"Wrong input shape height={H}, width={W}. Expected image height and width "
+                               f"divisible by 32.")
+        x1, y1, cw, ch = ops.center_crop_box(h, w, W, H)
+        self._ensure_flat(x.device)
+        eng = self._engine(B, H, W, x.device)
+        self._pack_if_needed(eng)
+        shape = (B, H, 2 * W, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device:
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on the input's device")
+        rt = self._rt
+        m = (C.c_float * 3)(*[float(v) for v in mean])
+        sd = (C.c_float * 3)(*[float(v) for v in std])
+        check(_lib.lib().d3f_unet_predict_frames_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), h, w, x1, y1, cw, ch,
+                                                    ptr(out), m, sd, ptr(eng.workspace), 1 if graph else 0, stream_ptr()))
+        eng.keep = (x, out)  # the captured graph bakes these pointers in: keep them alive with the engine
+        return out[0] if single else out
+
     def export_activation(self, name):
         """debugging / parity tests: an internal tensor of the MOST RECENT forward (+ backward) as NCHW f32 --
         "<conv name>:y" raw conv output, ":a" post BatchNorm(+residual)+ReLU activation, ":da" gradient w.r.t. that

@@ -142,6 +142,19 @@ int d3f_unet_forward_graph(d3f_unet_t h, const float* params, float* bnstats, co
  * sequence is captured into a hipGraph on first use (per set of pointers) and replayed afterwards. */
 int d3f_unet_predict_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* bgr_in, uint8_t* bgr_out,
                         const float mean[3], const float std[3], void* workspace, int use_graph, void* stream);
+/* The frame loop of d3f/script_tools/put_video_through_fake_model.py:54-70, 111-145 on decoded frames of any size:
+ * raw_in [B][src_h][src_w][3] uint8 BGR in device memory -> crop box (x1, y1, cw, ch) -> bicubic resize to the handle's
+ * H x W (d3f_crop_resize_cubic_u8 below) -> d3f_unet_predict_u8 -> pair_out [B][H][2W][3]: the left half is the resized
+ * real frame, the right half the fake (np.concatenate([real, fake], axis=1)).  Three steps around the forward pass:
+ * one kernel writes the real half and, from the same rounded bytes, the normalised network input (the reference
+ * normalises cv2's uint8 result); the last kernel writes the fake half.  The left half is byte for byte
+ * d3f_crop_resize_cubic_u8, the right half d3f_unet_predict_u8 of the left half.  The crop box is the caller's
+ * (crop_image_at_center's float arithmetic stays in Python: ops.center_crop_box).  use_graph != 0: captured on first use
+ * per set of pointers, frame size, crop box and mean / std, replayed afterwards.  Per-frame results do not depend on the
+ * other frames of a batch, but the plan's kernel choices depend on B: bytes are not promised equal across batch sizes. */
+int d3f_unet_predict_frames_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
+                               int src_w, int x1, int y1, int cw, int ch, uint8_t* pair_out, const float mean[3],
+                               const float std[3], void* workspace, int use_graph, void* stream);
 /* gradients of every parameter (written, not accumulated) for the preceding training forward.
  * The backward pass is cut into d3f_unet_num_segments() buckets so a data-parallel caller can
  * all-reduce bucket k while bucket k+1 computes: run segments [seg_begin, seg_end) in order 0..n;
@@ -336,6 +349,18 @@ int d3f_nhwc_to_nchw(int dtype, const void* in, float* out, int B, int C, int H,
  * own order of fp32 operations (bit-identical); the batch crosses worker IPC and PCIe as bytes. */
 int d3f_u8rgb_normalise(const uint8_t* in_hwc, float* out_nchw, int B, int H, int W, const float mean[3],
                         const float std[3], void* stream);
+
+/* crop_image_at_center + resize_image of the script tools (d3f/script_tools/put_video_through_fake_model.py:121-145,
+ * video_to_center_cropped_images.py:83-107): the crop box (x1, y1, cw, ch) of src [B][src_h][src_w][3] uint8 (any
+ * channel order) resized to dst [B][H][W][3] uint8 whose rows lie dst_row_stride_bytes apart (>= 3 * W; frames H rows
+ * apart) -- 6 * W writes the left half of a side-by-side frame.  The resize is cv2.INTER_CUBIC in float arithmetic:
+ * source coordinate f = (d + 0.5) * n_in / n_out - 0.5 computed exactly (integers), taps floor(f) - 1 .. floor(f) + 2
+ * clamped to the crop (replicate border), Keys weights with A = -0.75, no antialiasing, horizontal then vertical pass in
+ * fp32, rintf (half to even), clamp to 0..255; equal extents copy the bytes.  OpenCV's own 8-bit path uses 11-bit
+ * fixed-point coefficients and may differ from this definition by one level on some pixels: byte equality with OpenCV
+ * is not claimed.  Refused: a box outside the frame, non-positive sizes, extents above 16384, a stride below 3 * W. */
+int d3f_crop_resize_cubic_u8(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch, uint8_t* dst,
+                             int H, int W, int64_t dst_row_stride_bytes, void* stream);
 
 /* GPU-side augmentation of the training step (d3f/train_denoiser/lit_module.py:55-65 RandomAffine, applied at :113):
  * out[b] = grid_sample(in[b], affine_grid(theta[b]), bilinear, zeros padding, align_corners=False), NCHW f32,

@@ -1,0 +1,98 @@
+"""The frame path of script_tools at the authors' size, 1080x1920 BGR frames -> 448x448 (HIP events, device resident).
+
+  resize       : d3f_crop_resize_cubic_u8 alone (centre crop 1080x1080 -> 448x448), B = 1 and B = 8; and its
+                 global-tap form at 2160x3840 -> 64x64
+  frames       : Unet.predict_frames_u8 (resize + forward + real|fake pair), B = 1 eager / hipGraph, B = 8 eager
+  yardstick    : Unet.predict_u8 on frames that are ALREADY 448x448 (what the parent commit offers), same B and mode
+
+Back-to-back enqueues on one stream, ITERS iterations after WARMUP, the forms alternating in ROUNDS rounds; the figure is
+the median round's time per call (and per frame).  Host work of the reference's loop (cv2.resize on one CPU thread, the
+concatenate, two PCIe trips) is not part of any figure here.  One JSON line at the end.
+    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+import torch
+from denoising_diffusion_deep_fake_amd import Unet, _lib, ops
+
+RAW, SIZE = (1080, 1920), (448, 448)
+MEAN, STD = [0.5, 0.5, 0.5], [0.5, 0.5, 0.5]
+
+
+def timed(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3  # us per call
+
+
+def compare(forms, warmup, iters, rounds):
+    """forms: {name: callable}; returns {name: (median, min, max)} in us per call, the forms alternating"""
+    for _ in range(warmup):
+        for fn in forms.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in forms}
+    for _ in range(rounds):
+        for name, fn in forms.items():
+            times[name].append(timed(fn, iters))
+    return {name: (statistics.median(t), min(t), max(t)) for name, t in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--precision", default="f32", choices=["f32", "bf16"])
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=5)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the MI355X"
+    print(f"{torch.cuda.get_device_name(0)}, torch {torch.__version__}, library digest {_lib.built_digest()}")
+    torch.manual_seed(0)
+    net = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
+    g = torch.Generator().manual_seed(1)
+    result = {"raw": list(RAW), "size": list(SIZE), "precision": args.precision, "digest": _lib.built_digest(),
+              "iters": args.iters, "rounds": args.rounds, "us_per_call": {}}
+    for B in (1, 8):
+        raw = torch.randint(0, 256, (B,) + RAW + (3,), generator=g, dtype=torch.uint8).cuda()
+        small = ops.crop_resize_cubic_u8(raw, SIZE)
+        resized = torch.empty_like(small)
+        pair = torch.empty((B, SIZE[0], 2 * SIZE[1], 3), dtype=torch.uint8, device="cuda")
+        fake = torch.empty_like(small)
+        forms = {
+            f"resize_B{B}": lambda: ops.crop_resize_cubic_u8(raw, SIZE, out=resized),
+            f"frames_eager_B{B}": lambda: net.predict_frames_u8(raw, SIZE, MEAN, STD, graph=False, out=pair),
+            f"predict_u8_eager_B{B}": lambda: net.predict_u8(small, MEAN, STD, graph=False, out=fake),
+        }
+        if B == 1:
+            forms[f"frames_graph_B{B}"] = lambda: net.predict_frames_u8(raw, SIZE, MEAN, STD, graph=True, out=pair)
+            forms[f"predict_u8_graph_B{B}"] = lambda: net.predict_u8(small, MEAN, STD, graph=True, out=fake)
+        for name, (med, lo, hi) in compare(forms, args.warmup, args.iters, args.rounds).items():
+            print(f"{name:24s} {med:9.1f} us per call (min {lo:.1f}, max {hi:.1f})   {med / B:9.1f} us per frame")
+            result["us_per_call"][name] = round(med, 1)
+    # the kernel's other form: a crop so much larger than the output that a tile's patch exceeds the LDS budget (taps from
+    # global memory) -- 2160x3840 -> 64x64, a shrink of 33.75
+    big = torch.randint(0, 256, (1, 2160, 3840, 3), generator=g, dtype=torch.uint8).cuda()
+    thumb = torch.empty((1, 64, 64, 3), dtype=torch.uint8, device="cuda")
+    forms = {"resize_global_taps_2160x3840_to_64x64_B1": lambda: ops.crop_resize_cubic_u8(big, (64, 64), out=thumb)}
+    for name, (med, lo, hi) in compare(forms, args.warmup, args.iters, args.rounds).items():
+        print(f"{name:24s} {med:9.1f} us per call (min {lo:.1f}, max {hi:.1f})")
+        result["us_per_call"][name] = round(med, 1)
+    u = result["us_per_call"]
+    result["resize_share_of_predict_u8_B1"] = round(u["resize_B1"] / u["predict_u8_eager_B1"], 4)
+    result["resize_share_of_predict_u8_B8"] = round(u["resize_B8"] / u["predict_u8_eager_B8"], 4)
+    # bytes the resize must move per frame: the crop once, the output once
+    need = 1080 * 1080 * 3 + SIZE[0] * SIZE[1] * 3
+    result["resize_GBps_B8"] = round(8 * need / (u["resize_B8"] * 1e-6) / 1e9, 1)
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
