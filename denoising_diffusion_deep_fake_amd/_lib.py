@@ -15,6 +15,12 @@ HEADER_PATH = _HERE.parent / "include" / "d3f_hip.h"
 F32, BF16, F32X3 = 0, 1, 2  # F32X3: fp32 tensors, contractions on the bf16 matrix pipe (exact 3-way split)
 
 
+# D3F_ACT_*: the head activation codes, by the canonical names Unet.activation holds
+ACT_IDENTITY, ACT_SIGMOID, ACT_TANH, ACT_SOFTMAX, ACT_LOGSOFTMAX, ACT_CLAMP = range(6)
+HEAD_ACTIVATIONS = {None: ACT_IDENTITY, "sigmoid": ACT_SIGMOID, "tanh": ACT_TANH, "softmax2d": ACT_SOFTMAX,
+                    "logsoftmax": ACT_LOGSOFTMAX, "clamp": ACT_CLAMP}
+
+
 class D3FError(RuntimeError):
     pass
 
@@ -60,6 +66,8 @@ PROTOTYPES = {
     "d3f_unet_pair_pack_weights": (_i, [_p, C.POINTER(_p), _p, _p]),
     "d3f_unet_pair_forward": (_i, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), _p, _p]),
     "d3f_unet_pair_backward": (_i, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), _p, _i, _i, _i, _p]),
+    "d3f_unet_set_head_activation": (_i, [_p, _i]),
+    "d3f_unet_head_activation": (_i, [_p]),
     "d3f_unet_num_params": (_i, [_p]),
     "d3f_unet_param_info": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(C.c_int32), C.POINTER(_i), C.POINTER(_i64)]),
     "d3f_unet_param_floats": (_i64, [_p]),
@@ -115,6 +123,8 @@ PROTOTYPES = {
     "d3f_bn_layer_forward": (_i, [_bnd, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "d3f_bn_layer_backward": (_i, [_bnd, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
     "d3f_unet_bn_layer": (_i, [_p, _i, _bnd, _bnp]),
+    "d3f_head_activation_forward": (_i, [_i, _p, _p, _i, _i, _i, _i, _p]),
+    "d3f_head_activation_backward": (_i, [_i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "d3f_maxpool3x3s2_forward": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _p]),
     "d3f_maxpool3x3s2_backward": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "d3f_upsample2x_backward": (_i, [_i, _p, _p, _i, _i, _i, _i, _p]),

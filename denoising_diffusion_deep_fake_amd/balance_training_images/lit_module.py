@@ -35,7 +35,7 @@ class LitModule(LightningModule):
 
     def create_model_instance(self):
         p = self.hparams
-        return Unet(encoder_name=p["encoder_name"], encoder_weights=None, in_channels=3, classes=3, activation=None,
+        return Unet(encoder_name=p["encoder_name"], encoder_weights=None, in_channels=3, classes=3, activation=p.get("activation"),
                     compute_dtype=p.get("precision", "f32"))
 
     def _data_path(self):

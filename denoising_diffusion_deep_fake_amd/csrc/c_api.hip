@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "head_act.h"
 #include "philox.h"
 
 namespace d3f {
@@ -188,6 +189,15 @@ int d3f_unet_pair_backward(d3f_unet_t h, const float* const params[2], const flo
   return h->e.backward(params[0], grad_out[0], grads[0], workspace, seg_begin, seg_end, (hipStream_t)stream, join ? 1 : 0,
                        &io);
 }
+static_assert(D3F_ACT_IDENTITY == HEAD_ACT_IDENTITY && D3F_ACT_SIGMOID == HEAD_ACT_SIGMOID && D3F_ACT_TANH == HEAD_ACT_TANH &&
+                  D3F_ACT_SOFTMAX == HEAD_ACT_SOFTMAX && D3F_ACT_LOGSOFTMAX == HEAD_ACT_LOGSOFTMAX &&
+                  D3F_ACT_CLAMP == HEAD_ACT_CLAMP && HEAD_ACT_COUNT == 6,
+              "d3f_hip.h states the activation codes");
+int d3f_unet_set_head_activation(d3f_unet_t h, int act) {
+  D3F_CHECK(h, "unet_set_head_activation: null handle");
+  return h->e.set_head_activation(act);
+}
+int d3f_unet_head_activation(d3f_unet_t h) { return h ? h->e.head_activation() : -1; }
 int d3f_unet_num_params(d3f_unet_t h) { return h ? (int)h->e.params.size() : -1; }
 int d3f_unet_param_info(d3f_unet_t h, int i, char* name, int name_cap, int32_t shape[4], int* ndim,
                         int64_t* offset) {
@@ -623,6 +633,18 @@ int d3f_unet_bn_layer(d3f_unet_t h, int i, d3f_bn_desc* d, d3f_bn_plan* plan) {
     return 0;
   }
   return set_error(-1, "bn_layer: index %d", i);
+}
+
+int d3f_head_activation_forward(int act, const float* z, float* a, int B, int C, int H, int W, void* stream) {
+  if (int rc = head_act_check(act, C, C)) return rc;
+  D3F_CHECK(z && a, "head_activation_forward: null argument");
+  return head_act_forward_launch(act, z, a, B, C, H, W, (hipStream_t)stream);
+}
+int d3f_head_activation_backward(int act, int dtype, const float* z, const float* g, float* dz_nchw, void* dy_nhwc,
+                                 int B, int C, int H, int W, int Cpad, void* stream) {
+  if (int rc = head_act_check(act, C, Cpad)) return rc;
+  D3F_CHECK(z && g && dz_nchw && dy_nhwc, "head_activation_backward: null argument");
+  return head_act_backward_launch(act, sdt(dtype), z, g, dz_nchw, dy_nhwc, B, C, H, W, Cpad, (hipStream_t)stream);
 }
 
 int d3f_maxpool3x3s2_forward(int dtype, const void* in, void* out, uint8_t* idx, int B, int H, int W,

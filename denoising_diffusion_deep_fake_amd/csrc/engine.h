@@ -138,6 +138,13 @@ class UnetEngine {
   typedef int (*AllReduceFn)(void* ctx, float* data, int64_t count, void* stream);
   bool bn_sync_installed() const { return bn_sync_.fn != nullptr; }
   void set_bn_sync(AllReduceFn fn, void* ctx, int world) { bn_sync_ = BnSync{fn, ctx, world > 0 ? world : 1}; }
+  // The activation behind the segmentation head (head_act.h: HeadAct; smp's Activation).  Identity: the head's convolution
+  // writes the caller's `out`, exactly the launches of a network without the feature.  Otherwise it writes z into the
+  // workspace (head_nchw_off), one more launch writes out = act(z), and the backward pass's head turns (z, dout) into dz,
+  // overwriting z: ONE backward pass (its segment 0) per training forward; a second one is refused.
+  // A pair's two networks share the setting.  A change drops the captured graphs, as a pointer change does.
+  int set_head_activation(int act);
+  int head_activation() const { return head_act_; }
   int export_tensor(const char* name, const void* ws, float* out_nchw, hipStream_t s) const;
   int export_shape(const char* name, int32_t dims[3]) const;
 
@@ -191,8 +198,13 @@ class UnetEngine {
   int first_mid_unit_ = -1;   // first unit (index into `units`) of the second part (encoder.layer1)
   int first_late_unit_ = -1;  // first unit of the third part (encoder.layer3)
   // predict_u8 graph: private capture/launch stream + the pointers and constants the captured graph bakes in
+  // apply_act false: `out` receives z, whatever the activation (the uint8 entries apply it in their last kernel)
   int forward_body(const float* params, float* bnstats, float* out, char* ws, int training, hipStream_t s,
-                   const NetSplit* ns = nullptr) const;
+                   const NetSplit* ns = nullptr, bool apply_act = true) const;
+  // the uint8 entries' last kernel: head output (head_nchw_off) -> [activation ->] de-normalised BGR bytes
+  int head_to_u8bgr(const char* ws, uint8_t* out, long out_row_stride, const float mean255[3], const float std255[3],
+                    hipStream_t s) const;
+  void drop_graphs() const;
   // what a launch of this engine hands to the kernels: null for a single network
   bool make_split(const NetIO* io, long in_delta, NetSplit* ns) const;
   int predict_u8_launches(const float* params, float* bnstats, const uint8_t* bgr_in, uint8_t* bgr_out,
@@ -223,7 +235,11 @@ class UnetEngine {
   mutable StepArgs g_step_key_{};
   mutable const void* g_step_ws_ = nullptr;
   mutable hipEvent_t ev_gin_ = nullptr, ev_gout_ = nullptr;
+  int head_act_ = 0;          // HEAD_ACT_IDENTITY
+  // NCHW fp32 head output: predict_u8's, and z of an activated head, which the head of the backward pass turns into dz IN
+  // PLACE (the bias gradient's channel sum reads that): the workspace is the one of a plan without activations
   size_t head_nchw_off = 0;
+  mutable bool head_z_live_ = false;  // the slot holds the z of a training forward that no backward pass has consumed
   size_t ws_top = 0;
   int t_x = -1, t_pool = -1, head = -1, conv1 = -1;
   size_t pool_idx_off = 0, stats_off = 0, bnpart_off = 0, dz_off = 0, dfull_off = 0,

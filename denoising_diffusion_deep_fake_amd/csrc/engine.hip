@@ -8,6 +8,8 @@
 #include "engine.h"
 #include <vector>
 
+#include "head_act.h"
+
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -573,7 +575,7 @@ int UnetEngine::forward(const float* params_, float* bnstats, const float* x, fl
 
 // everything after the input layout conversion; `out` = NCHW fp32 destination of the head
 int UnetEngine::forward_body(const float* params_, float* bnstats, float* out, char* ws, int training,
-                             hipStream_t s, const NetSplit* ns) const {
+                             hipStream_t s, const NetSplit* ns, bool apply_act) const {
   auto T = [&](int tid) { return ws + tensors[tid].off; };
   auto coef = [&](const Unit& u) { return reinterpret_cast<float*>(ws + u.coef_off); };
   D3F_CHECK(ns == nullptr || (training && bn_sync() == nullptr), "unet: the pair engine runs train-mode passes with "
@@ -617,9 +619,23 @@ int UnetEngine::forward_body(const float* params_, float* bnstats, float* out, c
     b.w = ws + (u.wino ? u.wu_off : u.upfold ? u.wfc_off : u.wf_off);
     b.slabs = reinterpret_cast<float*>(ws + splitk_off);
     if (!u.bn) {  // segmentation head
-      b.out = out;
       b.bias = params_ + u.bias_off;
-      if (int rc = conv_layer_forward(u, b, false, s, ns)) return rc;
+      if (head_act_ == HEAD_ACT_IDENTITY || !apply_act) {
+        b.out = out;
+        if (int rc = conv_layer_forward(u, b, false, s, ns)) return rc;
+        continue;
+      }
+      // activated head: z into the workspace (net 1: its own copy), where backward finds it; then out = act(z)
+      float* z = reinterpret_cast<float*>(ws + head_nchw_off);
+      NetSplit zs{};
+      if (ns) {
+        zs = *ns;
+        zs.out = zs.ws;
+      }
+      b.out = z;
+      if (int rc = conv_layer_forward(u, b, false, s, ns ? &zs : nullptr)) return rc;
+      if (int rc = head_act_forward_launch(head_act_, z, out, B, u.Cout, u.Ho, u.Wo, s, ns)) return rc;
+      head_z_live_ = training != 0;
       continue;
     }
     const Unit* ds = u.res_unit >= 0 ? &units[u.res_unit] : nullptr;
@@ -658,8 +674,37 @@ int UnetEngine::predict_u8_launches(const float* params_, float* bnstats, const 
                                     std255, s))
     return rc;
   float* head_out = reinterpret_cast<float*>(ws + head_nchw_off);
-  if (int rc = forward_body(params_, bnstats, head_out, ws, 0, s)) return rc;
-  return nchw_to_u8bgr_launch(head_out, bgr_out, B, H, W, 3L * W, mean255, std255, s);
+  if (int rc = forward_body(params_, bnstats, head_out, ws, 0, s, nullptr, false)) return rc;
+  head_z_live_ = false;
+  return head_to_u8bgr(ws, bgr_out, 3L * W, mean255, std255, s);
+}
+
+int UnetEngine::head_to_u8bgr(const char* ws, uint8_t* out, long out_row_stride, const float mean255[3],
+                              const float std255[3], hipStream_t s) const {
+  const float* head_out = reinterpret_cast<const float*>(ws + head_nchw_off);
+  if (head_act_ == HEAD_ACT_IDENTITY) return nchw_to_u8bgr_launch(head_out, out, B, H, W, out_row_stride, mean255, std255, s);
+  return head_act_to_u8bgr_launch(head_act_, head_out, out, B, H, W, out_row_stride, mean255, std255, s);
+}
+
+int UnetEngine::set_head_activation(int act) {
+  D3F_CHECK(act >= 0 && act < HEAD_ACT_COUNT, "head activation: unknown code %d (D3F_ACT_IDENTITY .. D3F_ACT_CLAMP)", act);
+  if (act != head_act_) {
+    drop_graphs();  // they bake the head's launches in
+    head_act_ = act;
+  }
+  return 0;
+}
+
+void UnetEngine::drop_graphs() const {
+  for (GraphSlot* slot : {&g_predict_, &g_eval_, &g_frames_})
+    if (slot->exec) {
+      (void)hipGraphExecDestroy(slot->exec);
+      slot->exec = nullptr;
+    }
+  if (g_step_) {
+    (void)hipGraphExecDestroy(g_step_);
+    g_step_ = nullptr;
+  }
 }
 
 int UnetEngine::predict_u8(const float* params_, float* bnstats, const uint8_t* bgr_in, uint8_t* bgr_out,
@@ -688,8 +733,9 @@ int UnetEngine::predict_frames_u8_launches(const float* params_, float* bnstats,
                                                 H, W, 6L * W, ws + tensors[t_x].off, tensors[t_x].C, mean255, std255, s))
     return rc;
   float* head_out = reinterpret_cast<float*>(ws + head_nchw_off);
-  if (int rc = forward_body(params_, bnstats, head_out, ws, 0, s)) return rc;
-  return nchw_to_u8bgr_launch(head_out, pair_out + 3L * W, B, H, W, 6L * W, mean255, std255, s);
+  if (int rc = forward_body(params_, bnstats, head_out, ws, 0, s, nullptr, false)) return rc;
+  head_z_live_ = false;
+  return head_to_u8bgr(ws, pair_out + 3L * W, 6L * W, mean255, std255, s);
 }
 
 int UnetEngine::predict_frames_u8(const float* params_, float* bnstats, const uint8_t* raw_in, int src_h, int src_w, int x1,
@@ -825,10 +871,7 @@ int UnetEngine::graph_replay(GraphSlot& slot, const GraphKey& key, hipStream_t s
 }
 
 UnetEngine::~UnetEngine() {
-  if (g_predict_.exec) (void)hipGraphExecDestroy(g_predict_.exec);
-  if (g_eval_.exec) (void)hipGraphExecDestroy(g_eval_.exec);
-  if (g_frames_.exec) (void)hipGraphExecDestroy(g_frames_.exec);
-  if (g_step_) (void)hipGraphExecDestroy(g_step_);
+  drop_graphs();
   if (ev_gin_) (void)hipEventDestroy(ev_gin_);
   if (ev_gout_) (void)hipEventDestroy(ev_gout_);
   if (gstream_) (void)hipStreamDestroy(gstream_);
@@ -875,6 +918,13 @@ int UnetEngine::backward(const float* params_, const float* dout, float* grads, 
             "offsets and runs with per-GPU BatchNorm statistics");
   NetSplit split{};
   const NetSplit* ns = make_split(io, io ? io->dout : 0, &split) ? &split : nullptr;
+  // The head's output gradient as the bias sum reads it: the caller's dout, or an activated head's dz (NCHW fp32, written
+  // by the head of this pass over z in the workspace: net 1's lies in its own workspace copy)
+  const bool head_act = head_act_ != HEAD_ACT_IDENTITY;
+  const float* head_dz = head_act ? reinterpret_cast<const float*>(ws + head_nchw_off) : dout;
+  NetSplit split_dz = split;
+  split_dz.in = split_dz.ws;
+  const NetSplit* ns_dz = (ns && head_act) ? &split_dz : ns;
   auto T = [&](int tid) { return ws + tensors[tid].off; };
   auto G = [&](int gid) { return gid == -2 ? ws + dz_off : ws + gtensors[gid].off; };
   auto coef = [&](const Unit& u) { return reinterpret_cast<float*>(ws + u.coef_off); };
@@ -919,8 +969,8 @@ int UnetEngine::backward(const float* params_, const float* dout, float* grads, 
     }
     if (head_bias_pending) {  // the head's bias gradient: two small launches that nothing on the chain waits for
       const Unit& uh = units[head];
-      if (int rc = channel_sum_nchw_launch(dout, B, uh.Cout, (long)uh.Ho * uh.Wo, reinterpret_cast<float*>(ws + bsum_off),
-                                           grads + uh.bias_off, ws_stream, ns))
+      if (int rc = channel_sum_nchw_launch(head_dz, B, uh.Cout, (long)uh.Ho * uh.Wo, reinterpret_cast<float*>(ws + bsum_off),
+                                           grads + uh.bias_off, ws_stream, ns_dz))
         return rc;
       head_bias_pending = false;
     }
@@ -957,10 +1007,20 @@ int UnetEngine::backward(const float* params_, const float* dout, float* grads, 
     const Unit& u = units[op.unit];
     char* dy = ws + u.dy_off;
     if (op.kind == BW_HEAD) {
-      if (int rc = nchw_to_nhwc_launch(dtype, dout, dy, B, u.Cout, u.Ho, u.Wo, u.CoutD, s, ns)) return rc;
+      if (head_act) {  // (z, dout) -> dz, as dY and (over z) as the NCHW tensor of the bias sum: one launch for the layout pass
+        D3F_CHECK(head_z_live_, "unet backward: the head's pre-activation output of the last training forward is gone (an "
+                  "earlier backward pass turned it into dz, or an inference pass overwrote it): one backward pass per "
+                  "training forward with an activated head");
+        float* z = reinterpret_cast<float*>(ws + head_nchw_off);
+        if (int rc = head_act_backward_launch(head_act_, dtype, z, dout, z, dy, B, u.Cout, u.Ho, u.Wo, u.CoutD, s, ns))
+          return rc;
+        head_z_live_ = false;
+      } else {
+        if (int rc = nchw_to_nhwc_launch(dtype, dout, dy, B, u.Cout, u.Ho, u.Wo, u.CoutD, s, ns)) return rc;
+      }
       if (skip_w) {  // (profiling ablation without weight-gradient launches: nothing would flush it)
-        if (int rc = channel_sum_nchw_launch(dout, B, u.Cout, (long)u.Ho * u.Wo,
-                                             reinterpret_cast<float*>(ws + bsum_off), grads + u.bias_off, s, ns))
+        if (int rc = channel_sum_nchw_launch(head_dz, B, u.Cout, (long)u.Ho * u.Wo,
+                                             reinterpret_cast<float*>(ws + bsum_off), grads + u.bias_off, s, ns_dz))
           return rc;
       } else {
         head_bias_pending = true;  // with the head's weight gradient, on the weight-gradient stream (flush_pending)

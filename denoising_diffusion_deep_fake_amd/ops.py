@@ -48,6 +48,42 @@ def nhwc_to_nchw(x, c, dtype=F32):
     return out
 
 
+def head_activation_code(act):
+    """D3F_ACT_* code of an activation given by code or by one of the names `Unet(activation=...)` accepts"""
+    if isinstance(act, int) and not isinstance(act, bool):
+        return act
+    from .unet import canonical_activation
+    return _lib.HEAD_ACTIVATIONS[canonical_activation(act)]
+
+
+def head_activation_forward(act, z):
+    """a = act(z) over the channel axis of z [B, C, H, W] f32 (C <= 16): the launch the engine makes behind the
+    segmentation head's convolution"""
+    z = z.contiguous().float()
+    B, Cc, H, W = z.shape
+    a = torch.empty_like(z)
+    _dev(z)
+    check(_lib.lib().d3f_head_activation_forward(head_activation_code(act), ptr(z), ptr(a), B, Cc, H, W, stream_ptr()))
+    return a
+
+
+def head_activation_backward(act, z, g, dtype=F32, cpad=None):
+    """(z, g = d loss / d act(z)), both [B, C, H, W] f32 -> (dz NCHW f32, dY NHWC [B, H, W, cpad] in the storage dtype,
+    rounded once from the f32 dz, padding channels zero): the launch at the head of the engine's backward pass"""
+    z, g = z.contiguous().float(), g.contiguous().float()
+    B, Cc, H, W = z.shape
+    if g.shape != z.shape:
+        raise ValueError(f"head_activation_backward: g {tuple(g.shape)} does not match z {tuple(z.shape)}")
+    if cpad is None:
+        ve = 8 if dtype == BF16 else 4
+        cpad = (Cc + ve - 1) // ve * ve
+    dz = torch.empty_like(z)
+    dy = torch.empty((B, H, W, cpad), dtype=_tdtype(dtype), device=_dev(z))
+    check(_lib.lib().d3f_head_activation_backward(head_activation_code(act), dtype, ptr(z), ptr(g), ptr(dz), ptr(dy),
+                                                  B, Cc, H, W, cpad, stream_ptr()))
+    return dz, dy
+
+
 def pack_weights(d, w, dtype=F32, dgrad=True):
     L = _lib.lib()
     dev = _dev(w)

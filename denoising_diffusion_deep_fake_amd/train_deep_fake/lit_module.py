@@ -103,7 +103,7 @@ class LitModule(LightningModule):
             encoder_weights=None,
             in_channels=3,
             classes=3,
-            activation=None,
+            activation=p.get("activation"),  # optional hparam (smp's names); saved with the checkpoint's hparams
             compute_dtype=p.get("precision", "f32"),
         )
 

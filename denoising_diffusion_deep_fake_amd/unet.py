@@ -92,16 +92,49 @@ class _Decoder(nn.Module):
 
 _ENCODERS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}
 
+# names of smp's Activation module -> the canonical name `Unet.activation` holds (a key of _lib.HEAD_ACTIVATIONS)
+_ACTIVATION_NAMES = {None: None, "identity": None, "sigmoid": "sigmoid", "tanh": "tanh", "softmax2d": "softmax2d",
+                     "softmax": "softmax2d", "logsoftmax": "logsoftmax", "clamp": "clamp"}
+
+
+def canonical_activation(activation):
+    """the `activation` argument of smp.Unet -> None / "sigmoid" / "tanh" / "softmax2d" / "logsoftmax" / "clamp";
+    ValueError for what the HIP path does not run"""
+    if activation in ("argmax", "argmax2d"):
+        raise ValueError(f"Activation {activation} returns an integer tensor and has no gradient: the HIP path trains "
+                         "through its head and does not offer argmax heads")
+    if callable(activation):
+        raise ValueError(f"Activation {activation!r} is a Python callable: there is no device kernel for a Python "
+                         "callable (use sigmoid/softmax/logsoftmax/tanh/clamp/None)")
+    if not (activation is None or isinstance(activation, str)) or activation not in _ACTIVATION_NAMES:
+        raise ValueError("Activation should be callable/sigmoid/softmax/logsoftmax/tanh/argmax/argmax2d/clamp/None; "
+                         f"got {activation}")
+    return _ACTIVATION_NAMES[activation]
+
+
+class _HeadActivation(nn.Module):
+    """Last child of `segmentation_head` for an activated head: parameter-free, shows the activation in repr.  Its
+    forward() is never used: the engine applies the activation (csrc/head_act.hip)."""
+
+    def __init__(self, name):
+        super().__init__()
+        self.name = name
+
+    def extra_repr(self):
+        return self.name
+
 
 class _Engine:
     """one libd3f_hip whole-network plan + its workspace, for a fixed (B, H, W, dtype)."""
 
-    def __init__(self, encoder_name, in_channels, classes, B, H, W, dtype, device, nets, plan_nets):
+    def __init__(self, encoder_name, in_channels, classes, B, H, W, dtype, device, nets, plan_nets, activation=None):
         # nets = 2: a pair, B images PER network; plan_nets = 2 with nets = 1: one network planned like the pair
         L = _lib.lib()
         self.h = C.c_void_p()
         check(L.d3f_unet_create_nets(encoder_name.encode(), in_channels, classes, B, H, W, dtype, nets, plan_nets,
                                      C.byref(self.h)))
+        if activation is not None:  # (a handle starts as identity)
+            check(L.d3f_unet_set_head_activation(self.h, _lib.HEAD_ACTIVATIONS[activation]))
         self.nets = nets
         self.net_stride = L.d3f_unet_net_workspace_stride(self.h)
         self.shape = (B, H, W)
@@ -269,7 +302,7 @@ class _NetsRuntime:
         nets = self._nets
         a = nets[0]
         plan_nets = max(len(nets), getattr(a, "plan_nets", 1))  # (a pair plans for two networks whatever its nets say)
-        key = (B, H, W, a.compute_dtype, device.index, plan_nets)
+        key = (B, H, W, a.compute_dtype, device.index, plan_nets, a.activation)
         pool = self._rt["engines"].setdefault(key, [])
         for eng in pool:
             if not eng.in_use:
@@ -277,7 +310,8 @@ class _NetsRuntime:
         if len(pool) >= self.MAX_LIVE_GRAPHS:
             raise D3FError(f"{len(pool)} forward passes of shape {(B, H, W)} are waiting for their backward pass; "
                            f"run inference-only forwards under torch.no_grad()")
-        eng = _Engine(a.encoder_name, a.in_channels, a.classes, B, H, W, a.compute_dtype, device, len(nets), plan_nets)
+        eng = _Engine(a.encoder_name, a.in_channels, a.classes, B, H, W, a.compute_dtype, device, len(nets), plan_nets,
+                      a.activation)
         if a._rt.get("bn_sync"):  # (a UnetPair refuses synchronised statistics before it gets here)
             eng.set_bn_sync(*a._rt["bn_sync"])
         pool.append(eng)
@@ -403,14 +437,19 @@ def _views_unverified(module, incompatible_keys):
 class Unet(nn.Module, _NetsRuntime):
     def __init__(self, encoder_name="resnet34", encoder_weights=None, in_channels=3, classes=3,
                  activation=None, compute_dtype="f32"):
+        """activation: a name of smp's Activation module, applied last to the head's convolution output in fp32 --
+        None / "identity", "sigmoid", "tanh", "softmax2d" / "softmax", "logsoftmax", "clamp" (to [0, 1], smp's default
+        bounds).  smp builds nn.Softmax() and nn.LogSoftmax() without `dim`, which torch resolves to dim=1 for a 4-D
+        input: "softmax" and "logsoftmax" run over the channel axis, "softmax" is "softmax2d".  `self.activation` holds
+        the canonical name ("identity" -> None, "softmax" -> "softmax2d").  "argmax" / "argmax2d" (integer output, no
+        gradient) and callables (no device kernel) are refused."""
         super().__init__()
         if encoder_name not in _ENCODERS:
             raise KeyError(f"Wrong encoder name `{encoder_name}`, supported encoders: {list(_ENCODERS)}")
         if encoder_weights is not None:
             raise KeyError(f"Wrong pretrained weights `{encoder_weights}` for encoder `{encoder_name}`. "
                            f"Available options are: [None] (no network access)")
-        if activation is not None:
-            raise ValueError(f"Activation should be None (the reference passes activation=None); got {activation}")
+        self.activation = canonical_activation(activation)
         if compute_dtype not in _DTYPES:
             raise ValueError(f"compute_dtype must be one of f32 / f32x3 / bf16, got {compute_dtype}")
         self.encoder_name, self.in_channels, self.classes = encoder_name, in_channels, classes
@@ -418,7 +457,9 @@ class Unet(nn.Module, _NetsRuntime):
         self.plan_nets = 1  # set_plan_nets(2): this network's kernels are chosen as for a UnetPair (bit-identity runs)
         self.encoder = _Encoder(in_channels, _ENCODERS[encoder_name])
         self.decoder = _Decoder()
-        self.segmentation_head = nn.Sequential(nn.Conv2d(16, classes, 3, padding=1), nn.Identity(), nn.Identity())
+        self.segmentation_head = nn.Sequential(
+            nn.Conv2d(16, classes, 3, padding=1), nn.Identity(),
+            nn.Identity() if self.activation is None else _HeadActivation(self.activation))
         nn.init.xavier_uniform_(self.segmentation_head[0].weight)
         nn.init.constant_(self.segmentation_head[0].bias, 0)
         self._init_runtime_state()
@@ -849,7 +890,7 @@ class UnetPair(_NetsRuntime):
     def __init__(self, net_a, net_b):
         if not (isinstance(net_a, Unet) and isinstance(net_b, Unet)) or net_a is net_b:
             raise TypeError("UnetPair takes two distinct d3f Unet modules")
-        for attr in ("encoder_name", "in_channels", "classes", "compute_dtype"):
+        for attr in ("encoder_name", "in_channels", "classes", "compute_dtype", "activation"):
             if getattr(net_a, attr) != getattr(net_b, attr):
                 raise ValueError(f"UnetPair: the two networks differ in {attr}")
         self.nets = (net_a, net_b)

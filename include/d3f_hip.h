@@ -104,6 +104,35 @@ int d3f_unet_pair_forward(d3f_unet_t h, const float* const params[2], float* con
 int d3f_unet_pair_backward(d3f_unet_t h, const float* const params[2], const float* const grad_out[2],
                            float* const grads[2], void* workspace, int seg_begin, int seg_end, int join, void* stream);
 
+/* The `activation` argument of Unet(...): smp's Activation module, which smp.Unet applies last in its SegmentationHead
+ * (the model the reference builds at d3f/train_denoiser/lit_module.py:46-52 with activation=None), over the head's
+ * convolution output z [B][classes][H][W]:
+ *   D3F_ACT_IDENTITY    z                                            (None, "identity")
+ *   D3F_ACT_SIGMOID     1 / (1 + exp(-z))
+ *   D3F_ACT_TANH        tanh(z)
+ *   D3F_ACT_SOFTMAX     softmax over the channel axis per pixel      ("softmax2d", and "softmax": nn.Softmax() without
+ *                       dim resolves to dim = 1 for a 4-D input)
+ *   D3F_ACT_LOGSOFTMAX  log-softmax over the channel axis
+ *   D3F_ACT_CLAMP       clamp(z, 0, 1)                               (smp's default bounds)
+ * in fp32 whatever the compute dtype.  Host only, either kind of handle (a pair's two networks share the setting); the
+ * default after d3f_unet_create / d3f_unet_create_nets is identity, whose launches are exactly those of a handle that
+ * never heard of activations.  Every entry point honours the setting: d3f_unet_forward (both modes), _forward_graph,
+ * _pair_forward, _predict_u8 and _predict_frames_u8 (applied inside their last kernel), _backward, _backward_nojoin,
+ * _pair_backward (the upstream gradient is the one w.r.t. the ACTIVATED output; z is kept in the workspace by the
+ * training forward, so the caller may overwrite `out` before backward; segment 0 of the backward pass turns z into dz in
+ * place, so an activated head takes ONE backward pass per training forward: a second one is an error, not a wrong
+ * gradient) and _train_step.  The workspace size does not depend on the setting.  Setting a different value
+ * drops the handle's captured graphs (eval, predict, frames, step), as a pointer change does.  argmax heads return
+ * integer tensors without a gradient and are not offered. */
+#define D3F_ACT_IDENTITY 0
+#define D3F_ACT_SIGMOID 1
+#define D3F_ACT_TANH 2
+#define D3F_ACT_SOFTMAX 3
+#define D3F_ACT_LOGSOFTMAX 4
+#define D3F_ACT_CLAMP 5
+int d3f_unet_set_head_activation(d3f_unet_t h, int act);
+int d3f_unet_head_activation(d3f_unet_t h); /* the code, or < 0 for a null handle */
+
 /* parameter table, in torch named_parameters() order; offsets are in floats into ONE flat
  * f32 buffer that holds every parameter (gradients use the same layout). */
 int d3f_unet_num_params(d3f_unet_t h);
@@ -336,6 +365,16 @@ int d3f_bn_layer_backward(const d3f_bn_desc* d, float* partial, const float* gam
                           void* stream);
 /* the description and plan the engine holds for BatchNorm layer i (d3f_unet_bn_info's order); host only */
 int d3f_unet_bn_layer(d3f_unet_t h, int i, d3f_bn_desc* d, d3f_bn_plan* plan);
+
+/* The head activation's two launches as the engine makes them (D3F_ACT_* above; smp's Activation behind
+ * SegmentationHead, d3f/train_denoiser/lit_module.py:46-52).  forward: a = act(z), both NCHW f32 [B][C][H][W].
+ * backward: (z, g = d loss / d a) -> dz, written twice by one launch: dz_nchw NCHW f32 (the bias gradient's channel sum
+ * reads it) and dy_nhwc [B][H][W][Cpad] in the storage dtype, rounded once from the f32 dz, channels [C, Cpad) zero
+ * (the head's data and weight gradients read it); dz_nchw may be z itself.  C < 1, C > 16, Cpad < C and an unknown act are D3F_EINVAL (-1)
+ * before anything is enqueued. */
+int d3f_head_activation_forward(int act, const float* z, float* a, int B, int C, int H, int W, void* stream);
+int d3f_head_activation_backward(int act, int dtype, const float* z, const float* g, float* dz_nchw, void* dy_nhwc,
+                                 int B, int C, int H, int W, int Cpad, void* stream);
 
 int d3f_maxpool3x3s2_forward(int dtype, const void* in, void* out, uint8_t* idx, int B, int H, int W, int C, void* stream);
 int d3f_maxpool3x3s2_backward(int dtype, const void* dout, const uint8_t* idx, void* din, int accumulate,
