@@ -7,8 +7,9 @@ reconstruction error and bins the scores into `number_of_classes` difficulty cla
     validation_step : same blend, eval-mode forward, compute_difficulty_loss = mean |pred - image| per image (:123-142)
     validation_epoch_end : concatenate, compute_difficulty_index_for_each_loss (min-max, clamp, bin) (:144-193)
 
-Device work is HIP: ops.noise_blend_fixed, the Unet engine, the fused loss, ops.l1_per_image.  Differences from the
-reference, on purpose: TensorBoard image / histogram logging is dropped (no tensorboard / matplotlib on the box);
+Device work is HIP: ops.noise_blend_fixed, the Unet engine, the fused loss, ops.l1_per_image, ops.image_grid_u8 (the
+`image` / `image_noisy` / `image_prediction` grids of :102-104, written as PNG files: helpers/image_grid_logger.py).
+Differences from the reference, on purpose: the matplotlib histogram figure of validation_epoch_end is not drawn;
 the reference accepts `--output_list` but never writes it (dead option) -- here the classes ARE written, one
 "<relative image path>\\t<class>" line per image, when `output_image_list_path` is set.
 `device_rng: true` (off by default; optional `rng_seed`): the noise is drawn inside the blend kernel by the counter-based
@@ -19,16 +20,18 @@ from torch.utils.data import DataLoader
 
 from .. import ops, rng
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset
+from ..helpers import ImageLoggingMixin
 from ..lightning import LightningModule
 from ..loss_functions import MseStructuralSimilarityLoss
 from ..optim import FusedAdam
 from ..unet import Unet
 
 
-class LitModule(LightningModule):
+class LitModule(ImageLoggingMixin, LightningModule):
     def __init__(self, **kwargs):
         super().__init__()
         self.save_hyperparameters()
+        self.setup_image_logging()  # image_logging_scheduler; None unless `image_logging: true`
         self.model = self.create_model_instance()
         self.training_criterion = MseStructuralSimilarityLoss(-1.0, 1.0)
         self.difficulty_index = None  # filled by validation_epoch_end: (image index [N], class [N])
@@ -67,10 +70,15 @@ class LitModule(LightningModule):
         return FusedAdam(self.model.parameters(), lr=p.learning_rate, module=self.model)
 
     def training_step(self, batch, batch_idx):
+        self.update_image_logging_schedule()
         image = batch["image"]
         image_noisy = self.blend_fixed_amount_of_noise_with_each_sample(image)
         image_prediction = self.model(image_noisy)
         loss = self.training_criterion(image_prediction, image)
+        self.log_batch_as_image_grid("image", image)
+        self.log_batch_as_image_grid("image_noisy", image_noisy)
+        self.log_batch_as_image_grid("image_prediction", image_prediction)
+        self.emit_image_grids()
         self.log("loss", loss)
         return loss
 

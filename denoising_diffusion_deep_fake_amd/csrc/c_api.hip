@@ -678,6 +678,18 @@ int d3f_crop_resize_cubic_u8(const uint8_t* src, int B, int src_h, int src_w, in
                                      (hipStream_t)stream);
 }
 
+int d3f_image_grid_shape(int images, int nrow, int padding, int H, int W, int32_t dims[2]) {
+  D3F_CHECK(dims != nullptr, "image_grid_shape: null argument");
+  return image_grid_shape(images, nrow, padding, H, W, dims);
+}
+
+int d3f_image_grid_u8(const float* const* batches, int n, int B, int C, int H, int W, int images, int nrow, int padding,
+                      float pad_value, float scale, float shift, uint8_t* out, void* stream) {
+  D3F_CHECK(batches && out, "image_grid_u8: null argument");
+  return image_grid_u8_launch(batches, n, B, C, H, W, images, nrow, padding, pad_value, scale, shift, out,
+                              (hipStream_t)stream);
+}
+
 int d3f_affine_warp(const float* in, const float* theta, float* out, int B, int C, int H, int W, void* stream) {
   if (B == 0) return 0;
   D3F_CHECK(in && theta && out && in != out, "affine_warp: null or aliased argument");

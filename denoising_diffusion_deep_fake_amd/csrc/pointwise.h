@@ -124,6 +124,12 @@ int crop_resize_cubic_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int s
                                      int ch, uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
                                      const float mean255[3], const float std255[3], hipStream_t stream);
 
+// training image grids (image_grid.hip): make_grid + scale + clamp + uint8 of up to 8 fp32 NCHW batches in one launch;
+// `batches` is a host array of n device pointers, out [n][GH][GW][3] with {GH, GW} from image_grid_shape
+int image_grid_shape(int images, int nrow, int padding, int H, int W, int32_t dims[2]);
+int image_grid_u8_launch(const float* const* batches, int n, int B, int C, int H, int W, int images, int nrow, int padding,
+                         float pad_value, float scale, float shift, uint8_t* out, hipStream_t stream);
+
 // input pipeline: uint8 RGB [B][H][W][3] -> NCHW fp32, ((float)u8 / 255 - mean[c]) / std[c]
 int u8rgb_to_nchw_launch(const uint8_t* in, float* out, int B, long HW, const float mean[3], const float stdv[3],
                          hipStream_t stream);

@@ -1,0 +1,7 @@
+"""`d3f.helpers` (d3f/helpers/__init__.py): the image-logging cadence of the three LitModules and the device-side grid
+logger behind their `log_batch_as_image_grid`.  (The reference's convert_pyplot_figure_to_image_tensor serves balance's
+matplotlib histogram, which is not built here.)"""
+from .image_grid_logger import ImageGridLogger, ImageLoggingMixin
+from .logging_scheduler import LoggingScheduler
+
+__all__ = ["ImageGridLogger", "ImageLoggingMixin", "LoggingScheduler"]

@@ -474,3 +474,33 @@ def crop_resize_cubic_u8(frames, size, box=None, out=None):
                          f"and frames H rows apart")
     check(_lib.lib().d3f_crop_resize_cubic_u8(ptr(x), B, h, w, x1, y1, cw, ch, ptr(out), H, W, out.stride(1), stream_ptr()))
     return out[0] if single else out
+
+
+def image_grid_shape(images, nrow=3, padding=2, size=(1, 1)):
+    """(GH, GW) of torchvision.utils.make_grid over `images` images of size = (H, W) (d3f_image_grid_shape; host only)"""
+    dims = (C.c_int32 * 2)()
+    check(_lib.lib().d3f_image_grid_shape(int(images), int(nrow), int(padding), int(size[0]), int(size[1]), dims))
+    return int(dims[0]), int(dims[1])
+
+
+def image_grid_u8(batches, nrow=3, padding=2, pad_value=0.0, scale=0.5, shift=0.5, max_images=9, out=None):
+    """log_batch_as_image_grid of the LitModules (d3f/train_deep_fake/lit_module.py:235-249) for up to 8 tags in one
+    launch: an NCHW batch, or a list of up to 8 of one shape, on the HIP device -> uint8 [n, GH, GW, 3], grid i being
+    make_grid(batches[i][:max_images], nrow, padding, pad_value) * scale + shift, clamped to 0..1, times 255, truncated
+    (include/d3f_hip.h: d3f_image_grid_u8).  out: a contiguous uint8 tensor of that shape to write into."""
+    single = isinstance(batches, torch.Tensor)
+    xs = [b.detach().contiguous().float() for b in ([batches] if single else list(batches))]
+    if not xs or any(x.dim() != 4 or x.shape != xs[0].shape or x.device != xs[0].device for x in xs):
+        raise ValueError("image_grid_u8 expects an NCHW batch or a list of NCHW batches of one shape on one device")
+    dev = _dev(xs[0])
+    n, (B, Cc, H, W) = len(xs), xs[0].shape
+    images = min(B, int(max_images))
+    GH, GW = image_grid_shape(images, nrow, padding, (H, W))
+    if out is None:
+        out = torch.empty((n, GH, GW, 3), dtype=torch.uint8, device=dev)
+    elif tuple(out.shape) != (n, GH, GW, 3) or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {(n, GH, GW, 3)} on the input's device")
+    pointers = (C.c_void_p * n)(*[x.data_ptr() for x in xs])
+    check(_lib.lib().d3f_image_grid_u8(pointers, n, B, Cc, H, W, images, int(nrow), int(padding), float(pad_value),
+                                       float(scale), float(shift), ptr(out), stream_ptr()))
+    return out

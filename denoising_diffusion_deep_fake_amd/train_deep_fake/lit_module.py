@@ -36,6 +36,7 @@ from torch.utils.data import DataLoader
 
 from .. import ops, rng
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset, ToUint8Tensor
+from ..helpers import ImageLoggingMixin
 from ..lightning import LightningModule
 from ..loss_functions import MseStructuralSimilarityLoss
 from ..optim import EMA, FusedAdam
@@ -81,10 +82,11 @@ class ShiftScaleRotate(nn.Module):
         return torch.where(d["apply"].reshape(-1, 1, 1, 1), warped, x)
 
 
-class LitModule(LightningModule):
+class LitModule(ImageLoggingMixin, LightningModule):
     def __init__(self, **kwargs):
         super().__init__()
         self.save_hyperparameters()
+        self.setup_image_logging()  # image_logging_scheduler (:44); None unless `image_logging: true`
         self.augmentation = self.create_gpu_augmentation()
         self.model_a = self.create_model_instance()
         self.model_b = self.create_model_instance()
@@ -203,6 +205,7 @@ class LitModule(LightningModule):
             else:
                 batch_b = self.augment(batch_b, 1)
         if optimizer_idx == 0:
+            self.update_image_logging_schedule()  # once per batch (:148)
             loss = self.training_step_for_one_model("a", batch_a, self.model_a, self.ema_model_b)
         if optimizer_idx == 1:
             loss = self.training_step_for_one_model("b", batch_b, self.model_b, self.ema_model_a)
@@ -243,6 +246,7 @@ class LitModule(LightningModule):
         forward of UnetPair(model_a, model_b), the two losses.  Returns (loss_a, loss_b); the caller runs ONE backward,
         torch.autograd.backward([loss_a, loss_b]), then both optimizer steps."""
         p = self.hparams
+        self.update_image_logging_schedule()
         reals, noisy = [], []
         for stream, (key, mean) in enumerate((("a", p.mean_a), ("b", p.mean_b))):
             x = batch[key]["image"]
@@ -255,10 +259,13 @@ class LitModule(LightningModule):
             reals.append(x)
         predictions = self._unet_pair()(noisy[0], noisy[1])
         losses = []
-        for name, prediction, real in zip("ab", predictions, reals):
+        for name, prediction, real, noisy_real in zip("ab", predictions, reals, noisy):
             loss = self.criterion(prediction, real)
+            self.log_batch_as_image_grid(f"denoise_1_model_input/{name}", noisy_real)
+            self.log_batch_as_image_grid(f"denoise_2_model_prediction/{name}", prediction)
             self.log(f"loss_denoise/train_{name}", loss)
             losses.append(loss)
+        self.emit_image_grids()  # the four tags of the sequential loop, one launch
         self.log("epoch", float(self.current_epoch))
         return tuple(losses)
 
@@ -283,6 +290,9 @@ class LitModule(LightningModule):
             noisy_real = self.blend_random_amount_of_noise_with_each_sample(real, "ab".index(name))
         real_prediction = real_model(noisy_real)
         loss = self.criterion(real_prediction, real)
+        self.log_batch_as_image_grid(f"denoise_1_model_input/{name}", noisy_real)
+        self.log_batch_as_image_grid(f"denoise_2_model_prediction/{name}", real_prediction)
+        self.emit_image_grids()
         self.log(f"loss_denoise/train_{name}", loss)
         return loss
 
@@ -294,6 +304,11 @@ class LitModule(LightningModule):
             noisy_fake = self.blend_random_amount_of_noise_with_each_sample(fake, "ab".index(name))
         real_prediction = real_model(noisy_fake)
         loss = self.criterion(real_prediction, real)
+        self.log_batch_as_image_grid(f"swap_1_real/{name}", real)
+        self.log_batch_as_image_grid(f"swap_2_fake/{name}_to_fake", fake)
+        self.log_batch_as_image_grid(f"swap_3_model_input/{name}", noisy_fake)
+        self.log_batch_as_image_grid(f"swap_4_model_prediction/{name}", real_prediction)
+        self.emit_image_grids()
         self.log(f"swap_difference/{name}", swap_diff)
         self.log(f"loss_swap/train_{name}", loss)
         return loss

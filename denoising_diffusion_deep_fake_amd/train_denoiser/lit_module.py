@@ -11,6 +11,8 @@ Differences, all outside the parity-checked arithmetic
   * kornia's RandomAffine is replaced by the same parameter ranges drawn with torch RNG and one HIP warp
     kernel (ops.affine_warp = affine_grid + grid_sample(bilinear, zeros), parity-tested against torch on CPU);
     the random draws themselves are not part of the numerics contract; off in benchmarks (`augment: false`);
+  * `image_logging: true` (absent: off; not together with `graph_step`): the `image` / `image_noisy` /
+    `image_prediction` grids of :121-123 as PNG files (helpers/image_grid_logger.py), one HIP kernel per logging step;
   * `device_rng: true` (off by default; optional `rng_seed`): the noise, y and augmentation draws come from the
     counter-based generator inside the kernels that consume them (rng.py, csrc/philox.h) -- a function of (seed,
     global_step, rank), so a resumed run continues the interrupted one.  Not together with `graph_step`.
@@ -23,6 +25,7 @@ from torch.utils.data import DataLoader
 
 from .. import ops, rng
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset, ToUint8Tensor
+from ..helpers import ImageLoggingMixin
 from ..lightning import LightningModule
 from ..loss_functions import MseStructuralSimilarityLoss
 from ..optim import FusedAdam
@@ -52,10 +55,11 @@ class RandomAffine(torch.nn.Module):
         return ops.affine_warp(x, theta)  # K17: affine_grid + grid_sample(bilinear, zeros) in one HIP kernel
 
 
-class LitModule(LightningModule):
+class LitModule(ImageLoggingMixin, LightningModule):
     def __init__(self, **kwargs):
         super().__init__()
         self.save_hyperparameters()
+        self.setup_image_logging()  # image_logging_scheduler; None unless `image_logging: true` (not with graph_step)
         self.model = self.create_model_instance()
         self.training_criterion = MseStructuralSimilarityLoss(-1.0, 1.0)
         self.shared_augmentation_sequence = self.create_shared_augmentation_sequence()
@@ -131,6 +135,7 @@ class LitModule(LightningModule):
         return self.model(image)
 
     def training_step(self, batch, batch_idx):
+        self.update_image_logging_schedule()
         image = batch["image"]
         if image.dtype == torch.uint8:
             image = self.normalise_on_device(image)
@@ -153,6 +158,10 @@ class LitModule(LightningModule):
         image_noisy = self.blend_random_amount_of_noise_with_each_sample(image)
         image_prediction = self.model(image_noisy)
         loss = self.training_criterion(image_prediction, image)
+        self.log_batch_as_image_grid("image", image)
+        self.log_batch_as_image_grid("image_noisy", image_noisy)
+        self.log_batch_as_image_grid("image_prediction", image_prediction)
+        self.emit_image_grids()
         self.log("loss", loss)
         return loss
 

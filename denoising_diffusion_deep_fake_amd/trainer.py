@@ -310,6 +310,8 @@ class Trainer:
         return d
 
     def _flush_metrics(self):
+        if hasattr(self.module, "drain_image_grids"):
+            self.module.drain_image_grids()  # queued image grids (helpers/image_grid_logger.py): wait, then write
         if not self._metric_rows or self.global_rank != 0:
             self._metric_rows = []
             return
@@ -437,4 +439,6 @@ class Trainer:
             self._flush_metrics()
             self.current_epoch += 1
         torch.cuda.synchronize()
+        if hasattr(model, "drain_image_grids"):
+            model.drain_image_grids()
         return self

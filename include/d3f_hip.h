@@ -401,6 +401,23 @@ int d3f_u8rgb_normalise(const uint8_t* in_hwc, float* out_nchw, int B, int H, in
 int d3f_crop_resize_cubic_u8(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch, uint8_t* dst,
                              int H, int W, int64_t dst_row_stride_bytes, void* stream);
 
+/* log_batch_as_image_grid of the three LitModules (d3f/train_deep_fake/lit_module.py:235-249,
+ * d3f/train_denoiser/lit_module.py:157-171, d3f/balance_training_images/lit_module.py:197-211):
+ * torchvision.utils.make_grid(batch[:images], nrow, padding, pad_value), the whole grid -- padding included -- taken
+ * through * scale + shift and clamp(0, 1), then TensorBoard's uint8 conversion (* 255, truncated), as HWC bytes.
+ * Layout: xmaps = min(nrow, images), ymaps = ceil(images / xmaps); the grid is GH x GW = (ymaps * (H + padding) + padding)
+ * x (xmaps * (W + padding) + padding); image k at row (k / xmaps) * (H + padding) + padding, column (k % xmaps) *
+ * (W + padding) + padding; everything else, the blank cells of a ragged last row too, is pad_value; images == 1 gives the
+ * bare H x W image; C == 1 is replicated to three channels.  Value: t = v * scale + shift in fp32 (product and sum
+ * rounded separately), t = fminf(fmaxf(t, 0), 1) (NaN -> 0), byte = (uint8_t)(t * 255.0f).
+ * d3f_image_grid_shape (host only) writes {GH, GW}.  d3f_image_grid_u8: batches is a HOST array of n device pointers to
+ * fp32 NCHW batches [B][C][H][W] of one shape; out [n][GH][GW][3] (any byte alignment); one launch for all n.
+ * Refused before any device call: n outside 1..8, images outside 1..B, nrow < 1, padding outside 0..64, H or W outside
+ * 1..16384, C other than 1 or 3, an output of 2^31 bytes or more, null pointers. */
+int d3f_image_grid_shape(int images, int nrow, int padding, int H, int W, int32_t dims[2]);
+int d3f_image_grid_u8(const float* const* batches, int n, int B, int C, int H, int W, int images, int nrow, int padding,
+                      float pad_value, float scale, float shift, uint8_t* out, void* stream);
+
 /* GPU-side augmentation of the training step (d3f/train_denoiser/lit_module.py:55-65 RandomAffine, applied at :113):
  * out[b] = grid_sample(in[b], affine_grid(theta[b]), bilinear, zeros padding, align_corners=False), NCHW f32,
  * theta [B][2][3] row-major (normalised output -> input coordinates).  in and out must not alias. */
