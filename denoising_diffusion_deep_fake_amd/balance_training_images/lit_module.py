@@ -9,16 +9,25 @@ reconstruction error and bins the scores into `number_of_classes` difficulty cla
 
 Device work is HIP: ops.noise_blend_fixed, the Unet engine, the fused loss, ops.l1_per_image, ops.image_grid_u8 (the
 `image` / `image_noisy` / `image_prediction` grids of :102-104, written as PNG files: helpers/image_grid_logger.py).
-Differences from the reference, on purpose: the matplotlib histogram figure of validation_epoch_end is not drawn;
-the reference accepts `--output_list` but never writes it (dead option) -- here the classes ARE written, one
-"<relative image path>\\t<class>" line per image, when `output_image_list_path` is set.
+Differences from the reference, on purpose: the matplotlib histogram figure of validation_epoch_end (:151-155) is
+produced only with `device_scoring: true` (below), as a chart without text; the reference accepts `--output_list` but
+never writes it (dead option) -- here the classes ARE written, one "<relative image path>\\t<class>" line per image, when
+`output_image_list_path` is set.
 `device_rng: true` (off by default; optional `rng_seed`): the noise is drawn inside the blend kernel by the counter-based
 generator (rng.py, csrc/philox.h), a function of (seed, global_step or validation batch index, rank).
+`device_scoring: true` (off by default; one process only): the scoring epoch stays on the device.  validation_step writes
+its batch's scores into ONE [len(val dataset)] buffer at the batch's `index` (ops.l1_per_image_scatter; NaN = not scored)
+and neither copies nor waits; validation_epoch_end runs ops.difficulty_classes and ops.difficulty_histogram_u8 on the
+buffer, copies their results out once and logs `difficulty_class_max_count`, the 10 counts of axes.hist as
+`difficulty_class_histogram/bin_<k>` and the chart as <log_dir>/images/difficulty_class_histogram/step_<global_step>.png
+(helpers/image_grid_logger.py).  Where every score is equal (or one image was scored) the classes are 0; the host path
+inherits the reference's NaN -> INT64_MIN there and fails in bincount.
 """
+import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
-from .. import ops, rng
+from .. import distributed, ops, rng
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset
 from ..helpers import ImageLoggingMixin
 from ..lightning import LightningModule
@@ -35,6 +44,11 @@ class LitModule(ImageLoggingMixin, LightningModule):
         self.model = self.create_model_instance()
         self.training_criterion = MseStructuralSimilarityLoss(-1.0, 1.0)
         self.difficulty_index = None  # filled by validation_epoch_end: (image index [N], class [N])
+        if self.hparams.get("device_scoring", False) and distributed.env_world()[0] > 1:
+            raise ValueError("device_scoring: true scores the whole image list in one process: it cannot be combined with "
+                             f"a world size above 1 (WORLD_SIZE={distributed.env_world()[0]}); sharded scoring is not built")
+        self.__dict__["_val_dataset_length"] = None  # recorded by val_dataloader()
+        self.__dict__["_score_buffer"] = None        # device_scoring: [len(val dataset)] f32, NaN = not scored
 
     def create_model_instance(self):
         p = self.hparams
@@ -51,7 +65,9 @@ class LitModule(ImageLoggingMixin, LightningModule):
 
     def val_dataloader(self):
         p = self.hparams
-        return self.create_dataloader(self._data_path(), p.mean, p.std, shuffle=True)  # the reference shuffles here too
+        loader = self.create_dataloader(self._data_path(), p.mean, p.std, shuffle=True)  # the reference shuffles here too
+        self.__dict__["_val_dataset_length"] = len(loader.dataset)
+        return loader
 
     def create_dataloader(self, path, mean, std, shuffle=True):
         p = self.hparams
@@ -97,13 +113,34 @@ class LitModule(ImageLoggingMixin, LightningModule):
         # (device_rng: validation has no optimiser step to count -- the batch index names the draws)
         image_noisy = self.blend_fixed_amount_of_noise_with_each_sample(image, step=batch_idx)
         image_prediction = self.model(image_noisy)
+        if self.hparams.get("device_scoring", False):
+            # no copy, no wait: the scores land in the epoch's buffer at the images' indices
+            image_index = torch.as_tensor(image_index).to(device=image.device, dtype=torch.int64)  # (it is there already)
+            ops.l1_per_image_scatter(image_prediction, image, image_index,
+                                     self.score_buffer(image.device, reset=batch_idx == 0))
+            return {"scored": int(image.shape[0])}
         difficulty_loss = self.compute_difficulty_loss(image_prediction, image)
         return {"index": torch.as_tensor(image_index).cpu(), "loss": difficulty_loss.cpu()}
+
+    def score_buffer(self, device, reset=False):
+        """device_scoring: the [len(val dataset)] score buffer of the current scoring epoch; reset: every entry NaN"""
+        if self._val_dataset_length is None:
+            self.val_dataloader()
+        buffer = self._score_buffer
+        if buffer is None or buffer.numel() != self._val_dataset_length or buffer.device != device:
+            buffer = torch.empty(self._val_dataset_length, dtype=torch.float32, device=device)
+            self.__dict__["_score_buffer"] = buffer
+            reset = True
+        if reset:
+            buffer.fill_(float("nan"))
+        return buffer
 
     def compute_difficulty_loss(self, predicted, target):
         return ops.l1_per_image(predicted, target)
 
     def validation_epoch_end(self, validation_step_output_list):
+        if self.hparams.get("device_scoring", False):
+            return self.device_scoring_epoch_end()
         tensors = self.concat_validation_output(validation_step_output_list)
         image_index, difficulty_loss = tensors["index"], tensors["loss"]
         difficulty_index = self.compute_difficulty_index_for_each_loss(difficulty_loss)
@@ -113,6 +150,43 @@ class LitModule(ImageLoggingMixin, LightningModule):
         out_path = self.hparams.get("output_image_list_path")
         if out_path:
             self.write_output_list(out_path, image_index, difficulty_index)
+        return difficulty_index
+
+    HISTOGRAM_BINS, HISTOGRAM_SIZE = 10, (480, 640)  # matplotlib's defaults: axes.hist(x), plt.subplots(1, 1)
+
+    def device_scoring_epoch_end(self):
+        """the epilogue of a device_scoring epoch: classes, counts, histogram and chart in five launches on the score buffer,
+        ONE copy to the host (all results live in one byte buffer), then the host-side logging"""
+        scores = self._score_buffer
+        if scores is None:
+            raise RuntimeError("device_scoring: validation_epoch_end before any validation_step")
+        N, nc, bins, (H, W) = scores.numel(), int(self.hparams.number_of_classes), self.HISTOGRAM_BINS, self.HISTOGRAM_SIZE
+        layout, total = {}, 0
+        for name, dtype, shape in (("classes", torch.int64, (N,)), ("range", torch.float64, (2,)),
+                                   ("counts", torch.int32, (nc,)), ("bin_counts", torch.int32, (bins,)),
+                                   ("minmax", torch.float32, (2,)), ("chart", torch.uint8, (H, W, 3))):
+            size = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+            layout[name] = (total, size, dtype, shape)
+            total += (size + 15) // 16 * 16
+        packed = torch.empty(total, dtype=torch.uint8, device=scores.device)
+        view = {k: packed[o:o + n].view(dt).view(shape) for k, (o, n, dt, shape) in layout.items()}
+        ops.difficulty_classes(scores, nc, out=(view["classes"], view["counts"], view["minmax"]))
+        ops.difficulty_histogram_u8(view["classes"], bins, (H, W), out=(view["bin_counts"], view["range"], view["chart"]))
+        host = packed.cpu()  # the epoch's one device-to-host copy
+        host = {k: host[o:o + n].view(dt).view(shape) for k, (o, n, dt, shape) in layout.items()}
+        image_index = torch.nonzero(host["classes"] >= 0).reshape(-1)  # the scored images, ascending
+        difficulty_index = host["classes"][image_index].clone()
+        self.difficulty_index = (image_index, difficulty_index)
+        self.log("difficulty_class_max_count", host["counts"].max().float())
+        for k in range(bins):
+            self.log(f"difficulty_class_histogram/bin_{k}", float(host["bin_counts"][k]))
+        out_path = self.hparams.get("output_image_list_path")
+        if out_path:
+            self.write_output_list(out_path, image_index, difficulty_index)
+        logger = self.image_grid_logger()  # rank 0 writes; `sink` / `experiment` as for the image grids
+        if logger.log_dir is not None or logger.sink is not None:  # (a module driven by hand without either: no chart)
+            logger.enqueue(["difficulty_class_histogram"], self.global_step, host["chart"].numpy()[None])
+            logger.drain()
         return difficulty_index
 
     def write_output_list(self, out_path, image_index, difficulty_index):

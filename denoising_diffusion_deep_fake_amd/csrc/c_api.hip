@@ -772,6 +772,28 @@ int d3f_l1_per_image(const float* prediction, const float* target, float* out, v
   D3F_CHECK(prediction && target && out && workspace, "l1_per_image: null argument");
   return l1_per_image_launch(prediction, target, out, workspace, B, (long)per_image, (hipStream_t)stream);
 }
+int d3f_l1_per_image_scatter(const float* prediction, const float* target, const int64_t* index, float* scores, int N,
+                             void* workspace, int B, int64_t per_image, void* stream) {
+  if (B == 0) return 0;
+  D3F_CHECK(prediction && target && index && scores && workspace, "l1_per_image_scatter: null argument");
+  D3F_CHECK(B > 0 && N >= 0 && per_image > 0, "l1_per_image_scatter: bad shape");
+  return l1_per_image_scatter_launch(prediction, target, index, scores, N, workspace, B, (long)per_image,
+                                     (hipStream_t)stream);
+}
+size_t d3f_difficulty_classes_workspace_bytes(int N) { return difficulty_classes_workspace_bytes(N); }
+int d3f_difficulty_classes(const float* scores, int N, int number_of_classes, int64_t* classes, int32_t* counts,
+                           float* minmax, void* workspace, void* stream) {
+  D3F_CHECK(counts && minmax, "difficulty_classes: null argument");
+  D3F_CHECK(N <= 0 || (scores && classes && workspace), "difficulty_classes: null argument");
+  return difficulty_classes_launch(scores, N, number_of_classes, classes, counts, minmax, workspace, (hipStream_t)stream);
+}
+size_t d3f_difficulty_histogram_u8_workspace_bytes(int N) { return difficulty_histogram_workspace_bytes(N); }
+int d3f_difficulty_histogram_u8(const int64_t* classes, int N, int bins, int32_t* bin_counts, double* range, uint8_t* chart,
+                                int H, int W, void* workspace, void* stream) {
+  D3F_CHECK(bin_counts && range && chart && workspace, "difficulty_histogram_u8: null argument");
+  D3F_CHECK(N <= 0 || classes, "difficulty_histogram_u8: null argument");
+  return difficulty_histogram_u8_launch(classes, N, bins, bin_counts, range, chart, H, W, workspace, (hipStream_t)stream);
+}
 size_t d3f_mse_ssim_loss_workspace_bytes(int B, int H, int W) {
   return loss_workspace_floats(B, H, W) * sizeof(float);
 }

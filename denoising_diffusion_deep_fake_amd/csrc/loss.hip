@@ -476,8 +476,7 @@ int noise_draw_launch(uint64_t seed, uint64_t offset, float* noise, float* y, in
 }
 
 // per-image mean absolute error (compute_difficulty_loss, d3f/balance_training_images/lit_module.py:139-142):
-// L1_PARTS partial sums per image, then one thread block per image adds them in a fixed order (f64)
-constexpr int L1_PARTS = 64;
+// L1_PARTS partial sums per image, then one thread block per image adds them in a fixed order (f64; l1_image_mean)
 __global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict__ p, const float* __restrict__ t,
                                                          double* __restrict__ partial, long per_image) {
   __shared__ double red[256];
@@ -498,17 +497,22 @@ __global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict
 __global__ void l1_finalize_kernel(const double* __restrict__ partial, float* __restrict__ out, int B, long per_image) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  double s = 0.0;
-  for (int i = 0; i < L1_PARTS; ++i) s += partial[(long)b * L1_PARTS + i];
-  out[b] = (float)(s / (double)per_image);
+  out[b] = l1_image_mean(partial, b, per_image);
 }
 size_t l1_per_image_workspace_bytes(int B) { return (size_t)B * L1_PARTS * sizeof(double) + 64; }
+// the first stage alone: partial [B][L1_PARTS] (l1_per_image_scatter_launch, difficulty.hip, shares it)
+int l1_partials_launch(const float* pred, const float* target, double* partial, int B, long per_image,
+                       hipStream_t stream) {
+  hipLaunchKernelGGL(l1_partial_kernel, dim3(L1_PARTS, (unsigned)B), dim3(256), 0, stream, pred, target, partial,
+                     per_image);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
 int l1_per_image_launch(const float* pred, const float* target, float* out, void* workspace, int B, long per_image,
                         hipStream_t stream) {
   if (B == 0) return 0;
   double* partial = reinterpret_cast<double*>(workspace);
-  hipLaunchKernelGGL(l1_partial_kernel, dim3(L1_PARTS, (unsigned)B), dim3(256), 0, stream, pred, target, partial,
-                     per_image);
+  if (int rc = l1_partials_launch(pred, target, partial, B, per_image, stream)) return rc;
   hipLaunchKernelGGL(l1_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, partial, out, B, per_image);
   D3F_HIP(hipGetLastError());
   return 0;

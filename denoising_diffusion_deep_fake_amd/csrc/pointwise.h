@@ -199,6 +199,25 @@ int noise_draw_launch(uint64_t seed, uint64_t offset, float* noise, float* y, in
 size_t l1_per_image_workspace_bytes(int B);
 int l1_per_image_launch(const float* pred, const float* target, float* out, void* workspace, int B, long per_image,
                         hipStream_t stream);
+// its two stages, shared with the scattered form (difficulty.hip): L1_PARTS float64 partial sums per image, added in index
+// order and divided once -- ONE expression for both last stages, so that both give the same bits
+constexpr int L1_PARTS = 64;
+int l1_partials_launch(const float* pred, const float* target, double* partial /*[B][L1_PARTS]*/, int B, long per_image,
+                       hipStream_t stream);
+__device__ __forceinline__ float l1_image_mean(const double* __restrict__ partial, int b, long per_image) {
+  double s = 0.0;
+  for (int i = 0; i < L1_PARTS; ++i) s += partial[(long)b * L1_PARTS + i];
+  return (float)(s / (double)per_image);
+}
+// balance_training_images' scoring epoch on the device (difficulty.hip; include/d3f_hip.h states the contracts)
+int l1_per_image_scatter_launch(const float* pred, const float* target, const int64_t* index, float* scores, int N,
+                                void* workspace, int B, long per_image, hipStream_t stream);
+size_t difficulty_classes_workspace_bytes(int N);
+int difficulty_classes_launch(const float* scores, int N, int number_of_classes, int64_t* classes, int32_t* counts,
+                              float* minmax, void* workspace, hipStream_t stream);
+size_t difficulty_histogram_workspace_bytes(int N);
+int difficulty_histogram_u8_launch(const int64_t* classes, int N, int bins, int32_t* bin_counts, double* range,
+                                   uint8_t* chart, int H, int W, void* workspace, hipStream_t stream);
 size_t loss_workspace_floats(int B, int H, int W);
 int mse_ssim_loss_launch(const float* pred, const float* target, float in_min, float in_max,
                          float* loss_out /*[3]: loss, mse, ssim*/, float* grad_pred, float* workspace,

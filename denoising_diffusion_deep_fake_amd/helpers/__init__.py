@@ -1,6 +1,7 @@
 """`d3f.helpers` (d3f/helpers/__init__.py): the image-logging cadence of the three LitModules and the device-side grid
 logger behind their `log_batch_as_image_grid`.  (The reference's convert_pyplot_figure_to_image_tensor serves balance's
-matplotlib histogram, which is not built here.)"""
+matplotlib histogram: with `device_scoring: true` the balance LitModule builds that figure's counts and a chart of them on
+the device, ops.difficulty_histogram_u8, and hands the chart to ImageGridLogger.enqueue -- no pyplot figure is converted.)"""
 from .image_grid_logger import ImageGridLogger, ImageLoggingMixin
 from .logging_scheduler import LoggingScheduler
 

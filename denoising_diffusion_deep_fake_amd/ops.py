@@ -414,6 +414,74 @@ def l1_per_image(pred, target):
     return out
 
 
+def l1_per_image_scatter(pred, target, index, scores):
+    """scores[index[b]] = l1_per_image(pred, target)[b], bit for bit, without leaving the device: index [B] int64 and scores
+    [N] contiguous f32 on the HIP device (a slice of a larger buffer will do).  An index outside [0, N) writes nothing;
+    entries no index names keep their value.  Returns scores.  (include/d3f_hip.h: d3f_l1_per_image_scatter)"""
+    L = _lib.lib()
+    pred, target = pred.contiguous().float(), target.contiguous().float()
+    dev = _dev(pred)
+    B = pred.shape[0]
+    if scores.dtype != torch.float32 or scores.dim() != 1 or scores.device != dev or not scores.is_contiguous():
+        raise ValueError("scores must be a contiguous 1-D float32 tensor on the device of pred")
+    if index.dtype != torch.int64 or index.device != dev or index.numel() != B:
+        raise ValueError(f"index must be an int64 tensor of {B} entries on the device of pred")
+    if B == 0:
+        return scores
+    index = index.reshape(-1).contiguous()
+    ws = torch.empty(L.d3f_l1_per_image_workspace_bytes(B), dtype=torch.uint8, device=dev)
+    check(L.d3f_l1_per_image_scatter(ptr(pred), ptr(target), ptr(index), ptr(scores), scores.numel(), ptr(ws), B,
+                                     pred.numel() // B, stream_ptr()))
+    return scores
+
+
+def _out_or_new(out, shape, dtype, dev, what):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)} on the input's device")
+    return out
+
+
+def difficulty_classes(scores, number_of_classes, out=None):
+    """compute_difficulty_index_for_each_loss of the balance LitModule over a device score buffer [N] f32 in which NaN
+    means "not scored": (classes [N] int64, -1 where not scored; counts [number_of_classes] int32; minmax [2] f32).  The
+    reference's fp32 arithmetic operation for operation, except that max == min gives class 0.  out: the three tensors to
+    write into.  (include/d3f_hip.h: d3f_difficulty_classes)"""
+    L = _lib.lib()
+    dev = _dev(scores)
+    if scores.dtype != torch.float32 or scores.dim() != 1 or not scores.is_contiguous():
+        raise ValueError("scores must be a contiguous 1-D float32 tensor")
+    N, nc = scores.numel(), int(number_of_classes)
+    classes, counts, minmax = out if out is not None else (None, None, None)
+    classes = _out_or_new(classes, (N,), torch.int64, dev, "classes")
+    counts = _out_or_new(counts, (max(nc, 0),), torch.int32, dev, "counts")
+    minmax = _out_or_new(minmax, (2,), torch.float32, dev, "minmax")
+    ws = torch.empty(L.d3f_difficulty_classes_workspace_bytes(N), dtype=torch.uint8, device=dev)
+    check(L.d3f_difficulty_classes(ptr(scores), N, nc, ptr(classes), ptr(counts), ptr(minmax), ptr(ws), stream_ptr()))
+    return classes, counts, minmax
+
+
+def difficulty_histogram_u8(classes, bins=10, size=(480, 640), out=None):
+    """what axes.hist(difficulty_index) of the balance LitModule computes, and a chart of it: classes [N] int64 on the HIP
+    device (entries < 0 passed over) -> (bin_counts [bins] int32 and range [2] f64 as numpy.histogram(x, bins) gives them,
+    chart [H, W, 3] uint8).  bins = 10 and size = (480, 640) are matplotlib's defaults.  out: the three tensors to write
+    into.  (include/d3f_hip.h: d3f_difficulty_histogram_u8)"""
+    L = _lib.lib()
+    dev = _dev(classes)
+    if classes.dtype != torch.int64 or classes.dim() != 1 or not classes.is_contiguous():
+        raise ValueError("classes must be a contiguous 1-D int64 tensor")
+    N, bins, H, W = classes.numel(), int(bins), int(size[0]), int(size[1])
+    bin_counts, rng_, chart = out if out is not None else (None, None, None)
+    bin_counts = _out_or_new(bin_counts, (max(bins, 0),), torch.int32, dev, "bin_counts")
+    rng_ = _out_or_new(rng_, (2,), torch.float64, dev, "range")
+    chart = _out_or_new(chart, (max(H, 0), max(W, 0), 3), torch.uint8, dev, "chart")
+    ws = torch.empty(L.d3f_difficulty_histogram_u8_workspace_bytes(N), dtype=torch.uint8, device=dev)
+    check(L.d3f_difficulty_histogram_u8(ptr(classes), N, bins, ptr(bin_counts), ptr(rng_), ptr(chart), H, W, ptr(ws),
+                                        stream_ptr()))
+    return bin_counts, rng_, chart
+
+
 def mse_ssim_loss(pred, target, in_min=-1.0, in_max=1.0):
     """returns (loss[3] = {loss, mse, ssim} device tensor, grad wrt pred)."""
     L = _lib.lib()

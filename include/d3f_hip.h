@@ -489,6 +489,44 @@ int d3f_noise_draw(uint64_t seed, uint64_t offset, float* noise_or_null, float* 
 size_t d3f_l1_per_image_workspace_bytes(int B);
 int d3f_l1_per_image(const float* prediction, const float* target, float* out, void* workspace, int B,
                      int64_t per_image, void* stream);
+/* The scoring epoch of balance_training_images on the device (csrc/difficulty.hip).
+ *
+ * d3f_l1_per_image_scatter -- compute_difficulty_loss (d3f/balance_training_images/lit_module.py:137-140) written where
+ * validation_step's `index` says (:122-135): scores[index[b]] = d3f_l1_per_image's out[b], bit for bit (the same partial
+ * stage, the same last-stage expression).  index [B] int64 and scores [N] fp32 on the device; an index outside [0, N)
+ * writes nothing; two equal indices in one call leave either value; entries no index names are not touched.  B == 0
+ * launches nothing.  workspace: d3f_l1_per_image_workspace_bytes(B). */
+int d3f_l1_per_image_scatter(const float* prediction, const float* target, const int64_t* index, float* scores, int N,
+                             void* workspace, int B, int64_t per_image, void* stream);
+/* compute_difficulty_index_for_each_loss (d3f/balance_training_images/lit_module.py:181-193) over a score buffer in which
+ * NaN means "not scored": such an entry gets class -1 and takes no part in min, max or the counts.  A scored entry s:
+ *   q = (s - min) / (max - min)      one IEEE fp32 subtraction and one IEEE fp32 division (no reciprocal, no contraction)
+ *   q = min(max(q, 0.f), 0.99999f)   (:189)
+ *   class = (int64)(q * (float)number_of_classes), truncated   (:191)
+ * DIFFERENCE from the reference, on purpose: when max == min (every scored entry equal, or a single one) the reference
+ * divides 0 by 0 and `.long()` of the NaN is INT64_MIN; here every scored entry gets class 0.
+ * classes [N] int64; counts [number_of_classes] int32 = scored entries per class (integer adds: independent of the launch
+ * geometry); minmax [2] fp32 = {min, max}, NaN twice when nothing was scored.  number_of_classes 1..65536.  N == 0: no
+ * kernel, counts zeroed, minmax NaN.  workspace: d3f_difficulty_classes_workspace_bytes(N). */
+size_t d3f_difficulty_classes_workspace_bytes(int N);
+int d3f_difficulty_classes(const float* scores, int N, int number_of_classes, int64_t* classes, int32_t* counts,
+                           float* minmax, void* workspace, void* stream);
+/* The figure validation_epoch_end logs as `difficulty_class_histogram` (d3f/balance_training_images/lit_module.py:151-155:
+ * axes.hist(difficulty_index), matplotlib's default of 10 bins): the counts and a chart of them, without a host round trip
+ * in between.  classes [N] int64 on the device; entries < 0 are passed over.
+ * Counts: numpy.histogram(x, bins) over the entries >= 0.  lo, hi = min, max (0, 1 without data); lo == hi: lo -= 0.5,
+ * hi += 0.5; edges e_k = k * ((hi - lo) / bins) + lo in float64, e_bins = hi; an entry counts for the k with
+ * e_k <= v < e_(k+1), the last bin closed.  bin_counts [bins] int32, range [2] float64 = {lo, hi}.
+ * Chart: uint8 [H][W][3], integer geometry (every division truncates): background 255; box x0 = W/8, x1 = W - W/10,
+ * y0 = H*3/25, y1 = H - H*11/100; frame colour 0 on rows y0 and y1-1 over [x0, x1) and columns x0 and x1-1 over [y0, y1);
+ * interior xi0 = x0+1, xi1 = x1-1, yi0 = y0+1, yi1 = y1-1, IW = xi1-xi0, IH = yi1-yi0; bar i covers the columns
+ * [xi0 + i*IW/bins, xi0 + (i+1)*IW/bins) and the rows [yi1 - h_i, yi1), h_i = counts[i]*IH*20 / (cmax*21) in 64-bit
+ * integers (0 when the largest count cmax is 0; the tallest bar ends at 1/1.05 of the box like matplotlib's y margin),
+ * colour (31, 119, 180).  No text, no ticks.  Refused before any device call: bins < 1, bins > IW, H or W outside
+ * 32..16384, null pointers.  workspace: d3f_difficulty_histogram_u8_workspace_bytes(N). */
+size_t d3f_difficulty_histogram_u8_workspace_bytes(int N);
+int d3f_difficulty_histogram_u8(const int64_t* classes, int N, int bins, int32_t* bin_counts, double* range, uint8_t* chart,
+                                int H, int W, void* workspace, void* stream);
 /* MseStructuralSimilarityLoss(input_min, input_max)(prediction, target)
  * (d3f/loss_functions/structural_similarity_loss.py:14-26; piqa.SSIM defaults) on NCHW f32
  * [B][3][H][W]: loss_out = {loss, mse, ssim}; grad_pred = d loss / d prediction. */
