@@ -148,6 +148,8 @@ PROTOTYPES = {
     "d3f_noise_draw": (_i, [_u64, _u64, _p, _p, _i, _i64, _p]),
     "d3f_affine_warp_rng": (_i, [_p, _p, _u64, _u64, _i, C.POINTER(_f), _i, _i, _i, _i, _p]),
     "d3f_affine_theta_draw": (_i, [_u64, _u64, _i, C.POINTER(_f), _p, _p, _i, _i, _i, _p]),
+    "d3f_pool_batch": (_i, [_p, _i64, _p, _p, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _p, _p, _p]),
+    "d3f_pool_batch_rng": (_i, [_p, _i64, _p, _p, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _u64, _u64, _i, C.POINTER(_f), _p]),
 }
 
 # d3f_allreduce_fn: int (*)(void* ctx, float* data, int64_t count, void* stream)

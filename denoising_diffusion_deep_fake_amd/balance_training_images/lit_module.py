@@ -22,12 +22,17 @@ buffer, copies their results out once and logs `difficulty_class_max_count`, the
 `difficulty_class_histogram/bin_<k>` and the chart as <log_dir>/images/difficulty_class_histogram/step_<global_step>.png
 (helpers/image_grid_logger.py).  Where every score is equal (or one image was scored) the classes are 0; the host path
 inherits the reference's NaN -> INT64_MIN there and fails in bincount.
+`device_dataset: true` (off by default; optional `device_dataset_max_fraction`; not with `synthetic`): the image list is
+decoded once into a uint8 pool on the device (dataset/device_pool.py) that the training and the scoring loader share; both
+yield indices and `step_images` gathers and normalises a batch in one launch -- the host transform's values, bit for bit.
 """
 import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
 from .. import distributed, ops, rng
+from ..dataset import device_pool
+from ..dataset.device_pool import DeviceImagePool
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset
 from ..helpers import ImageLoggingMixin
 from ..lightning import LightningModule
@@ -40,6 +45,8 @@ class LitModule(ImageLoggingMixin, LightningModule):
     def __init__(self, **kwargs):
         super().__init__()
         self.save_hyperparameters()
+        device_pool.check_hparams(self.hparams, self._data_path())
+        self.__dict__["_pool"] = None  # device_dataset: the DeviceImagePool both loaders draw from
         self.setup_image_logging()  # image_logging_scheduler; None unless `image_logging: true`
         self.model = self.create_model_instance()
         self.training_criterion = MseStructuralSimilarityLoss(-1.0, 1.0)
@@ -69,13 +76,20 @@ class LitModule(ImageLoggingMixin, LightningModule):
         self.__dict__["_val_dataset_length"] = len(loader.dataset)
         return loader
 
+    def mean_std_unit(self, mean, std):
+        """config means / stds in 0..255 units -> [0, 1] units"""
+        return [v / 255.0 if max(mean) > 1 else v for v in mean], [v / 255.0 if max(std) > 1 else v for v in std]
+
     def create_dataloader(self, path, mean, std, shuffle=True):
         p = self.hparams
+        if device_pool.check_hparams(p, path):  # the list decoded once into device memory, batches of indices
+            if self._pool is None:
+                self.__dict__["_pool"] = DeviceImagePool.from_hparams(p, path, self.device)
+            return self._pool.loader(p.batch_size, shuffle=shuffle, pin_memory=False)
         if p.get("synthetic", False) or path is None:
             dataset = SyntheticFaceDataset(p.get("synthetic_length", 4 * p.batch_size), p.get("image_size", 256))
         else:
-            m = [v / 255.0 if max(mean) > 1 else v for v in mean]
-            s = [v / 255.0 if max(std) > 1 else v for v in std]
+            m, s = self.mean_std_unit(mean, std)
             dataset = ImageDataset(path, transform=NormalizeToTensor(m, s))
         workers = p.get("num_workers", 0)
         extra = dict(multiprocessing_context="spawn", persistent_workers=True) if workers > 0 else {}  # never fork after HIP init
@@ -85,9 +99,18 @@ class LitModule(ImageLoggingMixin, LightningModule):
         p = self.hparams
         return FusedAdam(self.model.parameters(), lr=p.learning_rate, module=self.model)
 
+    @torch.no_grad()
+    def step_images(self, batch):
+        """a loader's batch -> the normalised float batch.  A `device_dataset` batch carries `index` only: gather from the
+        pool and normalise in one launch."""
+        if "image" in batch:
+            return batch["image"]
+        p = self.hparams
+        return self._pool.batch(batch["index"], *self.mean_std_unit(p.mean, p.std))
+
     def training_step(self, batch, batch_idx):
         self.update_image_logging_schedule()
-        image = batch["image"]
+        image = self.step_images(batch)
         image_noisy = self.blend_fixed_amount_of_noise_with_each_sample(image)
         image_prediction = self.model(image_noisy)
         loss = self.training_criterion(image_prediction, image)
@@ -108,7 +131,7 @@ class LitModule(ImageLoggingMixin, LightningModule):
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx):
-        image = batch["image"]
+        image = self.step_images(batch)
         image_index = batch["index"]
         # (device_rng: validation has no optimiser step to count -- the batch index names the draws)
         image_noisy = self.blend_fixed_amount_of_noise_with_each_sample(image, step=batch_idx)

@@ -716,6 +716,40 @@ int d3f_affine_theta_draw(uint64_t seed, uint64_t offset, int kind, const float 
   return affine_theta_draw_launch(seed, offset, q, theta, apply, B, (hipStream_t)stream);
 }
 
+// the argument checks both device-dataset entries share; `who` names the entry in the message (B == 0: an empty batch has
+// no index and no output to point at)
+static int pool_batch_check(const char* who, const uint8_t* pool, int64_t N, const int64_t* index, const float* out, int B,
+                            int H, int W, const float mean[3], const float std[3]) {
+  D3F_CHECK(pool != nullptr, "%s: pool is null", who);
+  D3F_CHECK(index != nullptr || B == 0, "%s: index is null", who);
+  D3F_CHECK(out != nullptr || B == 0, "%s: out is null", who);
+  D3F_CHECK(mean != nullptr, "%s: mean is null", who);
+  D3F_CHECK(std != nullptr, "%s: std is null", who);
+  D3F_CHECK(N >= 1, "%s: N %lld < 1", who, (long long)N);
+  D3F_CHECK(B >= 0, "%s: B %d < 0", who, B);
+  D3F_CHECK(H >= 1 && W >= 1, "%s: H %d, W %d below 1", who, H, W);
+  D3F_CHECK(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "%s: zero std", who);
+  D3F_CHECK((long)H * W * 3 < (1L << 31), "%s: an image of %ld bytes (H x W x 3 must stay below 2^31)", who,
+            (long)H * W * 3);
+  return 0;
+}
+int d3f_pool_batch(const uint8_t* pool, int64_t N, const int64_t* index, float* out, int B, int H, int W,
+                   const float mean[3], const float std[3], const float* theta, const uint8_t* apply, void* stream) {
+  if (int rc = pool_batch_check("pool_batch", pool, N, index, out, B, H, W, mean, std)) return rc;
+  D3F_CHECK(theta != nullptr || apply == nullptr, "pool_batch: apply without theta");
+  return pool_batch_launch(pool, N, index, out, B, H, W, mean, std, theta, apply, 0, 0, nullptr, (hipStream_t)stream);
+}
+int d3f_pool_batch_rng(const uint8_t* pool, int64_t N, const int64_t* index, float* out, int B, int H, int W,
+                       const float mean[3], const float std[3], uint64_t seed, uint64_t offset, int kind,
+                       const float params[5], void* stream) {
+  if (int rc = pool_batch_check("pool_batch_rng", pool, N, index, out, B, H, W, mean, std)) return rc;
+  D3F_CHECK(params != nullptr, "pool_batch_rng: params is null");
+  AffineRngParams q;
+  if (int rc = affine_rng_params(kind, params, H, W, q)) return rc;
+  return pool_batch_launch(pool, N, index, out, B, H, W, mean, std, nullptr, nullptr, seed, offset, &q,
+                           (hipStream_t)stream);
+}
+
 int d3f_nchw_to_nhwc(int dtype, const float* in, void* out, int B, int C, int H, int W, int Cpad, void* stream) {
   D3F_CHECK(in && out && Cpad >= C, "nchw_to_nhwc: argument");
   return nchw_to_nhwc_launch(sdt(dtype), in, out, B, C, H, W, Cpad, (hipStream_t)stream);

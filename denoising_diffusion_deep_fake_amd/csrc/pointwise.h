@@ -3,6 +3,7 @@
 #include <string>
 
 #include "common.h"
+#include "philox.h"
 
 namespace d3f {
 
@@ -133,10 +134,55 @@ int image_grid_u8_launch(const float* const* batches, int n, int B, int C, int H
 // input pipeline: uint8 RGB [B][H][W][3] -> NCHW fp32, ((float)u8 / 255 - mean[c]) / std[c]
 int u8rgb_to_nchw_launch(const uint8_t* in, float* out, int B, long HW, const float mean[3], const float stdv[3],
                          hipStream_t stream);
+// that expression -- the order of fp32 operations of albumentations.Normalize(max_pixel_value=255): ONE definition for
+// u8rgb_to_nchw_kernel and for the device dataset's kernel (dataset.hip), so that both give the same bits
+struct U8Normalise {
+  float m0, m1, m2, s0, s1, s2;
+  __device__ __forceinline__ float operator()(uint8_t v, int c) const {
+    return ((float)v / 255.0f - (c == 0 ? m0 : c == 1 ? m1 : m2)) / (c == 0 ? s0 : c == 1 ? s1 : s2);
+  }
+};
 
 // K17: affine_grid + grid_sample(bilinear, zeros, align_corners=False) on NCHW fp32, theta [B][2][3]
 int affine_warp_launch(const float* in, const float* theta, float* out, int B, int C, int H, int W,
                        hipStream_t stream);
+// The texel sources of the sampling: texel (channel c, offset y * W + x) of ONE image, either fp32 channel planes HW apart
+// or a uint8 HWC image of the device dataset's pool normalised on the fly (32-bit offsets: an image is below 2^31 bytes).
+struct PlaneTexels {
+  const float* __restrict__ img;
+  long HW;
+  __device__ __forceinline__ float operator()(int c, long off) const { return img[(long)c * HW + off]; }
+};
+struct PoolTexels {
+  const uint8_t* __restrict__ img;
+  U8Normalise norm;
+  __device__ __forceinline__ float operator()(int c, long off) const { return norm(img[(int)off * 3 + c], c); }
+};
+// one output pixel of an image, every channel: the sampling every warp kernel shares (affine_warp_kernel,
+// affine_warp_rng_kernel, pool_batch_kernel).  theta t[6] maps normalised output coordinates to normalised input
+// coordinates; a tap outside the frame is 0; dst_image: the image's C output planes.
+template <class Texels>
+__device__ __forceinline__ void affine_warp_pixel(const Texels& src, float* __restrict__ dst_image, const float* t, int pix,
+                                                  int C, int H, int W) {
+  const long HW = (long)H * W;
+  const int y = pix / W, x = pix - y * W;
+  const float xn = (2.0f * x + 1.0f) / W - 1.0f, yn = (2.0f * y + 1.0f) / H - 1.0f;
+  const float xs = t[0] * xn + t[1] * yn + t[2], ys = t[3] * xn + t[4] * yn + t[5];
+  const float fx = ((xs + 1.0f) * W - 1.0f) * 0.5f, fy = ((ys + 1.0f) * H - 1.0f) * 0.5f;
+  const float x0f = floorf(fx), y0f = floorf(fy);
+  const int x0 = (int)x0f, y0 = (int)y0f;
+  const float wx1 = fx - x0f, wy1 = fy - y0f, wx0 = 1.0f - wx1, wy0 = 1.0f - wy1;
+  const bool vx0 = (unsigned)x0 < (unsigned)W, vx1 = (unsigned)(x0 + 1) < (unsigned)W;
+  const bool vy0 = (unsigned)y0 < (unsigned)H, vy1 = (unsigned)(y0 + 1) < (unsigned)H;
+  float* dst = dst_image + pix;
+  for (int c = 0; c < C; ++c) {
+    const float v00 = (vx0 && vy0) ? src(c, (long)y0 * W + x0) : 0.f;
+    const float v01 = (vx1 && vy0) ? src(c, (long)y0 * W + x0 + 1) : 0.f;
+    const float v10 = (vx0 && vy1) ? src(c, (long)(y0 + 1) * W + x0) : 0.f;
+    const float v11 = (vx1 && vy1) ? src(c, (long)(y0 + 1) * W + x0 + 1) : 0.f;
+    dst[(long)c * HW] = v00 * (wx0 * wy0) + v01 * (wx1 * wy0) + v10 * (wx0 * wy1) + v11 * (wx1 * wy1);
+  }
+}
 // K17 with theta drawn inside (philox.h): the ranges of RandomAffine (kind 0) / ShiftScaleRotate (kind 1) as the kernels
 // take them -- python-side double constants rounded to fp32 once, like a python scalar meeting a float tensor
 struct AffineRngParams {
@@ -153,6 +199,51 @@ int affine_warp_rng_launch(const float* in, float* out, uint64_t seed, uint64_t 
                            int C, int H, int W, hipStream_t stream);
 int affine_theta_draw_launch(uint64_t seed, uint64_t offset, const AffineRngParams& q, float* theta, uint8_t* apply, int B,
                              hipStream_t stream);
+// the draws + theta of K17 (philox.h: the draw layout), shared by affine_warp_rng_kernel, affine_theta_draw_kernel and
+// pool_batch_kernel.
+// The python draws + theta of RandomAffine.forward (d3f/train_denoiser/lit_module.py:55-65) and of ShiftScaleRotate
+// (d3f/train_deep_fake/lit_module.py:99-111) -- two to three dozen tiny launches per step -- as arithmetic on five
+// uniforms per image: u0..u3 = block 0xFFFFFFFE of image b, u4 = word 0 of block 0xFFFFFFFD.
+//   kind 0, RandomAffine:     ang = (2 u0 - 1) radians(degrees), sc = u1 (scale_hi - scale_lo) + scale_lo,
+//                             tx = (2 u2 - 1) translate_x 2, ty = (2 u3 - 1) translate_y 2, always applied;
+//                             theta = [[cos/sc, -sin/sc, tx], [sin/sc, cos/sc, ty]]
+//   kind 1, ShiftScaleRotate: angle = (2 u0 - 1) rotate_limit, scale = 1 + (2 u1 - 1) scale_limit, dx = (2 u2 - 1) shift_limit,
+//                             dy = (2 u3 - 1) shift_limit, apply = u4 < p; theta as ShiftScaleRotate.theta
+// Returns whether the image is warped; the python expressions' order of fp32 operations (no contraction).
+__device__ __forceinline__ bool affine_theta_rng(uint64_t seed, uint64_t offset, int b, const AffineRngParams& q,
+                                                 float t[6]) {
+  const Philox4 p = rng_block(seed, offset, (uint32_t)b, RNG_G_AUG);
+  const float s0 = rng_uniform24(p.x[0]) * 2.0f - 1.0f, u1 = rng_uniform24(p.x[1]);
+  const float s2 = rng_uniform24(p.x[2]) * 2.0f - 1.0f, s3 = rng_uniform24(p.x[3]) * 2.0f - 1.0f;
+  float sn, cs;
+  if (q.kind == 0) {
+    const float sc = u1 * q.scale_span + q.scale_lo;
+    sincosf(s0 * q.angle_unit, &sn, &cs);
+    cs = cs / sc;
+    sn = sn / sc;
+    t[0] = cs, t[1] = -sn, t[2] = s2 * q.shift_x * 2.0f;
+    t[3] = sn, t[4] = cs, t[5] = s3 * q.shift_y * 2.0f;
+    return true;
+  }
+  const float angle = s0 * q.angle_unit, scale = 1.0f + (u1 * 2.0f - 1.0f) * q.scale_span;
+  const float dx = s2 * q.shift_x, dy = s3 * q.shift_y;
+  sincosf(angle * q.deg2rad, &sn, &cs);
+  cs = cs / scale;
+  sn = sn / scale;
+  const float a11 = cs, a12 = -sn * q.h_over_w, a21 = sn * q.w_over_h, a22 = cs;
+  t[0] = a11, t[1] = a12, t[2] = -2.0f * (a11 * dx + a12 * dy);
+  t[3] = a21, t[4] = a22, t[5] = -2.0f * (a21 * dx + a22 * dy);
+  return rng_uniform24(rng_block(seed, offset, (uint32_t)b, RNG_G_APPLY).x[0]) < q.p;
+}
+
+// Device dataset (dataset.hip): a training batch out [B][3][H][W] f32 assembled from a resident pool [N][H][W][3] uint8
+// RGB in one launch -- gather by index [B] (int64, device), the normalisation of u8rgb_to_nchw_launch, then nothing
+// (theta == apply == nullptr, q == nullptr), the sampling of affine_warp_launch with theta [B][2][3] where apply [B] is set
+// (apply == nullptr: everywhere), or what affine_warp_rng_launch does (q != nullptr).  An index outside [0, N): the image
+// is all NaN and nothing is read for it.
+int pool_batch_launch(const uint8_t* pool, int64_t N, const int64_t* index, float* out, int B, int H, int W,
+                      const float mean[3], const float stdv[3], const float* theta, const uint8_t* apply, uint64_t seed,
+                      uint64_t offset, const AffineRngParams* q, hipStream_t stream);
 
 // ---- weights -------------------------------------------------------------------------------
 // conv(cat(upsample2x(x), skip)) with the up-sampling folded into pre-summed weights (pointwise.hip): per-class

@@ -297,53 +297,29 @@ __global__ __launch_bounds__(256) void nchw_to_u8bgr_kernel(const float* __restr
 // ToTensorV2 (d3f/train_deep_fake/lit_module.py:100-110) -- bit-identical to the host transform, but the batch crosses
 // worker IPC and PCIe as 1 byte per value instead of 4.
 __global__ __launch_bounds__(256) void u8rgb_to_nchw_kernel(const uint8_t* __restrict__ in, float* __restrict__ out,
-                                                            int B, long HW, float m0, float m1, float m2, float s0,
-                                                            float s1, float s2) {
+                                                            int B, long HW, U8Normalise norm) {
   const long total = (long)B * HW;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long b = i / HW, pix = i - b * HW;
     const uint8_t* px = in + i * 3;
     float* o = out + b * 3 * HW + pix;
-    o[0] = ((float)px[0] / 255.0f - m0) / s0;
-    o[HW] = ((float)px[1] / 255.0f - m1) / s1;
-    o[2 * HW] = ((float)px[2] / 255.0f - m2) / s2;
+    o[0] = norm(px[0], 0);
+    o[HW] = norm(px[1], 1);
+    o[2 * HW] = norm(px[2], 2);
   }
 }
 
 // K17: batched affine warp of NCHW fp32 images -- affine_grid + grid_sample(bilinear, zeros, align_corners=False)
 // in one pass (the GPU-side augmentation of train_denoiser, d3f/train_denoiser/lit_module.py:55-65,113).
 // theta [B][2][3] maps normalised output coordinates to normalised input coordinates.
-// one output pixel of image b, every channel: the sampling both warp kernels share
-__device__ __forceinline__ void affine_warp_pixel(const float* __restrict__ in, float* __restrict__ out,
-                                                  const float* t, int b, int pix, int C, int H, int W) {
-  const long HW = (long)H * W;
-  const int y = pix / W, x = pix - y * W;
-  const float xn = (2.0f * x + 1.0f) / W - 1.0f, yn = (2.0f * y + 1.0f) / H - 1.0f;
-  const float xs = t[0] * xn + t[1] * yn + t[2], ys = t[3] * xn + t[4] * yn + t[5];
-  const float fx = ((xs + 1.0f) * W - 1.0f) * 0.5f, fy = ((ys + 1.0f) * H - 1.0f) * 0.5f;
-  const float x0f = floorf(fx), y0f = floorf(fy);
-  const int x0 = (int)x0f, y0 = (int)y0f;
-  const float wx1 = fx - x0f, wy1 = fy - y0f, wx0 = 1.0f - wx1, wy0 = 1.0f - wy1;
-  const bool vx0 = (unsigned)x0 < (unsigned)W, vx1 = (unsigned)(x0 + 1) < (unsigned)W;
-  const bool vy0 = (unsigned)y0 < (unsigned)H, vy1 = (unsigned)(y0 + 1) < (unsigned)H;
-  const float* src = in + (long)b * C * HW;
-  float* dst = out + (long)b * C * HW + pix;
-  for (int c = 0; c < C; ++c) {
-    const float* pl = src + (long)c * HW;
-    const float v00 = (vx0 && vy0) ? pl[(long)y0 * W + x0] : 0.f;
-    const float v01 = (vx1 && vy0) ? pl[(long)y0 * W + x0 + 1] : 0.f;
-    const float v10 = (vx0 && vy1) ? pl[(long)(y0 + 1) * W + x0] : 0.f;
-    const float v11 = (vx1 && vy1) ? pl[(long)(y0 + 1) * W + x0 + 1] : 0.f;
-    dst[(long)c * HW] = v00 * (wx0 * wy0) + v01 * (wx1 * wy0) + v10 * (wx0 * wy1) + v11 * (wx1 * wy1);
-  }
-}
-
+// (the sampling: affine_warp_pixel, pointwise.h)
 __global__ __launch_bounds__(256) void affine_warp_kernel(const float* __restrict__ in, const float* __restrict__ theta,
                                                           float* __restrict__ out, int B, int C, int H, int W) {
   const long HW = (long)H * W, total = (long)B * HW;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int b = (int)(i / HW);
-    affine_warp_pixel(in, out, theta + b * 6, b, (int)(i - (long)b * HW), C, H, W);
+    affine_warp_pixel(PlaneTexels{in + (long)b * C * HW, HW}, out + (long)b * C * HW, theta + b * 6,
+                      (int)(i - (long)b * HW), C, H, W);
   }
 }
 
@@ -357,42 +333,7 @@ int affine_warp_launch(const float* in, const float* theta, float* out, int B, i
   return 0;
 }
 
-// ---- K17 with its parameters drawn inside (philox.h: the draw layout) -------------------------------------------------
-// The python draws + theta of RandomAffine.forward (d3f/train_denoiser/lit_module.py:55-65) and of ShiftScaleRotate
-// (d3f/train_deep_fake/lit_module.py:99-111) -- two to three dozen tiny launches per step -- as arithmetic on five
-// uniforms per image: u0..u3 = block 0xFFFFFFFE of image b, u4 = word 0 of block 0xFFFFFFFD.
-//   kind 0, RandomAffine:     ang = (2 u0 - 1) radians(degrees), sc = u1 (scale_hi - scale_lo) + scale_lo,
-//                             tx = (2 u2 - 1) translate_x 2, ty = (2 u3 - 1) translate_y 2, always applied;
-//                             theta = [[cos/sc, -sin/sc, tx], [sin/sc, cos/sc, ty]]
-//   kind 1, ShiftScaleRotate: angle = (2 u0 - 1) rotate_limit, scale = 1 + (2 u1 - 1) scale_limit, dx = (2 u2 - 1) shift_limit,
-//                             dy = (2 u3 - 1) shift_limit, apply = u4 < p; theta as ShiftScaleRotate.theta
-// Returns whether the image is warped; the python expressions' order of fp32 operations (no contraction).
-__device__ __forceinline__ bool affine_theta_rng(uint64_t seed, uint64_t offset, int b, const AffineRngParams& q,
-                                                 float t[6]) {
-  const Philox4 p = rng_block(seed, offset, (uint32_t)b, RNG_G_AUG);
-  const float s0 = rng_uniform24(p.x[0]) * 2.0f - 1.0f, u1 = rng_uniform24(p.x[1]);
-  const float s2 = rng_uniform24(p.x[2]) * 2.0f - 1.0f, s3 = rng_uniform24(p.x[3]) * 2.0f - 1.0f;
-  float sn, cs;
-  if (q.kind == 0) {
-    const float sc = u1 * q.scale_span + q.scale_lo;
-    sincosf(s0 * q.angle_unit, &sn, &cs);
-    cs = cs / sc;
-    sn = sn / sc;
-    t[0] = cs, t[1] = -sn, t[2] = s2 * q.shift_x * 2.0f;
-    t[3] = sn, t[4] = cs, t[5] = s3 * q.shift_y * 2.0f;
-    return true;
-  }
-  const float angle = s0 * q.angle_unit, scale = 1.0f + (u1 * 2.0f - 1.0f) * q.scale_span;
-  const float dx = s2 * q.shift_x, dy = s3 * q.shift_y;
-  sincosf(angle * q.deg2rad, &sn, &cs);
-  cs = cs / scale;
-  sn = sn / scale;
-  const float a11 = cs, a12 = -sn * q.h_over_w, a21 = sn * q.w_over_h, a22 = cs;
-  t[0] = a11, t[1] = a12, t[2] = -2.0f * (a11 * dx + a12 * dy);
-  t[3] = a21, t[4] = a22, t[5] = -2.0f * (a21 * dx + a22 * dy);
-  return rng_uniform24(rng_block(seed, offset, (uint32_t)b, RNG_G_APPLY).x[0]) < q.p;
-}
-
+// ---- K17 with its parameters drawn inside (affine_theta_rng, pointwise.h) ---------------------------------------------
 // one image per blockIdx.y; thread 0 draws the image's theta, the workgroup samples with it (or copies the image)
 __global__ __launch_bounds__(256) void affine_warp_rng_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                               uint64_t seed, uint64_t offset, AffineRngParams q, int C,
@@ -410,8 +351,9 @@ __global__ __launch_bounds__(256) void affine_warp_rng_kernel(const float* __res
   if (warped) {
     float t[6];
     for (int k = 0; k < 6; ++k) t[k] = th[k];
+    const PlaneTexels src{in + (long)b * C * HW, HW};
     for (long pix = (long)blockIdx.x * 256 + threadIdx.x; pix < HW; pix += (long)gridDim.x * 256)
-      affine_warp_pixel(in, out, t, b, (int)pix, C, H, W);
+      affine_warp_pixel(src, out + (long)b * C * HW, t, (int)pix, C, H, W);
   } else {
     const long n = (long)C * HW;
     const float* __restrict__ src = in + (long)b * n;
@@ -495,8 +437,8 @@ int u8bgr_to_nhwc_launch(int dtype, const uint8_t* in, void* out, long npix, int
 int u8rgb_to_nchw_launch(const uint8_t* in, float* out, int B, long HW, const float mean[3], const float stdv[3],
                          hipStream_t stream) {
   if ((long)B * HW == 0) return 0;
-  hipLaunchKernelGGL(u8rgb_to_nchw_kernel, dim3(grid_for((long)B * HW)), dim3(256), 0, stream, in, out, B, HW, mean[0],
-                     mean[1], mean[2], stdv[0], stdv[1], stdv[2]);
+  hipLaunchKernelGGL(u8rgb_to_nchw_kernel, dim3(grid_for((long)B * HW)), dim3(256), 0, stream, in, out, B, HW,
+                     U8Normalise{mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2]});
   D3F_HIP(hipGetLastError());
   return 0;
 }

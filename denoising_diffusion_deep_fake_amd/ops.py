@@ -334,6 +334,55 @@ def u8rgb_normalise(frames, mean, std):
     return out
 
 
+def _pool_batch_args(pool, index, mean, std):
+    if pool.dtype != torch.uint8 or pool.dim() != 4 or pool.shape[-1] != 3 or not pool.is_contiguous():
+        raise ValueError("pool_batch expects a contiguous uint8 pool [N, H, W, 3] (RGB)")
+    dev = _dev(pool)
+    if index.dtype != torch.int64 or index.dim() != 1 or index.device != dev:
+        raise ValueError("pool_batch expects an int64 index [B] on the pool's device")
+    N, H, W, _ = pool.shape
+    out = torch.empty((index.shape[0], 3, H, W), dtype=torch.float32, device=dev)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    return index.contiguous(), out, m, s
+
+
+def pool_batch(pool, index, mean, std, theta=None, apply=None):
+    """a training batch from a device-resident pool [N, H, W, 3] uint8 in one launch (d3f_pool_batch): gather by index [B]
+    (int64, on the device), u8rgb_normalise, and with theta [B, 2, 3] affine_warp of the images whose apply [B] (bool /
+    uint8; None: all) is set -- bit for bit torch.where(apply, affine_warp(x, theta), x) of x = u8rgb_normalise(pool[index]).
+    An index outside [0, N) gives an all-NaN image."""
+    index, out, m, s = _pool_batch_args(pool, index, mean, std)
+    N, H, W, _ = pool.shape
+    B = index.shape[0]
+    if theta is not None:
+        theta = theta.to(device=pool.device, dtype=torch.float32).contiguous()
+        if theta.shape != (B, 2, 3):
+            raise ValueError(f"theta must be [{B}, 2, 3], got {list(theta.shape)}")
+    if apply is not None:
+        if theta is None:
+            raise ValueError("pool_batch: apply without theta")
+        if apply.dtype == torch.bool:
+            apply = apply.view(torch.uint8) if apply.is_contiguous() else apply.to(torch.uint8)
+        apply = apply.to(device=pool.device, dtype=torch.uint8).contiguous()
+        if apply.shape != (B,):
+            raise ValueError(f"apply must be [{B}], got {list(apply.shape)}")
+    check(_lib.lib().d3f_pool_batch(ptr(pool), N, ptr(index), ptr(out), B, H, W, m, s, ptr(theta), ptr(apply),
+                                    stream_ptr()))
+    return out
+
+
+def pool_batch_rng(pool, index, mean, std, seed, offset, kind, params):
+    """pool_batch with the augmentation of affine_warp_rng (same kinds, params and draws) instead of a given theta
+    (d3f_pool_batch_rng): bit for bit affine_warp_rng(u8rgb_normalise(pool[index]), seed, offset, kind, params)"""
+    index, out, m, s = _pool_batch_args(pool, index, mean, std)
+    N, H, W, _ = pool.shape
+    kind, cparams = _affine_rng_params(kind, params)
+    check(_lib.lib().d3f_pool_batch_rng(ptr(pool), N, ptr(index), ptr(out), index.shape[0], H, W, m, s, int(seed),
+                                        int(offset), kind, cparams, stream_ptr()))
+    return out
+
+
 def noise_blend(x, noise, y_uniform, lam, return_r=False):
     x = x.contiguous().float()
     out = torch.empty_like(x)

@@ -20,6 +20,10 @@ generator inside the kernels that consume them (rng.py, csrc/philox.h) -- a func
 stream 0 for a, 1 for b), so the fused two-network step equals the sequential loop whatever the order of the draws and a
 resumed run continues the interrupted one.
 
+`device_dataset: true` (off by default; optional `device_dataset_max_fraction`; not with `synthetic`): each domain's image
+list is decoded once into a uint8 pool on the device (dataset/device_pool.py), the loaders yield indices and `domain_images`
+gathers, normalises and augments a domain's batch in one launch -- the values of the `uint8_batches` path, bit for bit.
+
 Reference quirks kept on purpose: the dataloaders receive `mean_x` as BOTH
 mean and std (lit_module.py:75-76); `predict_fake("a")` uses model_a with B's mean/std (:253-257);
 de-normalisation truncates with `.int()` BEFORE clamping (:293-294).
@@ -35,6 +39,8 @@ import torch.optim.lr_scheduler as schedulers
 from torch.utils.data import DataLoader
 
 from .. import ops, rng
+from ..dataset import device_pool
+from ..dataset.device_pool import DeviceImagePool
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset, ToUint8Tensor
 from ..helpers import ImageLoggingMixin
 from ..lightning import LightningModule
@@ -71,21 +77,33 @@ class ShiftScaleRotate(nn.Module):
         return {"apply": torch.rand(B, device=device) < self.p, "angle": u(self.rotate_limit),
                 "scale": 1.0 + u(self.scale_limit), "dx": u(self.shift_limit), "dy": u(self.shift_limit)}
 
+    KIND = "shift_scale_rotate"
+
+    def rng_params(self):
+        """the `params` of ops.affine_warp_rng / ops.pool_batch_rng"""
+        return (self.shift_limit, self.scale_limit, self.rotate_limit, self.p)
+
+    @torch.no_grad()
+    def draw_theta(self, B, height, width, device, draws=None):
+        """the torch draws of one batch, in their order -> (theta [B, 2, 3], apply [B] bool)"""
+        d = self.draw(B, device) if draws is None else draws
+        return self.theta(d["angle"], d["scale"], d["dx"], d["dy"], height, width), d["apply"]
+
     @torch.no_grad()
     def forward(self, x, draws=None, seed_offset=None):
         if seed_offset is not None:  # device_rng: (seed, offset) -- draws, theta, warp and pass-through in one kernel
-            return ops.affine_warp_rng(x, seed_offset[0], seed_offset[1], "shift_scale_rotate",
-                                       (self.shift_limit, self.scale_limit, self.rotate_limit, self.p))
-        d = self.draw(x.shape[0], x.device) if draws is None else draws
-        th = self.theta(d["angle"], d["scale"], d["dx"], d["dy"], x.shape[2], x.shape[3])
+            return ops.affine_warp_rng(x, seed_offset[0], seed_offset[1], self.KIND, self.rng_params())
+        th, apply = self.draw_theta(x.shape[0], x.shape[2], x.shape[3], x.device, draws)
         warped = ops.affine_warp(x, th)
-        return torch.where(d["apply"].reshape(-1, 1, 1, 1), warped, x)
+        return torch.where(apply.reshape(-1, 1, 1, 1), warped, x)
 
 
 class LitModule(ImageLoggingMixin, LightningModule):
     def __init__(self, **kwargs):
         super().__init__()
         self.save_hyperparameters()
+        device_pool.check_hparams(self.hparams, self.hparams.get("data_path_a"), self.hparams.get("data_path_b"))
+        self.__dict__["_pools"] = {}  # device_dataset: the DeviceImagePool of domain "a" / "b", made by train_dataloader()
         self.setup_image_logging()  # image_logging_scheduler (:44); None unless `image_logging: true`
         self.augmentation = self.create_gpu_augmentation()
         self.model_a = self.create_model_instance()
@@ -128,6 +146,10 @@ class LitModule(ImageLoggingMixin, LightningModule):
 
     def create_dataloader(self, path, mean, std, domain=""):
         p = self.hparams
+        if device_pool.check_hparams(p, path):  # the list decoded once into device memory, batches of indices
+            if domain not in self._pools:
+                self._pools[domain] = DeviceImagePool.from_hparams(p, path, self.device)
+            return self._pools[domain].loader(p.batch_size, shuffle=True, pin_memory=p.get("pin_memory", True))
         if p.get("synthetic", False) or path is None:
             # a stable, per-domain seed (str hashes are randomised per process; two None paths must still differ)
             seed = 1234 + zlib.crc32(f"{domain}:{path}".encode()) % 1000
@@ -190,27 +212,40 @@ class LitModule(ImageLoggingMixin, LightningModule):
         ]
 
     def training_step(self, batch, batch_idx, optimizer_idx):
-        batch_a = batch["a"]["image"]
-        batch_b = batch["b"]["image"]
-        p = self.hparams
-        if optimizer_idx == 0 and batch_a.dtype == torch.uint8:  # a `uint8_batches: true` loader (mean passed as std too,
-            batch_a = ops.u8rgb_normalise(batch_a, p.mean_a, p.mean_a)  # like train_dataloader / the reference :75-76)
-        if optimizer_idx == 1 and batch_b.dtype == torch.uint8:
-            batch_b = ops.u8rgb_normalise(batch_b, p.mean_b, p.mean_b)
-        if self.augmentation is not None:
-            # the reference augments in the dataset; each image of a combined batch is consumed by exactly one of the
-            # two optimiser steps (a by 0, b by 1), so warping the half a step uses is the same thing
-            if optimizer_idx == 0:
-                batch_a = self.augment(batch_a, 0)
-            else:
-                batch_b = self.augment(batch_b, 1)
+        # the reference augments in the dataset; each image of a combined batch is consumed by exactly one of the two
+        # optimiser steps (a by 0, b by 1), so preparing the half a step uses is the same thing
         if optimizer_idx == 0:
+            batch_a = self.domain_images(batch, "a")
             self.update_image_logging_schedule()  # once per batch (:148)
             loss = self.training_step_for_one_model("a", batch_a, self.model_a, self.ema_model_b)
         if optimizer_idx == 1:
+            batch_b = self.domain_images(batch, "b")
             loss = self.training_step_for_one_model("b", batch_b, self.model_b, self.ema_model_a)
         self.log("epoch", float(self.current_epoch))
         return loss
+
+    @torch.no_grad()
+    def domain_images(self, batch, key):
+        """domain `key`'s part of a combined batch -> the normalised, augmented float batch its step trains on.  A
+        `device_dataset` part carries `index` only: gather from the domain's pool, normalise and augment in ONE launch (the
+        draws inside it under `device_rng`, otherwise ShiftScaleRotate's torch draws in their order, then the launch with
+        their theta and apply).  The mean is passed as std too, like train_dataloader / the reference :75-76."""
+        p = self.hparams
+        part, mean, stream, aug = batch[key], p[f"mean_{key}"], "ab".index(key), self.augmentation
+        if "image" not in part:
+            pool, index = self._pools[key], part["index"]
+            if aug is None:
+                return pool.batch(index, mean, mean)
+            if p.get("device_rng", False):
+                return pool.batch_rng(index, mean, mean, *rng.module_stream(self, stream), aug.KIND, aug.rng_params())
+            theta, apply = aug.draw_theta(index.shape[0], *pool.geometry, index.device)
+            return pool.batch(index, mean, mean, theta=theta, apply=apply)
+        x = part["image"]
+        if x.dtype == torch.uint8:  # a `uint8_batches: true` loader
+            x = ops.u8rgb_normalise(x, mean, mean)
+        if aug is not None:
+            x = self.augment(x, stream)
+        return x
 
     def augment(self, x, stream):
         if self.hparams.get("device_rng", False):
@@ -231,7 +266,11 @@ class LitModule(ImageLoggingMixin, LightningModule):
             if len(optimizers) != 2 or not all(isinstance(o, FusedAdam) for o in optimizers) or \
                     optimizers[0].module is not self.model_a or optimizers[1].module is not self.model_b:
                 return False
-        if batch is not None:
+        if batch is not None and "image" not in batch["a"]:  # device_dataset: equal B and equal pool geometry
+            a, b = batch["a"]["index"], batch["b"]["index"]
+            if a.shape != b.shape or a.device.type != "cuda" or self._pools["a"].geometry != self._pools["b"].geometry:
+                return False
+        elif batch is not None:
             a, b = batch["a"]["image"], batch["b"]["image"]
             if a.shape != b.shape or a.dtype != b.dtype or a.device.type != "cuda":
                 return False
@@ -245,15 +284,10 @@ class LitModule(ImageLoggingMixin, LightningModule):
         `device_rng` the same streams 0 / 1, whatever the order), ONE
         forward of UnetPair(model_a, model_b), the two losses.  Returns (loss_a, loss_b); the caller runs ONE backward,
         torch.autograd.backward([loss_a, loss_b]), then both optimizer steps."""
-        p = self.hparams
         self.update_image_logging_schedule()
         reals, noisy = [], []
-        for stream, (key, mean) in enumerate((("a", p.mean_a), ("b", p.mean_b))):
-            x = batch[key]["image"]
-            if x.dtype == torch.uint8:
-                x = ops.u8rgb_normalise(x, mean, mean)
-            if self.augmentation is not None:
-                x = self.augment(x, stream)
+        for stream, key in enumerate("ab"):
+            x = self.domain_images(batch, key)
             with torch.no_grad():
                 noisy.append(self.blend_random_amount_of_noise_with_each_sample(x, stream))
             reals.append(x)

@@ -16,6 +16,9 @@ Differences, all outside the parity-checked arithmetic
   * `device_rng: true` (off by default; optional `rng_seed`): the noise, y and augmentation draws come from the
     counter-based generator inside the kernels that consume them (rng.py, csrc/philox.h) -- a function of (seed,
     global_step, rank), so a resumed run continues the interrupted one.  Not together with `graph_step`.
+  * `device_dataset: true` (off by default; optional `device_dataset_max_fraction`; not with `synthetic`): the image list is
+    decoded once into a uint8 pool on the device (dataset/device_pool.py), the loader yields indices and `step_images`
+    gathers, normalises and augments the batch in one launch -- the values of the `uint8_batches` path, bit for bit.
 """
 import math
 
@@ -24,6 +27,8 @@ import torch.optim.lr_scheduler as schedulers
 from torch.utils.data import DataLoader
 
 from .. import ops, rng
+from ..dataset import device_pool
+from ..dataset.device_pool import DeviceImagePool
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset, ToUint8Tensor
 from ..helpers import ImageLoggingMixin
 from ..lightning import LightningModule
@@ -40,25 +45,33 @@ class RandomAffine(torch.nn.Module):
         super().__init__()
         self.degrees, self.translate, self.scale = degrees, translate, scale
 
+    KIND = "random_affine"
+
+    def rng_params(self):
+        """the `params` of ops.affine_warp_rng / ops.pool_batch_rng"""
+        return (self.degrees, self.translate[0], self.translate[1], self.scale[0], self.scale[1])
+
     def forward(self, x, seed_offset=None):
         if seed_offset is not None:  # device_rng: (seed, offset) -- the draws and theta happen inside the warp kernel
-            return ops.affine_warp_rng(x, seed_offset[0], seed_offset[1], "random_affine",
-                                       (self.degrees, self.translate[0], self.translate[1], self.scale[0], self.scale[1]))
-        B = x.shape[0]
-        dev = x.device
+            return ops.affine_warp_rng(x, seed_offset[0], seed_offset[1], self.KIND, self.rng_params())
+        return ops.affine_warp(x, self.draw_theta(x.shape[0], x.device))  # K17: affine_grid + grid_sample in one HIP kernel
+
+    def draw_theta(self, B, dev):
+        """the torch draws of one batch, in their order, and the [B, 2, 3] theta they give"""
         ang = (torch.rand(B, device=dev) * 2 - 1) * math.radians(self.degrees)
         sc = torch.rand(B, device=dev) * (self.scale[1] - self.scale[0]) + self.scale[0]
         tx = (torch.rand(B, device=dev) * 2 - 1) * self.translate[0] * 2
         ty = (torch.rand(B, device=dev) * 2 - 1) * self.translate[1] * 2
         cos, sin = torch.cos(ang) / sc, torch.sin(ang) / sc
-        theta = torch.stack([torch.stack([cos, -sin, tx], 1), torch.stack([sin, cos, ty], 1)], 1)
-        return ops.affine_warp(x, theta)  # K17: affine_grid + grid_sample(bilinear, zeros) in one HIP kernel
+        return torch.stack([torch.stack([cos, -sin, tx], 1), torch.stack([sin, cos, ty], 1)], 1)
 
 
 class LitModule(ImageLoggingMixin, LightningModule):
     def __init__(self, **kwargs):
         super().__init__()
         self.save_hyperparameters()
+        device_pool.check_hparams(self.hparams, self.hparams.get("input_image_list_path"))
+        self.__dict__["_pool"] = None  # device_dataset: the DeviceImagePool, made by train_dataloader()
         self.setup_image_logging()  # image_logging_scheduler; None unless `image_logging: true` (not with graph_step)
         self.model = self.create_model_instance()
         self.training_criterion = MseStructuralSimilarityLoss(-1.0, 1.0)
@@ -92,6 +105,10 @@ class LitModule(ImageLoggingMixin, LightningModule):
 
     def create_dataloader(self, path, mean, std):
         p = self.hparams
+        if device_pool.check_hparams(p, path):  # the list decoded once into device memory, batches of indices
+            if self._pool is None:
+                self.__dict__["_pool"] = DeviceImagePool.from_hparams(p, path, self.device)
+            return self._pool.loader(p.batch_size, shuffle=True, pin_memory=p.get("pin_memory", True))
         if p.get("synthetic", False) or path is None:
             dataset = SyntheticFaceDataset(p.get("synthetic_length", 64 * p.batch_size), p.get("image_size", 256))
         else:
@@ -122,6 +139,28 @@ class LitModule(ImageLoggingMixin, LightningModule):
         m, s = self.mean_std_unit()
         return ops.u8rgb_normalise(frames_u8, m, s)
 
+    @torch.no_grad()
+    def step_images(self, batch):
+        """a loader's batch -> the normalised, augmented float batch the step trains on.  A `device_dataset` batch carries
+        `index` only: gather from the pool, normalise and augment in ONE launch (the draws inside it under `device_rng`,
+        otherwise RandomAffine's torch draws in their order, then the launch with their theta)."""
+        p = self.hparams
+        augment, aug = p.get("augment", True), self.shared_augmentation_sequence
+        if "image" not in batch:
+            index = batch["index"]
+            m, s = self.mean_std_unit()
+            if not augment:
+                return self._pool.batch(index, m, s)
+            if p.get("device_rng", False):
+                return self._pool.batch_rng(index, m, s, *rng.module_stream(self), aug.KIND, aug.rng_params())
+            return self._pool.batch(index, m, s, theta=aug.draw_theta(index.shape[0], index.device))
+        image = batch["image"]
+        if image.dtype == torch.uint8:
+            image = self.normalise_on_device(image)
+        if augment:
+            image = aug(image, rng.module_stream(self)) if p.get("device_rng", False) else aug(image)
+        return image
+
     def configure_optimizers(self):
         p = self.hparams
         # optimizer_overlap_tail: true -- the update of layer3 / layer4 / decoder / head runs inside backward next to the
@@ -136,15 +175,7 @@ class LitModule(ImageLoggingMixin, LightningModule):
 
     def training_step(self, batch, batch_idx):
         self.update_image_logging_schedule()
-        image = batch["image"]
-        if image.dtype == torch.uint8:
-            image = self.normalise_on_device(image)
-        if self.hparams.get("augment", True):
-            with torch.no_grad():
-                if self.hparams.get("device_rng", False):
-                    image = self.shared_augmentation_sequence(image, rng.module_stream(self))
-                else:
-                    image = self.shared_augmentation_sequence(image)
+        image = self.step_images(batch)
         if not self.automatic_optimization:
             if self._graph_step is None:
                 from ..graph_step import GraphTrainStep

@@ -457,6 +457,31 @@ int d3f_affine_warp_rng(const float* in, float* out, uint64_t seed, uint64_t off
 int d3f_affine_theta_draw(uint64_t seed, uint64_t offset, int kind, const float params[5],
                           float* theta, uint8_t* apply, int B, int H, int W, void* stream);
 
+/* Device dataset: a training batch assembled from a pool of decoded images that stays in device memory.  Replaces, per
+ * step, the host's decode + transform (d3f/dataset/image_dataset.py:33-44), the copy of the batch to the device, and the
+ * augmentation of d3f/train_deep_fake/lit_module.py:99-111 (A.Normalize + A.ShiftScaleRotate) or of
+ * d3f/train_denoiser/lit_module.py:55-65,113 (RandomAffine) -- one launch.
+ *   pool [N][H][W][3] uint8 RGB (the input layout of d3f_u8rgb_normalise), index [B] int64 on the device,
+ *   out [B][3][H][W] f32, mean / std host arrays.
+ *   plain (theta == NULL, apply == NULL): out[b] = ((float)pool[index[b]] / 255 - mean[c]) / std[c], the bits of
+ *     d3f_u8rgb_normalise;
+ *   theta [B][2][3]: the plain image through the sampling of d3f_affine_warp where apply[b] != 0 (apply [B] uint8 on the
+ *     device; NULL: every image), the plain image elsewhere -- the bits of torch.where(apply, warp(x, theta), x);
+ *   d3f_pool_batch_rng: the plain image through d3f_affine_warp_rng(seed, offset, kind, params): same draw layout, an
+ *     image whose `apply` draw fails is the plain image.
+ * The three forms and the two warp entries above instantiate ONE sampling function and ONE theta function; with
+ * contraction off the fused result is bit for bit the composition it replaces.
+ * An index outside [0, N) makes that output image all NaN; nothing is read for it, the other images are unaffected.
+ * Image bases are 64-bit (N * H * W * 3 may pass 2^32) and need no alignment.
+ * Refused before any device call: a null pool / index / out / mean / std / params (index and out may be null at B == 0,
+ * which launches nothing), N < 1, B < 0, H or W < 1, a zero std, an image of 2^31 bytes or more, apply without theta, a bad
+ * kind or bad params (as d3f_affine_warp_rng). */
+int d3f_pool_batch(const uint8_t* pool, int64_t N, const int64_t* index, float* out, int B, int H, int W,
+                   const float mean[3], const float std[3], const float* theta, const uint8_t* apply, void* stream);
+int d3f_pool_batch_rng(const uint8_t* pool, int64_t N, const int64_t* index, float* out, int B, int H, int W,
+                       const float mean[3], const float std[3], uint64_t seed, uint64_t offset, int kind,
+                       const float params[5], void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Training-step arithmetic around the network
  * ------------------------------------------------------------------------------------- */
