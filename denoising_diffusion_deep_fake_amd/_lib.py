@@ -13,6 +13,7 @@ LIB_PATH = Path(os.environ["D3F_LIB"]) if os.environ.get("D3F_LIB") else _HERE /
 HEADER_PATH = _HERE.parent / "include" / "d3f_hip.h"
 
 F32, BF16, F32X3 = 0, 1, 2  # F32X3: fp32 tensors, contractions on the bf16 matrix pipe (exact 3-way split)
+AUGMENT_NONE = -1  # D3F_AUGMENT_NONE: the `kind` of d3f_pool_batch_balanced_rng that warps nothing
 
 
 # D3F_ACT_*: the head activation codes, by the canonical names Unet.activation holds
@@ -150,6 +151,9 @@ PROTOTYPES = {
     "d3f_affine_theta_draw": (_i, [_u64, _u64, _i, C.POINTER(_f), _p, _p, _i, _i, _i, _p]),
     "d3f_pool_batch": (_i, [_p, _i64, _p, _p, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _p, _p, _p]),
     "d3f_pool_batch_rng": (_i, [_p, _i64, _p, _p, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _u64, _u64, _i, C.POINTER(_f), _p]),
+    "d3f_pool_batch_balanced_rng": (_i, [_p, _i64, _p, _p, _i, _p, _p, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _u64, _u64, _i,
+                                         C.POINTER(_f), _p]),
+    "d3f_balanced_index_draw": (_i, [_p, _p, _i, _u64, _u64, _p, _i, _p]),
 }
 
 # d3f_allreduce_fn: int (*)(void* ctx, float* data, int64_t count, void* stream)

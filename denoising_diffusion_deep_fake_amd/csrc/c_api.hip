@@ -750,6 +750,37 @@ int d3f_pool_batch_rng(const uint8_t* pool, int64_t N, const int64_t* index, flo
                            (hipStream_t)stream);
 }
 
+int d3f_pool_batch_balanced_rng(const uint8_t* pool, int64_t N, const int64_t* members, const int64_t* class_start, int Kn,
+                                float* out, int64_t* index_out, int B, int H, int W, const float mean[3],
+                                const float std[3], uint64_t seed, uint64_t offset, int kind, const float params[5],
+                                void* stream) {
+  const char* who = "pool_batch_balanced_rng";
+  D3F_CHECK(members != nullptr, "%s: members is null", who);
+  D3F_CHECK(class_start != nullptr, "%s: class_start is null", who);
+  D3F_CHECK(index_out != nullptr || B == 0, "%s: index_out is null", who);
+  D3F_CHECK(Kn >= 1, "%s: Kn %d < 1 (no class with an image)", who, Kn);
+  D3F_CHECK(B <= 65535, "%s: B %d above 65535 images per launch", who, B);
+  if (int rc = pool_batch_check(who, pool, N, index_out, out, B, H, W, mean, std)) return rc;
+  AffineRngParams q;
+  if (kind != D3F_AUGMENT_NONE) {
+    D3F_CHECK(params != nullptr, "%s: params is null", who);
+    if (int rc = affine_rng_params(kind, params, H, W, q)) return rc;
+  }
+  return pool_batch_balanced_launch(pool, N, members, class_start, Kn, out, index_out, B, H, W, mean, std, seed, offset,
+                                    kind != D3F_AUGMENT_NONE ? &q : nullptr, (hipStream_t)stream);
+}
+int d3f_balanced_index_draw(const int64_t* members, const int64_t* class_start, int Kn, uint64_t seed, uint64_t offset,
+                            int64_t* index_out, int B, void* stream) {
+  const char* who = "balanced_index_draw";
+  D3F_CHECK(members != nullptr, "%s: members is null", who);
+  D3F_CHECK(class_start != nullptr, "%s: class_start is null", who);
+  D3F_CHECK(index_out != nullptr || B == 0, "%s: index_out is null", who);
+  D3F_CHECK(Kn >= 1, "%s: Kn %d < 1 (no class with an image)", who, Kn);
+  D3F_CHECK(B >= 0, "%s: B %d < 0", who, B);
+  D3F_CHECK(B <= 65535, "%s: B %d above 65535 images per launch", who, B);
+  return balanced_index_draw_launch(members, class_start, Kn, seed, offset, index_out, B, (hipStream_t)stream);
+}
+
 int d3f_nchw_to_nhwc(int dtype, const float* in, void* out, int B, int C, int H, int W, int Cpad, void* stream) {
   D3F_CHECK(in && out && Cpad >= C, "nchw_to_nhwc: argument");
   return nchw_to_nhwc_launch(sdt(dtype), in, out, B, C, H, W, Cpad, (hipStream_t)stream);

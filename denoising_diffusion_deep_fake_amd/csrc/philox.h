@@ -10,6 +10,11 @@
 //   g = 0xFFFFFFFF  word 0: the per-image uniform y of the exponential sampler, y = (x0 >> 8) * 2^-24 in [0,1)
 //   g = 0xFFFFFFFE  words 0..3: the augmentation uniforms u0..u3 of image b (same conversion as y)
 //   g = 0xFFFFFFFD  word 0: u4, the augmentation's Bernoulli draw (apply = u4 < p)
+//                   words 1, 2: balanced sampling's index of image b (pointwise.h: balanced_index_rng), integers only:
+//                   class j = (x1 * Kn) >> 32 among the Kn non-empty classes, member m = (x2 * cnt_j) >> 32 of its cnt_j.
+//                   Multiply-high maps 2^32 words onto cnt values: each value gets floor or ceil of 2^32 / cnt words,
+//                   so a probability is off from 1 / cnt by less than 2^-32 (relative bias at most cnt / 2^32)
+//                   word 3: free
 // The python side packs offset = global_step << 24 | rank << 8 | stream (rng.py).
 #pragma once
 #include <stdint.h>

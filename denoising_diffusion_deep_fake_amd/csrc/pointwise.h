@@ -244,6 +244,28 @@ __device__ __forceinline__ bool affine_theta_rng(uint64_t seed, uint64_t offset,
 int pool_batch_launch(const uint8_t* pool, int64_t N, const int64_t* index, float* out, int B, int H, int W,
                       const float mean[3], const float stdv[3], const float* theta, const uint8_t* apply, uint64_t seed,
                       uint64_t offset, const AffineRngParams* q, hipStream_t stream);
+// Balanced sampling: pool_batch_launch's rng form (q == nullptr: no augmentation) with the index of image b drawn inside the
+// launch and written to index_out [B], and the draws alone.  The table, in device memory: members [M] int64, the listed
+// images sorted by (class, index); class_start [Kn + 1] int64, offsets into members of the Kn non-empty classes.
+int pool_batch_balanced_launch(const uint8_t* pool, int64_t N, const int64_t* members, const int64_t* class_start, int Kn,
+                               float* out, int64_t* index_out, int B, int H, int W, const float mean[3],
+                               const float stdv[3], uint64_t seed, uint64_t offset, const AffineRngParams* q,
+                               hipStream_t stream);
+int balanced_index_draw_launch(const int64_t* members, const int64_t* class_start, int Kn, uint64_t seed, uint64_t offset,
+                               int64_t* index_out, int B, hipStream_t stream);
+// the draw (philox.h: words 1 and 2 of block 0xFFFFFFFD): a class among the Kn non-empty ones, then one of its members,
+// each by multiply-high -- integers only, so a host restatement is exact.  A class_start that does not ascend (the host
+// builds it; the kernel cannot know M) gives -1, which pool_batch_kernel answers with a NaN image.
+__device__ __forceinline__ int64_t balanced_index_rng(uint64_t seed, uint64_t offset, int b,
+                                                      const int64_t* __restrict__ members,
+                                                      const int64_t* __restrict__ class_start, int Kn) {
+  const Philox4 p = rng_block(seed, offset, (uint32_t)b, RNG_G_APPLY);
+  const uint32_t j = (uint32_t)(((uint64_t)p.x[1] * (uint32_t)Kn) >> 32);
+  const int64_t start = class_start[j], cnt = class_start[j + 1] - start;
+  if (cnt <= 0 || cnt >= ((int64_t)1 << 31)) return -1;
+  const int64_t m = (int64_t)(((uint64_t)p.x[2] * (uint64_t)cnt) >> 32);
+  return members[start + m];
+}
 
 // ---- weights -------------------------------------------------------------------------------
 // conv(cat(upsample2x(x), skip)) with the up-sampling folded into pre-summed weights (pointwise.hip): per-class

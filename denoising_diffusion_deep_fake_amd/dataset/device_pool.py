@@ -5,7 +5,8 @@ decoded again by the host loader in every one of them.  `DeviceImagePool` decode
 `[N, H, W, 3]` uint8 tensor in device memory (10 000 frames at 448x448 are 6 GB of the MI355X's 288 GB); after that a batch
 is its indices: the loader yields `{"index": int64 [B]}` and the LitModule's step turns them into the normalised, augmented
 float batch with one kernel launch (ops.pool_batch / ops.pool_batch_rng).  No image byte crosses PCIe in steady state and
-loader workers run only while the pool is filled.
+loader workers run only while the pool is filled.  With `balanced_sampling` and `device_rng` the launch draws the indices too
+(ops.pool_batch_balanced_rng, from `balance_table`): the loader then only counts the epoch's batches.
 
 The loader is an ordinary DataLoader over an index-only dataset, so everything the trainer does to a loader --
 `shard_loader`, the per-epoch generator of `_set_epoch` (and with it the replay of a mid-epoch resume), `CombinedLoader`,
@@ -16,6 +17,7 @@ every epoch, so a rank needs every image sooner or later.
 import torch
 from torch.utils.data import DataLoader, Dataset
 
+from . import balanced
 from .image_dataset import ImageDataset, ToUint8Tensor
 
 
@@ -68,11 +70,12 @@ def _list_collate(items):
 class DeviceImagePool:
     CHUNK = 64  # images per staging buffer and copy while the pool is filled
 
-    def __init__(self, images, paths=None):
+    def __init__(self, images, paths=None, classes=None):
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
             raise ValueError("DeviceImagePool holds uint8 images [N, H, W, 3] (RGB)")
         self.images = images.contiguous()
         self.paths = paths
+        self.classes = classes  # the list's difficulty classes (ImageDataset.image_class_list), or None
 
     def __len__(self):
         return self.images.shape[0]
@@ -126,19 +129,31 @@ class DeviceImagePool:
                 copied[k % 2].record()
         if on_gpu:
             torch.cuda.current_stream(device).synchronize()
-        return cls(pool, paths=dataset.image_path_list)
+        return cls(pool, paths=dataset.image_path_list, classes=dataset.image_class_list)
 
     @classmethod
     def from_hparams(cls, hparams, path, device):
         return cls.from_list(path, device, num_workers=hparams.get("num_workers", 0),
                              max_fraction=hparams.get("device_dataset_max_fraction", 0.5))
 
-    def loader(self, batch_size, shuffle=True, pin_memory=True):
-        """index batches in the order the host loader visits the images: RandomSampler / SequentialSampler, ragged last
-        batch kept, no workers (there is nothing to decode)"""
+    def loader(self, batch_size, shuffle=True, pin_memory=True, sampler=None):
+        """index batches in the order the host loader visits the images: RandomSampler / SequentialSampler (or `sampler`,
+        a BalancedSampler say), ragged last batch kept, no workers (there is nothing to decode)"""
         N = len(self)
-        return DataLoader(IndexDataset(N), batch_size=batch_size, shuffle=shuffle, num_workers=0,
-                          collate_fn=IndexCollate(N), pin_memory=bool(pin_memory) and torch.cuda.is_available())
+        order = dict(shuffle=shuffle) if sampler is None else dict(sampler=sampler)
+        return DataLoader(IndexDataset(N), batch_size=batch_size, num_workers=0, collate_fn=IndexCollate(N),
+                          pin_memory=bool(pin_memory) and torch.cuda.is_available(), **order)
+
+    def balance_table(self, classes=None, index=None):
+        """the table the balanced launch draws from, in device memory next to the pool: `members`, the listed images sorted
+        by (class, index), and `class_start`, the offsets of the classes that have an image (balanced.balance_table, built on
+        the host once).  classes: default the classes of the list the pool was filled from; index: the image each entry
+        means when the classes cover only part of the pool."""
+        classes = self.classes if classes is None else classes
+        if classes is None:
+            raise ValueError("device dataset: the pool's image list carries no difficulty classes")
+        members, class_start = balanced.balance_table(classes, len(self), index)
+        return balanced.BalanceTable(members.to(self.images.device), class_start.to(self.images.device))
 
     # ---- a batch part {"index": int64 [B] on the device} -> the float batch, one launch ---------------------------------
     def batch(self, index, mean, std, theta=None, apply=None):
@@ -148,3 +163,9 @@ class DeviceImagePool:
     def batch_rng(self, index, mean, std, seed, offset, kind, params):
         from .. import ops
         return ops.pool_batch_rng(self.images, index, mean, std, seed, offset, kind, params)
+
+    def batch_balanced_rng(self, table, B, mean, std, seed, offset, kind, params=None):
+        """(batch, index): B images drawn from `table` inside the launch that gathers, normalises and augments them"""
+        from .. import ops
+        return ops.pool_batch_balanced_rng(self.images, table.members, table.class_start, B, mean, std, seed, offset, kind,
+                                           params)

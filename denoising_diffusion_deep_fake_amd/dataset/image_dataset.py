@@ -19,15 +19,31 @@ class ImageDataset(Dataset):
     def __init__(self, image_list_path, transform=None):
         self.image_list_path = Path(image_list_path)
         self.transform = transform
+        self.image_class_list = None  # one int per image when the list is the `--output_list` of `d3f balance`
         self.image_path_list = self.read_list_of_image_paths()
 
     def read_list_of_image_paths(self):
-        image_path_list = []
+        """the reference's list, one relative path per line -- or the list `d3f balance` writes, "<path>\t<class>" per line:
+        a line whose text after its last tab is a decimal integer.  Either every line carries a class or none does (a mixed
+        list is refused); `image_class_list` is then one int per image, else None."""
+        image_path_list, class_list = [], []
         with open(self.image_list_path) as f:
-            for relative_image_path in f.readlines():
-                relative_image_path = relative_image_path.strip()
-                if relative_image_path:
-                    image_path_list.append(self.image_list_path.parent / relative_image_path)
+            for number, line in enumerate(f.readlines(), start=1):
+                relative_image_path = line.strip()
+                if not relative_image_path:
+                    continue
+                head, tab, tail = relative_image_path.rpartition("\t")
+                has_class = bool(tab) and bool(head.strip()) and tail.isascii() and tail.isdigit()
+                if image_path_list and has_class != bool(class_list):
+                    raise ValueError(f"{self.image_list_path}: line {number} ({relative_image_path!r}) "
+                                     f"{'has a' if has_class else 'has no'} difficulty class and the lines before it "
+                                     f"{'have none' if has_class else 'have one'}: a list carries a class on every line or on "
+                                     f"none")
+                if has_class:
+                    relative_image_path = head.strip()
+                    class_list.append(int(tail))
+                image_path_list.append(self.image_list_path.parent / relative_image_path)
+        self.image_class_list = class_list or None
         return image_path_list
 
     def __len__(self):

@@ -383,6 +383,50 @@ def pool_batch_rng(pool, index, mean, std, seed, offset, kind, params):
     return out
 
 
+def _balance_table_args(members, class_start, dev):
+    for name, t in (("members", members), ("class_start", class_start)):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"balanced sampling expects {name} as a contiguous int64 vector on {dev}")
+    if class_start.shape[0] < 2:
+        raise ValueError("balanced sampling: class_start [Kn + 1] names no class (Kn == 0)")
+    return class_start.shape[0] - 1
+
+
+def pool_batch_balanced_rng(pool, members, class_start, B, mean, std, seed, offset, kind, params=None):
+    """pool_batch_rng with the B indices drawn inside the launch from a balance table (d3f_pool_batch_balanced_rng;
+    DeviceImagePool.balance_table builds members [M] and class_start [Kn + 1]): every non-empty class with equal probability,
+    every image of a class with equal probability, with replacement.  kind as pool_batch_rng, or "none" (params ignored): no
+    augmentation.  Returns (batch [B, 3, H, W], index [B] int64) with batch bit for bit pool_batch_rng(pool, index, ...) and
+    index = balanced_index_draw(members, class_start, seed, offset, B)."""
+    if pool.dtype != torch.uint8 or pool.dim() != 4 or pool.shape[-1] != 3 or not pool.is_contiguous():
+        raise ValueError("pool_batch expects a contiguous uint8 pool [N, H, W, 3] (RGB)")
+    dev = _dev(pool)
+    Kn = _balance_table_args(members, class_start, dev)
+    N, H, W, _ = pool.shape
+    B = int(B)
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    index = torch.empty(B, dtype=torch.int64, device=dev)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    if kind in ("none", None, _lib.AUGMENT_NONE):
+        kind, cparams = _lib.AUGMENT_NONE, None
+    else:
+        kind, cparams = _affine_rng_params(kind, params)
+    check(_lib.lib().d3f_pool_batch_balanced_rng(ptr(pool), N, ptr(members), ptr(class_start), Kn, ptr(out), ptr(index), B, H,
+                                                 W, m, s, int(seed), int(offset), kind, cparams, stream_ptr()))
+    return out, index
+
+
+def balanced_index_draw(members, class_start, seed, offset, B):
+    """the index [B] int64 pool_batch_balanced_rng draws for the same table, seed and offset (d3f_balanced_index_draw)"""
+    dev = _dev(members)
+    Kn = _balance_table_args(members, class_start, dev)
+    index = torch.empty(int(B), dtype=torch.int64, device=dev)
+    check(_lib.lib().d3f_balanced_index_draw(ptr(members), ptr(class_start), Kn, int(seed), int(offset), ptr(index), int(B),
+                                             stream_ptr()))
+    return index
+
+
 def noise_blend(x, noise, y_uniform, lam, return_r=False):
     x = x.contiguous().float()
     out = torch.empty_like(x)

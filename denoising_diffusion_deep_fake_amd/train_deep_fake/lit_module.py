@@ -24,6 +24,11 @@ resumed run continues the interrupted one.
 list is decoded once into a uint8 pool on the device (dataset/device_pool.py), the loaders yield indices and `domain_images`
 gathers, normalises and augments a domain's batch in one launch -- the values of the `uint8_batches` path, bit for bit.
 
+`balanced_sampling: true` (absent: off; not with `synthetic`): `data_path_a` and `data_path_b` are `--output_list`s of
+`d3f balance`; in each domain every difficulty class that has an image is drawn with equal probability, then every image of
+it, with replacement, N draws an epoch (dataset/balanced.py).  A BalancedSampler per domain on the host; with `device_dataset`
+and `device_rng` the launch that assembles a domain's batch draws its indices too (ops.pool_batch_balanced_rng).
+
 Reference quirks kept on purpose: the dataloaders receive `mean_x` as BOTH
 mean and std (lit_module.py:75-76); `predict_fake("a")` uses model_a with B's mean/std (:253-257);
 de-normalisation truncates with `.int()` BEFORE clamping (:293-294).
@@ -39,7 +44,7 @@ import torch.optim.lr_scheduler as schedulers
 from torch.utils.data import DataLoader
 
 from .. import ops, rng
-from ..dataset import device_pool
+from ..dataset import balanced, device_pool
 from ..dataset.device_pool import DeviceImagePool
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset, ToUint8Tensor
 from ..helpers import ImageLoggingMixin
@@ -104,6 +109,8 @@ class LitModule(ImageLoggingMixin, LightningModule):
         self.save_hyperparameters()
         device_pool.check_hparams(self.hparams, self.hparams.get("data_path_a"), self.hparams.get("data_path_b"))
         self.__dict__["_pools"] = {}  # device_dataset: the DeviceImagePool of domain "a" / "b", made by train_dataloader()
+        balanced.check_hparams(self.hparams, self.hparams.get("data_path_a"), self.hparams.get("data_path_b"))
+        self.__dict__["_balance_tables"] = {}  # balanced_sampling on the device: each pool's table, made with the pool
         self.setup_image_logging()  # image_logging_scheduler (:44); None unless `image_logging: true`
         self.augmentation = self.create_gpu_augmentation()
         self.model_a = self.create_model_instance()
@@ -149,7 +156,12 @@ class LitModule(ImageLoggingMixin, LightningModule):
         if device_pool.check_hparams(p, path):  # the list decoded once into device memory, batches of indices
             if domain not in self._pools:
                 self._pools[domain] = DeviceImagePool.from_hparams(p, path, self.device)
-            return self._pools[domain].loader(p.batch_size, shuffle=True, pin_memory=p.get("pin_memory", True))
+            pool, sampler = self._pools[domain], None
+            if self.balanced_on_device():  # the launch draws: the loader gives the epoch its length and nothing else
+                self._balance_tables[domain] = pool.balance_table()
+            elif p.get("balanced_sampling", False):
+                sampler = self.balanced_sampler(pool.classes, domain)
+            return pool.loader(p.batch_size, shuffle=True, pin_memory=p.get("pin_memory", True), sampler=sampler)
         if p.get("synthetic", False) or path is None:
             # a stable, per-domain seed (str hashes are randomised per process; two None paths must still differ)
             seed = 1234 + zlib.crc32(f"{domain}:{path}".encode()) % 1000
@@ -162,8 +174,24 @@ class LitModule(ImageLoggingMixin, LightningModule):
         extra = dict(multiprocessing_context="spawn", persistent_workers=True,
                      prefetch_factor=p.get("prefetch_factor", 2)) if workers > 0 else {}
         # pin_memory: the trainer's `.to(device, non_blocking=True)` is only asynchronous from page-locked memory
-        return DataLoader(dataset=dataset, batch_size=p.batch_size, num_workers=workers, shuffle=True,
-                          pin_memory=bool(p.get("pin_memory", True)) and torch.cuda.is_available(), **extra)
+        order = dict(shuffle=True)
+        if p.get("balanced_sampling", False):
+            order = dict(sampler=self.balanced_sampler(dataset.image_class_list, domain))
+        return DataLoader(dataset=dataset, batch_size=p.batch_size, num_workers=workers,
+                          pin_memory=bool(p.get("pin_memory", True)) and torch.cuda.is_available(), **order, **extra)
+
+    def balanced_on_device(self):
+        """`balanced_sampling` where a domain's launch draws the indices: the pools with the device generator"""
+        p = self.hparams
+        return bool(p.get("balanced_sampling", False) and p.get("device_dataset", False) and p.get("device_rng", False))
+
+    def balanced_sampler(self, classes, domain):
+        """the host path's sampler of one domain (stream 0 for a, 1 for b); its seed is the device generator's (`rng_seed`,
+        else the trainer's base seed, which a checkpoint carries), asked for when an epoch's draws are made"""
+        if classes is None:
+            raise ValueError("balanced_sampling: true needs the difficulty class of every image (the --output_list of "
+                             "`d3f balance`)")
+        return balanced.BalancedSampler(classes, seed=lambda: rng.module_stream(self)[0], stream="ab".index(domain))
 
     def create_augmentation_sequence(self, mean, std):
         # host half of the reference's A.Compose: Normalize + ToTensorV2; its ShiftScaleRotate(p=0.7) runs on the
@@ -229,11 +257,16 @@ class LitModule(ImageLoggingMixin, LightningModule):
         """domain `key`'s part of a combined batch -> the normalised, augmented float batch its step trains on.  A
         `device_dataset` part carries `index` only: gather from the domain's pool, normalise and augment in ONE launch (the
         draws inside it under `device_rng`, otherwise ShiftScaleRotate's torch draws in their order, then the launch with
-        their theta and apply).  The mean is passed as std too, like train_dataloader / the reference :75-76."""
+        their theta and apply).  Under `balanced_sampling` with `device_rng` the launch draws the images as well and `index` only
+        says how many.  The mean is passed as std too, like train_dataloader / the reference :75-76."""
         p = self.hparams
         part, mean, stream, aug = batch[key], p[f"mean_{key}"], "ab".index(key), self.augmentation
         if "image" not in part:
             pool, index = self._pools[key], part["index"]
+            if key in self._balance_tables:  # balanced_sampling: the indices are drawn inside the launch
+                kind, params = (aug.KIND, aug.rng_params()) if aug is not None else ("none", None)
+                return pool.batch_balanced_rng(self._balance_tables[key], index.shape[0], mean, mean,
+                                               *rng.module_stream(self, stream), kind, params)[0]
             if aug is None:
                 return pool.batch(index, mean, mean)
             if p.get("device_rng", False):

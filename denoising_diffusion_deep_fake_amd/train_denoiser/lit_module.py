@@ -19,6 +19,10 @@ Differences, all outside the parity-checked arithmetic
   * `device_dataset: true` (off by default; optional `device_dataset_max_fraction`; not with `synthetic`): the image list is
     decoded once into a uint8 pool on the device (dataset/device_pool.py), the loader yields indices and `step_images`
     gathers, normalises and augments the batch in one launch -- the values of the `uint8_batches` path, bit for bit.
+  * `balanced_sampling: true` (absent: off; not with `synthetic`): `input_image_list_path` is the `--output_list` of
+    `d3f balance`; every difficulty class that has an image is drawn with equal probability, then every image of it, with
+    replacement, N draws an epoch (dataset/balanced.py).  A BalancedSampler on the host; with `device_dataset` and
+    `device_rng` the launch that assembles the batch draws the indices too (ops.pool_batch_balanced_rng).
 """
 import math
 
@@ -27,7 +31,7 @@ import torch.optim.lr_scheduler as schedulers
 from torch.utils.data import DataLoader
 
 from .. import ops, rng
-from ..dataset import device_pool
+from ..dataset import balanced, device_pool
 from ..dataset.device_pool import DeviceImagePool
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset, ToUint8Tensor
 from ..helpers import ImageLoggingMixin
@@ -72,6 +76,8 @@ class LitModule(ImageLoggingMixin, LightningModule):
         self.save_hyperparameters()
         device_pool.check_hparams(self.hparams, self.hparams.get("input_image_list_path"))
         self.__dict__["_pool"] = None  # device_dataset: the DeviceImagePool, made by train_dataloader()
+        balanced.check_hparams(self.hparams, self.hparams.get("input_image_list_path"))  # refusals: now, on the host
+        self.__dict__["_balance_table"] = None  # balanced_sampling on the device: the pool's table, made with the pool
         self.setup_image_logging()  # image_logging_scheduler; None unless `image_logging: true` (not with graph_step)
         self.model = self.create_model_instance()
         self.training_criterion = MseStructuralSimilarityLoss(-1.0, 1.0)
@@ -108,7 +114,12 @@ class LitModule(ImageLoggingMixin, LightningModule):
         if device_pool.check_hparams(p, path):  # the list decoded once into device memory, batches of indices
             if self._pool is None:
                 self.__dict__["_pool"] = DeviceImagePool.from_hparams(p, path, self.device)
-            return self._pool.loader(p.batch_size, shuffle=True, pin_memory=p.get("pin_memory", True))
+            sampler = None
+            if self.balanced_on_device():  # the launch draws: the loader gives the epoch its length and nothing else
+                self.__dict__["_balance_table"] = self._pool.balance_table()
+            elif p.get("balanced_sampling", False):
+                sampler = self.balanced_sampler(self._pool.classes)
+            return self._pool.loader(p.batch_size, shuffle=True, pin_memory=p.get("pin_memory", True), sampler=sampler)
         if p.get("synthetic", False) or path is None:
             dataset = SyntheticFaceDataset(p.get("synthetic_length", 64 * p.batch_size), p.get("image_size", 256))
         else:
@@ -123,8 +134,24 @@ class LitModule(ImageLoggingMixin, LightningModule):
         extra = dict(multiprocessing_context="spawn", persistent_workers=True,
                      prefetch_factor=p.get("prefetch_factor", 2)) if workers > 0 else {}
         # pin_memory: the trainer's `.to(device, non_blocking=True)` is only asynchronous from page-locked memory
-        return DataLoader(dataset=dataset, batch_size=p.batch_size, num_workers=workers, shuffle=True,
-                          pin_memory=bool(p.get("pin_memory", True)) and torch.cuda.is_available(), **extra)
+        order = dict(shuffle=True)
+        if p.get("balanced_sampling", False):
+            order = dict(sampler=self.balanced_sampler(dataset.image_class_list))
+        return DataLoader(dataset=dataset, batch_size=p.batch_size, num_workers=workers,
+                          pin_memory=bool(p.get("pin_memory", True)) and torch.cuda.is_available(), **order, **extra)
+
+    def balanced_on_device(self):
+        """`balanced_sampling` where the batch's launch draws the indices: the pool with the device generator"""
+        p = self.hparams
+        return bool(p.get("balanced_sampling", False) and p.get("device_dataset", False) and p.get("device_rng", False))
+
+    def balanced_sampler(self, classes):
+        """the host path's sampler; its seed is the device generator's (`rng_seed`, else the trainer's base seed, which a
+        checkpoint carries), asked for when an epoch's draws are made"""
+        if classes is None:
+            raise ValueError("balanced_sampling: true needs the difficulty class of every image (the --output_list of "
+                             "`d3f balance`)")
+        return balanced.BalancedSampler(classes, seed=lambda: rng.module_stream(self)[0])
 
     def mean_std_unit(self):
         """config means / stds are in 0..255 units (denoiser_config.yml:10-11) -> [0, 1] units"""
@@ -143,12 +170,17 @@ class LitModule(ImageLoggingMixin, LightningModule):
     def step_images(self, batch):
         """a loader's batch -> the normalised, augmented float batch the step trains on.  A `device_dataset` batch carries
         `index` only: gather from the pool, normalise and augment in ONE launch (the draws inside it under `device_rng`,
-        otherwise RandomAffine's torch draws in their order, then the launch with their theta)."""
+        otherwise RandomAffine's torch draws in their order, then the launch with their theta).  Under `balanced_sampling`
+        with `device_rng` the launch draws the images as well and `index` only says how many."""
         p = self.hparams
         augment, aug = p.get("augment", True), self.shared_augmentation_sequence
         if "image" not in batch:
             index = batch["index"]
             m, s = self.mean_std_unit()
+            if self._balance_table is not None:  # balanced_sampling: the indices are drawn inside the launch
+                kind, params = (aug.KIND, aug.rng_params()) if augment else ("none", None)
+                return self._pool.batch_balanced_rng(self._balance_table, index.shape[0], m, s, *rng.module_stream(self),
+                                                     kind, params)[0]
             if not augment:
                 return self._pool.batch(index, m, s)
             if p.get("device_rng", False):

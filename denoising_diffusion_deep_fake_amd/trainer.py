@@ -119,14 +119,18 @@ def shard_loader(loader, world_size, rank, seed=0):
     if loader.batch_sampler is not None and type(loader.batch_sampler).__name__ != "BatchSampler":
         raise TypeError(f"shard_loader: a custom batch_sampler ({type(loader.batch_sampler).__name__}) cannot be "
                         f"sharded automatically; build the per-rank loader in train_dataloader()")
-    if type(loader.sampler) not in (RandomSampler, SequentialSampler):
+    if hasattr(loader.sampler, "for_rank"):
+        # a sampler that shards itself (dataset.BalancedSampler: draws with replacement, one stream per rank)
+        sampler = loader.sampler.for_rank(world_size, rank, seed)
+    elif type(loader.sampler) not in (RandomSampler, SequentialSampler):
         # e.g. a WeightedRandomSampler over the `balance` difficulty classes: replacing it with a plain
         # DistributedSampler would silently change what the run trains on
         raise TypeError(f"shard_loader: sampler {type(loader.sampler).__name__} is neither sequential nor random; "
                         f"shard it yourself (per-rank sampler) in train_dataloader()")
-    shuffle = isinstance(loader.sampler, RandomSampler)
-    sampler = DistributedSampler(loader.dataset, num_replicas=world_size, rank=rank, shuffle=shuffle, seed=seed,
-                                 drop_last=False)
+    else:
+        shuffle = isinstance(loader.sampler, RandomSampler)
+        sampler = DistributedSampler(loader.dataset, num_replicas=world_size, rank=rank, shuffle=shuffle, seed=seed,
+                                     drop_last=False)
     kw = dict(batch_size=loader.batch_size, sampler=sampler, num_workers=loader.num_workers,
               collate_fn=loader.collate_fn, pin_memory=loader.pin_memory, drop_last=loader.drop_last,
               timeout=loader.timeout, worker_init_fn=loader.worker_init_fn, generator=loader.generator,

@@ -482,6 +482,27 @@ int d3f_pool_batch_rng(const uint8_t* pool, int64_t N, const int64_t* index, flo
                        const float mean[3], const float std[3], uint64_t seed, uint64_t offset, int kind,
                        const float params[5], void* stream);
 
+/* Balanced sampling: d3f_pool_batch_rng with the index of every image drawn inside the launch, from the difficulty classes
+ * `d3f balance` writes.  The table lies in device memory:
+ *   members [M] int64: the listed images, sorted by (class, index);
+ *   class_start [Kn + 1] int64: offsets into members of the Kn classes that have an image (empty classes are left out).
+ * Image b of the stream (seed, offset) is, with x = block 0xFFFFFFFD of image b (word 0 is the augmentation's Bernoulli
+ * draw):  j = (x1 * Kn) >> 32,  cnt = class_start[j + 1] - class_start[j],  m = (x2 * cnt) >> 32,
+ *         index = members[class_start[j] + m]        (64-bit products of 32-bit words)
+ * -- every class with equal probability, every image of a class with equal probability, with replacement; a function of
+ * (seed, offset, b) alone.  index_out [B] int64 receives the indices; out is d3f_pool_batch_rng(pool, N, index_out, ...),
+ * bit for bit.  kind: 0 / 1 as d3f_affine_warp_rng, or D3F_AUGMENT_NONE (params may be NULL): the plain image.
+ * d3f_balanced_index_draw writes the same indices without touching a pool.
+ * Refused before any device call: what d3f_pool_batch_rng refuses, a null members / class_start / index_out (index_out and
+ * out may be null at B == 0, which launches nothing), Kn < 1, B > 65535. */
+#define D3F_AUGMENT_NONE (-1)
+int d3f_pool_batch_balanced_rng(const uint8_t* pool, int64_t N, const int64_t* members, const int64_t* class_start, int Kn,
+                                float* out, int64_t* index_out, int B, int H, int W, const float mean[3],
+                                const float std[3], uint64_t seed, uint64_t offset, int kind, const float params[5],
+                                void* stream);
+int d3f_balanced_index_draw(const int64_t* members, const int64_t* class_start, int Kn, uint64_t seed, uint64_t offset,
+                            int64_t* index_out, int B, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Training-step arithmetic around the network
  * ------------------------------------------------------------------------------------- */
