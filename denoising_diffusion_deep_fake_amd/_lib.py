@@ -44,12 +44,32 @@ class BnPlan(C.Structure):
                 ("rows_per_block", C.c_int64), ("stat_floats", C.c_uint64), ("part_floats", C.c_uint64)]
 
 
+class ConvLaunchPlan(C.Structure):
+    """d3f_conv_launch_plan: the kernel form of one forward / data-gradient launch"""
+    _fields_ = [(n, C.c_int32) for n in
+                ("planned", "patch", "tile_bm", "tile_bn", "tiles_m", "tiles_n", "splitk", "par", "nz", "small_c",
+                 "fast_addr", "sum2", "stat_rows")]
+
+
+class ConvWgradPlan(C.Structure):
+    """d3f_conv_wgrad_plan: one pass of a layer's weight gradient"""
+    _fields_ = [(n, C.c_int32) for n in ("part", "cls", "patch", "splits", "chunks_per_split", "tile", "tiles")]
+
+
+class ConvPlan(C.Structure):
+    """d3f_conv_plan: what conv_layer_plan made of a ConvDesc"""
+    _fields_ = [("upfold", C.c_int32), ("parity", C.c_int32), ("wino", C.c_int32), ("wino_rows", C.c_int32),
+                ("fwd", ConvLaunchPlan), ("dgrad", ConvLaunchPlan), ("dgrad_lo", ConvLaunchPlan),
+                ("wgrad_parts", C.c_int32), ("wgrad", ConvWgradPlan * 2)]
+
+
 BN_COEF_ROWS = 7  # D3F_BN_COEF_ROWS: mean invstd scale shift k0 k1 k2
 
 _p, _i, _i64, _f, _sz, _dbl = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_double
 _u64, _u32p = C.c_uint64, C.POINTER(C.c_uint32)
 _desc = C.POINTER(ConvDesc)
 _bnd, _bnp = C.POINTER(BnDesc), C.POINTER(BnPlan)
+_cvp = C.POINTER(ConvPlan)
 
 # name -> (restype, argtypes); must list every symbol include/d3f_hip.h declares
 PROTOTYPES = {
@@ -123,6 +143,9 @@ PROTOTYPES = {
     "d3f_conv_backward_data": (_i, [_i, _desc, _p, _p, _p, _p, _i, _i, _p, _p]),
     "d3f_conv_backward_weight_workspace_bytes": (_sz, [_i, _desc]),
     "d3f_conv_backward_weight": (_i, [_i, _desc, _p, _p, _p, _p, _p, _p]),
+    "d3f_conv_layer_plan": (_i, [_i, _desc, _i, _cvp]),
+    "d3f_unet_num_conv_layers": (_i, [_p]),
+    "d3f_unet_conv_layer": (_i, [_p, _i, _desc, _cvp]),
     "d3f_bn_finalize": (_i, [_p, _i, _i, _i64, _p, _p, _p, _p, _p, _p]),
     "d3f_bn_apply": (_i, [_i, _p, _p, _i, _i64, _p, _i, _p, _p]),
     "d3f_bn_backward_workspace_bytes": (_sz, [_i, _i, _i64]),

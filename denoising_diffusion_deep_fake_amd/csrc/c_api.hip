@@ -493,6 +493,63 @@ int d3f_conv_backward_weight(int dtype, const d3f_conv_desc* d, const void* dy, 
                             (hipStream_t)stream);
 }
 
+// ---- plan introspection: the planned layer's own fields, copied out ----
+static void conv_launch_out(const ConvParams& p, int dtype, d3f_conv_launch_plan* o) {
+  const bool igemm = p.patch == 0, smallc = igemm && conv_igemm_small_c(p, dtype);
+  o->planned = 1;
+  o->patch = p.patch; o->tile_bm = p.tile_bm; o->tile_bn = p.tile_bn; o->tiles_m = p.tiles_m; o->tiles_n = p.tiles_n;
+  o->splitk = p.splitk; o->par = p.par; o->nz = p.nz;
+  o->small_c = smallc ? 1 : 0;
+  o->fast_addr = igemm && conv_igemm_fast_addr(p, smallc) ? 1 : 0;
+  o->sum2 = p.sum2; o->stat_rows = p.stat_rows;
+}
+static void conv_layer_out(const ConvLayer& L, d3f_conv_plan* o) {
+  o->upfold = L.upfold; o->parity = L.parity;
+}
+static void conv_fwd_out(const ConvLayer& L, d3f_conv_plan* o) {
+  o->wino = L.wino; o->wino_rows = L.wino_rows;
+  conv_launch_out(L.fwd, L.dtype, &o->fwd);
+}
+static void conv_dgrad_out(const ConvLayer& L, d3f_conv_plan* o) {
+  if (L.upfold) conv_launch_out(L.dgrad_lo, L.dtype, &o->dgrad_lo);
+  if (!L.upfold || L.C1 > 0) conv_launch_out(L.dgrad, L.dtype, &o->dgrad);
+}
+static void conv_wgrad_out(const ConvLayer& L, d3f_conv_plan* o) {
+  o->wgrad_parts = L.wl.nparts;
+  for (int i = 0; i < L.wl.nparts; ++i) {
+    const WgradParams& w = L.wl.part[i];
+    d3f_conv_wgrad_plan& q = o->wgrad[i];
+    q.part = w.part; q.cls = w.cls; q.patch = w.patch; q.splits = w.splits; q.chunks_per_split = w.chunks_per_split;
+    q.tile = wgrad_tile_edge(w); q.tiles = wgrad_tiles(w);
+  }
+}
+int d3f_conv_layer_plan(int dtype, const d3f_conv_desc* d, int with_workspace, d3f_conv_plan* out) {
+  D3F_CHECK(out != nullptr, "conv_layer_plan: null argument");
+  std::memset(out, 0, sizeof(*out));
+  ConvLayer G, F, D, W;  // geometry, then the layer as d3f_conv_forward / _backward_data / _backward_weight plan it
+  if (int rc = plan(G, dtype, d, 0)) return rc;
+  conv_layer_out(G, out);
+  const int sk = with_workspace ? PLAN_SPLITK : 0;
+  if (plan(F, dtype, d, PLAN_FWD | sk) == 0) conv_fwd_out(F, out);
+  if (plan(D, dtype, d, PLAN_DGRAD | (d->upsample0 == 2 ? PLAN_SUM2 : 0) | sk) == 0) conv_dgrad_out(D, out);
+  if (plan(W, dtype, d, PLAN_WGRAD) == 0) conv_wgrad_out(W, out);
+  return 0;
+}
+int d3f_unet_num_conv_layers(d3f_unet_t h) { return h ? (int)h->e.units.size() : -1; }
+int d3f_unet_conv_layer(d3f_unet_t h, int i, d3f_conv_desc* d, d3f_conv_plan* plan) {
+  D3F_CHECK(h && d && plan && i >= 0 && i < (int)h->e.units.size(), "unet_conv_layer: index %d", i);
+  const Unit& u = h->e.units[i];
+  d->B = u.B; d->H = u.Hv; d->W = u.Wv; d->C0 = u.C0; d->C1 = u.C1;
+  d->upsample0 = u.up0 ? (u.want_sum2 ? 2 : 1) : 0;
+  d->Cout = u.Cout; d->KH = u.KH; d->KW = u.KW; d->stride = u.stride; d->pad = u.pad; d->CinReal = u.CinReal;
+  std::memset(plan, 0, sizeof(*plan));
+  conv_layer_out(u, plan);
+  if (u.need_fwd) conv_fwd_out(u, plan);
+  if (u.need_dgrad) conv_dgrad_out(u, plan);
+  if (u.need_wgrad) conv_wgrad_out(u, plan);
+  return 0;
+}
+
 // describe -> plan: a BatchNorm layer of the single-operator entry points (the split form)
 static BnLayer bn_layer(int dtype, int C, int64_t rows, int fwd_rows = 0) {
   BnLayer L;

@@ -281,6 +281,10 @@ struct ConvTile {
 int conv_igemm_plan(ConvParams& p, int dtype, bool allow_splitk = false);
 size_t conv_splitk_floats(const ConvParams& p);
 int conv_igemm_launch(const ConvParams& p, int dtype, hipStream_t stream);
+// the loader conv_igemm_launch instantiates for a planned launch (plan introspection reads the launch's own decisions):
+// small-channel (a k-row spans taps), and the plain-gather addressing of the regular loader
+bool conv_igemm_small_c(const ConvParams& p, int dtype);
+bool conv_igemm_fast_addr(const ConvParams& p, bool smallc);
 // conv_patch.hip: LDS-patch form of the full-resolution 16-channel 3x3 layers (chosen inside conv_igemm_plan)
 // conv_winograd.hip: Winograd F(2x2, 3x3) forward of the wide-enough stride-1 3x3 layers in train mode (fp32)
 bool conv_winograd_fits(const ConvParams& p, int dtype);     // shapes the kernel can run
@@ -348,6 +352,11 @@ enum WgradPart : int { WG_WHOLE = 0, WG_CLASS = 1, WG_SKIP = 2 };
 // fills splits / tiles / extents for one launch; returns 0
 int wgrad_plan(WgradParams& p, int dtype);
 size_t wgrad_partial_floats(const WgradParams& p);
+// a planned launch's work items and tile edge (plan introspection): the 32-pixel k-chunks the tap-parallel kernel's slabs
+// share (chunks_per_split each, the last slab the rest) on its 32 or 64 tile, or the spatial tiles the persistent patch
+// kernel's `splits` workgroups stride over (tile edge 0)
+int wgrad_tiles(const WgradParams& p);
+int wgrad_tile_edge(const WgradParams& p);
 int wgrad_launch(const WgradParams& p, int dtype, hipStream_t stream);  // p.dy / p.src0 / p.src1 -> slabs in p.partial
 
 // Slab reduces: the slabs [splits][CoutP][taps][Cin] are summed in a fixed order and written as the PyTorch-layout

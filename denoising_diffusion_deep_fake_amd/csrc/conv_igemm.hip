@@ -1429,6 +1429,12 @@ static bool is_small_c(const ConvParams& p, int dtype) {
   const int bke = dtype == D3F_BF16 ? 64 : 32;
   return ((p.C0 + p.C1) % bke) != 0;
 }
+bool conv_igemm_small_c(const ConvParams& p, int dtype) { return is_small_c(p, dtype); }
+// the plain-gather loader (FAST == 1) of a launch that is neither small-channel nor up-folded (par == 3 has its own)
+bool conv_igemm_fast_addr(const ConvParams& p, bool smallc) {
+  static const bool no_fast = prof_knob("D3F_NO_FAST_ADDR") != nullptr;  // debugging knob
+  return !no_fast && !smallc && p.C1 == 0 && p.shift0 == 0 && p.zi == 0 && p.KH * p.KW <= 32;
+}
 
 // tuning knob (debug): D3F_FORCE_TILE="BM,BN,SK" overrides the heuristics for regular (non small-C) layers
 static bool forced_tile(int* bm, int* bn, int* sk) {
@@ -1567,8 +1573,7 @@ int conv_igemm_plan(ConvParams& p, int dtype, bool allow_splitk) {
 template <typename T, int BM, int BN, int WGM, int WGN, int MT, bool X3>
 static int launch_cfg(const ConvParams& p, bool smallc, hipStream_t stream) {
   const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)p.splitk, (unsigned)(p.nz * nets_of(p.nets))), block(256);
-  static const bool no_fast = prof_knob("D3F_NO_FAST_ADDR") != nullptr;  // debugging knob
-  const bool fast = !no_fast && !smallc && p.C1 == 0 && p.shift0 == 0 && p.zi == 0 && p.KH * p.KW <= 32;
+  const bool fast = conv_igemm_fast_addr(p, smallc);
   if (p.par == 3)
     hipLaunchKernelGGL((conv_igemm_kernel<T, BM, BN, WGM, WGN, MT, false, 2, X3>), grid, block, 0, stream, p);
   else if (smallc)

@@ -518,6 +518,7 @@ static bool patch_wgrad_off() {
 
 int wgrad_patch_variant(const WgradParams& p, int dtype);
 void wgrad_patch_grid(const WgradParams& p, int variant, int* gx, int* gy);
+int wgrad_patch_tiles(const WgradParams& p);
 int wgrad_patch_launch(const WgradParams& p, int variant, int dtype, hipStream_t stream);
 
 // Does the weight gradient of conv(cat(upsample2x(src0), src1)) run as WG_CLASS + WG_SKIP passes?  The tap-parallel
@@ -577,7 +578,7 @@ int wgrad_plan(WgradParams& p, int dtype) {
   p.tiles_co = cdiv(p.Cout, t);
   p.tiles_ci = cdiv(p.slab_cin, t);
   const long base = (long)p.tiles_co * p.tiles_ci * p.slab_taps;
-  const int total_chunks = cdiv(p.Mi, KP);
+  const int total_chunks = wgrad_tiles(p);
   static const long target_env = prof_knob("D3F_WGRAD_TARGET") ? atol(prof_knob("D3F_WGRAD_TARGET")) : 0;  // sweep knob
   // fp32: ~3.6 workgroups per CU (r02_ao/ap/aq sweep of 640 ... 1280: 896-960 best, 1024 +1 %, 1280 +2 %).  bf16 storage
   // (round 5 sweep, profiles/README.md: 232 ... 1856): the launches are latency-bound, not MFMA-bound, and the stream is as
@@ -592,6 +593,9 @@ int wgrad_plan(WgradParams& p, int dtype) {
   p.splits = cdiv(total_chunks, p.chunks_per_split);
   return 0;
 }
+
+int wgrad_tiles(const WgradParams& p) { return p.patch ? wgrad_patch_tiles(p) : cdiv(p.Mi, KP); }
+int wgrad_tile_edge(const WgradParams& p) { return p.patch ? 0 : pick_wtile(p); }
 
 size_t wgrad_partial_floats(const WgradParams& p) {
   return (size_t)p.splits * p.Cout * p.slab_taps * p.slab_cin;

@@ -550,12 +550,15 @@ int wgrad_patch_variant(const WgradParams& p, int dtype) {
   return 0;
 }
 
+// spatial tiles (PT_TH rows x 16 columns of the output) every persistent kernel strides over
+int wgrad_patch_tiles(const WgradParams& p) { return p.B * cdiv(p.Ho, PT_TH) * cdiv(p.Wo, 16); }
+
 void wgrad_patch_grid(const WgradParams& p, int variant, int* gx, int* gy) {
   const int cin = p.part == WG_WHOLE ? p.C0 + p.C1 : p.part == WG_CLASS ? p.C0 : p.C1;  // channels of this launch
   const int ci_t = variant == 1 ? 32 : variant == 2 ? 16 : (variant == 3 || variant == 7) ? 32 : (variant == 5 || variant == 6) ? 8 : 4;
   const int co_t = (variant == 3 || variant == 4 || variant == 5 || variant == 6 || variant == 7) ? 32 : 16;
   const int slices = cdiv(cin, ci_t) * cdiv(p.Cout, co_t) * (p.part == WG_CLASS ? 2 : 1);  // class form: x 2 row parities
-  const int tiles = p.B * cdiv(p.Ho, PT_TH) * cdiv(p.Wo, 16);
+  const int tiles = wgrad_patch_tiles(p);
   // ~3 workgroups per CU in total; the native bf16 kernel (7): ONE per CU -- its tiles are 18 MFMAs per wave, so fewer,
   // longer-lived workgroups amortise the nine-tap epilogue and write a third of the slabs (sweep 128 / 192 / 256 / 320 / 384 /
   // 512 / 768 / 1024 workgroups: 3.64 / 3.55 / 3.46 / 3.53 / 3.48 / 3.49-3.54 / 3.52 / 3.55 ms per bf16 step)

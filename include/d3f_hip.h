@@ -313,6 +313,49 @@ size_t d3f_conv_backward_weight_workspace_bytes(int dtype, const d3f_conv_desc* 
 int d3f_conv_backward_weight(int dtype, const d3f_conv_desc* d, const void* dy, const void* src0,
                              const void* src1, void* workspace, float* dw, void* stream);
 
+/* Plan introspection (host only, nothing is launched): which kernel instantiation each launch of a convolution layer
+ * takes, read from the very layer description the three calls above plan -- a regression guard, and the table the operator
+ * tests key their cases to.  A launch the layer does not have (or that the description cannot run through the
+ * single-operator entry, e.g. a forward with Cout % 4 != 0, a data gradient of a convolution that is neither 'same' nor
+ * exactly halving) has planned == 0 and every other field 0. */
+typedef struct d3f_conv_launch_plan {
+  int32_t planned;
+  int32_t patch;             /* ConvParams::patch: 0 = conv_igemm_kernel, 1 / 3-7 conv_patch_kernel forms, 2 / 8 the stem
+                              * kernels, 9-12 conv_pres_kernel for 64 / 128 / 256 / 512 channels */
+  int32_t tile_bm, tile_bn;  /* conv_igemm_kernel's tile (0 for the patch kernels) */
+  int32_t tiles_m, tiles_n, splitk; /* splitk > 1: split-K slabs + conv_splitk_reduce_kernel */
+  int32_t par, nz;           /* output-parity form (1 / 2 stride-2 data gradient, 3 up-folded forward), classes per launch */
+  int32_t small_c;           /* conv_igemm_kernel's small-channel loader (a k-row spans taps) */
+  int32_t fast_addr;         /* its plain-gather loader, as the launch decides it (both 0 for the patch kernels) */
+  int32_t sum2;              /* data gradient stored 2x2-summed at half resolution */
+  int32_t stat_rows;         /* forward: statistics rows written ([stat_rows][CoutPad][2]) */
+} d3f_conv_launch_plan;
+typedef struct d3f_conv_wgrad_plan {
+  int32_t part, cls;         /* 0 whole layer, 1 class form of the up-sampled source, 2 the skip tensor; cls: 16 folded taps */
+  int32_t patch;             /* 0 tap-parallel conv_wgrad_kernel, 1-3 persistent patch kernel, 4 / 5 / 6 the stem's, 7 native bf16 */
+  int32_t splits;            /* slabs = workgroup columns */
+  int32_t chunks_per_split;  /* tap-parallel: 32-pixel chunks per slab (the last slab takes the rest); persistent: 0 */
+  int32_t tile;              /* tap-parallel: 32 or 64 (co x ci tile edge); persistent: 0 */
+  int32_t tiles;             /* tap-parallel: chunks in all; persistent: spatial tiles the `splits` workgroups stride over */
+} d3f_conv_wgrad_plan;
+typedef struct d3f_conv_plan {
+  int32_t upfold;            /* up-sampling folded into pre-summed weights (forward par 3, dgrad_lo + dgrad of the skip tensor) */
+  int32_t parity;            /* stride-2 data gradient as output-parity classes */
+  int32_t wino, wino_rows;   /* the whole-network plan runs the forward as Winograd; its statistics rows where the kernel fits */
+  d3f_conv_launch_plan fwd, dgrad, dgrad_lo; /* dgrad_lo: the up-folded layer's low-resolution source (then dgrad: its skip tensor) */
+  int32_t wgrad_parts;       /* 1 or 2 */
+  d3f_conv_wgrad_plan wgrad[2];
+} d3f_conv_plan;
+/* the plans d3f_conv_forward, d3f_conv_backward_data (upsample0 == 2: with the 2x2-summed request) and
+ * d3f_conv_backward_weight make of (dtype, d); with_workspace: as if the two former were handed their split-K workspace.
+ * < 0: a description no entry accepts (dtype, extents, channel multiples). */
+int d3f_conv_layer_plan(int dtype, const d3f_conv_desc* d, int with_workspace, d3f_conv_plan* out);
+/* the convolution layers of a network handle, in launch order (d3f_unet_plan_counts counts the same units), as the engine
+ * planned them: its own plan_nets, split-K workspace and 2x2-summed request (d->upsample0 == 2 where the source is
+ * up-sampled).  The segmentation head (the last layer) runs its forward with the bias + NCHW epilogue. */
+int d3f_unet_num_conv_layers(d3f_unet_t h);
+int d3f_unet_conv_layer(d3f_unet_t h, int i, d3f_conv_desc* d, d3f_conv_plan* plan);
+
 /* BatchNorm2d, train mode (eps 1e-5, momentum 0.1): finalize conv statistics, then
  * a = relu?(y*scale + shift + residual); coef = mean[C] invstd[C] scale[C] shift[C] */
 int d3f_bn_finalize(const float* stats, int tiles, int C, int64_t count, const float* gamma,

@@ -49,14 +49,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from util import rel_l2
+from util import SENTINEL, Guarded, rel_l2
 
 pytestmark = pytest.mark.gpu
 
 F32, BF16 = 0, 1
 NOISE = 4.0          # the project's factor over the CPU-fp32 reference's own distance from float64
 FLOOR = 2e-6
-SENTINEL = -8192.0   # exact in fp32 and bf16
 GUARD_ROWS = 64
 EPS = float(np.float32(1e-5))       # the kernels' constants are floats widened to double
 MOMENTUM = float(np.float32(0.1))
@@ -85,23 +84,6 @@ def tdt(dt):
 def stored(x64, dt):
     """what the storage dtype keeps of a float64 tensor, as float64"""
     return x64.to(tdt(dt)).double()
-
-
-class Guarded:
-    """a device buffer of n elements between two sentinel bands"""
-
-    def __init__(self, n, guard, dtype, fill=SENTINEL, band=SENTINEL):
-        self.n, self.g, self.band = n, guard, band
-        self.buf = torch.full((guard + n + guard,), band, dtype=dtype, device=DEV)
-        self.t = self.buf[guard:guard + n]
-        if fill != band:
-            self.t.fill_(fill)
-
-    def intact(self):
-        front, back = self.buf[:self.g], self.buf[self.g + self.n:]
-        if self.band != self.band:  # NaN bands
-            return bool(torch.isnan(front).all() and torch.isnan(back).all())
-        return bool((front == self.band).all() and (back == self.band).all())
 
 
 def chunk_ids(rows, n, rng):
