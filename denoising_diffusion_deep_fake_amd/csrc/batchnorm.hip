@@ -101,6 +101,32 @@ __device__ __forceinline__ void block_sum2(double& s1, double& s2) {
   s2 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
 }
 
+// a thread's share of one channel's partial rows (rows tid, tid + 256, ... of [rows][ld / 2][2]), added in that order;
+// the loads of eight rows (then four) are issued in front of their adds -- a C = 16 layer brings 4096 rows to 16
+// workgroups, and with one load in flight per thread the kernel was sixteen dependent L2 round trips long
+__device__ __forceinline__ void column_sum2(const float* __restrict__ col, int rows, long ld, double& s1, double& s2) {
+  int t = threadIdx.x;
+  for (; t + 7 * 256 < rows; t += 8 * 256) {
+    float2 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float2*>(col + (long)(t + j * 256) * ld);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { s1 += (double)v[j].x; s2 += (double)v[j].y; }
+  }
+  for (; t + 3 * 256 < rows; t += 4 * 256) {
+    float2 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const float2*>(col + (long)(t + j * 256) * ld);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { s1 += (double)v[j].x; s2 += (double)v[j].y; }
+  }
+  for (; t < rows; t += 256) {
+    const float2 v = *reinterpret_cast<const float2*>(col + (long)t * ld);
+    s1 += (double)v.x;
+    s2 += (double)v.y;
+  }
+}
+
 __global__ __launch_bounds__(256) void bn_finalize_kernel(
     const float* __restrict__ stats, int tiles, int C, int Cpad, double count,
     const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float momentum,
@@ -114,11 +140,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(
   }
   const int c = blockIdx.x;
   double s1 = 0.0, s2 = 0.0;
-  for (int t = threadIdx.x; t < tiles; t += 256) {
-    const float2 v = *reinterpret_cast<const float2*>(stats + ((long)t * Cpad + c) * 2);
-    s1 += (double)v.x;
-    s2 += (double)v.y;
-  }
+  column_sum2(stats + (long)c * 2, tiles, (long)Cpad * 2, s1, s2);
   block_sum2(s1, s2);
   if (threadIdx.x == 0)
     bn_fwd_coef(s1, s2, count, c, gamma, beta, eps, momentum, true, running_mean, running_var, mean_o, invstd_o, scale_o,
@@ -148,7 +170,11 @@ int bn_eval_coeff_all_launch(const float* params, const float* bnstats, void* ws
   return 0;
 }
 
-template <typename T>
+// out = [relu](y * scale + shift [+ residual]).  RES: 0 no residual, 1 a tensor, 2 another layer's y under its own
+// coefficients.  A thread's vectors are a whole number of tensor rows apart (256 * N % C == 0: bn_layer_apply), so its N
+// channels and their coefficients are loop invariants held in registers; U vectors per trip, every load of a trip in
+// front of its arithmetic.
+template <typename T, int RES>
 __global__ __launch_bounds__(256) void bn_apply_kernel(
     const T* __restrict__ y, const float* __restrict__ scale, const float* __restrict__ shift,
     const T* __restrict__ res, const T* __restrict__ yr, const float* __restrict__ scale_r,
@@ -158,35 +184,52 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(
     net_shift(y, net_ws); net_shift(scale, net_ws); net_shift(shift, net_ws); net_shift(res, net_ws); net_shift(yr, net_ws);
     net_shift(scale_r, net_ws); net_shift(shift_r, net_ws); net_shift(out, net_ws);
   }
-  constexpr int N = V16<T>::N;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-    const int c0 = (int)((i * N) % C);
-    float v[N], sc[N], sf[N];
-    V16<T>::load(y + i * N, v);
+  constexpr int N = V16<T>::N, U = N == 4 ? 4 : 2;  // (bf16: 8 floats per vector; U = 4 takes up to 98 VGPRs here, 5 waves per SIMD with U = 2)
+  const int c0 = ((int)threadIdx.x * N) % C;
+  float sc[N], sf[N], scr[N], sfr[N];
 #pragma unroll
-    for (int k = 0; k < N; k += 4) {
-      const float4 a = *reinterpret_cast<const float4*>(scale + c0 + k);
-      const float4 b = *reinterpret_cast<const float4*>(shift + c0 + k);
-      sc[k] = a.x; sc[k + 1] = a.y; sc[k + 2] = a.z; sc[k + 3] = a.w;
-      sf[k] = b.x; sf[k + 1] = b.y; sf[k + 2] = b.z; sf[k + 3] = b.w;
-    }
+  for (int k = 0; k < N; ++k) {
+    sc[k] = scale[c0 + k];
+    sf[k] = shift[c0 + k];
+    scr[k] = RES == 2 ? scale_r[c0 + k] : 0.f;
+    sfr[k] = RES == 2 ? shift_r[c0 + k] : 0.f;
+  }
+  const T* __restrict__ rsrc = RES == 2 ? yr : res;
+  auto one = [&](float (&v)[N], const float (&r)[N]) {
 #pragma unroll
     for (int k = 0; k < N; ++k) v[k] = v[k] * sc[k] + sf[k];
-    if (res != nullptr) {
-      float r[N];
-      V16<T>::load(res + i * N, r);
+    if constexpr (RES == 1) {
 #pragma unroll
       for (int k = 0; k < N; ++k) v[k] += r[k];
-    } else if (yr != nullptr) {
-      float r[N];
-      V16<T>::load(yr + i * N, r);
+    } else if constexpr (RES == 2) {
 #pragma unroll
-      for (int k = 0; k < N; ++k) v[k] += r[k] * scale_r[c0 + k] + shift_r[c0 + k];
+      for (int k = 0; k < N; ++k) v[k] += r[k] * scr[k] + sfr[k];
     }
     if (relu) {
 #pragma unroll
       for (int k = 0; k < N; ++k) v[k] = fmaxf(v[k], 0.f);
     }
+  };
+  const long stride = (long)gridDim.x * 256;
+  long i = (long)blockIdx.x * 256 + threadIdx.x;
+  for (; i + (U - 1) * stride < nvec; i += U * stride) {
+    float v[U][N], r[U][N];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      V16<T>::load(y + (i + u * stride) * N, v[u]);
+      if constexpr (RES != 0) V16<T>::load(rsrc + (i + u * stride) * N, r[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      one(v[u], r[u]);
+      V16<T>::store(out + (i + u * stride) * N, v[u]);
+    }
+  }
+  for (; i < nvec; i += stride) {
+    float v[N], r[N];
+    V16<T>::load(y + i * N, v);
+    if constexpr (RES != 0) V16<T>::load(rsrc + i * N, r);
+    one(v, r);
     V16<T>::store(out + i * N, v);
   }
 }
@@ -293,20 +336,19 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(
   }
   const int c = blockIdx.x;
   double s1 = 0.0, s2 = 0.0;
-  for (int t = threadIdx.x; t < nblocks; t += 256) {
-    const float2 v = *reinterpret_cast<const float2*>(partial + ((long)t * C + c) * 2);
-    s1 += (double)v.x;
-    s2 += (double)v.y;
-  }
+  column_sum2(partial + (long)c * 2, nblocks, (long)C * 2, s1, s2);
   block_sum2(s1, s2);
   if (threadIdx.x == 0) bn_bwd_coef(s1, s2, count, c, C, gamma, invstd, true, dgamma, dbeta, coef);
 }
 
-template <typename T>
+// MASK: 0 none, 1 recomputed from y, 2 read from a.  DRES: 0 none, 1 written, 2 accumulated.  As bn_apply_kernel: the
+// thread's channels and their seven coefficient vectors are loop invariants, U vectors per trip with every load of a
+// trip in front of its arithmetic.
+template <typename T, int MASK, int DRES>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const T* __restrict__ dA, const T* __restrict__ a, const T* __restrict__ y,
     const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ coef,
-    T* __restrict__ dy, T* __restrict__ dres, int dres_acc, long nvec, int C,
+    T* __restrict__ dy, T* __restrict__ dres, long nvec, int C,
     const float* __restrict__ mask_scale, const float* __restrict__ mask_shift, long net_ws) {
   chain_priority();
   if (blockIdx.z != 0) {  // two networks in one launch (common.h, NetSplit): every operand lives in the workspace
@@ -314,37 +356,72 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     net_shift(coef, net_ws); net_shift(dy, net_ws); net_shift(dres, net_ws); net_shift(mask_scale, net_ws);
     net_shift(mask_shift, net_ws);
   }
-  constexpr int N = V16<T>::N;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-    const int c0 = (int)((i * N) % C);
-    float g[N], yy[N], o[N];
-    V16<T>::load(dA + i * N, g);
-    V16<T>::load(y + i * N, yy);
-    if (mask_scale != nullptr) {
+  constexpr int N = V16<T>::N, U = N == 4 ? 4 : 2;  // (bf16: 8 floats per vector: U = 2 already takes 127-202 VGPRs, 2-4 waves per SIMD -- 101 MB in 20 us all the same; U = 4: 160-236)
+  const int c0 = ((int)threadIdx.x * N) % C;
+  float mu[N], is[N], k0[N], k1[N], k2[N], msc[N], msf[N];
 #pragma unroll
-      for (int k = 0; k < N; ++k) g[k] = (yy[k] * mask_scale[c0 + k] + mask_shift[c0 + k]) > 0.f ? g[k] : 0.f;
-    } else if (a != nullptr) {
-      float aa[N];
-      V16<T>::load(a + i * N, aa);
+  for (int k = 0; k < N; ++k) {
+    const int c = c0 + k;
+    mu[k] = mean[c];
+    is[k] = invstd[c];
+    k0[k] = coef[c];
+    k1[k] = coef[C + c];
+    k2[k] = coef[2 * C + c];
+    msc[k] = MASK == 1 ? mask_scale[c] : 0.f;
+    msf[k] = MASK == 1 ? mask_shift[c] : 0.f;
+  }
+  auto one = [&](float (&g)[N], const float (&yy)[N], const float (&aa)[N], float (&o)[N]) {
+    if constexpr (MASK == 1) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) g[k] = (yy[k] * msc[k] + msf[k]) > 0.f ? g[k] : 0.f;
+    } else if constexpr (MASK == 2) {
 #pragma unroll
       for (int k = 0; k < N; ++k) g[k] = aa[k] > 0.f ? g[k] : 0.f;
     }
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-      const int c = c0 + k;
-      const float xhat = (yy[k] - mean[c]) * invstd[c];
-      o[k] = coef[c] * (g[k] - coef[C + c] - xhat * coef[2 * C + c]);
+      const float xhat = (yy[k] - mu[k]) * is[k];
+      o[k] = k0[k] * (g[k] - k1[k] - xhat * k2[k]);
     }
-    V16<T>::store(dy + i * N, o);
-    if (dres != nullptr) {
-      if (dres_acc) {
-        float d[N];
-        V16<T>::load(dres + i * N, d);
+  };
+  const long stride = (long)gridDim.x * 256;
+  long i = (long)blockIdx.x * 256 + threadIdx.x;
+  for (; i + (U - 1) * stride < nvec; i += U * stride) {
+    float g[U][N], yy[U][N], aa[U][N], d[U][N];
 #pragma unroll
-        for (int k = 0; k < N; ++k) g[k] += d[k];
-      }
-      V16<T>::store(dres + i * N, g);
+    for (int u = 0; u < U; ++u) {
+      const long e = (i + u * stride) * N;
+      V16<T>::load(dA + e, g[u]);
+      V16<T>::load(y + e, yy[u]);
+      if constexpr (MASK == 2) V16<T>::load(a + e, aa[u]);
+      if constexpr (DRES == 2) V16<T>::load(dres + e, d[u]);
     }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long e = (i + u * stride) * N;
+      float o[N];
+      one(g[u], yy[u], aa[u], o);
+      V16<T>::store(dy + e, o);
+      if constexpr (DRES == 2) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) g[u][k] += d[u][k];
+      }
+      if constexpr (DRES != 0) V16<T>::store(dres + e, g[u]);
+    }
+  }
+  for (; i < nvec; i += stride) {
+    float g[N], yy[N], aa[N], d[N], o[N];
+    V16<T>::load(dA + i * N, g);
+    V16<T>::load(y + i * N, yy);
+    if constexpr (MASK == 2) V16<T>::load(a + i * N, aa);
+    if constexpr (DRES == 2) V16<T>::load(dres + i * N, d);
+    one(g, yy, aa, o);
+    V16<T>::store(dy + i * N, o);
+    if constexpr (DRES == 2) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) g[k] += d[k];
+    }
+    if constexpr (DRES != 0) V16<T>::store(dres + i * N, g);
   }
 }
 
@@ -748,9 +825,14 @@ int bn_layer_apply(const BnLayer& L, const BnBufs& b, hipStream_t stream, const 
   const BnResidualOps r = residual_ops(L, b);
   by_dtype(L.dtype, [&](auto* typed) {
     typedef std::remove_pointer_t<decltype(typed)> T;
-    hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(grid_for(nvec), 1, nv.nets), dim3(256), 0, stream, (const T*)b.y,
-                       bn_coef(b.coef, L.C, BN_SCALE), bn_coef(b.coef, L.C, BN_SHIFT), (const T*)r.res, (const T*)r.yr,
-                       r.scale_r, r.shift_r, L.relu ? 1 : 0, (T*)b.a, nvec, L.C, nv.ws);
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(grid_for(nvec), 1, nv.nets), dim3(256), 0, stream, (const T*)b.y,
+                         bn_coef(b.coef, L.C, BN_SCALE), bn_coef(b.coef, L.C, BN_SHIFT), (const T*)r.res, (const T*)r.yr,
+                         r.scale_r, r.shift_r, L.relu ? 1 : 0, (T*)b.a, nvec, L.C, nv.ws);
+    };
+    if (r.res != nullptr) go(bn_apply_kernel<T, 1>);  // (the order the kernel used to test the two pointers in)
+    else if (r.yr != nullptr) go(bn_apply_kernel<T, 2>);
+    else go(bn_apply_kernel<T, 0>);
   });
   D3F_HIP(hipGetLastError());
   return 0;
@@ -806,9 +888,22 @@ int bn_layer_backward(const BnLayer& L, const BnBufs& b, const BnSync* sync, hip
   if (nvec == 0) return 0;
   by_dtype(L.dtype, [&](auto* typed) {
     typedef std::remove_pointer_t<decltype(typed)> T;
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(grid_for(nvec), 1, nv.nets), dim3(256), 0, stream, (const T*)b.dA,
-                       (const T*)o.a, (const T*)b.y, o.mean, o.invstd, o.k, (T*)b.dy, (T*)b.dres, b.dres_acc, nvec, C,
-                       o.mask_scale, o.mask_shift, nv.ws);
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(grid_for(nvec), 1, nv.nets), dim3(256), 0, stream, (const T*)b.dA, (const T*)o.a,
+                         (const T*)b.y, o.mean, o.invstd, o.k, (T*)b.dy, (T*)b.dres, nvec, C, o.mask_scale, o.mask_shift,
+                         nv.ws);
+    };
+    const int mask = o.mask_scale != nullptr ? 1 : (o.a != nullptr ? 2 : 0);
+    const int dres = b.dres == nullptr ? 0 : (b.dres_acc ? 2 : 1);
+    auto by_dres = [&](auto m) {
+      constexpr int M = decltype(m)::value;
+      if (dres == 0) go(bn_bwd_apply_kernel<T, M, 0>);
+      else if (dres == 1) go(bn_bwd_apply_kernel<T, M, 1>);
+      else go(bn_bwd_apply_kernel<T, M, 2>);
+    };
+    if (mask == 0) by_dres(std::integral_constant<int, 0>());
+    else if (mask == 1) by_dres(std::integral_constant<int, 1>());
+    else by_dres(std::integral_constant<int, 2>());
   });
   D3F_HIP(hipGetLastError());
   return 0;

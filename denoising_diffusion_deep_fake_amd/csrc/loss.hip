@@ -21,10 +21,12 @@ constexpr int SS_T = 32;            // tile edge (outputs)
 constexpr int SS_K = 11;            // window
 constexpr int SS_IN = SS_T + SS_K - 1;  // 42
 constexpr int SS_LD = SS_IN + 1;        // 43: odd stride -> conflict-free column walks
+constexpr int SS_FILL = (SS_IN * SS_IN + 255) / 256;  // 7: elements of the input tile per thread
 
 struct GaussK {
   float g[SS_K];
 };
+typedef float f32x2 __attribute__((ext_vector_type(2)));  // a register pair for the packed fp32 instructions
 
 static GaussK make_gauss() {
   GaussK k;
@@ -60,51 +62,69 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
   const float* __restrict__ px = pred + (long)plane * H * W;
   const float* __restrict__ py = target + (long)plane * H * W;
   const int tid = threadIdx.x;
-  for (int e = tid; e < SS_IN * SS_IN; e += 256) {
-    const int r = e / SS_IN, c = e - r * SS_IN;
-    const int iy = oy0 + r, ix = ox0 + c;
-    float a = 0.f, b = 0.f;
-    if (iy < H && ix < W) {
-      a = norm01(px[(long)iy * W + ix], lo, range);
-      b = norm01(py[(long)iy * W + ix], lo, range);
+  // the tile's seven elements per thread are all loaded (branch-free, from a clamped address) before the first is used:
+  // as a rolled load -> normalise -> store loop the fill was seven dependent memory round trips per workgroup, at three
+  // workgroups per CU
+  {
+    float ra[SS_FILL], rb[SS_FILL];
+#pragma unroll
+    for (int k = 0; k < SS_FILL; ++k) {
+      const int e = tid + k * 256, r = e / SS_IN, c = e - r * SS_IN;
+      const int iy = oy0 + r, ix = ox0 + c;
+      const long off = (e < SS_IN * SS_IN && iy < H && ix < W) ? (long)iy * W + ix : 0;
+      ra[k] = px[off];
+      rb[k] = py[off];
     }
-    tx[r * SS_LD + c] = a;
-    ty[r * SS_LD + c] = b;
+#pragma unroll
+    for (int k = 0; k < SS_FILL; ++k) {
+      const int e = tid + k * 256, r = e / SS_IN, c = e - r * SS_IN;
+      const int iy = oy0 + r, ix = ox0 + c;
+      if (e < SS_IN * SS_IN) {
+        const bool in = iy < H && ix < W;
+        tx[r * SS_LD + c] = in ? norm01(ra[k], lo, range) : 0.f;
+        ty[r * SS_LD + c] = in ? norm01(rb[k], lo, range) : 0.f;
+      }
+    }
   }
   __syncthreads();
   // filter along H (piqa filters dim -2 first): vv[q][r][c], r < 32 output rows, c < 42 columns.  Register-blocked:
   // a thread owns column c and 8 consecutive output rows, reads its 18 input rows ONCE (the products a*a, b*b, a*b
   // are formed once per input instead of once per tap) -- 36 LDS reads instead of 176; every output is still summed
   // over the taps in the order i = 0 .. 10.
+  // The taps run as packed fp32 pairs (v_pk_mul_f32 + v_pk_add_f32, two IEEE operations per instruction: the same
+  // products and sums, rounded the same way, as the scalar form -- never a fused multiply-add): (x, y) and (x^2, y^2)
+  // of one row pair up, xy pairs up across two neighbouring output rows.
   constexpr int RB = 8;
   if (tid < SS_IN * (SS_T / RB)) {
     const int c = tid % SS_IN, r0 = (tid / SS_IN) * RB;
-    float a[RB + SS_K - 1], b[RB + SS_K - 1], aa[RB + SS_K - 1], bb[RB + SS_K - 1], ab[RB + SS_K - 1];
+    f32x2 xy[RB + SS_K - 1], sq[RB + SS_K - 1];
+    float ab[RB + SS_K - 1];
 #pragma unroll
     for (int i = 0; i < RB + SS_K - 1; ++i) {
-      a[i] = tx[(r0 + i) * SS_LD + c];
-      b[i] = ty[(r0 + i) * SS_LD + c];
-      aa[i] = a[i] * a[i];
-      bb[i] = b[i] * b[i];
-      ab[i] = a[i] * b[i];
+      xy[i] = f32x2{tx[(r0 + i) * SS_LD + c], ty[(r0 + i) * SS_LD + c]};
+      sq[i] = xy[i] * xy[i];
+      ab[i] = xy[i].x * xy[i].y;
     }
 #pragma unroll
-    for (int r = 0; r < RB; ++r) {
-      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
+    for (int r = 0; r < RB; r += 2) {
+      f32x2 s01[2] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}}, s23[2] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}}, s4 = f32x2{0.f, 0.f};
 #pragma unroll
       for (int i = 0; i < SS_K; ++i) {
-        const float g = gk.g[i];
-        s0 += g * a[r + i];
-        s1 += g * b[r + i];
-        s2 += g * aa[r + i];
-        s3 += g * bb[r + i];
-        s4 += g * ab[r + i];
+        const f32x2 g = f32x2{gk.g[i], gk.g[i]};
+        s01[0] += g * xy[r + i];
+        s23[0] += g * sq[r + i];
+        s01[1] += g * xy[r + 1 + i];
+        s23[1] += g * sq[r + 1 + i];
+        s4 += g * f32x2{ab[r + i], ab[r + 1 + i]};
       }
-      vv[0][(r0 + r) * SS_LD + c] = s0;
-      vv[1][(r0 + r) * SS_LD + c] = s1;
-      vv[2][(r0 + r) * SS_LD + c] = s2;
-      vv[3][(r0 + r) * SS_LD + c] = s3;
-      vv[4][(r0 + r) * SS_LD + c] = s4;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        vv[0][(r0 + r + e) * SS_LD + c] = s01[e].x;
+        vv[1][(r0 + r + e) * SS_LD + c] = s01[e].y;
+        vv[2][(r0 + r + e) * SS_LD + c] = s23[e].x;
+        vv[3][(r0 + r + e) * SS_LD + c] = s23[e].y;
+        vv[4][(r0 + r + e) * SS_LD + c] = e ? s4.y : s4.x;
+      }
     }
   }
   __syncthreads();
@@ -114,24 +134,39 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
   // instead of 44)
   constexpr int CBk = 4;
   const int rr = tid / (SS_T / CBk), cq = (tid % (SS_T / CBk)) * CBk;
-  float win[5][CBk + SS_K - 1];
+  f32x2 w01[CBk + SS_K - 1], w23[CBk + SS_K - 1];
+  float w4[CBk + SS_K - 1];
 #pragma unroll
-  for (int q = 0; q < 5; ++q)
+  for (int j = 0; j < CBk + SS_K - 1; ++j) {
+    w01[j] = f32x2{vv[0][rr * SS_LD + cq + j], vv[1][rr * SS_LD + cq + j]};
+    w23[j] = f32x2{vv[2][rr * SS_LD + cq + j], vv[3][rr * SS_LD + cq + j]};
+    w4[j] = vv[4][rr * SS_LD + cq + j];
+  }
+  float mm[CBk][5];  // (packed like the column pass; the fifth map pairs up across two neighbouring columns)
 #pragma unroll
-    for (int j = 0; j < CBk + SS_K - 1; ++j) win[q][j] = vv[q][rr * SS_LD + cq + j];
+  for (int cc = 0; cc < CBk; cc += 2) {
+    f32x2 s01[2] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}}, s23[2] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}}, s4 = f32x2{0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < SS_K; ++j) {
+      const f32x2 g = f32x2{gk.g[j], gk.g[j]};
+      s01[0] += g * w01[cc + j];
+      s23[0] += g * w23[cc + j];
+      s01[1] += g * w01[cc + 1 + j];
+      s23[1] += g * w23[cc + 1 + j];
+      s4 += g * f32x2{w4[cc + j], w4[cc + 1 + j]};
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      mm[cc + e][0] = s01[e].x; mm[cc + e][1] = s01[e].y; mm[cc + e][2] = s23[e].x; mm[cc + e][3] = s23[e].y;
+      mm[cc + e][4] = e ? s4.y : s4.x;
+    }
+  }
 #pragma unroll
   for (int cc = 0; cc < CBk; ++cc) {
     const int r = rr, c = cq + cc;
     const int oy = oy0 + r, ox = ox0 + c;
     if (oy >= Hv || ox >= Wv) continue;
-    float m[5];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < SS_K; ++j) s += gk.g[j] * win[q][cc + j];
-      m[q] = s;
-    }
+    const float (&m)[5] = mm[cc];
     const float mux = m[0], muy = m[1];
     const float sxx = m[2] - mux * mux, syy = m[3] - muy * muy, sxy = m[4] - mux * muy;
     const float a1 = 2.f * mux * muy + c1, b1 = mux * mux + muy * muy + c1;
@@ -169,19 +204,41 @@ __global__ __launch_bounds__(256) void ssim_mse_bwd_kernel(
   const int py0 = blockIdx.y * SS_T, px0 = blockIdx.x * SS_T;
   const int tid = threadIdx.x;
   // derivative maps at outputs o = p - k, k in [0,10]: tile origin (py0-10, px0-10)
-  for (int e = tid; e < SS_IN * SS_IN; e += 256) {
-    const int r = e / SS_IN, c = e - r * SS_IN;
-    const int oy = py0 - (SS_K - 1) + r, ox = px0 - (SS_K - 1) + c;
-    float a = 0.f, b = 0.f, d = 0.f;
-    if (oy >= 0 && oy < Hv && ox >= 0 && ox < Wv) {
-      const long o = ((long)plane * Hv + oy) * Wv + ox;
-      a = dA[o];
-      b = dB[o];
-      d = dC[o];
+  // (all loads of the fill before its first LDS store, as in ssim_fwd_kernel; and the four pixels this thread finishes
+  // are fetched here too, so that they travel during the two filter passes)
+  constexpr int CBk = 4;  // row r, 4 consecutive columns per thread
+  const int rr = tid / (SS_T / CBk), cq = (tid % (SS_T / CBk)) * CBk;
+  float pv4[CBk], tv4[CBk];
+  {
+    float ra[SS_FILL], rb[SS_FILL], rd[SS_FILL];
+#pragma unroll
+    for (int k = 0; k < SS_FILL; ++k) {
+      const int e = tid + k * 256, r = e / SS_IN, c = e - r * SS_IN;
+      const int oy = py0 - (SS_K - 1) + r, ox = px0 - (SS_K - 1) + c;
+      const bool in = e < SS_IN * SS_IN && oy >= 0 && oy < Hv && ox >= 0 && ox < Wv;
+      const long o = (long)plane * Hv * Wv + (in ? (long)oy * Wv + ox : 0);
+      ra[k] = dA[o];
+      rb[k] = dB[o];
+      rd[k] = dC[o];
     }
-    t3[0][r * SS_LD + c] = a;
-    t3[1][r * SS_LD + c] = b;
-    t3[2][r * SS_LD + c] = d;
+#pragma unroll
+    for (int cc = 0; cc < CBk; ++cc) {
+      const int iy = py0 + rr, ix = px0 + cq + cc;
+      const long p = (long)plane * H * W + ((iy < H && ix < W) ? (long)iy * W + ix : 0);
+      pv4[cc] = pred[p];
+      tv4[cc] = target[p];
+    }
+#pragma unroll
+    for (int k = 0; k < SS_FILL; ++k) {
+      const int e = tid + k * 256, r = e / SS_IN, c = e - r * SS_IN;
+      const int oy = py0 - (SS_K - 1) + r, ox = px0 - (SS_K - 1) + c;
+      if (e < SS_IN * SS_IN) {
+        const bool in = oy >= 0 && oy < Hv && ox >= 0 && ox < Wv;
+        t3[0][r * SS_LD + c] = in ? ra[k] : 0.f;
+        t3[1][r * SS_LD + c] = in ? rb[k] : 0.f;
+        t3[2][r * SS_LD + c] = in ? rd[k] : 0.f;
+      }
+    }
   }
   __syncthreads();
   // adjoint filter: G(p) = sum_k g[k] * D[p - k] = sum_i g[10 - i] * tile[r + i]; register-blocked like the forward
@@ -189,53 +246,65 @@ __global__ __launch_bounds__(256) void ssim_mse_bwd_kernel(
   constexpr int RB = 8;
   if (tid < SS_IN * (SS_T / RB)) {
     const int c = tid % SS_IN, r0 = (tid / SS_IN) * RB;
-    float v0[RB + SS_K - 1], v1[RB + SS_K - 1], v2[RB + SS_K - 1];
+    f32x2 v01[RB + SS_K - 1];  // (packed pairs as in ssim_fwd_kernel: maps 0 and 1 of a row, map 2 of two rows)
+    float v2[RB + SS_K - 1];
 #pragma unroll
     for (int i = 0; i < RB + SS_K - 1; ++i) {
-      v0[i] = t3[0][(r0 + i) * SS_LD + c];
-      v1[i] = t3[1][(r0 + i) * SS_LD + c];
+      v01[i] = f32x2{t3[0][(r0 + i) * SS_LD + c], t3[1][(r0 + i) * SS_LD + c]};
       v2[i] = t3[2][(r0 + i) * SS_LD + c];
     }
 #pragma unroll
-    for (int r = 0; r < RB; ++r) {
-      float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int r = 0; r < RB; r += 2) {
+      f32x2 s01[2] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}}, s2 = f32x2{0.f, 0.f};
 #pragma unroll
       for (int i = 0; i < SS_K; ++i) {
-        const float g = gk.g[SS_K - 1 - i];
-        s0 += g * v0[r + i];
-        s1 += g * v1[r + i];
-        s2 += g * v2[r + i];
+        const f32x2 g = f32x2{gk.g[SS_K - 1 - i], gk.g[SS_K - 1 - i]};
+        s01[0] += g * v01[r + i];
+        s01[1] += g * v01[r + 1 + i];
+        s2 += g * f32x2{v2[r + i], v2[r + 1 + i]};
       }
-      vv[0][(r0 + r) * SS_LD + c] = s0;
-      vv[1][(r0 + r) * SS_LD + c] = s1;
-      vv[2][(r0 + r) * SS_LD + c] = s2;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        vv[0][(r0 + r + e) * SS_LD + c] = s01[e].x;
+        vv[1][(r0 + r + e) * SS_LD + c] = s01[e].y;
+        vv[2][(r0 + r + e) * SS_LD + c] = e ? s2.y : s2.x;
+      }
     }
   }
   __syncthreads();
   const float inv_range = 1.f / range;
   float local = 0.f;
-  constexpr int CBk = 4;  // row r, 4 consecutive columns per thread
-  const int rr = tid / (SS_T / CBk), cq = (tid % (SS_T / CBk)) * CBk;
-  float win[3][CBk + SS_K - 1];
+  f32x2 w01[CBk + SS_K - 1];
+  float w2[CBk + SS_K - 1];
 #pragma unroll
-  for (int q = 0; q < 3; ++q)
+  for (int j = 0; j < CBk + SS_K - 1; ++j) {
+    w01[j] = f32x2{vv[0][rr * SS_LD + cq + j], vv[1][rr * SS_LD + cq + j]};
+    w2[j] = vv[2][rr * SS_LD + cq + j];
+  }
+  float gg[CBk][3];
 #pragma unroll
-    for (int j = 0; j < CBk + SS_K - 1; ++j) win[q][j] = vv[q][rr * SS_LD + cq + j];
+  for (int cc = 0; cc < CBk; cc += 2) {
+    f32x2 s01[2] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}}, s2 = f32x2{0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < SS_K; ++j) {
+      const f32x2 g = f32x2{gk.g[SS_K - 1 - j], gk.g[SS_K - 1 - j]};
+      s01[0] += g * w01[cc + j];
+      s01[1] += g * w01[cc + 1 + j];
+      s2 += g * f32x2{w2[cc + j], w2[cc + 1 + j]};
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      gg[cc + e][0] = s01[e].x; gg[cc + e][1] = s01[e].y; gg[cc + e][2] = e ? s2.y : s2.x;
+    }
+  }
 #pragma unroll
   for (int cc = 0; cc < CBk; ++cc) {
     const int r = rr, c = cq + cc;
     const int iy = py0 + r, ix = px0 + c;
     if (iy >= H || ix >= W) continue;
-    float ga = 0.f, gb = 0.f, gc = 0.f;
-#pragma unroll
-    for (int j = 0; j < SS_K; ++j) {
-      const float g = gk.g[SS_K - 1 - j];
-      ga += g * win[0][cc + j];
-      gb += g * win[1][cc + j];
-      gc += g * win[2][cc + j];
-    }
+    const float ga = gg[cc][0], gb = gg[cc][1], gc = gg[cc][2];
     const long p = (long)plane * H * W + (long)iy * W + ix;
-    const float pv = pred[p], tv = target[p];
+    const float pv = pv4[cc], tv = tv4[cc];
     const float rawx = (pv - lo) / range;
     const float xh = fminf(fmaxf(rawx, 0.f), 1.f);
     const float yh = norm01(tv, lo, range);
@@ -260,9 +329,19 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
                                                             double n_elems, float* __restrict__ out) {
   chain_priority();
   __shared__ double red[2][256];
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < n_ss; i += 256) a += (double)part_ss[i];
-  for (int i = threadIdx.x; i < n_mse; i += 256) b += (double)part_mse[i];
+  // a thread adds elements tid, tid + 256, ... in that order; four loads are issued in front of their adds (one block
+  // walks 3072 + 3072 partials at the headline shape: twelve dependent round trips per array otherwise)
+  auto strided_sum = [](const float* __restrict__ p, int n) {
+    double s = 0.0;
+    int i = threadIdx.x;
+    for (; i + 3 * 256 < n; i += 4 * 256) {
+      const float v0 = p[i], v1 = p[i + 256], v2 = p[i + 512], v3 = p[i + 768];
+      s += (double)v0; s += (double)v1; s += (double)v2; s += (double)v3;
+    }
+    for (; i < n; i += 256) s += (double)p[i];
+    return s;
+  };
+  const double a = strided_sum(part_ss, n_ss), b = strided_sum(part_mse, n_mse);
   red[0][threadIdx.x] = a;
   red[1][threadIdx.x] = b;
   __syncthreads();

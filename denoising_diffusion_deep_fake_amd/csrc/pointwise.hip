@@ -10,6 +10,8 @@
 #include "philox.h"
 #include "vec16.h"
 
+#include <type_traits>
+
 namespace d3f {
 
 // ------------------------------------------------------------------------------------------
@@ -64,14 +66,21 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
   }
 }
 
-// grid = (blocks over one input row's W * C/N vectors, B * H rows): the row (b, iy) -- and with it which filter rows
-// reach it -- is block-uniform, the column decode is one multiply-high; the argmax bytes of a vector are one load.
+// grid = (blocks over one input row's W * C/N vectors, blocks of MPB_PAIRS row pairs): the column decode is one
+// multiply-high; the argmax bytes of a vector are one load.
 // (r03: the first form decoded a flat index with four 64-bit divisions and walked all 9 taps under branches: ~600
 // vector instructions per 16 bytes written -- the pass was ALU-bound at 2.6 TB/s.)
-template <typename T>
+// A thread owns its column of MPB_PAIRS pairs of input rows (2m, 2m + 1).  Window row oy covers input rows 2*oy-1 ..
+// 2*oy+1, so the even row lies in window row m alone (as its filter row 1) and the odd row in window rows m + 1 (filter
+// row 0) and m (filter row 2): the pair needs the two window rows m, m + 1 once, where one row per thread fetched three.
+// The same holds for columns: candidates ox0 = (ix + 1) / 2 and, for odd ix, ox0 - 1 with filter column 2.  Every
+// candidate is loaded from a clamped (always valid) address in front of all arithmetic and enters under a select, in
+// the order the taps have always been added: window row m + 1 before m, column ox0 before ox0 - 1.
+constexpr int MPB_PAIRS = 2;
+template <typename T, bool ACC>
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ dout,
                                                           const uint8_t* __restrict__ idx,
-                                                          T* __restrict__ din, int accumulate, int B,
+                                                          T* __restrict__ din, int npairs,
                                                           int H, int W, int C, unsigned vc_mul, unsigned vc_shr,
                                                           long net_ws) {
   chain_priority();
@@ -83,50 +92,69 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
   const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;  // (ix, cv) in the row
   if (j >= W * VC) return;
   const int ix = fast_div(j, vc_mul, vc_shr), cv = j - ix * VC;
-  const int row = (int)blockIdx.y;  // b * H + iy
-  const int iy = row % H, b = row / H;  // (scalar: block-uniform)
-  // windows containing (iy, ix): window oy covers rows 2*oy-1 .. 2*oy+1 -> an odd row lies in two windows (as their
-  // filter row 0 / 2), an even row in one (filter row 1); the same for columns
-  const int noy = (iy & 1) ? 2 : 1, nox = (ix & 1) ? 2 : 1;
-  const int oy0 = (iy + 1) >> 1, kh0 = (iy & 1) ? 0 : 1;  // second candidate: oy0 - 1 with filter row 2
-  const int ox0 = (ix + 1) >> 1, kw0 = (ix & 1) ? 0 : 1;
-  float g[N];
+  const int ox0 = (ix + 1) >> 1;
+  const bool okc[2] = {ox0 < Wo, (ix & 1) != 0};
+  const int oxc[2] = {ox0 < Wo ? ox0 : Wo - 1, ox0 > 0 ? ox0 - 1 : 0};
+  const unsigned kwc[2] = {(ix & 1) ? 0u : 1u, 2u};
+  float d[MPB_PAIRS][2][2][N], old[MPB_PAIRS][2][N];  // [pair][window row m, m + 1][candidate column]
+  uint32_t w[MPB_PAIRS][2][2][N / 4];
+  bool next[MPB_PAIRS];
 #pragma unroll
-  for (int k = 0; k < N; ++k) g[k] = 0.f;
+  for (int u = 0; u < MPB_PAIRS; ++u) {
+    int p = (int)blockIdx.y * MPB_PAIRS + u;  // b * Ho + m  (block-uniform)
+    if (p >= npairs) p = npairs - 1;          // (loaded again, not stored)
+    next[u] = p % Ho + 1 < Ho;
 #pragma unroll
-  for (int a = 0; a < 2; ++a) {
-    const int oy = oy0 - a, kh = a ? 2 : kh0;
-    if (a >= noy || oy >= Ho) continue;  // (block-uniform)
+    for (int a = 0; a < 2; ++a) {
+      const long prow = a && next[u] ? p + 1 : p;
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int ox = ox0 - c, kw = c ? 2 : kw0;
-      if (c < nox && ox < Wo) {
-        const long o = (((long)b * Ho + oy) * Wo + ox) * C + cv * N;
-        float d[N];
-        V16<T>::load(dout + o, d);
-        const unsigned tap = (unsigned)(kh * 3 + kw);
-        uint32_t w[N / 4];
+      for (int c = 0; c < 2; ++c) {
+        const long o = (prow * Wo + oxc[c]) * C + cv * N;
+        V16<T>::load(dout + o, d[u][a][c]);
         if constexpr (N == 4) {
-          w[0] = *reinterpret_cast<const uint32_t*>(idx + o);
+          w[u][a][c][0] = *reinterpret_cast<const uint32_t*>(idx + o);
         } else {
           const uint2 t = *reinterpret_cast<const uint2*>(idx + o);
-          w[0] = t.x;
-          w[1] = t.y;
+          w[u][a][c][0] = t.x;
+          w[u][a][c][1] = t.y;
         }
-#pragma unroll
-        for (int k = 0; k < N; ++k)
-          if (((w[k >> 2] >> (8 * (k & 3))) & 0xffu) == tap) g[k] += d[k];
       }
     }
-  }
-  T* dst = din + ((long)row * W * VC + j) * N;
-  if (accumulate) {
-    float old[N];
-    V16<T>::load(dst, old);
+    if constexpr (ACC) {
 #pragma unroll
-    for (int k = 0; k < N; ++k) g[k] += old[k];
+      for (int e = 0; e < 2; ++e) V16<T>::load(din + ((2L * p + e) * W * VC + j) * N, old[u][e]);
+    }
   }
-  V16<T>::store(dst, g);
+#pragma unroll
+  for (int u = 0; u < MPB_PAIRS; ++u) {
+    const int p = (int)blockIdx.y * MPB_PAIRS + u;
+    if (p >= npairs) break;
+    float g[2][N];  // the even row, the odd row
+#pragma unroll
+    for (int k = 0; k < N; ++k) g[0][k] = g[1][k] = 0.f;
+    auto add = [&](float (&gr)[N], int a, unsigned kh, bool row_ok) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const unsigned tap = kh * 3 + kwc[c];
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          const bool hit = row_ok && okc[c] && ((w[u][a][c][k >> 2] >> (8 * (k & 3))) & 0xffu) == tap;
+          gr[k] = hit ? gr[k] + d[u][a][c][k] : gr[k];
+        }
+      }
+    };
+    add(g[0], 0, 1, true);
+    add(g[1], 1, 0, next[u]);
+    add(g[1], 0, 2, true);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      if constexpr (ACC) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) g[e][k] += old[u][e][k];
+      }
+      V16<T>::store(din + ((2L * p + e) * W * VC + j) * N, g[e]);
+    }
+  }
 }
 
 int maxpool3x3s2_fwd_launch(int dtype, const void* in, void* out, uint8_t* idx, int B, int H, int W,
@@ -158,13 +186,20 @@ int maxpool3x3s2_bwd_launch(int dtype, const void* dout, const uint8_t* idx, voi
   unsigned vc_mul, vc_shr;
   fast_div_setup((unsigned)vc, &vc_mul, &vc_shr);
   D3F_CHECK((long)B * H <= 65535, "maxpool backward: %d rows exceed the grid", B * H);
-  const dim3 grid((unsigned)cdiv((long)W * vc, 256), (unsigned)(B * H), (unsigned)nv.nets);
-  if (dtype == D3F_F32)
-    hipLaunchKernelGGL(maxpool_bwd_kernel<float>, grid, dim3(256), 0, stream,
-                       (const float*)dout, idx, (float*)din, accumulate, B, H, W, C, vc_mul, vc_shr, nv.ws);
-  else
-    hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, grid, dim3(256), 0, stream,
-                       (const bf16_t*)dout, idx, (bf16_t*)din, accumulate, B, H, W, C, vc_mul, vc_shr, nv.ws);
+  const int npairs = B * (H / 2);
+  const dim3 grid((unsigned)cdiv((long)W * vc, 256), (unsigned)cdiv(npairs, MPB_PAIRS), (unsigned)nv.nets);
+  auto go = [&](auto kernel, auto* typed) {
+    typedef std::remove_pointer_t<decltype(typed)> T;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (const T*)dout, idx, (T*)din, npairs, H, W, C, vc_mul, vc_shr,
+                       nv.ws);
+  };
+  if (dtype == D3F_F32) {
+    if (accumulate) go(maxpool_bwd_kernel<float, true>, (float*)nullptr);
+    else go(maxpool_bwd_kernel<float, false>, (float*)nullptr);
+  } else {
+    if (accumulate) go(maxpool_bwd_kernel<bf16_t, true>, (bf16_t*)nullptr);
+    else go(maxpool_bwd_kernel<bf16_t, false>, (bf16_t*)nullptr);
+  }
   D3F_HIP(hipGetLastError());
   return 0;
 }
@@ -233,6 +268,18 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
     net_shift(in, net_in); net_shift(out, net_ws);
   }
   const long total = (long)B * HW;
+  constexpr int N = V16<T>::N;
+  if (Cpad == N && C <= N && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+    // the stem's case (3 channels padded to one vector): a pixel is ONE 16-byte store, not Cpad stores 16 bytes apart
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+      const long b = i / HW, pix = i - b * HW;
+      alignas(16) T px[N];
+#pragma unroll
+      for (int c = 0; c < N; ++c) px[c] = from_f32<T>(c < C ? in[(b * C + c) * HW + pix] : 0.f);
+      *reinterpret_cast<uint4*>(out + i * N) = *reinterpret_cast<const uint4*>(px);
+    }
+    return;
+  }
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long b = i / HW, pix = i - b * HW;
     for (int c = 0; c < Cpad; ++c) {
@@ -653,12 +700,25 @@ __global__ __launch_bounds__(256) void pack_all_kernel(const float* __restrict__
   // alone for 265 MB)
   const unsigned tmul = e.taps_mul, tshr = e.taps_shr, lgct = e.ct_log2;
   // ---- load: contiguous runs of the torch layout, zero outside the real filter ----
-  for (int i = threadIdx.x; i < PACK_NT * run; i += 256) {
-    const int nl = fast_div(i >> lgct, tmul, tshr), r = i - nl * run;
-    const int n = n0 + nl, c = c0 + fast_div(r, tmul, tshr);
-    float v = 0.f;
-    if (n < Cout && c < CinReal) v = w[(unsigned)((n * CinReal + c0) * taps + r)];
-    tile[nl * stride + r] = v;
+  // (eight loads per thread are issued before the first LDS store: the stem's entry runs as two workgroups on the
+  // caller's stream, and 25 load -> store rounds of one element each were 25 dependent memory round trips)
+  constexpr int LU = 8;
+  for (int i0 = threadIdx.x; i0 < PACK_NT * run; i0 += 256 * LU) {
+    float v[LU];
+    int dst[LU];
+#pragma unroll
+    for (int u = 0; u < LU; ++u) {
+      const int i = i0 + u * 256;
+      const int nl = fast_div(i >> lgct, tmul, tshr), r = i - nl * run;
+      const int n = n0 + nl, c = c0 + fast_div(r, tmul, tshr);
+      dst[u] = i < PACK_NT * run ? nl * stride + r : -1;
+      const bool real = dst[u] >= 0 && n < Cout && c < CinReal;
+      const float x = w[real ? (unsigned)((n * CinReal + c0) * taps + r) : 0u];  // (branch-free: element 0 stands in)
+      v[u] = real ? x : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < LU; ++u)
+      if (dst[u] >= 0) tile[dst[u]] = v[u];
   }
   __syncthreads();
   // ---- forward layout wf[n][tap*Cin + c] ----
