@@ -105,6 +105,8 @@ PROTOTYPES = {
     "d3f_l1_per_image_workspace_bytes": (_sz, [_i]),
     "d3f_l1_per_image": (_i, [_p, _p, _p, _p, _i, _i64, _p]),
     "d3f_l1_per_image_scatter": (_i, [_p, _p, _p, _p, _i, _p, _i, _i64, _p]),
+    "d3f_quality_per_image_workspace_bytes": (_sz, [_i, _i, _i]),
+    "d3f_quality_per_image_scatter": (_i, [_p, _p, _f, _f, _p, _p, _i, _p, _i, _i, _i, _p]),
     "d3f_difficulty_classes_workspace_bytes": (_sz, [_i]),
     "d3f_difficulty_classes": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),
     "d3f_difficulty_histogram_u8_workspace_bytes": (_sz, [_i]),
@@ -169,6 +171,7 @@ PROTOTYPES = {
     "d3f_philox4x32_10": (_i, [_u32p, _u32p, _u32p]),
     "d3f_noise_blend_rng": (_i, [_p, _u64, _u64, _f, _p, _p, _i, _i64, _p]),
     "d3f_noise_blend_fixed_rng": (_i, [_p, _u64, _u64, _p, _p, _i, _i64, _p]),
+    "d3f_noise_blend_fixed_index_rng": (_i, [_p, _u64, _u64, _p, _p, _p, _i, _i64, _p]),
     "d3f_noise_draw": (_i, [_u64, _u64, _p, _p, _i, _i64, _p]),
     "d3f_affine_warp_rng": (_i, [_p, _p, _u64, _u64, _i, C.POINTER(_f), _i, _i, _i, _i, _p]),
     "d3f_affine_theta_draw": (_i, [_u64, _u64, _i, C.POINTER(_f), _p, _p, _i, _i, _i, _p]),

@@ -881,6 +881,13 @@ int d3f_noise_blend_fixed_rng(const float* x, uint64_t seed, uint64_t offset, co
   D3F_CHECK(B > 0 && per_image > 0, "noise_blend_fixed_rng: bad shape");
   return noise_blend_fixed_rng_launch(x, seed, offset, r, out, B, (long)per_image, (hipStream_t)stream);
 }
+int d3f_noise_blend_fixed_index_rng(const float* x, uint64_t seed, uint64_t offset, const float* r, const int64_t* index,
+                                    float* out, int B, int64_t per_image, void* stream) {
+  if (B == 0 || per_image == 0) return 0;
+  D3F_CHECK(x && r && index && out && x != out, "noise_blend_fixed_index_rng: null or aliased argument");
+  D3F_CHECK(B > 0 && per_image > 0, "noise_blend_fixed_index_rng: bad shape");
+  return noise_blend_fixed_index_rng_launch(x, seed, offset, r, index, out, B, (long)per_image, (hipStream_t)stream);
+}
 int d3f_noise_draw(uint64_t seed, uint64_t offset, float* noise_or_null, float* y_or_null, int B, int64_t per_image,
                    void* stream) {
   if (B == 0) return 0;
@@ -901,6 +908,15 @@ int d3f_l1_per_image_scatter(const float* prediction, const float* target, const
   D3F_CHECK(B > 0 && N >= 0 && per_image > 0, "l1_per_image_scatter: bad shape");
   return l1_per_image_scatter_launch(prediction, target, index, scores, N, workspace, B, (long)per_image,
                                      (hipStream_t)stream);
+}
+size_t d3f_quality_per_image_workspace_bytes(int B, int H, int W) { return quality_per_image_workspace_bytes(B, H, W); }
+int d3f_quality_per_image_scatter(const float* prediction, const float* target, float input_min, float input_max,
+                                  const int64_t* index_or_null, float* metrics, int N, void* workspace, int B, int H, int W,
+                                  void* stream) {
+  // every refusal is the host's, made before a device call (quality_per_image_scatter_launch states the shape ones)
+  D3F_CHECK(prediction && target && metrics && workspace, "quality_per_image_scatter: null argument");
+  return quality_per_image_scatter_launch(prediction, target, input_min, input_max, index_or_null, metrics, N, workspace,
+                                          B, H, W, (hipStream_t)stream);
 }
 size_t d3f_difficulty_classes_workspace_bytes(int N) { return difficulty_classes_workspace_bytes(N); }
 int d3f_difficulty_classes(const float* scores, int N, int number_of_classes, int64_t* classes, int32_t* counts,

@@ -14,37 +14,9 @@
 // d loss / d prediction cost 2 stencil passes over the images instead of ~15 torch kernels.
 #include "pointwise.h"
 #include "philox.h"
+#include "ssim_common.h"  // the tile geometry, GaussK / make_gauss, norm01 (shared with quality.hip)
 
 namespace d3f {
-
-constexpr int SS_T = 32;            // tile edge (outputs)
-constexpr int SS_K = 11;            // window
-constexpr int SS_IN = SS_T + SS_K - 1;  // 42
-constexpr int SS_LD = SS_IN + 1;        // 43: odd stride -> conflict-free column walks
-constexpr int SS_FILL = (SS_IN * SS_IN + 255) / 256;  // 7: elements of the input tile per thread
-
-struct GaussK {
-  float g[SS_K];
-};
-typedef float f32x2 __attribute__((ext_vector_type(2)));  // a register pair for the packed fp32 instructions
-
-static GaussK make_gauss() {
-  GaussK k;
-  // same arithmetic as the oracle (float32 throughout)
-  float s = 0.f;
-  for (int i = 0; i < SS_K; ++i) {
-    const float d = (float)i - (float)(SS_K - 1) / 2.f;
-    k.g[i] = expf(-(d * d) / (2.f * 1.5f * 1.5f));
-    s += k.g[i];
-  }
-  for (int i = 0; i < SS_K; ++i) k.g[i] /= s;
-  return k;
-}
-
-__device__ __forceinline__ float norm01(float v, float lo, float range) {
-  const float t = (v - lo) / range;  // same op order as structural_similarity_loss.py:24
-  return fminf(fmaxf(t, 0.f), 1.f);
-}
 
 __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__ pred,
                                                        const float* __restrict__ target, float lo,
@@ -539,6 +511,41 @@ int noise_blend_fixed_rng_launch(const float* x, uint64_t seed, uint64_t offset,
   if (B == 0 || per_image == 0) return 0;
   hipLaunchKernelGGL(noise_blend_rng_kernel, dim3(rng_blocks(per_image), (unsigned)B), dim3(256), 0, stream, x, seed,
                      offset, r, 0.f, 0.f, -1.f, out, (float*)nullptr, per_image);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+// the fixed-ratio blend with the counter's image word taken from index[b] instead of b (held-out validation: an image
+// meets the same noise whatever batch it arrives in, and wherever in it).  A kernel of its own next to
+// noise_blend_rng_kernel, whose launches stay as they are; the same device functions, so index = 0 .. B-1 gives that
+// kernel's bits.  An index outside [0, 2^32) names no counter: the image is written as NaN.
+__global__ __launch_bounds__(256) void noise_blend_fixed_index_rng_kernel(const float* __restrict__ x, uint64_t seed,
+                                                                          uint64_t offset, const float* __restrict__ r,
+                                                                          const int64_t* __restrict__ index,
+                                                                          float* __restrict__ out, long per_image) {
+  const int b = blockIdx.y;
+  const int64_t word = index[b];
+  const bool named = word >= 0 && word <= (int64_t)0xFFFFFFFFll;
+  const BlendCoef k = blend_coef(r[b], 0.f, 0.f, -1.f);
+  const long nvec = per_image / 4;
+  const float4* __restrict__ xv = reinterpret_cast<const float4*>(x + (long)b * per_image);
+  float4* __restrict__ ov = reinterpret_cast<float4*>(out + (long)b * per_image);
+  if (!named) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256)
+      ov[i] = make_float4(NAN, NAN, NAN, NAN);
+    return;
+  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256)
+    ov[i] = blend4(k, xv[i], rng_normal4(seed, offset, (uint32_t)word, (uint32_t)i));
+}
+
+int noise_blend_fixed_index_rng_launch(const float* x, uint64_t seed, uint64_t offset, const float* r,
+                                       const int64_t* index, float* out, int B, long per_image, hipStream_t stream) {
+  if (int rc = rng_shape_check("noise_blend_fixed_index_rng", per_image)) return rc;
+  if (B == 0 || per_image == 0) return 0;
+  D3F_CHECK(B <= 65535, "noise_blend_fixed_index_rng: %d images in one call (at most 65535)", B);
+  hipLaunchKernelGGL(noise_blend_fixed_index_rng_kernel, dim3(rng_blocks(per_image), (unsigned)B), dim3(256), 0, stream,
+                     x, seed, offset, r, index, out, per_image);
   D3F_HIP(hipGetLastError());
   return 0;
 }

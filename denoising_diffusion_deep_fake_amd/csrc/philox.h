@@ -15,6 +15,10 @@
 //                   Multiply-high maps 2^32 words onto cnt values: each value gets floor or ceil of 2^32 / cnt words,
 //                   so a probability is off from 1 / cnt by less than 2^-32 (relative bias at most cnt / 2^32)
 //                   word 3: free
+// The image word b is the image's place in the batch for the training step's consumers.  Held-out validation
+// (noise_blend_fixed_index_rng_kernel, loss.hip) puts the image's place in its DATASET there instead, b = index[b] in
+// [0, 2^32): the draws of a held-out image then depend on nothing but (seed, offset, the image), not on the batch size or
+// the batch it arrives in.  The layout of the groups g is the same.
 // The python side packs offset = global_step << 24 | rank << 8 | stream (rng.py).
 #pragma once
 #include <stdint.h>

@@ -307,8 +307,16 @@ int noise_blend_rng_launch(const float* x, uint64_t seed, uint64_t offset, float
                            long per_image, hipStream_t stream);
 int noise_blend_fixed_rng_launch(const float* x, uint64_t seed, uint64_t offset, const float* r, float* out, int B,
                                  long per_image, hipStream_t stream);
+// noise_blend_fixed_rng with the counter's image word read from index[b] (loss.hip)
+int noise_blend_fixed_index_rng_launch(const float* x, uint64_t seed, uint64_t offset, const float* r,
+                                       const int64_t* index, float* out, int B, long per_image, hipStream_t stream);
 int noise_draw_launch(uint64_t seed, uint64_t offset, float* noise, float* y, int B, long per_image,
                       hipStream_t stream);
+// per-image mse / ssim / psnr / loss of a prediction, forward only, scattered into metrics [4][N] (quality.hip)
+size_t quality_per_image_workspace_bytes(int B, int H, int W);
+int quality_per_image_scatter_launch(const float* pred, const float* target, float in_min, float in_max,
+                                     const int64_t* index_or_null, float* metrics, int N, void* workspace, int B, int H,
+                                     int W, hipStream_t stream);
 size_t l1_per_image_workspace_bytes(int B);
 int l1_per_image_launch(const float* pred, const float* target, float* out, void* workspace, int B, long per_image,
                         hipStream_t stream);

@@ -472,6 +472,30 @@ def noise_blend_fixed_rng(x, seed, offset, ratio):
     return out
 
 
+def noise_blend_fixed_index_rng(x, seed, offset, ratio, index):
+    """noise_blend_fixed_rng with the counter's image word taken from index[b] instead of b: the draws of image b depend on
+    (seed, offset, index[b]) alone, so a held-out image meets the same noise in any batch.  index: [B] int64; a host
+    tensor or a sequence is checked here (every value in [0, 2**32), else ValueError) and moved to the device; a device
+    tensor is not read back -- an image whose index is outside the range comes out as NaN.  With index = arange(B) the
+    result is noise_blend_fixed_rng's bit for bit.  (include/d3f_hip.h: d3f_noise_blend_fixed_index_rng)"""
+    B = x.shape[0]
+    if not torch.is_tensor(index):
+        index = torch.as_tensor(index, dtype=torch.int64)
+    if index.dtype != torch.int64 or index.numel() != B:
+        raise ValueError(f"index must be an int64 tensor of {B} entries")
+    if index.device.type != "cuda" and B and (int(index.min()) < 0 or int(index.max()) >= 1 << 32):
+        raise ValueError("noise_blend_fixed_index_rng: an index outside [0, 2**32) names no counter")  # the host can see it
+    x = x.contiguous().float()
+    dev = _dev(x)
+    index = index.to(dev).reshape(-1).contiguous()
+    r = ratio if torch.is_tensor(ratio) else torch.ones(B, device=dev) * float(ratio)
+    r = r.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    out = torch.empty_like(x)
+    check(_lib.lib().d3f_noise_blend_fixed_index_rng(ptr(x), int(seed), int(offset), ptr(r), ptr(index), ptr(out), B,
+                                                     x.numel() // max(B, 1), stream_ptr()))
+    return out
+
+
 def noise_draw(seed, offset, shape, device="cuda", noise=True, y=True):
     """the draws noise_blend_rng / noise_blend_fixed_rng make for a batch of this shape: (noise [shape] or None, y [B] or
     None)"""
@@ -589,6 +613,46 @@ def mse_ssim_loss(pred, target, in_min=-1.0, in_max=1.0):
     check(L.d3f_mse_ssim_loss(ptr(pred), ptr(target), float(in_min), float(in_max), ptr(out), ptr(grad), ptr(ws),
                               B, H, W, stream_ptr()))
     return out, grad
+
+
+QUALITY_ROWS = ("mse", "ssim", "psnr", "loss")  # the rows of quality_per_image's result
+
+
+def quality_per_image(pred, target, lo=-1.0, hi=1.0, index=None, out=None, N=None):
+    """the criterion's terms per image, forward only: [4, N] f32 with rows QUALITY_ROWS, image b's values at column
+    index[b] (int64 on the device), or at column b when index is None (then N defaults to B).  out: a contiguous [4, N] f32
+    device tensor to scatter into -- columns no index names keep their value, an index outside [0, N) writes nothing;
+    without out the result starts as NaN.  An image's values do not depend on the batch it is scored in.  Refused before
+    any device call: images smaller than 11 x 11, hi <= lo, N < 1.  (include/d3f_hip.h: d3f_quality_per_image_scatter)"""
+    if pred.dim() != 4 or pred.shape[1] != 3 or pred.shape != target.shape:
+        raise ValueError("quality_per_image expects prediction and target of one shape [B, 3, H, W] (piqa n_channels=3)")
+    B, _, H, W = pred.shape
+    if H < 11 or W < 11:
+        raise ValueError(f"quality_per_image: image {H}x{W} smaller than the 11x11 SSIM window")
+    if not float(hi) > float(lo):
+        raise ValueError("quality_per_image: hi must be above lo")
+    if N is None:
+        N = out.shape[-1] if out is not None else B
+    N = int(N)
+    if N < 1:
+        raise ValueError(f"quality_per_image: N = {N}")
+    if index is not None and (index.dtype != torch.int64 or index.numel() != B):
+        raise ValueError(f"index must be an int64 tensor of {B} entries")
+    L = _lib.lib()
+    pred, target = pred.contiguous().float(), target.contiguous().float()
+    dev = _dev(pred)
+    if out is None:
+        out = torch.full((4, N), float("nan"), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (4, N) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 tensor of shape (4, {N}) on the device of pred")
+    if B == 0:
+        return out
+    if index is not None:
+        index = index.to(dev).reshape(-1).contiguous()
+    ws = torch.empty(L.d3f_quality_per_image_workspace_bytes(B, H, W), dtype=torch.uint8, device=dev)
+    check(L.d3f_quality_per_image_scatter(ptr(pred), ptr(target), float(lo), float(hi), ptr(index), ptr(out), N, ptr(ws),
+                                          B, H, W, stream_ptr()))
+    return out
 
 
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):

@@ -7,6 +7,15 @@ optimiser step on one rank:
 
 The noise, the per-image y and the augmentation uniforms of one (step, rank, stream) never collide: they sit at different
 counter groups g of the same offset (normals below 0xFFFFFFFD, the rest above).
+
+Held-out validation (helpers/validation.py) has streams of its own, which never meet a training step's: the step field
+holds the position k of the noise ratio in `val_noise_ratios`, the rank is 0 and the stream is 2 (the denoiser / domain a)
+or 3 (domain b),
+
+    offset = k << 24 | stream                               stream 2: held-out list / domain a, 3: domain b
+
+and the counter's image word is the image's index in the held-out dataset instead of its place in the batch
+(ops.noise_blend_fixed_index_rng): an image meets the same noise every epoch, at any batch size.
 """
 MAX_STEP, MAX_RANK, MAX_STREAM = 1 << 40, 1 << 16, 1 << 8
 

@@ -29,6 +29,12 @@ gathers, normalises and augments a domain's batch in one launch -- the values of
 it, with replacement, N draws an epoch (dataset/balanced.py).  A BalancedSampler per domain on the host; with `device_dataset`
 and `device_rng` the launch that assembles a domain's batch draws its indices too (ops.pool_batch_balanced_rng).
 
+`val_data_path_a` and `val_data_path_b` (or `val_synthetic_length` with `synthetic`; absent: off; not with a world size above
+1): held-out lists scored after every epoch at the fixed noise ratios `val_noise_ratios` -- model a on domain a, model b on
+domain b, in both modes: per-image MSE, SSIM, PSNR and criterion value on the device, `val_a/...`, `val_b/...` and their mean
+`val/...` in metrics.csv, `best.ckpt` by `val/loss`, optionally a per-image report (`val_report_path`).
+helpers/validation.py states the contract.
+
 Reference quirks kept on purpose: the dataloaders receive `mean_x` as BOTH
 mean and std (lit_module.py:75-76); `predict_fake("a")` uses model_a with B's mean/std (:253-257);
 de-normalisation truncates with `.int()` BEFORE clamping (:293-294).
@@ -47,7 +53,7 @@ from .. import ops, rng
 from ..dataset import balanced, device_pool
 from ..dataset.device_pool import DeviceImagePool
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset, ToUint8Tensor
-from ..helpers import ImageLoggingMixin
+from ..helpers import ImageLoggingMixin, ValidationMixin
 from ..lightning import LightningModule
 from ..loss_functions import MseStructuralSimilarityLoss
 from ..optim import EMA, FusedAdam
@@ -103,7 +109,10 @@ class ShiftScaleRotate(nn.Module):
         return torch.where(apply.reshape(-1, 1, 1, 1), warped, x)
 
 
-class LitModule(ImageLoggingMixin, LightningModule):
+class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
+    # (domain, the key of its held-out list, RNG stream)
+    VALIDATION_DOMAINS = (("a", "val_data_path_a", 2), ("b", "val_data_path_b", 3))
+
     def __init__(self, **kwargs):
         super().__init__()
         self.save_hyperparameters()
@@ -112,6 +121,7 @@ class LitModule(ImageLoggingMixin, LightningModule):
         balanced.check_hparams(self.hparams, self.hparams.get("data_path_a"), self.hparams.get("data_path_b"))
         self.__dict__["_balance_tables"] = {}  # balanced_sampling on the device: each pool's table, made with the pool
         self.setup_image_logging()  # image_logging_scheduler (:44); None unless `image_logging: true`
+        self.setup_validation()     # held-out validation; off unless `val_...` lists are named (helpers/validation.py)
         self.augmentation = self.create_gpu_augmentation()
         self.model_a = self.create_model_instance()
         self.model_b = self.create_model_instance()
@@ -237,7 +247,20 @@ class LitModule(ImageLoggingMixin, LightningModule):
             LearningRateMonitor(logging_interval="step"),
             ModelCheckpoint(save_top_k=8, monitor="epoch", mode="max", train_time_interval=timedelta(hours=2)),
             ModelCheckpoint(filename="last", save_on_train_epoch_end=True),
-        ]
+        ] + self.validation_callbacks()  # validation on: the best epoch's checkpoint by val/loss
+
+    # ---- held-out validation (helpers/validation.py) -----------------------------------------------------------------
+    def validation_model(self, domain):
+        return self.model_a if domain == "a" else self.model_b
+
+    def validation_transform(self, domain):
+        mean = self.hparams[f"mean_{domain}"]
+        return self.create_augmentation_sequence(mean, mean)  # the mean as std too, like train_dataloader
+
+    @torch.no_grad()
+    def validation_images(self, batch, domain):
+        x, mean = batch["image"], self.hparams[f"mean_{domain}"]
+        return ops.u8rgb_normalise(x, mean, mean) if x.dtype == torch.uint8 else x
 
     def training_step(self, batch, batch_idx, optimizer_idx):
         # the reference augments in the dataset; each image of a combined batch is consumed by exactly one of the two

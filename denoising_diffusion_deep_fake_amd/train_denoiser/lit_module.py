@@ -23,6 +23,10 @@ Differences, all outside the parity-checked arithmetic
     `d3f balance`; every difficulty class that has an image is drawn with equal probability, then every image of it, with
     replacement, N draws an epoch (dataset/balanced.py).  A BalancedSampler on the host; with `device_dataset` and
     `device_rng` the launch that assembles the batch draws the indices too (ops.pool_batch_balanced_rng).
+  * `val_image_list_path` (or `val_synthetic_length` with `synthetic`; absent: off; not with `graph_step` or a world size
+    above 1): a held-out list scored after every epoch at the fixed noise ratios `val_noise_ratios` -- per-image MSE, SSIM,
+    PSNR and criterion value on the device, `val/...` keys in metrics.csv, `best.ckpt` by `val/loss`, optionally a per-image
+    report (`val_report_path`).  helpers/validation.py states the contract.
 """
 import math
 
@@ -34,7 +38,7 @@ from .. import ops, rng
 from ..dataset import balanced, device_pool
 from ..dataset.device_pool import DeviceImagePool
 from ..dataset.image_dataset import ImageDataset, NormalizeToTensor, SyntheticFaceDataset, ToUint8Tensor
-from ..helpers import ImageLoggingMixin
+from ..helpers import ImageLoggingMixin, ValidationMixin
 from ..lightning import LightningModule
 from ..loss_functions import MseStructuralSimilarityLoss
 from ..optim import FusedAdam
@@ -70,7 +74,9 @@ class RandomAffine(torch.nn.Module):
         return torch.stack([torch.stack([cos, -sin, tx], 1), torch.stack([sin, cos, ty], 1)], 1)
 
 
-class LitModule(ImageLoggingMixin, LightningModule):
+class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
+    VALIDATION_DOMAINS = (("", "val_image_list_path", 2),)  # (domain, the key of its held-out list, RNG stream)
+
     def __init__(self, **kwargs):
         super().__init__()
         self.save_hyperparameters()
@@ -79,6 +85,7 @@ class LitModule(ImageLoggingMixin, LightningModule):
         balanced.check_hparams(self.hparams, self.hparams.get("input_image_list_path"))  # refusals: now, on the host
         self.__dict__["_balance_table"] = None  # balanced_sampling on the device: the pool's table, made with the pool
         self.setup_image_logging()  # image_logging_scheduler; None unless `image_logging: true` (not with graph_step)
+        self.setup_validation()     # held-out validation; off unless a `val_...` list is named (helpers/validation.py)
         self.model = self.create_model_instance()
         self.training_criterion = MseStructuralSimilarityLoss(-1.0, 1.0)
         self.shared_augmentation_sequence = self.create_shared_augmentation_sequence()
@@ -139,6 +146,26 @@ class LitModule(ImageLoggingMixin, LightningModule):
             order = dict(sampler=self.balanced_sampler(dataset.image_class_list))
         return DataLoader(dataset=dataset, batch_size=p.batch_size, num_workers=workers,
                           pin_memory=bool(p.get("pin_memory", True)) and torch.cuda.is_available(), **order, **extra)
+
+    # ---- held-out validation (helpers/validation.py) -----------------------------------------------------------------
+    def validation_model(self, domain):
+        return self.model
+
+    def validation_transform(self, domain):
+        m, s = self.mean_std_unit()
+        return ToUint8Tensor() if self.hparams.get("uint8_batches", False) else NormalizeToTensor(m, s)
+
+    @torch.no_grad()
+    def validation_images(self, batch, domain):
+        image = batch["image"]
+        return self.normalise_on_device(image) if image.dtype == torch.uint8 else image
+
+    def configure_callbacks(self):
+        """nothing without validation (the Trainer then adds its checkpoint per epoch, as ever); with it that checkpoint
+        and the best epoch's"""
+        from ..trainer import ModelCheckpoint
+        best = self.validation_callbacks()
+        return [ModelCheckpoint()] + best if best else []
 
     def balanced_on_device(self):
         """`balanced_sampling` where the batch's launch draws the indices: the pool with the device generator"""

@@ -49,14 +49,35 @@ class LearningRateMonitor(Callback):
 
 
 class ModelCheckpoint(Callback):
+    """monitor: None saves whenever its turn comes.  A `monitor` that is a key of what the module has logged
+    (`module._logged`) saves only when the value is not worse than the best one seen in `mode`'s direction ("min" or
+    "max"; a NaN never saves); a monitor the module has not logged (yet) saves as None does.  The reference's
+    monitor="epoch", mode="max" therefore saves every time, as it always has: the epoch never falls.  The best value lives
+    in this object: it is NOT carried across `resume`, where the first validated epoch counts as the best again."""
+
     def __init__(self, filename=None, save_top_k=1, monitor=None, mode="min", train_time_interval=None,
                  save_on_train_epoch_end=None, dirpath=None):
+        if mode not in ("min", "max"):
+            raise ValueError(f"ModelCheckpoint: mode {mode!r} is neither 'min' nor 'max'")
         self.filename, self.save_top_k, self.monitor, self.mode = filename, save_top_k, monitor, mode
         self.train_time_interval = train_time_interval
         self.save_on_train_epoch_end = save_on_train_epoch_end
         self.dirpath = dirpath
         self._last_time = time.monotonic()
         self._saved = []
+        self.best_value = None
+
+    def _improved(self, module):
+        logged = getattr(module, "_logged", {})
+        if self.monitor is None or self.monitor not in logged:
+            return True
+        value = float(logged[self.monitor])
+        if value != value:
+            return False
+        if self.best_value is not None and (value > self.best_value if self.mode == "min" else value < self.best_value):
+            return False
+        self.best_value = value
+        return True
 
     def _path(self, trainer):
         d = Path(self.dirpath) if self.dirpath else trainer.log_dir / "checkpoints"
@@ -64,7 +85,7 @@ class ModelCheckpoint(Callback):
         return d / f"{name}.ckpt"
 
     def _save(self, trainer, module):
-        if trainer.global_rank != 0:
+        if trainer.global_rank != 0 or not self._improved(module):
             return
         path = self._path(trainer)
         trainer.save_checkpoint(path)
@@ -333,16 +354,26 @@ class Trainer:
         no grad, validation_step over val_dataloader(), then validation_epoch_end(outputs)."""
         if not (hasattr(model, "validation_step") and hasattr(model, "val_dataloader")):
             return
+        loader = model.val_dataloader()
+        if loader is None:  # a module that can validate and was not asked to (helpers/validation.py): as one that cannot
+            return
+        before = dict(model._logged)
         model.eval()
         outputs = []
         with torch.no_grad():
-            for batch_idx, batch in enumerate(model.val_dataloader()):
+            for batch_idx, batch in enumerate(loader):
                 if self.limit_val_batches is not None and batch_idx >= self.limit_val_batches:
                     break
                 outputs.append(model.validation_step(_to_device(batch, device), batch_idx))
             if outputs and hasattr(model, "validation_epoch_end"):
                 model.validation_epoch_end(outputs)
         model.train()
+        # a validation that logged anything gets a metrics row of its own at the current global_step, so that its values
+        # reach metrics.csv without waiting for the next training log step (modules that ask for it:
+        # `validation_logs_metrics_row`; balance_training_images keeps the rows it had)
+        if getattr(model, "validation_logs_metrics_row", False) and \
+                any(k not in before or before[k] is not v for k, v in model._logged.items()):
+            self._metric_rows.append((self.global_step, dict(model._logged)))
 
     def fit(self, model, ckpt_path=None):
         if not torch.cuda.is_available():

@@ -569,7 +569,14 @@ int d3f_noise_blend_rng(const float* x, uint64_t seed, uint64_t offset, float la
  * the device; normals as above, no y.  out must not alias x. */
 int d3f_noise_blend_fixed_rng(const float* x, uint64_t seed, uint64_t offset, const float* r, float* out, int B,
                               int64_t per_image, void* stream);
-/* the draws of the two calls above, written out: noise [B][per_image] (normals of counter g = element / 4), y [B]
+/* d3f_noise_blend_fixed_rng with the Philox counter's image word taken from index[b] instead of b (held-out validation:
+ * an image meets the same noise every epoch, whatever batch it arrives in and wherever in it).  index [B] int64 on the
+ * device.  With index = 0 .. B-1 the output equals d3f_noise_blend_fixed_rng's bit for bit; the draw layout is otherwise
+ * unchanged.  The index lives on the device, so this entry cannot refuse a value outside [0, 2^32): such an image names no
+ * counter and is written as NaN (every element), which no later score can hide.  out must not alias x. */
+int d3f_noise_blend_fixed_index_rng(const float* x, uint64_t seed, uint64_t offset, const float* r, const int64_t* index,
+                                    float* out, int B, int64_t per_image, void* stream);
+/* the draws of the calls above, written out: noise [B][per_image] (normals of counter g = element / 4), y [B]
  * (g = 0xFFFFFFFF); either may be NULL */
 int d3f_noise_draw(uint64_t seed, uint64_t offset, float* noise_or_null, float* y_or_null, int B, int64_t per_image,
                    void* stream);
@@ -622,6 +629,25 @@ int d3f_difficulty_histogram_u8(const int64_t* classes, int N, int bins, int32_t
 size_t d3f_mse_ssim_loss_workspace_bytes(int B, int H, int W);
 int d3f_mse_ssim_loss(const float* pred, const float* target, float input_min, float input_max,
                       float* loss_out, float* grad_pred, void* workspace, int B, int H, int W, void* stream);
+/* The criterion's terms per image, forward only (csrc/quality.hip): what a held-out validation pass scores.
+ * MseStructuralSimilarityLoss (d3f/loss_functions/structural_similarity_loss.py:14-26; piqa.SSIM defaults) restricted to
+ * image b of NCHW f32 [B][3][H][W] inputs:
+ *   mse  = mean over its 3*H*W raw elements of (p - t)^2
+ *   ssim = mean over its 3*(H-10)*(W-10) valid positions of the SSIM map (d3f_mse_ssim_loss's arithmetic: the same
+ *          normalisation, fp32 taps, column-then-row order, tap order and constants; no fused multiply-add)
+ *   loss = (mse + (1.0f - ssim)) / 2.0f
+ *   psnr = -10 log10(mse01), mse01 = mean of (norm01(p) - norm01(t))^2 (norm01: to [0, 1] by the input range, clipped);
+ *          +inf when mse01 is 0
+ * metrics [4][N] f32 on the device, rows mse, ssim, psnr, loss; image b's values go to column index[b] (int64, device), or
+ * to column b when index is NULL.  As d3f_l1_per_image_scatter: an index outside [0, N) writes nothing, entries no index
+ * names are not touched, B == 0 launches nothing.  One stencil pass and a float64 sum of each image's tile partials in a
+ * fixed order: an image's four values have the same bits whatever batch it is scored in and wherever in it, and a repeat
+ * is bit for bit.  Refused on the host before any device call: null pointers (index apart), H or W below 11,
+ * input_max <= input_min, N < 1, more than 21845 images.  workspace: d3f_quality_per_image_workspace_bytes(B, H, W). */
+size_t d3f_quality_per_image_workspace_bytes(int B, int H, int W);
+int d3f_quality_per_image_scatter(const float* prediction, const float* target, float input_min, float input_max,
+                                  const int64_t* index_or_null, float* metrics, int N, void* workspace, int B, int H, int W,
+                                  void* stream);
 /* torch.optim.Adam step over a flat buffer (lit_module.py:95 / train_deep_fake/lit_module.py:116-120);
  * step counts from 1; grad_scale multiplies the gradient first (1/world_size for data parallel) */
 int d3f_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
