@@ -259,6 +259,17 @@ int d3f_unet_predict_frames_u8(d3f_unet_t h, const float* params, float* bnstats
                                 use_graph, (hipStream_t)stream);
 }
 
+int d3f_unet_predict_frames_full_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
+                                    int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* pair_out,
+                                    uint8_t* full_out, const float mean[3], const float std[3], void* workspace,
+                                    int use_graph, void* stream) {
+  D3F_CHECK(h && params && bnstats && raw_in && pair_out && full_out && mean && std && workspace,
+            "predict_frames_full_u8: null argument");
+  if (int rc = single_net(h, "predict_frames_full_u8", "has no eval-mode forward (run each network alone)")) return rc;
+  return h->e.predict_frames_full_u8(params, bnstats, raw_in, src_h, src_w, x1, y1, cw, ch, feather, pair_out, full_out,
+                                     mean, std, workspace, use_graph, (hipStream_t)stream);
+}
+
 int d3f_unet_num_segments(d3f_unet_t h) { return h ? h->e.num_segments : -1; }
 int d3f_unet_plan_counts(d3f_unet_t h, int32_t fwd[16], int32_t dgrad[16], int32_t wgrad[16]) {
   D3F_CHECK(h && fwd && dgrad && wgrad, "unet_plan_counts: null argument");
@@ -733,6 +744,14 @@ int d3f_crop_resize_cubic_u8(const uint8_t* src, int B, int src_h, int src_w, in
   D3F_CHECK(src && dst, "crop_resize_cubic_u8: null argument");
   return crop_resize_cubic_u8_launch(src, B, src_h, src_w, x1, y1, cw, ch, dst, H, W, (long)dst_row_stride_bytes,
                                      (hipStream_t)stream);
+}
+
+int d3f_paste_resize_cubic_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                              const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather,
+                              uint8_t* out, void* stream) {
+  D3F_CHECK(patch && frame && out, "paste_resize_cubic_u8: null argument");
+  return paste_resize_cubic_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, x1, y1, cw, ch,
+                                      feather, out, (hipStream_t)stream);
 }
 
 int d3f_image_grid_shape(int images, int nrow, int padding, int H, int W, int32_t dims[2]) {

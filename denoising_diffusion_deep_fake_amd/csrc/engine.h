@@ -115,6 +115,12 @@ class UnetEngine {
   int predict_frames_u8(const float* params, float* bnstats, const uint8_t* raw_in, int src_h, int src_w, int x1, int y1,
                         int cw, int ch, uint8_t* pair_out, const float mean[3], const float stdv[3], void* ws,
                         int use_graph, hipStream_t s) const;
+  // predict_frames_u8 into pair_out, then ONE more launch (paste_resize_cubic, resize.hip): the fake half of pair_out resized
+  // back to the crop box and blended into raw_in over `feather` pixels -> full_out [B][src_h][src_w][3].  full_out == raw_in
+  // pastes in place, eager only: a replay would read frames it has overwritten.  A graph slot of its own.
+  int predict_frames_full_u8(const float* params, float* bnstats, const uint8_t* raw_in, int src_h, int src_w, int x1,
+                             int y1, int cw, int ch, int feather, uint8_t* pair_out, uint8_t* full_out, const float mean[3],
+                             const float stdv[3], void* ws, int use_graph, hipStream_t s) const;
   // eval-mode forward (f32 NCHW in / out) replayed from a hipGraph captured once per set of pointers -- the
   // "hipGraph-captured denoise step" of BASELINE.json configs[4]; bit-identical to forward(training = 0)
   int forward_graph(const float* params, float* bnstats, const float* x, float* out, void* ws, hipStream_t s) const;
@@ -213,11 +219,11 @@ class UnetEngine {
                                  uint8_t* pair_out, const float mean255[3], const float std255[3], char* ws,
                                  hipStream_t s) const;
   // captured graphs: one slot per entry point; a slot is re-captured when what it baked in changes -- the pointers, the
-  // constants and (predict_frames_u8) the raw frame size and crop box
+  // constants and (predict_frames_u8, predict_frames_full_u8) the raw frame size and crop box, the latter's full_out and feather
   struct GraphKey {
-    const void* ptr[5];
+    const void* ptr[6];
     float cst[6];
-    int geo[6];
+    int geo[8];
   };
   struct GraphSlot {
     hipGraphExec_t exec = nullptr;
@@ -227,7 +233,7 @@ class UnetEngine {
   int graph_replay(GraphSlot& slot, const GraphKey& key, hipStream_t s, F&& launches) const;
   int wait_for_packed_weights(hipStream_t s) const;
   mutable hipStream_t gstream_ = nullptr;
-  mutable GraphSlot g_predict_, g_eval_, g_frames_;
+  mutable GraphSlot g_predict_, g_eval_, g_frames_, g_frames_full_;
   BnSync bn_sync_{nullptr, nullptr, 1};
   const BnSync* bn_sync() const { return bn_sync_.fn != nullptr ? &bn_sync_ : nullptr; }
   int train_step_launches(const StepArgs& a, void* ws, hipStream_t s) const;

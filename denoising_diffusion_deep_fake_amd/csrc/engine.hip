@@ -696,7 +696,7 @@ int UnetEngine::set_head_activation(int act) {
 }
 
 void UnetEngine::drop_graphs() const {
-  for (GraphSlot* slot : {&g_predict_, &g_eval_, &g_frames_})
+  for (GraphSlot* slot : {&g_predict_, &g_eval_, &g_frames_, &g_frames_full_})
     if (slot->exec) {
       (void)hipGraphExecDestroy(slot->exec);
       slot->exec = nullptr;
@@ -758,6 +758,38 @@ int UnetEngine::predict_frames_u8(const float* params_, float* bnstats, const ui
   return graph_replay(g_frames_, key, s, [&](hipStream_t gs) {
     return predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, gs);
   });
+}
+
+int UnetEngine::predict_frames_full_u8(const float* params_, float* bnstats, const uint8_t* raw_in, int src_h, int src_w,
+                                       int x1, int y1, int cw, int ch, int feather, uint8_t* pair_out, uint8_t* full_out,
+                                       const float mean[3], const float stdv[3], void* ws_, int use_graph,
+                                       hipStream_t s) const {
+  D3F_CHECK(in_channels == 3 && classes == 3, "predict_frames_full_u8: 3-channel frames only (in %d, out %d)", in_channels,
+            classes);
+  D3F_CHECK(!(use_graph && full_out == raw_in),
+            "predict_frames_full_u8: full_out == raw_in (in place) cannot be replayed from a graph: pass use_graph = 0");
+  char* ws = reinterpret_cast<char*>(ws_);
+  float m255[3], s255[3];
+  for (int c = 0; c < 3; ++c) {  // as predict_u8
+    m255[c] = mean[c] * 255.0f;
+    s255[c] = stdv[c] * 255.0f;
+  }
+  if (int rc = crop_resize_cubic_check(B, src_h, src_w, x1, y1, cw, ch, H, W, 6L * W)) return rc;
+  if (int rc = paste_resize_cubic_check(pair_out + 3L * W, raw_in, full_out, B, H, W, 6L * W, src_h, src_w, x1, y1, cw, ch,
+                                        feather))
+    return rc;
+  const int geo[6] = {src_h, src_w, x1, y1, cw, ch};
+  auto launches = [&](hipStream_t ls) {
+    if (int rc = predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, ls)) return rc;
+    // the fake half of the pair is the patch: rows 6 * W bytes apart
+    return paste_resize_cubic_u8_launch(pair_out + 3L * W, B, H, W, 6L * W, raw_in, src_h, src_w, x1, y1, cw, ch, feather,
+                                        full_out, ls);
+  };
+  if (!use_graph) return launches(s);
+  const GraphKey key = {{params_, bnstats, raw_in, pair_out, ws_, full_out},
+                        {m255[0], m255[1], m255[2], s255[0], s255[1], s255[2]},
+                        {src_h, src_w, x1, y1, cw, ch, feather, 0}};
+  return graph_replay(g_frames_full_, key, s, launches);
 }
 
 int UnetEngine::forward_graph(const float* params_, float* bnstats, const float* x, float* out, void* ws_,
@@ -840,7 +872,7 @@ int UnetEngine::graph_replay(GraphSlot& slot, const GraphKey& key, hipStream_t s
     D3F_HIP(hipEventCreateWithFlags(&ev_gout_, hipEventDisableTiming));
   }
   // (GraphKey has no padding: pointers, then 4-byte fields filling whole 8-byte units)
-  static_assert(sizeof(GraphKey) == 5 * sizeof(void*) + 6 * sizeof(float) + 6 * sizeof(int), "GraphKey is compared bytewise");
+  static_assert(sizeof(GraphKey) == 6 * sizeof(void*) + 6 * sizeof(float) + 8 * sizeof(int), "GraphKey is compared bytewise");
   const bool same = slot.exec != nullptr && memcmp(&key, &slot.key, sizeof(GraphKey)) == 0;
   if (!same) {
     if (slot.exec) {

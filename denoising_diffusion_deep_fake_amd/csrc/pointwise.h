@@ -124,6 +124,15 @@ int crop_resize_cubic_u8_launch(const uint8_t* src, int B, int src_h, int src_w,
 int crop_resize_cubic_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw,
                                      int ch, uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
                                      const float mean255[3], const float std255[3], hipStream_t stream);
+// full-frame output (resize.hip): patch [B][H][W][3], rows patch_row_stride bytes apart, resized to the box (x1, y1, cw, ch)
+// of frame [B][src_h][src_w][3] with the same arithmetic and blended in over a ramp of `feather` pixels; the rest of out
+// is the frame.  out == frame runs in place.  (_check: the host-side argument check, for a caller that must refuse
+// before it starts a capture)
+int paste_resize_cubic_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, int B, int H, int W,
+                             long patch_row_stride, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather);
+int paste_resize_cubic_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
+                                 int src_h, int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* out,
+                                 hipStream_t stream);
 
 // training image grids (image_grid.hip): make_grid + scale + clamp + uint8 of up to 8 fp32 NCHW batches in one launch;
 // `batches` is a host array of n device pointers, out [n][GH][GW][3] with {GH, GW} from image_grid_shape

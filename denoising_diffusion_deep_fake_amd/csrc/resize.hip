@@ -19,6 +19,9 @@
 // gathers that would otherwise each be a global transaction -- and both passes read from there.  A crop so much larger
 // than the output that a tile's patch exceeds RESIZE_LDS_BYTES takes the same arithmetic with the taps read from global
 // memory (STAGED = false).
+//
+// Staging and the two passes are device functions (resize_stage, resize_value): the paste kernel at the end of this file,
+// the inverse of this operator, runs the same arithmetic on a patch instead of a crop.
 #include "common.h"
 #include "pointwise.h"
 
@@ -62,6 +65,87 @@ __device__ __forceinline__ int floor_src(int d, int n_in, int n_out) {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// One resize n_h x n_w -> out_h x out_w of an image of 3-byte pixels: first pixel at img, rows src_pitch bytes apart.
+// crop_resize_cubic_kernel reads the crop of a frame this way, paste_resize_cubic_kernel the whole patch.
+struct ResizeSrc {
+  const uint8_t* img;
+  long src_pitch;
+  int n_h, n_w, out_h, out_w;
+  int pitch;  // bytes of one staged row (a multiple of 4)
+};
+
+// where a tile's staged part of the image sits in LDS: rows from ry0, columns from cx0, and the dword alignment of its
+// rows (all zero when the taps are read from global memory)
+struct ResizeTile {
+  int ry0 = 0, cx0 = 0;
+  unsigned align0 = 0, align_step = 0;
+};
+
+// stages what the output indices [ox_f, ox_l] x [oy_f, oy_l] read, with aligned dword loads; a dword is loaded whole only
+// inside [lo, hi).  The caller synchronises the workgroup afterwards.
+__device__ __forceinline__ ResizeTile resize_stage(uint8_t* patch, const ResizeSrc& g, int ox_f, int ox_l, int oy_f,
+                                                   int oy_l, const uint8_t* lo, const uint8_t* hi, int tid) {
+  ResizeTile t;
+  t.cx0 = max(floor_src(ox_f, g.n_w, g.out_w) - 1, 0);
+  t.ry0 = max(floor_src(oy_f, g.n_h, g.out_h) - 1, 0);
+  const int cx1 = min(floor_src(ox_l, g.n_w, g.out_w) + 2, g.n_w - 1);
+  const int ry1 = min(floor_src(oy_l, g.n_h, g.out_h) + 2, g.n_h - 1);
+  const int row_bytes = (cx1 - t.cx0 + 1) * 3, rows = ry1 - t.ry0 + 1, pitch_dw = g.pitch >> 2;
+  // patch row r holds the aligned dwords that cover its bytes: byte k of the row sits at r * pitch + align_r + k
+  const uint8_t* first = g.img + (long)t.ry0 * g.src_pitch + (long)t.cx0 * 3;
+  t.align0 = (unsigned)(reinterpret_cast<uintptr_t>(first) & 3);
+  t.align_step = (unsigned)(g.src_pitch & 3);
+  for (int i = tid; i < rows * pitch_dw; i += RESIZE_TW * RESIZE_TH) {
+    const int r = i / pitch_dw, k = i - r * pitch_dw;
+    const unsigned al = (t.align0 + (unsigned)r * t.align_step) & 3;
+    if (k * 4 >= (int)al + row_bytes) continue;
+    const uint8_t* p = first + (long)r * g.src_pitch - al + k * 4;
+    uint32_t v;
+    if (p >= lo && p + 4 <= hi) {
+      v = *reinterpret_cast<const uint32_t*>(p);
+    } else {
+      v = 0;
+      for (int j = 0; j < 4; ++j)
+        if (p + j >= lo && p + j < hi) v |= (uint32_t)p[j] << (8 * j);
+    }
+    *reinterpret_cast<uint32_t*>(patch + (long)r * g.pitch + k * 4) = v;
+  }
+  return t;
+}
+
+// the fp32 value of output pixel (ox, oy) before rounding: horizontal pass, then vertical pass
+template <bool STAGED>
+__device__ __forceinline__ void resize_value(const uint8_t* patch, const ResizeSrc& g, const ResizeTile& t, int ox, int oy,
+                                             float v[3]) {
+  float wx[4], wy[4];
+  const int sx = cubic_taps(ox, g.n_w, g.out_w, wx), sy = cubic_taps(oy, g.n_h, g.out_h, wy);
+  int col[4];
+  for (int k = 0; k < 4; ++k) col[k] = (clampi(sx - 1 + k, 0, g.n_w - 1) - t.cx0) * 3;
+  float hrow[4][3];
+  for (int r = 0; r < 4; ++r) {
+    const int cy = clampi(sy - 1 + r, 0, g.n_h - 1) - t.ry0;
+    const uint8_t* row;
+    if (STAGED)
+      row = patch + (long)cy * g.pitch + ((t.align0 + (unsigned)cy * t.align_step) & 3);
+    else
+      row = g.img + (long)cy * g.src_pitch;
+    for (int c = 0; c < 3; ++c) {  // horizontal pass
+      float h = wx[0] * (float)row[col[0] + c];
+      h = h + wx[1] * (float)row[col[1] + c];
+      h = h + wx[2] * (float)row[col[2] + c];
+      h = h + wx[3] * (float)row[col[3] + c];
+      hrow[r][c] = h;
+    }
+  }
+  for (int c = 0; c < 3; ++c) {  // vertical pass
+    float a = wy[0] * hrow[0][c];
+    a = a + wy[1] * hrow[1][c];
+    a = a + wy[2] * hrow[2][c];
+    a = a + wy[3] * hrow[3][c];
+    v[c] = a;
+  }
+}
+
 template <typename T, bool ACT, bool STAGED>
 __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void crop_resize_cubic_kernel(
     const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, T* __restrict__ act, ResizeGeom g, int Cpad, float m0,
@@ -71,71 +155,21 @@ __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void crop_resize_cubic_kerne
   const int ox0 = blockIdx.x * RESIZE_TW, oy0 = blockIdx.y * RESIZE_TH, b = blockIdx.z;
   const long frame_bytes = (long)g.src_h * g.src_w * 3;
   const uint8_t* frame = src + b * frame_bytes;
-  // the crop's first pixel, and the patch of it this tile reads: rows [ry0, ry1], columns [cx0, cx1] of the crop
-  const uint8_t* crop = frame + ((long)g.y1 * g.src_w + g.x1) * 3;
-  const long src_pitch = (long)g.src_w * 3;
-  int ry0 = 0, cx0 = 0;
-  unsigned align0 = 0, align_step = 0;
+  // the crop's first pixel; the tile stages rows and columns of the crop
+  const ResizeSrc rs = {frame + ((long)g.y1 * g.src_w + g.x1) * 3, (long)g.src_w * 3, g.ch, g.cw, g.H, g.W, g.pitch};
+  ResizeTile t;
   if (STAGED) {
-    const int oxl = min(ox0 + RESIZE_TW, g.W) - 1, oyl = min(oy0 + RESIZE_TH, g.H) - 1;
-    cx0 = max(floor_src(ox0, g.cw, g.W) - 1, 0);
-    ry0 = max(floor_src(oy0, g.ch, g.H) - 1, 0);
-    const int cx1 = min(floor_src(oxl, g.cw, g.W) + 2, g.cw - 1);
-    const int ry1 = min(floor_src(oyl, g.ch, g.H) + 2, g.ch - 1);
-    const int row_bytes = (cx1 - cx0 + 1) * 3, rows = ry1 - ry0 + 1, pitch_dw = g.pitch >> 2;
-    // patch row r holds the aligned dwords that cover its bytes: byte k of the row sits at r * pitch + align_r + k
-    const uint8_t* first = crop + (long)ry0 * src_pitch + (long)cx0 * 3;
-    align0 = (unsigned)(reinterpret_cast<uintptr_t>(first) & 3);
-    align_step = (unsigned)(src_pitch & 3);
-    const uint8_t* lo = src;                                  // a dword is loaded whole only inside the batch's bytes
-    const uint8_t* hi = src + (long)gridDim.z * frame_bytes;
-    for (int i = tid; i < rows * pitch_dw; i += RESIZE_TW * RESIZE_TH) {
-      const int r = i / pitch_dw, k = i - r * pitch_dw;
-      const unsigned al = (align0 + (unsigned)r * align_step) & 3;
-      if (k * 4 >= (int)al + row_bytes) continue;
-      const uint8_t* p = first + (long)r * src_pitch - al + k * 4;
-      uint32_t v;
-      if (p >= lo && p + 4 <= hi) {
-        v = *reinterpret_cast<const uint32_t*>(p);
-      } else {
-        v = 0;
-        for (int j = 0; j < 4; ++j)
-          if (p + j >= lo && p + j < hi) v |= (uint32_t)p[j] << (8 * j);
-      }
-      *reinterpret_cast<uint32_t*>(patch + (long)r * g.pitch + k * 4) = v;
-    }
+    t = resize_stage(patch, rs, ox0, min(ox0 + RESIZE_TW, g.W) - 1, oy0, min(oy0 + RESIZE_TH, g.H) - 1, src,
+                     src + (long)gridDim.z * frame_bytes, tid);
     __syncthreads();
   }
   const int ox = ox0 + (tid % RESIZE_TW), oy = oy0 + (tid / RESIZE_TW);
   if (ox >= g.W || oy >= g.H) return;
-  float wx[4], wy[4];
-  const int sx = cubic_taps(ox, g.cw, g.W, wx), sy = cubic_taps(oy, g.ch, g.H, wy);
-  int col[4];
-  for (int k = 0; k < 4; ++k) col[k] = (clampi(sx - 1 + k, 0, g.cw - 1) - cx0) * 3;
-  float acc[3];
-  float hrow[4][3];
-  for (int r = 0; r < 4; ++r) {
-    const int cy = clampi(sy - 1 + r, 0, g.ch - 1) - ry0;
-    const uint8_t* row;
-    if (STAGED)
-      row = patch + (long)cy * g.pitch + ((align0 + (unsigned)cy * align_step) & 3);
-    else
-      row = crop + (long)cy * src_pitch;
-    for (int c = 0; c < 3; ++c) {  // horizontal pass
-      float h = wx[0] * (float)row[col[0] + c];
-      h = h + wx[1] * (float)row[col[1] + c];
-      h = h + wx[2] * (float)row[col[2] + c];
-      h = h + wx[3] * (float)row[col[3] + c];
-      hrow[r][c] = h;
-    }
-  }
+  float v[3], acc[3];
+  resize_value<STAGED>(patch, rs, t, ox, oy, v);
   uint8_t px[3];
-  for (int c = 0; c < 3; ++c) {  // vertical pass, rintf, clamp
-    float v = wy[0] * hrow[0][c];
-    v = v + wy[1] * hrow[1][c];
-    v = v + wy[2] * hrow[2][c];
-    v = v + wy[3] * hrow[3][c];
-    acc[c] = rintf(v);
+  for (int c = 0; c < 3; ++c) {  // rintf, clamp
+    acc[c] = rintf(v[c]);
     px[c] = (uint8_t)(acc[c] < 0.f ? 0.f : (acc[c] > 255.f ? 255.f : acc[c]));
   }
   uint8_t* o = dst + ((long)b * g.H + oy) * g.dst_row_stride + (long)ox * 3;
@@ -152,22 +186,30 @@ __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void crop_resize_cubic_kerne
   }
 }
 
+// LDS bytes of the largest part of an n_h x n_w image a tile of a resize to out_h x out_w can need, and the pitch of its
+// rows; 0 when that passes RESIZE_LDS_BYTES (the taps are then read from global memory)
+static long resize_lds_bytes(int n_h, int n_w, int out_h, int out_w, int* pitch_out) {
+  // floor(a + n r) - floor(a) <= floor(n r) + 1 source steps over n output steps, plus the three taps around them, plus up
+  // to 3 bytes of dword alignment in front
+  const long cols = (long)(RESIZE_TW - 1) * n_w / out_w + 1 + 4, rows = (long)(RESIZE_TH - 1) * n_h / out_h + 1 + 4;
+  const long pitch = (cols * 3 + 3 + 3) / 4 * 4;
+  const bool staged = rows * pitch <= RESIZE_LDS_BYTES;
+  *pitch_out = staged ? (int)pitch : 0;
+  return staged ? rows * pitch : 0;
+}
+
 template <typename T, bool ACT>
 static int resize_launch(const uint8_t* src, uint8_t* dst, T* act, const ResizeGeom& g0, int B, int Cpad,
                          const float mean255[3], const float std255[3], hipStream_t stream) {
   ResizeGeom g = g0;
-  // the largest patch a tile can need: floor(a + n r) - floor(a) <= floor(n r) + 1 source steps over n output steps,
-  // plus the three taps around them, plus up to 3 bytes of dword alignment in front
-  const long cols = (long)(RESIZE_TW - 1) * g.cw / g.W + 1 + 4, rows = (long)(RESIZE_TH - 1) * g.ch / g.H + 1 + 4;
-  const long pitch = (cols * 3 + 3 + 3) / 4 * 4;
-  const bool staged = rows * pitch <= RESIZE_LDS_BYTES;
-  g.pitch = staged ? (int)pitch : 0;
+  const long lds = resize_lds_bytes(g.ch, g.cw, g.H, g.W, &g.pitch);
+  const bool staged = lds > 0;
   const dim3 grid((g.W + RESIZE_TW - 1) / RESIZE_TW, (g.H + RESIZE_TH - 1) / RESIZE_TH, B), block(RESIZE_TW * RESIZE_TH);
   const float z[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
   const float* m = mean255 ? mean255 : z;
   const float* s = std255 ? std255 : one;
   if (staged)
-    hipLaunchKernelGGL((crop_resize_cubic_kernel<T, ACT, true>), grid, block, (size_t)(rows * pitch), stream, src, dst, act,
+    hipLaunchKernelGGL((crop_resize_cubic_kernel<T, ACT, true>), grid, block, (size_t)lds, stream, src, dst, act,
                        g, Cpad, m[0], m[1], m[2], s[0], s[1], s[2]);
   else
     hipLaunchKernelGGL((crop_resize_cubic_kernel<T, ACT, false>), grid, block, 0, stream, src, dst, act, g, Cpad, m[0],
@@ -215,6 +257,149 @@ int crop_resize_cubic_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int s
   if (dtype == D3F_F32)
     return resize_launch<float, true>(src, dst, (float*)act, g, B, Cpad, mean255, std255, stream);
   return resize_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, B, Cpad, mean255, std255, stream);
+}
+
+// ---- full-frame output: the inverse of the operator above with a blend in the epilogue ----
+// patch [B][H][W][3] (rows patch_row_stride bytes apart) is resized H x W -> ch x cw with resize_value and blended into the
+// box (x1, y1, cw, ch) of frame [B][src_h][src_w][3]; everything else of out is the frame (include/d3f_hip.h:
+// d3f_paste_resize_cubic_u8 is the definition; tests/paste_restatement.py restates it in float64).
+// Tiles lie on the FRAME's 32 x 8 grid.  A tile that meets the box stages the part of the patch its box pixels read and
+// runs one lane per pixel; a tile outside the box moves the frame's bytes as aligned dwords (a row of a tile is 96
+// contiguous bytes).  out == frame: only the tiles that meet the box are launched (tx0, ty0: the first of them), and a
+// lane reads no frame byte but the three it writes.
+struct PasteGeom {
+  int H, W;
+  long patch_row_stride;
+  int src_h, src_w, x1, y1, cw, ch, feather;
+  int pitch;
+  int tx0, ty0;
+};
+
+template <bool STAGED>
+__global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void paste_resize_cubic_kernel(const uint8_t* __restrict__ patch,
+                                                                                  const uint8_t* frame, uint8_t* out,
+                                                                                  PasteGeom g) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t staged[];
+  const int tid = threadIdx.x;
+  const int ox0 = ((int)blockIdx.x + g.tx0) * RESIZE_TW, oy0 = ((int)blockIdx.y + g.ty0) * RESIZE_TH, b = blockIdx.z;
+  const long frame_bytes = (long)g.src_h * g.src_w * 3, row_bytes = (long)g.src_w * 3;
+  const uint8_t* f = frame + b * frame_bytes;
+  uint8_t* o = out + b * frame_bytes;
+  const bool in_place = frame == out;
+  const int tile_w = min(RESIZE_TW, g.src_w - ox0), tile_h = min(RESIZE_TH, g.src_h - oy0);
+  // the box pixels of this tile: columns [bx_f, bx_l] and rows [by_f, by_l] of the box
+  const int bx_f = max(ox0, g.x1) - g.x1, bx_l = min(ox0 + tile_w, g.x1 + g.cw) - 1 - g.x1;
+  const int by_f = max(oy0, g.y1) - g.y1, by_l = min(oy0 + tile_h, g.y1 + g.ch) - 1 - g.y1;
+  const int lx = tid % RESIZE_TW, ly = tid / RESIZE_TW;
+  if (bx_f > bx_l || by_f > by_l) {  // (workgroup-uniform) a tile outside the box: a copy
+    if (in_place || ly >= tile_h) return;
+    const long at = (long)(oy0 + ly) * row_bytes + (long)ox0 * 3;
+    const uint8_t* p = f + at;
+    uint8_t* q = o + at;
+    const int n = tile_w * 3;
+    const int al = (int)(reinterpret_cast<uintptr_t>(p) & 3);
+    if (al == (int)(reinterpret_cast<uintptr_t>(q) & 3)) {
+      // lane lx takes the aligned dword lx of the row: whole where it lies inside the row's n bytes, else its bytes that do
+      const int k = lx * 4 - al;  // offset of the dword's first byte from p
+      if (k >= 0 && k + 4 <= n) {
+        *reinterpret_cast<uint32_t*>(q + k) = *reinterpret_cast<const uint32_t*>(p + k);
+      } else {
+        for (int j = 0; j < 4; ++j)
+          if (k + j >= 0 && k + j < n) q[k + j] = p[k + j];
+      }
+    } else if (lx < tile_w) {  // frame and out a different number of bytes past a dword: bytes
+      q[lx * 3 + 0] = p[lx * 3 + 0];
+      q[lx * 3 + 1] = p[lx * 3 + 1];
+      q[lx * 3 + 2] = p[lx * 3 + 2];
+    }
+    return;
+  }
+  const uint8_t* img = patch + (long)b * g.H * g.patch_row_stride;
+  const ResizeSrc rs = {img, g.patch_row_stride, g.H, g.W, g.ch, g.cw, g.pitch};
+  ResizeTile t;
+  if (STAGED) {
+    // a dword is loaded whole only inside the bytes from the first patch's first pixel to the last one's last
+    const uint8_t* hi = patch + ((long)gridDim.z * g.H - 1) * g.patch_row_stride + (long)g.W * 3;
+    t = resize_stage(staged, rs, bx_f, bx_l, by_f, by_l, patch, hi, tid);
+    __syncthreads();
+  }
+  if (lx >= tile_w || ly >= tile_h) return;
+  const long at = (long)(oy0 + ly) * row_bytes + (long)(ox0 + lx) * 3;
+  const int j = ox0 + lx - g.x1, i = oy0 + ly - g.y1;
+  if (j < 0 || j >= g.cw || i < 0 || i >= g.ch) {  // a pixel of the tile outside the box
+    if (!in_place) {
+      const uint8_t s0 = f[at], s1 = f[at + 1], s2 = f[at + 2];
+      o[at] = s0;
+      o[at + 1] = s1;
+      o[at + 2] = s2;
+    }
+    return;
+  }
+  float v[3];
+  resize_value<STAGED>(staged, rs, t, j, i, v);
+  // the separable ramp: 1 at distance >= feather from the box's edges, (d + 1) / (feather + 1) inside that
+  const int dy = min(i, g.ch - 1 - i), dx = min(j, g.cw - 1 - j);
+  const float ay = (float)min(dy + 1, g.feather + 1) / (float)(g.feather + 1);
+  const float ax = (float)min(dx + 1, g.feather + 1) / (float)(g.feather + 1);
+  const float a = ay * ax, na = 1.f - a;
+  const float s[3] = {(float)f[at], (float)f[at + 1], (float)f[at + 2]};
+  uint8_t px[3];
+  for (int c = 0; c < 3; ++c) {
+    const float vc = fminf(fmaxf(v[c], 0.f), 255.f);
+    const float pv = a * vc, ps = na * s[c];
+    const float r = rintf(pv + ps);
+    px[c] = (uint8_t)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r));
+  }
+  o[at] = px[0];
+  o[at + 1] = px[1];
+  o[at + 2] = px[2];
+}
+
+int paste_resize_cubic_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, int B, int H, int W,
+                             long patch_row_stride, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather) {
+  D3F_CHECK(B >= 0 && B <= 65535, "paste_resize_cubic: B %d outside 0..65535 frames per call", B);
+  D3F_CHECK(src_h > 0 && src_w > 0 && cw > 0 && ch > 0 && H > 0 && W > 0,
+            "paste_resize_cubic: non-positive size (frame %dx%d, box %dx%d, patch %dx%d)", src_h, src_w, ch, cw, H, W);
+  D3F_CHECK(x1 >= 0 && y1 >= 0 && (long)x1 + cw <= src_w && (long)y1 + ch <= src_h,
+            "paste_resize_cubic: box (x1 %d, y1 %d, %d x %d) outside the %d x %d frame", x1, y1, cw, ch, src_w, src_h);
+  D3F_CHECK(src_h <= RESIZE_MAX_EXTENT && src_w <= RESIZE_MAX_EXTENT && H <= RESIZE_MAX_EXTENT && W <= RESIZE_MAX_EXTENT,
+            "paste_resize_cubic: extents up to %d (32-bit source coordinates)", RESIZE_MAX_EXTENT);
+  D3F_CHECK(feather >= 0 && feather <= RESIZE_MAX_EXTENT, "paste_resize_cubic: feather %d outside 0..%d", feather,
+            RESIZE_MAX_EXTENT);
+  D3F_CHECK(patch_row_stride >= 3L * W, "paste_resize_cubic: patch row stride %ld below 3 * W = %ld bytes",
+            patch_row_stride, 3L * W);
+  const long bytes = (long)B * src_h * src_w * 3;
+  D3F_CHECK(frame == out || out + bytes <= frame || frame + bytes <= out,
+            "paste_resize_cubic: frame and out overlap in part (out == frame runs in place)");
+  // other workgroups write out while a tile stages its part of the patch: the patches' bytes must lie outside out
+  const long patch_bytes = B > 0 ? ((long)B * H - 1) * patch_row_stride + 3L * W : 0;
+  D3F_CHECK(patch_bytes == 0 || patch + patch_bytes <= out || out + bytes <= patch,
+            "paste_resize_cubic: patch overlaps out");
+  return 0;
+}
+
+int paste_resize_cubic_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
+                                 int src_h, int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* out,
+                                 hipStream_t stream) {
+  if (int rc = paste_resize_cubic_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather))
+    return rc;
+  if (B == 0) return 0;
+  PasteGeom g = {H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather, 0, 0, 0};
+  const long lds = resize_lds_bytes(H, W, ch, cw, &g.pitch);
+  dim3 grid((src_w + RESIZE_TW - 1) / RESIZE_TW, (src_h + RESIZE_TH - 1) / RESIZE_TH, B);
+  if (frame == out) {  // in place: the tiles that meet the box
+    g.tx0 = x1 / RESIZE_TW;
+    g.ty0 = y1 / RESIZE_TH;
+    grid.x = (x1 + cw - 1) / RESIZE_TW - g.tx0 + 1;
+    grid.y = (y1 + ch - 1) / RESIZE_TH - g.ty0 + 1;
+  }
+  const dim3 block(RESIZE_TW * RESIZE_TH);
+  if (lds > 0)
+    hipLaunchKernelGGL(paste_resize_cubic_kernel<true>, grid, block, (size_t)lds, stream, patch, frame, out, g);
+  else
+    hipLaunchKernelGGL(paste_resize_cubic_kernel<false>, grid, block, 0, stream, patch, frame, out, g);
+  D3F_HIP(hipGetLastError());
+  return 0;
 }
 
 }  // namespace d3f

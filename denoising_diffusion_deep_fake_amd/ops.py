@@ -701,6 +701,48 @@ def crop_resize_cubic_u8(frames, size, box=None, out=None):
     return out[0] if single else out
 
 
+def default_feather(cw, ch):
+    """width in source pixels of the ramp over which a pasted patch fades into its frame: the one place the default lives"""
+    return min(int(cw), int(ch)) // 16
+
+
+def paste_resize_cubic_u8(patch, frames, box, feather=0, out=None):
+    """The inverse of `crop_resize_cubic_u8` with a blend: uint8 `patch` [H, W, 3] / [B, H, W, 3] on the HIP device is resized
+    to the box (x1, y1, cw, ch) of uint8 `frames` [h, w, 3] / [B, h, w, 3] with the same arithmetic and blended in over a
+    ramp of `feather` pixels; outside the box the result is the frame (include/d3f_hip.h: d3f_paste_resize_cubic_u8).
+    patch: packed pixels, rows may be strided -- the right half of a [B, H, 2W, 3] pair buffer, for one.  out=frames runs in
+    place; otherwise out is a contiguous tensor shaped like frames, allocated when None."""
+    if (patch.dtype != torch.uint8 or patch.shape[-1] != 3 or patch.dim() not in (3, 4) or frames.dtype != torch.uint8
+            or frames.shape[-1] != 3 or frames.dim() != patch.dim()):
+        raise ValueError("paste_resize_cubic_u8 expects a uint8 patch [H, W, 3] and frames [h, w, 3], or a batch of both")
+    dev = _dev(frames)
+    single = frames.dim() == 3
+    p = patch.unsqueeze(0) if single else patch
+    in_place = out is frames
+    f = frames.unsqueeze(0) if single else frames
+    if in_place and not f.is_contiguous():
+        raise ValueError("out=frames (in place) needs contiguous frames")
+    f = f.contiguous()
+    B, h, w, _ = f.shape
+    H, W = int(p.shape[1]), int(p.shape[2])
+    if (p.shape[0] != B or p.device != dev or p.stride(3) != 1 or p.stride(2) != 3 or p.stride(1) < 3 * W
+            or (B > 1 and p.stride(0) != H * p.stride(1))):
+        raise ValueError(f"patch must be a uint8 tensor [{B}, H, W, 3] on the frames' device with packed pixels and frames "
+                         f"H rows apart")
+    x1, y1, cw, ch = [int(v) for v in box]
+    if in_place:
+        o = f
+    elif out is None:
+        o = torch.empty_like(f)
+    else:
+        o = out.unsqueeze(0) if single and out.dim() == 3 else out
+        if tuple(o.shape) != tuple(f.shape) or o.dtype != torch.uint8 or o.device != dev or not o.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(frames.shape)} on the frames' device")
+    check(_lib.lib().d3f_paste_resize_cubic_u8(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, x1, y1, cw, ch, int(feather),
+                                               ptr(o), stream_ptr()))
+    return o[0] if single else o
+
+
 def image_grid_shape(images, nrow=3, padding=2, size=(1, 1)):
     """(GH, GW) of torchvision.utils.make_grid over `images` images of size = (H, W) (d3f_image_grid_shape; host only)"""
     dims = (C.c_int32 * 2)()

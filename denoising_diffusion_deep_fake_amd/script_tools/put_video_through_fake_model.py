@@ -1,10 +1,12 @@
 """Render a video through a trained face-swap model as real|fake frames side by side
 (d3f/script_tools/put_video_through_fake_model.py).  Per frame the reference crops at the centre, cv2.resize()s,
 predicts and concatenates on the host; here all of that is one device call per batch of frames
-(LitModule.predict_fake_frames -> Unet.predict_frames_u8), and cv2 only decodes and encodes."""
+(LitModule.predict_fake_frames -> Unet.predict_frames_u8), and cv2 only decodes and encodes.
+--output full writes the swapped video instead: the source's frames at their own size with the fake pasted back into
+the centre-crop box (LitModule.predict_fake_frames_full -> Unet.predict_frames_full_u8), still one device call per batch."""
 import argparse
 import datetime
-from contextlib import nullcontext
+from contextlib import ExitStack, nullcontext
 from pathlib import Path
 
 from ..train_deep_fake.lit_module import LitModule
@@ -22,7 +24,12 @@ def main():
         args.width,
         args.height,
         batch_frames=args.batch_frames,
+        output=args.output,
+        feather=args.feather,
         )
+
+
+OUTPUTS = ("pair", "full")
 
 
 def parse_command_line_arguments(argv=None):
@@ -34,17 +41,25 @@ def parse_command_line_arguments(argv=None):
     parser.add_argument("width", help="desired video width")
     parser.add_argument("height", help="desired video height")
     parser.add_argument("--batch-frames", type=int, default=1, help="frames per device call")
+    parser.add_argument("--output", choices=list(OUTPUTS), default="pair",
+                        help="pair: real|fake centre crops side by side at the network's size; full: the source's frames "
+                             "at their own size with the fake pasted back into the crop box")
+    parser.add_argument("--feather", type=int, default=None,
+                        help="--output full: width in source pixels of the ramp over which the fake fades into the frame "
+                             "(default: min(crop_w, crop_h) // 16)")
 
     return parser.parse_args(argv)
 
 
 class RenderFakeVideo():
     """frames=: an iterable of decoded BGR frames instead of the video file; sink=: a callable that takes each real|fake
-    frame instead of the .mp4 writer; model=: a loaded LitModule instead of the checkpoint.  With both hooks no video
-    file is touched and cv2 is not needed."""
+    frame (output="full": each full frame) instead of the .mp4 writer; model=: a loaded LitModule instead of the
+    checkpoint.  With both hooks no video file is touched and cv2 is not needed.
+    output="full" takes the writer's size from the first frame, so the writer is opened when the first batch arrives: a
+    source without frames leaves no output file (output="pair" knows its size up front and leaves an empty video)."""
 
     def __init__(self, video_path, checkpoint_path, model_a_or_b, image_width, image_height, batch_frames=1,
-                 frames=None, sink=None, model=None):
+                 frames=None, sink=None, model=None, output="pair", feather=None):
 
         self.video_path = Path(video_path)
         self.checkpoint_path = Path(checkpoint_path) if checkpoint_path is not None else None
@@ -54,6 +69,10 @@ class RenderFakeVideo():
         self.batch_frames = int(batch_frames)
         if self.batch_frames < 1:
             raise ValueError("batch_frames is at least 1")
+        if output not in OUTPUTS:
+            raise ValueError(f"output is one of {OUTPUTS}, not {output!r}")
+        self.output = output
+        self.feather = None if feather is None else int(feather)
         self.frames = frames
         self.sink = sink
 
@@ -62,7 +81,10 @@ class RenderFakeVideo():
 
         self.model = model if model is not None else self.load_model_from_checkpoint()
 
-        self.render_real_fake_video()
+        if self.output == "full":
+            self.render_full_video()
+        else:
+            self.render_real_fake_video()
 
     def load_model_from_checkpoint(self):
         model = LitModule.load_from_checkpoint(self.checkpoint_path)
@@ -88,11 +110,26 @@ class RenderFakeVideo():
                 for frame in real_and_fake[:real_frames]:  # the padding of a short last batch is dropped
                     write(frame)
 
-    def get_output_video_path(self):
+    def render_full_video(self):
+        frames = self.frames if self.frames is not None else open_video_as_generator(self.video_path)
+
+        with ExitStack() as stack:
+            write = self.sink
+            for batch, real_frames in batches(frames, self.batch_frames):
+                if write is None:  # the writer takes the source's size, read off the first frame
+                    h, w = batch.shape[1:3]
+                    write = stack.enter_context(VideoWriter(str(self.get_output_video_path("_full")), w, h,
+                                                            self.get_input_video_properties())).write
+                full = self.model.predict_fake_frames_full(batch, self.model_a_or_b, self.image_width,
+                                                           self.image_height, feather=self.feather)
+                for frame in full[:real_frames]:  # the padding of a short last batch is dropped
+                    write(frame)
+
+    def get_output_video_path(self, tag=""):
 
         datetime_str = datetime.datetime.now().strftime("%Y%m%d_%a_%H%M%S")
 
-        output_name = f"{self.video_path.stem}_model_{self.model_a_or_b}_{datetime_str}.mp4"
+        output_name = f"{self.video_path.stem}_model_{self.model_a_or_b}{tag}_{datetime_str}.mp4"
         output_path = self.video_path.with_name(output_name)
         return output_path
 

@@ -487,6 +487,59 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         torch.cuda.current_stream().synchronize()
         return host_out.numpy().copy()
 
+    def _frame_path_inputs(self, raw_bgr_batch, model_a_or_b, who):
+        """what a raw-frame entry needs before it touches the device: the model with the OTHER domain's mean / std (as
+        `predict_fake`), in eval mode, and the frames as one contiguous uint8 [B, h, w, 3] array"""
+        p = self.hparams
+        if model_a_or_b == "a":
+            model, mean, std = self.model_a, p.mean_b, p.std_b
+        elif model_a_or_b == "b":
+            model, mean, std = self.model_b, p.mean_a, p.std_a
+        else:
+            raise ValueError("model_a_or_b is 'a' or 'b'")
+        if model.training:
+            raise RuntimeError(f"{who} is the eval-mode frame path: call .eval() first")
+        raw = np.ascontiguousarray(raw_bgr_batch)
+        if raw.dtype != np.uint8 or raw.ndim != 4 or raw.shape[-1] != 3:
+            raise ValueError(f"{who} expects uint8 frames [B, h, w, 3] in BGR order")
+        return model, mean, std, raw
+
+    def _staging(self, cache, key, shape):
+        """a pinned host buffer and a device buffer of `shape`, kept in the dict `cache` under `key`"""
+        bufs = cache.get(key)
+        if bufs is None:
+            bufs = cache[key] = (torch.empty(shape, dtype=torch.uint8).pin_memory(),
+                                 torch.empty(shape, dtype=torch.uint8, device=self.device))
+        return bufs
+
+    @torch.no_grad()
+    def predict_fake_frames_full(self, raw_bgr_batch, model_a_or_b, width, height, feather=None, with_pair=False):
+        """host frames [B, h, w, 3] (uint8 BGR, any size) -> host frames of the same shape with the centre-crop box replaced
+        by the fake, resized back to the box and blended in over `feather` source pixels (None: `ops.default_feather`):
+        the swapped video at the source's size, in one device call (`Unet.predict_frames_full_u8`).  with_pair: returns
+        (full, pair), pair being what `predict_fake_frames` returns.  Models and statistics as `predict_fake_frames`;
+        pinned and device staging is kept per shape in a cache of its own."""
+        model, mean, std, raw = self._frame_path_inputs(raw_bgr_batch, model_a_or_b, "predict_fake_frames_full")
+        width, height = int(width), int(height)
+        if not hasattr(self, "_frames_full_buffers"):
+            self._frames_full_buffers = {}
+        cache, key = self._frames_full_buffers, (raw.shape, id(model), width, height)
+        host_in, dev_in = self._staging(cache, key + ("in",), raw.shape)
+        host_full, dev_full = self._staging(cache, key + ("full",), raw.shape)
+        host_pair, dev_pair = self._staging(cache, key + ("pair",), (raw.shape[0], height, 2 * width, 3))
+        host_in.copy_(torch.from_numpy(raw))
+        dev_in.copy_(host_in, non_blocking=True)
+        model.predict_frames_full_u8(dev_in, (height, width), mean, std, feather=feather,
+                                     graph=bool(self.hparams.get("inference_graph", False)), out=dev_full,
+                                     pair_out=dev_pair)
+        host_full.copy_(dev_full, non_blocking=True)
+        if with_pair:
+            host_pair.copy_(dev_pair, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        if with_pair:
+            return host_full.numpy().copy(), host_pair.numpy().copy()
+        return host_full.numpy().copy()
+
     def cv2_to_tensor_normalised(self, image_bgr, mean, std):
         image_rgb = np.ascontiguousarray(image_bgr[:, :, ::-1])  # cv2.COLOR_BGR2RGB
         tensor = torch.from_numpy(image_rgb).float().to(self.device)

@@ -857,6 +857,59 @@ class Unet(nn.Module, _NetsRuntime):
         eng.keep = (x, out)  # the captured graph bakes these pointers in: keep them alive with the engine
         return out[0] if single else out
 
+    @torch.no_grad()
+    def predict_frames_full_u8(self, raw_bgr, size, mean, std, feather=None, graph=True, out=None, pair_out=None):
+        """`predict_frames_u8`, then the fake pasted back into the source frames: uint8 BGR frames [h,w,3] or [B,h,w,3] on
+        the HIP device -> the frames at their own size with the centre-crop box replaced by the fake, resized back
+        (`ops.paste_resize_cubic_u8`) and blended in over `feather` source pixels (None: `ops.default_feather` of the
+        box), all in one C call.  Returns the full frames.  pair_out: a [B,H,2W,3] buffer, filled as `predict_frames_u8`
+        fills it (allocated when None: it stages the fake).  out=raw_bgr pastes in place (graph=False only).  `graph=True`
+        replays a hipGraph of its own, captured per set of buffers, frame size, box and feather."""
+        from . import ops
+        if raw_bgr.dtype != torch.uint8 or raw_bgr.shape[-1] != 3 or raw_bgr.dim() not in (3, 4):
+            raise ValueError("predict_frames_full_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3] in BGR order")
+        if raw_bgr.device.type != "cuda":
+            raise D3FError("predict_frames_full_u8 needs frames on the HIP device (no CPU fallback)")
+        single = raw_bgr.dim() == 3
+        x = raw_bgr.unsqueeze(0) if single else raw_bgr
+        in_place = out is raw_bgr
+        if in_place and not x.is_contiguous():
+            raise ValueError("out=raw_bgr (in place) needs contiguous frames")
+        x = x.contiguous()
+        B, h, w, _ = x.shape
+        H, W = int(size[0]), int(size[1])
+        if H % 32 or W % 32:
+            raise RuntimeError(f"Wrong input shape height={H}, width={W}. Expected image height and width "
+                               f"divisible by 32.")
+        x1, y1, cw, ch = ops.center_crop_box(h, w, W, H)
+        feather = ops.default_feather(cw, ch) if feather is None else int(feather)
+        self._ensure_flat(x.device)
+        eng = self._engine(B, H, W, x.device)
+        self._pack_if_needed(eng)
+        shape = (B, H, 2 * W, 3)
+        if pair_out is None:
+            pair_out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+        elif (tuple(pair_out.shape) != shape or pair_out.dtype != torch.uint8 or not pair_out.is_contiguous()
+              or pair_out.device != x.device):
+            raise ValueError(f"pair_out must be a contiguous uint8 tensor of shape {shape} on the input's device")
+        if in_place:
+            full = x
+        elif out is None:
+            full = torch.empty_like(x)
+        else:
+            full = out.unsqueeze(0) if single and out.dim() == 3 else out
+            if (tuple(full.shape) != tuple(x.shape) or full.dtype != torch.uint8 or not full.is_contiguous()
+                    or full.device != x.device):
+                raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(raw_bgr.shape)} on the input's device")
+        rt = self._rt
+        m = (C.c_float * 3)(*[float(v) for v in mean])
+        sd = (C.c_float * 3)(*[float(v) for v in std])
+        check(_lib.lib().d3f_unet_predict_frames_full_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), h, w, x1, y1, cw,
+                                                         ch, feather, ptr(pair_out), ptr(full), m, sd, ptr(eng.workspace),
+                                                         1 if graph else 0, stream_ptr()))
+        eng.keep_full = (x, pair_out, full)  # the captured graph bakes these pointers in: keep them alive with the engine
+        return full[0] if single else full
+
     def export_activation(self, name):
         """debugging / parity tests: an internal tensor of the MOST RECENT forward (+ backward) as NCHW f32 --
         "<conv name>:y" raw conv output, ":a" post BatchNorm(+residual)+ReLU activation, ":da" gradient w.r.t. that

@@ -184,6 +184,20 @@ int d3f_unet_predict_u8(d3f_unet_t h, const float* params, float* bnstats, const
 int d3f_unet_predict_frames_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
                                int src_w, int x1, int y1, int cw, int ch, uint8_t* pair_out, const float mean[3],
                                const float std[3], void* workspace, int use_graph, void* stream);
+/* The swapped video at the source's size (nothing in the reference: its tool stops at the real|fake pair).  Exactly the
+ * launches of d3f_unet_predict_frames_u8 into pair_out [B][H][2W][3], then ONE d3f_paste_resize_cubic_u8 launch (below):
+ * patch = the right half of pair_out (row stride 6 * W), frame = raw_in, out = full_out [B][src_h][src_w][3], same box.
+ * pair_out holds the bytes d3f_unet_predict_frames_u8 writes, full_out the bytes d3f_paste_resize_cubic_u8 gives on them,
+ * both bit for bit; the caller owns both buffers (pair_out doubles as the fake's staging buffer; nothing is allocated).
+ * full_out == raw_in pastes in place and is refused together with use_graph: a replay would read frames it has already
+ * overwritten.  use_graph != 0: captured on first use per set of pointers (full_out included), frame size, crop box,
+ * feather and mean / std, in a graph slot of its own (alternating with d3f_unet_predict_frames_u8 re-captures neither).
+ * Refused as d3f_unet_predict_frames_u8 refuses: a pair handle, a null argument, a network that is not 3 -> 3 channels;
+ * and whatever either operator refuses, before any capture. */
+int d3f_unet_predict_frames_full_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
+                                    int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* pair_out,
+                                    uint8_t* full_out, const float mean[3], const float std[3], void* workspace,
+                                    int use_graph, void* stream);
 /* gradients of every parameter (written, not accumulated) for the preceding training forward.
  * The backward pass is cut into d3f_unet_num_segments() buckets so a data-parallel caller can
  * all-reduce bucket k while bucket k+1 computes: run segments [seg_begin, seg_end) in order 0..n;
@@ -443,6 +457,28 @@ int d3f_u8rgb_normalise(const uint8_t* in_hwc, float* out_nchw, int B, int H, in
  * is not claimed.  Refused: a box outside the frame, non-positive sizes, extents above 16384, a stride below 3 * W. */
 int d3f_crop_resize_cubic_u8(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch, uint8_t* dst,
                              int H, int W, int64_t dst_row_stride_bytes, void* stream);
+/* The inverse of d3f_crop_resize_cubic_u8 with a blend in the epilogue: paste a patch back into the frames it was cropped
+ * from.  patch [B][H][W][3] uint8, rows patch_row_stride_bytes apart (>= 3 * W; frames H rows apart; 6 * W reads the right
+ * half of a pair_out buffer); frame and out [B][src_h][src_w][3] uint8, packed; (x1, y1, cw, ch) the box the crop was taken
+ * from.  Definition (the acceptance contract; tests/paste_restatement.py restates it in float64):
+ *   - outside the box: out is the byte of frame;
+ *   - inside, at box pixel (i, j), row i in [0, ch), column j in [0, cw): v = the fp32 value of d3f_crop_resize_cubic_u8's
+ *     definition for the resize H x W -> ch x cw of the whole patch (the same exact integer source coordinates, Keys
+ *     weights with A = -0.75, taps clamped inside the patch, horizontal then vertical pass in fp32 without contraction --
+ *     the same device functions), taken BEFORE that operator's rintf; then v = fminf(fmaxf(v, 0), 255);
+ *   - the ramp, per axis: d_y = min(i, ch - 1 - i), a_y = (float)min(d_y + 1, feather + 1) / (float)(feather + 1) (one
+ *     IEEE fp32 division of exact integers), a_x likewise from j and cw, a = a_y * a_x;
+ *   - the blend: o = a * v + (1.f - a) * s with s the frame's byte, both products and the sum rounded separately; the byte
+ *     is rintf(o) (half to even) clamped to 0..255.  Where a == 1 that is rintf(v): the byte
+ *     d3f_crop_resize_cubic_u8(patch -> ch x cw) writes.  feather == 0: the whole box is that.
+ * out == frame runs in place (a lane reads only the frame bytes it writes; only the tiles that meet the box are
+ * launched); with out != frame one launch covers the whole frame.  Refused before any device call: null pointers, B < 0
+ * or B > 65535 (B == 0 launches nothing), non-positive sizes, a box outside the frame, extents above 16384, feather < 0
+ * or > 16384, a patch stride below 3 * W, frame and out that overlap in part, a patch whose bytes (first pixel of the first patch to
+ * last pixel of the last) overlap out -- a tile reads its part of the patch while other tiles write out. */
+int d3f_paste_resize_cubic_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                              const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather,
+                              uint8_t* out, void* stream);
 
 /* log_batch_as_image_grid of the three LitModules (d3f/train_deep_fake/lit_module.py:235-249,
  * d3f/train_denoiser/lit_module.py:157-171, d3f/balance_training_images/lit_module.py:197-211):

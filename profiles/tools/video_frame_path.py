@@ -4,6 +4,10 @@
                  global-tap form at 2160x3840 -> 64x64
   frames       : Unet.predict_frames_u8 (resize + forward + real|fake pair), B = 1 eager / hipGraph, B = 8 eager
   yardstick    : Unet.predict_u8 on frames that are ALREADY 448x448 (what the parent commit offers), same B and mode
+  paste        : d3f_paste_resize_cubic_u8 alone (448x448 -> the 1080x1080 centre box of the 1080x1920 frame, default
+                 feather 67), out of place (the whole frame is written) and in place (only the box's tiles), B = 1 and 8
+  full         : Unet.predict_frames_full_u8 (frames + paste), B = 1 eager / hipGraph, B = 8 eager; the added time per
+                 frame against predict_frames_u8 in the same run, next to the byte-bound estimate of the paste
 
 Back-to-back enqueues on one stream, ITERS iterations after WARMUP, the forms alternating in ROUNDS rounds; the figure is
 the median round's time per call (and per frame).  Host work of the reference's loop (cv2.resize on one CPU thread, the
@@ -66,7 +70,14 @@ def main():
         resized = torch.empty_like(small)
         pair = torch.empty((B, SIZE[0], 2 * SIZE[1], 3), dtype=torch.uint8, device="cuda")
         fake = torch.empty_like(small)
+        full, work = torch.empty_like(raw), raw.clone()
+        box = ops.center_crop_box(RAW[0], RAW[1], SIZE[1], SIZE[0])
+        feather = ops.default_feather(box[2], box[3])
+        pair2 = torch.empty_like(pair)
         forms = {
+            f"paste_B{B}": lambda: ops.paste_resize_cubic_u8(small, raw, box, feather, out=full),
+            f"paste_in_place_B{B}": lambda: ops.paste_resize_cubic_u8(small, work, box, feather, out=work),
+            f"full_eager_B{B}": lambda: net.predict_frames_full_u8(raw, SIZE, MEAN, STD, graph=False, out=full, pair_out=pair2),
             f"resize_B{B}": lambda: ops.crop_resize_cubic_u8(raw, SIZE, out=resized),
             f"frames_eager_B{B}": lambda: net.predict_frames_u8(raw, SIZE, MEAN, STD, graph=False, out=pair),
             f"predict_u8_eager_B{B}": lambda: net.predict_u8(small, MEAN, STD, graph=False, out=fake),
@@ -74,6 +85,8 @@ def main():
         if B == 1:
             forms[f"frames_graph_B{B}"] = lambda: net.predict_frames_u8(raw, SIZE, MEAN, STD, graph=True, out=pair)
             forms[f"predict_u8_graph_B{B}"] = lambda: net.predict_u8(small, MEAN, STD, graph=True, out=fake)
+            forms[f"full_graph_B{B}"] = lambda: net.predict_frames_full_u8(raw, SIZE, MEAN, STD, graph=True, out=full,
+                                                                          pair_out=pair2)
         for name, (med, lo, hi) in compare(forms, args.warmup, args.iters, args.rounds).items():
             print(f"{name:24s} {med:9.1f} us per call (min {lo:.1f}, max {hi:.1f})   {med / B:9.1f} us per frame")
             result["us_per_call"][name] = round(med, 1)
@@ -91,6 +104,17 @@ def main():
     # bytes the resize must move per frame: the crop once, the output once
     need = 1080 * 1080 * 3 + SIZE[0] * SIZE[1] * 3
     result["resize_GBps_B8"] = round(8 * need / (u["resize_B8"] * 1e-6) / 1e9, 1)
+    # full-frame output: what the paste adds per frame to predict_frames_u8 of the same run, and the least the paste could
+    # take -- the frame read once and written once (12.4 MB; the 0.6 MB patch is not counted) at 6.3 TB/s achievable HBM
+    frame_bytes = 2 * RAW[0] * RAW[1] * 3
+    result["paste_bytes_per_frame"] = frame_bytes
+    result["paste_byte_bound_us_per_frame"] = round(frame_bytes / 6.3e12 * 1e6, 2)
+    result["paste_GBps_B8"] = round(8 * frame_bytes / (u["paste_B8"] * 1e-6) / 1e9, 1)
+    result["full_added_us_per_frame"] = {
+        "eager_B1": round(u["full_eager_B1"] - u["frames_eager_B1"], 1),
+        "graph_B1": round(u["full_graph_B1"] - u["frames_graph_B1"], 1),
+        "eager_B8": round((u["full_eager_B8"] - u["frames_eager_B8"]) / 8, 1),
+    }
     print(json.dumps(result))
 
 
