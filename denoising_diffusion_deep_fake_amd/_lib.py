@@ -22,6 +22,9 @@ HEAD_ACTIVATIONS = {None: ACT_IDENTITY, "sigmoid": ACT_SIGMOID, "tanh": ACT_TANH
                     "logsoftmax": ACT_LOGSOFTMAX, "clamp": ACT_CLAMP}
 
 
+RESAMPLE_CUBIC, RESAMPLE_CUBIC_AA = 0, 1  # D3F_RESAMPLE_*: how the frame entries resize the crop to the network's size
+
+
 class D3FError(RuntimeError):
     pass
 
@@ -89,6 +92,8 @@ PROTOTYPES = {
     "d3f_unet_pair_backward": (_i, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), _p, _i, _i, _i, _p]),
     "d3f_unet_set_head_activation": (_i, [_p, _i]),
     "d3f_unet_head_activation": (_i, [_p]),
+    "d3f_unet_set_frame_resample": (_i, [_p, _i]),
+    "d3f_unet_frame_resample": (_i, [_p]),
     "d3f_unet_num_params": (_i, [_p]),
     "d3f_unet_param_info": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(C.c_int32), C.POINTER(_i), C.POINTER(_i64)]),
     "d3f_unet_param_floats": (_i64, [_p]),
@@ -116,6 +121,7 @@ PROTOTYPES = {
     "d3f_unet_predict_u8": (_i, [_p, _p, _p, _p, _p, C.POINTER(_f), C.POINTER(_f), _p, _i, _p]),
     "d3f_unet_predict_frames_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, C.POINTER(_f), C.POINTER(_f), _p, _i, _p]),
     "d3f_crop_resize_cubic_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i64, _p]),
+    "d3f_crop_resize_cubic_aa_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i64, _p]),
     "d3f_paste_resize_cubic_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "d3f_unet_predict_frames_full_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, C.POINTER(_f), C.POINTER(_f),
                                              _p, _i, _p]),

@@ -198,6 +198,12 @@ int d3f_unet_set_head_activation(d3f_unet_t h, int act) {
   return h->e.set_head_activation(act);
 }
 int d3f_unet_head_activation(d3f_unet_t h) { return h ? h->e.head_activation() : -1; }
+int d3f_unet_set_frame_resample(d3f_unet_t h, int mode) {
+  D3F_CHECK(h, "unet_set_frame_resample: null handle");
+  if (int rc = single_net(h, "unet_set_frame_resample", "has no frame entries (run each network alone)")) return rc;
+  return h->e.set_frame_resample(mode);
+}
+int d3f_unet_frame_resample(d3f_unet_t h) { return h ? h->e.frame_resample() : -1; }
 int d3f_unet_num_params(d3f_unet_t h) { return h ? (int)h->e.params.size() : -1; }
 int d3f_unet_param_info(d3f_unet_t h, int i, char* name, int name_cap, int32_t shape[4], int* ndim,
                         int64_t* offset) {
@@ -744,6 +750,13 @@ int d3f_crop_resize_cubic_u8(const uint8_t* src, int B, int src_h, int src_w, in
   D3F_CHECK(src && dst, "crop_resize_cubic_u8: null argument");
   return crop_resize_cubic_u8_launch(src, B, src_h, src_w, x1, y1, cw, ch, dst, H, W, (long)dst_row_stride_bytes,
                                      (hipStream_t)stream);
+}
+
+int d3f_crop_resize_cubic_aa_u8(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch,
+                                uint8_t* dst, int H, int W, int64_t dst_row_stride_bytes, void* stream) {
+  D3F_CHECK(src && dst, "crop_resize_cubic_aa_u8: null argument");
+  return crop_resize_cubic_aa_u8_launch(src, B, src_h, src_w, x1, y1, cw, ch, dst, H, W, (long)dst_row_stride_bytes,
+                                        (hipStream_t)stream);
 }
 
 int d3f_paste_resize_cubic_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,

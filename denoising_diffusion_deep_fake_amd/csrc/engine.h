@@ -151,6 +151,12 @@ class UnetEngine {
   // A pair's two networks share the setting.  A change drops the captured graphs, as a pointer change does.
   int set_head_activation(int act);
   int head_activation() const { return head_act_; }
+  // How predict_frames_u8 / predict_frames_full_u8 resize the crop to the network's size (D3F_RESAMPLE_*): the plain
+  // bicubic (the default: exactly the launches of an engine without the setting) or the antialiased one
+  // (crop_resize_cubic_aa, resize.hip).  The paste is not touched.  A change drops the two captured frame graphs.
+  enum { FRAME_RESAMPLE_CUBIC = 0, FRAME_RESAMPLE_CUBIC_AA = 1 };
+  int set_frame_resample(int mode);
+  int frame_resample() const { return frame_resample_; }
   int export_tensor(const char* name, const void* ws, float* out_nchw, hipStream_t s) const;
   int export_shape(const char* name, int32_t dims[3]) const;
 
@@ -242,6 +248,9 @@ class UnetEngine {
   mutable const void* g_step_ws_ = nullptr;
   mutable hipEvent_t ev_gin_ = nullptr, ev_gout_ = nullptr;
   int head_act_ = 0;          // HEAD_ACT_IDENTITY
+  int frame_resample_ = FRAME_RESAMPLE_CUBIC;
+  // the host-side argument check of the frame entries' resize, in the mode that is set
+  int frame_resize_check(int src_h, int src_w, int x1, int y1, int cw, int ch) const;
   // NCHW fp32 head output: predict_u8's, and z of an activated head, which the head of the backward pass turns into dz IN
   // PLACE (the bias gradient's channel sum reads that): the workspace is the one of a plan without activations
   size_t head_nchw_off = 0;

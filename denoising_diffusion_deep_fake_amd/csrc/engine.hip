@@ -695,6 +695,26 @@ int UnetEngine::set_head_activation(int act) {
   return 0;
 }
 
+int UnetEngine::set_frame_resample(int mode) {
+  D3F_CHECK(mode == FRAME_RESAMPLE_CUBIC || mode == FRAME_RESAMPLE_CUBIC_AA,
+            "frame resample: unknown mode %d (D3F_RESAMPLE_CUBIC, D3F_RESAMPLE_CUBIC_AA)", mode);
+  if (mode != frame_resample_) {
+    for (GraphSlot* slot : {&g_frames_, &g_frames_full_})  // they bake the resize launch in
+      if (slot->exec) {
+        (void)hipGraphExecDestroy(slot->exec);
+        slot->exec = nullptr;
+      }
+    frame_resample_ = mode;
+  }
+  return 0;
+}
+
+int UnetEngine::frame_resize_check(int src_h, int src_w, int x1, int y1, int cw, int ch) const {
+  if (frame_resample_ == FRAME_RESAMPLE_CUBIC_AA)
+    return crop_resize_cubic_aa_check(B, src_h, src_w, x1, y1, cw, ch, H, W, 6L * W);
+  return crop_resize_cubic_check(B, src_h, src_w, x1, y1, cw, ch, H, W, 6L * W);
+}
+
 void UnetEngine::drop_graphs() const {
   for (GraphSlot* slot : {&g_predict_, &g_eval_, &g_frames_, &g_frames_full_})
     if (slot->exec) {
@@ -729,8 +749,10 @@ int UnetEngine::predict_frames_u8_launches(const float* params_, float* bnstats,
                                            uint8_t* pair_out, const float mean255[3], const float std255[3], char* ws,
                                            hipStream_t s) const {
   // one launch writes the real half of the pair and, from the same rounded bytes, the network input
-  if (int rc = crop_resize_cubic_u8_nhwc_launch(dtype, raw_in, B, geo[0], geo[1], geo[2], geo[3], geo[4], geo[5], pair_out,
-                                                H, W, 6L * W, ws + tensors[t_x].off, tensors[t_x].C, mean255, std255, s))
+  const auto resize = frame_resample_ == FRAME_RESAMPLE_CUBIC_AA ? crop_resize_cubic_aa_u8_nhwc_launch
+                                                                 : crop_resize_cubic_u8_nhwc_launch;
+  if (int rc = resize(dtype, raw_in, B, geo[0], geo[1], geo[2], geo[3], geo[4], geo[5], pair_out, H, W, 6L * W,
+                      ws + tensors[t_x].off, tensors[t_x].C, mean255, std255, s))
     return rc;
   float* head_out = reinterpret_cast<float*>(ws + head_nchw_off);
   if (int rc = forward_body(params_, bnstats, head_out, ws, 0, s, nullptr, false)) return rc;
@@ -749,7 +771,7 @@ int UnetEngine::predict_frames_u8(const float* params_, float* bnstats, const ui
     m255[c] = mean[c] * 255.0f;
     s255[c] = stdv[c] * 255.0f;
   }
-  if (int rc = crop_resize_cubic_check(B, src_h, src_w, x1, y1, cw, ch, H, W, 6L * W)) return rc;
+  if (int rc = frame_resize_check(src_h, src_w, x1, y1, cw, ch)) return rc;
   const int geo[6] = {src_h, src_w, x1, y1, cw, ch};
   if (!use_graph) return predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, s);
   const GraphKey key = {{params_, bnstats, raw_in, pair_out, ws_},
@@ -774,7 +796,7 @@ int UnetEngine::predict_frames_full_u8(const float* params_, float* bnstats, con
     m255[c] = mean[c] * 255.0f;
     s255[c] = stdv[c] * 255.0f;
   }
-  if (int rc = crop_resize_cubic_check(B, src_h, src_w, x1, y1, cw, ch, H, W, 6L * W)) return rc;
+  if (int rc = frame_resize_check(src_h, src_w, x1, y1, cw, ch)) return rc;
   if (int rc = paste_resize_cubic_check(pair_out + 3L * W, raw_in, full_out, B, H, W, 6L * W, src_h, src_w, x1, y1, cw, ch,
                                         feather))
     return rc;

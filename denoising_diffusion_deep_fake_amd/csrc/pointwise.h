@@ -124,6 +124,15 @@ int crop_resize_cubic_u8_launch(const uint8_t* src, int B, int src_h, int src_w,
 int crop_resize_cubic_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw,
                                      int ch, uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
                                      const float mean255[3], const float std255[3], hipStream_t stream);
+// the antialiased form of the three above (Pillow's bicubic: the window widens with the scale; include/d3f_hip.h:
+// d3f_crop_resize_cubic_aa_u8); refuses what they refuse and a crop above 32 times the output on an axis
+int crop_resize_cubic_aa_check(int B, int src_h, int src_w, int x1, int y1, int cw, int ch, int H, int W,
+                               long dst_row_stride);
+int crop_resize_cubic_aa_u8_launch(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch,
+                                   uint8_t* dst, int H, int W, long dst_row_stride, hipStream_t stream);
+int crop_resize_cubic_aa_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw,
+                                        int ch, uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
+                                        const float mean255[3], const float std255[3], hipStream_t stream);
 // full-frame output (resize.hip): patch [B][H][W][3], rows patch_row_stride bytes apart, resized to the box (x1, y1, cw, ch)
 // of frame [B][src_h][src_w][3] with the same arithmetic and blended in over a ramp of `feather` pixels; the rest of out
 // is the frame.  out == frame runs in place.  (_check: the host-side argument check, for a caller that must refuse

@@ -22,6 +22,9 @@
 //
 // Staging and the two passes are device functions (resize_stage, resize_value): the paste kernel at the end of this file,
 // the inverse of this operator, runs the same arithmetic on a patch instead of a crop.
+//
+// The antialiased form (d3f_crop_resize_cubic_aa_u8: Pillow's bicubic, whose window widens with the scale) has a kernel of
+// its own behind the plain one.
 #include "common.h"
 #include "pointwise.h"
 
@@ -146,6 +149,28 @@ __device__ __forceinline__ void resize_value(const uint8_t* patch, const ResizeS
   }
 }
 
+// the epilogue of the crop kernels: rintf and clamp of a pixel's fp32 value v -> its three bytes at o and, ACT, the
+// normalised network input at a (u8bgr_to_nhwc_kernel on the rounded byte, operation for operation)
+template <typename T, bool ACT>
+__device__ __forceinline__ void resize_store(const float v[3], uint8_t* o, T* a, int Cpad, float m0, float m1, float m2,
+                                             float s0, float s1, float s2) {
+  uint8_t px[3];
+  for (int c = 0; c < 3; ++c) {  // rintf, clamp
+    const float r = rintf(v[c]);
+    px[c] = (uint8_t)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r));
+  }
+  o[0] = px[0];
+  o[1] = px[1];
+  o[2] = px[2];
+  if (ACT) {
+    const float r = ((float)px[2] - m0) / s0, gg = ((float)px[1] - m1) / s1, bb = ((float)px[0] - m2) / s2;
+    a[0] = from_f32<T>(r);
+    a[1] = from_f32<T>(gg);
+    a[2] = from_f32<T>(bb);
+    for (int c = 3; c < Cpad; ++c) a[c] = from_f32<T>(0.f);
+  }
+}
+
 template <typename T, bool ACT, bool STAGED>
 __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void crop_resize_cubic_kernel(
     const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, T* __restrict__ act, ResizeGeom g, int Cpad, float m0,
@@ -165,25 +190,10 @@ __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void crop_resize_cubic_kerne
   }
   const int ox = ox0 + (tid % RESIZE_TW), oy = oy0 + (tid / RESIZE_TW);
   if (ox >= g.W || oy >= g.H) return;
-  float v[3], acc[3];
+  float v[3];
   resize_value<STAGED>(patch, rs, t, ox, oy, v);
-  uint8_t px[3];
-  for (int c = 0; c < 3; ++c) {  // rintf, clamp
-    acc[c] = rintf(v[c]);
-    px[c] = (uint8_t)(acc[c] < 0.f ? 0.f : (acc[c] > 255.f ? 255.f : acc[c]));
-  }
-  uint8_t* o = dst + ((long)b * g.H + oy) * g.dst_row_stride + (long)ox * 3;
-  o[0] = px[0];
-  o[1] = px[1];
-  o[2] = px[2];
-  if (ACT) {  // u8bgr_to_nhwc_kernel on the rounded byte, operation for operation
-    const float r = ((float)px[2] - m0) / s0, gg = ((float)px[1] - m1) / s1, bb = ((float)px[0] - m2) / s2;
-    T* a = act + (((long)b * g.H + oy) * g.W + ox) * Cpad;
-    a[0] = from_f32<T>(r);
-    a[1] = from_f32<T>(gg);
-    a[2] = from_f32<T>(bb);
-    for (int c = 3; c < Cpad; ++c) a[c] = from_f32<T>(0.f);
-  }
+  resize_store<T, ACT>(v, dst + ((long)b * g.H + oy) * g.dst_row_stride + (long)ox * 3,
+                       ACT ? act + (((long)b * g.H + oy) * g.W + ox) * Cpad : nullptr, Cpad, m0, m1, m2, s0, s1, s2);
 }
 
 // LDS bytes of the largest part of an n_h x n_w image a tile of a resize to out_h x out_w can need, and the pitch of its
@@ -259,7 +269,235 @@ int crop_resize_cubic_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int s
   return resize_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, B, Cpad, mean255, std255, stream);
 }
 
-// ---- full-frame output: the inverse of the operator above with a blend in the epilogue ----
+// ---- antialiased form: Pillow's bicubic (torch's interpolate(mode="bicubic", antialias=True)) ----
+// include/d3f_hip.h: d3f_crop_resize_cubic_aa_u8 is the definition; tests/resize_aa_restatement.py restates it in float64.
+// An axis that shrinks by r widens the Keys kernel (A = -0.5) by r: up to 4 r + 1 taps, 129 at the ratio limit of 32, and a
+// tile's source footprint grows with r on both axes -- far beyond LDS at r = 16.  So nothing is staged whole.  One
+// workgroup per 32 x 8 tile of output pixels:
+//   * the normalised weights of the tile's 32 columns and 8 rows are computed once, as two tables in LDS (eight lanes per
+//     output index: the taps t = lane, lane + 8, ... and their partial sum);
+//   * the source rows the tile's 8 output rows read are streamed in chunks of AA_ROWS: the columns the tile reads of each
+//     row are staged with aligned dword loads (as resize_stage does), the horizontal filter turns a staged row into 32
+//     fp32 pixels of a row buffer in LDS (lane = one column of one row), and each lane -- now one output pixel -- adds the
+//     chunk's rows that lie inside its window to its vertical sum.
+// Loop bounds are the table's (first tap, count), which come from xmin / xmax alone: every index lies inside the crop.
+constexpr int AA_ROWS = 8;        // source rows per chunk: one per 32 lanes of the horizontal filter
+constexpr int AA_MAX_RATIO = 32;  // n_in <= 32 n_out per axis
+constexpr int AA_LDS_LIMIT = 64 * 1024;
+
+struct AaGeom {
+  int src_h, src_w, x1, y1, cw, ch, H, W;
+  long dst_row_stride;
+  int ntx, nty;  // floats per table row: at least the most taps of an output column / row (aa_max_taps), odd
+  int pitch;     // bytes of one staged source row (a multiple of 4)
+};
+
+// the most taps an output index of an axis n_in -> n_out has: xmax - xmin <= floor(2 s) + 1, 2 s = 4 n_in / n_out or 4
+static int aa_max_taps(int n_in, int n_out) { return (n_in >= n_out ? (int)(4L * n_in / n_out) : 4) + 1; }
+// the most source columns RESIZE_TW consecutive output columns read: xmax(i + n) - xmin(i) <= floor(n n_in / n_out + 2 s) + 1
+static int aa_max_cols(int n_in, int n_out) {
+  const long S = n_in >= n_out ? 4L * n_in : 4L * n_out;
+  const long cols = ((long)(RESIZE_TW - 1) * n_in + S) / n_out + 1;
+  return (int)(cols < n_in ? cols : n_in);
+}
+
+__device__ __forceinline__ float keys_aa(float x) {  // x >= 0, A = -0.5
+  const float A = -0.5f;
+  if (x < 1.f) return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
+  if (x < 2.f) return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
+  return 0.f;
+}
+
+// The taps of output indices i0 .. i0 + n_idx - 1 (n_idx <= 32) of an axis n_in -> n_out: first tap lo[j], count cnt[j] and
+// the normalised weights wt[j * nt + t], t < cnt[j].  Eight lanes per index: lane `sub` takes the taps t = sub, sub + 8, ...
+// and their sum p_sub (in that order); the weights' sum is ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)); each weight is
+// divided by it.  Called by all 256 lanes (two barriers inside); part: 256 floats of scratch.
+__device__ __forceinline__ void aa_axis_table(float* wt, int* lo, int* cnt, float* part, int i0, int n_idx, int n_in,
+                                              int n_out, int nt, int tid) {
+  const int j = tid >> 3, sub = tid & 7;
+  int count = 0;
+  float p = 0.f;
+  if (j < n_idx) {
+    const bool down = n_in >= n_out;
+    const int S = down ? 4 * n_in : 4 * n_out, D = down ? 2 * n_in : 2 * n_out;
+    const int c2 = (2 * (i0 + j) + 1) * n_in, den = 2 * n_out;  // below 2^30 for extents up to RESIZE_MAX_EXTENT
+    const int a = c2 - S + n_out;
+    const int first = a > 0 ? a / den : 0;  // max(floor(a / den), 0)
+    const int end = min((c2 + S + n_out) / den, n_in);
+    count = min(end - first, nt);  // (end - first <= aa_max_taps <= nt)
+    for (int t = sub; t < count; t += 8) {
+      const int num = (2 * (first + t) + 1) * n_out - c2;  // |num| < 2^24: exact in fp32
+      const float w = keys_aa(fabsf((float)num / (float)D));
+      wt[j * nt + t] = w;
+      p = p + w;
+    }
+    if (sub == 0) {
+      lo[j] = first;
+      cnt[j] = count;
+    }
+  }
+  part[tid] = p;
+  __syncthreads();
+  if (j < n_idx) {
+    const float* q = part + (j << 3);
+    const float sum = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+    for (int t = sub; t < count; t += 8) wt[j * nt + t] = wt[j * nt + t] / sum;
+  }
+  __syncthreads();
+}
+
+template <typename T, bool ACT>
+__global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void crop_resize_cubic_aa_kernel(
+    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, T* __restrict__ act, AaGeom g, int Cpad, float m0, float m1,
+    float m2, float s0, float s1, float s2) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t aa_lds[];
+  // (aa_lds_bytes below is this layout)
+  float* wx = reinterpret_cast<float*>(aa_lds);     // [RESIZE_TW][ntx]
+  float* wy = wx + RESIZE_TW * g.ntx;               // [RESIZE_TH][nty]
+  float* hbuf = wy + RESIZE_TH * g.nty;             // [AA_ROWS][RESIZE_TW][3]: the horizontal pass of a chunk's rows
+  float* part = hbuf + AA_ROWS * RESIZE_TW * 3;     // [256]
+  int* xlo = reinterpret_cast<int*>(part + RESIZE_TW * RESIZE_TH);
+  int* xcnt = xlo + RESIZE_TW;
+  int* ylo = xcnt + RESIZE_TW;
+  int* ycnt = ylo + RESIZE_TH;
+  uint8_t* rows = reinterpret_cast<uint8_t*>(ycnt + RESIZE_TH);  // [AA_ROWS][pitch]
+  const int tid = threadIdx.x;
+  const int ox0 = blockIdx.x * RESIZE_TW, oy0 = blockIdx.y * RESIZE_TH, b = blockIdx.z;
+  const int tile_w = min(RESIZE_TW, g.W - ox0), tile_h = min(RESIZE_TH, g.H - oy0);
+  aa_axis_table(wx, xlo, xcnt, part, ox0, tile_w, g.cw, g.W, g.ntx, tid);
+  aa_axis_table(wy, ylo, ycnt, part, oy0, tile_h, g.ch, g.H, g.nty, tid);
+  // what the tile reads of the crop: columns [cx0, cx1), rows [ry0, ry1) (xmin and xmax do not decrease with the index)
+  const int cx0 = xlo[0], cx1 = xlo[tile_w - 1] + xcnt[tile_w - 1];
+  const int ry0 = ylo[0], ry1 = ylo[tile_h - 1] + ycnt[tile_h - 1];
+  const int row_bytes = (cx1 - cx0) * 3, pitch_dw = g.pitch >> 2;  // row_bytes + 3 <= pitch (aa_max_cols)
+  const long frame_bytes = (long)g.src_h * g.src_w * 3, src_pitch = (long)g.src_w * 3;
+  const uint8_t* crop = src + b * frame_bytes + ((long)g.y1 * g.src_w + g.x1) * 3;
+  const uint8_t* lo = src;
+  const uint8_t* hi = src + (long)gridDim.z * frame_bytes;  // a dword is loaded whole only inside [lo, hi)
+  const unsigned align_step = (unsigned)(src_pitch & 3);
+  const int lx = tid % RESIZE_TW, ly = tid / RESIZE_TW;
+  const bool live = lx < tile_w && ly < tile_h;  // as an output pixel
+  const int my_lo = live ? ylo[ly] : 0, my_cnt = live ? ycnt[ly] : 0;
+  const int my_x = lx < tile_w ? (xlo[lx] - cx0) * 3 : 0, my_nx = lx < tile_w ? xcnt[lx] : 0;
+  const float* my_wx = wx + lx * g.ntx;
+  const float* my_wy = wy + ly * g.nty;
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int r0 = ry0; r0 < ry1; r0 += AA_ROWS) {  // (workgroup-uniform)
+    const int nrows = min(AA_ROWS, ry1 - r0);
+    // stage: byte k of chunk row r sits at rows[r * pitch + align_r + k], in the aligned dwords that cover the row's bytes
+    const uint8_t* first = crop + (long)r0 * src_pitch + (long)cx0 * 3;
+    const unsigned align0 = (unsigned)(reinterpret_cast<uintptr_t>(first) & 3);
+    for (int i = tid; i < nrows * pitch_dw; i += RESIZE_TW * RESIZE_TH) {
+      const int r = i / pitch_dw, k = i - r * pitch_dw;
+      const unsigned al = (align0 + (unsigned)r * align_step) & 3;
+      if (k * 4 >= (int)al + row_bytes) continue;
+      const uint8_t* p = first + (long)r * src_pitch - al + k * 4;
+      uint32_t v;
+      if (p >= lo && p + 4 <= hi) {
+        v = *reinterpret_cast<const uint32_t*>(p);
+      } else {
+        v = 0;
+        for (int q = 0; q < 4; ++q)
+          if (p + q >= lo && p + q < hi) v |= (uint32_t)p[q] << (8 * q);
+      }
+      *reinterpret_cast<uint32_t*>(rows + (long)r * g.pitch + k * 4) = v;
+    }
+    __syncthreads();
+    // horizontal pass: lane = column lx of chunk row ly.  Four sums q_u over the taps t = u, u + 4, ... (in that order),
+    // h = (q0 + q1) + (q2 + q3)
+    if (ly < nrows && lx < tile_w) {
+      const uint8_t* px = rows + (long)ly * g.pitch + ((align0 + (unsigned)ly * align_step) & 3) + my_x;
+      float q[4][3] = {};
+      int t = 0;
+      for (; t + 4 <= my_nx; t += 4)
+        for (int u = 0; u < 4; ++u) {
+          const float w = my_wx[t + u];
+          for (int c = 0; c < 3; ++c) q[u][c] = q[u][c] + w * (float)px[(t + u) * 3 + c];
+        }
+      for (int u = 0; u < 3; ++u)
+        if (t + u < my_nx) {
+          const float w = my_wx[t + u];
+          for (int c = 0; c < 3; ++c) q[u][c] = q[u][c] + w * (float)px[(t + u) * 3 + c];
+        }
+      for (int c = 0; c < 3; ++c) hbuf[(ly * RESIZE_TW + lx) * 3 + c] = (q[0][c] + q[1][c]) + (q[2][c] + q[3][c]);
+    }
+    __syncthreads();
+    // vertical pass: lane = output pixel (lx, ly).  The chunk's rows inside its window, in order, then onto the running sum
+    float partial[3] = {0.f, 0.f, 0.f};
+    for (int r = 0; r < nrows; ++r) {
+      const int t = r0 + r - my_lo;
+      if (t >= 0 && t < my_cnt) {
+        const float w = my_wy[t];
+        for (int c = 0; c < 3; ++c) partial[c] = partial[c] + w * hbuf[(r * RESIZE_TW + lx) * 3 + c];
+      }
+    }
+    for (int c = 0; c < 3; ++c) acc[c] = acc[c] + partial[c];
+    // (the next chunk's staging writes rows, read before the barrier above; its horizontal pass writes hbuf behind the
+    // next barrier)
+  }
+  if (!live) return;
+  const int ox = ox0 + lx, oy = oy0 + ly;
+  resize_store<T, ACT>(acc, dst + ((long)b * g.H + oy) * g.dst_row_stride + (long)ox * 3,
+                       ACT ? act + (((long)b * g.H + oy) * g.W + ox) * Cpad : nullptr, Cpad, m0, m1, m2, s0, s1, s2);
+}
+
+static size_t aa_lds_bytes(const AaGeom& g) {
+  const size_t floats = (size_t)RESIZE_TW * g.ntx + (size_t)RESIZE_TH * g.nty + AA_ROWS * RESIZE_TW * 3 + RESIZE_TW * RESIZE_TH;
+  return (floats + 2 * RESIZE_TW + 2 * RESIZE_TH) * 4 + (size_t)AA_ROWS * g.pitch;
+}
+
+static int aa_geometry(AaGeom& g, int B, int src_h, int src_w, int x1, int y1, int cw, int ch, int H, int W,
+                       long dst_row_stride) {
+  ResizeGeom r;
+  if (int rc = resize_geometry(r, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride)) return rc;
+  D3F_CHECK((long)cw <= (long)AA_MAX_RATIO * W && (long)ch <= (long)AA_MAX_RATIO * H,
+            "crop_resize_cubic_aa: crop %d x %d above %d times the output %d x %d on an axis (at most %d taps per axis)", cw,
+            ch, AA_MAX_RATIO, W, H, 4 * AA_MAX_RATIO + 1);
+  g = AaGeom{src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride, aa_max_taps(cw, W) | 1, aa_max_taps(ch, H) | 1,
+             (aa_max_cols(cw, W) * 3 + 3 + 3) / 4 * 4};  // up to 3 bytes of dword alignment in front
+  D3F_CHECK(aa_lds_bytes(g) <= (size_t)AA_LDS_LIMIT, "crop_resize_cubic_aa: %zu bytes of LDS", aa_lds_bytes(g));
+  return 0;
+}
+
+int crop_resize_cubic_aa_check(int B, int src_h, int src_w, int x1, int y1, int cw, int ch, int H, int W,
+                               long dst_row_stride) {
+  AaGeom g;
+  return aa_geometry(g, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride);
+}
+
+template <typename T, bool ACT>
+static int aa_launch(const uint8_t* src, uint8_t* dst, T* act, const AaGeom& g, int B, int Cpad, const float mean255[3],
+                     const float std255[3], hipStream_t stream) {
+  const dim3 grid((g.W + RESIZE_TW - 1) / RESIZE_TW, (g.H + RESIZE_TH - 1) / RESIZE_TH, B), block(RESIZE_TW * RESIZE_TH);
+  const float z[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
+  const float* m = mean255 ? mean255 : z;
+  const float* s = std255 ? std255 : one;
+  hipLaunchKernelGGL((crop_resize_cubic_aa_kernel<T, ACT>), grid, block, aa_lds_bytes(g), stream, src, dst, act, g, Cpad,
+                     m[0], m[1], m[2], s[0], s[1], s[2]);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+int crop_resize_cubic_aa_u8_launch(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch,
+                                   uint8_t* dst, int H, int W, long dst_row_stride, hipStream_t stream) {
+  AaGeom g;
+  if (int rc = aa_geometry(g, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride)) return rc;
+  if (B == 0) return 0;
+  return aa_launch<float, false>(src, dst, nullptr, g, B, 0, nullptr, nullptr, stream);
+}
+
+int crop_resize_cubic_aa_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw,
+                                        int ch, uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
+                                        const float mean255[3], const float std255[3], hipStream_t stream) {
+  AaGeom g;
+  if (int rc = aa_geometry(g, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride)) return rc;
+  D3F_CHECK(Cpad >= 3, "crop_resize_cubic_aa: activation of %d channels", Cpad);
+  if (B == 0) return 0;
+  if (dtype == D3F_F32) return aa_launch<float, true>(src, dst, (float*)act, g, B, Cpad, mean255, std255, stream);
+  return aa_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, B, Cpad, mean255, std255, stream);
+}
+
+// ---- full-frame output: the inverse of crop_resize_cubic (the plain form) with a blend in the epilogue ----
 // patch [B][H][W][3] (rows patch_row_stride bytes apart) is resized H x W -> ch x cw with resize_value and blended into the
 // box (x1, y1, cw, ch) of frame [B][src_h][src_w][3]; everything else of out is the frame (include/d3f_hip.h:
 // d3f_paste_resize_cubic_u8 is the definition; tests/paste_restatement.py restates it in float64).

@@ -678,11 +678,14 @@ def center_crop_box(h, w, width, height):
     return x1, y1, crop_width, crop_height
 
 
-def crop_resize_cubic_u8(frames, size, box=None, out=None):
+def crop_resize_cubic_u8(frames, size, box=None, out=None, antialias=False):
     """uint8 frames [h, w, 3] or [B, h, w, 3] on the HIP device -> the crop box (x1, y1, cw, ch) resized to size = (H, W)
     as cv2.resize(..., INTER_CUBIC) defines it in float arithmetic (include/d3f_hip.h: d3f_crop_resize_cubic_u8).
     box=None: the reference's centre crop to the target aspect.  out: a uint8 tensor [B, H, W, 3] whose pixels are packed
-    and whose rows may be strided -- the left half of a [B, H, 2W, 3] side-by-side buffer, for one."""
+    and whose rows may be strided -- the left half of a [B, H, 2W, 3] side-by-side buffer, for one.
+    antialias=True: Pillow's bicubic instead, whose window widens with the scale -- what
+    torch.nn.functional.interpolate(mode="bicubic", antialias=True) computes (d3f_crop_resize_cubic_aa_u8); for crops several
+    times the size of the output, where four taps per axis skip most of the source pixels."""
     if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
         raise ValueError("crop_resize_cubic_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3]")
     dev = _dev(frames)
@@ -697,7 +700,9 @@ def crop_resize_cubic_u8(frames, size, box=None, out=None):
           or out.stride(2) != 3 or (B > 1 and out.stride(0) != H * out.stride(1))):
         raise ValueError(f"out must be a uint8 tensor of shape {(B, H, W, 3)} on the input's device with packed pixels "
                          f"and frames H rows apart")
-    check(_lib.lib().d3f_crop_resize_cubic_u8(ptr(x), B, h, w, x1, y1, cw, ch, ptr(out), H, W, out.stride(1), stream_ptr()))
+    L = _lib.lib()
+    resize = L.d3f_crop_resize_cubic_aa_u8 if antialias else L.d3f_crop_resize_cubic_u8
+    check(resize(ptr(x), B, h, w, x1, y1, cw, ch, ptr(out), H, W, out.stride(1), stream_ptr()))
     return out[0] if single else out
 
 

@@ -26,6 +26,7 @@ def main():
         batch_frames=args.batch_frames,
         output=args.output,
         feather=args.feather,
+        antialias=args.antialias,
         )
 
 
@@ -47,6 +48,9 @@ def parse_command_line_arguments(argv=None):
     parser.add_argument("--feather", type=int, default=None,
                         help="--output full: width in source pixels of the ramp over which the fake fades into the frame "
                              "(default: min(crop_w, crop_h) // 16)")
+    parser.add_argument("--antialias", action="store_true",
+                        help="resize the crop with the antialiased bicubic filter (Pillow's); use it when the crop is "
+                             "several times the network's size, and on a model whose training images were made with it")
 
     return parser.parse_args(argv)
 
@@ -56,10 +60,11 @@ class RenderFakeVideo():
     frame (output="full": each full frame) instead of the .mp4 writer; model=: a loaded LitModule instead of the
     checkpoint.  With both hooks no video file is touched and cv2 is not needed.
     output="full" takes the writer's size from the first frame, so the writer is opened when the first batch arrives: a
-    source without frames leaves no output file (output="pair" knows its size up front and leaves an empty video)."""
+    source without frames leaves no output file (output="pair" knows its size up front and leaves an empty video).
+    antialias=True: the crop is resized to the network's size with the antialiased bicubic filter, in either output."""
 
     def __init__(self, video_path, checkpoint_path, model_a_or_b, image_width, image_height, batch_frames=1,
-                 frames=None, sink=None, model=None, output="pair", feather=None):
+                 frames=None, sink=None, model=None, output="pair", feather=None, antialias=False):
 
         self.video_path = Path(video_path)
         self.checkpoint_path = Path(checkpoint_path) if checkpoint_path is not None else None
@@ -73,6 +78,7 @@ class RenderFakeVideo():
             raise ValueError(f"output is one of {OUTPUTS}, not {output!r}")
         self.output = output
         self.feather = None if feather is None else int(feather)
+        self.antialias = bool(antialias)
         self.frames = frames
         self.sink = sink
 
@@ -106,7 +112,7 @@ class RenderFakeVideo():
             write = self.sink if self.sink is not None else video_writer.write
             for batch, real_frames in batches(frames, self.batch_frames):
                 real_and_fake = self.model.predict_fake_frames(batch, self.model_a_or_b, self.image_width,
-                                                               self.image_height)
+                                                               self.image_height, antialias=self.antialias)
                 for frame in real_and_fake[:real_frames]:  # the padding of a short last batch is dropped
                     write(frame)
 
@@ -121,7 +127,8 @@ class RenderFakeVideo():
                     write = stack.enter_context(VideoWriter(str(self.get_output_video_path("_full")), w, h,
                                                             self.get_input_video_properties())).write
                 full = self.model.predict_fake_frames_full(batch, self.model_a_or_b, self.image_width,
-                                                           self.image_height, feather=self.feather)
+                                                           self.image_height, feather=self.feather,
+                                                           antialias=self.antialias)
                 for frame in full[:real_frames]:  # the padding of a short last batch is dropped
                     write(frame)
 

@@ -19,6 +19,7 @@ def main():
         args.width,
         args.height,
         batch_frames=args.batch_frames,
+        antialias=args.antialias,
         )
 
 
@@ -29,15 +30,19 @@ def parse_command_line_arguments(argv=None):
     parser.add_argument("width", help="output image width")
     parser.add_argument("height", help="output image height")
     parser.add_argument("--batch-frames", type=int, default=16, help="frames per device call")
+    parser.add_argument("--antialias", action="store_true",
+                        help="resize with the antialiased bicubic filter (Pillow's); use it when the crop is several times "
+                             "the image size, and render videos through the trained model with the same flag")
 
     return parser.parse_args(argv)
 
 
 class VideoToImages():
     """frames=: an iterable of decoded BGR frames instead of the video file (cv2 is not needed then); the output folder
-    is still named after video_path"""
+    is still named after video_path.  antialias=True: ops.crop_resize_cubic_u8(..., antialias=True)"""
 
-    def __init__(self, video_path, image_width, image_height, batch_frames=16, frames=None, device="cuda"):
+    def __init__(self, video_path, image_width, image_height, batch_frames=16, frames=None, device="cuda",
+                 antialias=False):
 
         self.video_path = Path(video_path)
         self.image_width = int(image_width)
@@ -47,6 +52,7 @@ class VideoToImages():
             raise ValueError("batch_frames is at least 1")
         self.frames = frames
         self.device = device
+        self.antialias = bool(antialias)
 
         if frames is None:
             import_cv2()  # fail before the output folder is made
@@ -76,7 +82,8 @@ class VideoToImages():
     def resize_frames(self, batch):
         """[n, h, w, 3] host BGR frames -> [n, height, width, 3] host BGR frames, cropped at the centre and resized"""
         dev = torch.from_numpy(batch).to(self.device)
-        return ops.crop_resize_cubic_u8(dev, (self.image_height, self.image_width)).cpu().numpy()
+        return ops.crop_resize_cubic_u8(dev, (self.image_height, self.image_width),
+                                        antialias=self.antialias).cpu().numpy()
 
     def save_frame_to_disk(self, frame, frame_index):
         from PIL import Image

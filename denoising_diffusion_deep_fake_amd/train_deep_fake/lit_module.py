@@ -449,11 +449,13 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
 
     # ---- raw frames to real|fake frames (script_tools/put_video_through_fake_model.py:111-119, 68) ----
     @torch.no_grad()
-    def predict_fake_frames(self, raw_bgr_batch, model_a_or_b, width, height):
+    def predict_fake_frames(self, raw_bgr_batch, model_a_or_b, width, height, antialias=False):
         """host frames [B, h, w, 3] (uint8 BGR, any size) -> host real|fake frames [B, height, 2 * width, 3]: centre crop,
         bicubic resize, `predict_fake` and the side-by-side concatenate of the reference's frame loop in one device call
         (`Unet.predict_frames_u8`).  Mean / std as in `predict_fake`: a model is fed the other domain's statistics.
-        Pinned and device staging buffers are kept per shape, so a frame loop allocates nothing after its first batch."""
+        Pinned and device staging buffers are kept per shape, so a frame loop allocates nothing after its first batch.
+        antialias=True: the antialiased bicubic resize (`ops.crop_resize_cubic_u8(..., antialias=True)`) -- prepare the
+        training images the same way."""
         p = self.hparams
         if model_a_or_b == "a":
             model, mean, std = self.model_a, p.mean_b, p.std_b
@@ -482,7 +484,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         host_in.copy_(torch.from_numpy(raw))
         dev_in.copy_(host_in, non_blocking=True)
         model.predict_frames_u8(dev_in, (height, width), mean, std, graph=bool(p.get("inference_graph", False)),
-                                out=dev_out)
+                                out=dev_out, antialias=antialias)
         host_out.copy_(dev_out, non_blocking=True)
         torch.cuda.current_stream().synchronize()
         return host_out.numpy().copy()
@@ -513,12 +515,14 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         return bufs
 
     @torch.no_grad()
-    def predict_fake_frames_full(self, raw_bgr_batch, model_a_or_b, width, height, feather=None, with_pair=False):
+    def predict_fake_frames_full(self, raw_bgr_batch, model_a_or_b, width, height, feather=None, with_pair=False,
+                                 antialias=False):
         """host frames [B, h, w, 3] (uint8 BGR, any size) -> host frames of the same shape with the centre-crop box replaced
         by the fake, resized back to the box and blended in over `feather` source pixels (None: `ops.default_feather`):
         the swapped video at the source's size, in one device call (`Unet.predict_frames_full_u8`).  with_pair: returns
         (full, pair), pair being what `predict_fake_frames` returns.  Models and statistics as `predict_fake_frames`;
-        pinned and device staging is kept per shape in a cache of its own."""
+        pinned and device staging is kept per shape in a cache of its own.  antialias: as `predict_fake_frames` (the
+        crop-to-network resize only)."""
         model, mean, std, raw = self._frame_path_inputs(raw_bgr_batch, model_a_or_b, "predict_fake_frames_full")
         width, height = int(width), int(height)
         if not hasattr(self, "_frames_full_buffers"):
@@ -531,7 +535,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         dev_in.copy_(host_in, non_blocking=True)
         model.predict_frames_full_u8(dev_in, (height, width), mean, std, feather=feather,
                                      graph=bool(self.hparams.get("inference_graph", False)), out=dev_full,
-                                     pair_out=dev_pair)
+                                     pair_out=dev_pair, antialias=antialias)
         host_full.copy_(dev_full, non_blocking=True)
         if with_pair:
             host_pair.copy_(dev_pair, non_blocking=True)

@@ -818,15 +818,21 @@ class Unet(nn.Module, _NetsRuntime):
         eng.keep = (x, out)  # the captured graph bakes these pointers in: keep them alive with the engine
         return out[0] if single else out
 
+    @staticmethod
+    def _set_frame_resample(eng, antialias):
+        """the frame entries' resize mode on the engine's handle (d3f_unet_set_frame_resample)"""
+        check(_lib.lib().d3f_unet_set_frame_resample(eng.h, _lib.RESAMPLE_CUBIC_AA if antialias else _lib.RESAMPLE_CUBIC))
+
     @torch.no_grad()
-    def predict_frames_u8(self, raw_bgr, size, mean, std, graph=True, out=None):
+    def predict_frames_u8(self, raw_bgr, size, mean, std, graph=True, out=None, antialias=False):
         """The frame path of d3f/script_tools/put_video_through_fake_model.py:111-119, 68 on decoded frames of any
         size: uint8 BGR frames [h,w,3] or [B,h,w,3] on the HIP device -> centre crop to the aspect of size = (H, W)
         (`ops.center_crop_box`) -> bicubic resize (`ops.crop_resize_cubic_u8`) -> `predict_u8` -> the real|fake frames
         [B,H,2W,3] ([H,2W,3] for a single frame), all in one C call.  The left half is byte for byte
         `ops.crop_resize_cubic_u8`, the right half `predict_u8` of the left half at the same batch size.  `graph=True`
         replays a hipGraph captured per (input, output) buffer pair, raw frame size and crop box: pass the same buffers
-        again (`out=`) in a frame loop."""
+        again (`out=`) in a frame loop.  antialias=True resizes as `ops.crop_resize_cubic_u8(..., antialias=True)` does
+        (the handle's D3F_RESAMPLE_CUBIC_AA mode); a change of it between calls re-captures the graph."""
         from . import ops
         if raw_bgr.dtype != torch.uint8 or raw_bgr.shape[-1] != 3 or raw_bgr.dim() not in (3, 4):
             raise ValueError("predict_frames_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3] in BGR order")
@@ -852,19 +858,22 @@ class Unet(nn.Module, _NetsRuntime):
         rt = self._rt
         m = (C.c_float * 3)(*[float(v) for v in mean])
         sd = (C.c_float * 3)(*[float(v) for v in std])
+        self._set_frame_resample(eng, antialias)
         check(_lib.lib().d3f_unet_predict_frames_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), h, w, x1, y1, cw, ch,
                                                     ptr(out), m, sd, ptr(eng.workspace), 1 if graph else 0, stream_ptr()))
         eng.keep = (x, out)  # the captured graph bakes these pointers in: keep them alive with the engine
         return out[0] if single else out
 
     @torch.no_grad()
-    def predict_frames_full_u8(self, raw_bgr, size, mean, std, feather=None, graph=True, out=None, pair_out=None):
+    def predict_frames_full_u8(self, raw_bgr, size, mean, std, feather=None, graph=True, out=None, pair_out=None,
+                               antialias=False):
         """`predict_frames_u8`, then the fake pasted back into the source frames: uint8 BGR frames [h,w,3] or [B,h,w,3] on
         the HIP device -> the frames at their own size with the centre-crop box replaced by the fake, resized back
         (`ops.paste_resize_cubic_u8`) and blended in over `feather` source pixels (None: `ops.default_feather` of the
         box), all in one C call.  Returns the full frames.  pair_out: a [B,H,2W,3] buffer, filled as `predict_frames_u8`
         fills it (allocated when None: it stages the fake).  out=raw_bgr pastes in place (graph=False only).  `graph=True`
-        replays a hipGraph of its own, captured per set of buffers, frame size, box and feather."""
+        replays a hipGraph of its own, captured per set of buffers, frame size, box and feather.  antialias: as
+        `predict_frames_u8`, for the crop-to-network resize only; the paste enlarges and stays as it is."""
         from . import ops
         if raw_bgr.dtype != torch.uint8 or raw_bgr.shape[-1] != 3 or raw_bgr.dim() not in (3, 4):
             raise ValueError("predict_frames_full_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3] in BGR order")
@@ -904,6 +913,7 @@ class Unet(nn.Module, _NetsRuntime):
         rt = self._rt
         m = (C.c_float * 3)(*[float(v) for v in mean])
         sd = (C.c_float * 3)(*[float(v) for v in std])
+        self._set_frame_resample(eng, antialias)
         check(_lib.lib().d3f_unet_predict_frames_full_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), h, w, x1, y1, cw,
                                                          ch, feather, ptr(pair_out), ptr(full), m, sd, ptr(eng.workspace),
                                                          1 if graph else 0, stream_ptr()))

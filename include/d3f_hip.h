@@ -198,6 +198,20 @@ int d3f_unet_predict_frames_full_u8(d3f_unet_t h, const float* params, float* bn
                                     int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* pair_out,
                                     uint8_t* full_out, const float mean[3], const float std[3], void* workspace,
                                     int use_graph, void* stream);
+/* How d3f_unet_predict_frames_u8 and d3f_unet_predict_frames_full_u8 resize the crop box to the handle's H x W:
+ *   D3F_RESAMPLE_CUBIC     d3f_crop_resize_cubic_u8 (cv2.INTER_CUBIC: four taps per axis whatever the scale).  The default
+ *                          after d3f_unet_create; its launches are exactly those of a handle that never heard of the setting.
+ *   D3F_RESAMPLE_CUBIC_AA  d3f_crop_resize_cubic_aa_u8 (Pillow's antialiased bicubic: the window widens with the scale).
+ * The crop-to-network step only: the paste of the full-frame entry enlarges and stays d3f_paste_resize_cubic_u8.  With
+ * D3F_RESAMPLE_CUBIC_AA the left half of pair_out is byte for byte d3f_crop_resize_cubic_aa_u8 (one kernel writes it and,
+ * from the same rounded bytes, the normalised network input), the right half d3f_unet_predict_u8 of the left half, and
+ * the entries refuse what that operator refuses (a crop above 32 times the output on an axis) before any capture.
+ * Host only.  Setting a different value drops the handle's captured frames and full-frame graphs, as a pointer change does;
+ * an unknown mode and a pair handle (which has no frame entries) are refused. */
+#define D3F_RESAMPLE_CUBIC 0
+#define D3F_RESAMPLE_CUBIC_AA 1
+int d3f_unet_set_frame_resample(d3f_unet_t h, int mode);
+int d3f_unet_frame_resample(d3f_unet_t h); /* the mode, or < 0 for a null handle */
 /* gradients of every parameter (written, not accumulated) for the preceding training forward.
  * The backward pass is cut into d3f_unet_num_segments() buckets so a data-parallel caller can
  * all-reduce bucket k while bucket k+1 computes: run segments [seg_begin, seg_end) in order 0..n;
@@ -457,6 +471,37 @@ int d3f_u8rgb_normalise(const uint8_t* in_hwc, float* out_nchw, int B, int H, in
  * is not claimed.  Refused: a box outside the frame, non-positive sizes, extents above 16384, a stride below 3 * W. */
 int d3f_crop_resize_cubic_u8(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch, uint8_t* dst,
                              int H, int W, int64_t dst_row_stride_bytes, void* stream);
+/* d3f_crop_resize_cubic_u8 with antialiasing: arguments, layouts and refusals are its own, the filter is Pillow's bicubic,
+ * which is also torch.nn.functional.interpolate(mode="bicubic", antialias=True, align_corners=False): an axis that shrinks
+ * by r = n_in / n_out widens the Keys kernel by r, so that every source pixel of an output pixel's footprint is read.
+ * Definition (the acceptance contract; tests/resize_aa_restatement.py restates it in float64).  Per axis n_in -> n_out,
+ * output index i, everything up to the weights' arguments in exact integers:
+ *   - down = n_in >= n_out; centre c = (2i + 1) n_in / (2 n_out); support s = 2 n_in / n_out when down, else 2;
+ *   - with S = 4 n_in when down, else 4 n_out: first tap xmin = max(floor(((2i + 1) n_in - S + n_out) / (2 n_out)), 0), end
+ *     xmax = min(floor(((2i + 1) n_in + S + n_out) / (2 n_out)), n_in); taps k = xmin .. xmax - 1, at most
+ *     floor(S / n_out) + 1 of them.  The window is TRUNCATED at the crop's edge, not replicated;
+ *   - raw weight w_k = keys(|a_k|), a_k = ((2k + 1) n_out - (2i + 1) n_in) / D, D = 2 n_in when down, else 2 n_out: the
+ *     numerator is an exact integer below 2^24 in magnitude for extents up to 16384, so ONE fp32 division rounds a_k
+ *     correctly; keys with A = -0.5 in fp32, Horner form: ((A + 2) x - (A + 3)) x x + 1 for x < 1,
+ *     ((A x - 5A) x + 8A) x - 4A for 1 <= x < 2, 0 from 2 on;
+ *   - the weights' sum, in fp32: with t = k - xmin, eight sums p_j over the taps t = j, j + 8, j + 16, ... in that order
+ *     (0 when there is none), sum = ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)); the weight of tap k is the fp32
+ *     quotient w_k / sum.
+ * The two passes, in fp32 without contraction (no fma), over the crop:
+ *   - horizontal: for a source row, four sums q_u over the taps t = u, u + 4, u + 8, ... of weight * (float)byte, each
+ *     started from 0 and taken in that order, h = (q0 + q1) + (q2 + q3);
+ *   - vertical: the source rows are taken in chunks of 8 counted from ymin of the first output row of the pixel's tile of 8
+ *     output rows (row 8 floor(i_y / 8)); inside a chunk the products weight * h of the rows in the pixel's window are
+ *     added in row order from 0, and the chunk's sum is added to the running value, chunks in order;
+ *   - rintf (half to even), clamp to 0..255.
+ * Equal extents on an axis give weight 1 on tap i and exact zeros elsewhere (a = -1, 0, 1, 2); equal extents on both axes
+ * therefore copy the bytes, as the plain operator does.  An axis that ENLARGES gets Pillow's up-sampling -- A = -0.5, the
+ * window truncated at the edge and renormalised -- and not cv2's (A = -0.75, replicated border) as in
+ * d3f_crop_resize_cubic_u8: deliberately, the mode is one filter whatever the direction, and it is the one torch computes.
+ * Refused on the host before any launch: everything d3f_crop_resize_cubic_u8 refuses, and a crop extent above 32 times the
+ * output extent on either axis (n_in > 32 n_out: the limit caps an axis at 129 taps; 2160 -> 128 is 16.9 and fits). */
+int d3f_crop_resize_cubic_aa_u8(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch,
+                                uint8_t* dst, int H, int W, int64_t dst_row_stride_bytes, void* stream);
 /* The inverse of d3f_crop_resize_cubic_u8 with a blend in the epilogue: paste a patch back into the frames it was cropped
  * from.  patch [B][H][W][3] uint8, rows patch_row_stride_bytes apart (>= 3 * W; frames H rows apart; 6 * W reads the right
  * half of a pair_out buffer); frame and out [B][src_h][src_w][3] uint8, packed; (x1, y1, cw, ch) the box the crop was taken

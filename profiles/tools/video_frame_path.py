@@ -9,10 +9,14 @@
   full         : Unet.predict_frames_full_u8 (frames + paste), B = 1 eager / hipGraph, B = 8 eager; the added time per
                  frame against predict_frames_u8 in the same run, next to the byte-bound estimate of the paste
 
+  --antialias  : instead of the above, d3f_crop_resize_cubic_aa_u8 next to d3f_crop_resize_cubic_u8 on the same inputs and
+                 Unet.predict_u8 (the eval forward of the same call) at the same size: 1080x1920 -> 448x448 and 256x256,
+                 2160x3840 -> 256x256, B = 1 and B = 8; with the byte bound (crop read once, output written once)
+
 Back-to-back enqueues on one stream, ITERS iterations after WARMUP, the forms alternating in ROUNDS rounds; the figure is
 the median round's time per call (and per frame).  Host work of the reference's loop (cv2.resize on one CPU thread, the
 concatenate, two PCIe trips) is not part of any figure here.  One JSON line at the end.
-    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N]
+    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N] [--antialias]
 """
 import argparse
 import json
@@ -50,8 +54,38 @@ def compare(forms, warmup, iters, rounds):
     return {name: (statistics.median(t), min(t), max(t)) for name, t in times.items()}
 
 
+def antialias_section(net, args, g):
+    """the antialiased resize against the plain one and the eval forward, per frame; one JSON line"""
+    result = {"precision": args.precision, "digest": _lib.built_digest(), "iters": args.iters, "rounds": args.rounds,
+              "antialias_us_per_frame": {}}
+    for raw_hw, side in (((1080, 1920), 448), ((1080, 1920), 256), ((2160, 3840), 256)):
+        size = (side, side)
+        box = ops.center_crop_box(raw_hw[0], raw_hw[1], side, side)
+        need = box[2] * box[3] * 3 + side * side * 3  # bytes per frame: the crop read once, the output written once
+        for B in (1, 8):
+            raw = torch.randint(0, 256, (B,) + raw_hw + (3,), generator=g, dtype=torch.uint8).cuda()
+            small = ops.crop_resize_cubic_u8(raw, size, antialias=True)
+            resized, fake = torch.empty_like(small), torch.empty_like(small)
+            forms = {
+                "plain": lambda: ops.crop_resize_cubic_u8(raw, size, out=resized),
+                "antialias": lambda: ops.crop_resize_cubic_u8(raw, size, out=resized, antialias=True),
+                "predict_u8": lambda: net.predict_u8(small, MEAN, STD, graph=False, out=fake),
+            }
+            t = {name: med / B for name, (med, _, _) in compare(forms, args.warmup, args.iters, args.rounds).items()}
+            bound = need / 6.3e12 * 1e6  # at 6.3 TB/s achievable HBM
+            key = f"{raw_hw[0]}x{raw_hw[1]}_to_{side}_B{B}"
+            print(f"{key:28s} plain {t['plain']:8.2f}  antialias {t['antialias']:8.2f}  predict_u8 {t['predict_u8']:9.1f} us per "
+                  f"frame; {need} bytes per frame, byte bound {bound:.2f} us, antialias at {t['antialias'] / bound:.1f} times it")
+            result["antialias_us_per_frame"][key] = {"plain": round(t["plain"], 2), "antialias": round(t["antialias"], 2),
+                                                     "predict_u8": round(t["predict_u8"], 1), "bytes": need,
+                                                     "byte_bound_us": round(bound, 2)}
+            del raw
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--antialias", action="store_true", help="measure the antialiased resize instead (see above)")
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
@@ -62,6 +96,8 @@ def main():
     torch.manual_seed(0)
     net = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
     g = torch.Generator().manual_seed(1)
+    if args.antialias:
+        return antialias_section(net, args, g)
     result = {"raw": list(RAW), "size": list(SIZE), "precision": args.precision, "digest": _lib.built_digest(),
               "iters": args.iters, "rounds": args.rounds, "us_per_call": {}}
     for B in (1, 8):
