@@ -23,6 +23,15 @@ HEAD_ACTIVATIONS = {None: ACT_IDENTITY, "sigmoid": ACT_SIGMOID, "tanh": ACT_TANH
 
 
 RESAMPLE_CUBIC, RESAMPLE_CUBIC_AA = 0, 1  # D3F_RESAMPLE_*: how the frame entries resize the crop to the network's size
+COLOR_NONE, COLOR_MEANSTD = 0, 1  # D3F_COLOR_*: whether the full-frame entry matches the fake's colour before it pastes
+COLOR_MATCH_MODES = {None: COLOR_NONE, "none": COLOR_NONE, "meanstd": COLOR_MEANSTD}
+
+
+def color_match_mode(color_match):
+    """the D3F_COLOR_* code of None / "none" / "meanstd"; anything else is a ValueError"""
+    if not (color_match is None or isinstance(color_match, str)) or color_match not in COLOR_MATCH_MODES:
+        raise ValueError(f"color_match is None, 'none' or 'meanstd', not {color_match!r}")
+    return COLOR_MATCH_MODES[color_match]
 
 
 class D3FError(RuntimeError):
@@ -94,6 +103,8 @@ PROTOTYPES = {
     "d3f_unet_head_activation": (_i, [_p]),
     "d3f_unet_set_frame_resample": (_i, [_p, _i]),
     "d3f_unet_frame_resample": (_i, [_p]),
+    "d3f_unet_set_frame_color_match": (_i, [_p, _i]),
+    "d3f_unet_frame_color_match": (_i, [_p]),
     "d3f_unet_num_params": (_i, [_p]),
     "d3f_unet_param_info": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(C.c_int32), C.POINTER(_i), C.POINTER(_i64)]),
     "d3f_unet_param_floats": (_i64, [_p]),
@@ -123,6 +134,9 @@ PROTOTYPES = {
     "d3f_crop_resize_cubic_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i64, _p]),
     "d3f_crop_resize_cubic_aa_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i64, _p]),
     "d3f_paste_resize_cubic_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "d3f_channel_sums_u8": (_i, [_p, _i, _i, _i, _i64, _p, _p]),
+    "d3f_color_match_coef": (_i, [_p, _p, _i, _i64, _p, _p]),
+    "d3f_paste_resize_cubic_color_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "d3f_unet_predict_frames_full_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, C.POINTER(_f), C.POINTER(_f),
                                              _p, _i, _p]),
     "d3f_image_grid_shape": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),

@@ -204,6 +204,14 @@ int d3f_unet_set_frame_resample(d3f_unet_t h, int mode) {
   return h->e.set_frame_resample(mode);
 }
 int d3f_unet_frame_resample(d3f_unet_t h) { return h ? h->e.frame_resample() : -1; }
+static_assert(D3F_COLOR_NONE == UnetEngine::FRAME_COLOR_NONE && D3F_COLOR_MEANSTD == UnetEngine::FRAME_COLOR_MEANSTD,
+              "d3f_hip.h states the colour match modes");
+int d3f_unet_set_frame_color_match(d3f_unet_t h, int mode) {
+  D3F_CHECK(h, "unet_set_frame_color_match: null handle");
+  if (int rc = single_net(h, "unet_set_frame_color_match", "has no frame entries (run each network alone)")) return rc;
+  return h->e.set_frame_color_match(mode);
+}
+int d3f_unet_frame_color_match(d3f_unet_t h) { return h ? h->e.frame_color_match() : -1; }
 int d3f_unet_num_params(d3f_unet_t h) { return h ? (int)h->e.params.size() : -1; }
 int d3f_unet_param_info(d3f_unet_t h, int i, char* name, int name_cap, int32_t shape[4], int* ndim,
                         int64_t* offset) {
@@ -765,6 +773,24 @@ int d3f_paste_resize_cubic_u8(const uint8_t* patch, int B, int H, int W, int64_t
   D3F_CHECK(patch && frame && out, "paste_resize_cubic_u8: null argument");
   return paste_resize_cubic_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, x1, y1, cw, ch,
                                       feather, out, (hipStream_t)stream);
+}
+
+int d3f_channel_sums_u8(const uint8_t* img, int B, int H, int W, int64_t row_stride_bytes, uint64_t* sums, void* stream) {
+  D3F_CHECK(img && sums, "channel_sums_u8: null argument");
+  return channel_sums_u8_launch(img, B, H, W, (long)row_stride_bytes, sums, (hipStream_t)stream);
+}
+
+int d3f_color_match_coef(const uint64_t* sums_from, const uint64_t* sums_to, int B, int64_t n, float* coef, void* stream) {
+  D3F_CHECK(sums_from && sums_to && coef, "color_match_coef: null argument");
+  return color_match_coef_launch(sums_from, sums_to, 1, B, (long)n, coef, (hipStream_t)stream);
+}
+
+int d3f_paste_resize_cubic_color_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                    const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather,
+                                    const float* coef, uint8_t* out, void* stream) {
+  D3F_CHECK(patch && frame && out && coef, "paste_resize_cubic_color_u8: null argument");
+  return paste_resize_cubic_color_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, x1, y1, cw, ch,
+                                            feather, coef, out, (hipStream_t)stream);
 }
 
 int d3f_image_grid_shape(int images, int nrow, int padding, int H, int W, int32_t dims[2]) {

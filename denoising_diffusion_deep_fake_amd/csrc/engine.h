@@ -157,6 +157,15 @@ class UnetEngine {
   enum { FRAME_RESAMPLE_CUBIC = 0, FRAME_RESAMPLE_CUBIC_AA = 1 };
   int set_frame_resample(int mode);
   int frame_resample() const { return frame_resample_; }
+  // Whether predict_frames_full_u8 matches the fake's colour to the resized real crop before the paste (D3F_COLOR_*).  NONE
+  // (the default): exactly the launches of an engine without the setting.  MEANSTD: behind the launches into pair_out, the
+  // sums of both halves of pair_out in one launch (color.hip: a partial row per workgroup), the rows' fixed-order sum and
+  // the coefficients in a second one, and the paste in its colour form.  The partial sums and the coefficients are the
+  // engine's own device memory, allocated at the first switch away from NONE and freed with the engine.  A change drops the
+  // two captured frame graphs; H * W above COLOR_MAX_PIXELS is refused here.
+  enum { FRAME_COLOR_NONE = 0, FRAME_COLOR_MEANSTD = 1 };
+  int set_frame_color_match(int mode);
+  int frame_color_match() const { return frame_color_; }
   int export_tensor(const char* name, const void* ws, float* out_nchw, hipStream_t s) const;
   int export_shape(const char* name, int32_t dims[3]) const;
 
@@ -225,7 +234,8 @@ class UnetEngine {
                                  uint8_t* pair_out, const float mean255[3], const float std255[3], char* ws,
                                  hipStream_t s) const;
   // captured graphs: one slot per entry point; a slot is re-captured when what it baked in changes -- the pointers, the
-  // constants and (predict_frames_u8, predict_frames_full_u8) the raw frame size and crop box, the latter's full_out and feather
+  // constants and (predict_frames_u8, predict_frames_full_u8) the raw frame size and crop box, the latter's full_out, feather
+  // and colour match mode
   struct GraphKey {
     const void* ptr[6];
     float cst[6];
@@ -249,6 +259,11 @@ class UnetEngine {
   mutable hipEvent_t ev_gin_ = nullptr, ev_gout_ = nullptr;
   int head_act_ = 0;          // HEAD_ACT_IDENTITY
   int frame_resample_ = FRAME_RESAMPLE_CUBIC;
+  int frame_color_ = FRAME_COLOR_NONE;
+  // partial sums of a call, [2][B][parts][3][2] (the real half's, then the fake's; parts <= COLOR_SUMS_MAX_PARTS comes from
+  // the sums launch, and the buffer has room for the most)
+  uint64_t* color_slabs_ = nullptr;
+  float* color_coef_ = nullptr;      // [B][3][2]
   // the host-side argument check of the frame entries' resize, in the mode that is set
   int frame_resize_check(int src_h, int src_w, int x1, int y1, int cw, int ch) const;
   // NCHW fp32 head output: predict_u8's, and z of an activated head, which the head of the backward pass turns into dz IN

@@ -709,6 +709,28 @@ int UnetEngine::set_frame_resample(int mode) {
   return 0;
 }
 
+int UnetEngine::set_frame_color_match(int mode) {
+  D3F_CHECK(mode == FRAME_COLOR_NONE || mode == FRAME_COLOR_MEANSTD,
+            "frame colour match: unknown mode %d (D3F_COLOR_NONE, D3F_COLOR_MEANSTD)", mode);
+  if (mode == frame_color_) return 0;
+  if (mode != FRAME_COLOR_NONE) {
+    if (int rc = channel_sums_check(B, H, W, 6L * W)) return rc;  // H * W above 2^22
+    // (each on its own: a call that got the first and failed on the second leaves a state the next call completes)
+    if (color_slabs_ == nullptr)
+      D3F_HIP(hipMalloc(reinterpret_cast<void**>(&color_slabs_),
+                        2 * (size_t)(B > 0 ? B : 1) * COLOR_SUMS_MAX_PARTS * 6 * sizeof(uint64_t)));
+    if (color_coef_ == nullptr)
+      D3F_HIP(hipMalloc(reinterpret_cast<void**>(&color_coef_), (size_t)(B > 0 ? B : 1) * 6 * sizeof(float)));
+  }
+  for (GraphSlot* slot : {&g_frames_, &g_frames_full_})
+    if (slot->exec) {
+      (void)hipGraphExecDestroy(slot->exec);
+      slot->exec = nullptr;
+    }
+  frame_color_ = mode;
+  return 0;
+}
+
 int UnetEngine::frame_resize_check(int src_h, int src_w, int x1, int y1, int cw, int ch) const {
   if (frame_resample_ == FRAME_RESAMPLE_CUBIC_AA)
     return crop_resize_cubic_aa_check(B, src_h, src_w, x1, y1, cw, ch, H, W, 6L * W);
@@ -797,20 +819,33 @@ int UnetEngine::predict_frames_full_u8(const float* params_, float* bnstats, con
     s255[c] = stdv[c] * 255.0f;
   }
   if (int rc = frame_resize_check(src_h, src_w, x1, y1, cw, ch)) return rc;
-  if (int rc = paste_resize_cubic_check(pair_out + 3L * W, raw_in, full_out, B, H, W, 6L * W, src_h, src_w, x1, y1, cw, ch,
-                                        feather))
+  const bool color = frame_color_ == FRAME_COLOR_MEANSTD;
+  if (int rc = color ? paste_resize_cubic_color_check(pair_out + 3L * W, raw_in, full_out, color_coef_, B, H, W, 6L * W, src_h,
+                                                      src_w, x1, y1, cw, ch, feather)
+                     : paste_resize_cubic_check(pair_out + 3L * W, raw_in, full_out, B, H, W, 6L * W, src_h, src_w, x1, y1, cw,
+                                                ch, feather))
     return rc;
   const int geo[6] = {src_h, src_w, x1, y1, cw, ch};
   auto launches = [&](hipStream_t ls) {
     if (int rc = predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, ls)) return rc;
     // the fake half of the pair is the patch: rows 6 * W bytes apart
-    return paste_resize_cubic_u8_launch(pair_out + 3L * W, B, H, W, 6L * W, raw_in, src_h, src_w, x1, y1, cw, ch, feather,
-                                        full_out, ls);
+    if (!color)
+      return paste_resize_cubic_u8_launch(pair_out + 3L * W, B, H, W, 6L * W, raw_in, src_h, src_w, x1, y1, cw, ch, feather,
+                                          full_out, ls);
+    // colour match: the sums of both halves (set 0 the real crop = `to`, set 1 the fake = `from`), the coefficients, and
+    // the paste in its colour form
+    int parts = 0;
+    if (int rc = channel_sums_pair_slabs_launch(pair_out, 3L * W, B, H, W, 6L * W, color_slabs_, &parts, ls)) return rc;
+    const uint64_t* to = color_slabs_;
+    const uint64_t* from = color_slabs_ + (size_t)B * parts * 6;
+    if (int rc = color_match_coef_launch(from, to, parts, B, (long)H * W, color_coef_, ls)) return rc;
+    return paste_resize_cubic_color_u8_launch(pair_out + 3L * W, B, H, W, 6L * W, raw_in, src_h, src_w, x1, y1, cw, ch,
+                                              feather, color_coef_, full_out, ls);
   };
   if (!use_graph) return launches(s);
   const GraphKey key = {{params_, bnstats, raw_in, pair_out, ws_, full_out},
                         {m255[0], m255[1], m255[2], s255[0], s255[1], s255[2]},
-                        {src_h, src_w, x1, y1, cw, ch, feather, 0}};
+                        {src_h, src_w, x1, y1, cw, ch, feather, frame_color_}};
   return graph_replay(g_frames_full_, key, s, launches);
 }
 
@@ -936,6 +971,8 @@ UnetEngine::~UnetEngine() {
   if (ev_pack_in_) (void)hipEventDestroy(ev_pack_in_);
   if (ev_pack_done_) (void)hipEventDestroy(ev_pack_done_);
   if (ev_pack_mid_) (void)hipEventDestroy(ev_pack_mid_);
+  if (color_slabs_) (void)hipFree(color_slabs_);
+  if (color_coef_) (void)hipFree(color_coef_);
   // (side_ is the process-wide stream of this device: not ours to destroy)
 }
 

@@ -142,6 +142,30 @@ int paste_resize_cubic_check(const uint8_t* patch, const uint8_t* frame, const u
 int paste_resize_cubic_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
                                  int src_h, int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* out,
                                  hipStream_t stream);
+// the colour form (include/d3f_hip.h: d3f_paste_resize_cubic_color_u8): the clamped patch value times coef[b][c][0] plus
+// coef[b][c][1], clamped again, in front of the blend; coef [B][3][2] fp32 in device memory.  The same kernel with one more
+// template parameter; refuses what the plain form refuses and a coef that overlaps out
+int paste_resize_cubic_color_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef, int B,
+                                   int H, int W, long patch_row_stride, int src_h, int src_w, int x1, int y1, int cw, int ch,
+                                   int feather);
+int paste_resize_cubic_color_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
+                                       const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch,
+                                       int feather, const float* coef, uint8_t* out, hipStream_t stream);
+
+// colour match (color.hip; include/d3f_hip.h: d3f_channel_sums_u8, d3f_color_match_coef).  Sums: per frame and byte-in-pixel
+// S = sum p, Q = sum p^2 as uint64 [B][3][2], exact; at most COLOR_MAX_PIXELS pixels per frame, so that n Q and S^2 stay
+// below 2^60.  channel_sums_u8_launch overwrites sums (a zeroing launch, then one 64-bit atomic add per workgroup and
+// quantity).  channel_sums_pair_slabs_launch takes two image sets img_delta bytes apart (the halves of a pair buffer) in ONE
+// launch and resets nothing: every workgroup stores its sums as a row of slabs [2][B][*parts_out][3][2], and
+// color_match_coef_launch adds `parts` rows per frame in order (parts == 1: plain sums) before it forms gain and offset.
+constexpr long COLOR_MAX_PIXELS = 1L << 22;
+constexpr int COLOR_SUMS_MAX_PARTS = 64;  // workgroups per image, the rows of a slab
+int channel_sums_check(int B, int H, int W, long row_stride);
+int channel_sums_u8_launch(const uint8_t* img, int B, int H, int W, long row_stride, uint64_t* sums, hipStream_t stream);
+int channel_sums_pair_slabs_launch(const uint8_t* img, long img_delta, int B, int H, int W, long row_stride, uint64_t* slabs,
+                                   int* parts_out, hipStream_t stream);
+int color_match_coef_launch(const uint64_t* sums_from, const uint64_t* sums_to, int parts, int B, long n, float* coef,
+                            hipStream_t stream);
 
 // training image grids (image_grid.hip): make_grid + scale + clamp + uint8 of up to 8 fp32 NCHW batches in one launch;
 // `batches` is a host array of n device pointers, out [n][GH][GW][3] with {GH, GW} from image_grid_shape

@@ -512,11 +512,25 @@ struct PasteGeom {
   int pitch;
   int tx0, ty0;
 };
+// the kernel's last argument: the geometry and, in the colour form only, the coefficients [B][3][2] (gain, offset) -- the
+// plain form's arguments are the ones it had before there was a colour form
+template <bool COLOR>
+struct PasteArgs {
+  PasteGeom g;
+};
+template <>
+struct PasteArgs<true> {
+  PasteGeom g;
+  const float* coef;
+};
 
-template <bool STAGED>
+// COLOR (include/d3f_hip.h: d3f_paste_resize_cubic_color_u8): the clamped patch value goes through gain * v + offset of its
+// frame and channel (product and sum rounded separately) and a second clamp before the blend
+template <bool STAGED, bool COLOR>
 __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void paste_resize_cubic_kernel(const uint8_t* __restrict__ patch,
                                                                                   const uint8_t* frame, uint8_t* out,
-                                                                                  PasteGeom g) {
+                                                                                  PasteArgs<COLOR> args) {
+  const PasteGeom& g = args.g;
   extern __shared__ __attribute__((aligned(16))) uint8_t staged[];
   const int tid = threadIdx.x;
   const int ox0 = ((int)blockIdx.x + g.tx0) * RESIZE_TW, oy0 = ((int)blockIdx.y + g.ty0) * RESIZE_TH, b = blockIdx.z;
@@ -583,7 +597,11 @@ __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void paste_resize_cubic_kern
   const float s[3] = {(float)f[at], (float)f[at + 1], (float)f[at + 2]};
   uint8_t px[3];
   for (int c = 0; c < 3; ++c) {
-    const float vc = fminf(fmaxf(v[c], 0.f), 255.f);
+    float vc = fminf(fmaxf(v[c], 0.f), 255.f);
+    if constexpr (COLOR) {
+      const float scaled = args.coef[((long)b * 3 + c) * 2] * vc;
+      vc = fminf(fmaxf(scaled + args.coef[((long)b * 3 + c) * 2 + 1], 0.f), 255.f);
+    }
     const float pv = a * vc, ps = na * s[c];
     const float r = rintf(pv + ps);
     px[c] = (uint8_t)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r));
@@ -616,13 +634,28 @@ int paste_resize_cubic_check(const uint8_t* patch, const uint8_t* frame, const u
   return 0;
 }
 
-int paste_resize_cubic_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
-                                 int src_h, int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* out,
-                                 hipStream_t stream) {
+int paste_resize_cubic_color_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef, int B,
+                                   int H, int W, long patch_row_stride, int src_h, int src_w, int x1, int y1, int cw, int ch,
+                                   int feather) {
   if (int rc = paste_resize_cubic_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather))
     return rc;
-  if (B == 0) return 0;
-  PasteGeom g = {H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather, 0, 0, 0};
+  D3F_CHECK(coef != nullptr, "paste_resize_cubic_color: null coef");
+  // a tile reads its frame's coefficients while other tiles write out
+  const long bytes = (long)B * src_h * src_w * 3, coef_bytes = (long)B * 6 * sizeof(float);
+  const uint8_t* cb = reinterpret_cast<const uint8_t*>(coef);
+  D3F_CHECK(cb + coef_bytes <= out || out + bytes <= cb, "paste_resize_cubic_color: coef overlaps out");
+  return 0;
+}
+
+// the launch of both forms; coef is read by the colour form only
+template <bool COLOR>
+static int paste_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
+                        int src_w, int x1, int y1, int cw, int ch, int feather, const float* coef, uint8_t* out,
+                        hipStream_t stream) {
+  PasteArgs<COLOR> args;
+  PasteGeom& g = args.g;
+  g = PasteGeom{H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather, 0, 0, 0};
+  if constexpr (COLOR) args.coef = coef;
   const long lds = resize_lds_bytes(H, W, ch, cw, &g.pitch);
   dim3 grid((src_w + RESIZE_TW - 1) / RESIZE_TW, (src_h + RESIZE_TH - 1) / RESIZE_TH, B);
   if (frame == out) {  // in place: the tiles that meet the box
@@ -633,11 +666,31 @@ int paste_resize_cubic_u8_launch(const uint8_t* patch, int B, int H, int W, long
   }
   const dim3 block(RESIZE_TW * RESIZE_TH);
   if (lds > 0)
-    hipLaunchKernelGGL(paste_resize_cubic_kernel<true>, grid, block, (size_t)lds, stream, patch, frame, out, g);
+    hipLaunchKernelGGL((paste_resize_cubic_kernel<true, COLOR>), grid, block, (size_t)lds, stream, patch, frame, out, args);
   else
-    hipLaunchKernelGGL(paste_resize_cubic_kernel<false>, grid, block, 0, stream, patch, frame, out, g);
+    hipLaunchKernelGGL((paste_resize_cubic_kernel<false, COLOR>), grid, block, 0, stream, patch, frame, out, args);
   D3F_HIP(hipGetLastError());
   return 0;
+}
+
+int paste_resize_cubic_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
+                                 int src_h, int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* out,
+                                 hipStream_t stream) {
+  if (int rc = paste_resize_cubic_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather))
+    return rc;
+  if (B == 0) return 0;
+  return paste_launch<false>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, x1, y1, cw, ch, feather, nullptr, out,
+                             stream);
+}
+
+int paste_resize_cubic_color_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
+                                       const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch,
+                                       int feather, const float* coef, uint8_t* out, hipStream_t stream) {
+  if (int rc = paste_resize_cubic_color_check(patch, frame, out, coef, B, H, W, patch_row_stride, src_h, src_w, x1, y1, cw,
+                                              ch, feather))
+    return rc;
+  if (B == 0) return 0;
+  return paste_launch<true>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, x1, y1, cw, ch, feather, coef, out, stream);
 }
 
 }  // namespace d3f

@@ -711,12 +711,57 @@ def default_feather(cw, ch):
     return min(int(cw), int(ch)) // 16
 
 
-def paste_resize_cubic_u8(patch, frames, box, feather=0, out=None):
+def channel_sums_u8(img, out=None):
+    """uint8 images [H, W, 3] / [B, H, W, 3] on the HIP device -> uint64 sums [3, 2] / [B, 3, 2]: per frame and byte-in-pixel
+    S = sum of p and Q = sum of p * p over the H * W pixels, exact (include/d3f_hip.h: d3f_channel_sums_u8; at most 2^22
+    pixels per frame).  img: packed pixels at any byte address, rows may be strided -- one half of a [B, H, 2W, 3] pair
+    buffer, for one.  out: a contiguous uint64 tensor [B, 3, 2] to overwrite."""
+    if img.dtype != torch.uint8 or img.shape[-1] != 3 or img.dim() not in (3, 4):
+        raise ValueError("channel_sums_u8 expects uint8 images [H, W, 3] or [B, H, W, 3]")
+    single = img.dim() == 3
+    x = img.unsqueeze(0) if single else img
+    B, H, W, _ = x.shape
+    if x.stride(3) != 1 or x.stride(2) != 3 or x.stride(1) < 3 * W or (B > 1 and x.stride(0) != H * x.stride(1)):
+        raise ValueError("channel_sums_u8 expects packed pixels and frames H rows apart")
+    dev = _dev(img)
+    if out is None:
+        sums = torch.empty((B, 3, 2), dtype=torch.uint64, device=dev)
+    else:
+        sums = out.unsqueeze(0) if single and out.dim() == 2 else out
+        if tuple(sums.shape) != (B, 3, 2) or sums.dtype != torch.uint64 or sums.device != dev or not sums.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint64 tensor of shape {(B, 3, 2)} on the images' device")
+    if B > 0:
+        check(_lib.lib().d3f_channel_sums_u8(ptr(x), B, H, W, x.stride(1), ptr(sums), stream_ptr()))
+    return sums[0] if single else sums
+
+
+def color_match_coef(sums_from, sums_to, n):
+    """sums [B, 3, 2] (or [3, 2]) uint64 of two image sets over n pixels per frame, as `channel_sums_u8` gives them -> float32
+    coefficients of the same shape, gain then offset: gain * p + offset takes the mean and standard deviation of `from` to
+    those of `to`, the gain clamped to 0.5 .. 2 (include/d3f_hip.h: d3f_color_match_coef)."""
+    if (sums_from.dtype != torch.uint64 or sums_to.dtype != torch.uint64 or sums_from.shape != sums_to.shape
+            or tuple(sums_from.shape[-2:]) != (3, 2) or sums_from.dim() not in (2, 3)):
+        raise ValueError("color_match_coef expects two uint64 tensors [B, 3, 2] or [3, 2] of one shape")
+    dev = _dev(sums_from)
+    if sums_to.device != dev:
+        raise ValueError("color_match_coef expects both sums on one device")
+    f, t = sums_from.contiguous(), sums_to.contiguous()
+    B = 1 if f.dim() == 2 else f.shape[0]
+    coef = torch.empty(tuple(f.shape), dtype=torch.float32, device=dev)
+    if B > 0:  # (an empty tensor has no pointer to hand over)
+        check(_lib.lib().d3f_color_match_coef(ptr(f), ptr(t), B, int(n), ptr(coef), stream_ptr()))
+    return coef
+
+
+def paste_resize_cubic_u8(patch, frames, box, feather=0, out=None, color=None):
     """The inverse of `crop_resize_cubic_u8` with a blend: uint8 `patch` [H, W, 3] / [B, H, W, 3] on the HIP device is resized
     to the box (x1, y1, cw, ch) of uint8 `frames` [h, w, 3] / [B, h, w, 3] with the same arithmetic and blended in over a
     ramp of `feather` pixels; outside the box the result is the frame (include/d3f_hip.h: d3f_paste_resize_cubic_u8).
     patch: packed pixels, rows may be strided -- the right half of a [B, H, 2W, 3] pair buffer, for one.  out=frames runs in
-    place; otherwise out is a contiguous tensor shaped like frames, allocated when None."""
+    place; otherwise out is a contiguous tensor shaped like frames, allocated when None.
+    color: float32 coefficients [B, 3, 2] ([3, 2] for a single frame), gain then offset per frame and byte-in-pixel, as
+    `color_match_coef` gives them: the patch's resized, clamped value goes through gain * v + offset and a second clamp before
+    the blend (d3f_paste_resize_cubic_color_u8).  None: the plain call."""
     if (patch.dtype != torch.uint8 or patch.shape[-1] != 3 or patch.dim() not in (3, 4) or frames.dtype != torch.uint8
             or frames.shape[-1] != 3 or frames.dim() != patch.dim()):
         raise ValueError("paste_resize_cubic_u8 expects a uint8 patch [H, W, 3] and frames [h, w, 3], or a batch of both")
@@ -743,8 +788,16 @@ def paste_resize_cubic_u8(patch, frames, box, feather=0, out=None):
         o = out.unsqueeze(0) if single and out.dim() == 3 else out
         if tuple(o.shape) != tuple(f.shape) or o.dtype != torch.uint8 or o.device != dev or not o.is_contiguous():
             raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(frames.shape)} on the frames' device")
-    check(_lib.lib().d3f_paste_resize_cubic_u8(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, x1, y1, cw, ch, int(feather),
-                                               ptr(o), stream_ptr()))
+    if color is None:
+        check(_lib.lib().d3f_paste_resize_cubic_u8(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, x1, y1, cw, ch, int(feather),
+                                                   ptr(o), stream_ptr()))
+        return o[0] if single else o
+    coef = color.unsqueeze(0) if single and color.dim() == 2 else color
+    if tuple(coef.shape) != (B, 3, 2) or coef.dtype != torch.float32 or coef.device != dev:
+        raise ValueError(f"color must be a float32 tensor of shape {(B, 3, 2)} on the frames' device")
+    coef = coef.contiguous()
+    check(_lib.lib().d3f_paste_resize_cubic_color_u8(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, x1, y1, cw, ch, int(feather),
+                                                     ptr(coef), ptr(o), stream_ptr()))
     return o[0] if single else o
 
 

@@ -27,10 +27,12 @@ def main():
         output=args.output,
         feather=args.feather,
         antialias=args.antialias,
+        color_match=args.color_match,
         )
 
 
 OUTPUTS = ("pair", "full")
+COLOR_MATCHES = ("none", "meanstd")
 
 
 def parse_command_line_arguments(argv=None):
@@ -52,7 +54,14 @@ def parse_command_line_arguments(argv=None):
                         help="resize the crop with the antialiased bicubic filter (Pillow's); use it when the crop is "
                              "several times the network's size, and on a model whose training images were made with it")
 
-    return parser.parse_args(argv)
+    parser.add_argument("--color-match", choices=list(COLOR_MATCHES), default=None,
+                        help="--output full: match the fake's colour to the crop it replaces before the paste; meanstd: "
+                             "mean and standard deviation per frame and channel (default: none)")
+
+    args = parser.parse_args(argv)
+    if args.color_match is not None and args.output != "full":
+        parser.error("--color-match needs --output full: the real|fake pair is not pasted anywhere")
+    return args
 
 
 class RenderFakeVideo():
@@ -61,10 +70,12 @@ class RenderFakeVideo():
     checkpoint.  With both hooks no video file is touched and cv2 is not needed.
     output="full" takes the writer's size from the first frame, so the writer is opened when the first batch arrives: a
     source without frames leaves no output file (output="pair" knows its size up front and leaves an empty video).
-    antialias=True: the crop is resized to the network's size with the antialiased bicubic filter, in either output."""
+    antialias=True: the crop is resized to the network's size with the antialiased bicubic filter, in either output.
+    color_match="meanstd" (output="full" only): the fake's mean and standard deviation are matched to those of the crop it
+    replaces, per frame and channel, before the paste; None / "none": the fake is pasted as the network made it."""
 
     def __init__(self, video_path, checkpoint_path, model_a_or_b, image_width, image_height, batch_frames=1,
-                 frames=None, sink=None, model=None, output="pair", feather=None, antialias=False):
+                 frames=None, sink=None, model=None, output="pair", feather=None, antialias=False, color_match=None):
 
         self.video_path = Path(video_path)
         self.checkpoint_path = Path(checkpoint_path) if checkpoint_path is not None else None
@@ -79,6 +90,11 @@ class RenderFakeVideo():
         self.output = output
         self.feather = None if feather is None else int(feather)
         self.antialias = bool(antialias)
+        if not (color_match is None or isinstance(color_match, str)) or color_match not in (None,) + COLOR_MATCHES:
+            raise ValueError(f"color_match is None or one of {COLOR_MATCHES}, not {color_match!r}")
+        if color_match is not None and output != "full":
+            raise ValueError("color_match needs output='full': the real|fake pair is not pasted anywhere")
+        self.color_match = color_match
         self.frames = frames
         self.sink = sink
 
@@ -128,7 +144,7 @@ class RenderFakeVideo():
                                                             self.get_input_video_properties())).write
                 full = self.model.predict_fake_frames_full(batch, self.model_a_or_b, self.image_width,
                                                            self.image_height, feather=self.feather,
-                                                           antialias=self.antialias)
+                                                           antialias=self.antialias, color_match=self.color_match)
                 for frame in full[:real_frames]:  # the padding of a short last batch is dropped
                     write(frame)
 

@@ -866,15 +866,20 @@ class Unet(nn.Module, _NetsRuntime):
 
     @torch.no_grad()
     def predict_frames_full_u8(self, raw_bgr, size, mean, std, feather=None, graph=True, out=None, pair_out=None,
-                               antialias=False):
+                               antialias=False, color_match=None):
         """`predict_frames_u8`, then the fake pasted back into the source frames: uint8 BGR frames [h,w,3] or [B,h,w,3] on
         the HIP device -> the frames at their own size with the centre-crop box replaced by the fake, resized back
         (`ops.paste_resize_cubic_u8`) and blended in over `feather` source pixels (None: `ops.default_feather` of the
         box), all in one C call.  Returns the full frames.  pair_out: a [B,H,2W,3] buffer, filled as `predict_frames_u8`
         fills it (allocated when None: it stages the fake).  out=raw_bgr pastes in place (graph=False only).  `graph=True`
         replays a hipGraph of its own, captured per set of buffers, frame size, box and feather.  antialias: as
-        `predict_frames_u8`, for the crop-to-network resize only; the paste enlarges and stays as it is."""
+        `predict_frames_u8`, for the crop-to-network resize only; the paste enlarges and stays as it is.
+        color_match: None / "none", or "meanstd": the fake's mean and standard deviation are matched to the resized real
+        crop's, per frame and channel, before the paste (`ops.channel_sums_u8` of both halves of the pair,
+        `ops.color_match_coef`, `ops.paste_resize_cubic_u8(..., color=)`, still in the one C call; the handle's
+        D3F_COLOR_MEANSTD mode).  pair_out is not touched by it; a change between calls re-captures the graph."""
         from . import ops
+        color_mode = _lib.color_match_mode(color_match)
         if raw_bgr.dtype != torch.uint8 or raw_bgr.shape[-1] != 3 or raw_bgr.dim() not in (3, 4):
             raise ValueError("predict_frames_full_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3] in BGR order")
         if raw_bgr.device.type != "cuda":
@@ -914,6 +919,9 @@ class Unet(nn.Module, _NetsRuntime):
         m = (C.c_float * 3)(*[float(v) for v in mean])
         sd = (C.c_float * 3)(*[float(v) for v in std])
         self._set_frame_resample(eng, antialias)
+        if getattr(eng, "color_mode", _lib.COLOR_NONE) != color_mode:  # (the handle starts at D3F_COLOR_NONE)
+            check(_lib.lib().d3f_unet_set_frame_color_match(eng.h, color_mode))
+            eng.color_mode = color_mode
         check(_lib.lib().d3f_unet_predict_frames_full_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), h, w, x1, y1, cw,
                                                          ch, feather, ptr(pair_out), ptr(full), m, sd, ptr(eng.workspace),
                                                          1 if graph else 0, stream_ptr()))

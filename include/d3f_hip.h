@@ -212,6 +212,23 @@ int d3f_unet_predict_frames_full_u8(d3f_unet_t h, const float* params, float* bn
 #define D3F_RESAMPLE_CUBIC_AA 1
 int d3f_unet_set_frame_resample(d3f_unet_t h, int mode);
 int d3f_unet_frame_resample(d3f_unet_t h); /* the mode, or < 0 for a null handle */
+/* Whether d3f_unet_predict_frames_full_u8 matches the fake's colour to the resized real crop before it pastes:
+ *   D3F_COLOR_NONE     no.  The default after d3f_unet_create; the launches are exactly those of a handle that never heard
+ *                      of the setting.
+ *   D3F_COLOR_MEANSTD  after the launches into pair_out, TWO more launches and the paste in its colour form: one launch takes
+ *                      the sums of d3f_channel_sums_u8 over both halves of pair_out (every workgroup stores a partial row; no
+ *                      accumulator to reset), one adds the rows in a fixed order and forms d3f_color_match_coef's
+ *                      coefficients with from = the right half (the fake) and to = the left half (the resized real crop),
+ *                      n = H * W; then d3f_paste_resize_cubic_color_u8.  full_out is bit for bit the composition of the three
+ *                      operators on pair_out; pair_out itself stays byte for byte what d3f_unet_predict_frames_u8 writes.
+ * The partial sums and the coefficients live in device memory that belongs to the handle: allocated at the first switch to a
+ * mode other than D3F_COLOR_NONE, freed with the handle, nothing inside a frame call.  d3f_unet_predict_frames_u8 ignores the
+ * mode.  The mode is part of the full-frame graph's key, and setting a different value drops the handle's captured frames and
+ * full-frame graphs.  Refused: an unknown mode, a pair handle, and a handle whose H * W is above 2^22 (at set time). */
+#define D3F_COLOR_NONE 0
+#define D3F_COLOR_MEANSTD 1
+int d3f_unet_set_frame_color_match(d3f_unet_t h, int mode);
+int d3f_unet_frame_color_match(d3f_unet_t h); /* the mode, or < 0 for a null handle */
 /* gradients of every parameter (written, not accumulated) for the preceding training forward.
  * The backward pass is cut into d3f_unet_num_segments() buckets so a data-parallel caller can
  * all-reduce bucket k while bucket k+1 computes: run segments [seg_begin, seg_end) in order 0..n;
@@ -524,6 +541,38 @@ int d3f_crop_resize_cubic_aa_u8(const uint8_t* src, int B, int src_h, int src_w,
 int d3f_paste_resize_cubic_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
                               const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather,
                               uint8_t* out, void* stream);
+
+/* Colour match of a pasted patch: mean / std (Reinhard) matching per frame and per byte-in-pixel, in three operators.  The
+ * definitions are the acceptance contract; tests/color_match_restatement.py restates them (sums with Python integers,
+ * coefficients in float64, the paste on top of tests/paste_restatement.py).
+ *
+ * d3f_channel_sums_u8: img [B][H][W][3] uint8, rows row_stride_bytes apart (>= 3 * W; frames H rows apart; 6 * W reads one
+ * half of a pair_out buffer), from any byte address.  sums [B][3][2] uint64: for frame b and byte-in-pixel c, S = sum of p and
+ * Q = sum of p * p over all n = H * W pixels, exact.  The call OVERWRITES sums: the reset of the accumulators is part of the
+ * enqueued work, so a captured call replayed on new bytes gives the new sums.  Refused before any device call: null
+ * pointers, B < 0 or B > 65535 (B == 0 launches nothing), non-positive sizes, a stride below 3 * W, H * W > 2^22 (the limit
+ * keeps n * Q and S * S below 2^60, so the next step is exact in 64-bit integers). */
+int d3f_channel_sums_u8(const uint8_t* img, int B, int H, int W, int64_t row_stride_bytes, uint64_t* sums, void* stream);
+/* d3f_color_match_coef: sums_from, sums_to [B][3][2] uint64 as above, both over n pixels -> coef [B][3][2] fp32, gain then
+ * offset, such that gain * p + offset takes the mean and standard deviation of `from` to those of `to`.  Per (b, c), in
+ * float64:
+ *   - D = n * Q - S * S as exact uint64, for from and to; m = (double)S / (double)n for each;
+ *   - g = 1 if D_from == 0 or D_to == 0, else sqrt((double)D_to / (double)D_from);
+ *   - g = fmin(fmax(g, D3F_COLOR_GAIN_MIN), D3F_COLOR_GAIN_MAX): a design choice, not a measurement -- it keeps a nearly flat
+ *     frame from amplifying noise eight-fold;
+ *   - o = m_to - g * m_from, product and difference rounded separately; coef = (float)g, (float)o.
+ * Refused before any device call: null pointers, B < 0 or B > 65535 (B == 0 launches nothing), n <= 0 or n > 2^22. */
+#define D3F_COLOR_GAIN_MIN 0.5
+#define D3F_COLOR_GAIN_MAX 2.0
+int d3f_color_match_coef(const uint64_t* sums_from, const uint64_t* sums_to, int B, int64_t n, float* coef, void* stream);
+/* d3f_paste_resize_cubic_color_u8: d3f_paste_resize_cubic_u8 with one insertion.  coef [B][3][2] fp32 in device memory; at
+ * frame b, byte-in-pixel c, after v = fminf(fmaxf(v, 0), 255): w = coef[b][c][0] * v (rounded), w = w + coef[b][c][1]
+ * (rounded), w = fminf(fmaxf(w, 0), 255), and the blend takes w where it took v.  Ramp, blend, in-place form, tile selection
+ * and refusals are those of d3f_paste_resize_cubic_u8 (the same kernel with one more template parameter); a null coef and a
+ * coef whose B * 24 bytes overlap out are refused too.  Coefficients (1, 0) give d3f_paste_resize_cubic_u8's bytes. */
+int d3f_paste_resize_cubic_color_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                    const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather,
+                                    const float* coef, uint8_t* out, void* stream);
 
 /* log_batch_as_image_grid of the three LitModules (d3f/train_deep_fake/lit_module.py:235-249,
  * d3f/train_denoiser/lit_module.py:157-171, d3f/balance_training_images/lit_module.py:197-211):

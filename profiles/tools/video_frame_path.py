@@ -13,10 +13,21 @@
                  Unet.predict_u8 (the eval forward of the same call) at the same size: 1080x1920 -> 448x448 and 256x256,
                  2160x3840 -> 256x256, B = 1 and B = 8; with the byte bound (crop read once, output written once)
 
+  --color      : instead of the above, the colour match of the full-frame output: Unet.predict_frames_full_u8 with
+                 color_match=None and "meanstd" (two networks, so that neither handle's mode ever changes and no graph is
+                 re-captured inside a timed block), eager and hipGraph, next to the operators the mode adds -- the sums of
+                 both halves of the pair (two d3f_channel_sums_u8 calls: each a zeroing launch and the sums kernel, where the
+                 fused call takes both halves in one launch and zeroes nothing), d3f_color_match_coef, and the paste in its
+                 plain and colour forms: 1080x1920 -> 448x448 and 256x256, B = 1 and B = 8; with the byte bound of the sums
+                 (2 * H * W * 3 bytes read per frame).  On a library without the colour entries (an older build named
+                 through D3F_LIB), or with --off-only, only the color_match=None forms run: the parent's figures for the
+                 same launches, and this library's in the same sequence of allocations and captures (the hipGraph figures
+                 depend on that sequence: profiles/README.md "Colour match")
+
 Back-to-back enqueues on one stream, ITERS iterations after WARMUP, the forms alternating in ROUNDS rounds; the figure is
 the median round's time per call (and per frame).  Host work of the reference's loop (cv2.resize on one CPU thread, the
 concatenate, two PCIe trips) is not part of any figure here.  One JSON line at the end.
-    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N] [--antialias]
+    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N] [--antialias | --color [--off-only]]
 """
 import argparse
 import json
@@ -83,9 +94,69 @@ def antialias_section(net, args, g):
     print(json.dumps(result))
 
 
+def color_section(args, g):
+    """the colour match mode against the same call without it, and the operators it adds, per frame; one JSON line"""
+    has_color = hasattr(_lib.lib(), "d3f_unet_set_frame_color_match") and not args.off_only
+    result = {"precision": args.precision, "digest": _lib.built_digest(), "iters": args.iters, "rounds": args.rounds,
+              "has_color": has_color, "color_us_per_frame": {}}
+    torch.manual_seed(0)
+    net_off = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
+    net_on = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
+    for side in (448, 256):
+        size = (side, side)
+        box = ops.center_crop_box(RAW[0], RAW[1], side, side)
+        feather = ops.default_feather(box[2], box[3])
+        need = 2 * side * side * 3  # bytes the sums read per frame: both halves of the pair once
+        bound = need / 6.3e12 * 1e6  # at 6.3 TB/s achievable HBM
+        for B in (1, 8):
+            raw = torch.randint(0, 256, (B,) + RAW + (3,), generator=g, dtype=torch.uint8).cuda()
+            pair = net_off.predict_frames_u8(raw, size, MEAN, STD, graph=False).clone()
+            bufs = {k: (torch.empty_like(raw), torch.empty_like(pair)) for k in ("oe", "og", "me", "mg")}
+            full = torch.empty_like(raw)
+
+            def call(net, key, graph, mode):
+                return lambda: net.predict_frames_full_u8(raw, size, MEAN, STD, graph=graph, out=bufs[key][0],
+                                                          pair_out=bufs[key][1], color_match=mode)
+            forms = {"off_eager": call(net_off, "oe", False, None), "off_graph": call(net_off, "og", True, None),
+                     "paste": lambda: ops.paste_resize_cubic_u8(pair[:, :, side:], raw, box, feather, out=full)}
+            if has_color:
+                s_to = ops.channel_sums_u8(pair[:, :, :side])
+                s_from = ops.channel_sums_u8(pair[:, :, side:])
+                coef = ops.color_match_coef(s_from, s_to, side * side)
+
+                def both_sums():
+                    ops.channel_sums_u8(pair[:, :, :side], out=s_to)
+                    ops.channel_sums_u8(pair[:, :, side:], out=s_from)
+                forms.update({
+                    "meanstd_eager": call(net_on, "me", False, "meanstd"), "meanstd_graph": call(net_on, "mg", True, "meanstd"),
+                    "sums_both_halves_ops": both_sums,
+                    "coef_op": lambda: ops.color_match_coef(s_from, s_to, side * side),
+                    "paste_color": lambda: ops.paste_resize_cubic_u8(pair[:, :, side:], raw, box, feather, out=full, color=coef),
+                })
+            t = compare(forms, args.warmup, args.iters, args.rounds)
+            key = f"{RAW[0]}x{RAW[1]}_to_{side}_B{B}"
+            row = {}
+            for name, (med, lo, hi) in t.items():
+                print(f"{key:24s} {name:22s} {med / B:9.2f} us per frame (min {lo / B:.2f}, max {hi / B:.2f})")
+                row[name] = [round(med / B, 2), round(lo / B, 2), round(hi / B, 2)]
+            if has_color:
+                row["added_eager"] = round((t["meanstd_eager"][0] - t["off_eager"][0]) / B, 2)
+                row["added_graph"] = round((t["meanstd_graph"][0] - t["off_graph"][0]) / B, 2)
+                row["sums_bytes"], row["sums_byte_bound_us"] = need, round(bound, 3)
+                print(f"{key:24s} colour match adds {row['added_eager']:.2f} (eager) / {row['added_graph']:.2f} (hipGraph) us per "
+                      f"frame; the sums read {need} bytes per frame, byte bound {bound:.3f} us")
+            result["color_us_per_frame"][key] = row
+            del raw, bufs, full
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--antialias", action="store_true", help="measure the antialiased resize instead (see above)")
+    ap.add_argument("--color", action="store_true", help="measure the colour match of the full-frame output instead (see above)")
+    ap.add_argument("--off-only", action="store_true",
+                    help="--color: only the color_match=None forms, as on a library without the colour entries -- the same "
+                         "sequence of allocations and captures on both sides of an A/B of the unchanged path")
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
@@ -93,6 +164,8 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     print(f"{torch.cuda.get_device_name(0)}, torch {torch.__version__}, library digest {_lib.built_digest()}")
+    if args.color:
+        return color_section(args, torch.Generator().manual_seed(1))
     torch.manual_seed(0)
     net = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
     g = torch.Generator().manual_seed(1)
