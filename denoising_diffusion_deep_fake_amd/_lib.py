@@ -34,6 +34,35 @@ def color_match_mode(color_match):
     return COLOR_MATCH_MODES[color_match]
 
 
+TEMPORAL_STRENGTH, TEMPORAL_THRESHOLD = 0.75, 8  # D3F_TEMPORAL_*: design choices, not measurements
+
+
+def temporal_setting(temporal, threshold=None):
+    """(strength, threshold) of temporal = None (off: strength 0) / a strength / (strength, threshold); the strength as the
+    float32 the handle will hold.  A strength outside [0, 1) or NaN, a threshold outside 1..255 and anything else are a
+    ValueError.  threshold: what a bare strength gets (None: D3F_TEMPORAL_THRESHOLD)."""
+    import struct
+    thr = TEMPORAL_THRESHOLD if threshold is None else threshold
+    if temporal is None:
+        strength = 0.0
+    elif isinstance(temporal, (tuple, list)):
+        if len(temporal) != 2:
+            raise ValueError(f"temporal is None, a strength or (strength, threshold), not {temporal!r}")
+        strength, thr = temporal
+    else:
+        strength = temporal
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)):
+        raise ValueError(f"temporal: the strength is a number in [0, 1), not {strength!r}")
+    if isinstance(thr, bool) or not isinstance(thr, int) or not 1 <= thr <= 255:
+        raise ValueError(f"temporal: the threshold is an integer in 1..255, not {thr!r}")
+    if 0.0 <= strength < 1.0:  # (0.99999999 rounds to 1.0f: the second look refuses it)
+        strength = struct.unpack("f", struct.pack("f", float(strength)))[0]
+    if not 0.0 <= strength < 1.0:
+        raise ValueError(f"temporal: the strength is a number in [0, 1), not {strength!r}")
+    return (strength + 0.0, int(thr))
+
+
+
 class D3FError(RuntimeError):
     pass
 
@@ -105,6 +134,9 @@ PROTOTYPES = {
     "d3f_unet_frame_resample": (_i, [_p]),
     "d3f_unet_set_frame_color_match": (_i, [_p, _i]),
     "d3f_unet_frame_color_match": (_i, [_p]),
+    "d3f_unet_set_frame_temporal": (_i, [_p, _f, _i]),
+    "d3f_unet_frame_temporal": (_i, [_p, C.POINTER(_f), C.POINTER(_i)]),
+    "d3f_unet_frame_temporal_reset": (_i, [_p, _p]),
     "d3f_unet_num_params": (_i, [_p]),
     "d3f_unet_param_info": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(C.c_int32), C.POINTER(_i), C.POINTER(_i64)]),
     "d3f_unet_param_floats": (_i64, [_p]),
@@ -137,6 +169,9 @@ PROTOTYPES = {
     "d3f_channel_sums_u8": (_i, [_p, _i, _i, _i, _i64, _p, _p]),
     "d3f_color_match_coef": (_i, [_p, _p, _i, _i64, _p, _p]),
     "d3f_paste_resize_cubic_color_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "d3f_temporal_filter_u8": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _p, _p, _p, _f, _i, _p]),
+    "d3f_color_coef_smooth": (_i, [_p, _p, _i, _i64, _f, _p, _p, _p, _p]),
+    "d3f_temporal_flag_set": (_i, [_p, _i, _p]),
     "d3f_unet_predict_frames_full_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, C.POINTER(_f), C.POINTER(_f),
                                              _p, _i, _p]),
     "d3f_image_grid_shape": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),

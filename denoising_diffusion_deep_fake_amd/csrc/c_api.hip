@@ -212,6 +212,22 @@ int d3f_unet_set_frame_color_match(d3f_unet_t h, int mode) {
   return h->e.set_frame_color_match(mode);
 }
 int d3f_unet_frame_color_match(d3f_unet_t h) { return h ? h->e.frame_color_match() : -1; }
+int d3f_unet_set_frame_temporal(d3f_unet_t h, float strength, int threshold) {
+  D3F_CHECK(h, "unet_set_frame_temporal: null handle");
+  if (int rc = single_net(h, "unet_set_frame_temporal", "has no frame entries (run each network alone)")) return rc;
+  return h->e.set_frame_temporal(strength, threshold);
+}
+int d3f_unet_frame_temporal(d3f_unet_t h, float* strength, int* threshold) {
+  D3F_CHECK(h, "unet_frame_temporal: null handle");
+  if (strength) *strength = h->e.frame_temporal_strength();
+  if (threshold) *threshold = h->e.frame_temporal_threshold();
+  return 0;
+}
+int d3f_unet_frame_temporal_reset(d3f_unet_t h, void* stream) {
+  D3F_CHECK(h, "unet_frame_temporal_reset: null handle");
+  if (int rc = single_net(h, "unet_frame_temporal_reset", "has no frame entries (run each network alone)")) return rc;
+  return h->e.frame_temporal_reset((hipStream_t)stream);
+}
 int d3f_unet_num_params(d3f_unet_t h) { return h ? (int)h->e.params.size() : -1; }
 int d3f_unet_param_info(d3f_unet_t h, int i, char* name, int name_cap, int32_t shape[4], int* ndim,
                         int64_t* offset) {
@@ -791,6 +807,25 @@ int d3f_paste_resize_cubic_color_u8(const uint8_t* patch, int B, int H, int W, i
   D3F_CHECK(patch && frame && out && coef, "paste_resize_cubic_color_u8: null argument");
   return paste_resize_cubic_color_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, x1, y1, cw, ch,
                                             feather, coef, out, (hipStream_t)stream);
+}
+
+int d3f_temporal_filter_u8(const uint8_t* real, int64_t real_row_stride_bytes, uint8_t* fake, int64_t fake_row_stride_bytes,
+                           int B, int H, int W, float* state_fake, uint8_t* state_real, int32_t* state_valid, float strength,
+                           int threshold, void* stream) {
+  D3F_CHECK(real && fake && state_fake && state_real && state_valid, "temporal_filter_u8: null argument");
+  return temporal_filter_u8_launch(real, fake, B, H, W, (long)real_row_stride_bytes, (long)fake_row_stride_bytes, state_fake,
+                                   state_real, state_valid, strength, threshold, (hipStream_t)stream);
+}
+
+int d3f_color_coef_smooth(float* coef, const uint64_t* sums_to, int B, int64_t n, float strength, float* state_coef,
+                          uint64_t* state_sum, int32_t* state_valid, void* stream) {
+  D3F_CHECK(coef && sums_to && state_coef && state_sum && state_valid, "color_coef_smooth: null argument");
+  return color_coef_smooth_launch(coef, sums_to, 1, B, (long)n, strength, state_coef, state_sum, state_valid,
+                                  (hipStream_t)stream);
+}
+
+int d3f_temporal_flag_set(int32_t* flag, int value, void* stream) {
+  return temporal_flag_set_launch(flag, value, (hipStream_t)stream);
 }
 
 int d3f_image_grid_shape(int images, int nrow, int padding, int H, int W, int32_t dims[2]) {

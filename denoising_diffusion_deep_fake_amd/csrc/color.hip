@@ -169,6 +169,69 @@ __global__ __launch_bounds__(64) void color_match_coef_kernel(const u64* __restr
   coef[((long)b * 3 + c) * 2 + 1] = (float)offset;
 }
 
+// Temporal smoothing of the coefficients (include/d3f_hip.h: d3f_color_coef_smooth).  One wave for the whole batch, the
+// frames in order: the lanes add a frame's rows of `to` sums (parts == 1: the sums themselves) with shuffles, every lane
+// then holds the three S and decides the cut in exact 64-bit integers, and lanes 0..5 carry one coefficient each from
+// frame to frame in a register.  valid is read here and set by the launch function's flag launch behind this one.
+__global__ __launch_bounds__(64) void color_coef_smooth_kernel(float* __restrict__ coef, const u64* __restrict__ to, int parts,
+                                                               int B, u64 n, float strength, float* __restrict__ state_coef,
+                                                               u64* __restrict__ state_sum, const int* __restrict__ valid) {
+  const int lane = threadIdx.x;
+  bool have_prev = *valid != 0;
+  u64 sp[3] = {0, 0, 0};
+  float cp = 0.f;
+  if (have_prev) {
+    for (int c = 0; c < 3; ++c) sp[c] = state_sum[c];
+    if (lane < 6) cp = state_coef[lane];
+  }
+  const u64 limit = (u64)D3F_TEMPORAL_CUT_LEVELS * n;
+  for (int b = 0; b < B; ++b) {
+    u64 s[3] = {0, 0, 0};
+    for (int p = lane; p < parts; p += 64)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) s[c] += to[(((long)b * parts + p) * 3 + c) * 2];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) s[c] += __shfl_xor(s[c], off, 64);
+    bool cut = !have_prev;
+    if (have_prev)
+      for (int c = 0; c < 3; ++c) {
+        const u64 d = s[c] > sp[c] ? s[c] - sp[c] : sp[c] - s[c];
+        if (d > limit) cut = true;
+      }
+    if (lane < 6) {
+      const float cn = coef[(long)b * 6 + lane];
+      float v = cn;
+      if (!cut) {  // c' + a * (c_prev - c'), three roundings; at a cut c' itself, and the state is not read
+        const float d = __fsub_rn(cp, cn);
+        const float q = __fmul_rn(strength, d);
+        v = __fadd_rn(cn, q);
+      }
+      coef[(long)b * 6 + lane] = v;
+      cp = v;
+    }
+    for (int c = 0; c < 3; ++c) sp[c] = s[c];
+    have_prev = true;
+  }
+  if (lane < 6) state_coef[lane] = cp;
+  if (lane < 3) state_sum[lane] = sp[lane];
+}
+
+int color_coef_smooth_launch(float* coef, const uint64_t* sums_to, int parts, int B, long n, float strength, float* state_coef,
+                             uint64_t* state_sum, int* state_valid, hipStream_t stream) {
+  D3F_CHECK(B >= 0 && B <= 65535, "color_coef_smooth: B %d outside 0..65535 frames per call", B);
+  D3F_CHECK(n > 0 && n <= COLOR_MAX_PIXELS, "color_coef_smooth: n %ld outside 1..%ld pixels per frame", n, COLOR_MAX_PIXELS);
+  D3F_CHECK(parts >= 1 && parts <= COLOR_SUMS_MAX_PARTS, "color_coef_smooth: %d rows per frame", parts);
+  D3F_CHECK(strength >= 0.f && strength < 1.f, "color_coef_smooth: strength %g outside [0, 1)", (double)strength);  // (NaN fails)
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(color_coef_smooth_kernel, dim3(1), dim3(64), 0, stream, coef, reinterpret_cast<const u64*>(sums_to), parts,
+                     B, (u64)n, strength, state_coef, reinterpret_cast<u64*>(state_sum), state_valid);
+  D3F_HIP(hipGetLastError());
+  // behind the kernel on the stream (temporal.hip)
+  return temporal_flag_set_launch(state_valid, 1, stream);
+}
+
 int channel_sums_check(int B, int H, int W, long row_stride) {
   D3F_CHECK(B >= 0 && B <= 65535, "channel_sums: B %d outside 0..65535 frames per call", B);
   D3F_CHECK(H > 0 && W > 0, "channel_sums: non-positive size (%d x %d)", H, W);

@@ -166,6 +166,16 @@ class UnetEngine {
   enum { FRAME_COLOR_NONE = 0, FRAME_COLOR_MEANSTD = 1 };
   int set_frame_color_match(int mode);
   int frame_color_match() const { return frame_color_; }
+  // The temporal filter of the two frame entries (include/d3f_hip.h: d3f_unet_set_frame_temporal).  strength 0 (the default)
+  // is off: exactly the launches of an engine without the setting.  On: behind the launches into pair_out, the filter launch
+  // on its two halves and the state-and-flag launch; in predict_frames_full_u8 with MEANSTD the coefficients' smoothing behind the
+  // coefficient launch.  The state of both is the engine's own device memory, allocated at the first switch on and freed
+  // with the engine.  A change of either value drops the two captured frame graphs and makes the next frame a first frame:
+  // the setter has no stream, so the reset is enqueued by the next frame call, on its stream, in front of its launches.
+  int set_frame_temporal(float strength, int threshold);
+  float frame_temporal_strength() const { return temporal_strength_; }
+  int frame_temporal_threshold() const { return temporal_threshold_; }
+  int frame_temporal_reset(hipStream_t s) const;
   int export_tensor(const char* name, const void* ws, float* out_nchw, hipStream_t s) const;
   int export_shape(const char* name, int32_t dims[3]) const;
 
@@ -235,11 +245,11 @@ class UnetEngine {
                                  hipStream_t s) const;
   // captured graphs: one slot per entry point; a slot is re-captured when what it baked in changes -- the pointers, the
   // constants and (predict_frames_u8, predict_frames_full_u8) the raw frame size and crop box, the latter's full_out, feather
-  // and colour match mode
+  // and colour match mode, and both frame entries' temporal filter setting (strength bits, threshold)
   struct GraphKey {
     const void* ptr[6];
     float cst[6];
-    int geo[8];
+    int geo[10];
   };
   struct GraphSlot {
     hipGraphExec_t exec = nullptr;
@@ -264,6 +274,21 @@ class UnetEngine {
   // the sums launch, and the buffer has room for the most)
   uint64_t* color_slabs_ = nullptr;
   float* color_coef_ = nullptr;      // [B][3][2]
+  float temporal_strength_ = 0.f;    // 0: off
+  int temporal_threshold_ = 8;       // D3F_TEMPORAL_THRESHOLD
+  // the filter's state (state_fake [H][W][3] fp32, state_real [H][W][3] bytes), the smoothing's (state_coef [3][2] fp32,
+  // state_sum [3] uint64) and the two valid flags (the filter's, then the smoothing's)
+  float* temporal_fake_ = nullptr;
+  uint8_t* temporal_real_ = nullptr;
+  float* temporal_coef_ = nullptr;
+  uint64_t* temporal_sum_ = nullptr;
+  int* temporal_valid_ = nullptr;
+  mutable bool temporal_reset_pending_ = false;  // a changed setting: the next frame call zeroes the flags on its stream
+  int temporal_key() const;  // the strength's bits, for the graph keys
+  // the filter's launches on the halves of pair_out, behind predict_frames_u8_launches
+  int temporal_filter_launches(uint8_t* pair_out, hipStream_t s) const;
+  // in front of a frame call's launches and outside its graph: the pending reset, on the caller's stream
+  int temporal_begin(hipStream_t s) const;
   // the host-side argument check of the frame entries' resize, in the mode that is set
   int frame_resize_check(int src_h, int src_w, int x1, int y1, int cw, int ch) const;
   // NCHW fp32 head output: predict_u8's, and z of an activated head, which the head of the backward pass turns into dz IN

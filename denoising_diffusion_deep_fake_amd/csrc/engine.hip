@@ -731,6 +731,55 @@ int UnetEngine::set_frame_color_match(int mode) {
   return 0;
 }
 
+int UnetEngine::set_frame_temporal(float strength, int threshold) {
+  D3F_CHECK(strength >= 0.f && strength < 1.f, "frame temporal filter: strength %g outside [0, 1) (0 is off)",
+            (double)strength);  // (NaN fails)
+  D3F_CHECK(threshold >= 1 && threshold <= 255, "frame temporal filter: threshold %d outside 1..255", threshold);
+  if (strength == 0.f) strength = 0.f;  // (-0 is off as well, with the bits of 0)
+  if (memcmp(&strength, &temporal_strength_, sizeof(float)) == 0 && threshold == temporal_threshold_) return 0;
+  if (strength != 0.f) {
+    const size_t px = (size_t)H * W;
+    // (each on its own: a call that failed half way leaves a state the next call completes)
+    if (temporal_fake_ == nullptr) D3F_HIP(hipMalloc(reinterpret_cast<void**>(&temporal_fake_), px * 3 * sizeof(float)));
+    if (temporal_real_ == nullptr) D3F_HIP(hipMalloc(reinterpret_cast<void**>(&temporal_real_), px * 3));
+    if (temporal_coef_ == nullptr) D3F_HIP(hipMalloc(reinterpret_cast<void**>(&temporal_coef_), 6 * sizeof(float)));
+    if (temporal_sum_ == nullptr) D3F_HIP(hipMalloc(reinterpret_cast<void**>(&temporal_sum_), 3 * sizeof(uint64_t)));
+    if (temporal_valid_ == nullptr) D3F_HIP(hipMalloc(reinterpret_cast<void**>(&temporal_valid_), 2 * sizeof(int)));
+  }
+  for (GraphSlot* slot : {&g_frames_, &g_frames_full_})
+    if (slot->exec) {
+      (void)hipGraphExecDestroy(slot->exec);
+      slot->exec = nullptr;
+    }
+  temporal_strength_ = strength;
+  temporal_threshold_ = threshold;
+  temporal_reset_pending_ = true;
+  return 0;
+}
+
+int UnetEngine::temporal_key() const {
+  int bits;
+  memcpy(&bits, &temporal_strength_, sizeof(bits));
+  return bits;
+}
+
+int UnetEngine::frame_temporal_reset(hipStream_t s) const {
+  temporal_reset_pending_ = false;
+  if (temporal_valid_ == nullptr) return 0;  // never on: nothing to forget
+  if (int rc = temporal_flag_set_launch(temporal_valid_, 0, s)) return rc;
+  return temporal_flag_set_launch(temporal_valid_ + 1, 0, s);
+}
+
+int UnetEngine::temporal_begin(hipStream_t s) const {
+  if (!temporal_reset_pending_) return 0;
+  return frame_temporal_reset(s);
+}
+
+int UnetEngine::temporal_filter_launches(uint8_t* pair_out, hipStream_t s) const {
+  return temporal_filter_u8_launch(pair_out, pair_out + 3L * W, B, H, W, 6L * W, 6L * W, temporal_fake_, temporal_real_,
+                                   temporal_valid_, temporal_strength_, temporal_threshold_, s);
+}
+
 int UnetEngine::frame_resize_check(int src_h, int src_w, int x1, int y1, int cw, int ch) const {
   if (frame_resample_ == FRAME_RESAMPLE_CUBIC_AA)
     return crop_resize_cubic_aa_check(B, src_h, src_w, x1, y1, cw, ch, H, W, 6L * W);
@@ -795,13 +844,22 @@ int UnetEngine::predict_frames_u8(const float* params_, float* bnstats, const ui
   }
   if (int rc = frame_resize_check(src_h, src_w, x1, y1, cw, ch)) return rc;
   const int geo[6] = {src_h, src_w, x1, y1, cw, ch};
-  if (!use_graph) return predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, s);
+  const bool temporal = temporal_strength_ != 0.f;
+  if (temporal) {
+    if (int rc = temporal_filter_check(pair_out, pair_out + 3L * W, B, H, W, 6L * W, 6L * W, temporal_fake_, temporal_real_,
+                                       temporal_valid_, temporal_strength_, temporal_threshold_))
+      return rc;
+    if (int rc = temporal_begin(s)) return rc;
+  }
+  auto launches = [&](hipStream_t ls) {
+    if (int rc = predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, ls)) return rc;
+    return temporal ? temporal_filter_launches(pair_out, ls) : 0;
+  };
+  if (!use_graph) return launches(s);
   const GraphKey key = {{params_, bnstats, raw_in, pair_out, ws_},
                         {m255[0], m255[1], m255[2], s255[0], s255[1], s255[2]},
-                        {src_h, src_w, x1, y1, cw, ch}};
-  return graph_replay(g_frames_, key, s, [&](hipStream_t gs) {
-    return predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, gs);
-  });
+                        {src_h, src_w, x1, y1, cw, ch, 0, 0, temporal_key(), temporal ? temporal_threshold_ : 0}};
+  return graph_replay(g_frames_, key, s, launches);
 }
 
 int UnetEngine::predict_frames_full_u8(const float* params_, float* bnstats, const uint8_t* raw_in, int src_h, int src_w,
@@ -826,8 +884,18 @@ int UnetEngine::predict_frames_full_u8(const float* params_, float* bnstats, con
                                                 ch, feather))
     return rc;
   const int geo[6] = {src_h, src_w, x1, y1, cw, ch};
+  const bool temporal = temporal_strength_ != 0.f;
+  if (temporal) {
+    if (int rc = temporal_filter_check(pair_out, pair_out + 3L * W, B, H, W, 6L * W, 6L * W, temporal_fake_, temporal_real_,
+                                       temporal_valid_, temporal_strength_, temporal_threshold_))
+      return rc;
+    if (int rc = temporal_begin(s)) return rc;
+  }
   auto launches = [&](hipStream_t ls) {
     if (int rc = predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, ls)) return rc;
+    // the temporal filter first: the sums and the paste then read the filtered fake
+    if (temporal)
+      if (int rc = temporal_filter_launches(pair_out, ls)) return rc;
     // the fake half of the pair is the patch: rows 6 * W bytes apart
     if (!color)
       return paste_resize_cubic_u8_launch(pair_out + 3L * W, B, H, W, 6L * W, raw_in, src_h, src_w, x1, y1, cw, ch, feather,
@@ -839,13 +907,18 @@ int UnetEngine::predict_frames_full_u8(const float* params_, float* bnstats, con
     const uint64_t* to = color_slabs_;
     const uint64_t* from = color_slabs_ + (size_t)B * parts * 6;
     if (int rc = color_match_coef_launch(from, to, parts, B, (long)H * W, color_coef_, ls)) return rc;
+    if (temporal)
+      if (int rc = color_coef_smooth_launch(color_coef_, to, parts, B, (long)H * W, temporal_strength_, temporal_coef_,
+                                            temporal_sum_, temporal_valid_ + 1, ls))
+        return rc;
     return paste_resize_cubic_color_u8_launch(pair_out + 3L * W, B, H, W, 6L * W, raw_in, src_h, src_w, x1, y1, cw, ch,
                                               feather, color_coef_, full_out, ls);
   };
   if (!use_graph) return launches(s);
   const GraphKey key = {{params_, bnstats, raw_in, pair_out, ws_, full_out},
                         {m255[0], m255[1], m255[2], s255[0], s255[1], s255[2]},
-                        {src_h, src_w, x1, y1, cw, ch, feather, frame_color_}};
+                        {src_h, src_w, x1, y1, cw, ch, feather, frame_color_, temporal_key(),
+                         temporal ? temporal_threshold_ : 0}};
   return graph_replay(g_frames_full_, key, s, launches);
 }
 
@@ -929,7 +1002,7 @@ int UnetEngine::graph_replay(GraphSlot& slot, const GraphKey& key, hipStream_t s
     D3F_HIP(hipEventCreateWithFlags(&ev_gout_, hipEventDisableTiming));
   }
   // (GraphKey has no padding: pointers, then 4-byte fields filling whole 8-byte units)
-  static_assert(sizeof(GraphKey) == 6 * sizeof(void*) + 6 * sizeof(float) + 8 * sizeof(int), "GraphKey is compared bytewise");
+  static_assert(sizeof(GraphKey) == 6 * sizeof(void*) + 6 * sizeof(float) + 10 * sizeof(int), "GraphKey is compared bytewise");
   const bool same = slot.exec != nullptr && memcmp(&key, &slot.key, sizeof(GraphKey)) == 0;
   if (!same) {
     if (slot.exec) {
@@ -973,6 +1046,11 @@ UnetEngine::~UnetEngine() {
   if (ev_pack_mid_) (void)hipEventDestroy(ev_pack_mid_);
   if (color_slabs_) (void)hipFree(color_slabs_);
   if (color_coef_) (void)hipFree(color_coef_);
+  if (temporal_fake_) (void)hipFree(temporal_fake_);
+  if (temporal_real_) (void)hipFree(temporal_real_);
+  if (temporal_coef_) (void)hipFree(temporal_coef_);
+  if (temporal_sum_) (void)hipFree(temporal_sum_);
+  if (temporal_valid_) (void)hipFree(temporal_valid_);
   // (side_ is the process-wide stream of this device: not ours to destroy)
 }
 

@@ -167,6 +167,22 @@ int channel_sums_pair_slabs_launch(const uint8_t* img, long img_delta, int B, in
 int color_match_coef_launch(const uint64_t* sums_from, const uint64_t* sums_to, int parts, int B, long n, float* coef,
                             hipStream_t stream);
 
+// temporal filter (temporal.hip, color.hip; include/d3f_hip.h: d3f_temporal_filter_u8, d3f_color_coef_smooth).  Both
+// launch functions enqueue their kernel and, behind it, a launch that sets state_valid to 1 (the kernels read the flag and
+// never write it): temporal_flag_set_launch for the smoothing; for the filter the launch that also copies the call's last
+// real frame into state_real, which the filter kernel's workgroups read across tile borders.  temporal_filter_check is the host-side refusal of temporal_filter_u8_launch (real and fake may be
+// the two halves of a pair buffer: one stride, the rows interleaved).  color_coef_smooth_launch reads S of `sums_to`
+// [B][parts][3][2], adding `parts` rows per frame as color_match_coef_launch does.
+int temporal_flag_set_launch(int* flag, int value, hipStream_t stream);
+int temporal_filter_check(const uint8_t* real, const uint8_t* fake, int B, int H, int W, long real_stride, long fake_stride,
+                          const float* state_fake, const uint8_t* state_real, const int* state_valid, float strength,
+                          int threshold);
+int temporal_filter_u8_launch(const uint8_t* real, uint8_t* fake, int B, int H, int W, long real_stride, long fake_stride,
+                              float* state_fake, uint8_t* state_real, int* state_valid, float strength, int threshold,
+                              hipStream_t stream);
+int color_coef_smooth_launch(float* coef, const uint64_t* sums_to, int parts, int B, long n, float strength, float* state_coef,
+                             uint64_t* state_sum, int* state_valid, hipStream_t stream);
+
 // training image grids (image_grid.hip): make_grid + scale + clamp + uint8 of up to 8 fp32 NCHW batches in one launch;
 // `batches` is a host array of n device pointers, out [n][GH][GW][3] with {GH, GW} from image_grid_shape
 int image_grid_shape(int images, int nrow, int padding, int H, int W, int32_t dims[2]);

@@ -753,6 +753,94 @@ def color_match_coef(sums_from, sums_to, n):
     return coef
 
 
+class TemporalState:
+    """The state of the temporal filter for H x W images: `temporal_filter_u8`'s (`fake` [H, W, 3] float32, the last frame's
+    unrounded filtered values; `real` [H, W, 3] uint8, its real bytes) and `color_coef_smooth`'s (`coef` [3, 2] float32,
+    `sums` [3] uint64), with `valid` int32 [2]: the filter's flag, then the smoothing's.  A new state is invalid, so the
+    first frame passes through; the buffers are uninitialised and are not read before they are written.  `reset()` makes
+    the next frame a first frame again (both flags, on the current stream)."""
+
+    def __init__(self, H, W, device="cuda"):
+        H, W = int(H), int(W)
+        if H <= 0 or W <= 0:
+            raise ValueError(f"TemporalState: non-positive size ({H} x {W})")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.D3FError("libd3f_hip ops need tensors on the HIP device (no CPU fallback)")
+        self.H, self.W = H, W
+        self.fake = torch.empty((H, W, 3), dtype=torch.float32, device=device)
+        self.real = torch.empty((H, W, 3), dtype=torch.uint8, device=device)
+        self.coef = torch.empty((3, 2), dtype=torch.float32, device=device)
+        self.sums = torch.empty((3,), dtype=torch.uint64, device=device)
+        self.valid = torch.zeros((2,), dtype=torch.int32, device=device)
+
+    def reset(self):
+        for k in range(2):
+            check(_lib.lib().d3f_temporal_flag_set(self.valid.data_ptr() + 4 * k, 0, stream_ptr()))
+        return self
+
+
+def _strength(strength, what):
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 <= strength < 1.0:
+        raise ValueError(f"{what}: the strength is a number in [0, 1), not {strength!r}")
+    return float(strength)
+
+
+def temporal_filter_u8(real, fake, state, strength=_lib.TEMPORAL_STRENGTH, threshold=_lib.TEMPORAL_THRESHOLD):
+    """The motion-gated recursive filter against flicker (include/d3f_hip.h: d3f_temporal_filter_u8): uint8 `fake` [H, W, 3]
+    / [B, H, W, 3] on the HIP device is filtered IN PLACE along time and returned; `real`, of the same shape, is the crop
+    the network saw, and the 3 x 3 sum of absolute differences of it against its predecessor gates the filter per pixel
+    (27 * threshold and above: the fake's byte passes bit for bit).  The frames of a call are consecutive in time and follow
+    the last frame of the previous call on the same `state` (a `TemporalState` of this H x W).  Both images: packed pixels at
+    any byte address, rows may be strided, frames H rows apart -- the halves of a [B, H, 2W, 3] pair buffer, for one."""
+    if (real.dtype != torch.uint8 or fake.dtype != torch.uint8 or real.shape[-1] != 3 or real.dim() not in (3, 4)
+            or tuple(real.shape) != tuple(fake.shape)):
+        raise ValueError("temporal_filter_u8 expects uint8 real and fake of one shape, [H, W, 3] or [B, H, W, 3]")
+    strength = _strength(strength, "temporal_filter_u8")
+    if isinstance(threshold, bool) or not isinstance(threshold, int) or not 1 <= threshold <= 255:
+        raise ValueError(f"temporal_filter_u8: the threshold is an integer in 1..255, not {threshold!r}")
+    single = real.dim() == 3
+    r, f = (real.unsqueeze(0), fake.unsqueeze(0)) if single else (real, fake)
+    B, H, W, _ = r.shape
+    for x in (r, f):
+        if x.stride(3) != 1 or x.stride(2) != 3 or x.stride(1) < 3 * W or (B > 1 and x.stride(0) != H * x.stride(1)):
+            raise ValueError("temporal_filter_u8 expects packed pixels and frames H rows apart")
+    if not isinstance(state, TemporalState) or (state.H, state.W) != (H, W):
+        raise ValueError(f"temporal_filter_u8: state must be a TemporalState of {H} x {W}")
+    dev = _dev(real)
+    if fake.device != dev or state.fake.device != dev:
+        raise ValueError("temporal_filter_u8 expects real, fake and state on one device")
+    if B > 0:
+        check(_lib.lib().d3f_temporal_filter_u8(ptr(r), r.stride(1), ptr(f), f.stride(1), B, H, W, ptr(state.fake),
+                                                ptr(state.real), ptr(state.valid), strength, threshold, stream_ptr()))
+    return fake
+
+
+def color_coef_smooth(coef, sums_to, n, state, strength=_lib.TEMPORAL_STRENGTH):
+    """`color_match_coef`'s float32 coefficients [B, 3, 2] (or [3, 2]) smoothed across frames IN PLACE and returned
+    (include/d3f_hip.h: d3f_color_coef_smooth): c = c' + strength * (c_prev - c'), the frames in order behind the last frame
+    of the previous call on `state` (a `TemporalState`).  sums_to: the real crop's `channel_sums_u8` over n pixels, of the
+    same shape in uint64 -- where any channel's sum moves by more than 16 * n against the predecessor's (a cut), and at a
+    first frame, the coefficients pass as they are."""
+    if (coef.dtype != torch.float32 or sums_to.dtype != torch.uint64 or tuple(coef.shape) != tuple(sums_to.shape)
+            or tuple(coef.shape[-2:]) != (3, 2) or coef.dim() not in (2, 3)):
+        raise ValueError("color_coef_smooth expects float32 coef and uint64 sums_to of one shape, [B, 3, 2] or [3, 2]")
+    strength = _strength(strength, "color_coef_smooth")
+    if not isinstance(state, TemporalState):
+        raise ValueError("color_coef_smooth: state must be a TemporalState")
+    if not coef.is_contiguous():
+        raise ValueError("color_coef_smooth works in place: coef must be contiguous")
+    dev = _dev(coef)
+    if sums_to.device != dev or state.coef.device != dev:
+        raise ValueError("color_coef_smooth expects coef, sums_to and state on one device")
+    t = sums_to.contiguous()
+    B = 1 if coef.dim() == 2 else coef.shape[0]
+    if B > 0:
+        check(_lib.lib().d3f_color_coef_smooth(ptr(coef), ptr(t), B, int(n), strength, ptr(state.coef), ptr(state.sums),
+                                               state.valid.data_ptr() + 4, stream_ptr()))
+    return coef
+
+
 def paste_resize_cubic_u8(patch, frames, box, feather=0, out=None, color=None):
     """The inverse of `crop_resize_cubic_u8` with a blend: uint8 `patch` [H, W, 3] / [B, H, W, 3] on the HIP device is resized
     to the box (x1, y1, cw, ch) of uint8 `frames` [h, w, 3] / [B, h, w, 3] with the same arithmetic and blended in over a

@@ -9,6 +9,7 @@ import datetime
 from contextlib import ExitStack, nullcontext
 from pathlib import Path
 
+from .._lib import TEMPORAL_STRENGTH, TEMPORAL_THRESHOLD, temporal_setting
 from ..train_deep_fake.lit_module import LitModule
 from .video_writer_context_manager import VideoWriter, batches, import_cv2, open_video_as_generator, video_fps
 
@@ -28,6 +29,8 @@ def main():
         feather=args.feather,
         antialias=args.antialias,
         color_match=args.color_match,
+        temporal=args.temporal,
+        temporal_threshold=args.temporal_threshold,
         )
 
 
@@ -58,7 +61,21 @@ def parse_command_line_arguments(argv=None):
                         help="--output full: match the fake's colour to the crop it replaces before the paste; meanstd: "
                              "mean and standard deviation per frame and channel (default: none)")
 
+    parser.add_argument("--temporal", type=float, nargs="?", const=TEMPORAL_STRENGTH, default=None, metavar="STRENGTH",
+                        help="filter the fake against flicker, in either output: where the crop stands still the fake is "
+                             "averaged over time with this strength in (0, 1), where it moves the network's bytes pass "
+                             f"(bare flag: {TEMPORAL_STRENGTH}; default: off)")
+    parser.add_argument("--temporal-threshold", type=int, default=None, metavar="N",
+                        help="--temporal: mean absolute change of the crop, in levels per sample over a pixel's 3 x 3 "
+                             f"surroundings, from which a pixel counts as moving (1..255, default {TEMPORAL_THRESHOLD})")
+
     args = parser.parse_args(argv)
+    if args.temporal_threshold is not None and args.temporal is None:
+        parser.error("--temporal-threshold needs --temporal")
+    try:
+        temporal_setting(args.temporal, args.temporal_threshold)
+    except ValueError as e:
+        parser.error(str(e))
     if args.color_match is not None and args.output != "full":
         parser.error("--color-match needs --output full: the real|fake pair is not pasted anywhere")
     return args
@@ -72,10 +89,13 @@ class RenderFakeVideo():
     source without frames leaves no output file (output="pair" knows its size up front and leaves an empty video).
     antialias=True: the crop is resized to the network's size with the antialiased bicubic filter, in either output.
     color_match="meanstd" (output="full" only): the fake's mean and standard deviation are matched to those of the crop it
-    replaces, per frame and channel, before the paste; None / "none": the fake is pasted as the network made it."""
+    replaces, per frame and channel, before the paste; None / "none": the fake is pasted as the network made it.
+    temporal=STRENGTH (either output; temporal_threshold=N with it): the fake is filtered against flicker along the video
+    (`Unet.predict_frames_u8`, temporal=); the model's filter state is reset once, before the first batch."""
 
     def __init__(self, video_path, checkpoint_path, model_a_or_b, image_width, image_height, batch_frames=1,
-                 frames=None, sink=None, model=None, output="pair", feather=None, antialias=False, color_match=None):
+                 frames=None, sink=None, model=None, output="pair", feather=None, antialias=False, color_match=None,
+                 temporal=None, temporal_threshold=None):
 
         self.video_path = Path(video_path)
         self.checkpoint_path = Path(checkpoint_path) if checkpoint_path is not None else None
@@ -95,6 +115,10 @@ class RenderFakeVideo():
         if color_match is not None and output != "full":
             raise ValueError("color_match needs output='full': the real|fake pair is not pasted anywhere")
         self.color_match = color_match
+        if temporal_threshold is not None and temporal is None:
+            raise ValueError("temporal_threshold needs temporal")
+        strength, threshold = temporal_setting(temporal, temporal_threshold)
+        self.temporal = None if temporal is None or strength == 0.0 else (strength, threshold)
         self.frames = frames
         self.sink = sink
 
@@ -102,6 +126,9 @@ class RenderFakeVideo():
             import_cv2()  # a video file is read or written: fail before the checkpoint is loaded
 
         self.model = model if model is not None else self.load_model_from_checkpoint()
+
+        if self.temporal is not None:
+            self.model.reset_frame_temporal(self.model_a_or_b)  # this video does not follow the last one
 
         if self.output == "full":
             self.render_full_video()
@@ -128,7 +155,8 @@ class RenderFakeVideo():
             write = self.sink if self.sink is not None else video_writer.write
             for batch, real_frames in batches(frames, self.batch_frames):
                 real_and_fake = self.model.predict_fake_frames(batch, self.model_a_or_b, self.image_width,
-                                                               self.image_height, antialias=self.antialias)
+                                                               self.image_height, antialias=self.antialias,
+                                                               temporal=self.temporal)
                 for frame in real_and_fake[:real_frames]:  # the padding of a short last batch is dropped
                     write(frame)
 
@@ -144,7 +172,8 @@ class RenderFakeVideo():
                                                             self.get_input_video_properties())).write
                 full = self.model.predict_fake_frames_full(batch, self.model_a_or_b, self.image_width,
                                                            self.image_height, feather=self.feather,
-                                                           antialias=self.antialias, color_match=self.color_match)
+                                                           antialias=self.antialias, color_match=self.color_match,
+                                                           temporal=self.temporal)
                 for frame in full[:real_frames]:  # the padding of a short last batch is dropped
                     write(frame)
 

@@ -449,13 +449,15 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
 
     # ---- raw frames to real|fake frames (script_tools/put_video_through_fake_model.py:111-119, 68) ----
     @torch.no_grad()
-    def predict_fake_frames(self, raw_bgr_batch, model_a_or_b, width, height, antialias=False):
+    def predict_fake_frames(self, raw_bgr_batch, model_a_or_b, width, height, antialias=False, temporal=None):
         """host frames [B, h, w, 3] (uint8 BGR, any size) -> host real|fake frames [B, height, 2 * width, 3]: centre crop,
         bicubic resize, `predict_fake` and the side-by-side concatenate of the reference's frame loop in one device call
         (`Unet.predict_frames_u8`).  Mean / std as in `predict_fake`: a model is fed the other domain's statistics.
         Pinned and device staging buffers are kept per shape, so a frame loop allocates nothing after its first batch.
         antialias=True: the antialiased bicubic resize (`ops.crop_resize_cubic_u8(..., antialias=True)`) -- prepare the
-        training images the same way."""
+        training images the same way.  temporal: None, a strength or (strength, threshold), as `Unet.predict_frames_u8`: the
+        fake half filtered against flicker; successive calls are then consecutive in time (`reset_frame_temporal` starts a
+        new sequence)."""
         p = self.hparams
         if model_a_or_b == "a":
             model, mean, std = self.model_a, p.mean_b, p.std_b
@@ -484,10 +486,17 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         host_in.copy_(torch.from_numpy(raw))
         dev_in.copy_(host_in, non_blocking=True)
         model.predict_frames_u8(dev_in, (height, width), mean, std, graph=bool(p.get("inference_graph", False)),
-                                out=dev_out, antialias=antialias)
+                                out=dev_out, antialias=antialias, temporal=temporal)
         host_out.copy_(dev_out, non_blocking=True)
         torch.cuda.current_stream().synchronize()
         return host_out.numpy().copy()
+
+    def reset_frame_temporal(self, model_a_or_b):
+        """the next frame of `predict_fake_frames` / `predict_fake_frames_full` with `temporal=` on this model is a first
+        frame again (`Unet.reset_frame_temporal`)"""
+        if model_a_or_b not in ("a", "b"):
+            raise ValueError("model_a_or_b is 'a' or 'b'")
+        (self.model_a if model_a_or_b == "a" else self.model_b).reset_frame_temporal()
 
     def _frame_path_inputs(self, raw_bgr_batch, model_a_or_b, who):
         """what a raw-frame entry needs before it touches the device: the model with the OTHER domain's mean / std (as
@@ -516,14 +525,15 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
 
     @torch.no_grad()
     def predict_fake_frames_full(self, raw_bgr_batch, model_a_or_b, width, height, feather=None, with_pair=False,
-                                 antialias=False, color_match=None):
+                                 antialias=False, color_match=None, temporal=None):
         """host frames [B, h, w, 3] (uint8 BGR, any size) -> host frames of the same shape with the centre-crop box replaced
         by the fake, resized back to the box and blended in over `feather` source pixels (None: `ops.default_feather`):
         the swapped video at the source's size, in one device call (`Unet.predict_frames_full_u8`).  with_pair: returns
         (full, pair), pair being what `predict_fake_frames` returns.  Models and statistics as `predict_fake_frames`;
         pinned and device staging is kept per shape in a cache of its own.  antialias: as `predict_fake_frames` (the
         crop-to-network resize only).  color_match: None / "none" / "meanstd", as `Unet.predict_frames_full_u8`: the fake's
-        colour statistics matched to the crop it replaces before the paste; the pair is the same either way."""
+        colour statistics matched to the crop it replaces before the paste; the pair is the same either way.  temporal: as
+        `predict_fake_frames`; the pair then holds the filtered fake, and with color_match the coefficients are smoothed."""
         model, mean, std, raw = self._frame_path_inputs(raw_bgr_batch, model_a_or_b, "predict_fake_frames_full")
         width, height = int(width), int(height)
         if not hasattr(self, "_frames_full_buffers"):
@@ -536,7 +546,8 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         dev_in.copy_(host_in, non_blocking=True)
         model.predict_frames_full_u8(dev_in, (height, width), mean, std, feather=feather,
                                      graph=bool(self.hparams.get("inference_graph", False)), out=dev_full,
-                                     pair_out=dev_pair, antialias=antialias, color_match=color_match)
+                                     pair_out=dev_pair, antialias=antialias, color_match=color_match,
+                                     temporal=temporal)
         host_full.copy_(dev_full, non_blocking=True)
         if with_pair:
             host_pair.copy_(dev_pair, non_blocking=True)

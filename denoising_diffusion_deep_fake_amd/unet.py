@@ -823,8 +823,25 @@ class Unet(nn.Module, _NetsRuntime):
         """the frame entries' resize mode on the engine's handle (d3f_unet_set_frame_resample)"""
         check(_lib.lib().d3f_unet_set_frame_resample(eng.h, _lib.RESAMPLE_CUBIC_AA if antialias else _lib.RESAMPLE_CUBIC))
 
+    @staticmethod
+    def _set_frame_temporal(eng, setting):
+        """the frame entries' temporal filter on the engine's handle (d3f_unet_set_frame_temporal); `setting` is what
+        `_lib.temporal_setting` returns.  The handle is told only when the setting changes: the same values keep its state"""
+        if getattr(eng, "temporal", (0.0, _lib.TEMPORAL_THRESHOLD)) != setting:  # (the handle starts switched off)
+            check(_lib.lib().d3f_unet_set_frame_temporal(eng.h, setting[0], setting[1]))
+            eng.temporal = setting
+
+    def reset_frame_temporal(self):
+        """forget the temporal filter's past on every plan of this network: the next frame of `predict_frames_u8` /
+        `predict_frames_full_u8` with `temporal=` is a first frame again (d3f_unet_frame_temporal_reset, on the current
+        stream; captured graphs stay)"""
+        for pool in self._rt.get("engines", {}).values():
+            for eng in pool:
+                if getattr(eng, "temporal", None) is not None:
+                    check(_lib.lib().d3f_unet_frame_temporal_reset(eng.h, stream_ptr()))
+
     @torch.no_grad()
-    def predict_frames_u8(self, raw_bgr, size, mean, std, graph=True, out=None, antialias=False):
+    def predict_frames_u8(self, raw_bgr, size, mean, std, graph=True, out=None, antialias=False, temporal=None):
         """The frame path of d3f/script_tools/put_video_through_fake_model.py:111-119, 68 on decoded frames of any
         size: uint8 BGR frames [h,w,3] or [B,h,w,3] on the HIP device -> centre crop to the aspect of size = (H, W)
         (`ops.center_crop_box`) -> bicubic resize (`ops.crop_resize_cubic_u8`) -> `predict_u8` -> the real|fake frames
@@ -832,8 +849,13 @@ class Unet(nn.Module, _NetsRuntime):
         `ops.crop_resize_cubic_u8`, the right half `predict_u8` of the left half at the same batch size.  `graph=True`
         replays a hipGraph captured per (input, output) buffer pair, raw frame size and crop box: pass the same buffers
         again (`out=`) in a frame loop.  antialias=True resizes as `ops.crop_resize_cubic_u8(..., antialias=True)` does
-        (the handle's D3F_RESAMPLE_CUBIC_AA mode); a change of it between calls re-captures the graph."""
+        (the handle's D3F_RESAMPLE_CUBIC_AA mode); a change of it between calls re-captures the graph.
+        temporal: None (off), a strength in (0, 1) or (strength, threshold): the fake half is filtered against flicker
+        (`ops.temporal_filter_u8` with real = the left half, fake = the right half; d3f_unet_set_frame_temporal).  The
+        frames of successive calls are then consecutive in time, the state lives with the plan of this batch size and
+        network size, `reset_frame_temporal()` starts a new sequence, and a change of the values starts one too."""
         from . import ops
+        temporal = _lib.temporal_setting(temporal)
         if raw_bgr.dtype != torch.uint8 or raw_bgr.shape[-1] != 3 or raw_bgr.dim() not in (3, 4):
             raise ValueError("predict_frames_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3] in BGR order")
         if raw_bgr.device.type != "cuda":
@@ -859,6 +881,7 @@ class Unet(nn.Module, _NetsRuntime):
         m = (C.c_float * 3)(*[float(v) for v in mean])
         sd = (C.c_float * 3)(*[float(v) for v in std])
         self._set_frame_resample(eng, antialias)
+        self._set_frame_temporal(eng, temporal)
         check(_lib.lib().d3f_unet_predict_frames_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), h, w, x1, y1, cw, ch,
                                                     ptr(out), m, sd, ptr(eng.workspace), 1 if graph else 0, stream_ptr()))
         eng.keep = (x, out)  # the captured graph bakes these pointers in: keep them alive with the engine
@@ -866,7 +889,7 @@ class Unet(nn.Module, _NetsRuntime):
 
     @torch.no_grad()
     def predict_frames_full_u8(self, raw_bgr, size, mean, std, feather=None, graph=True, out=None, pair_out=None,
-                               antialias=False, color_match=None):
+                               antialias=False, color_match=None, temporal=None):
         """`predict_frames_u8`, then the fake pasted back into the source frames: uint8 BGR frames [h,w,3] or [B,h,w,3] on
         the HIP device -> the frames at their own size with the centre-crop box replaced by the fake, resized back
         (`ops.paste_resize_cubic_u8`) and blended in over `feather` source pixels (None: `ops.default_feather` of the
@@ -877,9 +900,12 @@ class Unet(nn.Module, _NetsRuntime):
         color_match: None / "none", or "meanstd": the fake's mean and standard deviation are matched to the resized real
         crop's, per frame and channel, before the paste (`ops.channel_sums_u8` of both halves of the pair,
         `ops.color_match_coef`, `ops.paste_resize_cubic_u8(..., color=)`, still in the one C call; the handle's
-        D3F_COLOR_MEANSTD mode).  pair_out is not touched by it; a change between calls re-captures the graph."""
+        D3F_COLOR_MEANSTD mode).  pair_out is not touched by it; a change between calls re-captures the graph.
+        temporal: as `predict_frames_u8` -- the fake half of pair_out is filtered before the sums and the paste read it,
+        and with color_match="meanstd" the coefficients are smoothed across frames too (`ops.color_coef_smooth`)."""
         from . import ops
         color_mode = _lib.color_match_mode(color_match)
+        temporal = _lib.temporal_setting(temporal)
         if raw_bgr.dtype != torch.uint8 or raw_bgr.shape[-1] != 3 or raw_bgr.dim() not in (3, 4):
             raise ValueError("predict_frames_full_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3] in BGR order")
         if raw_bgr.device.type != "cuda":
@@ -922,6 +948,7 @@ class Unet(nn.Module, _NetsRuntime):
         if getattr(eng, "color_mode", _lib.COLOR_NONE) != color_mode:  # (the handle starts at D3F_COLOR_NONE)
             check(_lib.lib().d3f_unet_set_frame_color_match(eng.h, color_mode))
             eng.color_mode = color_mode
+        self._set_frame_temporal(eng, temporal)
         check(_lib.lib().d3f_unet_predict_frames_full_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), h, w, x1, y1, cw,
                                                          ch, feather, ptr(pair_out), ptr(full), m, sd, ptr(eng.workspace),
                                                          1 if graph else 0, stream_ptr()))

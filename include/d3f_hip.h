@@ -229,6 +229,27 @@ int d3f_unet_frame_resample(d3f_unet_t h); /* the mode, or < 0 for a null handle
 #define D3F_COLOR_MEANSTD 1
 int d3f_unet_set_frame_color_match(d3f_unet_t h, int mode);
 int d3f_unet_frame_color_match(d3f_unet_t h); /* the mode, or < 0 for a null handle */
+/* The temporal filter of the two frame entries (d3f_temporal_filter_u8, d3f_color_coef_smooth below).  strength == 0 is off and
+ * the default after d3f_unet_create: the launches, bytes and graphs are exactly those of a handle that never heard of the
+ * setting.  strength in (0, 1), threshold in 1..255:
+ *   - d3f_unet_predict_frames_u8 runs its launches, then d3f_temporal_filter_u8 on pair_out (real = the left half, fake = the
+ *     right half, both with row stride 6 * W, in place) and the flag launch: the right half of pair_out then holds the
+ *     FILTERED fake, bit for bit the operator's on the bytes the plain entry writes;
+ *   - d3f_unet_predict_frames_full_u8 does the same and pastes from the filtered half.  With D3F_COLOR_MEANSTD the order is
+ *     filter, sums over both halves (the filtered fake), coefficients, d3f_color_coef_smooth with to = the left half's sums
+ *     and n = H * W, the colour paste.
+ * Every call of either entry advances the handle's time by B frames: the frames of successive calls are consecutive.  The
+ * state of both operators lives in device memory of the handle at fixed addresses (a captured graph replays correctly):
+ * allocated at the first switch on, freed with the handle, nothing inside a frame call.  The smoothing's state advances only
+ * in calls that run it (the full-frame entry with D3F_COLOR_MEANSTD).  Setting the values the handle has changes nothing, not
+ * the state and not a captured graph; different values drop the two frame graphs and make the next frame a first frame (the
+ * reset is enqueued on that call's stream).  Strength bits and threshold are part of both graph keys.
+ * d3f_unet_frame_temporal reads the setting (either pointer may be null); d3f_unet_frame_temporal_reset makes the next frame
+ * a first frame by work on `stream`, without dropping graphs (a no-op while the mode has never been on).  Refused: a pair
+ * handle, strength outside [0, 1) or NaN, threshold outside 1..255. */
+int d3f_unet_set_frame_temporal(d3f_unet_t h, float strength, int threshold);
+int d3f_unet_frame_temporal(d3f_unet_t h, float* strength, int* threshold);
+int d3f_unet_frame_temporal_reset(d3f_unet_t h, void* stream);
 /* gradients of every parameter (written, not accumulated) for the preceding training forward.
  * The backward pass is cut into d3f_unet_num_segments() buckets so a data-parallel caller can
  * all-reduce bucket k while bucket k+1 computes: run segments [seg_begin, seg_end) in order 0..n;
@@ -573,6 +594,53 @@ int d3f_color_match_coef(const uint64_t* sums_from, const uint64_t* sums_to, int
 int d3f_paste_resize_cubic_color_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
                                     const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather,
                                     const float* coef, uint8_t* out, void* stream);
+
+/* Temporal filter against flicker in the fake video, in two operators.  The definitions are the acceptance contract;
+ * tests/temporal_restatement.py restates them in numpy float32 and int64, and every comparison is exact.  All fp32 arithmetic
+ * is single operations without contraction, integer-to-float conversions are exact, the division is the correctly rounded one.
+ * The defaults (D3F_TEMPORAL_STRENGTH, D3F_TEMPORAL_THRESHOLD, D3F_TEMPORAL_CUT_LEVELS) are design choices, not measurements.
+ *
+ * d3f_temporal_filter_u8: a motion-gated recursive filter on the fake.  real [B][H][W][3] uint8, rows real_row_stride_bytes
+ * apart, frames H rows apart, any byte address; fake the same with its own stride, filtered IN PLACE (6 * W and a fake 3 * W
+ * bytes behind real: the halves of a pair_out buffer).  State, in device memory: state_fake [H][W][3] fp32, state_real
+ * [H][W][3] uint8 packed, state_valid int32[1].  The frames of a call are consecutive in time: frame b's predecessor is frame
+ * b - 1, frame 0's is the state.  For frame b at pixel (i, j), with r the real frame, r_prev the predecessor's, f the fake's
+ * bytes and S_prev the predecessor's filtered value (fp32):
+ *   - sad = sum over dy, dx in {-1, 0, 1} and the 3 bytes of a pixel of |r[cy][cx][c] - r_prev[cy][cx][c]|, cy = clamp(i + dy,
+ *     0, H - 1), cx = clamp(j + dx, 0, W - 1): replicated border, always 27 terms, an exact integer in 0..6885;
+ *   - T = 27 * threshold, k = strength * ((float)max(T - sad, 0) / (float)T): one k per pixel for its three bytes;
+ *   - per byte d = S_prev - (float)f, p = k * d, S = (float)f + p; the byte written is rintf(S) clamped to 0..255, and S,
+ *     unrounded, is the successor's S_prev.  k == 0 (the surroundings moved) keeps the fake's byte bit for bit;
+ *   - with no valid predecessor (*state_valid == 0 and b == 0) S = (float)f, and neither state buffer is read: they may
+ *     hold anything, NaN included.
+ * The gate reads the REAL crop: the fake changing where its input did not is the flicker, the fake changing where the input
+ * moved is the signal.  A cut needs no detector: after one nearly every pixel has sad >= T and passes through.
+ * After a call state_fake holds the last frame's S, state_real its real bytes, and state_valid is 1 -- set by a small launch
+ * enqueued BEHIND the kernel on the stream, so a captured call replays correctly.  To reset, store 0 to state_valid on the
+ * same stream.  B == 0 touches nothing.  Refused before any device call: null pointers, B < 0 or B > 65535, sizes outside
+ * 1..16384, strength outside [0, 1) or NaN, threshold outside 1..255, a row stride below 3 * W, a state_fake or state_valid
+ * that is not 4-byte aligned, and any overlap between real, fake and the state buffers (real and fake may interleave row by
+ * row with one stride, as the halves of a pair buffer do). */
+#define D3F_TEMPORAL_STRENGTH 0.75f
+#define D3F_TEMPORAL_THRESHOLD 8
+#define D3F_TEMPORAL_CUT_LEVELS 16
+int d3f_temporal_filter_u8(const uint8_t* real, int64_t real_row_stride_bytes, uint8_t* fake, int64_t fake_row_stride_bytes,
+                           int B, int H, int W, float* state_fake, uint8_t* state_real, int32_t* state_valid, float strength,
+                           int threshold, void* stream);
+/* d3f_color_coef_smooth: d3f_color_match_coef's coefficients smoothed across frames, in place.  coef [B][3][2] fp32 (gain,
+ * offset); sums_to [B][3][2] uint64, the real crop's d3f_channel_sums_u8, of which only S = [..][0] is read; n pixels per frame.
+ * State: state_coef [3][2] fp32, state_sum [3] uint64, state_valid int32[1].  For the frames in order:
+ *   - cut = the predecessor is invalid, or for any channel |S[c] - S_prev[c]| > D3F_TEMPORAL_CUT_LEVELS * n in exact 64-bit
+ *     integers (the crop's mean moved by more than 16 levels);
+ *   - at a cut c = c' exactly and the state is not read; otherwise c = c' + strength * (c_prev - c'): difference, product
+ *     and sum rounded separately;
+ *   - coef[b] = c, and the state becomes (c, S).
+ * state_valid is set behind the launch, as above; B == 0 touches nothing.  Refused: null pointers, B < 0 or B > 65535,
+ * n <= 0 or n > 2^22, strength outside [0, 1) or NaN. */
+int d3f_color_coef_smooth(float* coef, const uint64_t* sums_to, int B, int64_t n, float strength, float* state_coef,
+                          uint64_t* state_sum, int32_t* state_valid, void* stream);
+/* *flag = value by a one-lane launch on the stream: the reset of either operator's state (value 0). */
+int d3f_temporal_flag_set(int32_t* flag, int value, void* stream);
 
 /* log_batch_as_image_grid of the three LitModules (d3f/train_deep_fake/lit_module.py:235-249,
  * d3f/train_denoiser/lit_module.py:157-171, d3f/balance_training_images/lit_module.py:197-211):

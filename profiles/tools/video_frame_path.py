@@ -24,10 +24,20 @@
                  same launches, and this library's in the same sequence of allocations and captures (the hipGraph figures
                  depend on that sequence: profiles/README.md "Colour match")
 
+  --temporal   : instead of the above, the temporal filter of the two frame entries: Unet.predict_frames_u8 and
+                 Unet.predict_frames_full_u8 with color_match="meanstd", each with temporal=None and temporal=0.75 (two
+                 networks, so that neither handle's setting ever changes inside a timed block), eager and hipGraph, next to
+                 the filter operator alone on the halves of the pair: 1080x1920 -> 448x448 and 256x256, B = 1 and B = 8; with
+                 the filter's byte bound (H * W * 3 bytes read twice and written once per frame, plus 15 bytes per pixel of
+                 state read and written once per call).  The same raw frames every call, so the gate is fully open (k = s
+                 everywhere): the kernel's work does not depend on the data.  With --off-only, or on a library without the
+                 entries (an older build named through D3F_LIB), only the temporal=None forms run: the parent's figures for
+                 the same launches, in the same sequence of allocations and captures
+
 Back-to-back enqueues on one stream, ITERS iterations after WARMUP, the forms alternating in ROUNDS rounds; the figure is
 the median round's time per call (and per frame).  Host work of the reference's loop (cv2.resize on one CPU thread, the
 concatenate, two PCIe trips) is not part of any figure here.  One JSON line at the end.
-    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N] [--antialias | --color [--off-only]]
+    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N] [--antialias | --color [--off-only] | --temporal [--off-only]]
 """
 import argparse
 import json
@@ -150,12 +160,70 @@ def color_section(args, g):
     print(json.dumps(result))
 
 
+def temporal_section(args, g):
+    """the temporal filter mode against the same calls without it, and the filter operator alone, per frame; one JSON line"""
+    has_temporal = hasattr(_lib.lib(), "d3f_unet_set_frame_temporal") and not args.off_only
+    result = {"precision": args.precision, "digest": _lib.built_digest(), "iters": args.iters, "rounds": args.rounds,
+              "has_temporal": has_temporal, "temporal_us_per_frame": {}}
+    torch.manual_seed(0)
+    net_off = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
+    net_on = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
+    for side in (448, 256):
+        size = (side, side)
+        for B in (1, 8):
+            # bytes the filter must move per frame: real read, fake read and written, and the state once per call
+            need = 3 * side * side * 3 + 2 * 15 * side * side // B
+            bound = need / 6.3e12 * 1e6  # at 6.3 TB/s achievable HBM
+            raw = torch.randint(0, 256, (B,) + RAW + (3,), generator=g, dtype=torch.uint8).cuda()
+            pair = net_off.predict_frames_u8(raw, size, MEAN, STD, graph=False).clone()
+            names = ("fe", "fg", "ue", "ug", "tfe", "tfg", "tue", "tug")
+            bufs = {k: (torch.empty_like(raw), torch.empty_like(pair)) for k in names}
+
+            def frames(net, key, graph, **kw):
+                return lambda: net.predict_frames_u8(raw, size, MEAN, STD, graph=graph, out=bufs[key][1], **kw)
+
+            def full(net, key, graph, **kw):
+                return lambda: net.predict_frames_full_u8(raw, size, MEAN, STD, graph=graph, out=bufs[key][0],
+                                                          pair_out=bufs[key][1], color_match="meanstd", **kw)
+            forms = {"frames_off_eager": frames(net_off, "fe", False), "frames_off_graph": frames(net_off, "fg", True),
+                     "full_off_eager": full(net_off, "ue", False), "full_off_graph": full(net_off, "ug", True)}
+            if has_temporal:
+                state = ops.TemporalState(side, side)
+                forms.update({
+                    "frames_on_eager": frames(net_on, "tfe", False, temporal=0.75),
+                    "frames_on_graph": frames(net_on, "tfg", True, temporal=0.75),
+                    "full_on_eager": full(net_on, "tue", False, temporal=0.75),
+                    "full_on_graph": full(net_on, "tug", True, temporal=0.75),
+                    "filter_op": lambda: ops.temporal_filter_u8(pair[:, :, :side], pair[:, :, side:], state),
+                })
+            t = compare(forms, args.warmup, args.iters, args.rounds)
+            key = f"{RAW[0]}x{RAW[1]}_to_{side}_B{B}"
+            row = {}
+            for name, (med, lo, hi) in t.items():
+                print(f"{key:24s} {name:18s} {med / B:9.2f} us per frame (min {lo / B:.2f}, max {hi / B:.2f})")
+                row[name] = [round(med / B, 2), round(lo / B, 2), round(hi / B, 2)]
+            if has_temporal:
+                for what in ("frames", "full"):
+                    for mode in ("eager", "graph"):
+                        row[f"{what}_added_{mode}"] = round((t[f"{what}_on_{mode}"][0] - t[f"{what}_off_{mode}"][0]) / B, 2)
+                row["filter_bytes"], row["filter_byte_bound_us"] = need, round(bound, 3)
+                row["filter_op_times_bound"] = round(t["filter_op"][0] / B / bound, 1)
+                print(f"{key:24s} the mode adds {row['frames_added_eager']:.2f} / {row['frames_added_graph']:.2f} us per frame to "
+                      f"predict_frames_u8 (eager / hipGraph), {row['full_added_eager']:.2f} / {row['full_added_graph']:.2f} to "
+                      f"predict_frames_full_u8 with colour match; the filter moves {need} bytes per frame, byte bound "
+                      f"{bound:.3f} us, the operator (kernel and state launch) at {row['filter_op_times_bound']:.1f} times it")
+            result["temporal_us_per_frame"][key] = row
+            del raw, bufs
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--antialias", action="store_true", help="measure the antialiased resize instead (see above)")
     ap.add_argument("--color", action="store_true", help="measure the colour match of the full-frame output instead (see above)")
+    ap.add_argument("--temporal", action="store_true", help="measure the temporal filter of the frame entries instead (see above)")
     ap.add_argument("--off-only", action="store_true",
-                    help="--color: only the color_match=None forms, as on a library without the colour entries -- the same "
+                    help="--color / --temporal: only the forms without the mode, as on a library without its entries -- the same "
                          "sequence of allocations and captures on both sides of an A/B of the unchanged path")
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--iters", type=int, default=100)
@@ -166,6 +234,8 @@ def main():
     print(f"{torch.cuda.get_device_name(0)}, torch {torch.__version__}, library digest {_lib.built_digest()}")
     if args.color:
         return color_section(args, torch.Generator().manual_seed(1))
+    if args.temporal:
+        return temporal_section(args, torch.Generator().manual_seed(1))
     torch.manual_seed(0)
     net = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
     g = torch.Generator().manual_seed(1)
