@@ -198,23 +198,25 @@ int d3f_unet_set_head_activation(d3f_unet_t h, int act) {
   return h->e.set_head_activation(act);
 }
 int d3f_unet_head_activation(d3f_unet_t h) { return h ? h->e.head_activation() : -1; }
+// the frame settings' entries: a non-null handle of a single network
+static int frame_handle(d3f_unet_t h, const char* fn) {
+  D3F_CHECK(h, "%s: null handle", fn);
+  return single_net(h, fn, "has no frame entries (run each network alone)");
+}
 int d3f_unet_set_frame_resample(d3f_unet_t h, int mode) {
-  D3F_CHECK(h, "unet_set_frame_resample: null handle");
-  if (int rc = single_net(h, "unet_set_frame_resample", "has no frame entries (run each network alone)")) return rc;
+  if (int rc = frame_handle(h, "unet_set_frame_resample")) return rc;
   return h->e.set_frame_resample(mode);
 }
 int d3f_unet_frame_resample(d3f_unet_t h) { return h ? h->e.frame_resample() : -1; }
 static_assert(D3F_COLOR_NONE == UnetEngine::FRAME_COLOR_NONE && D3F_COLOR_MEANSTD == UnetEngine::FRAME_COLOR_MEANSTD,
               "d3f_hip.h states the colour match modes");
 int d3f_unet_set_frame_color_match(d3f_unet_t h, int mode) {
-  D3F_CHECK(h, "unet_set_frame_color_match: null handle");
-  if (int rc = single_net(h, "unet_set_frame_color_match", "has no frame entries (run each network alone)")) return rc;
+  if (int rc = frame_handle(h, "unet_set_frame_color_match")) return rc;
   return h->e.set_frame_color_match(mode);
 }
 int d3f_unet_frame_color_match(d3f_unet_t h) { return h ? h->e.frame_color_match() : -1; }
 int d3f_unet_set_frame_temporal(d3f_unet_t h, float strength, int threshold) {
-  D3F_CHECK(h, "unet_set_frame_temporal: null handle");
-  if (int rc = single_net(h, "unet_set_frame_temporal", "has no frame entries (run each network alone)")) return rc;
+  if (int rc = frame_handle(h, "unet_set_frame_temporal")) return rc;
   return h->e.set_frame_temporal(strength, threshold);
 }
 int d3f_unet_frame_temporal(d3f_unet_t h, float* strength, int* threshold) {
@@ -224,8 +226,7 @@ int d3f_unet_frame_temporal(d3f_unet_t h, float* strength, int* threshold) {
   return 0;
 }
 int d3f_unet_frame_temporal_reset(d3f_unet_t h, void* stream) {
-  D3F_CHECK(h, "unet_frame_temporal_reset: null handle");
-  if (int rc = single_net(h, "unet_frame_temporal_reset", "has no frame entries (run each network alone)")) return rc;
+  if (int rc = frame_handle(h, "unet_frame_temporal_reset")) return rc;
   return h->e.frame_temporal_reset((hipStream_t)stream);
 }
 int d3f_unet_num_params(d3f_unet_t h) { return h ? (int)h->e.params.size() : -1; }
@@ -285,8 +286,8 @@ int d3f_unet_predict_frames_u8(d3f_unet_t h, const float* params, float* bnstats
                                const float std[3], void* workspace, int use_graph, void* stream) {
   D3F_CHECK(h && params && bnstats && raw_in && pair_out && mean && std && workspace, "predict_frames_u8: null argument");
   if (int rc = single_net(h, "predict_frames_u8", "has no eval-mode forward (run each network alone)")) return rc;
-  return h->e.predict_frames_u8(params, bnstats, raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, mean, std, workspace,
-                                use_graph, (hipStream_t)stream);
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, nullptr, 0};
+  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
 }
 
 int d3f_unet_predict_frames_full_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
@@ -296,8 +297,8 @@ int d3f_unet_predict_frames_full_u8(d3f_unet_t h, const float* params, float* bn
   D3F_CHECK(h && params && bnstats && raw_in && pair_out && full_out && mean && std && workspace,
             "predict_frames_full_u8: null argument");
   if (int rc = single_net(h, "predict_frames_full_u8", "has no eval-mode forward (run each network alone)")) return rc;
-  return h->e.predict_frames_full_u8(params, bnstats, raw_in, src_h, src_w, x1, y1, cw, ch, feather, pair_out, full_out,
-                                     mean, std, workspace, use_graph, (hipStream_t)stream);
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, full_out, feather};
+  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
 }
 
 int d3f_unet_num_segments(d3f_unet_t h) { return h ? h->e.num_segments : -1; }

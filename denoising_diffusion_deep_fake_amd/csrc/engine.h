@@ -108,19 +108,24 @@ class UnetEngine {
   // use_graph: the launch sequence is captured once per set of pointers into a hipGraph and replayed
   int predict_u8(const float* params, float* bnstats, const uint8_t* bgr_in, uint8_t* bgr_out,
                  const float mean[3], const float stdv[3], void* ws, int use_graph, hipStream_t s) const;
-  // the frame loop of d3f/script_tools/put_video_through_fake_model.py:111-119, 64-68 on raw frames: crop box
-  // (x1, y1, cw, ch) of uint8 BGR frames [B][src_h][src_w][3] -> bicubic resize to the plan's H x W (resize.hip), written
-  // both as the left half of pair_out [B][H][2W][3] and, normalised, as the network input -> eval-mode forward -> the
-  // fake frame into the right half.  use_graph: captured once per set of pointers, frame size and crop box
-  int predict_frames_u8(const float* params, float* bnstats, const uint8_t* raw_in, int src_h, int src_w, int x1, int y1,
-                        int cw, int ch, uint8_t* pair_out, const float mean[3], const float stdv[3], void* ws,
-                        int use_graph, hipStream_t s) const;
-  // predict_frames_u8 into pair_out, then ONE more launch (paste_resize_cubic, resize.hip): the fake half of pair_out resized
-  // back to the crop box and blended into raw_in over `feather` pixels -> full_out [B][src_h][src_w][3].  full_out == raw_in
-  // pastes in place, eager only: a replay would read frames it has overwritten.  A graph slot of its own.
-  int predict_frames_full_u8(const float* params, float* bnstats, const uint8_t* raw_in, int src_h, int src_w, int x1,
-                             int y1, int cw, int ch, int feather, uint8_t* pair_out, uint8_t* full_out, const float mean[3],
-                             const float stdv[3], void* ws, int use_graph, hipStream_t s) const;
+  // One call of the frame path: the frame loop of d3f/script_tools/put_video_through_fake_model.py:111-119, 64-68 on raw
+  // frames.  Crop box (x1, y1, cw, ch) of uint8 BGR frames [B][src_h][src_w][3] -> resize to the plan's H x W (resize.hip;
+  // set_frame_resample), written both as the left half of pair_out [B][H][2W][3] and, normalised, as the network input ->
+  // eval-mode forward -> the fake frame into the right half -> [temporal filter on the two halves (set_frame_temporal)].
+  // full_out null is d3f_unet_predict_frames_u8 and ends there.  Otherwise (d3f_unet_predict_frames_full_u8) the fake half
+  // is resized back to the box and blended into raw_in over `feather` pixels -> full_out [B][src_h][src_w][3]: one paste
+  // launch, or with set_frame_color_match sums -> coefficients -> [their smoothing] -> the paste in its colour form.
+  // full_out == raw_in pastes in place, eager only: a replay would read frames it has overwritten.
+  struct FrameCall {
+    const uint8_t* raw_in;
+    int src_h, src_w, x1, y1, cw, ch;
+    uint8_t* pair_out;
+    uint8_t* full_out;  // null: the pair entry, which ignores feather and the colour mode
+    int feather;
+  };
+  // use_graph: captured once per set of pointers, constants, frame size, crop box and settings; a slot per entry
+  int predict_frames(const FrameCall& c, const float* params, float* bnstats, const float mean[3], const float stdv[3],
+                     void* ws, int use_graph, hipStream_t s) const;
   // eval-mode forward (f32 NCHW in / out) replayed from a hipGraph captured once per set of pointers -- the
   // "hipGraph-captured denoise step" of BASELINE.json configs[4]; bit-identical to forward(training = 0)
   int forward_graph(const float* params, float* bnstats, const float* x, float* out, void* ws, hipStream_t s) const;
@@ -151,30 +156,27 @@ class UnetEngine {
   // A pair's two networks share the setting.  A change drops the captured graphs, as a pointer change does.
   int set_head_activation(int act);
   int head_activation() const { return head_act_; }
-  // How predict_frames_u8 / predict_frames_full_u8 resize the crop to the network's size (D3F_RESAMPLE_*): the plain
-  // bicubic (the default: exactly the launches of an engine without the setting) or the antialiased one
-  // (crop_resize_cubic_aa, resize.hip).  The paste is not touched.  A change drops the two captured frame graphs.
+  // The three settings of predict_frames.  Each default gives exactly the launches of an engine without the setting; a
+  // change drops the two captured frame graphs; device memory a setting needs is the engine's own, allocated at its first
+  // switch away from the default and freed with the engine.
+  // How the crop is resized to the network's size (D3F_RESAMPLE_*): the plain bicubic or the antialiased one
+  // (crop_resize_cubic_aa, resize.hip).  The paste is not touched.
   enum { FRAME_RESAMPLE_CUBIC = 0, FRAME_RESAMPLE_CUBIC_AA = 1 };
   int set_frame_resample(int mode);
-  int frame_resample() const { return frame_resample_; }
-  // Whether predict_frames_full_u8 matches the fake's colour to the resized real crop before the paste (D3F_COLOR_*).  NONE
-  // (the default): exactly the launches of an engine without the setting.  MEANSTD: behind the launches into pair_out, the
+  int frame_resample() const { return frame_.resample; }
+  // Whether the full entry matches the fake's colour to the resized real crop before the paste (D3F_COLOR_*).  MEANSTD: the
   // sums of both halves of pair_out in one launch (color.hip: a partial row per workgroup), the rows' fixed-order sum and
-  // the coefficients in a second one, and the paste in its colour form.  The partial sums and the coefficients are the
-  // engine's own device memory, allocated at the first switch away from NONE and freed with the engine.  A change drops the
-  // two captured frame graphs; H * W above COLOR_MAX_PIXELS is refused here.
+  // the coefficients in a second one, and the paste in its colour form.  H * W above COLOR_MAX_PIXELS is refused here.
   enum { FRAME_COLOR_NONE = 0, FRAME_COLOR_MEANSTD = 1 };
   int set_frame_color_match(int mode);
-  int frame_color_match() const { return frame_color_; }
-  // The temporal filter of the two frame entries (include/d3f_hip.h: d3f_unet_set_frame_temporal).  strength 0 (the default)
-  // is off: exactly the launches of an engine without the setting.  On: behind the launches into pair_out, the filter launch
-  // on its two halves and the state-and-flag launch; in predict_frames_full_u8 with MEANSTD the coefficients' smoothing behind the
-  // coefficient launch.  The state of both is the engine's own device memory, allocated at the first switch on and freed
-  // with the engine.  A change of either value drops the two captured frame graphs and makes the next frame a first frame:
-  // the setter has no stream, so the reset is enqueued by the next frame call, on its stream, in front of its launches.
+  int frame_color_match() const { return frame_.color; }
+  // The temporal filter (include/d3f_hip.h: d3f_unet_set_frame_temporal); strength 0 is off.  On: the filter launch on the
+  // two halves of pair_out with its state-and-flag launch, and with MEANSTD the coefficients' smoothing.  A change of either
+  // value also makes the next frame a first frame: the setter has no stream, so the reset is enqueued by the next frame
+  // call, on its stream, in front of its launches.
   int set_frame_temporal(float strength, int threshold);
-  float frame_temporal_strength() const { return temporal_strength_; }
-  int frame_temporal_threshold() const { return temporal_threshold_; }
+  float frame_temporal_strength() const { return frame_.strength; }
+  int frame_temporal_threshold() const { return frame_.threshold; }
   int frame_temporal_reset(hipStream_t s) const;
   int export_tensor(const char* name, const void* ws, float* out_nchw, hipStream_t s) const;
   int export_shape(const char* name, int32_t dims[3]) const;
@@ -236,16 +238,14 @@ class UnetEngine {
   int head_to_u8bgr(const char* ws, uint8_t* out, long out_row_stride, const float mean255[3], const float std255[3],
                     hipStream_t s) const;
   void drop_graphs() const;
+  void drop_frame_graphs() const;  // the two slots of predict_frames: they bake its settings' launches in
   // what a launch of this engine hands to the kernels: null for a single network
   bool make_split(const NetIO* io, long in_delta, NetSplit* ns) const;
   int predict_u8_launches(const float* params, float* bnstats, const uint8_t* bgr_in, uint8_t* bgr_out,
                           const float mean255[3], const float std255[3], char* ws, hipStream_t s) const;
-  int predict_frames_u8_launches(const float* params, float* bnstats, const uint8_t* raw_in, const int geo[6],
-                                 uint8_t* pair_out, const float mean255[3], const float std255[3], char* ws,
-                                 hipStream_t s) const;
   // captured graphs: one slot per entry point; a slot is re-captured when what it baked in changes -- the pointers, the
-  // constants and (predict_frames_u8, predict_frames_full_u8) the raw frame size and crop box, the latter's full_out, feather
-  // and colour match mode, and both frame entries' temporal filter setting (strength bits, threshold)
+  // constants and (predict_frames) the raw frame size and crop box, the full entry's full_out, feather and colour match
+  // mode, and the temporal filter setting (strength bits, threshold)
   struct GraphKey {
     const void* ptr[6];
     float cst[6];
@@ -254,6 +254,7 @@ class UnetEngine {
   struct GraphSlot {
     hipGraphExec_t exec = nullptr;
     GraphKey key = {};
+    void destroy();
   };
   template <typename F>
   int graph_replay(GraphSlot& slot, const GraphKey& key, hipStream_t s, F&& launches) const;
@@ -268,29 +269,40 @@ class UnetEngine {
   mutable const void* g_step_ws_ = nullptr;
   mutable hipEvent_t ev_gin_ = nullptr, ev_gout_ = nullptr;
   int head_act_ = 0;          // HEAD_ACT_IDENTITY
-  int frame_resample_ = FRAME_RESAMPLE_CUBIC;
-  int frame_color_ = FRAME_COLOR_NONE;
-  // partial sums of a call, [2][B][parts][3][2] (the real half's, then the fake's; parts <= COLOR_SUMS_MAX_PARTS comes from
-  // the sums launch, and the buffer has room for the most)
-  uint64_t* color_slabs_ = nullptr;
-  float* color_coef_ = nullptr;      // [B][3][2]
-  float temporal_strength_ = 0.f;    // 0: off
-  int temporal_threshold_ = 8;       // D3F_TEMPORAL_THRESHOLD
-  // the filter's state (state_fake [H][W][3] fp32, state_real [H][W][3] bytes), the smoothing's (state_coef [3][2] fp32,
-  // state_sum [3] uint64) and the two valid flags (the filter's, then the smoothing's)
-  float* temporal_fake_ = nullptr;
-  uint8_t* temporal_real_ = nullptr;
-  float* temporal_coef_ = nullptr;
-  uint64_t* temporal_sum_ = nullptr;
-  int* temporal_valid_ = nullptr;
-  mutable bool temporal_reset_pending_ = false;  // a changed setting: the next frame call zeroes the flags on its stream
-  int temporal_key() const;  // the strength's bits, for the graph keys
-  // the filter's launches on the halves of pair_out, behind predict_frames_u8_launches
-  int temporal_filter_launches(uint8_t* pair_out, hipStream_t s) const;
-  // in front of a frame call's launches and outside its graph: the pending reset, on the caller's stream
-  int temporal_begin(hipStream_t s) const;
-  // the host-side argument check of the frame entries' resize, in the mode that is set
-  int frame_resize_check(int src_h, int src_w, int x1, int y1, int cw, int ch) const;
+  // device memory of a frame setting: allocated once, when the setting first needs it, and freed with the engine
+  template <typename T>
+  struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    // (a setter that got one buffer and failed on the next leaves a state its next call completes)
+    hipError_t ensure(size_t bytes) { return p ? hipSuccess : hipMalloc(reinterpret_cast<void**>(&p), bytes); }
+  };
+  // what predict_frames takes from the handle: the settings and their device memory
+  struct FrameOptions {
+    int resample = FRAME_RESAMPLE_CUBIC;
+    int color = FRAME_COLOR_NONE;
+    float strength = 0.f;  // of the temporal filter; 0: off
+    int threshold = 8;     // D3F_TEMPORAL_THRESHOLD
+    mutable bool reset_pending = false;  // a changed temporal setting: the next (const) frame call zeroes the flags on its stream
+    // colour match: the partial sums of a call, [2][B][parts][3][2] (the real half's, then the fake's; parts <=
+    // COLOR_SUMS_MAX_PARTS comes from the sums launch, and the buffer has room for the most), and the coefficients [B][3][2]
+    DevBuf<uint64_t> color_slabs;
+    DevBuf<float> color_coef;
+    // temporal: the filter's state (fake [H][W][3] fp32, real [H][W][3] bytes), the smoothing's (coef [3][2] fp32, sum [3]
+    // uint64) and the two valid flags (the filter's, then the smoothing's)
+    DevBuf<float> state_fake;
+    DevBuf<uint8_t> state_real;
+    DevBuf<float> state_coef;
+    DevBuf<uint64_t> state_sum;
+    DevBuf<int> valid;
+  };
+  FrameOptions frame_;
+  // the pair buffer [B][H][2W][3]: where the fake half starts in a row, and the bytes from row to row
+  long pair_fake_off() const { return 3L * W; }
+  long pair_stride() const { return 2 * pair_fake_off(); }
   // NCHW fp32 head output: predict_u8's, and z of an activated head, which the head of the backward pass turns into dz IN
   // PLACE (the bias gradient's channel sum reads that): the workspace is the one of a plan without activations
   size_t head_nchw_off = 0;

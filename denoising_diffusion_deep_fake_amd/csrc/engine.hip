@@ -698,13 +698,9 @@ int UnetEngine::set_head_activation(int act) {
 int UnetEngine::set_frame_resample(int mode) {
   D3F_CHECK(mode == FRAME_RESAMPLE_CUBIC || mode == FRAME_RESAMPLE_CUBIC_AA,
             "frame resample: unknown mode %d (D3F_RESAMPLE_CUBIC, D3F_RESAMPLE_CUBIC_AA)", mode);
-  if (mode != frame_resample_) {
-    for (GraphSlot* slot : {&g_frames_, &g_frames_full_})  // they bake the resize launch in
-      if (slot->exec) {
-        (void)hipGraphExecDestroy(slot->exec);
-        slot->exec = nullptr;
-      }
-    frame_resample_ = mode;
+  if (mode != frame_.resample) {
+    drop_frame_graphs();
+    frame_.resample = mode;
   }
   return 0;
 }
@@ -712,22 +708,15 @@ int UnetEngine::set_frame_resample(int mode) {
 int UnetEngine::set_frame_color_match(int mode) {
   D3F_CHECK(mode == FRAME_COLOR_NONE || mode == FRAME_COLOR_MEANSTD,
             "frame colour match: unknown mode %d (D3F_COLOR_NONE, D3F_COLOR_MEANSTD)", mode);
-  if (mode == frame_color_) return 0;
+  if (mode == frame_.color) return 0;
   if (mode != FRAME_COLOR_NONE) {
-    if (int rc = channel_sums_check(B, H, W, 6L * W)) return rc;  // H * W above 2^22
-    // (each on its own: a call that got the first and failed on the second leaves a state the next call completes)
-    if (color_slabs_ == nullptr)
-      D3F_HIP(hipMalloc(reinterpret_cast<void**>(&color_slabs_),
-                        2 * (size_t)(B > 0 ? B : 1) * COLOR_SUMS_MAX_PARTS * 6 * sizeof(uint64_t)));
-    if (color_coef_ == nullptr)
-      D3F_HIP(hipMalloc(reinterpret_cast<void**>(&color_coef_), (size_t)(B > 0 ? B : 1) * 6 * sizeof(float)));
+    if (int rc = channel_sums_check(B, H, W, pair_stride())) return rc;  // H * W above 2^22
+    const size_t frames = B > 0 ? B : 1;
+    D3F_HIP(frame_.color_slabs.ensure(2 * frames * COLOR_SUMS_MAX_PARTS * 6 * sizeof(uint64_t)));
+    D3F_HIP(frame_.color_coef.ensure(frames * 6 * sizeof(float)));
   }
-  for (GraphSlot* slot : {&g_frames_, &g_frames_full_})
-    if (slot->exec) {
-      (void)hipGraphExecDestroy(slot->exec);
-      slot->exec = nullptr;
-    }
-  frame_color_ = mode;
+  drop_frame_graphs();
+  frame_.color = mode;
   return 0;
 }
 
@@ -736,190 +725,152 @@ int UnetEngine::set_frame_temporal(float strength, int threshold) {
             (double)strength);  // (NaN fails)
   D3F_CHECK(threshold >= 1 && threshold <= 255, "frame temporal filter: threshold %d outside 1..255", threshold);
   if (strength == 0.f) strength = 0.f;  // (-0 is off as well, with the bits of 0)
-  if (memcmp(&strength, &temporal_strength_, sizeof(float)) == 0 && threshold == temporal_threshold_) return 0;
+  if (memcmp(&strength, &frame_.strength, sizeof(float)) == 0 && threshold == frame_.threshold) return 0;
   if (strength != 0.f) {
     const size_t px = (size_t)H * W;
-    // (each on its own: a call that failed half way leaves a state the next call completes)
-    if (temporal_fake_ == nullptr) D3F_HIP(hipMalloc(reinterpret_cast<void**>(&temporal_fake_), px * 3 * sizeof(float)));
-    if (temporal_real_ == nullptr) D3F_HIP(hipMalloc(reinterpret_cast<void**>(&temporal_real_), px * 3));
-    if (temporal_coef_ == nullptr) D3F_HIP(hipMalloc(reinterpret_cast<void**>(&temporal_coef_), 6 * sizeof(float)));
-    if (temporal_sum_ == nullptr) D3F_HIP(hipMalloc(reinterpret_cast<void**>(&temporal_sum_), 3 * sizeof(uint64_t)));
-    if (temporal_valid_ == nullptr) D3F_HIP(hipMalloc(reinterpret_cast<void**>(&temporal_valid_), 2 * sizeof(int)));
+    D3F_HIP(frame_.state_fake.ensure(px * 3 * sizeof(float)));
+    D3F_HIP(frame_.state_real.ensure(px * 3));
+    D3F_HIP(frame_.state_coef.ensure(6 * sizeof(float)));
+    D3F_HIP(frame_.state_sum.ensure(3 * sizeof(uint64_t)));
+    D3F_HIP(frame_.valid.ensure(2 * sizeof(int)));
   }
-  for (GraphSlot* slot : {&g_frames_, &g_frames_full_})
-    if (slot->exec) {
-      (void)hipGraphExecDestroy(slot->exec);
-      slot->exec = nullptr;
-    }
-  temporal_strength_ = strength;
-  temporal_threshold_ = threshold;
-  temporal_reset_pending_ = true;
+  drop_frame_graphs();
+  frame_.strength = strength;
+  frame_.threshold = threshold;
+  frame_.reset_pending = true;
   return 0;
 }
 
-int UnetEngine::temporal_key() const {
-  int bits;
-  memcpy(&bits, &temporal_strength_, sizeof(bits));
-  return bits;
-}
-
 int UnetEngine::frame_temporal_reset(hipStream_t s) const {
-  temporal_reset_pending_ = false;
-  if (temporal_valid_ == nullptr) return 0;  // never on: nothing to forget
-  if (int rc = temporal_flag_set_launch(temporal_valid_, 0, s)) return rc;
-  return temporal_flag_set_launch(temporal_valid_ + 1, 0, s);
+  frame_.reset_pending = false;
+  int* valid = frame_.valid.p;
+  if (valid == nullptr) return 0;  // never on: nothing to forget
+  if (int rc = temporal_flag_set_launch(valid, 0, s)) return rc;
+  return temporal_flag_set_launch(valid + 1, 0, s);
 }
 
-int UnetEngine::temporal_begin(hipStream_t s) const {
-  if (!temporal_reset_pending_) return 0;
-  return frame_temporal_reset(s);
+void UnetEngine::GraphSlot::destroy() {
+  if (exec) (void)hipGraphExecDestroy(exec);
+  exec = nullptr;
 }
 
-int UnetEngine::temporal_filter_launches(uint8_t* pair_out, hipStream_t s) const {
-  return temporal_filter_u8_launch(pair_out, pair_out + 3L * W, B, H, W, 6L * W, 6L * W, temporal_fake_, temporal_real_,
-                                   temporal_valid_, temporal_strength_, temporal_threshold_, s);
-}
-
-int UnetEngine::frame_resize_check(int src_h, int src_w, int x1, int y1, int cw, int ch) const {
-  if (frame_resample_ == FRAME_RESAMPLE_CUBIC_AA)
-    return crop_resize_cubic_aa_check(B, src_h, src_w, x1, y1, cw, ch, H, W, 6L * W);
-  return crop_resize_cubic_check(B, src_h, src_w, x1, y1, cw, ch, H, W, 6L * W);
+void UnetEngine::drop_frame_graphs() const {
+  g_frames_.destroy();
+  g_frames_full_.destroy();
 }
 
 void UnetEngine::drop_graphs() const {
-  for (GraphSlot* slot : {&g_predict_, &g_eval_, &g_frames_, &g_frames_full_})
-    if (slot->exec) {
-      (void)hipGraphExecDestroy(slot->exec);
-      slot->exec = nullptr;
-    }
+  g_predict_.destroy();
+  g_eval_.destroy();
+  drop_frame_graphs();
   if (g_step_) {
     (void)hipGraphExecDestroy(g_step_);
     g_step_ = nullptr;
   }
 }
 
+// the uint8 entries' mean * 255 and std * 255: fp32 products, as torch.tensor(mean) * 255 gives
+struct Scale255 {
+  float mean[3], stdv[3];
+  Scale255(const float m[3], const float sd[3]) {
+    for (int c = 0; c < 3; ++c) {
+      mean[c] = m[c] * 255.0f;
+      stdv[c] = sd[c] * 255.0f;
+    }
+  }
+};
+
 int UnetEngine::predict_u8(const float* params_, float* bnstats, const uint8_t* bgr_in, uint8_t* bgr_out,
                            const float mean[3], const float stdv[3], void* ws_, int use_graph,
                            hipStream_t s) const {
   D3F_CHECK(in_channels == 3 && classes == 3, "predict_u8: 3-channel frames only (in %d, out %d)", in_channels, classes);
   char* ws = reinterpret_cast<char*>(ws_);
-  float m255[3], s255[3];
-  for (int c = 0; c < 3; ++c) {  // fp32 products, as torch.tensor(mean) * 255 gives
-    m255[c] = mean[c] * 255.0f;
-    s255[c] = stdv[c] * 255.0f;
-  }
-  if (!use_graph) return predict_u8_launches(params_, bnstats, bgr_in, bgr_out, m255, s255, ws, s);
+  const Scale255 k(mean, stdv);
+  if (!use_graph) return predict_u8_launches(params_, bnstats, bgr_in, bgr_out, k.mean, k.stdv, ws, s);
   // hipGraph path: at B = 1 the ~100 launches of an eval forward are launch-bound; capture them once
-  const GraphKey key = {{params_, bnstats, bgr_in, bgr_out, ws_}, {m255[0], m255[1], m255[2], s255[0], s255[1], s255[2]}, {}};
+  const GraphKey key = {{params_, bnstats, bgr_in, bgr_out, ws_},
+                        {k.mean[0], k.mean[1], k.mean[2], k.stdv[0], k.stdv[1], k.stdv[2]}, {}};
   return graph_replay(g_predict_, key, s, [&](hipStream_t gs) {
-    return predict_u8_launches(params_, bnstats, bgr_in, bgr_out, m255, s255, ws, gs);
+    return predict_u8_launches(params_, bnstats, bgr_in, bgr_out, k.mean, k.stdv, ws, gs);
   });
 }
 
-int UnetEngine::predict_frames_u8_launches(const float* params_, float* bnstats, const uint8_t* raw_in, const int geo[6],
-                                           uint8_t* pair_out, const float mean255[3], const float std255[3], char* ws,
-                                           hipStream_t s) const {
-  // one launch writes the real half of the pair and, from the same rounded bytes, the network input
-  const auto resize = frame_resample_ == FRAME_RESAMPLE_CUBIC_AA ? crop_resize_cubic_aa_u8_nhwc_launch
-                                                                 : crop_resize_cubic_u8_nhwc_launch;
-  if (int rc = resize(dtype, raw_in, B, geo[0], geo[1], geo[2], geo[3], geo[4], geo[5], pair_out, H, W, 6L * W,
-                      ws + tensors[t_x].off, tensors[t_x].C, mean255, std255, s))
-    return rc;
-  float* head_out = reinterpret_cast<float*>(ws + head_nchw_off);
-  if (int rc = forward_body(params_, bnstats, head_out, ws, 0, s, nullptr, false)) return rc;
-  head_z_live_ = false;
-  return head_to_u8bgr(ws, pair_out + 3L * W, 6L * W, mean255, std255, s);
-}
-
-int UnetEngine::predict_frames_u8(const float* params_, float* bnstats, const uint8_t* raw_in, int src_h, int src_w, int x1,
-                                  int y1, int cw, int ch, uint8_t* pair_out, const float mean[3], const float stdv[3],
-                                  void* ws_, int use_graph, hipStream_t s) const {
-  D3F_CHECK(in_channels == 3 && classes == 3, "predict_frames_u8: 3-channel frames only (in %d, out %d)", in_channels,
-            classes);
+int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* bnstats, const float mean[3],
+                               const float stdv[3], void* ws_, int use_graph, hipStream_t s) const {
+  const bool full = c.full_out != nullptr;
+  D3F_CHECK(in_channels == 3 && classes == 3, "%s: 3-channel frames only (in %d, out %d)",
+            full ? "predict_frames_full_u8" : "predict_frames_u8", in_channels, classes);
   char* ws = reinterpret_cast<char*>(ws_);
-  float m255[3], s255[3];
-  for (int c = 0; c < 3; ++c) {  // as predict_u8
-    m255[c] = mean[c] * 255.0f;
-    s255[c] = stdv[c] * 255.0f;
-  }
-  if (int rc = frame_resize_check(src_h, src_w, x1, y1, cw, ch)) return rc;
-  const int geo[6] = {src_h, src_w, x1, y1, cw, ch};
-  const bool temporal = temporal_strength_ != 0.f;
-  if (temporal) {
-    if (int rc = temporal_filter_check(pair_out, pair_out + 3L * W, B, H, W, 6L * W, 6L * W, temporal_fake_, temporal_real_,
-                                       temporal_valid_, temporal_strength_, temporal_threshold_))
+  const Scale255 k(mean, stdv);
+  const FrameOptions& o = frame_;
+  const bool aa = o.resample == FRAME_RESAMPLE_CUBIC_AA;
+  const bool color = full && o.color == FRAME_COLOR_MEANSTD;  // (the pair entry has no paste to colour)
+  const bool temporal = o.strength != 0.f;
+  uint8_t* const pair = c.pair_out;
+  uint8_t* const fake = pair + pair_fake_off();
+  const long stride = pair_stride();
+  if (int rc = (aa ? crop_resize_cubic_aa_check : crop_resize_cubic_check)(B, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, H, W,
+                                                                           stride))
+    return rc;
+  if (full) {
+    if (int rc = color ? paste_resize_cubic_color_check(fake, c.raw_in, c.full_out, o.color_coef.p, B, H, W, stride, c.src_h,
+                                                        c.src_w, c.x1, c.y1, c.cw, c.ch, c.feather)
+                       : paste_resize_cubic_check(fake, c.raw_in, c.full_out, B, H, W, stride, c.src_h, c.src_w, c.x1, c.y1,
+                                                  c.cw, c.ch, c.feather))
       return rc;
-    if (int rc = temporal_begin(s)) return rc;
+    D3F_CHECK(!(use_graph && c.full_out == c.raw_in),
+              "predict_frames_full_u8: full_out == raw_in (in place) cannot be replayed from a graph: pass use_graph = 0");
+  }
+  if (temporal) {
+    if (int rc = temporal_filter_check(pair, fake, B, H, W, stride, stride, o.state_fake.p, o.state_real.p, o.valid.p,
+                                       o.strength, o.threshold))
+      return rc;
+    // a changed setting's reset: in front of the launches and outside their graph, on the caller's stream
+    if (o.reset_pending)
+      if (int rc = frame_temporal_reset(s)) return rc;
   }
   auto launches = [&](hipStream_t ls) {
-    if (int rc = predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, ls)) return rc;
-    return temporal ? temporal_filter_launches(pair_out, ls) : 0;
-  };
-  if (!use_graph) return launches(s);
-  const GraphKey key = {{params_, bnstats, raw_in, pair_out, ws_},
-                        {m255[0], m255[1], m255[2], s255[0], s255[1], s255[2]},
-                        {src_h, src_w, x1, y1, cw, ch, 0, 0, temporal_key(), temporal ? temporal_threshold_ : 0}};
-  return graph_replay(g_frames_, key, s, launches);
-}
-
-int UnetEngine::predict_frames_full_u8(const float* params_, float* bnstats, const uint8_t* raw_in, int src_h, int src_w,
-                                       int x1, int y1, int cw, int ch, int feather, uint8_t* pair_out, uint8_t* full_out,
-                                       const float mean[3], const float stdv[3], void* ws_, int use_graph,
-                                       hipStream_t s) const {
-  D3F_CHECK(in_channels == 3 && classes == 3, "predict_frames_full_u8: 3-channel frames only (in %d, out %d)", in_channels,
-            classes);
-  D3F_CHECK(!(use_graph && full_out == raw_in),
-            "predict_frames_full_u8: full_out == raw_in (in place) cannot be replayed from a graph: pass use_graph = 0");
-  char* ws = reinterpret_cast<char*>(ws_);
-  float m255[3], s255[3];
-  for (int c = 0; c < 3; ++c) {  // as predict_u8
-    m255[c] = mean[c] * 255.0f;
-    s255[c] = stdv[c] * 255.0f;
-  }
-  if (int rc = frame_resize_check(src_h, src_w, x1, y1, cw, ch)) return rc;
-  const bool color = frame_color_ == FRAME_COLOR_MEANSTD;
-  if (int rc = color ? paste_resize_cubic_color_check(pair_out + 3L * W, raw_in, full_out, color_coef_, B, H, W, 6L * W, src_h,
-                                                      src_w, x1, y1, cw, ch, feather)
-                     : paste_resize_cubic_check(pair_out + 3L * W, raw_in, full_out, B, H, W, 6L * W, src_h, src_w, x1, y1, cw,
-                                                ch, feather))
-    return rc;
-  const int geo[6] = {src_h, src_w, x1, y1, cw, ch};
-  const bool temporal = temporal_strength_ != 0.f;
-  if (temporal) {
-    if (int rc = temporal_filter_check(pair_out, pair_out + 3L * W, B, H, W, 6L * W, 6L * W, temporal_fake_, temporal_real_,
-                                       temporal_valid_, temporal_strength_, temporal_threshold_))
+    // one launch writes the real half of the pair and, from the same rounded bytes, the network input
+    if (int rc = (aa ? crop_resize_cubic_aa_u8_nhwc_launch : crop_resize_cubic_u8_nhwc_launch)(
+            dtype, c.raw_in, B, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, pair, H, W, stride, ws + tensors[t_x].off,
+            tensors[t_x].C, k.mean, k.stdv, ls))
       return rc;
-    if (int rc = temporal_begin(s)) return rc;
-  }
-  auto launches = [&](hipStream_t ls) {
-    if (int rc = predict_frames_u8_launches(params_, bnstats, raw_in, geo, pair_out, m255, s255, ws, ls)) return rc;
+    float* head_out = reinterpret_cast<float*>(ws + head_nchw_off);
+    if (int rc = forward_body(params_, bnstats, head_out, ws, 0, ls, nullptr, false)) return rc;
+    head_z_live_ = false;
+    if (int rc = head_to_u8bgr(ws, fake, stride, k.mean, k.stdv, ls)) return rc;
     // the temporal filter first: the sums and the paste then read the filtered fake
     if (temporal)
-      if (int rc = temporal_filter_launches(pair_out, ls)) return rc;
-    // the fake half of the pair is the patch: rows 6 * W bytes apart
+      if (int rc = temporal_filter_u8_launch(pair, fake, B, H, W, stride, stride, o.state_fake.p, o.state_real.p, o.valid.p,
+                                             o.strength, o.threshold, ls))
+        return rc;
+    if (!full) return 0;
+    // the fake half of the pair is the patch
     if (!color)
-      return paste_resize_cubic_u8_launch(pair_out + 3L * W, B, H, W, 6L * W, raw_in, src_h, src_w, x1, y1, cw, ch, feather,
-                                          full_out, ls);
+      return paste_resize_cubic_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, c.feather,
+                                          c.full_out, ls);
     // colour match: the sums of both halves (set 0 the real crop = `to`, set 1 the fake = `from`), the coefficients, and
     // the paste in its colour form
     int parts = 0;
-    if (int rc = channel_sums_pair_slabs_launch(pair_out, 3L * W, B, H, W, 6L * W, color_slabs_, &parts, ls)) return rc;
-    const uint64_t* to = color_slabs_;
-    const uint64_t* from = color_slabs_ + (size_t)B * parts * 6;
-    if (int rc = color_match_coef_launch(from, to, parts, B, (long)H * W, color_coef_, ls)) return rc;
+    if (int rc = channel_sums_pair_slabs_launch(pair, pair_fake_off(), B, H, W, stride, o.color_slabs.p, &parts, ls)) return rc;
+    const uint64_t* to = o.color_slabs.p;
+    const uint64_t* from = to + (size_t)B * parts * 6;
+    if (int rc = color_match_coef_launch(from, to, parts, B, (long)H * W, o.color_coef.p, ls)) return rc;
     if (temporal)
-      if (int rc = color_coef_smooth_launch(color_coef_, to, parts, B, (long)H * W, temporal_strength_, temporal_coef_,
-                                            temporal_sum_, temporal_valid_ + 1, ls))
+      if (int rc = color_coef_smooth_launch(o.color_coef.p, to, parts, B, (long)H * W, o.strength, o.state_coef.p,
+                                            o.state_sum.p, o.valid.p + 1, ls))
         return rc;
-    return paste_resize_cubic_color_u8_launch(pair_out + 3L * W, B, H, W, 6L * W, raw_in, src_h, src_w, x1, y1, cw, ch,
-                                              feather, color_coef_, full_out, ls);
+    return paste_resize_cubic_color_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch,
+                                              c.feather, o.color_coef.p, c.full_out, ls);
   };
   if (!use_graph) return launches(s);
-  const GraphKey key = {{params_, bnstats, raw_in, pair_out, ws_, full_out},
-                        {m255[0], m255[1], m255[2], s255[0], s255[1], s255[2]},
-                        {src_h, src_w, x1, y1, cw, ch, feather, frame_color_, temporal_key(),
-                         temporal ? temporal_threshold_ : 0}};
-  return graph_replay(g_frames_full_, key, s, launches);
+  int strength_bits;
+  memcpy(&strength_bits, &o.strength, sizeof(strength_bits));
+  const GraphKey key = {{params_, bnstats, c.raw_in, pair, ws_, c.full_out},
+                        {k.mean[0], k.mean[1], k.mean[2], k.stdv[0], k.stdv[1], k.stdv[2]},
+                        {c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, full ? c.feather : 0, full ? o.color : 0, strength_bits,
+                         temporal ? o.threshold : 0}};
+  return graph_replay(full ? g_frames_full_ : g_frames_, key, s, launches);
 }
 
 int UnetEngine::forward_graph(const float* params_, float* bnstats, const float* x, float* out, void* ws_,
@@ -1005,10 +956,7 @@ int UnetEngine::graph_replay(GraphSlot& slot, const GraphKey& key, hipStream_t s
   static_assert(sizeof(GraphKey) == 6 * sizeof(void*) + 6 * sizeof(float) + 10 * sizeof(int), "GraphKey is compared bytewise");
   const bool same = slot.exec != nullptr && memcmp(&key, &slot.key, sizeof(GraphKey)) == 0;
   if (!same) {
-    if (slot.exec) {
-      (void)hipGraphExecDestroy(slot.exec);
-      slot.exec = nullptr;
-    }
+    slot.destroy();
     hipGraph_t graph = nullptr;
     D3F_HIP(hipStreamBeginCapture(gstream_, hipStreamCaptureModeThreadLocal));
     const int rc = launches(gstream_);
@@ -1044,14 +992,7 @@ UnetEngine::~UnetEngine() {
   if (ev_pack_in_) (void)hipEventDestroy(ev_pack_in_);
   if (ev_pack_done_) (void)hipEventDestroy(ev_pack_done_);
   if (ev_pack_mid_) (void)hipEventDestroy(ev_pack_mid_);
-  if (color_slabs_) (void)hipFree(color_slabs_);
-  if (color_coef_) (void)hipFree(color_coef_);
-  if (temporal_fake_) (void)hipFree(temporal_fake_);
-  if (temporal_real_) (void)hipFree(temporal_real_);
-  if (temporal_coef_) (void)hipFree(temporal_coef_);
-  if (temporal_sum_) (void)hipFree(temporal_sum_);
-  if (temporal_valid_) (void)hipFree(temporal_valid_);
-  // (side_ is the process-wide stream of this device: not ours to destroy)
+  // (side_ is the process-wide stream of this device: not ours to destroy; frame_'s buffers free themselves)
 }
 
 // Backward of segments [seg_begin, seg_end).  Per unit: BN backward (writes the unit's dY) -> {weight gradient,

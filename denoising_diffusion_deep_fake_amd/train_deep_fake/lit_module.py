@@ -458,18 +458,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         training images the same way.  temporal: None, a strength or (strength, threshold), as `Unet.predict_frames_u8`: the
         fake half filtered against flicker; successive calls are then consecutive in time (`reset_frame_temporal` starts a
         new sequence)."""
-        p = self.hparams
-        if model_a_or_b == "a":
-            model, mean, std = self.model_a, p.mean_b, p.std_b
-        elif model_a_or_b == "b":
-            model, mean, std = self.model_b, p.mean_a, p.std_a
-        else:
-            raise ValueError("model_a_or_b is 'a' or 'b'")
-        if model.training:
-            raise RuntimeError("predict_fake_frames is the eval-mode frame path: call .eval() first")
-        raw = np.ascontiguousarray(raw_bgr_batch)
-        if raw.dtype != np.uint8 or raw.ndim != 4 or raw.shape[-1] != 3:
-            raise ValueError("predict_fake_frames expects uint8 frames [B, h, w, 3] in BGR order")
+        model, mean, std, raw = self._frame_path_inputs(raw_bgr_batch, model_a_or_b, "predict_fake_frames")
         width, height = int(width), int(height)
         key = (raw.shape, id(model), width, height)
         if not hasattr(self, "_frames_buffers"):
@@ -485,7 +474,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         host_in, dev_in, dev_out, host_out = bufs
         host_in.copy_(torch.from_numpy(raw))
         dev_in.copy_(host_in, non_blocking=True)
-        model.predict_frames_u8(dev_in, (height, width), mean, std, graph=bool(p.get("inference_graph", False)),
+        model.predict_frames_u8(dev_in, (height, width), mean, std, graph=bool(self.hparams.get("inference_graph", False)),
                                 out=dev_out, antialias=antialias, temporal=temporal)
         host_out.copy_(dev_out, non_blocking=True)
         torch.cuda.current_stream().synchronize()

@@ -255,6 +255,11 @@ def _ptrs(ts):
     return ptr(ts[0]) if len(ts) == 1 else ptr2(*ts)
 
 
+def _float3(values):
+    """a `const float v[3]` argument of the uint8 entries: a mean or a standard deviation per channel"""
+    return (C.c_float * 3)(*[float(v) for v in values])
+
+
 class _NetsFunction(torch.autograd.Function):
     """the autograd node of one recorded forward pass of `owner` (a Unet, or a UnetPair: one output per network)"""
 
@@ -792,53 +797,85 @@ class Unet(nn.Module, _NetsRuntime):
         `cv2_to_tensor_normalised` / `tensor_cv2_to_denormalised` (d3f/train_deep_fake/lit_module.py:272-300) fused
         into the first and last kernel; `graph=True` replays a hipGraph captured per (input, output) buffer pair,
         so pass the same buffers again (`out=`) in a frame loop."""
-        if frames_bgr.dtype != torch.uint8 or frames_bgr.shape[-1] != 3 or frames_bgr.dim() not in (3, 4):
-            raise ValueError("predict_u8 expects uint8 frames [H, W, 3] or [B, H, W, 3] in BGR order")
-        if frames_bgr.device.type != "cuda":
-            raise D3FError("predict_u8 needs frames on the HIP device (no CPU fallback)")
-        single = frames_bgr.dim() == 3
-        x = frames_bgr.unsqueeze(0) if single else frames_bgr
+        x, single = self._u8_batch(frames_bgr, "predict_u8", "H, W")
         x = x.contiguous()
         B, H, W, _ = x.shape
-        if H % 32 or W % 32:
-            raise RuntimeError(f"Wrong input shape height={H}, width={W}. Expected image height and width "
-                               f"divisible by 32.")
-        self._ensure_flat(x.device)
-        eng = self._engine(B, H, W, x.device)
-        self._pack_if_needed(eng)
+        self._check_u8_size(H, W)
+        eng = self._u8_engine(B, H, W, x.device)
         if out is None:
             out = torch.empty_like(x)
         elif out.shape != x.shape or out.dtype != torch.uint8 or not out.is_contiguous():
             raise ValueError("out must be a contiguous uint8 tensor shaped like the input batch")
         rt = self._rt
-        m = (C.c_float * 3)(*[float(v) for v in mean])
-        sd = (C.c_float * 3)(*[float(v) for v in std])
-        check(_lib.lib().d3f_unet_predict_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), ptr(out), m, sd,
-                                             ptr(eng.workspace), 1 if graph else 0, stream_ptr()))
+        check(_lib.lib().d3f_unet_predict_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), ptr(out), _float3(mean),
+                                             _float3(std), ptr(eng.workspace), 1 if graph else 0, stream_ptr()))
         eng.keep = (x, out)  # the captured graph bakes these pointers in: keep them alive with the engine
         return out[0] if single else out
 
+    # -- what the uint8 entries share ------------------------------------------------------------------
     @staticmethod
-    def _set_frame_resample(eng, antialias):
-        """the frame entries' resize mode on the engine's handle (d3f_unet_set_frame_resample)"""
-        check(_lib.lib().d3f_unet_set_frame_resample(eng.h, _lib.RESAMPLE_CUBIC_AA if antialias else _lib.RESAMPLE_CUBIC))
+    def _u8_batch(frames, who, dims):
+        """the frames of the uint8 entry `who`, checked -> (the batch [B, ., ., 3], whether one frame [., ., 3] came in)"""
+        if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
+            raise ValueError(f"{who} expects uint8 frames [{dims}, 3] or [B, {dims}, 3] in BGR order")
+        if frames.device.type != "cuda":
+            raise D3FError(f"{who} needs frames on the HIP device (no CPU fallback)")
+        single = frames.dim() == 3
+        return (frames.unsqueeze(0) if single else frames), single
 
     @staticmethod
-    def _set_frame_temporal(eng, setting):
-        """the frame entries' temporal filter on the engine's handle (d3f_unet_set_frame_temporal); `setting` is what
-        `_lib.temporal_setting` returns.  The handle is told only when the setting changes: the same values keep its state"""
-        if getattr(eng, "temporal", (0.0, _lib.TEMPORAL_THRESHOLD)) != setting:  # (the handle starts switched off)
-            check(_lib.lib().d3f_unet_set_frame_temporal(eng.h, setting[0], setting[1]))
-            eng.temporal = setting
+    def _check_u8_size(H, W):
+        if H % 32 or W % 32:
+            raise RuntimeError(f"Wrong input shape height={H}, width={W}. Expected image height and width "
+                               f"divisible by 32.")
+
+    def _u8_engine(self, B, H, W, device):
+        """the plan for B frames at the network size H x W, its weights packed"""
+        self._ensure_flat(device)
+        eng = self._engine(B, H, W, device)
+        self._pack_if_needed(eng)
+        return eng
+
+    def _frame_inputs(self, who, raw_bgr, size, pair, pair_name, in_place=False):
+        """what the two raw-frame entries do before their C call -> (contiguous frames [B, h, w, 3], single, the call's
+        geometry (h, w, x1, y1, cw, ch) with the centre-crop box, the plan, the pair buffer [B, H, 2W, 3]: `pair`, checked, or
+        a new one)"""
+        from . import ops
+        x, single = self._u8_batch(raw_bgr, who, "h, w")
+        if in_place and not x.is_contiguous():
+            raise ValueError("out=raw_bgr (in place) needs contiguous frames")
+        x = x.contiguous()
+        B, h, w, _ = x.shape
+        H, W = int(size[0]), int(size[1])
+        self._check_u8_size(H, W)
+        geo = (h, w) + tuple(ops.center_crop_box(h, w, W, H))
+        eng = self._u8_engine(B, H, W, x.device)
+        shape = (B, H, 2 * W, 3)
+        if pair is None:
+            pair = torch.empty(shape, dtype=torch.uint8, device=x.device)
+        elif tuple(pair.shape) != shape or pair.dtype != torch.uint8 or not pair.is_contiguous() or pair.device != x.device:
+            raise ValueError(f"{pair_name} must be a contiguous uint8 tensor of shape {shape} on the input's device")
+        return x, single, geo, eng, pair
+
+    @staticmethod
+    def _apply_frame_settings(eng, antialias, color, temporal):
+        """the frame entries' settings on the plan's handle, in front of every call (the handle returns early on a value it
+        already has, and keeps its captured graphs and the filter's state then).  color: a D3F_COLOR_* code, or None: left
+        as it is -- `predict_frames_u8` has no paste to colour.  temporal: what `_lib.temporal_setting` returns."""
+        L = _lib.lib()
+        check(L.d3f_unet_set_frame_resample(eng.h, _lib.RESAMPLE_CUBIC_AA if antialias else _lib.RESAMPLE_CUBIC))
+        if color is not None:
+            check(L.d3f_unet_set_frame_color_match(eng.h, color))
+        check(L.d3f_unet_set_frame_temporal(eng.h, temporal[0], temporal[1]))
 
     def reset_frame_temporal(self):
         """forget the temporal filter's past on every plan of this network: the next frame of `predict_frames_u8` /
         `predict_frames_full_u8` with `temporal=` is a first frame again (d3f_unet_frame_temporal_reset, on the current
         stream; captured graphs stay)"""
+        # (every plan in a Unet's pools is a single network's, and one that never had the filter on has nothing to forget)
         for pool in self._rt.get("engines", {}).values():
             for eng in pool:
-                if getattr(eng, "temporal", None) is not None:
-                    check(_lib.lib().d3f_unet_frame_temporal_reset(eng.h, stream_ptr()))
+                check(_lib.lib().d3f_unet_frame_temporal_reset(eng.h, stream_ptr()))
 
     @torch.no_grad()
     def predict_frames_u8(self, raw_bgr, size, mean, std, graph=True, out=None, antialias=False, temporal=None):
@@ -854,36 +891,13 @@ class Unet(nn.Module, _NetsRuntime):
         (`ops.temporal_filter_u8` with real = the left half, fake = the right half; d3f_unet_set_frame_temporal).  The
         frames of successive calls are then consecutive in time, the state lives with the plan of this batch size and
         network size, `reset_frame_temporal()` starts a new sequence, and a change of the values starts one too."""
-        from . import ops
         temporal = _lib.temporal_setting(temporal)
-        if raw_bgr.dtype != torch.uint8 or raw_bgr.shape[-1] != 3 or raw_bgr.dim() not in (3, 4):
-            raise ValueError("predict_frames_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3] in BGR order")
-        if raw_bgr.device.type != "cuda":
-            raise D3FError("predict_frames_u8 needs frames on the HIP device (no CPU fallback)")
-        single = raw_bgr.dim() == 3
-        x = raw_bgr.unsqueeze(0) if single else raw_bgr
-        x = x.contiguous()
-        B, h, w, _ = x.shape
-        H, W = int(size[0]), int(size[1])
-        if H % 32 or W % 32:
-            raise RuntimeError(f"Wrong input shape height={H}, width={W}. Expected image height and width "
-                               f"divisible by 32.")
-        x1, y1, cw, ch = ops.center_crop_box(h, w, W, H)
-        self._ensure_flat(x.device)
-        eng = self._engine(B, H, W, x.device)
-        self._pack_if_needed(eng)
-        shape = (B, H, 2 * W, 3)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=x.device)
-        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device:
-            raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on the input's device")
+        x, single, geo, eng, out = self._frame_inputs("predict_frames_u8", raw_bgr, size, out, "out")
         rt = self._rt
-        m = (C.c_float * 3)(*[float(v) for v in mean])
-        sd = (C.c_float * 3)(*[float(v) for v in std])
-        self._set_frame_resample(eng, antialias)
-        self._set_frame_temporal(eng, temporal)
-        check(_lib.lib().d3f_unet_predict_frames_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), h, w, x1, y1, cw, ch,
-                                                    ptr(out), m, sd, ptr(eng.workspace), 1 if graph else 0, stream_ptr()))
+        self._apply_frame_settings(eng, antialias, None, temporal)
+        check(_lib.lib().d3f_unet_predict_frames_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), *geo, ptr(out),
+                                                    _float3(mean), _float3(std), ptr(eng.workspace), 1 if graph else 0,
+                                                    stream_ptr()))
         eng.keep = (x, out)  # the captured graph bakes these pointers in: keep them alive with the engine
         return out[0] if single else out
 
@@ -904,34 +918,12 @@ class Unet(nn.Module, _NetsRuntime):
         temporal: as `predict_frames_u8` -- the fake half of pair_out is filtered before the sums and the paste read it,
         and with color_match="meanstd" the coefficients are smoothed across frames too (`ops.color_coef_smooth`)."""
         from . import ops
-        color_mode = _lib.color_match_mode(color_match)
+        color_code = _lib.color_match_mode(color_match)
         temporal = _lib.temporal_setting(temporal)
-        if raw_bgr.dtype != torch.uint8 or raw_bgr.shape[-1] != 3 or raw_bgr.dim() not in (3, 4):
-            raise ValueError("predict_frames_full_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3] in BGR order")
-        if raw_bgr.device.type != "cuda":
-            raise D3FError("predict_frames_full_u8 needs frames on the HIP device (no CPU fallback)")
-        single = raw_bgr.dim() == 3
-        x = raw_bgr.unsqueeze(0) if single else raw_bgr
         in_place = out is raw_bgr
-        if in_place and not x.is_contiguous():
-            raise ValueError("out=raw_bgr (in place) needs contiguous frames")
-        x = x.contiguous()
-        B, h, w, _ = x.shape
-        H, W = int(size[0]), int(size[1])
-        if H % 32 or W % 32:
-            raise RuntimeError(f"Wrong input shape height={H}, width={W}. Expected image height and width "
-                               f"divisible by 32.")
-        x1, y1, cw, ch = ops.center_crop_box(h, w, W, H)
-        feather = ops.default_feather(cw, ch) if feather is None else int(feather)
-        self._ensure_flat(x.device)
-        eng = self._engine(B, H, W, x.device)
-        self._pack_if_needed(eng)
-        shape = (B, H, 2 * W, 3)
-        if pair_out is None:
-            pair_out = torch.empty(shape, dtype=torch.uint8, device=x.device)
-        elif (tuple(pair_out.shape) != shape or pair_out.dtype != torch.uint8 or not pair_out.is_contiguous()
-              or pair_out.device != x.device):
-            raise ValueError(f"pair_out must be a contiguous uint8 tensor of shape {shape} on the input's device")
+        x, single, geo, eng, pair_out = self._frame_inputs("predict_frames_full_u8", raw_bgr, size, pair_out, "pair_out",
+                                                           in_place)
+        feather = ops.default_feather(*geo[4:]) if feather is None else int(feather)
         if in_place:
             full = x
         elif out is None:
@@ -942,16 +934,10 @@ class Unet(nn.Module, _NetsRuntime):
                     or full.device != x.device):
                 raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(raw_bgr.shape)} on the input's device")
         rt = self._rt
-        m = (C.c_float * 3)(*[float(v) for v in mean])
-        sd = (C.c_float * 3)(*[float(v) for v in std])
-        self._set_frame_resample(eng, antialias)
-        if getattr(eng, "color_mode", _lib.COLOR_NONE) != color_mode:  # (the handle starts at D3F_COLOR_NONE)
-            check(_lib.lib().d3f_unet_set_frame_color_match(eng.h, color_mode))
-            eng.color_mode = color_mode
-        self._set_frame_temporal(eng, temporal)
-        check(_lib.lib().d3f_unet_predict_frames_full_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), h, w, x1, y1, cw,
-                                                         ch, feather, ptr(pair_out), ptr(full), m, sd, ptr(eng.workspace),
-                                                         1 if graph else 0, stream_ptr()))
+        self._apply_frame_settings(eng, antialias, color_code, temporal)
+        check(_lib.lib().d3f_unet_predict_frames_full_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), *geo, feather,
+                                                         ptr(pair_out), ptr(full), _float3(mean), _float3(std),
+                                                         ptr(eng.workspace), 1 if graph else 0, stream_ptr()))
         eng.keep_full = (x, pair_out, full)  # the captured graph bakes these pointers in: keep them alive with the engine
         return full[0] if single else full
 
