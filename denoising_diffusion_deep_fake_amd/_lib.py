@@ -174,6 +174,15 @@ PROTOTYPES = {
     "d3f_temporal_flag_set": (_i, [_p, _i, _p]),
     "d3f_unet_predict_frames_full_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, C.POINTER(_f), C.POINTER(_f),
                                              _p, _i, _p]),
+    # a box per frame: boxes is HOST memory, [B][4] int32
+    "d3f_crop_resize_cubic_boxes_u8": (_i, [_p, _i, _i, _i, C.POINTER(C.c_int32), _p, _i, _i, _i64, _p]),
+    "d3f_crop_resize_cubic_aa_boxes_u8": (_i, [_p, _i, _i, _i, C.POINTER(C.c_int32), _p, _i, _i, _i64, _p]),
+    "d3f_paste_resize_cubic_boxes_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, C.POINTER(C.c_int32), _i, _p, _p]),
+    "d3f_paste_resize_cubic_color_boxes_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, C.POINTER(C.c_int32), _i, _p, _p, _p]),
+    "d3f_unet_predict_frames_boxes_u8": (_i, [_p, _p, _p, _p, _i, _i, C.POINTER(C.c_int32), _p, C.POINTER(_f), C.POINTER(_f),
+                                              _p, _i, _p]),
+    "d3f_unet_predict_frames_full_boxes_u8": (_i, [_p, _p, _p, _p, _i, _i, C.POINTER(C.c_int32), _i, _p, _p, C.POINTER(_f),
+                                                   C.POINTER(_f), _p, _i, _p]),
     "d3f_image_grid_shape": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
     "d3f_image_grid_u8": (_i, [C.POINTER(_p), _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _p, _p]),
     "d3f_unet_num_segments": (_i, [_p]),

@@ -286,7 +286,7 @@ int d3f_unet_predict_frames_u8(d3f_unet_t h, const float* params, float* bnstats
                                const float std[3], void* workspace, int use_graph, void* stream) {
   D3F_CHECK(h && params && bnstats && raw_in && pair_out && mean && std && workspace, "predict_frames_u8: null argument");
   if (int rc = single_net(h, "predict_frames_u8", "has no eval-mode forward (run each network alone)")) return rc;
-  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, nullptr, 0};
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, nullptr, 0, nullptr};
   return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
 }
 
@@ -297,7 +297,30 @@ int d3f_unet_predict_frames_full_u8(d3f_unet_t h, const float* params, float* bn
   D3F_CHECK(h && params && bnstats && raw_in && pair_out && full_out && mean && std && workspace,
             "predict_frames_full_u8: null argument");
   if (int rc = single_net(h, "predict_frames_full_u8", "has no eval-mode forward (run each network alone)")) return rc;
-  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, full_out, feather};
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, full_out, feather, nullptr};
+  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
+}
+
+int d3f_unet_predict_frames_boxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
+                                     int src_w, const int32_t* boxes, uint8_t* pair_out, const float mean[3],
+                                     const float std[3], void* workspace, int use_graph, void* stream) {
+  D3F_CHECK(h && params && bnstats && raw_in && pair_out && mean && std && workspace,
+            "predict_frames_boxes_u8: null argument");
+  D3F_CHECK(boxes, "predict_frames_boxes_u8: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)");
+  if (int rc = single_net(h, "predict_frames_boxes_u8", "has no eval-mode forward (run each network alone)")) return rc;
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, nullptr, 0, boxes};
+  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
+}
+
+int d3f_unet_predict_frames_full_boxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in,
+                                          int src_h, int src_w, const int32_t* boxes, int feather, uint8_t* pair_out,
+                                          uint8_t* full_out, const float mean[3], const float std[3], void* workspace,
+                                          int use_graph, void* stream) {
+  D3F_CHECK(h && params && bnstats && raw_in && pair_out && full_out && mean && std && workspace,
+            "predict_frames_full_boxes_u8: null argument");
+  D3F_CHECK(boxes, "predict_frames_full_boxes_u8: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)");
+  if (int rc = single_net(h, "predict_frames_full_boxes_u8", "has no eval-mode forward (run each network alone)")) return rc;
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, full_out, feather, boxes};
   return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
 }
 
@@ -808,6 +831,37 @@ int d3f_paste_resize_cubic_color_u8(const uint8_t* patch, int B, int H, int W, i
   D3F_CHECK(patch && frame && out && coef, "paste_resize_cubic_color_u8: null argument");
   return paste_resize_cubic_color_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, x1, y1, cw, ch,
                                             feather, coef, out, (hipStream_t)stream);
+}
+
+static_assert(D3F_FRAME_BOXES_MAX == FRAME_BOXES_MAX, "d3f_hip.h states the boxes of a launch");
+int d3f_crop_resize_cubic_boxes_u8(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst, int H,
+                                   int W, int64_t dst_row_stride_bytes, void* stream) {
+  D3F_CHECK(src && dst, "crop_resize_cubic_boxes_u8: null argument");
+  return crop_resize_cubic_boxes_u8_launch(src, B, src_h, src_w, boxes, dst, H, W, (long)dst_row_stride_bytes,
+                                           (hipStream_t)stream);
+}
+
+int d3f_crop_resize_cubic_aa_boxes_u8(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
+                                      int H, int W, int64_t dst_row_stride_bytes, void* stream) {
+  D3F_CHECK(src && dst, "crop_resize_cubic_aa_boxes_u8: null argument");
+  return crop_resize_cubic_aa_boxes_u8_launch(src, B, src_h, src_w, boxes, dst, H, W, (long)dst_row_stride_bytes,
+                                              (hipStream_t)stream);
+}
+
+int d3f_paste_resize_cubic_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                    const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
+                                    uint8_t* out, void* stream) {
+  D3F_CHECK(patch && frame && out, "paste_resize_cubic_boxes_u8: null argument");
+  return paste_resize_cubic_boxes_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, boxes, feather,
+                                            out, (hipStream_t)stream);
+}
+
+int d3f_paste_resize_cubic_color_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                          const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
+                                          const float* coef, uint8_t* out, void* stream) {
+  D3F_CHECK(patch && frame && out && coef, "paste_resize_cubic_color_boxes_u8: null argument");
+  return paste_resize_cubic_color_boxes_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, boxes,
+                                                  feather, coef, out, (hipStream_t)stream);
 }
 
 int d3f_temporal_filter_u8(const uint8_t* real, int64_t real_row_stride_bytes, uint8_t* fake, int64_t fake_row_stride_bytes,

@@ -122,8 +122,14 @@ class UnetEngine {
     uint8_t* pair_out;
     uint8_t* full_out;  // null: the pair entry, which ignores feather and the colour mode
     int feather;
+    // HOST memory [B][4] (x1, y1, cw, ch of frame b), read before the call returns: a box per frame in place of the one
+    // above (d3f_unet_predict_frames_boxes_u8 / _full_boxes_u8).  The crop and the paste launches then run in their boxes
+    // forms (resize.hip); everything between them works on the pair buffer and is the same.  null: one box, as ever
+    const int32_t* boxes;
   };
-  // use_graph: captured once per set of pointers, constants, frame size, crop box and settings; a slot per entry
+  // use_graph: captured once per set of pointers, constants, frame size, crop box and settings; a slot per entry.  Refused
+  // with boxes: a captured launch bakes its kernel arguments in, the boxes among them, and a key on their values would
+  // re-capture on every call of a moving box
   int predict_frames(const FrameCall& c, const float* params, float* bnstats, const float mean[3], const float stdv[3],
                      void* ws, int use_graph, hipStream_t s) const;
   // eval-mode forward (f32 NCHW in / out) replayed from a hipGraph captured once per set of pointers -- the

@@ -798,8 +798,8 @@ int UnetEngine::predict_u8(const float* params_, float* bnstats, const uint8_t* 
 int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* bnstats, const float mean[3],
                                const float stdv[3], void* ws_, int use_graph, hipStream_t s) const {
   const bool full = c.full_out != nullptr;
-  D3F_CHECK(in_channels == 3 && classes == 3, "%s: 3-channel frames only (in %d, out %d)",
-            full ? "predict_frames_full_u8" : "predict_frames_u8", in_channels, classes);
+  const char* who = full ? "predict_frames_full_u8" : "predict_frames_u8";
+  D3F_CHECK(in_channels == 3 && classes == 3, "%s: 3-channel frames only (in %d, out %d)", who, in_channels, classes);
   char* ws = reinterpret_cast<char*>(ws_);
   const Scale255 k(mean, stdv);
   const FrameOptions& o = frame_;
@@ -809,15 +809,29 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
   uint8_t* const pair = c.pair_out;
   uint8_t* const fake = pair + pair_fake_off();
   const long stride = pair_stride();
-  if (int rc = (aa ? crop_resize_cubic_aa_check : crop_resize_cubic_check)(B, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, H, W,
-                                                                           stride))
+  const int32_t* const boxes = c.boxes;
+  D3F_CHECK(!(use_graph && boxes),
+            "%s with a box per frame cannot be replayed from a graph: a captured launch bakes its kernel arguments in, the "
+            "boxes among them, and a graph keyed on their values would be re-captured on every call; pass use_graph = 0",
+            who);
+  if (int rc = boxes ? (aa ? crop_resize_cubic_aa_boxes_check : crop_resize_cubic_boxes_check)(B, c.src_h, c.src_w, boxes, H,
+                                                                                              W, stride)
+                     : (aa ? crop_resize_cubic_aa_check : crop_resize_cubic_check)(B, c.src_h, c.src_w, c.x1, c.y1, c.cw,
+                                                                                  c.ch, H, W, stride))
     return rc;
   if (full) {
-    if (int rc = color ? paste_resize_cubic_color_check(fake, c.raw_in, c.full_out, o.color_coef.p, B, H, W, stride, c.src_h,
-                                                        c.src_w, c.x1, c.y1, c.cw, c.ch, c.feather)
-                       : paste_resize_cubic_check(fake, c.raw_in, c.full_out, B, H, W, stride, c.src_h, c.src_w, c.x1, c.y1,
-                                                  c.cw, c.ch, c.feather))
-      return rc;
+    int rc;
+    if (boxes)
+      rc = color ? paste_resize_cubic_color_boxes_check(fake, c.raw_in, c.full_out, o.color_coef.p, B, H, W, stride, c.src_h,
+                                                        c.src_w, boxes, c.feather)
+                 : paste_resize_cubic_boxes_check(fake, c.raw_in, c.full_out, B, H, W, stride, c.src_h, c.src_w, boxes,
+                                                  c.feather);
+    else
+      rc = color ? paste_resize_cubic_color_check(fake, c.raw_in, c.full_out, o.color_coef.p, B, H, W, stride, c.src_h,
+                                                  c.src_w, c.x1, c.y1, c.cw, c.ch, c.feather)
+                 : paste_resize_cubic_check(fake, c.raw_in, c.full_out, B, H, W, stride, c.src_h, c.src_w, c.x1, c.y1, c.cw,
+                                            c.ch, c.feather);
+    if (rc) return rc;
     D3F_CHECK(!(use_graph && c.full_out == c.raw_in),
               "predict_frames_full_u8: full_out == raw_in (in place) cannot be replayed from a graph: pass use_graph = 0");
   }
@@ -831,9 +845,12 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
   }
   auto launches = [&](hipStream_t ls) {
     // one launch writes the real half of the pair and, from the same rounded bytes, the network input
-    if (int rc = (aa ? crop_resize_cubic_aa_u8_nhwc_launch : crop_resize_cubic_u8_nhwc_launch)(
-            dtype, c.raw_in, B, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, pair, H, W, stride, ws + tensors[t_x].off,
-            tensors[t_x].C, k.mean, k.stdv, ls))
+    if (int rc = boxes ? (aa ? crop_resize_cubic_aa_boxes_u8_nhwc_launch : crop_resize_cubic_boxes_u8_nhwc_launch)(
+                             dtype, c.raw_in, B, c.src_h, c.src_w, boxes, pair, H, W, stride, ws + tensors[t_x].off,
+                             tensors[t_x].C, k.mean, k.stdv, ls)
+                       : (aa ? crop_resize_cubic_aa_u8_nhwc_launch : crop_resize_cubic_u8_nhwc_launch)(
+                             dtype, c.raw_in, B, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, pair, H, W, stride,
+                             ws + tensors[t_x].off, tensors[t_x].C, k.mean, k.stdv, ls))
       return rc;
     float* head_out = reinterpret_cast<float*>(ws + head_nchw_off);
     if (int rc = forward_body(params_, bnstats, head_out, ws, 0, ls, nullptr, false)) return rc;
@@ -847,8 +864,10 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
     if (!full) return 0;
     // the fake half of the pair is the patch
     if (!color)
-      return paste_resize_cubic_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, c.feather,
-                                          c.full_out, ls);
+      return boxes ? paste_resize_cubic_boxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, c.feather,
+                                                        c.full_out, ls)
+                   : paste_resize_cubic_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch,
+                                                  c.feather, c.full_out, ls);
     // colour match: the sums of both halves (set 0 the real crop = `to`, set 1 the fake = `from`), the coefficients, and
     // the paste in its colour form
     int parts = 0;
@@ -860,6 +879,9 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
       if (int rc = color_coef_smooth_launch(o.color_coef.p, to, parts, B, (long)H * W, o.strength, o.state_coef.p,
                                             o.state_sum.p, o.valid.p + 1, ls))
         return rc;
+    if (boxes)
+      return paste_resize_cubic_color_boxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, c.feather,
+                                                      o.color_coef.p, c.full_out, ls);
     return paste_resize_cubic_color_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch,
                                               c.feather, o.color_coef.p, c.full_out, ls);
   };

@@ -151,6 +151,36 @@ int paste_resize_cubic_color_check(const uint8_t* patch, const uint8_t* frame, c
 int paste_resize_cubic_color_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
                                        const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch,
                                        int feather, const float* coef, uint8_t* out, hipStream_t stream);
+// A box per frame (include/d3f_hip.h: the _boxes_ operators): each function above with (x1, y1, cw, ch) replaced by boxes,
+// HOST memory [B][4] as x1, y1, cw, ch, read before the call returns.  The boxes travel by value in the kernels' arguments,
+// FRAME_BOXES_MAX per launch; a longer call is several launches, in order.  Frame b is byte for byte the single-box call on
+// frame b with box b.  Refused before anything is launched: null boxes with B > 0, and for any frame what the single-box
+// function refuses of a box (the message names the frame)
+constexpr int FRAME_BOXES_MAX = 64;
+int crop_resize_cubic_boxes_check(int B, int src_h, int src_w, const int32_t* boxes, int H, int W, long dst_row_stride);
+int crop_resize_cubic_boxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
+                                      int H, int W, long dst_row_stride, hipStream_t stream);
+int crop_resize_cubic_boxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
+                                           uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
+                                           const float mean255[3], const float std255[3], hipStream_t stream);
+int crop_resize_cubic_aa_boxes_check(int B, int src_h, int src_w, const int32_t* boxes, int H, int W, long dst_row_stride);
+int crop_resize_cubic_aa_boxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
+                                         int H, int W, long dst_row_stride, hipStream_t stream);
+int crop_resize_cubic_aa_boxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w,
+                                              const int32_t* boxes, uint8_t* dst, int H, int W, long dst_row_stride,
+                                              void* act, int Cpad, const float mean255[3], const float std255[3],
+                                              hipStream_t stream);
+int paste_resize_cubic_boxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, int B, int H, int W,
+                                   long patch_row_stride, int src_h, int src_w, const int32_t* boxes, int feather);
+int paste_resize_cubic_boxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
+                                       const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
+                                       uint8_t* out, hipStream_t stream);
+int paste_resize_cubic_color_boxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef,
+                                         int B, int H, int W, long patch_row_stride, int src_h, int src_w,
+                                         const int32_t* boxes, int feather);
+int paste_resize_cubic_color_boxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
+                                             const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
+                                             const float* coef, uint8_t* out, hipStream_t stream);
 
 // colour match (color.hip; include/d3f_hip.h: d3f_channel_sums_u8, d3f_color_match_coef).  Sums: per frame and byte-in-pixel
 // S = sum p, Q = sum p^2 as uint64 [B][3][2], exact; at most COLOR_MAX_PIXELS pixels per frame, so that n Q and S^2 stay

@@ -33,12 +33,53 @@ namespace d3f {
 constexpr int RESIZE_TW = 32, RESIZE_TH = 8;
 constexpr int RESIZE_LDS_BYTES = 32 * 1024;
 constexpr int RESIZE_MAX_EXTENT = 16384;  // (2d + 1) * n_in stays below 2^31
+constexpr int AA_MAX_RATIO = 32;          // the antialiased form: n_in <= 32 n_out per axis
 
 struct ResizeGeom {
   int src_h, src_w, x1, y1, cw, ch, H, W;
   long dst_row_stride;
   int pitch;  // bytes of one staged patch row (a multiple of 4)
 };
+
+// ---- a box per frame (include/d3f_hip.h: the _boxes_ operators) ----
+// The boxes of a launch travel BY VALUE in the kernel's arguments: a table of at most FRAME_BOXES_MAX of them (1 KB), filled
+// on the host from host memory after every box has been checked.  No device buffer, no copy, no lifetime, and no device-side
+// read of a box nobody has checked.  A workgroup of frame blockIdx.z reads its own 16-byte entry -- a uniform index into the
+// kernel-argument segment, so one scalar load, and the box stays in SGPRs as the single box of the other form does -- and
+// from there on runs the code of the single-box kernel: the same device functions on the same operands, hence the same
+// bytes.  What a launch decides once (the staged pitch and STAGED, the antialiased form's table strides, the in-place
+// paste's grid) is the maximum over its boxes; each of these says where something sits in LDS or which workgroups exist,
+// none enters a value.  More than FRAME_BOXES_MAX frames are several launches, in order.
+// (FRAME_BOXES_MAX: pointwise.h)
+struct alignas(16) FrameBox {
+  int x1, y1, cw, ch;
+};
+struct FrameBoxes {
+  FrameBox box[FRAME_BOXES_MAX];
+};
+// a kernel's geometry argument: G alone (the single-box form: the arguments it always had), or G and the table
+template <typename G, bool BOXES>
+struct BoxedGeom {
+  G g;
+};
+template <typename G>
+struct BoxedGeom<G, true> {
+  G g;
+  FrameBoxes boxes;
+};
+// the geometry of frame b (= blockIdx.z of the launch): a.g, with frame b's own box in the boxes form
+template <typename G, bool BOXES>
+__device__ __forceinline__ G frame_geom(const BoxedGeom<G, BOXES>& a, int b) {
+  G g = a.g;
+  if constexpr (BOXES) {
+    const FrameBox bx = a.boxes.box[b];
+    g.x1 = bx.x1;
+    g.y1 = bx.y1;
+    g.cw = bx.cw;
+    g.ch = bx.ch;
+  }
+  return g;
+}
 
 // s = floor(f) and the four tap weights of output index d (n_in -> n_out)
 __device__ __forceinline__ int cubic_taps(int d, int n_in, int n_out, float w[4]) {
@@ -171,13 +212,15 @@ __device__ __forceinline__ void resize_store(const float v[3], uint8_t* o, T* a,
   }
 }
 
-template <typename T, bool ACT, bool STAGED>
+// BOXES: frame b takes box b of the table; g.pitch (and STAGED) are then the launch's, sized for its largest patch
+template <typename T, bool ACT, bool STAGED, bool BOXES>
 __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void crop_resize_cubic_kernel(
-    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, T* __restrict__ act, ResizeGeom g, int Cpad, float m0,
-    float m1, float m2, float s0, float s1, float s2) {
+    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, T* __restrict__ act, BoxedGeom<ResizeGeom, BOXES> geo,
+    int Cpad, float m0, float m1, float m2, float s0, float s1, float s2) {
   extern __shared__ __attribute__((aligned(16))) uint8_t patch[];
   const int tid = threadIdx.x;
   const int ox0 = blockIdx.x * RESIZE_TW, oy0 = blockIdx.y * RESIZE_TH, b = blockIdx.z;
+  const ResizeGeom g = frame_geom(geo, b);
   const long frame_bytes = (long)g.src_h * g.src_w * 3;
   const uint8_t* frame = src + b * frame_bytes;
   // the crop's first pixel; the tile stages rows and columns of the crop
@@ -198,33 +241,89 @@ __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void crop_resize_cubic_kerne
 
 // LDS bytes of the largest part of an n_h x n_w image a tile of a resize to out_h x out_w can need, and the pitch of its
 // rows; 0 when that passes RESIZE_LDS_BYTES (the taps are then read from global memory)
-static long resize_lds_bytes(int n_h, int n_w, int out_h, int out_w, int* pitch_out) {
+// (the boxes form sizes one patch for a launch: the most rows and the widest pitch of any of its frames)
+struct PatchExtent {
+  long rows = 0, pitch = 0;
+  void cover(const PatchExtent& e) {
+    rows = rows > e.rows ? rows : e.rows;
+    pitch = pitch > e.pitch ? pitch : e.pitch;
+  }
+  // LDS bytes and the rows' pitch, or 0 and 0 past RESIZE_LDS_BYTES
+  long lds_bytes(int* pitch_out) const {
+    const bool staged = rows * pitch <= RESIZE_LDS_BYTES;
+    *pitch_out = staged ? (int)pitch : 0;
+    return staged ? rows * pitch : 0;
+  }
+};
+static PatchExtent resize_patch_extent(int n_h, int n_w, int out_h, int out_w) {
   // floor(a + n r) - floor(a) <= floor(n r) + 1 source steps over n output steps, plus the three taps around them, plus up
   // to 3 bytes of dword alignment in front
   const long cols = (long)(RESIZE_TW - 1) * n_w / out_w + 1 + 4, rows = (long)(RESIZE_TH - 1) * n_h / out_h + 1 + 4;
-  const long pitch = (cols * 3 + 3 + 3) / 4 * 4;
-  const bool staged = rows * pitch <= RESIZE_LDS_BYTES;
-  *pitch_out = staged ? (int)pitch : 0;
-  return staged ? rows * pitch : 0;
+  return PatchExtent{rows, (cols * 3 + 3 + 3) / 4 * 4};
+}
+static long resize_lds_bytes(int n_h, int n_w, int out_h, int out_w, int* pitch_out) {
+  return resize_patch_extent(n_h, n_w, out_h, out_w).lds_bytes(pitch_out);
 }
 
-template <typename T, bool ACT>
-static int resize_launch(const uint8_t* src, uint8_t* dst, T* act, const ResizeGeom& g0, int B, int Cpad,
-                         const float mean255[3], const float std255[3], hipStream_t stream) {
-  ResizeGeom g = g0;
-  const long lds = resize_lds_bytes(g.ch, g.cw, g.H, g.W, &g.pitch);
+// the table of a launch over frames b0 .. b0 + n - 1 of a call's boxes [B][4] (host memory, checked by the caller)
+static void fill_frame_boxes(FrameBoxes& t, const int32_t* boxes, int b0, int n) {
+  t = FrameBoxes{};
+  for (int i = 0; i < n; ++i) {
+    const int32_t* bx = boxes + 4L * (b0 + i);
+    t.box[i] = FrameBox{bx[0], bx[1], bx[2], bx[3]};
+  }
+}
+
+// boxes null: the single-box launch with g0's box.  Otherwise frames b0 .. b0 + B - 1 of the table's call: one launch of at
+// most FRAME_BOXES_MAX frames (resize_boxes_launch cuts a call up)
+template <typename T, bool ACT, bool BOXES>
+static int resize_launch_one(const uint8_t* src, uint8_t* dst, T* act, const ResizeGeom& g0, const int32_t* boxes, int b0,
+                             int B, int Cpad, const float mean255[3], const float std255[3], hipStream_t stream) {
+  BoxedGeom<ResizeGeom, BOXES> a;
+  a.g = g0;
+  ResizeGeom& g = a.g;
+  long lds;
+  if constexpr (BOXES) {
+    fill_frame_boxes(a.boxes, boxes, b0, B);
+    PatchExtent e;
+    for (int i = 0; i < B; ++i) e.cover(resize_patch_extent(a.boxes.box[i].ch, a.boxes.box[i].cw, g.H, g.W));
+    lds = e.lds_bytes(&g.pitch);
+  } else {
+    lds = resize_lds_bytes(g.ch, g.cw, g.H, g.W, &g.pitch);
+  }
   const bool staged = lds > 0;
   const dim3 grid((g.W + RESIZE_TW - 1) / RESIZE_TW, (g.H + RESIZE_TH - 1) / RESIZE_TH, B), block(RESIZE_TW * RESIZE_TH);
   const float z[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
   const float* m = mean255 ? mean255 : z;
   const float* s = std255 ? std255 : one;
   if (staged)
-    hipLaunchKernelGGL((crop_resize_cubic_kernel<T, ACT, true>), grid, block, (size_t)lds, stream, src, dst, act,
-                       g, Cpad, m[0], m[1], m[2], s[0], s[1], s[2]);
+    hipLaunchKernelGGL((crop_resize_cubic_kernel<T, ACT, true, BOXES>), grid, block, (size_t)lds, stream, src, dst, act,
+                       a, Cpad, m[0], m[1], m[2], s[0], s[1], s[2]);
   else
-    hipLaunchKernelGGL((crop_resize_cubic_kernel<T, ACT, false>), grid, block, 0, stream, src, dst, act, g, Cpad, m[0],
-                       m[1], m[2], s[0], s[1], s[2]);
+    hipLaunchKernelGGL((crop_resize_cubic_kernel<T, ACT, false, BOXES>), grid, block, 0, stream, src, dst, act, a, Cpad,
+                       m[0], m[1], m[2], s[0], s[1], s[2]);
   D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+template <typename T, bool ACT>
+static int resize_launch(const uint8_t* src, uint8_t* dst, T* act, const ResizeGeom& g, int B, int Cpad,
+                         const float mean255[3], const float std255[3], hipStream_t stream) {
+  return resize_launch_one<T, ACT, false>(src, dst, act, g, nullptr, 0, B, Cpad, mean255, std255, stream);
+}
+
+// a call with a box per frame: launches of at most FRAME_BOXES_MAX frames each, in order
+template <typename T, bool ACT>
+static int resize_boxes_launch(const uint8_t* src, uint8_t* dst, T* act, const ResizeGeom& g, const int32_t* boxes, int B,
+                               int Cpad, const float mean255[3], const float std255[3], hipStream_t stream) {
+  const long frame_bytes = (long)g.src_h * g.src_w * 3, out_bytes = (long)g.H * g.dst_row_stride;
+  for (int b0 = 0; b0 < B; b0 += FRAME_BOXES_MAX) {
+    const int n = B - b0 < FRAME_BOXES_MAX ? B - b0 : FRAME_BOXES_MAX;
+    if (int rc = resize_launch_one<T, ACT, true>(src + b0 * frame_bytes, dst + b0 * out_bytes,
+                                                 ACT ? act + (long)b0 * g.H * g.W * Cpad : nullptr, g, boxes, b0, n, Cpad,
+                                                 mean255, std255, stream))
+      return rc;
+  }
   return 0;
 }
 
@@ -269,6 +368,53 @@ int crop_resize_cubic_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int s
   return resize_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, B, Cpad, mean255, std255, stream);
 }
 
+// What the single-box operators refuse of a box, for every frame of a boxes call, before anything is launched; the message
+// names the frame.  boxes: host memory [B][4] as x1, y1, cw, ch.  aa_H > 0: the antialiased form's ratio limit as well.
+static int frame_boxes_check(const char* op, const int32_t* boxes, int B, int src_h, int src_w, int aa_H = 0, int aa_W = 0) {
+  D3F_CHECK(boxes != nullptr || B <= 0, "%s: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)", op);
+  for (int b = 0; b < B; ++b) {
+    const int x1 = boxes[4L * b], y1 = boxes[4L * b + 1], cw = boxes[4L * b + 2], ch = boxes[4L * b + 3];
+    D3F_CHECK(cw > 0 && ch > 0, "%s: frame %d: non-positive box extent (%d x %d)", op, b, cw, ch);
+    D3F_CHECK(x1 >= 0 && y1 >= 0 && (long)x1 + cw <= src_w && (long)y1 + ch <= src_h,
+              "%s: frame %d: box (x1 %d, y1 %d, %d x %d) outside the %d x %d frame", op, b, x1, y1, cw, ch, src_w, src_h);
+    D3F_CHECK(aa_H <= 0 || ((long)cw <= (long)AA_MAX_RATIO * aa_W && (long)ch <= (long)AA_MAX_RATIO * aa_H),
+              "%s: frame %d: box %d x %d above %d times the output %d x %d on an axis", op, b, cw, ch, AA_MAX_RATIO, aa_W,
+              aa_H);
+  }
+  return 0;
+}
+
+// the geometry of a boxes call: everything of resize_geometry that is not the box (checked with a box every frame has),
+// then every frame's box
+static int resize_boxes_geometry(ResizeGeom& g, int B, int src_h, int src_w, const int32_t* boxes, int H, int W,
+                                 long dst_row_stride) {
+  if (int rc = resize_geometry(g, B, src_h, src_w, 0, 0, 1, 1, H, W, dst_row_stride)) return rc;
+  return frame_boxes_check("crop_resize_cubic_boxes", boxes, B, src_h, src_w);
+}
+
+int crop_resize_cubic_boxes_check(int B, int src_h, int src_w, const int32_t* boxes, int H, int W, long dst_row_stride) {
+  ResizeGeom g;
+  return resize_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride);
+}
+
+int crop_resize_cubic_boxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
+                                      int H, int W, long dst_row_stride, hipStream_t stream) {
+  ResizeGeom g;
+  if (int rc = resize_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride)) return rc;
+  return resize_boxes_launch<float, false>(src, dst, nullptr, g, boxes, B, 0, nullptr, nullptr, stream);
+}
+
+int crop_resize_cubic_boxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
+                                           uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
+                                           const float mean255[3], const float std255[3], hipStream_t stream) {
+  ResizeGeom g;
+  if (int rc = resize_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride)) return rc;
+  D3F_CHECK(Cpad >= 3, "crop_resize_cubic_boxes: activation of %d channels", Cpad);
+  if (dtype == D3F_F32)
+    return resize_boxes_launch<float, true>(src, dst, (float*)act, g, boxes, B, Cpad, mean255, std255, stream);
+  return resize_boxes_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, boxes, B, Cpad, mean255, std255, stream);
+}
+
 // ---- antialiased form: Pillow's bicubic (torch's interpolate(mode="bicubic", antialias=True)) ----
 // include/d3f_hip.h: d3f_crop_resize_cubic_aa_u8 is the definition; tests/resize_aa_restatement.py restates it in float64.
 // An axis that shrinks by r widens the Keys kernel (A = -0.5) by r: up to 4 r + 1 taps, 129 at the ratio limit of 32, and a
@@ -282,7 +428,6 @@ int crop_resize_cubic_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int s
 //     chunk's rows that lie inside its window to its vertical sum.
 // Loop bounds are the table's (first tap, count), which come from xmin / xmax alone: every index lies inside the crop.
 constexpr int AA_ROWS = 8;        // source rows per chunk: one per 32 lanes of the horizontal filter
-constexpr int AA_MAX_RATIO = 32;  // n_in <= 32 n_out per axis
 constexpr int AA_LDS_LIMIT = 64 * 1024;
 
 struct AaGeom {
@@ -346,11 +491,14 @@ __device__ __forceinline__ void aa_axis_table(float* wt, int* lo, int* cnt, floa
   __syncthreads();
 }
 
-template <typename T, bool ACT>
+// BOXES: frame b takes box b of the table; g.ntx, g.nty and g.pitch are then the launch's, the most of any of its frames
+// (aa_axis_table's count <= nt and row_bytes + 3 <= pitch hold for every frame; the three only place things in LDS)
+template <typename T, bool ACT, bool BOXES>
 __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void crop_resize_cubic_aa_kernel(
-    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, T* __restrict__ act, AaGeom g, int Cpad, float m0, float m1,
-    float m2, float s0, float s1, float s2) {
+    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, T* __restrict__ act, BoxedGeom<AaGeom, BOXES> geo, int Cpad,
+    float m0, float m1, float m2, float s0, float s1, float s2) {
   extern __shared__ __attribute__((aligned(16))) uint8_t aa_lds[];
+  const AaGeom g = frame_geom(geo, (int)blockIdx.z);
   // (aa_lds_bytes below is this layout)
   float* wx = reinterpret_cast<float*>(aa_lds);     // [RESIZE_TW][ntx]
   float* wy = wx + RESIZE_TW * g.ntx;               // [RESIZE_TH][nty]
@@ -446,6 +594,15 @@ static size_t aa_lds_bytes(const AaGeom& g) {
   return (floats + 2 * RESIZE_TW + 2 * RESIZE_TH) * 4 + (size_t)AA_ROWS * g.pitch;
 }
 
+// the table strides and the staged pitch of one box (aa_geometry), and of a launch: the most of its boxes
+static void aa_strides(AaGeom& g, int cw, int ch) {
+  const int ntx = aa_max_taps(cw, g.W) | 1, nty = aa_max_taps(ch, g.H) | 1;
+  const int pitch = (aa_max_cols(cw, g.W) * 3 + 3 + 3) / 4 * 4;  // up to 3 bytes of dword alignment in front
+  g.ntx = g.ntx > ntx ? g.ntx : ntx;
+  g.nty = g.nty > nty ? g.nty : nty;
+  g.pitch = g.pitch > pitch ? g.pitch : pitch;
+}
+
 static int aa_geometry(AaGeom& g, int B, int src_h, int src_w, int x1, int y1, int cw, int ch, int H, int W,
                        long dst_row_stride) {
   ResizeGeom r;
@@ -453,8 +610,8 @@ static int aa_geometry(AaGeom& g, int B, int src_h, int src_w, int x1, int y1, i
   D3F_CHECK((long)cw <= (long)AA_MAX_RATIO * W && (long)ch <= (long)AA_MAX_RATIO * H,
             "crop_resize_cubic_aa: crop %d x %d above %d times the output %d x %d on an axis (at most %d taps per axis)", cw,
             ch, AA_MAX_RATIO, W, H, 4 * AA_MAX_RATIO + 1);
-  g = AaGeom{src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride, aa_max_taps(cw, W) | 1, aa_max_taps(ch, H) | 1,
-             (aa_max_cols(cw, W) * 3 + 3 + 3) / 4 * 4};  // up to 3 bytes of dword alignment in front
+  g = AaGeom{src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride, 0, 0, 0};
+  aa_strides(g, cw, ch);
   D3F_CHECK(aa_lds_bytes(g) <= (size_t)AA_LDS_LIMIT, "crop_resize_cubic_aa: %zu bytes of LDS", aa_lds_bytes(g));
   return 0;
 }
@@ -465,17 +622,80 @@ int crop_resize_cubic_aa_check(int B, int src_h, int src_w, int x1, int y1, int 
   return aa_geometry(g, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride);
 }
 
-template <typename T, bool ACT>
-static int aa_launch(const uint8_t* src, uint8_t* dst, T* act, const AaGeom& g, int B, int Cpad, const float mean255[3],
-                     const float std255[3], hipStream_t stream) {
+// boxes null: the single-box launch of g0.  Otherwise frames b0 .. b0 + B - 1 of the table's call, at most FRAME_BOXES_MAX
+template <typename T, bool ACT, bool BOXES>
+static int aa_launch_one(const uint8_t* src, uint8_t* dst, T* act, const AaGeom& g0, const int32_t* boxes, int b0, int B,
+                         int Cpad, const float mean255[3], const float std255[3], hipStream_t stream) {
+  BoxedGeom<AaGeom, BOXES> a;
+  a.g = g0;
+  AaGeom& g = a.g;
+  if constexpr (BOXES) {
+    fill_frame_boxes(a.boxes, boxes, b0, B);
+    g.ntx = g.nty = g.pitch = 0;
+    for (int i = 0; i < B; ++i) aa_strides(g, a.boxes.box[i].cw, a.boxes.box[i].ch);
+    D3F_CHECK(aa_lds_bytes(g) <= (size_t)AA_LDS_LIMIT, "crop_resize_cubic_aa_boxes: %zu bytes of LDS", aa_lds_bytes(g));
+  }
   const dim3 grid((g.W + RESIZE_TW - 1) / RESIZE_TW, (g.H + RESIZE_TH - 1) / RESIZE_TH, B), block(RESIZE_TW * RESIZE_TH);
   const float z[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
   const float* m = mean255 ? mean255 : z;
   const float* s = std255 ? std255 : one;
-  hipLaunchKernelGGL((crop_resize_cubic_aa_kernel<T, ACT>), grid, block, aa_lds_bytes(g), stream, src, dst, act, g, Cpad,
-                     m[0], m[1], m[2], s[0], s[1], s[2]);
+  hipLaunchKernelGGL((crop_resize_cubic_aa_kernel<T, ACT, BOXES>), grid, block, aa_lds_bytes(g), stream, src, dst, act, a,
+                     Cpad, m[0], m[1], m[2], s[0], s[1], s[2]);
   D3F_HIP(hipGetLastError());
   return 0;
+}
+
+template <typename T, bool ACT>
+static int aa_launch(const uint8_t* src, uint8_t* dst, T* act, const AaGeom& g, int B, int Cpad, const float mean255[3],
+                     const float std255[3], hipStream_t stream) {
+  return aa_launch_one<T, ACT, false>(src, dst, act, g, nullptr, 0, B, Cpad, mean255, std255, stream);
+}
+
+// a call with a box per frame: launches of at most FRAME_BOXES_MAX frames each, in order
+template <typename T, bool ACT>
+static int aa_boxes_launch(const uint8_t* src, uint8_t* dst, T* act, const AaGeom& g, const int32_t* boxes, int B, int Cpad,
+                           const float mean255[3], const float std255[3], hipStream_t stream) {
+  const long frame_bytes = (long)g.src_h * g.src_w * 3, out_bytes = (long)g.H * g.dst_row_stride;
+  for (int b0 = 0; b0 < B; b0 += FRAME_BOXES_MAX) {
+    const int n = B - b0 < FRAME_BOXES_MAX ? B - b0 : FRAME_BOXES_MAX;
+    if (int rc = aa_launch_one<T, ACT, true>(src + b0 * frame_bytes, dst + b0 * out_bytes,
+                                             ACT ? act + (long)b0 * g.H * g.W * Cpad : nullptr, g, boxes, b0, n, Cpad,
+                                             mean255, std255, stream))
+      return rc;
+  }
+  return 0;
+}
+
+// the geometry of a boxes call: aa_geometry's checks with a box every frame has, then every frame's box.  (The LDS of a
+// launch -- its boxes' largest strides together -- stays below AA_LDS_LIMIT whatever the boxes: at the ratio limit on both
+// axes it is 52 KB.)
+static int aa_boxes_geometry(AaGeom& g, int B, int src_h, int src_w, const int32_t* boxes, int H, int W,
+                             long dst_row_stride) {
+  if (int rc = aa_geometry(g, B, src_h, src_w, 0, 0, 1, 1, H, W, dst_row_stride)) return rc;
+  return frame_boxes_check("crop_resize_cubic_aa_boxes", boxes, B, src_h, src_w, H, W);
+}
+
+int crop_resize_cubic_aa_boxes_check(int B, int src_h, int src_w, const int32_t* boxes, int H, int W, long dst_row_stride) {
+  AaGeom g;
+  return aa_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride);
+}
+
+int crop_resize_cubic_aa_boxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
+                                         int H, int W, long dst_row_stride, hipStream_t stream) {
+  AaGeom g;
+  if (int rc = aa_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride)) return rc;
+  return aa_boxes_launch<float, false>(src, dst, nullptr, g, boxes, B, 0, nullptr, nullptr, stream);
+}
+
+int crop_resize_cubic_aa_boxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w,
+                                              const int32_t* boxes, uint8_t* dst, int H, int W, long dst_row_stride,
+                                              void* act, int Cpad, const float mean255[3], const float std255[3],
+                                              hipStream_t stream) {
+  AaGeom g;
+  if (int rc = aa_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride)) return rc;
+  D3F_CHECK(Cpad >= 3, "crop_resize_cubic_aa_boxes: activation of %d channels", Cpad);
+  if (dtype == D3F_F32) return aa_boxes_launch<float, true>(src, dst, (float*)act, g, boxes, B, Cpad, mean255, std255, stream);
+  return aa_boxes_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, boxes, B, Cpad, mean255, std255, stream);
 }
 
 int crop_resize_cubic_aa_u8_launch(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch,
@@ -514,30 +734,43 @@ struct PasteGeom {
 };
 // the kernel's last argument: the geometry and, in the colour form only, the coefficients [B][3][2] (gain, offset) -- the
 // plain form's arguments are the ones it had before there was a colour form
-template <bool COLOR>
+// BOXES: the table of the launch's boxes behind the geometry
+template <bool COLOR, bool BOXES>
 struct PasteArgs {
-  PasteGeom g;
+  BoxedGeom<PasteGeom, BOXES> geo;
 };
-template <>
-struct PasteArgs<true> {
-  PasteGeom g;
+template <bool BOXES>
+struct PasteArgs<true, BOXES> {
+  BoxedGeom<PasteGeom, BOXES> geo;
   const float* coef;
 };
 
 // COLOR (include/d3f_hip.h: d3f_paste_resize_cubic_color_u8): the clamped patch value goes through gain * v + offset of its
 // frame and channel (product and sum rounded separately) and a second clamp before the blend
-template <bool STAGED, bool COLOR>
+// BOXES: frame b takes box b of the table; g.pitch (and STAGED) are the launch's, sized for its largest staged part.  In
+// place the grid is the largest tile count of any frame: a frame derives its own first tile here, and its workgroups past its
+// own tile count return before they touch memory -- the tiles they would name belong to no box of THIS frame
+template <bool STAGED, bool COLOR, bool BOXES>
 __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void paste_resize_cubic_kernel(const uint8_t* __restrict__ patch,
                                                                                   const uint8_t* frame, uint8_t* out,
-                                                                                  PasteArgs<COLOR> args) {
-  const PasteGeom& g = args.g;
+                                                                                  PasteArgs<COLOR, BOXES> args) {
+  const int b = blockIdx.z;
+  PasteGeom g = frame_geom(args.geo, b);
+  const bool in_place = frame == out;
+  if constexpr (BOXES) {
+    if (in_place) {  // (workgroup-uniform)
+      g.tx0 = g.x1 / RESIZE_TW;
+      g.ty0 = g.y1 / RESIZE_TH;
+      if ((int)blockIdx.x > (g.x1 + g.cw - 1) / RESIZE_TW - g.tx0 || (int)blockIdx.y > (g.y1 + g.ch - 1) / RESIZE_TH - g.ty0)
+        return;
+    }
+  }
   extern __shared__ __attribute__((aligned(16))) uint8_t staged[];
   const int tid = threadIdx.x;
-  const int ox0 = ((int)blockIdx.x + g.tx0) * RESIZE_TW, oy0 = ((int)blockIdx.y + g.ty0) * RESIZE_TH, b = blockIdx.z;
+  const int ox0 = ((int)blockIdx.x + g.tx0) * RESIZE_TW, oy0 = ((int)blockIdx.y + g.ty0) * RESIZE_TH;
   const long frame_bytes = (long)g.src_h * g.src_w * 3, row_bytes = (long)g.src_w * 3;
   const uint8_t* f = frame + b * frame_bytes;
   uint8_t* o = out + b * frame_bytes;
-  const bool in_place = frame == out;
   const int tile_w = min(RESIZE_TW, g.src_w - ox0), tile_h = min(RESIZE_TH, g.src_h - oy0);
   // the box pixels of this tile: columns [bx_f, bx_l] and rows [by_f, by_l] of the box
   const int bx_f = max(ox0, g.x1) - g.x1, bx_l = min(ox0 + tile_w, g.x1 + g.cw) - 1 - g.x1;
@@ -647,30 +880,111 @@ int paste_resize_cubic_color_check(const uint8_t* patch, const uint8_t* frame, c
   return 0;
 }
 
-// the launch of both forms; coef is read by the colour form only
+// one launch of both forms; coef is read by the colour form only.  boxes null: the single box (x1, y1, cw, ch).  Otherwise
+// frames b0 .. b0 + B - 1 of the table's call, at most FRAME_BOXES_MAX (patch, frame, out and coef are those frames')
+template <bool COLOR, bool BOXES>
+static int paste_launch_one(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
+                            int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes, int b0, int feather,
+                            const float* coef, uint8_t* out, hipStream_t stream) {
+  PasteArgs<COLOR, BOXES> args;
+  PasteGeom& g = args.geo.g;
+  g = PasteGeom{H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather, 0, 0, 0};
+  if constexpr (COLOR) args.coef = coef;
+  dim3 grid((src_w + RESIZE_TW - 1) / RESIZE_TW, (src_h + RESIZE_TH - 1) / RESIZE_TH, B);
+  long lds;
+  if constexpr (BOXES) {
+    fill_frame_boxes(args.geo.boxes, boxes, b0, B);
+    PatchExtent e;
+    unsigned tiles_x = 1, tiles_y = 1;  // in place: the most tiles any frame's box meets
+    for (int i = 0; i < B; ++i) {
+      const FrameBox& bx = args.geo.boxes.box[i];
+      e.cover(resize_patch_extent(H, W, bx.ch, bx.cw));
+      const unsigned nx = (bx.x1 + bx.cw - 1) / RESIZE_TW - bx.x1 / RESIZE_TW + 1;
+      const unsigned ny = (bx.y1 + bx.ch - 1) / RESIZE_TH - bx.y1 / RESIZE_TH + 1;
+      tiles_x = tiles_x > nx ? tiles_x : nx;
+      tiles_y = tiles_y > ny ? tiles_y : ny;
+    }
+    lds = e.lds_bytes(&g.pitch);
+    if (frame == out) {  // (the kernel derives each frame's tx0, ty0)
+      grid.x = tiles_x;
+      grid.y = tiles_y;
+    }
+  } else {
+    lds = resize_lds_bytes(H, W, ch, cw, &g.pitch);
+    if (frame == out) {  // in place: the tiles that meet the box
+      g.tx0 = x1 / RESIZE_TW;
+      g.ty0 = y1 / RESIZE_TH;
+      grid.x = (x1 + cw - 1) / RESIZE_TW - g.tx0 + 1;
+      grid.y = (y1 + ch - 1) / RESIZE_TH - g.ty0 + 1;
+    }
+  }
+  const dim3 block(RESIZE_TW * RESIZE_TH);
+  if (lds > 0)
+    hipLaunchKernelGGL((paste_resize_cubic_kernel<true, COLOR, BOXES>), grid, block, (size_t)lds, stream, patch, frame, out,
+                       args);
+  else
+    hipLaunchKernelGGL((paste_resize_cubic_kernel<false, COLOR, BOXES>), grid, block, 0, stream, patch, frame, out, args);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
 template <bool COLOR>
 static int paste_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
                         int src_w, int x1, int y1, int cw, int ch, int feather, const float* coef, uint8_t* out,
                         hipStream_t stream) {
-  PasteArgs<COLOR> args;
-  PasteGeom& g = args.g;
-  g = PasteGeom{H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather, 0, 0, 0};
-  if constexpr (COLOR) args.coef = coef;
-  const long lds = resize_lds_bytes(H, W, ch, cw, &g.pitch);
-  dim3 grid((src_w + RESIZE_TW - 1) / RESIZE_TW, (src_h + RESIZE_TH - 1) / RESIZE_TH, B);
-  if (frame == out) {  // in place: the tiles that meet the box
-    g.tx0 = x1 / RESIZE_TW;
-    g.ty0 = y1 / RESIZE_TH;
-    grid.x = (x1 + cw - 1) / RESIZE_TW - g.tx0 + 1;
-    grid.y = (y1 + ch - 1) / RESIZE_TH - g.ty0 + 1;
+  return paste_launch_one<COLOR, false>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, x1, y1, cw, ch, nullptr, 0,
+                                        feather, coef, out, stream);
+}
+
+// a call with a box per frame: launches of at most FRAME_BOXES_MAX frames each, in order
+template <bool COLOR>
+static int paste_boxes_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
+                              int src_h, int src_w, const int32_t* boxes, int feather, const float* coef, uint8_t* out,
+                              hipStream_t stream) {
+  const long frame_bytes = (long)src_h * src_w * 3, patch_bytes = (long)H * patch_row_stride;
+  for (int b0 = 0; b0 < B; b0 += FRAME_BOXES_MAX) {
+    const int n = B - b0 < FRAME_BOXES_MAX ? B - b0 : FRAME_BOXES_MAX;
+    if (int rc = paste_launch_one<COLOR, true>(patch + b0 * patch_bytes, n, H, W, patch_row_stride, frame + b0 * frame_bytes,
+                                               src_h, src_w, 0, 0, 0, 0, boxes, b0, feather, COLOR ? coef + 6L * b0 : nullptr,
+                                               out + b0 * frame_bytes, stream))
+      return rc;
   }
-  const dim3 block(RESIZE_TW * RESIZE_TH);
-  if (lds > 0)
-    hipLaunchKernelGGL((paste_resize_cubic_kernel<true, COLOR>), grid, block, (size_t)lds, stream, patch, frame, out, args);
-  else
-    hipLaunchKernelGGL((paste_resize_cubic_kernel<false, COLOR>), grid, block, 0, stream, patch, frame, out, args);
-  D3F_HIP(hipGetLastError());
   return 0;
+}
+
+// the checks of a boxes call: the single-box operator's with a box every frame has, then every frame's box
+int paste_resize_cubic_boxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, int B, int H, int W,
+                                   long patch_row_stride, int src_h, int src_w, const int32_t* boxes, int feather) {
+  if (int rc = paste_resize_cubic_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, 0, 0, 1, 1, feather))
+    return rc;
+  return frame_boxes_check("paste_resize_cubic_boxes", boxes, B, src_h, src_w);
+}
+
+int paste_resize_cubic_color_boxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef,
+                                         int B, int H, int W, long patch_row_stride, int src_h, int src_w,
+                                         const int32_t* boxes, int feather) {
+  if (int rc = paste_resize_cubic_color_check(patch, frame, out, coef, B, H, W, patch_row_stride, src_h, src_w, 0, 0, 1, 1,
+                                              feather))
+    return rc;
+  return frame_boxes_check("paste_resize_cubic_color_boxes", boxes, B, src_h, src_w);
+}
+
+int paste_resize_cubic_boxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
+                                       const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
+                                       uint8_t* out, hipStream_t stream) {
+  if (int rc = paste_resize_cubic_boxes_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, boxes, feather))
+    return rc;
+  return paste_boxes_launch<false>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, boxes, feather, nullptr, out,
+                                   stream);
+}
+
+int paste_resize_cubic_color_boxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
+                                             const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
+                                             const float* coef, uint8_t* out, hipStream_t stream) {
+  if (int rc = paste_resize_cubic_color_boxes_check(patch, frame, out, coef, B, H, W, patch_row_stride, src_h, src_w, boxes,
+                                                    feather))
+    return rc;
+  return paste_boxes_launch<true>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, boxes, feather, coef, out, stream);
 }
 
 int paste_resize_cubic_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,

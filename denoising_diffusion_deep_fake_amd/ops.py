@@ -678,22 +678,130 @@ def center_crop_box(h, w, width, height):
     return x1, y1, crop_width, crop_height
 
 
-def crop_resize_cubic_u8(frames, size, box=None, out=None, antialias=False):
+TRACK_MARGIN = 1.6  # a design choice, not a measurement: how much wider than the detector's box the crop is cut
+
+
+def track_crop_box(h, w, width, height, face, margin=TRACK_MARGIN):
+    """the crop box of the target aspect (width x height) around a detector's box face = (fx, fy, fw, fh) in an h x w frame,
+    as (x1, y1, crop_width, crop_height): `margin` times the face on the axis that needs the larger scale, capped by
+    `center_crop_box`'s own scale -- so the box always fits -- and moved inside the frame.  The face may stick out of the
+    frame.  The scale in Python floats with int() truncation, as `center_crop_box`; the position in integers."""
+    fx, fy, fw, fh = [int(v) for v in face]
+    if fw <= 0 or fh <= 0:
+        raise ValueError(f"track_crop_box: face extent {fw} x {fh} is not positive")
+    s = max(fw / width, fh / height) * margin
+    s = min(s, w / width, h / height)
+    cw = max(int(width * s), 1)
+    ch = max(int(height * s), 1)
+    x1 = min(max((2 * fx + fw - cw) // 2, 0), w - cw)
+    y1 = min(max((2 * fy + fh - ch) // 2, 0), h - ch)
+    return x1, y1, cw, ch
+
+
+def read_box_track(path):
+    """a detector's track file -> a list of boxes (fx, fy, fw, fh), entry k for frame k.  A line is four integers `x y w h`
+    separated by blanks or commas; `#` starts a comment; blank lines are skipped; a lone `-` is a frame without a
+    detection.  A gap takes the previous detection, leading gaps the first one; a file without any detection is a
+    ValueError.  (Frames past the last line keep the last box: `box_of_frame`.)"""
+    faces = []
+    with open(path) as f:
+        for number, line in enumerate(f, 1):
+            fields = line.split("#", 1)[0].replace(",", " ").split()
+            if not fields:
+                continue
+            if fields == ["-"]:
+                faces.append(None)
+                continue
+            try:
+                if len(fields) != 4:
+                    raise ValueError
+                faces.append(tuple(int(v) for v in fields))
+            except ValueError:
+                raise ValueError(f"{path}, line {number}: expected four integers `x y w h` or `-`, "
+                                 f"got {line.strip()!r}") from None
+    first = next((face for face in faces if face is not None), None)
+    if first is None:
+        raise ValueError(f"{path}: no detection in the track")
+    last = first
+    for k, face in enumerate(faces):
+        if face is None:
+            faces[k] = last
+        else:
+            last = face
+    return faces
+
+
+def smooth_box_track(faces, n):
+    """a centred moving average over up to 2 n + 1 entries of a track (the window is truncated at both ends): the mean of
+    (2 fx + fw, 2 fy + fh, fw, fh) in integers with floor division, turned back into (fx, fy, fw, fh).  n = 0 returns its
+    input.  A detector's jitter otherwise becomes crop jitter, which the temporal filter reads as motion."""
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"smooth_box_track: n = {n} is negative")
+    if n == 0:
+        return list(faces)
+    faces = [tuple(int(v) for v in face) for face in faces]
+    out = []
+    for k in range(len(faces)):
+        window = faces[max(k - n, 0):k + n + 1]
+        m = len(window)
+        cx2 = sum(2 * fx + fw for fx, _, fw, _ in window) // m
+        cy2 = sum(2 * fy + fh for _, fy, _, fh in window) // m
+        fw = sum(face[2] for face in window) // m
+        fh = sum(face[3] for face in window) // m
+        out.append(((cx2 - fw) // 2, (cy2 - fh) // 2, fw, fh))
+    return out
+
+
+def box_of_frame(track, k):
+    """entry k of a track; frames past its last line keep the last box"""
+    return track[min(int(k), len(track) - 1)]
+
+
+def track_crop_boxes(track, first, count, h, w, width, height, margin=TRACK_MARGIN):
+    """`track_crop_box` of frames first .. first + count - 1 of a track (what `read_box_track` returns) in h x w frames: the
+    [count][4] boxes of one batch of a frame loop"""
+    return [track_crop_box(h, w, width, height, box_of_frame(track, first + i), margin) for i in range(count)]
+
+
+def _boxes_arg(boxes, B, who):
+    """boxes = [B][4] integers (a sequence, a numpy array or a host tensor) -> a ctypes int32 array [B * 4] in host memory
+    and the boxes as a list of 4-tuples"""
+    if isinstance(boxes, torch.Tensor):
+        boxes = boxes.tolist()
+    rows = [tuple(int(v) for v in row) for row in boxes]
+    if len(rows) != B or any(len(row) != 4 for row in rows):
+        raise ValueError(f"{who}: boxes must be [{B}][4] integers (x1, y1, cw, ch), one box per frame")
+    if any(not -2 ** 31 <= v < 2 ** 31 for row in rows for v in row):
+        raise ValueError(f"{who}: boxes holds a value outside 32 bits")
+    flat = (C.c_int32 * (4 * B))(*[v for row in rows for v in row])
+    return flat, rows
+
+
+def crop_resize_cubic_u8(frames, size, box=None, out=None, antialias=False, boxes=None):
     """uint8 frames [h, w, 3] or [B, h, w, 3] on the HIP device -> the crop box (x1, y1, cw, ch) resized to size = (H, W)
     as cv2.resize(..., INTER_CUBIC) defines it in float arithmetic (include/d3f_hip.h: d3f_crop_resize_cubic_u8).
     box=None: the reference's centre crop to the target aspect.  out: a uint8 tensor [B, H, W, 3] whose pixels are packed
     and whose rows may be strided -- the left half of a [B, H, 2W, 3] side-by-side buffer, for one.
     antialias=True: Pillow's bicubic instead, whose window widens with the scale -- what
     torch.nn.functional.interpolate(mode="bicubic", antialias=True) computes (d3f_crop_resize_cubic_aa_u8); for crops several
-    times the size of the output, where four taps per axis skip most of the source pixels."""
+    times the size of the output, where four taps per axis skip most of the source pixels.
+    boxes: [B][4] integers in host memory, a box per frame, instead of box= (one of the two at most): frame b is byte for
+    byte the single-box call on frame b with boxes[b], still one device call (d3f_crop_resize_cubic_boxes_u8 and its _aa
+    form; one launch per 64 frames)."""
     if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
         raise ValueError("crop_resize_cubic_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3]")
+    if box is not None and boxes is not None:
+        raise ValueError("crop_resize_cubic_u8: box= and boxes= exclude each other")
     dev = _dev(frames)
     single = frames.dim() == 3
     x = (frames.unsqueeze(0) if single else frames).contiguous()
     B, h, w, _ = x.shape
     H, W = int(size[0]), int(size[1])
-    x1, y1, cw, ch = center_crop_box(h, w, W, H) if box is None else [int(v) for v in box]
+    if boxes is not None:
+        table, _ = _boxes_arg(boxes, B, "crop_resize_cubic_u8")
+    else:
+        x1, y1, cw, ch = center_crop_box(h, w, W, H) if box is None else [int(v) for v in box]
     if out is None:
         out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
     elif (tuple(out.shape) != (B, H, W, 3) or out.dtype != torch.uint8 or out.device != dev or out.stride(3) != 1
@@ -701,6 +809,10 @@ def crop_resize_cubic_u8(frames, size, box=None, out=None, antialias=False):
         raise ValueError(f"out must be a uint8 tensor of shape {(B, H, W, 3)} on the input's device with packed pixels "
                          f"and frames H rows apart")
     L = _lib.lib()
+    if boxes is not None:
+        resize = L.d3f_crop_resize_cubic_aa_boxes_u8 if antialias else L.d3f_crop_resize_cubic_boxes_u8
+        check(resize(ptr(x), B, h, w, table, ptr(out), H, W, out.stride(1), stream_ptr()))
+        return out[0] if single else out
     resize = L.d3f_crop_resize_cubic_aa_u8 if antialias else L.d3f_crop_resize_cubic_u8
     check(resize(ptr(x), B, h, w, x1, y1, cw, ch, ptr(out), H, W, out.stride(1), stream_ptr()))
     return out[0] if single else out
@@ -841,7 +953,7 @@ def color_coef_smooth(coef, sums_to, n, state, strength=_lib.TEMPORAL_STRENGTH):
     return coef
 
 
-def paste_resize_cubic_u8(patch, frames, box, feather=0, out=None, color=None):
+def paste_resize_cubic_u8(patch, frames, box=None, feather=0, out=None, color=None, boxes=None):
     """The inverse of `crop_resize_cubic_u8` with a blend: uint8 `patch` [H, W, 3] / [B, H, W, 3] on the HIP device is resized
     to the box (x1, y1, cw, ch) of uint8 `frames` [h, w, 3] / [B, h, w, 3] with the same arithmetic and blended in over a
     ramp of `feather` pixels; outside the box the result is the frame (include/d3f_hip.h: d3f_paste_resize_cubic_u8).
@@ -849,7 +961,12 @@ def paste_resize_cubic_u8(patch, frames, box, feather=0, out=None, color=None):
     place; otherwise out is a contiguous tensor shaped like frames, allocated when None.
     color: float32 coefficients [B, 3, 2] ([3, 2] for a single frame), gain then offset per frame and byte-in-pixel, as
     `color_match_coef` gives them: the patch's resized, clamped value goes through gain * v + offset and a second clamp before
-    the blend (d3f_paste_resize_cubic_color_u8).  None: the plain call."""
+    the blend (d3f_paste_resize_cubic_color_u8).  None: the plain call.
+    boxes: [B][4] integers in host memory, a box per frame, instead of box= (exactly one of the two); one `feather` for the
+    call.  Frame b is byte for byte the single-box call on frame b with boxes[b] (d3f_paste_resize_cubic_boxes_u8 and its
+    _color form; one launch per 64 frames)."""
+    if (box is None) == (boxes is None):
+        raise ValueError("paste_resize_cubic_u8: exactly one of box= and boxes=")
     if (patch.dtype != torch.uint8 or patch.shape[-1] != 3 or patch.dim() not in (3, 4) or frames.dtype != torch.uint8
             or frames.shape[-1] != 3 or frames.dim() != patch.dim()):
         raise ValueError("paste_resize_cubic_u8 expects a uint8 patch [H, W, 3] and frames [h, w, 3], or a batch of both")
@@ -867,7 +984,11 @@ def paste_resize_cubic_u8(patch, frames, box, feather=0, out=None, color=None):
             or (B > 1 and p.stride(0) != H * p.stride(1))):
         raise ValueError(f"patch must be a uint8 tensor [{B}, H, W, 3] on the frames' device with packed pixels and frames "
                          f"H rows apart")
-    x1, y1, cw, ch = [int(v) for v in box]
+    if boxes is not None:
+        table, _ = _boxes_arg(boxes, B, "paste_resize_cubic_u8")
+        geo = (table,)
+    else:
+        geo = tuple(int(v) for v in box)
     if in_place:
         o = f
     elif out is None:
@@ -876,16 +997,17 @@ def paste_resize_cubic_u8(patch, frames, box, feather=0, out=None, color=None):
         o = out.unsqueeze(0) if single and out.dim() == 3 else out
         if tuple(o.shape) != tuple(f.shape) or o.dtype != torch.uint8 or o.device != dev or not o.is_contiguous():
             raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(frames.shape)} on the frames' device")
+    L = _lib.lib()
     if color is None:
-        check(_lib.lib().d3f_paste_resize_cubic_u8(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, x1, y1, cw, ch, int(feather),
-                                                   ptr(o), stream_ptr()))
+        paste = L.d3f_paste_resize_cubic_u8 if boxes is None else L.d3f_paste_resize_cubic_boxes_u8
+        check(paste(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, *geo, int(feather), ptr(o), stream_ptr()))
         return o[0] if single else o
     coef = color.unsqueeze(0) if single and color.dim() == 2 else color
     if tuple(coef.shape) != (B, 3, 2) or coef.dtype != torch.float32 or coef.device != dev:
         raise ValueError(f"color must be a float32 tensor of shape {(B, 3, 2)} on the frames' device")
     coef = coef.contiguous()
-    check(_lib.lib().d3f_paste_resize_cubic_color_u8(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, x1, y1, cw, ch, int(feather),
-                                                     ptr(coef), ptr(o), stream_ptr()))
+    paste = L.d3f_paste_resize_cubic_color_u8 if boxes is None else L.d3f_paste_resize_cubic_color_boxes_u8
+    check(paste(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, *geo, int(feather), ptr(coef), ptr(o), stream_ptr()))
     return o[0] if single else o
 
 

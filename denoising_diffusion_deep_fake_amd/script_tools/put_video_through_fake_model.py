@@ -3,15 +3,20 @@
 predicts and concatenates on the host; here all of that is one device call per batch of frames
 (LitModule.predict_fake_frames -> Unet.predict_frames_u8), and cv2 only decodes and encodes.
 --output full writes the swapped video instead: the source's frames at their own size with the fake pasted back into
-the centre-crop box (LitModule.predict_fake_frames_full -> Unet.predict_frames_full_u8), still one device call per batch."""
+the centre-crop box (LitModule.predict_fake_frames_full -> Unet.predict_frames_full_u8), still one device call per batch.
+--track FILE follows a detector's per-frame face boxes instead of the centre crop (ops.read_box_track, ops.track_crop_box):
+every frame is cropped, and with --output full pasted, at its own box; video_to_center_cropped_images cuts the training
+images from the same track the same way."""
 import argparse
 import datetime
 from contextlib import ExitStack, nullcontext
 from pathlib import Path
 
+from .. import ops
 from .._lib import TEMPORAL_STRENGTH, TEMPORAL_THRESHOLD, temporal_setting
 from ..train_deep_fake.lit_module import LitModule
-from .video_writer_context_manager import VideoWriter, batches, import_cv2, open_video_as_generator, video_fps
+from .video_writer_context_manager import (VideoWriter, add_track_arguments, batches, check_track_arguments, import_cv2,
+                                           load_track, open_video_as_generator, track_setting, video_fps)
 
 
 def main():
@@ -31,6 +36,9 @@ def main():
         color_match=args.color_match,
         temporal=args.temporal,
         temporal_threshold=args.temporal_threshold,
+        track=args.track,
+        track_margin=args.track_margin,
+        track_smooth=args.track_smooth,
         )
 
 
@@ -69,7 +77,10 @@ def parse_command_line_arguments(argv=None):
                         help="--temporal: mean absolute change of the crop, in levels per sample over a pixel's 3 x 3 "
                              f"surroundings, from which a pixel counts as moving (1..255, default {TEMPORAL_THRESHOLD})")
 
+    add_track_arguments(parser)
+
     args = parser.parse_args(argv)
+    check_track_arguments(parser, args)
     if args.temporal_threshold is not None and args.temporal is None:
         parser.error("--temporal-threshold needs --temporal")
     try:
@@ -91,11 +102,16 @@ class RenderFakeVideo():
     color_match="meanstd" (output="full" only): the fake's mean and standard deviation are matched to those of the crop it
     replaces, per frame and channel, before the paste; None / "none": the fake is pasted as the network made it.
     temporal=STRENGTH (either output; temporal_threshold=N with it): the fake is filtered against flicker along the video
-    (`Unet.predict_frames_u8`, temporal=); the model's filter state is reset once, before the first batch."""
+    (`Unet.predict_frames_u8`, temporal=); the model's filter state is reset once, before the first batch.
+    track=FILE (or a list of (x, y, w, h) boxes; track_margin=M, track_smooth=N with it): frame k is cropped, and with
+    output="full" pasted, at `ops.track_crop_box` of the track's entry k instead of the centre box; the frame counter runs
+    across batches, and the padding frames of a short last batch repeat the last real frame's box.  output="full" without
+    feather= takes `ops.default_feather` of the smallest box of the whole track once, so the ramp does not change from
+    batch to batch.  A tracked call runs eager (`Unet.predict_frames_u8`, boxes=)."""
 
     def __init__(self, video_path, checkpoint_path, model_a_or_b, image_width, image_height, batch_frames=1,
                  frames=None, sink=None, model=None, output="pair", feather=None, antialias=False, color_match=None,
-                 temporal=None, temporal_threshold=None):
+                 temporal=None, temporal_threshold=None, track=None, track_margin=None, track_smooth=None):
 
         self.video_path = Path(video_path)
         self.checkpoint_path = Path(checkpoint_path) if checkpoint_path is not None else None
@@ -119,6 +135,9 @@ class RenderFakeVideo():
             raise ValueError("temporal_threshold needs temporal")
         strength, threshold = temporal_setting(temporal, temporal_threshold)
         self.temporal = None if temporal is None or strength == 0.0 else (strength, threshold)
+        self.track_margin, track_smooth = track_setting(track, track_margin, track_smooth)
+        self.track = None if track is None else load_track(track, self.track_margin, track_smooth)
+        self.frame_index = 0  # of the next batch's first frame: the track is followed across batches
         self.frames = frames
         self.sink = sink
 
@@ -141,6 +160,22 @@ class RenderFakeVideo():
         model.eval()
         return model
 
+    def batch_boxes(self, batch, real_frames):
+        """the boxes [B][4] of a batch of frames, or None without a track; the padding frames repeat the last real frame's"""
+        if self.track is None:
+            return None
+        h, w = batch.shape[1:3]
+        boxes = ops.track_crop_boxes(self.track, self.frame_index, real_frames, h, w, self.image_width, self.image_height,
+                                     self.track_margin)
+        self.frame_index += real_frames
+        return boxes + [boxes[-1]] * (len(batch) - real_frames)
+
+    def track_feather(self, h, w):
+        """output="full" with a track and no feather=: `ops.default_feather` of the smallest box of the whole track"""
+        boxes = ops.track_crop_boxes(self.track, 0, len(self.track), h, w, self.image_width, self.image_height,
+                                     self.track_margin)
+        return ops.default_feather(min(b[2] for b in boxes), min(b[3] for b in boxes))
+
     def render_real_fake_video(self):
         w = 2 * self.image_width
         h = self.image_height
@@ -156,7 +191,8 @@ class RenderFakeVideo():
             for batch, real_frames in batches(frames, self.batch_frames):
                 real_and_fake = self.model.predict_fake_frames(batch, self.model_a_or_b, self.image_width,
                                                                self.image_height, antialias=self.antialias,
-                                                               temporal=self.temporal)
+                                                               temporal=self.temporal,
+                                                               boxes=self.batch_boxes(batch, real_frames))
                 for frame in real_and_fake[:real_frames]:  # the padding of a short last batch is dropped
                     write(frame)
 
@@ -165,15 +201,19 @@ class RenderFakeVideo():
 
         with ExitStack() as stack:
             write = self.sink
+            feather = self.feather
             for batch, real_frames in batches(frames, self.batch_frames):
+                if feather is None and self.track is not None:
+                    feather = self.track_feather(*batch.shape[1:3])
                 if write is None:  # the writer takes the source's size, read off the first frame
                     h, w = batch.shape[1:3]
                     write = stack.enter_context(VideoWriter(str(self.get_output_video_path("_full")), w, h,
                                                             self.get_input_video_properties())).write
                 full = self.model.predict_fake_frames_full(batch, self.model_a_or_b, self.image_width,
-                                                           self.image_height, feather=self.feather,
+                                                           self.image_height, feather=feather,
                                                            antialias=self.antialias, color_match=self.color_match,
-                                                           temporal=self.temporal)
+                                                           temporal=self.temporal,
+                                                           boxes=self.batch_boxes(batch, real_frames))
                 for frame in full[:real_frames]:  # the padding of a short last batch is dropped
                     write(frame)
 

@@ -1,13 +1,16 @@
 """Turn a video into centre-cropped, resized training images plus images.txt
 (d3f/script_tools/video_to_center_cropped_images.py).  Crop and bicubic resize run on the device in batches
-(ops.crop_resize_cubic_u8); JPEGs are written with PIL (BGR -> RGB), as dataset.image_dataset reads them."""
+(ops.crop_resize_cubic_u8); JPEGs are written with PIL (BGR -> RGB), as dataset.image_dataset reads them.
+--track FILE cuts every frame at the box of a detector's track instead (ops.track_crop_box), exactly the boxes
+put_video_through_fake_model --track crops and pastes at: the model then sees what it is later asked to replace."""
 import argparse
 from pathlib import Path
 
 import torch
 
 from .. import ops
-from .video_writer_context_manager import batches, import_cv2, open_video_as_generator
+from .video_writer_context_manager import (add_track_arguments, batches, check_track_arguments, import_cv2, load_track,
+                                           open_video_as_generator, track_setting)
 
 
 def main():
@@ -20,6 +23,9 @@ def main():
         args.height,
         batch_frames=args.batch_frames,
         antialias=args.antialias,
+        track=args.track,
+        track_margin=args.track_margin,
+        track_smooth=args.track_smooth,
         )
 
 
@@ -34,15 +40,21 @@ def parse_command_line_arguments(argv=None):
                         help="resize with the antialiased bicubic filter (Pillow's); use it when the crop is several times "
                              "the image size, and render videos through the trained model with the same flag")
 
-    return parser.parse_args(argv)
+    add_track_arguments(parser)
+
+    args = parser.parse_args(argv)
+    check_track_arguments(parser, args)
+    return args
 
 
 class VideoToImages():
     """frames=: an iterable of decoded BGR frames instead of the video file (cv2 is not needed then); the output folder
-    is still named after video_path.  antialias=True: ops.crop_resize_cubic_u8(..., antialias=True)"""
+    is still named after video_path.  antialias=True: ops.crop_resize_cubic_u8(..., antialias=True).
+    track=FILE (or a list of (x, y, w, h) boxes; track_margin=M, track_smooth=N with it): frame k is cut at
+    `ops.track_crop_box` of the track's entry k, the frame counter running across batches, as RenderFakeVideo(track=) does"""
 
     def __init__(self, video_path, image_width, image_height, batch_frames=16, frames=None, device="cuda",
-                 antialias=False):
+                 antialias=False, track=None, track_margin=None, track_smooth=None):
 
         self.video_path = Path(video_path)
         self.image_width = int(image_width)
@@ -53,6 +65,9 @@ class VideoToImages():
         self.frames = frames
         self.device = device
         self.antialias = bool(antialias)
+        self.track_margin, track_smooth = track_setting(track, track_margin, track_smooth)
+        self.track = None if track is None else load_track(track, self.track_margin, track_smooth)
+        self.frame_index = 0  # of the next batch's first frame: the track is followed across batches
 
         if frames is None:
             import_cv2()  # fail before the output folder is made
@@ -73,17 +88,26 @@ class VideoToImages():
         frames = self.frames if self.frames is not None else open_video_as_generator(self.video_path)
 
         for batch, real_frames in batches(frames, self.batch_frames):
-            resized = self.resize_frames(batch)
+            resized = self.resize_frames(batch, real_frames)
             for frame in resized[:real_frames]:
                 file_path_list.append(self.save_frame_to_disk(frame, len(file_path_list)))
 
         self.save_file_path_list(file_path_list)
 
-    def resize_frames(self, batch):
-        """[n, h, w, 3] host BGR frames -> [n, height, width, 3] host BGR frames, cropped at the centre and resized"""
+    def resize_frames(self, batch, real_frames=None):
+        """[n, h, w, 3] host BGR frames -> [n, height, width, 3] host BGR frames, cropped at the centre -- with a track, each
+        at its own box (the first real_frames of the batch are frames of the video, the rest padding) -- and resized"""
         dev = torch.from_numpy(batch).to(self.device)
-        return ops.crop_resize_cubic_u8(dev, (self.image_height, self.image_width),
-                                        antialias=self.antialias).cpu().numpy()
+        boxes = None
+        if self.track is not None:
+            real = len(batch) if real_frames is None else real_frames
+            h, w = batch.shape[1:3]
+            boxes = ops.track_crop_boxes(self.track, self.frame_index, real, h, w, self.image_width, self.image_height,
+                                         self.track_margin)
+            self.frame_index += real
+            boxes += [boxes[-1]] * (len(batch) - real)
+        return ops.crop_resize_cubic_u8(dev, (self.image_height, self.image_width), antialias=self.antialias,
+                                        boxes=boxes).cpu().numpy()
 
     def save_frame_to_disk(self, frame, frame_index):
         from PIL import Image

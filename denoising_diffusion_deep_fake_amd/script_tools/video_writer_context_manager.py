@@ -1,6 +1,9 @@
 """cv2.VideoWriter as a context manager (d3f/script_tools/video_writer_context_manager.py) and the matching reader.
 cv2 is imported only when a file is opened: the frame path itself runs without it through the `frames=` / `sink=` hooks
 of RenderFakeVideo and VideoToImages."""
+from pathlib import Path
+
+from .. import ops
 
 NO_CV2 = ("OpenCV (cv2) is not installed, and it is only needed to decode / encode video files: pass decoded BGR frames "
           "through the frames= hook (an iterable of [h, w, 3] uint8 arrays) and take the output frames through the "
@@ -70,3 +73,46 @@ def batches(frames, n):
         real = len(chunk)
         chunk += [chunk[-1]] * (n - real)
         yield np.stack(chunk), real
+
+
+# ---- --track: the three flags of both tools that cut crops from a video ----
+def add_track_arguments(parser):
+    """--track, --track-margin, --track-smooth: the same three flags on both tools that cut crops from a video"""
+    parser.add_argument("--track", default=None, metavar="FILE",
+                        help="follow a detector's face boxes instead of the centre crop: a text file, line k for frame k, "
+                             "`x y w h` in pixels (blanks or commas), `-` for no detection, # comments")
+    parser.add_argument("--track-margin", type=float, default=None, metavar="M",
+                        help=f"--track: the crop is M times the face box (default {ops.TRACK_MARGIN})")
+    parser.add_argument("--track-smooth", type=int, default=None, metavar="N",
+                        help="--track: average the track over 2 N + 1 frames against detector jitter (default 0: off)")
+
+
+def check_track_arguments(parser, args):
+    try:
+        track_setting(args.track, args.track_margin, args.track_smooth)
+    except ValueError as e:
+        parser.error(str(e))
+
+
+def track_setting(track, margin, smooth):
+    """the three track arguments, checked -> (margin, smooth) with the defaults filled in"""
+    if track is None:
+        if margin is not None:
+            raise ValueError("--track-margin needs --track")
+        if smooth is not None:
+            raise ValueError("--track-smooth needs --track")
+    margin = ops.TRACK_MARGIN if margin is None else float(margin)
+    smooth = 0 if smooth is None else int(smooth)
+    if not margin > 0:
+        raise ValueError(f"--track-margin {margin} is not positive")
+    if smooth < 0:
+        raise ValueError(f"--track-smooth {smooth} is negative")
+    return margin, smooth
+
+
+def load_track(track, margin, smooth):
+    """track: a track file's path, or the boxes themselves (a list of (x, y, w, h)) -> the smoothed track"""
+    faces = ops.read_box_track(track) if isinstance(track, (str, Path)) else [tuple(int(v) for v in f) for f in track]
+    if not faces:
+        raise ValueError("track: no detection in the track")
+    return ops.smooth_box_track(faces, smooth)

@@ -449,7 +449,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
 
     # ---- raw frames to real|fake frames (script_tools/put_video_through_fake_model.py:111-119, 68) ----
     @torch.no_grad()
-    def predict_fake_frames(self, raw_bgr_batch, model_a_or_b, width, height, antialias=False, temporal=None):
+    def predict_fake_frames(self, raw_bgr_batch, model_a_or_b, width, height, antialias=False, temporal=None, boxes=None):
         """host frames [B, h, w, 3] (uint8 BGR, any size) -> host real|fake frames [B, height, 2 * width, 3]: centre crop,
         bicubic resize, `predict_fake` and the side-by-side concatenate of the reference's frame loop in one device call
         (`Unet.predict_frames_u8`).  Mean / std as in `predict_fake`: a model is fed the other domain's statistics.
@@ -457,7 +457,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         antialias=True: the antialiased bicubic resize (`ops.crop_resize_cubic_u8(..., antialias=True)`) -- prepare the
         training images the same way.  temporal: None, a strength or (strength, threshold), as `Unet.predict_frames_u8`: the
         fake half filtered against flicker; successive calls are then consecutive in time (`reset_frame_temporal` starts a
-        new sequence)."""
+        new sequence).  boxes: None (the centre crop), one box or a box per frame [B][4], as `Unet.predict_frames_u8`."""
         model, mean, std, raw = self._frame_path_inputs(raw_bgr_batch, model_a_or_b, "predict_fake_frames")
         width, height = int(width), int(height)
         key = (raw.shape, id(model), width, height)
@@ -475,7 +475,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         host_in.copy_(torch.from_numpy(raw))
         dev_in.copy_(host_in, non_blocking=True)
         model.predict_frames_u8(dev_in, (height, width), mean, std, graph=bool(self.hparams.get("inference_graph", False)),
-                                out=dev_out, antialias=antialias, temporal=temporal)
+                                out=dev_out, antialias=antialias, temporal=temporal, boxes=boxes)
         host_out.copy_(dev_out, non_blocking=True)
         torch.cuda.current_stream().synchronize()
         return host_out.numpy().copy()
@@ -514,7 +514,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
 
     @torch.no_grad()
     def predict_fake_frames_full(self, raw_bgr_batch, model_a_or_b, width, height, feather=None, with_pair=False,
-                                 antialias=False, color_match=None, temporal=None):
+                                 antialias=False, color_match=None, temporal=None, boxes=None):
         """host frames [B, h, w, 3] (uint8 BGR, any size) -> host frames of the same shape with the centre-crop box replaced
         by the fake, resized back to the box and blended in over `feather` source pixels (None: `ops.default_feather`):
         the swapped video at the source's size, in one device call (`Unet.predict_frames_full_u8`).  with_pair: returns
@@ -522,7 +522,8 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         pinned and device staging is kept per shape in a cache of its own.  antialias: as `predict_fake_frames` (the
         crop-to-network resize only).  color_match: None / "none" / "meanstd", as `Unet.predict_frames_full_u8`: the fake's
         colour statistics matched to the crop it replaces before the paste; the pair is the same either way.  temporal: as
-        `predict_fake_frames`; the pair then holds the filtered fake, and with color_match the coefficients are smoothed."""
+        `predict_fake_frames`; the pair then holds the filtered fake, and with color_match the coefficients are smoothed.
+        boxes: as `predict_fake_frames`; every frame's fake goes back into its own box (`Unet.predict_frames_full_u8`)."""
         model, mean, std, raw = self._frame_path_inputs(raw_bgr_batch, model_a_or_b, "predict_fake_frames_full")
         width, height = int(width), int(height)
         if not hasattr(self, "_frames_full_buffers"):
@@ -536,7 +537,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         model.predict_frames_full_u8(dev_in, (height, width), mean, std, feather=feather,
                                      graph=bool(self.hparams.get("inference_graph", False)), out=dev_full,
                                      pair_out=dev_pair, antialias=antialias, color_match=color_match,
-                                     temporal=temporal)
+                                     temporal=temporal, boxes=boxes)
         host_full.copy_(dev_full, non_blocking=True)
         if with_pair:
             host_pair.copy_(dev_pair, non_blocking=True)

@@ -836,10 +836,11 @@ class Unet(nn.Module, _NetsRuntime):
         self._pack_if_needed(eng)
         return eng
 
-    def _frame_inputs(self, who, raw_bgr, size, pair, pair_name, in_place=False):
+    def _frame_inputs(self, who, raw_bgr, size, pair, pair_name, in_place=False, boxes=None):
         """what the two raw-frame entries do before their C call -> (contiguous frames [B, h, w, 3], single, the call's
-        geometry (h, w, x1, y1, cw, ch) with the centre-crop box, the plan, the pair buffer [B, H, 2W, 3]: `pair`, checked, or
-        a new one)"""
+        geometry, the plan, the pair buffer [B, H, 2W, 3]: `pair`, checked, or a new one, the call's boxes as a list).
+        The geometry is (h, w, x1, y1, cw, ch) -- the centre-crop box for boxes=None, or the one box boxes names with 4
+        integers -- or, for boxes [B][4], (h, w, table) with the host int32 table the boxes entries take."""
         from . import ops
         x, single = self._u8_batch(raw_bgr, who, "h, w")
         if in_place and not x.is_contiguous():
@@ -848,14 +849,26 @@ class Unet(nn.Module, _NetsRuntime):
         B, h, w, _ = x.shape
         H, W = int(size[0]), int(size[1])
         self._check_u8_size(H, W)
-        geo = (h, w) + tuple(ops.center_crop_box(h, w, W, H))
+        if boxes is None:
+            rows = [tuple(ops.center_crop_box(h, w, W, H))]
+            geo = (h, w) + rows[0]
+        else:
+            if isinstance(boxes, torch.Tensor):
+                boxes = boxes.tolist()
+            boxes = list(boxes)
+            if len(boxes) == 4 and not any(hasattr(v, "__len__") for v in boxes):  # one box for every frame
+                rows = [tuple(int(v) for v in boxes)]
+                geo = (h, w) + rows[0]
+            else:
+                table, rows = ops._boxes_arg(boxes, B, who)
+                geo = (h, w, table)
         eng = self._u8_engine(B, H, W, x.device)
         shape = (B, H, 2 * W, 3)
         if pair is None:
             pair = torch.empty(shape, dtype=torch.uint8, device=x.device)
         elif tuple(pair.shape) != shape or pair.dtype != torch.uint8 or not pair.is_contiguous() or pair.device != x.device:
             raise ValueError(f"{pair_name} must be a contiguous uint8 tensor of shape {shape} on the input's device")
-        return x, single, geo, eng, pair
+        return x, single, geo, eng, pair, rows
 
     @staticmethod
     def _apply_frame_settings(eng, antialias, color, temporal):
@@ -878,7 +891,8 @@ class Unet(nn.Module, _NetsRuntime):
                 check(_lib.lib().d3f_unet_frame_temporal_reset(eng.h, stream_ptr()))
 
     @torch.no_grad()
-    def predict_frames_u8(self, raw_bgr, size, mean, std, graph=True, out=None, antialias=False, temporal=None):
+    def predict_frames_u8(self, raw_bgr, size, mean, std, graph=True, out=None, antialias=False, temporal=None,
+                          boxes=None):
         """The frame path of d3f/script_tools/put_video_through_fake_model.py:111-119, 68 on decoded frames of any
         size: uint8 BGR frames [h,w,3] or [B,h,w,3] on the HIP device -> centre crop to the aspect of size = (H, W)
         (`ops.center_crop_box`) -> bicubic resize (`ops.crop_resize_cubic_u8`) -> `predict_u8` -> the real|fake frames
@@ -890,20 +904,28 @@ class Unet(nn.Module, _NetsRuntime):
         temporal: None (off), a strength in (0, 1) or (strength, threshold): the fake half is filtered against flicker
         (`ops.temporal_filter_u8` with real = the left half, fake = the right half; d3f_unet_set_frame_temporal).  The
         frames of successive calls are then consecutive in time, the state lives with the plan of this batch size and
-        network size, `reset_frame_temporal()` starts a new sequence, and a change of the values starts one too."""
+        network size, `reset_frame_temporal()` starts a new sequence, and a change of the values starts one too.
+        boxes: None is the centre crop.  One box (x1, y1, cw, ch) is that box for every frame, through the same C entry, with
+        `graph=` honoured (the box is part of the graph's key).  [B][4] integers in host memory are a box per frame -- a
+        face that moves (`ops.track_crop_box`) -- through d3f_unet_predict_frames_boxes_u8: still one C call, the left half
+        byte for byte `ops.crop_resize_cubic_u8(..., boxes=)`, and it runs EAGER whatever `graph=` says: a captured launch
+        bakes the boxes in, so a moving box would re-capture on every call.  The temporal filter reads the resized crop: a
+        box that moves is motion to it."""
         temporal = _lib.temporal_setting(temporal)
-        x, single, geo, eng, out = self._frame_inputs("predict_frames_u8", raw_bgr, size, out, "out")
+        x, single, geo, eng, out, _ = self._frame_inputs("predict_frames_u8", raw_bgr, size, out, "out", boxes=boxes)
         rt = self._rt
         self._apply_frame_settings(eng, antialias, None, temporal)
-        check(_lib.lib().d3f_unet_predict_frames_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), *geo, ptr(out),
-                                                    _float3(mean), _float3(std), ptr(eng.workspace), 1 if graph else 0,
-                                                    stream_ptr()))
+        L = _lib.lib()
+        per_frame = len(geo) == 3
+        entry = L.d3f_unet_predict_frames_boxes_u8 if per_frame else L.d3f_unet_predict_frames_u8
+        check(entry(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), *geo, ptr(out), _float3(mean), _float3(std),
+                    ptr(eng.workspace), 1 if graph and not per_frame else 0, stream_ptr()))
         eng.keep = (x, out)  # the captured graph bakes these pointers in: keep them alive with the engine
         return out[0] if single else out
 
     @torch.no_grad()
     def predict_frames_full_u8(self, raw_bgr, size, mean, std, feather=None, graph=True, out=None, pair_out=None,
-                               antialias=False, color_match=None, temporal=None):
+                               antialias=False, color_match=None, temporal=None, boxes=None):
         """`predict_frames_u8`, then the fake pasted back into the source frames: uint8 BGR frames [h,w,3] or [B,h,w,3] on
         the HIP device -> the frames at their own size with the centre-crop box replaced by the fake, resized back
         (`ops.paste_resize_cubic_u8`) and blended in over `feather` source pixels (None: `ops.default_feather` of the
@@ -916,14 +938,19 @@ class Unet(nn.Module, _NetsRuntime):
         `ops.color_match_coef`, `ops.paste_resize_cubic_u8(..., color=)`, still in the one C call; the handle's
         D3F_COLOR_MEANSTD mode).  pair_out is not touched by it; a change between calls re-captures the graph.
         temporal: as `predict_frames_u8` -- the fake half of pair_out is filtered before the sums and the paste read it,
-        and with color_match="meanstd" the coefficients are smoothed across frames too (`ops.color_coef_smooth`)."""
+        and with color_match="meanstd" the coefficients are smoothed across frames too (`ops.color_coef_smooth`).
+        boxes: as `predict_frames_u8` -- None, one box (the same C entry, `graph=` honoured) or [B][4], a box per frame
+        (d3f_unet_predict_frames_full_boxes_u8: eager whatever `graph=` says); every frame's fake is pasted into its own
+        box, with one feather for the call: None is `ops.default_feather(min cw, min ch)` over the call's boxes."""
         from . import ops
         color_code = _lib.color_match_mode(color_match)
         temporal = _lib.temporal_setting(temporal)
         in_place = out is raw_bgr
-        x, single, geo, eng, pair_out = self._frame_inputs("predict_frames_full_u8", raw_bgr, size, pair_out, "pair_out",
-                                                           in_place)
-        feather = ops.default_feather(*geo[4:]) if feather is None else int(feather)
+        x, single, geo, eng, pair_out, rows = self._frame_inputs("predict_frames_full_u8", raw_bgr, size, pair_out,
+                                                                 "pair_out", in_place, boxes=boxes)
+        if feather is None:
+            feather = ops.default_feather(min(row[2] for row in rows), min(row[3] for row in rows))
+        feather = int(feather)
         if in_place:
             full = x
         elif out is None:
@@ -935,9 +962,11 @@ class Unet(nn.Module, _NetsRuntime):
                 raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(raw_bgr.shape)} on the input's device")
         rt = self._rt
         self._apply_frame_settings(eng, antialias, color_code, temporal)
-        check(_lib.lib().d3f_unet_predict_frames_full_u8(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), *geo, feather,
-                                                         ptr(pair_out), ptr(full), _float3(mean), _float3(std),
-                                                         ptr(eng.workspace), 1 if graph else 0, stream_ptr()))
+        L = _lib.lib()
+        per_frame = len(geo) == 3
+        entry = L.d3f_unet_predict_frames_full_boxes_u8 if per_frame else L.d3f_unet_predict_frames_full_u8
+        check(entry(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), *geo, feather, ptr(pair_out), ptr(full),
+                    _float3(mean), _float3(std), ptr(eng.workspace), 1 if graph and not per_frame else 0, stream_ptr()))
         eng.keep_full = (x, pair_out, full)  # the captured graph bakes these pointers in: keep them alive with the engine
         return full[0] if single else full
 

@@ -198,6 +198,24 @@ int d3f_unet_predict_frames_full_u8(d3f_unet_t h, const float* params, float* bn
                                     int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* pair_out,
                                     uint8_t* full_out, const float mean[3], const float std[3], void* workspace,
                                     int use_graph, void* stream);
+/* The two frame entries with a box per frame (a face that moves through the frames): the signatures above with boxes in
+ * place of x1, y1, cw, ch -- HOST memory, [B][4] int32 as x1, y1, cw, ch of frame b, B the handle's batch size, read before
+ * the call returns.  The same launch sequence with the crop and the paste in their boxes forms
+ * (d3f_crop_resize_cubic_boxes_u8 / _aa_boxes_u8, d3f_paste_resize_cubic_boxes_u8 / _color_boxes_u8 below): pair_out and
+ * full_out are byte for byte the composition of those operators, as the single-box entries are of theirs, and every frame
+ * setting (resample, colour match, temporal filter) applies unchanged -- they work on pair_out, where a box is no longer
+ * seen.  (The temporal filter's gate reads the resized real crop: a box that moves is motion to it.)  One feather for the
+ * call.  use_graph != 0 is REFUSED: a captured launch bakes its kernel arguments in, the boxes among them, and a graph keyed
+ * on their values would be re-captured on every call of a moving box; replay needs the boxes in device memory, which these
+ * entries do not have.  Refused before any device call besides: what the single-box entries refuse, a null boxes, and for
+ * any frame what the boxes operators refuse of its box, with the frame's index in the message. */
+int d3f_unet_predict_frames_boxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
+                                     int src_w, const int32_t* boxes, uint8_t* pair_out, const float mean[3],
+                                     const float std[3], void* workspace, int use_graph, void* stream);
+int d3f_unet_predict_frames_full_boxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in,
+                                          int src_h, int src_w, const int32_t* boxes, int feather, uint8_t* pair_out,
+                                          uint8_t* full_out, const float mean[3], const float std[3], void* workspace,
+                                          int use_graph, void* stream);
 /* How d3f_unet_predict_frames_u8 and d3f_unet_predict_frames_full_u8 resize the crop box to the handle's H x W:
  *   D3F_RESAMPLE_CUBIC     d3f_crop_resize_cubic_u8 (cv2.INTER_CUBIC: four taps per axis whatever the scale).  The default
  *                          after d3f_unet_create; its launches are exactly those of a handle that never heard of the setting.
@@ -594,6 +612,35 @@ int d3f_color_match_coef(const uint64_t* sums_from, const uint64_t* sums_to, int
 int d3f_paste_resize_cubic_color_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
                                     const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather,
                                     const float* coef, uint8_t* out, void* stream);
+
+/* A box per frame: a face that moves through the frames.  Each of the four operators below is the signature of its single-box
+ * operator with x1, y1, cw, ch replaced by boxes: HOST memory, [B][4] int32 as x1, y1, cw, ch of frame b, read before the call
+ * returns (the caller may free or change it then).  Definition by reference: frame b of the result is byte for byte what the
+ * single-box operator gives on frame b alone (B = 1) with box b -- the same device functions run on the same operands; the
+ * per-frame form is still one device call.  The boxes travel by value in the kernels' arguments, D3F_FRAME_BOXES_MAX of them
+ * (1 KB) per launch: there is no device copy of them and no device-side read of a box that was not checked; a call with more
+ * frames is several launches of at most D3F_FRAME_BOXES_MAX frames, enqueued in order.  The paste keeps ONE feather for the
+ * call.  Refused before any device call: a null boxes with B > 0; for ANY frame, whatever the single-box operator refuses of
+ * one box -- a non-positive extent, a box outside the frame, for the antialiased form an extent above 32 times the output's
+ * -- with the frame's index in the message; and whatever else the single-box operator refuses (pointers, sizes, strides,
+ * overlaps, feather). */
+#define D3F_FRAME_BOXES_MAX 64
+/* d3f_crop_resize_cubic_u8 with boxes */
+int d3f_crop_resize_cubic_boxes_u8(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst, int H,
+                                   int W, int64_t dst_row_stride_bytes, void* stream);
+/* d3f_crop_resize_cubic_aa_u8 with boxes */
+int d3f_crop_resize_cubic_aa_boxes_u8(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
+                                      int H, int W, int64_t dst_row_stride_bytes, void* stream);
+/* d3f_paste_resize_cubic_u8 with boxes.  out == frame runs in place: of every frame only the tiles that meet ITS box are
+ * written (one grid for the launch, the largest tile count of any of its frames; a frame's workgroups past its own count
+ * return at once), so bytes outside a frame's own box stay untouched. */
+int d3f_paste_resize_cubic_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                    const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
+                                    uint8_t* out, void* stream);
+/* d3f_paste_resize_cubic_color_u8 with boxes (coef [B][3][2] stays device memory) */
+int d3f_paste_resize_cubic_color_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                          const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
+                                          const float* coef, uint8_t* out, void* stream);
 
 /* Temporal filter against flicker in the fake video, in two operators.  The definitions are the acceptance contract;
  * tests/temporal_restatement.py restates them in numpy float32 and int64, and every comparison is exact.  All fp32 arithmetic

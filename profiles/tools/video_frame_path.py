@@ -34,10 +34,17 @@
                  entries (an older build named through D3F_LIB), only the temporal=None forms run: the parent's figures for
                  the same launches, in the same sequence of allocations and captures
 
+  --boxes      : instead of the above, the tracked crop: the per-frame-box forms with ALL boxes equal to the centre box next
+                 to the single-box forms on the same inputs -- the crop alone (plain; out=), the paste alone (out of place,
+                 default feather) and the whole Unet.predict_frames_full_u8 call, eager; and the single-box call's hipGraph
+                 replay at B = 1, which a tracked call gives up: 1080x1920 -> 448x448 and 256x256, B = 1 and B = 8.  On a
+                 library without the boxes entries (the parent's build named through D3F_LIB), or with --off-only, only the
+                 single-box forms run: the same sequence of calls on both sides of an A/B of the unchanged path
+
 Back-to-back enqueues on one stream, ITERS iterations after WARMUP, the forms alternating in ROUNDS rounds; the figure is
 the median round's time per call (and per frame).  Host work of the reference's loop (cv2.resize on one CPU thread, the
 concatenate, two PCIe trips) is not part of any figure here.  One JSON line at the end.
-    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N] [--antialias | --color [--off-only] | --temporal [--off-only]]
+    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N] [--antialias | --color [--off-only] | --temporal [--off-only] | --boxes [--off-only]]
 """
 import argparse
 import json
@@ -217,13 +224,60 @@ def temporal_section(args, g):
     print(json.dumps(result))
 
 
+def boxes_section(args, g):
+    """the per-frame-box forms (every box the centre box) against the single-box forms, per frame; one JSON line"""
+    has_boxes = hasattr(_lib.lib(), "d3f_unet_predict_frames_full_boxes_u8") and not args.off_only
+    result = {"precision": args.precision, "digest": _lib.built_digest(), "iters": args.iters, "rounds": args.rounds,
+              "has_boxes": has_boxes, "boxes_us_per_frame": {}}
+    torch.manual_seed(0)
+    net = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
+    for side in (448, 256):
+        size = (side, side)
+        box = ops.center_crop_box(RAW[0], RAW[1], side, side)
+        feather = ops.default_feather(box[2], box[3])
+        for B in (1, 8):
+            raw = torch.randint(0, 256, (B,) + RAW + (3,), generator=g, dtype=torch.uint8).cuda()
+            small = ops.crop_resize_cubic_u8(raw, size)
+            resized = torch.empty_like(small)
+            bufs = {k: (torch.empty_like(raw), torch.empty((B, side, 2 * side, 3), dtype=torch.uint8, device="cuda"))
+                    for k in ("e", "g", "b")}
+            full = torch.empty_like(raw)
+            many = [box] * B
+            forms = {
+                "crop_box": lambda: ops.crop_resize_cubic_u8(raw, size, box=box, out=resized),
+                "paste_box": lambda: ops.paste_resize_cubic_u8(small, raw, box, feather, out=full),
+                "full_box_eager": lambda: net.predict_frames_full_u8(raw, size, MEAN, STD, feather=feather, graph=False,
+                                                                     out=bufs["e"][0], pair_out=bufs["e"][1]),
+            }
+            if B == 1:
+                forms["full_box_graph"] = lambda: net.predict_frames_full_u8(raw, size, MEAN, STD, feather=feather, graph=True,
+                                                                             out=bufs["g"][0], pair_out=bufs["g"][1])
+            if has_boxes:
+                forms.update({
+                    "crop_boxes": lambda: ops.crop_resize_cubic_u8(raw, size, boxes=many, out=resized),
+                    "paste_boxes": lambda: ops.paste_resize_cubic_u8(small, raw, boxes=many, feather=feather, out=full),
+                    "full_boxes_eager": lambda: net.predict_frames_full_u8(raw, size, MEAN, STD, feather=feather, boxes=many,
+                                                                           out=bufs["b"][0], pair_out=bufs["b"][1]),
+                })
+            t = compare(forms, args.warmup, args.iters, args.rounds)
+            key = f"{RAW[0]}x{RAW[1]}_to_{side}_B{B}"
+            row = {}
+            for name, (med, lo, hi) in t.items():
+                print(f"{key:24s} {name:18s} {med / B:9.2f} us per frame (min {lo / B:.2f}, max {hi / B:.2f})")
+                row[name] = [round(med / B, 2), round(lo / B, 2), round(hi / B, 2)]
+            result["boxes_us_per_frame"][key] = row
+            del raw, bufs, full
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--antialias", action="store_true", help="measure the antialiased resize instead (see above)")
     ap.add_argument("--color", action="store_true", help="measure the colour match of the full-frame output instead (see above)")
     ap.add_argument("--temporal", action="store_true", help="measure the temporal filter of the frame entries instead (see above)")
+    ap.add_argument("--boxes", action="store_true", help="measure the per-frame-box forms against the single-box ones instead (see above)")
     ap.add_argument("--off-only", action="store_true",
-                    help="--color / --temporal: only the forms without the mode, as on a library without its entries -- the same "
+                    help="--color / --temporal / --boxes: only the forms without the mode, as on a library without its entries -- the same "
                          "sequence of allocations and captures on both sides of an A/B of the unchanged path")
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--iters", type=int, default=100)
@@ -236,6 +290,8 @@ def main():
         return color_section(args, torch.Generator().manual_seed(1))
     if args.temporal:
         return temporal_section(args, torch.Generator().manual_seed(1))
+    if args.boxes:
+        return boxes_section(args, torch.Generator().manual_seed(1))
     torch.manual_seed(0)
     net = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
     g = torch.Generator().manual_seed(1)
