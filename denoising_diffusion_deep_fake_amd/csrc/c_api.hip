@@ -883,6 +883,30 @@ int d3f_temporal_flag_set(int32_t* flag, int value, void* stream) {
   return temporal_flag_set_launch(flag, value, (hipStream_t)stream);
 }
 
+int d3f_gray_decimate_u8(const uint8_t* frames, int B, int h, int w, int s, uint8_t* out, void* stream) {
+  D3F_CHECK(frames && out, "gray_decimate_u8: null argument");
+  return gray_decimate_u8_launch(frames, B, h, w, s, out, (hipStream_t)stream);
+}
+
+int d3f_track_seed_u8(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, uint8_t* templ, int32_t* pos,
+                      void* stream) {
+  D3F_CHECK(frame && templ && pos, "track_seed_u8: null argument");
+  return track_seed_u8_launch(frame, h, w, s, tx, ty, tw, th, templ, pos, (hipStream_t)stream);
+}
+
+int d3f_track_search_u8(const uint8_t* gray, int B, int gh, int gw, int tw, int th, int search, int adapt, int lost,
+                        uint8_t* templ, int32_t* pos, int32_t* out, void* stream) {
+  D3F_CHECK(gray && templ && pos && out, "track_search_u8: null argument");
+  return track_search_u8_launch(gray, B, gh, gw, tw, th, search, adapt, lost, templ, pos, out, (hipStream_t)stream);
+}
+
+int d3f_track_template_u8(const uint8_t* frames, int B, int h, int w, int s, int tw, int th, int search, int adapt, int lost,
+                          uint8_t* templ, int32_t* pos, uint8_t* gray_ws, int32_t* out, void* stream) {
+  D3F_CHECK(frames && templ && pos && gray_ws && out, "track_template_u8: null argument");
+  return track_template_u8_launch(frames, B, h, w, s, tw, th, search, adapt, lost, templ, pos, gray_ws, out,
+                                  (hipStream_t)stream);
+}
+
 int d3f_image_grid_shape(int images, int nrow, int padding, int H, int W, int32_t dims[2]) {
   D3F_CHECK(dims != nullptr, "image_grid_shape: null argument");
   return image_grid_shape(images, nrow, padding, H, W, dims);

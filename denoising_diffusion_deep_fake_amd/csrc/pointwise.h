@@ -213,6 +213,20 @@ int temporal_filter_u8_launch(const uint8_t* real, uint8_t* fake, int B, int H, 
 int color_coef_smooth_launch(float* coef, const uint64_t* sums_to, int parts, int B, long n, float strength, float* state_coef,
                              uint64_t* state_sum, int* state_valid, hipStream_t stream);
 
+// template tracker (track.hip; include/d3f_hip.h: d3f_gray_decimate_u8 .. d3f_track_template_u8).  Every range is refused on
+// the host before a launch; the two checks are what track_template_u8_launch asks before it enqueues either kernel.  T is
+// packed (th rows of tw bytes) in a buffer of 64 * 64 bytes, pos int32[2], out int32 [B][4].
+int gray_decimate_check(int B, int h, int w, int s);
+int gray_decimate_u8_launch(const uint8_t* frames, int B, int h, int w, int s, uint8_t* out, hipStream_t stream);
+int track_seed_u8_launch(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, uint8_t* templ, int* pos,
+                         hipStream_t stream);
+int track_search_check(int B, int gh, int gw, int tw, int th, int search, int adapt, int lost, const int* pos,
+                       const int* out);
+int track_search_u8_launch(const uint8_t* gray, int B, int gh, int gw, int tw, int th, int search, int adapt, int lost,
+                           uint8_t* templ, int* pos, int* out, hipStream_t stream);
+int track_template_u8_launch(const uint8_t* frames, int B, int h, int w, int s, int tw, int th, int search, int adapt,
+                             int lost, uint8_t* templ, int* pos, uint8_t* gray_ws, int* out, hipStream_t stream);
+
 // training image grids (image_grid.hip): make_grid + scale + clamp + uint8 of up to 8 fp32 NCHW batches in one launch;
 // `batches` is a host array of n device pointers, out [n][GH][GW][3] with {GH, GW} from image_grid_shape
 int image_grid_shape(int images, int nrow, int padding, int H, int W, int32_t dims[2]);

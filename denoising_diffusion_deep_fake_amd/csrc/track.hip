@@ -1,0 +1,365 @@
+// Template tracker (include/d3f_hip.h: d3f_gray_decimate_u8, d3f_track_seed_u8, d3f_track_search_u8, d3f_track_template_u8): a
+// face box marked by hand at a key frame is followed from frame to frame by the smallest sum of absolute differences of a
+// reduced grey template.  Everything is integer arithmetic -- exact, and the same in any order of evaluation;
+// tests/track_restatement.py restates it in numpy and Python integers.
+//
+// gray_decimate_kernel (the per-frame hot path: every byte of every frame once): a workgroup takes one row of the reduced
+// image and GD_THREADS of its columns, a lane one column.  The s source rows of the tile are staged in LDS, GD rows at a
+// time, as the aligned dwords that cover each row's 3 s tx bytes (byte k of a row's span sits at its dword alignment + k, as
+// temporal.hip stages its tiles; a dword is loaded whole only inside the frames' bytes, up to GD_ROWS * GD_UNROLL loads of a lane
+// in flight), so the global loads are whole dwords at consecutive addresses whatever the byte address of the row.  A lane
+// then reads the dwords that cover its 3 s bytes, rotates each pair into place (v_alignbyte_b32) and weights the bytes B G R
+// with 1 2 1 by position in the 12-byte group (three dwords are four pixels: three constant weight words, v_dot4_u32_u8); the
+// bytes of the last dword past the lane's span are masked.  The sum, at most 4 * 255 * 1024, stays in 32 bits.
+//
+// track_search_kernel: ONE workgroup for the whole call and the loop over the call's frames inside the kernel, as
+// temporal_filter_kernel has it: frame k starts where frame k - 1 ended.  The template lives in LDS for the call (rows 64
+// bytes apart, zero behind tw), the position in every lane's registers.  Per frame the clipped search window (at most
+// 192 x 192 bytes) is staged as aligned dwords, a row at whatever byte phase its address has; a lane takes four candidates
+// next to each other in dx and a part of the template's rows, and walks them a dword at a time -- three of the window's
+// dwords rotated into 64 bits at the row's phase, v_qsad_pk_u16_u8 against the template's dword (four sums of absolute
+// differences, the window at byte offsets 0..3), the last dword of a row with v_sad_u8 and a mask where tw is no multiple
+// of 4; the parts are added and the 64-bit keys reduced with shuffles and through LDS; every lane decodes the winner, the
+// lanes blend the template, lane 0 stores the output row.
+#include "../../include/d3f_hip.h"
+#include "common.h"
+#include "pointwise.h"
+
+namespace d3f {
+
+typedef unsigned long long u64;
+
+constexpr int TRACK_MAX_SIDE = D3F_TRACK_MAX_SIDE, TRACK_MAX_SEARCH = D3F_TRACK_MAX_SEARCH;
+constexpr int TRACK_MAX_STRIDE = D3F_TRACK_MAX_STRIDE, TRACK_MIN_SIDE = 4;
+static_assert(TRACK_MAX_SIDE == 64, "the template's LDS rows are 64 bytes; 255 * 64 * 64 < 2^20 is the key's cost field");
+static_assert(2 * TRACK_MAX_SEARCH < 256 && 2 * TRACK_MAX_SEARCH * TRACK_MAX_SEARCH < 65536, "the key's fields");
+
+constexpr int GD_THREADS = 256;  // columns of the reduced image a workgroup takes, one per lane
+constexpr int GD_UNROLL = 4;     // dwords of a row a lane loads at a time ...
+constexpr int GD_ROWS = 4;       // ... of so many rows: 16 loads in flight
+constexpr int GD_LDS_DW = 6400;  // staged dwords: one row of the widest tile (s = 32), four of s = 8
+static_assert((3 * TRACK_MAX_STRIDE * GD_THREADS + 6) / 4 + 1 <= GD_LDS_DW, "one staged row of the widest tile fits");
+
+// the aligned dword at p: whole where it lies inside [lo, hi), its bytes inside that range otherwise (the rest 0)
+__device__ __forceinline__ uint32_t track_load_dword(const uint8_t* p, const uint8_t* lo, const uint8_t* hi) {
+  if (p >= lo && p + 4 <= hi) return *reinterpret_cast<const uint32_t*>(p);
+  uint32_t v = 0;
+  for (int j = 0; j < 4; ++j)
+    if (p + j >= lo && p + j < hi) v |= (uint32_t)p[j] << (8 * j);
+  return v;
+}
+
+struct DecimateGeom {
+  int B, h, w, s, gh, gw;
+};
+
+__global__ __launch_bounds__(GD_THREADS) void gray_decimate_kernel(const uint8_t* __restrict__ frames, DecimateGeom g,
+                                                                  uint8_t* __restrict__ out) {
+  __shared__ uint32_t lds[GD_LDS_DW];
+  const int tid = threadIdx.x, X0 = blockIdx.x * GD_THREADS, gy = blockIdx.y, b = blockIdx.z;
+  const int tx = min(GD_THREADS, g.gw - X0);
+  const int span = 3 * g.s * tx;          // bytes of a source row under this tile
+  const int row_dw = (span + 6) / 4 + 1;  // up to 3 bytes of alignment in front, and the dword a lane's last rotation reads
+  const int R = min(g.s, GD_LDS_DW / row_dw);
+  const uint8_t* lo = frames;
+  const uint8_t* hi = frames + (long)g.B * g.h * g.w * 3;
+  const long pitch = 3L * g.w;
+  const uint8_t* seg0 = frames + ((long)b * g.h + (long)gy * g.s) * pitch + 3L * X0 * g.s;
+  const int lane_bytes = 3 * g.s, nd = (lane_bytes + 3) / 4;
+  uint32_t acc = 0;
+  for (int j0 = 0; j0 < g.s; j0 += R) {
+    const int rows = min(R, g.s - j0);
+    // GD_ROWS rows at a time, so that a lane has GD_ROWS * GD_UNROLL loads in flight before its first LDS store
+    for (int r0 = 0; r0 < rows; r0 += GD_ROWS) {
+      const uint8_t* first[GD_ROWS];  // row r0 + q: its first aligned dword, and how many hold bytes of the span
+      int need[GD_ROWS], need_max = 0;
+#pragma unroll
+      for (int q = 0; q < GD_ROWS; ++q) {
+        const uint8_t* seg = seg0 + (j0 + r0 + q) * pitch;
+        const int al = (int)(reinterpret_cast<uintptr_t>(seg) & 3);
+        first[q] = seg - al;
+        need[q] = r0 + q < rows ? (al + span + 3) / 4 : 0;
+        need_max = max(need_max, need[q]);
+      }
+      for (int k0 = tid; k0 < need_max; k0 += GD_UNROLL * GD_THREADS) {
+        uint32_t v[GD_ROWS][GD_UNROLL];
+#pragma unroll
+        for (int q = 0; q < GD_ROWS; ++q)
+#pragma unroll
+          for (int u = 0; u < GD_UNROLL; ++u) {
+            const int k = k0 + u * GD_THREADS;
+            v[q][u] = k < need[q] ? track_load_dword(first[q] + 4 * k, lo, hi) : 0u;
+          }
+#pragma unroll
+        for (int q = 0; q < GD_ROWS; ++q)
+#pragma unroll
+          for (int u = 0; u < GD_UNROLL; ++u) {
+            const int k = k0 + u * GD_THREADS;
+            if (k < need[q]) lds[(r0 + q) * row_dw + k] = v[q][u];
+          }
+      }
+    }
+    __syncthreads();
+    if (tid < tx) {
+      for (int r = 0; r < rows; ++r) {
+        const int al = (int)(reinterpret_cast<uintptr_t>(seg0 + (j0 + r) * pitch) & 3);
+        const int o = al + lane_bytes * tid, ph = o & 3;
+        const uint32_t* row = lds + r * row_dw + (o >> 2);
+        uint32_t d_lo = row[0];
+        int m3 = 0;  // m mod 3: the dword's place in its 12-byte group
+        for (int m = 0; m < nd; ++m) {
+          const uint32_t d_hi = row[m + 1];
+          uint32_t d = __builtin_amdgcn_alignbyte(d_hi, d_lo, ph);
+          const int left = lane_bytes - 4 * m;
+          if (left < 4) d &= (1u << (8 * left)) - 1u;
+          // B G R B | G R B G | R B G R, byte 0 lowest
+          const uint32_t weights = m3 == 0 ? 0x01010201u : (m3 == 1 ? 0x02010102u : 0x01020101u);
+          acc = __builtin_amdgcn_udot4(d, weights, acc, false);
+          m3 = m3 == 2 ? 0 : m3 + 1;
+          d_lo = d_hi;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (tid < tx) out[((long)b * g.gh + gy) * g.gw + X0 + tid] = (uint8_t)(acc / (uint32_t)(4 * g.s * g.s));
+}
+
+// The grey of the key box only: block j is row j of the template, lane i its sample i; T is packed, th rows of tw bytes.
+__global__ __launch_bounds__(64) void track_seed_kernel(const uint8_t* __restrict__ frame, int w, int s, int tx, int ty,
+                                                       int tw, uint8_t* __restrict__ templ, int* __restrict__ pos) {
+  const int i = threadIdx.x, j = blockIdx.x;
+  if (j == 0 && i == 0) pos[0] = tx, pos[1] = ty;
+  if (i >= tw) return;
+  const uint8_t* p = frame + ((long)(ty + j) * s * w + (long)(tx + i) * s) * 3;
+  uint32_t acc = 0;
+  for (int y = 0; y < s; ++y, p += 3L * w)
+    for (int x = 0; x < s; ++x) acc += (uint32_t)p[3 * x] + 2u * p[3 * x + 1] + p[3 * x + 2];
+  templ[j * tw + i] = (uint8_t)(acc / (uint32_t)(4 * s * s));
+}
+
+constexpr int TS_THREADS = 1024;
+constexpr int TS_UNROLL = 4;                                  // dword loads a lane has in flight
+constexpr int TS_WMAX = TRACK_MAX_SIDE + 2 * TRACK_MAX_SEARCH;  // rows and bytes per row of the widest window
+constexpr int TS_STAGE_DW = (TS_WMAX + 3 + 3) / 4;            // dwords that can hold bytes of a window row
+constexpr int TS_PITCH_DW = TS_STAGE_DW + 3;                  // and the dwords a lane's last rotation reads behind them
+constexpr int TS_TDW = TRACK_MAX_SIDE / 4;                    // dwords of a template row in LDS
+
+struct SearchGeom {
+  int B, gh, gw, tw, th, R, adapt, lost;
+};
+
+__global__ __launch_bounds__(TS_THREADS) void track_search_kernel(const uint8_t* __restrict__ gray, SearchGeom g,
+                                                                 uint8_t* __restrict__ templ, int* __restrict__ pos,
+                                                                 int* __restrict__ out) {
+  __shared__ uint32_t win[TS_WMAX * TS_PITCH_DW];
+  __shared__ uint32_t tl[TRACK_MAX_SIDE * TS_TDW];
+  __shared__ u64 red[TS_THREADS / 64];
+  uint8_t* tb = reinterpret_cast<uint8_t*>(tl);
+  const uint8_t* wb = reinterpret_cast<const uint8_t*>(win);
+  const int tid = threadIdx.x, tw = g.tw, th = g.th, R = g.R;
+  for (int i = tid; i < TRACK_MAX_SIDE * TS_TDW; i += TS_THREADS) tl[i] = 0;
+  __syncthreads();
+  for (int i = tid; i < tw * th; i += TS_THREADS) tb[(i / tw) * TRACK_MAX_SIDE + i % tw] = templ[i];
+  // a position the host never saw: kept inside the image, so that no candidate reads outside it
+  int px = min(max(pos[0], 0), g.gw - tw), py = min(max(pos[1], 0), g.gh - th);
+  __syncthreads();
+  const int nfull = tw >> 2;  // whole dwords of a template row
+  const uint32_t tail = (tw & 3) ? (1u << (8 * (tw & 3))) - 1u : 0xffffffffu;
+  const uint8_t* lo = gray;
+  const uint8_t* hi = gray + (long)g.B * g.gh * g.gw;
+  for (int b = 0; b < g.B; ++b) {
+    const int dx_lo = max(-R, -px), dx_hi = min(R, g.gw - tw - px);
+    const int dy_lo = max(-R, -py), dy_hi = min(R, g.gh - th - py);
+    const int ncx = dx_hi - dx_lo + 1, ncy = dy_hi - dy_lo + 1;
+    const int wx0 = px + dx_lo, wy0 = py + dy_lo, ww = ncx - 1 + tw, wh = ncy - 1 + th;
+    const uint8_t* seg0 = gray + ((long)b * g.gh + wy0) * g.gw + wx0;
+    const int a0 = (int)(reinterpret_cast<uintptr_t>(seg0) & 3);  // row r of the window starts (a0 + r gw) mod 4 past a dword
+    const int items = wh * TS_STAGE_DW;
+    for (int i0 = tid; i0 < items; i0 += TS_UNROLL * TS_THREADS) {
+      uint32_t v[TS_UNROLL];
+      int at[TS_UNROLL];
+#pragma unroll
+      for (int u = 0; u < TS_UNROLL; ++u) {
+        const int i = i0 + u * TS_THREADS;
+        at[u] = -1;
+        v[u] = 0;
+        if (i >= items) continue;
+        const int r = i / TS_STAGE_DW, k = i - r * TS_STAGE_DW;
+        const int al = (a0 + r * g.gw) & 3;
+        if (4 * k >= al + ww) continue;
+        at[u] = r * TS_PITCH_DW + k;
+        v[u] = track_load_dword(seg0 + (long)r * g.gw - al + 4 * k, lo, hi);
+      }
+#pragma unroll
+      for (int u = 0; u < TS_UNROLL; ++u)
+        if (at[u] >= 0) win[at[u]] = v[u];
+    }
+    __syncthreads();
+    // A work item is four candidates next to each other in dx (one v_qsad_pk_u16_u8 a template dword: the window's 64 bits at
+    // four byte offsets) and one of p parts of the template's rows; the p lanes of a group of four lie next to each other
+    // and add their partial costs with shuffles.  p, a power of two: whatever leaves the fewest rows to the busiest lane.
+    const int ngx = (ncx + 3) >> 2, ngroups = ngx * ncy;
+    int p = 1, units = ((ngroups + TS_THREADS - 1) / TS_THREADS) * th;
+    for (int q = 2; q <= 64; q <<= 1) {
+      const int u = ((ngroups * q + TS_THREADS - 1) / TS_THREADS) * ((th + q - 1) / q);
+      if (u < units) p = q, units = u;
+    }
+    const int rpp = (th + p - 1) / p;
+    u64 best = ~0ull;
+    for (int it0 = 0; it0 < ngroups * p; it0 += TS_THREADS) {
+      const int item = it0 + tid, grp = item / p, part = item - grp * p;
+      const bool live = grp < ngroups;
+      const int cyr = live ? grp / ngx : 0, cxr = live ? (grp - cyr * ngx) * 4 : 0;
+      uint32_t cost[4] = {0, 0, 0, 0};
+      if (live) {
+        const int j1 = min(th, (part + 1) * rpp);
+        for (int j = part * rpp; j < j1; ++j) {
+          const int r = cyr + j;
+          const int o = ((a0 + r * g.gw) & 3) + cxr, ph = o & 3;
+          const uint32_t* row = win + r * TS_PITCH_DW + (o >> 2);
+          const uint32_t* trow = tl + j * TS_TDW;
+          uint32_t d0 = row[0], d1 = row[1];
+          u64 acc = 0;  // four 16-bit sums: at most 16 dwords of 4 * 255 a row
+          for (int m = 0; m < nfull; ++m) {
+            const uint32_t d2 = row[m + 2];
+            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
+            acc = __builtin_amdgcn_qsad_pk_u16_u8((u64)w1 << 32 | w0, trow[m], acc);
+            d0 = d1, d1 = d2;
+          }
+          if (tw & 3) {  // the row's last, partial dword: the window's bytes behind tw masked, the template's are 0
+            const uint32_t d2 = row[nfull + 2];
+            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
+            const uint32_t t = trow[nfull];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) cost[i] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, i) & tail, t, cost[i]);
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) cost[i] += (uint32_t)(acc >> (16 * i)) & 0xffffu;
+        }
+      }
+      for (int off = 1; off < p; off <<= 1)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cost[i] += __shfl_xor(cost[i], off, 64);
+      if (live && part == 0) {
+        const int dy = dy_lo + cyr;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int dx = dx_lo + cxr + i;
+          if (cxr + i >= ncx) continue;
+          const u64 key = (u64)cost[i] << 32 | (u64)(dx * dx + dy * dy) << 16 | (u64)(dy + R) << 8 | (u64)(dx + R);
+          best = key < best ? key : best;
+        }
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const u64 other = __shfl_xor(best, off, 64);
+      best = other < best ? other : best;
+    }
+    if ((tid & 63) == 0) red[tid >> 6] = best;
+    __syncthreads();
+    best = red[0];
+    for (int k = 1; k < TS_THREADS / 64; ++k) best = red[k] < best ? red[k] : best;
+    const int cost = (int)(best >> 32), dx = (int)(best & 255) - R, dy = (int)((best >> 8) & 255) - R;
+    const int found = cost <= g.lost * tw * th;
+    if (found) {
+      px += dx, py += dy;
+      if (g.adapt > 0)
+        for (int idx = tid; idx < tw * th; idx += TS_THREADS) {
+          const int j = idx / tw, i = idx - j * tw, r = py - wy0 + j;
+          const int wv = wb[r * (TS_PITCH_DW * 4) + ((a0 + r * g.gw) & 3) + (px - wx0) + i];
+          uint8_t* t = tb + j * TRACK_MAX_SIDE + i;
+          *t = (uint8_t)((*t * (8 - g.adapt) + wv * g.adapt + 4) >> 3);
+        }
+    }
+    if (tid == 0) {
+      int* o = out + 4L * b;
+      o[0] = px, o[1] = py, o[2] = cost, o[3] = found;
+    }
+    __syncthreads();  // the window, the template and red are the next frame's
+  }
+  for (int i = tid; i < tw * th; i += TS_THREADS) templ[i] = tb[(i / tw) * TRACK_MAX_SIDE + i % tw];
+  if (tid == 0) pos[0] = px, pos[1] = py;
+}
+
+static int track_frame_check(const char* who, int h, int w, int s) {
+  D3F_CHECK(h > 0 && w > 0 && h <= 16384 && w <= 16384, "%s: size %d x %d outside 1..16384", who, h, w);
+  D3F_CHECK(s >= 1 && s <= TRACK_MAX_STRIDE, "%s: stride %d outside 1..%d", who, s, TRACK_MAX_STRIDE);
+  return 0;
+}
+
+static int track_batch_check(const char* who, int B) {
+  D3F_CHECK(B >= 0 && B <= 65535, "%s: B %d outside 0..65535 frames per call", who, B);
+  return 0;
+}
+
+static int track_side_check(const char* who, int tw, int th) {
+  D3F_CHECK(tw >= TRACK_MIN_SIDE && tw <= TRACK_MAX_SIDE && th >= TRACK_MIN_SIDE && th <= TRACK_MAX_SIDE,
+            "%s: template %d x %d outside %d..%d", who, tw, th, TRACK_MIN_SIDE, TRACK_MAX_SIDE);
+  return 0;
+}
+
+int gray_decimate_check(int B, int h, int w, int s) {
+  if (int rc = track_batch_check("gray_decimate", B)) return rc;
+  return track_frame_check("gray_decimate", h, w, s);
+}
+
+int gray_decimate_u8_launch(const uint8_t* frames, int B, int h, int w, int s, uint8_t* out, hipStream_t stream) {
+  if (int rc = gray_decimate_check(B, h, w, s)) return rc;
+  const int gh = h / s, gw = w / s;
+  if (B == 0 || gh == 0 || gw == 0) return 0;
+  const DecimateGeom g = {B, h, w, s, gh, gw};
+  hipLaunchKernelGGL(gray_decimate_kernel, dim3((gw + GD_THREADS - 1) / GD_THREADS, gh, B), dim3(GD_THREADS), 0, stream,
+                     frames, g, out);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+int track_seed_u8_launch(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, uint8_t* templ, int* pos,
+                         hipStream_t stream) {
+  if (int rc = track_frame_check("track_seed", h, w, s)) return rc;
+  if (int rc = track_side_check("track_seed", tw, th)) return rc;
+  D3F_CHECK(tx >= 0 && ty >= 0 && tx + tw <= w / s && ty + th <= h / s,
+            "track_seed: box (%d, %d, %d, %d) outside the reduced image %d x %d", tx, ty, tw, th, w / s, h / s);
+  D3F_CHECK((reinterpret_cast<uintptr_t>(pos) & 3) == 0, "track_seed: pos must be aligned to 4 bytes");
+  hipLaunchKernelGGL(track_seed_kernel, dim3(th), dim3(64), 0, stream, frame, w, s, tx, ty, tw, templ, pos);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+int track_search_check(int B, int gh, int gw, int tw, int th, int search, int adapt, int lost, const int* pos,
+                       const int* out) {
+  if (int rc = track_batch_check("track_search", B)) return rc;
+  D3F_CHECK(gh > 0 && gw > 0 && gh <= 16384 && gw <= 16384, "track_search: reduced size %d x %d outside 1..16384", gh, gw);
+  if (int rc = track_side_check("track_search", tw, th)) return rc;
+  D3F_CHECK(gh >= th && gw >= tw, "track_search: template %d x %d larger than the reduced image %d x %d", tw, th, gw, gh);
+  D3F_CHECK(search >= 1 && search <= TRACK_MAX_SEARCH, "track_search: search %d outside 1..%d", search, TRACK_MAX_SEARCH);
+  D3F_CHECK(adapt >= 0 && adapt <= 8, "track_search: adapt %d outside 0..8", adapt);
+  D3F_CHECK(lost >= 0 && lost <= 255, "track_search: lost %d outside 0..255", lost);
+  D3F_CHECK(((reinterpret_cast<uintptr_t>(pos) | reinterpret_cast<uintptr_t>(out)) & 3) == 0,
+            "track_search: pos and out must be aligned to 4 bytes");
+  return 0;
+}
+
+int track_search_u8_launch(const uint8_t* gray, int B, int gh, int gw, int tw, int th, int search, int adapt, int lost,
+                           uint8_t* templ, int* pos, int* out, hipStream_t stream) {
+  if (int rc = track_search_check(B, gh, gw, tw, th, search, adapt, lost, pos, out)) return rc;
+  if (B == 0) return 0;
+  const SearchGeom g = {B, gh, gw, tw, th, search, adapt, lost};
+  hipLaunchKernelGGL(track_search_kernel, dim3(1), dim3(TS_THREADS), 0, stream, gray, g, templ, pos, out);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+int track_template_u8_launch(const uint8_t* frames, int B, int h, int w, int s, int tw, int th, int search, int adapt,
+                             int lost, uint8_t* templ, int* pos, uint8_t* gray_ws, int* out, hipStream_t stream) {
+  // both refusals before either launch
+  if (int rc = gray_decimate_check(B, h, w, s)) return rc;
+  D3F_CHECK(h / s > 0 && w / s > 0, "track_template: stride %d leaves nothing of %d x %d", s, h, w);
+  if (int rc = track_search_check(B, h / s, w / s, tw, th, search, adapt, lost, pos, out)) return rc;
+  if (int rc = gray_decimate_u8_launch(frames, B, h, w, s, gray_ws, stream)) return rc;
+  return track_search_u8_launch(gray_ws, B, h / s, w / s, tw, th, search, adapt, lost, templ, pos, out, stream);
+}
+
+}  // namespace d3f

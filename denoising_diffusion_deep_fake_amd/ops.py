@@ -953,6 +953,134 @@ def color_coef_smooth(coef, sums_to, n, state, strength=_lib.TEMPORAL_STRENGTH):
     return coef
 
 
+# ---- template tracker: the face box of a track file from hand-set key boxes (include/d3f_hip.h: "Template tracker") ----
+TRACK_TEMPLATE_SIDE, TRACK_SEARCH, TRACK_ADAPT, TRACK_LOST = (_lib.TRACK_TEMPLATE_SIDE, _lib.TRACK_SEARCH, _lib.TRACK_ADAPT,
+                                                              _lib.TRACK_LOST)
+
+
+def gray_decimate_u8(frames, s, out=None):
+    """uint8 BGR frames [h, w, 3] / [B, h, w, 3] on the HIP device -> the reduced grey image [h // s, w // s] /
+    [B, h // s, w // s] uint8: (sum over each s x s block of B + 2 G + R) // (4 s s), partial blocks at the right and bottom
+    dropped (include/d3f_hip.h: d3f_gray_decimate_u8).  frames: contiguous, at any byte address.  out: a contiguous uint8
+    tensor of the result's shape to write into."""
+    if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
+        raise ValueError("gray_decimate_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3]")
+    s = int(s)
+    if not 1 <= s <= _lib.TRACK_MAX_STRIDE:
+        raise ValueError(f"gray_decimate_u8: the stride is an integer in 1..{_lib.TRACK_MAX_STRIDE}, not {s}")
+    dev = _dev(frames)
+    single = frames.dim() == 3
+    x = (frames.unsqueeze(0) if single else frames).contiguous()
+    B, h, w, _ = x.shape
+    shape = (B, h // s, w // s)
+    if out is None:
+        g = torch.empty(shape, dtype=torch.uint8, device=dev)
+    else:
+        g = out.unsqueeze(0) if single and out.dim() == 2 else out
+        if tuple(g.shape) != shape or g.dtype != torch.uint8 or g.device != dev or not g.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on the frames' device")
+    if g.numel() > 0:
+        check(_lib.lib().d3f_gray_decimate_u8(ptr(x), B, h, w, s, ptr(g), stream_ptr()))
+    return g[0] if single else g
+
+
+def track_template_geometry(h, w, face, side=TRACK_TEMPLATE_SIDE):
+    """The tracker's geometry for a face box (fx, fy, fw, fh) marked in an h x w frame, as (s, tx, ty, tw, th, ox, oy, fw, fh):
+    the face clipped to the frame; the stride s = max(1, ceil(max(fw, fh) / side)) of the reduced grey image; the template's
+    box there, tx = fx // s, ty = fy // s, tw = (fx + fw) // s - tx, th = (fy + fh) // s - ty; and ox = fx - tx s,
+    oy = fy - ty s, so that a reduced position (px, py) is the face (px s + ox, py s + oy, fw, fh).  A ValueError: an empty
+    clip, a side above 64, a stride above 32, a template below 4 samples on an axis."""
+    h, w, side = int(h), int(w), int(side)
+    fx, fy, fw, fh = [int(v) for v in face]
+    if not 1 <= side <= _lib.TRACK_MAX_SIDE:
+        raise ValueError(f"track_template_geometry: side {side} outside 1..{_lib.TRACK_MAX_SIDE}")
+    x0, y0, x1, y1 = max(fx, 0), max(fy, 0), min(fx + fw, w), min(fy + fh, h)
+    if x1 <= x0 or y1 <= y0:
+        raise ValueError(f"track_template_geometry: the face {(fx, fy, fw, fh)} has nothing inside the {w} x {h} frame")
+    fx, fy, fw, fh = x0, y0, x1 - x0, y1 - y0
+    s = max(1, -(-max(fw, fh) // side))
+    if s > _lib.TRACK_MAX_STRIDE:
+        raise ValueError(f"track_template_geometry: a face of {fw} x {fh} at side {side} needs stride {s}, above "
+                         f"{_lib.TRACK_MAX_STRIDE}")
+    tx, ty = fx // s, fy // s
+    tw, th = (fx + fw) // s - tx, (fy + fh) // s - ty
+    if tw < _lib.TRACK_MIN_SIDE or th < _lib.TRACK_MIN_SIDE:
+        raise ValueError(f"track_template_geometry: the face {fw} x {fh} gives a template of {tw} x {th}, below "
+                         f"{_lib.TRACK_MIN_SIDE} samples")
+    return s, tx, ty, tw, th, fx - tx * s, fy - ty * s, fw, fh
+
+
+class TrackState:
+    """The state of the template tracker: `templ`, the template's th rows of tw bytes packed at the front of 64 * 64 uint8,
+    and `pos` int32 [2], both on the device; `geometry`, what `track_template_geometry` gave at the seed, and the frame
+    size (h, w) it was given for, on the host; a grey workspace grown on demand; `seeded`."""
+
+    def __init__(self, device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.D3FError("libd3f_hip ops need tensors on the HIP device (no CPU fallback)")
+        self.templ = torch.zeros((_lib.TRACK_MAX_SIDE * _lib.TRACK_MAX_SIDE,), dtype=torch.uint8, device=device)
+        self.pos = torch.zeros((2,), dtype=torch.int32, device=device)
+        self.geometry = None
+        self.h = self.w = 0
+        self.gray = None
+        self.seeded = False
+
+    def workspace(self, n):
+        if self.gray is None or self.gray.numel() < n:
+            self.gray = torch.empty((n,), dtype=torch.uint8, device=self.templ.device)
+        return self.gray
+
+
+def track_seed(state, frame, face, side=TRACK_TEMPLATE_SIDE):
+    """(re-)seed `state` from the face box (fx, fy, fw, fh) marked in `frame`, uint8 BGR [h, w, 3] on the HIP device: the
+    template is the reduced grey of the box (include/d3f_hip.h: d3f_track_seed_u8).  Returns the geometry."""
+    if not isinstance(state, TrackState):
+        raise ValueError("track_seed: state must be a TrackState")
+    if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
+        raise ValueError("track_seed expects one uint8 frame [h, w, 3]")
+    h, w = int(frame.shape[0]), int(frame.shape[1])
+    geometry = track_template_geometry(h, w, face, side)
+    s, tx, ty, tw, th = geometry[:5]
+    if _dev(frame) != state.templ.device:
+        raise ValueError("track_seed expects the frame on the state's device")
+    x = frame.contiguous()
+    check(_lib.lib().d3f_track_seed_u8(ptr(x), h, w, s, tx, ty, tw, th, ptr(state.templ), ptr(state.pos), stream_ptr()))
+    state.geometry, state.h, state.w, state.seeded = geometry, h, w, True
+    return geometry
+
+
+def track_template_u8(frames, state, search=TRACK_SEARCH, adapt=TRACK_ADAPT, lost=TRACK_LOST):
+    """follow the seeded template through uint8 BGR frames [B, h, w, 3] on the HIP device, consecutive in time and behind the
+    last frame of the previous call on `state` -> int32 [B, 4] on the device, a row (px, py, cost, found) per frame in the
+    reduced image (`track_faces` turns host rows into boxes).  One device call: the reduced grey of every frame, then the
+    search, frame by frame, inside one kernel (include/d3f_hip.h: d3f_track_template_u8)."""
+    if not isinstance(state, TrackState) or not state.seeded:
+        raise ValueError("track_template_u8: state must be a TrackState seeded by track_seed")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError("track_template_u8 expects uint8 frames [B, h, w, 3]")
+    B, h, w, _ = frames.shape
+    if (h, w) != (state.h, state.w):
+        raise ValueError(f"track_template_u8: frames of {h} x {w}, the state was seeded on {state.h} x {state.w}")
+    if _dev(frames) != state.templ.device:
+        raise ValueError("track_template_u8 expects the frames on the state's device")
+    s, _, _, tw, th = state.geometry[:5]
+    out = torch.empty((B, 4), dtype=torch.int32, device=frames.device)
+    if B > 0:
+        x = frames.contiguous()
+        ws = state.workspace(B * (h // s) * (w // s))
+        check(_lib.lib().d3f_track_template_u8(ptr(x), B, h, w, s, tw, th, int(search), int(adapt), int(lost),
+                                               ptr(state.templ), ptr(state.pos), ptr(ws), ptr(out), stream_ptr()))
+    return out
+
+
+def track_faces(rows, state):
+    """host rows (px, py, cost, found) of `track_template_u8` -> a list of face boxes (x, y, w, h) in frame pixels, None where
+    the frame's row says not found.  state: the TrackState the rows came from, or the geometry it had then"""
+    s, _, _, _, _, ox, oy, fw, fh = getattr(state, "geometry", state)
+    return [(int(px) * s + ox, int(py) * s + oy, fw, fh) if int(found) else None for px, py, _, found in rows]
+
+
 def paste_resize_cubic_u8(patch, frames, box=None, feather=0, out=None, color=None, boxes=None):
     """The inverse of `crop_resize_cubic_u8` with a blend: uint8 `patch` [H, W, 3] / [B, H, W, 3] on the HIP device is resized
     to the box (x1, y1, cw, ch) of uint8 `frames` [h, w, 3] / [B, h, w, 3] with the same arithmetic and blended in over a

@@ -1,0 +1,195 @@
+"""Write the face-box track of a video from boxes marked by hand at key frames: the file that
+put_video_through_fake_model --track and video_to_center_cropped_images --track read.  There is no detector: the box of a
+key frame is the template, and the device follows it from frame to frame (ops.track_template_u8: a reduced grey image of
+every frame, then the smallest sum of absolute differences in a search window).  There is no scale search either: where
+the face changes size, where the tracker drifts and behind a cut, mark another key frame -- the tracker is seeded anew
+at every key.
+
+    python -m d3f.script_tools.track_face_box VIDEO --key K X Y W H [--key ...] [-o FILE]
+"""
+import argparse
+from pathlib import Path
+
+import torch
+
+from .. import _lib, ops
+from .video_writer_context_manager import batches, import_cv2, open_video_as_generator
+
+
+def main():
+
+    args = parse_command_line_arguments()
+
+    tracker = TrackFaceBox(
+        args.video_path,
+        args.key,
+        output_path=args.output,
+        batch_frames=args.batch_frames,
+        search=args.search,
+        adapt=args.adapt,
+        lost=args.lost,
+        template_side=args.template_side,
+        )
+    found = sum(box is not None for box in tracker.track)
+    print(f"{tracker.output_path}: {len(tracker.track)} frames, the face found in {found}")
+
+
+def parse_command_line_arguments(argv=None):
+    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+
+    parser.add_argument("video_path", help="path to the video")
+    parser.add_argument("--key", type=int, nargs=5, action="append", metavar=("K", "X", "Y", "W", "H"), required=True,
+                        help="the face box x y w h, in pixels, marked at frame K (counted from 0); repeat it to correct "
+                             "drift, a cut or a change of size: the tracker starts anew at every key")
+    parser.add_argument("-o", "--output", default=None, metavar="FILE",
+                        help="the track file (default: <video stem>_track.txt next to the video)")
+    parser.add_argument("--batch-frames", type=int, default=8, help="frames per device call (the file does not depend on it)")
+    parser.add_argument("--search", type=int, default=ops.TRACK_SEARCH, metavar="R",
+                        help=f"search radius per frame in pixels of the reduced image, 1..{_lib.TRACK_MAX_SEARCH} "
+                             f"(default {ops.TRACK_SEARCH})")
+    parser.add_argument("--adapt", type=int, default=ops.TRACK_ADAPT, metavar="A",
+                        help=f"eighths of the found window blended into the template per frame, 0..8 (default {ops.TRACK_ADAPT})")
+    parser.add_argument("--lost", type=int, default=ops.TRACK_LOST, metavar="L",
+                        help=f"mean absolute difference in grey levels above which a frame is written as `-`, 0..255 "
+                             f"(default {ops.TRACK_LOST})")
+    parser.add_argument("--template-side", type=int, default=ops.TRACK_TEMPLATE_SIDE, metavar="S",
+                        help=f"the template's longer side in samples, 4..{_lib.TRACK_MAX_SIDE} (default "
+                             f"{ops.TRACK_TEMPLATE_SIDE})")
+
+    args = parser.parse_args(argv)
+    try:
+        check_settings(sorted_keys(args.key), args.batch_frames, args.search, args.adapt, args.lost, args.template_side)
+    except ValueError as e:
+        parser.error(str(e))
+    return args
+
+
+def sorted_keys(keys):
+    """keys: (k, x, y, w, h) each -> {k: (x, y, w, h)} in the order of k; a ValueError for none, a negative or a repeated
+    frame index and a box without extent"""
+    rows = sorted(tuple(int(v) for v in key) for key in keys or [])
+    if not rows or any(len(row) != 5 for row in rows):
+        raise ValueError("--key: at least one key `K X Y W H` is needed")
+    out = {}
+    for k, x, y, w, h in rows:
+        if k < 0:
+            raise ValueError(f"--key: frame index {k} is negative")
+        if k in out:
+            raise ValueError(f"--key: frame {k} has two keys")
+        if w <= 0 or h <= 0:
+            raise ValueError(f"--key: the box of frame {k} has extent {w} x {h}")
+        out[k] = (x, y, w, h)
+    return out
+
+
+def check_settings(keys, batch_frames, search, adapt, lost, template_side):
+    if int(batch_frames) < 1:
+        raise ValueError("--batch-frames is at least 1")
+    for name, value, low, high in (("--search", search, 1, _lib.TRACK_MAX_SEARCH), ("--adapt", adapt, 0, 8),
+                                   ("--lost", lost, 0, 255),
+                                   ("--template-side", template_side, _lib.TRACK_MIN_SIDE, _lib.TRACK_MAX_SIDE)):
+        if isinstance(value, bool) or not isinstance(value, int) or not low <= value <= high:
+            raise ValueError(f"{name} is an integer in {low}..{high}, not {value!r}")
+    return keys
+
+
+def write_track(path, track, header=()):
+    """line k for frame k: `x y w h`, or `-` where track[k] is None, behind `# ` comment lines -- what ops.read_box_track
+    parses"""
+    with open(path, "w") as f:
+        for line in header:
+            f.write(f"# {line}\n")
+        for box in track:
+            f.write("-\n" if box is None else "{} {} {} {}\n".format(*box))
+
+
+class TrackFaceBox():
+    """keys: (k, x, y, w, h) each, the face box marked at frame k.  frames=: an iterable of decoded BGR frames instead of the
+    video file (cv2 is not needed then); sink=: a callable that takes each frame's box, (x, y, w, h) or None -- without an
+    output_path no file is written then.  .track holds the result, entry k for frame k: None before the first key and where
+    the face was not found, the key's own box (clipped to the frame) at a key frame.  A batch is one upload, one device call
+    (one more, and a seed, per key frame inside it) and one small copy back; the result does not depend on batch_frames."""
+
+    def __init__(self, video_path, keys, output_path=None, batch_frames=8, frames=None, sink=None, device="cuda",
+                 search=ops.TRACK_SEARCH, adapt=ops.TRACK_ADAPT, lost=ops.TRACK_LOST,
+                 template_side=ops.TRACK_TEMPLATE_SIDE):
+
+        self.video_path = Path(video_path)
+        self.keys = check_settings(sorted_keys(keys), batch_frames, search, adapt, lost, template_side)
+        self.batch_frames = int(batch_frames)
+        self.frames = frames
+        self.sink = sink
+        self.device = device
+        self.search, self.adapt, self.lost, self.template_side = search, adapt, lost, template_side
+        if output_path is not None:
+            self.output_path = Path(output_path)
+        elif sink is None:
+            self.output_path = self.video_path.with_name(f"{self.video_path.stem}_track.txt")
+        else:
+            self.output_path = None
+        self.track = []
+
+        if frames is None:
+            import_cv2()
+
+        self.track_video()
+
+        if self.output_path is not None:
+            write_track(self.output_path, self.track, self.header())
+        late = [k for k in self.keys if k >= len(self.track)]
+        if late:
+            raise ValueError(f"--key: frame {late[0]} is past the video's last frame, {len(self.track) - 1}")
+
+    def header(self):
+        keys = ", ".join("{} {} {} {} {}".format(k, *box) for k, box in self.keys.items())
+        return (f"track_face_box {self.video_path.name}: x y w h per frame, - where the face was not found",
+                f"keys (frame x y w h): {keys}",
+                f"search {self.search}, adapt {self.adapt}, lost {self.lost}, template side {self.template_side}")
+
+    def track_video(self):
+
+        frames = self.frames if self.frames is not None else open_video_as_generator(self.video_path)
+        state = None
+
+        for batch, real_frames in batches(frames, self.batch_frames):
+            first = len(self.track)
+            if state is None and not any(first <= k < first + real_frames for k in self.keys):
+                boxes = [None] * real_frames  # before the first key: nothing to follow, nothing to upload
+            else:
+                if state is None:
+                    state = ops.TrackState(self.device)
+                boxes = self.track_batch(torch.from_numpy(batch).to(self.device)[:real_frames], first, state)
+            for box in boxes:
+                self.track.append(box)
+                if self.sink is not None:
+                    self.sink(box)
+
+    def track_batch(self, dev, first, state):
+        """the boxes of the frames `dev` [n, h, w, 3] on the device, frame `first` of the video onwards: the stretches
+        between key frames are followed, every key frame seeds"""
+        n = len(dev)
+        cuts = [i for i in range(n) if first + i in self.keys]
+        boxes = [None] * n
+        parts = []  # (index of the first frame, its device rows, the geometry they are in)
+        start = 0
+        for cut in cuts + [n]:
+            if cut > start and state.seeded:
+                parts.append((start, ops.track_template_u8(dev[start:cut], state, self.search, self.adapt, self.lost),
+                              state.geometry))
+            if cut < n:
+                geometry = ops.track_seed(state, dev[cut], self.keys[first + cut], self.template_side)
+                s, tx, ty, _, _, ox, oy, fw, fh = geometry
+                boxes[cut] = (tx * s + ox, ty * s + oy, fw, fh)  # the key's box, clipped
+            start = cut + 1
+        if parts:
+            rows = torch.cat([part[1] for part in parts]).cpu().tolist()  # one copy back
+            at = 0
+            for index, part, geometry in parts:
+                count = len(part)
+                boxes[index:index + count] = ops.track_faces(rows[at:at + count], geometry)
+                at += count
+        return boxes
+
+
+if __name__ == "__main__":
+    main()

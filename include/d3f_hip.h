@@ -689,6 +689,49 @@ int d3f_color_coef_smooth(float* coef, const uint64_t* sums_to, int B, int64_t n
 /* *flag = value by a one-lane launch on the stream: the reset of either operator's state (value 0). */
 int d3f_temporal_flag_set(int32_t* flag, int value, void* stream);
 
+/* Template tracker: the face box of a --track file from boxes set by hand at key frames, with no detector.  Integer
+ * arithmetic throughout, so the result does not depend on the order of evaluation; tests/track_restatement.py restates it in
+ * numpy and Python integers and every comparison is exact.  The defaults (D3F_TRACK_TEMPLATE_SIDE, _SEARCH, _ADAPT, _LOST) are
+ * design choices, not measurements.  There is no scale or rotation search: a face that changes size wants another key box.
+ *
+ * d3f_gray_decimate_u8: frames [B][h][w][3] uint8 BGR, packed, any byte address -> out [B][gh][gw] uint8, gh = h / s,
+ * gw = w / s (partial blocks at the right and bottom are dropped), out[y][x] = (sum over the s x s block of B + 2 G + R) /
+ * (4 s s) in integers.  gh == 0 or gw == 0 writes nothing.  No dword is loaded whole outside the frames' bytes, and no byte
+ * outside out is written.
+ * d3f_track_seed_u8: that grey of the box (tx, ty, tw, th) of ONE frame's reduced image -> templ, tw bytes a row, th rows,
+ * packed at the front of a buffer of D3F_TRACK_MAX_SIDE * D3F_TRACK_MAX_SIDE bytes; pos int32[2] = (tx, ty).
+ * d3f_track_search_u8: gray [B][gh][gw], the frames of a call consecutive in time; templ and pos are read at the start and
+ * written at the end (a pos outside 0..gw - tw, 0..gh - th is moved inside first).  For each frame in order:
+ *   - candidates (dx, dy) in [-search, search]^2 with 0 <= pos.x + dx <= gw - tw and 0 <= pos.y + dy <= gh - th;
+ *   - cost = sum over the template of |gray[pos.y + dy + j][pos.x + dx + i] - templ[j][i]|, below 2^20;
+ *   - key = cost << 32 | (dx dx + dy dy) << 16 | (dy + search) << 8 | (dx + search), unsigned 64 bits; the smallest key wins
+ *     (equal costs: the smaller displacement, then the smaller dy, then the smaller dx);
+ *   - found = cost <= lost * tw * th.  Found: pos += (dx, dy), then templ = (templ * (8 - adapt) + window * adapt + 4) >> 3 per
+ *     sample with the window at the new pos.  Not found: pos and templ stay exactly as they were;
+ *   - out[b] = (pos.x, pos.y, cost, found), pos after the update.
+ * A reduced position (px, py) is the face (px * s + ox, py * s + oy, fw, fh) of the seed's geometry (the Python side:
+ * ops.track_template_geometry).
+ * d3f_track_template_u8: d3f_gray_decimate_u8 of the frames into gray_ws [B][gh][gw], then d3f_track_search_u8 on it: two
+ * launches in one call.
+ * B == 0 touches nothing.  Refused before any device call: null pointers, B < 0 or B > 65535, sizes outside 1..16384, s outside
+ * 1..D3F_TRACK_MAX_STRIDE, tw or th outside 4..D3F_TRACK_MAX_SIDE, a template larger than the reduced image (gh < th, gw < tw)
+ * or a seed box outside it, search outside 1..D3F_TRACK_MAX_SEARCH, adapt outside 0..8, lost outside 0..255, a pos or out
+ * that is not 4-byte aligned. */
+#define D3F_TRACK_MAX_SIDE 64
+#define D3F_TRACK_MAX_SEARCH 64
+#define D3F_TRACK_MAX_STRIDE 32
+#define D3F_TRACK_TEMPLATE_SIDE 48
+#define D3F_TRACK_SEARCH 16
+#define D3F_TRACK_ADAPT 1
+#define D3F_TRACK_LOST 16
+int d3f_gray_decimate_u8(const uint8_t* frames, int B, int h, int w, int s, uint8_t* out, void* stream);
+int d3f_track_seed_u8(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, uint8_t* templ, int32_t* pos,
+                      void* stream);
+int d3f_track_search_u8(const uint8_t* gray, int B, int gh, int gw, int tw, int th, int search, int adapt, int lost,
+                        uint8_t* templ, int32_t* pos, int32_t* out, void* stream);
+int d3f_track_template_u8(const uint8_t* frames, int B, int h, int w, int s, int tw, int th, int search, int adapt, int lost,
+                          uint8_t* templ, int32_t* pos, uint8_t* gray_ws, int32_t* out, void* stream);
+
 /* log_batch_as_image_grid of the three LitModules (d3f/train_deep_fake/lit_module.py:235-249,
  * d3f/train_denoiser/lit_module.py:157-171, d3f/balance_training_images/lit_module.py:197-211):
  * torchvision.utils.make_grid(batch[:images], nrow, padding, pad_value), the whole grid -- padding included -- taken
