@@ -891,7 +891,28 @@ int d3f_gray_decimate_u8(const uint8_t* frames, int B, int h, int w, int s, uint
 int d3f_track_seed_u8(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, uint8_t* templ, int32_t* pos,
                       void* stream) {
   D3F_CHECK(frame && templ && pos, "track_seed_u8: null argument");
-  return track_seed_u8_launch(frame, h, w, s, tx, ty, tw, th, templ, pos, (hipStream_t)stream);
+  return track_seed_u8_launch(frame, h, w, s, tx, ty, tw, th, templ, pos, false, (hipStream_t)stream);
+}
+
+int d3f_track_seed_scale_u8(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, uint8_t* templ,
+                            int32_t* pos, void* stream) {
+  D3F_CHECK(frame && templ && pos, "track_seed_scale_u8: null argument");
+  return track_seed_u8_launch(frame, h, w, s, tx, ty, tw, th, templ, pos, true, (hipStream_t)stream);
+}
+
+int d3f_track_search_scale_u8(const uint8_t* gray, int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost,
+                              int levels, int penalty, uint8_t* templ, int32_t* pos, int32_t* out, void* stream) {
+  D3F_CHECK(gray && templ && pos && out, "track_search_scale_u8: null argument");
+  return track_search_scale_u8_launch(gray, B, gh, gw, tw0, th0, search, adapt, lost, levels, penalty, templ, pos, out,
+                                      (hipStream_t)stream);
+}
+
+int d3f_track_template_scale_u8(const uint8_t* frames, int B, int h, int w, int s, int tw0, int th0, int search, int adapt,
+                                int lost, int levels, int penalty, uint8_t* templ, int32_t* pos, uint8_t* gray_ws,
+                                int32_t* out, void* stream) {
+  D3F_CHECK(frames && templ && pos && gray_ws && out, "track_template_scale_u8: null argument");
+  return track_template_scale_u8_launch(frames, B, h, w, s, tw0, th0, search, adapt, lost, levels, penalty, templ, pos, gray_ws,
+                                        out, (hipStream_t)stream);
 }
 
 int d3f_track_search_u8(const uint8_t* gray, int B, int gh, int gw, int tw, int th, int search, int adapt, int lost,

@@ -219,13 +219,21 @@ int color_coef_smooth_launch(float* coef, const uint64_t* sums_to, int parts, in
 int gray_decimate_check(int B, int h, int w, int s);
 int gray_decimate_u8_launch(const uint8_t* frames, int B, int h, int w, int s, uint8_t* out, hipStream_t stream);
 int track_seed_u8_launch(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, uint8_t* templ, int* pos,
-                         hipStream_t stream);
+                         bool with_level, hipStream_t stream);  // with_level: pos is int32[3], pos[2] = max(tw, th)
 int track_search_check(int B, int gh, int gw, int tw, int th, int search, int adapt, int lost, const int* pos,
                        const int* out);
 int track_search_u8_launch(const uint8_t* gray, int B, int gh, int gw, int tw, int th, int search, int adapt, int lost,
                            uint8_t* templ, int* pos, int* out, hipStream_t stream);
 int track_template_u8_launch(const uint8_t* frames, int B, int h, int w, int s, int tw, int th, int search, int adapt,
                              int lost, uint8_t* templ, int* pos, uint8_t* gray_ws, int* out, hipStream_t stream);
+// the scale search (d3f_track_search_scale_u8): templ stays at the seed's tw0 x th0, pos int32[3] = x, y, level, out int32 [B][8]
+int track_search_scale_check(int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost, int levels, int penalty,
+                             const int* pos, const int* out);
+int track_search_scale_u8_launch(const uint8_t* gray, int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost,
+                                 int levels, int penalty, uint8_t* templ, int* pos, int* out, hipStream_t stream);
+int track_template_scale_u8_launch(const uint8_t* frames, int B, int h, int w, int s, int tw0, int th0, int search, int adapt,
+                                   int lost, int levels, int penalty, uint8_t* templ, int* pos, uint8_t* gray_ws, int* out,
+                                   hipStream_t stream);
 
 // training image grids (image_grid.hip): make_grid + scale + clamp + uint8 of up to 8 fp32 NCHW batches in one launch;
 // `batches` is a host array of n device pointers, out [n][GH][GW][3] with {GH, GW} from image_grid_shape

@@ -21,6 +21,9 @@
 // differences, the window at byte offsets 0..3), the last dword of a row with v_sad_u8 and a mask where tw is no multiple
 // of 4; the parts are added and the 64-bit keys reduced with shuffles and through LDS; every lane decodes the winner, the
 // lanes blend the template, lane 0 stores the output row.
+//
+// track_search_scale_kernel (d3f_track_search_scale_u8, opt-in): the same search over the neighbouring sizes too; its own
+// comment stands in front of it, tests/track_scale_restatement.py restates it.
 #include "../../include/d3f_hip.h"
 #include "common.h"
 #include "pointwise.h"
@@ -126,10 +129,15 @@ __global__ __launch_bounds__(GD_THREADS) void gray_decimate_kernel(const uint8_t
 }
 
 // The grey of the key box only: block j is row j of the template, lane i its sample i; T is packed, th rows of tw bytes.
+// level > 0: the scale search's state, pos[2] = level (the seed's own, L0).
 __global__ __launch_bounds__(64) void track_seed_kernel(const uint8_t* __restrict__ frame, int w, int s, int tx, int ty,
-                                                       int tw, uint8_t* __restrict__ templ, int* __restrict__ pos) {
+                                                       int tw, int level, uint8_t* __restrict__ templ,
+                                                       int* __restrict__ pos) {
   const int i = threadIdx.x, j = blockIdx.x;
-  if (j == 0 && i == 0) pos[0] = tx, pos[1] = ty;
+  if (j == 0 && i == 0) {
+    pos[0] = tx, pos[1] = ty;
+    if (level > 0) pos[2] = level;
+  }
   if (i >= tw) return;
   const uint8_t* p = frame + ((long)(ty + j) * s * w + (long)(tx + i) * s) * 3;
   uint32_t acc = 0;
@@ -283,6 +291,253 @@ __global__ __launch_bounds__(TS_THREADS) void track_search_kernel(const uint8_t*
   if (tid == 0) pos[0] = px, pos[1] = py;
 }
 
+// ---- the scale search (include/d3f_hip.h: d3f_track_search_scale_u8; tests/track_scale_restatement.py) ----
+// track_search_scale_kernel keeps the shape of track_search_kernel: ONE workgroup, the loop over the call's frames inside,
+// the position and the level in every lane's registers.  The state's template T0 stays at the seed's size tw0 x th0 in LDS
+// for the call; per frame it is resampled to the sizes of the (up to three) candidate levels, the union of their search
+// windows is staged once as aligned dwords, and the candidates of all levels are spread over the lanes as work items of
+// four dx and a part of the rows, as above.  A key-writing lane divides once per candidate (the cost over the area); the
+// winner's window is resampled back to the seed's size and blended into T0.
+constexpr int SS_LEVELS = 3;                                          // dL = -1, 0, 1
+constexpr int SS_WMAX = TRACK_MAX_SIDE + 2 * TRACK_MAX_SEARCH + 2;    // the union window: anchors of neighbouring levels lie
+constexpr int SS_STAGE_DW = (SS_WMAX + 3 + 3) / 4;                    // at most one sample apart, their sizes too
+constexpr int SS_PITCH_DW = SS_STAGE_DW + 3;
+// a level's entry: valid, tw, th, x and y of its first candidate in the image, dx_lo, dy_lo, ncx, ncy, ngx, anchor x, anchor y
+constexpr int SS_LV = 12;
+static_assert((SS_WMAX * SS_PITCH_DW + (1 + SS_LEVELS) * TRACK_MAX_SIDE * TS_TDW + SS_LEVELS * 2 * TRACK_MAX_SIDE) * 4 +
+                      SS_LEVELS * SS_LV * 4 + TS_THREADS / 64 * 8 <= 64 * 1024,
+              "track_search_scale_kernel's static LDS");
+
+struct ScaleGeom {
+  int B, gh, gw, tw0, th0, R, adapt, lost, levels, penalty, Lmin, Lmax;  // Lmin..Lmax: the valid levels, found on the host
+};
+
+__host__ __device__ __forceinline__ int track_level_side(int n0, int L, int L0) { return (n0 * L + (L0 >> 1)) / L0; }
+
+// the two taps and the 6-bit weight of output sample i of n_out from n_in, bilinear at pixel centres: i0 | i1 << 8 | f << 16
+__device__ __forceinline__ uint32_t track_resample_tap(int i, int n_in, int n_out) {
+  const int num = (2 * i + 1) * n_in - n_out, den = 2 * n_out;
+  int i0 = 0, f = 0;
+  if (num >= 0) {
+    i0 = num / den;
+    f = ((num - i0 * den) * 64) / den;
+  }
+  const int i1 = min(i0 + 1, n_in - 1);
+  i0 = min(i0, n_in - 1);
+  return (uint32_t)i0 | (uint32_t)i1 << 8 | (uint32_t)f << 16;
+}
+
+__device__ __forceinline__ int track_bilinear(int a00, int a01, int a10, int a11, int fx, int fy) {
+  return (a00 * (64 - fy) * (64 - fx) + a01 * (64 - fy) * fx + a10 * fy * (64 - fx) + a11 * fy * fx + 2048) >> 12;
+}
+
+__global__ __launch_bounds__(TS_THREADS) void track_search_scale_kernel(const uint8_t* __restrict__ gray, ScaleGeom g,
+                                                                       uint8_t* __restrict__ templ, int* __restrict__ pos,
+                                                                       int* __restrict__ out) {
+  __shared__ uint32_t win[SS_WMAX * SS_PITCH_DW];
+  __shared__ uint32_t t0[TRACK_MAX_SIDE * TS_TDW];              // T0, rows 64 bytes apart
+  __shared__ uint32_t tl[SS_LEVELS * TRACK_MAX_SIDE * TS_TDW];  // T(Lc) per level, rows 64 bytes apart, zero behind tw(Lc)
+  __shared__ uint32_t taps[SS_LEVELS * 2 * TRACK_MAX_SIDE];     // level k: 64 taps in x, then 64 in y
+  __shared__ int lv[SS_LEVELS][SS_LV];
+  __shared__ u64 red[TS_THREADS / 64];
+  uint8_t* t0b = reinterpret_cast<uint8_t*>(t0);
+  uint8_t* tlb = reinterpret_cast<uint8_t*>(tl);
+  const uint8_t* wb = reinterpret_cast<const uint8_t*>(win);
+  const int tid = threadIdx.x, tw0 = g.tw0, th0 = g.th0, R = g.R, L0 = max(tw0, th0);
+  for (int i = tid; i < tw0 * th0; i += TS_THREADS) t0b[(i / tw0) * TRACK_MAX_SIDE + i % tw0] = templ[i];
+  // a level or a position the host never saw: kept valid, so that no candidate reads outside the image
+  int L = min(max(pos[2], g.Lmin), g.Lmax);
+  int tw = track_level_side(tw0, L, L0), th = track_level_side(th0, L, L0);
+  int px = min(max(pos[0], 0), g.gw - tw), py = min(max(pos[1], 0), g.gh - th);
+  const uint8_t* lo = gray;
+  const uint8_t* hi = gray + (long)g.B * g.gh * g.gw;
+  __syncthreads();
+  for (int b = 0; b < g.B; ++b) {
+    // each level's entry (one lane) and the taps of T0 -> T(Lc) (a lane a tap)
+    if (tid < SS_LEVELS * 2 * TRACK_MAX_SIDE) {
+      const int k = tid >> 7, axis = (tid >> 6) & 1, i = tid & 63, Lc = L + k - 1;
+      const bool valid = abs(k - 1) <= g.levels && Lc >= g.Lmin && Lc <= g.Lmax;
+      const int twc = valid ? track_level_side(tw0, Lc, L0) : 0, thc = valid ? track_level_side(th0, Lc, L0) : 0;
+      if (valid && i < (axis ? thc : twc)) taps[tid] = axis ? track_resample_tap(i, th0, thc) : track_resample_tap(i, tw0, twc);
+      if ((tid & 127) == 0) {
+        int* e = lv[k];
+        const int ax = valid ? min(max(px + ((tw - twc) >> 1), 0), g.gw - twc) : 0;  // (>> 1 of a negative: the floor)
+        const int ay = valid ? min(max(py + ((th - thc) >> 1), 0), g.gh - thc) : 0;
+        const int dx_lo = max(-R, -ax), dx_hi = min(R, g.gw - twc - ax);
+        const int dy_lo = max(-R, -ay), dy_hi = min(R, g.gh - thc - ay);
+        e[0] = valid, e[1] = twc, e[2] = thc, e[3] = ax + dx_lo, e[4] = ay + dy_lo, e[5] = dx_lo, e[6] = dy_lo;
+        e[7] = valid ? dx_hi - dx_lo + 1 : 0, e[8] = valid ? dy_hi - dy_lo + 1 : 0, e[9] = (e[7] + 3) >> 2;
+        e[10] = ax, e[11] = ay;
+      }
+    }
+    __syncthreads();
+    // the union of the levels' windows, and where each level's groups start among all of them
+    int wx0 = g.gw, wy0 = g.gh, wx1 = 0, wy1 = 0, gfirst[SS_LEVELS + 1], thmax = 0;
+    gfirst[0] = 0;
+#pragma unroll
+    for (int k = 0; k < SS_LEVELS; ++k) {
+      const int* e = lv[k];
+      gfirst[k + 1] = gfirst[k] + e[9] * e[8];
+      if (!e[0]) continue;
+      wx0 = min(wx0, e[3]), wy0 = min(wy0, e[4]);
+      wx1 = max(wx1, e[3] + e[7] - 1 + e[1]), wy1 = max(wy1, e[4] + e[8] - 1 + e[2]);
+      thmax = max(thmax, e[2]);
+    }
+    const int ngroups = gfirst[SS_LEVELS];
+    const int ww = min(wx1 - wx0, SS_WMAX), wh = min(wy1 - wy0, SS_WMAX);  // (never above it: see SS_WMAX)
+    const uint8_t* seg0 = gray + ((long)b * g.gh + wy0) * g.gw + wx0;
+    const int a0 = (int)(reinterpret_cast<uintptr_t>(seg0) & 3);  // row r of the window starts (a0 + r gw) mod 4 past a dword
+    const int items = wh * SS_STAGE_DW;
+    for (int i0 = tid; i0 < items; i0 += TS_UNROLL * TS_THREADS) {
+      uint32_t v[TS_UNROLL];
+      int at[TS_UNROLL];
+#pragma unroll
+      for (int u = 0; u < TS_UNROLL; ++u) {
+        const int i = i0 + u * TS_THREADS;
+        at[u] = -1;
+        v[u] = 0;
+        if (i >= items) continue;
+        const int r = i / SS_STAGE_DW, k = i - r * SS_STAGE_DW;
+        const int al = (a0 + r * g.gw) & 3;
+        if (4 * k >= al + ww) continue;
+        at[u] = r * SS_PITCH_DW + k;
+        v[u] = track_load_dword(seg0 + (long)r * g.gw - al + 4 * k, lo, hi);
+      }
+#pragma unroll
+      for (int u = 0; u < TS_UNROLL; ++u)
+        if (at[u] >= 0) win[at[u]] = v[u];
+    }
+    // T(Lc) = resample(T0): whole dwords of a row are written, the bytes behind tw(Lc) as 0 (the tail's mask relies on it)
+#pragma unroll
+    for (int k = 0; k < SS_LEVELS; ++k) {
+      const int* e = lv[k];
+      if (!e[0]) continue;
+      const int twc = e[1], thc = e[2], tw4 = (twc + 3) & ~3;
+      for (int idx = tid; idx < tw4 * thc; idx += TS_THREADS) {
+        const int j = idx / tw4, i = idx - j * tw4;
+        int v = 0;
+        if (i < twc) {
+          const uint32_t tx = taps[k * 128 + i], ty = taps[k * 128 + 64 + j];
+          const uint8_t* r0 = t0b + (ty & 255) * TRACK_MAX_SIDE;
+          const uint8_t* r1 = t0b + ((ty >> 8) & 255) * TRACK_MAX_SIDE;
+          const int x0 = tx & 255, x1 = (tx >> 8) & 255;
+          v = track_bilinear(r0[x0], r0[x1], r1[x0], r1[x1], (int)(tx >> 16), (int)(ty >> 16));
+        }
+        tlb[(k * TRACK_MAX_SIDE + j) * TRACK_MAX_SIDE + i] = (uint8_t)v;
+      }
+    }
+    __syncthreads();
+    // work items as in track_search_kernel, over the groups of all levels; p on their sum and the tallest template
+    int p = 1, units = ((ngroups + TS_THREADS - 1) / TS_THREADS) * thmax;
+    for (int q = 2; q <= 64; q <<= 1) {
+      const int u = ((ngroups * q + TS_THREADS - 1) / TS_THREADS) * ((thmax + q - 1) / q);
+      if (u < units) p = q, units = u;
+    }
+    u64 best = ~0ull;
+    for (int it0 = 0; it0 < ngroups * p; it0 += TS_THREADS) {
+      const int item = it0 + tid, grp = item / p, part = item - grp * p;
+      const bool live = grp < ngroups;
+      const int k = !live || grp < gfirst[1] ? 0 : (grp < gfirst[2] ? 1 : 2);
+      const int* e = lv[k];
+      const int twc = e[1], thc = e[2], ncx = e[7], ngx = e[9];
+      const int local = live ? grp - (k == 0 ? 0 : (k == 1 ? gfirst[1] : gfirst[2])) : 0;
+      const int cyr = live ? local / ngx : 0, cxr = live ? (local - cyr * ngx) * 4 : 0;
+      const int nfull = twc >> 2;
+      const uint32_t tail = (1u << (8 * (twc & 3))) - 1u;
+      uint32_t cost[4] = {0, 0, 0, 0};
+      if (live) {
+        const int rpp = (thc + p - 1) / p, j1 = min(thc, (part + 1) * rpp);
+        const int xo = e[3] - wx0 + cxr, yo = e[4] - wy0 + cyr;
+        for (int j = part * rpp; j < j1; ++j) {
+          const int r = yo + j;
+          const int o = ((a0 + r * g.gw) & 3) + xo, ph = o & 3;
+          const uint32_t* row = win + r * SS_PITCH_DW + (o >> 2);
+          const uint32_t* trow = tl + (k * TRACK_MAX_SIDE + j) * TS_TDW;
+          uint32_t d0 = row[0], d1 = row[1];
+          u64 acc = 0;  // four 16-bit sums: at most 16 dwords of 4 * 255 a row
+          for (int m = 0; m < nfull; ++m) {
+            const uint32_t d2 = row[m + 2];
+            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
+            acc = __builtin_amdgcn_qsad_pk_u16_u8((u64)w1 << 32 | w0, trow[m], acc);
+            d0 = d1, d1 = d2;
+          }
+          if (twc & 3) {  // the row's last, partial dword: the window's bytes behind tw(Lc) masked, the template's are 0
+            const uint32_t d2 = row[nfull + 2];
+            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
+            const uint32_t t = trow[nfull];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) cost[i] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, i) & tail, t, cost[i]);
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) cost[i] += (uint32_t)(acc >> (16 * i)) & 0xffffu;
+        }
+      }
+      for (int off = 1; off < p; off <<= 1)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cost[i] += __shfl_xor(cost[i], off, 64);
+      if (live && part == 0) {
+        const int dy = e[6] + cyr, adl = k != 1;
+        const uint32_t area = (uint32_t)(twc * thc), bias = adl ? (uint32_t)g.penalty : 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int dx = e[5] + cxr + i;
+          if (cxr + i >= ncx) continue;
+          const uint32_t ncost = (cost[i] << 12) / area;  // cost << 12 <= 255 * 4096 * 4096 < 2^32
+          const u64 key = (u64)(ncost + bias) << 33 | (u64)adl << 32 | (u64)k << 30 | (u64)(dx * dx + dy * dy) << 16 |
+                          (u64)(dy + R) << 8 | (u64)(dx + R);
+          best = key < best ? key : best;
+        }
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const u64 other = __shfl_xor(best, off, 64);
+      best = other < best ? other : best;
+    }
+    if ((tid & 63) == 0) red[tid >> 6] = best;
+    __syncthreads();
+    best = red[0];
+    for (int k = 1; k < TS_THREADS / 64; ++k) best = red[k] < best ? red[k] : best;
+    // the winner: its level, its displacement, and its cost back from cost << 12 over the area (the area is at most 4096, so
+    // one multiple of 4096 lies in ncost * area .. ncost * area + area - 1)
+    const int kb = (int)((best >> 30) & 3), dx = (int)(best & 255) - R, dy = (int)((best >> 8) & 255) - R;
+    const int twb = lv[kb][1], thb = lv[kb][2];
+    const uint32_t areab = (uint32_t)(twb * thb);
+    const uint32_t ncost = (uint32_t)(best >> 33) - (kb != 1 ? (uint32_t)g.penalty : 0u);
+    const int cost = (int)((ncost * areab + 4095u) >> 12);
+    const int found = cost <= g.lost * (int)areab;
+    if (found) {
+      L += kb - 1, tw = twb, th = thb;
+      px = lv[kb][10] + dx, py = lv[kb][11] + dy;
+      // the taps of the window at the new box -> the seed's size
+      if (g.adapt > 0 && tid < 2 * TRACK_MAX_SIDE) {
+        const int axis = tid >> 6, i = tid & 63;
+        if (i < (axis ? th0 : tw0)) taps[tid] = axis ? track_resample_tap(i, th, th0) : track_resample_tap(i, tw, tw0);
+      }
+    }
+    __syncthreads();
+    if (found && g.adapt > 0)
+      for (int idx = tid; idx < tw0 * th0; idx += TS_THREADS) {
+        const int j = idx / tw0, i = idx - j * tw0;
+        const uint32_t tx = taps[i], ty = taps[64 + j];
+        const int ra = py - wy0 + (int)(ty & 255), rb = py - wy0 + (int)((ty >> 8) & 255);
+        const uint8_t* r0 = wb + ra * (SS_PITCH_DW * 4) + ((a0 + ra * g.gw) & 3) + (px - wx0);
+        const uint8_t* r1 = wb + rb * (SS_PITCH_DW * 4) + ((a0 + rb * g.gw) & 3) + (px - wx0);
+        const int x0 = tx & 255, x1 = (tx >> 8) & 255;
+        const int wv = track_bilinear(r0[x0], r0[x1], r1[x0], r1[x1], (int)(tx >> 16), (int)(ty >> 16));
+        uint8_t* t = t0b + j * TRACK_MAX_SIDE + i;
+        *t = (uint8_t)((*t * (8 - g.adapt) + wv * g.adapt + 4) >> 3);
+      }
+    if (tid == 0) {
+      int* o = out + 8L * b;
+      o[0] = px, o[1] = py, o[2] = tw, o[3] = th, o[4] = (int)ncost, o[5] = found, o[6] = L, o[7] = cost;
+    }
+    __syncthreads();  // the window, the templates, the taps, the levels' entries and red are the next frame's
+  }
+  for (int i = tid; i < tw0 * th0; i += TS_THREADS) templ[i] = t0b[(i / tw0) * TRACK_MAX_SIDE + i % tw0];
+  if (tid == 0) pos[0] = px, pos[1] = py, pos[2] = L;
+}
+
 static int track_frame_check(const char* who, int h, int w, int s) {
   D3F_CHECK(h > 0 && w > 0 && h <= 16384 && w <= 16384, "%s: size %d x %d outside 1..16384", who, h, w);
   D3F_CHECK(s >= 1 && s <= TRACK_MAX_STRIDE, "%s: stride %d outside 1..%d", who, s, TRACK_MAX_STRIDE);
@@ -317,13 +572,14 @@ int gray_decimate_u8_launch(const uint8_t* frames, int B, int h, int w, int s, u
 }
 
 int track_seed_u8_launch(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, uint8_t* templ, int* pos,
-                         hipStream_t stream) {
+                         bool with_level, hipStream_t stream) {
   if (int rc = track_frame_check("track_seed", h, w, s)) return rc;
   if (int rc = track_side_check("track_seed", tw, th)) return rc;
   D3F_CHECK(tx >= 0 && ty >= 0 && tx + tw <= w / s && ty + th <= h / s,
             "track_seed: box (%d, %d, %d, %d) outside the reduced image %d x %d", tx, ty, tw, th, w / s, h / s);
   D3F_CHECK((reinterpret_cast<uintptr_t>(pos) & 3) == 0, "track_seed: pos must be aligned to 4 bytes");
-  hipLaunchKernelGGL(track_seed_kernel, dim3(th), dim3(64), 0, stream, frame, w, s, tx, ty, tw, templ, pos);
+  hipLaunchKernelGGL(track_seed_kernel, dim3(th), dim3(64), 0, stream, frame, w, s, tx, ty, tw,
+                     with_level ? (tw > th ? tw : th) : 0, templ, pos);
   D3F_HIP(hipGetLastError());
   return 0;
 }
@@ -360,6 +616,46 @@ int track_template_u8_launch(const uint8_t* frames, int B, int h, int w, int s, 
   if (int rc = track_search_check(B, h / s, w / s, tw, th, search, adapt, lost, pos, out)) return rc;
   if (int rc = gray_decimate_u8_launch(frames, B, h, w, s, gray_ws, stream)) return rc;
   return track_search_u8_launch(gray_ws, B, h / s, w / s, tw, th, search, adapt, lost, templ, pos, out, stream);
+}
+
+int track_search_scale_check(int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost, int levels, int penalty,
+                             const int* pos, const int* out) {
+  if (int rc = track_search_check(B, gh, gw, tw0, th0, search, adapt, lost, pos, out)) return rc;
+  D3F_CHECK(levels >= 0 && levels <= 1, "track_search_scale: levels %d outside 0..1", levels);
+  D3F_CHECK(penalty >= 0 && penalty <= 65535, "track_search_scale: penalty %d outside 0..65535", penalty);
+  return 0;
+}
+
+int track_search_scale_u8_launch(const uint8_t* gray, int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost,
+                                 int levels, int penalty, uint8_t* templ, int* pos, int* out, hipStream_t stream) {
+  if (int rc = track_search_scale_check(B, gh, gw, tw0, th0, search, adapt, lost, levels, penalty, pos, out)) return rc;
+  if (B == 0) return 0;
+  // the valid levels around the seed's own, which the check above has found valid: the sizes grow with the level
+  const int L0 = tw0 > th0 ? tw0 : th0;
+  const auto valid = [&](int L) {
+    const int tw = track_level_side(tw0, L, L0), th = track_level_side(th0, L, L0);
+    return L >= 1 && tw >= TRACK_MIN_SIDE && th >= TRACK_MIN_SIDE && tw <= TRACK_MAX_SIDE && th <= TRACK_MAX_SIDE && tw <= gw &&
+           th <= gh;
+  };
+  int Lmin = L0, Lmax = L0;
+  while (valid(Lmin - 1)) --Lmin;
+  while (valid(Lmax + 1)) ++Lmax;
+  const ScaleGeom g = {B, gh, gw, tw0, th0, search, adapt, lost, levels, penalty, Lmin, Lmax};
+  hipLaunchKernelGGL(track_search_scale_kernel, dim3(1), dim3(TS_THREADS), 0, stream, gray, g, templ, pos, out);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+int track_template_scale_u8_launch(const uint8_t* frames, int B, int h, int w, int s, int tw0, int th0, int search, int adapt,
+                                   int lost, int levels, int penalty, uint8_t* templ, int* pos, uint8_t* gray_ws, int* out,
+                                   hipStream_t stream) {
+  // both refusals before either launch
+  if (int rc = gray_decimate_check(B, h, w, s)) return rc;
+  D3F_CHECK(h / s > 0 && w / s > 0, "track_template_scale: stride %d leaves nothing of %d x %d", s, h, w);
+  if (int rc = track_search_scale_check(B, h / s, w / s, tw0, th0, search, adapt, lost, levels, penalty, pos, out)) return rc;
+  if (int rc = gray_decimate_u8_launch(frames, B, h, w, s, gray_ws, stream)) return rc;
+  return track_search_scale_u8_launch(gray_ws, B, h / s, w / s, tw0, th0, search, adapt, lost, levels, penalty, templ, pos, out,
+                                      stream);
 }
 
 }  // namespace d3f

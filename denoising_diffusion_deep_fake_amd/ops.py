@@ -956,6 +956,7 @@ def color_coef_smooth(coef, sums_to, n, state, strength=_lib.TEMPORAL_STRENGTH):
 # ---- template tracker: the face box of a track file from hand-set key boxes (include/d3f_hip.h: "Template tracker") ----
 TRACK_TEMPLATE_SIDE, TRACK_SEARCH, TRACK_ADAPT, TRACK_LOST = (_lib.TRACK_TEMPLATE_SIDE, _lib.TRACK_SEARCH, _lib.TRACK_ADAPT,
                                                               _lib.TRACK_LOST)
+TRACK_SCALE_PENALTY = _lib.TRACK_SCALE_PENALTY
 
 
 def gray_decimate_u8(frames, s, out=None):
@@ -1013,14 +1014,17 @@ def track_template_geometry(h, w, face, side=TRACK_TEMPLATE_SIDE):
 class TrackState:
     """The state of the template tracker: `templ`, the template's th rows of tw bytes packed at the front of 64 * 64 uint8,
     and `pos` int32 [2], both on the device; `geometry`, what `track_template_geometry` gave at the seed, and the frame
-    size (h, w) it was given for, on the host; a grey workspace grown on demand; `seeded`."""
+    size (h, w) it was given for, on the host; a grey workspace grown on demand; `seeded`.  `pos_level` int32 [3] is `pos`
+    with the scale search's level behind it (`pos` is a view of its front): the seed sets it to L0 = max(tw, th), only
+    `track_template_scale_u8` reads and moves it, and with it `templ` stays at the seed's size."""
 
     def __init__(self, device="cuda"):
         device = torch.device(device)
         if device.type != "cuda":
             raise _lib.D3FError("libd3f_hip ops need tensors on the HIP device (no CPU fallback)")
         self.templ = torch.zeros((_lib.TRACK_MAX_SIDE * _lib.TRACK_MAX_SIDE,), dtype=torch.uint8, device=device)
-        self.pos = torch.zeros((2,), dtype=torch.int32, device=device)
+        self.pos_level = torch.zeros((3,), dtype=torch.int32, device=device)
+        self.pos = self.pos_level[:2]
         self.geometry = None
         self.h = self.w = 0
         self.gray = None
@@ -1034,7 +1038,8 @@ class TrackState:
 
 def track_seed(state, frame, face, side=TRACK_TEMPLATE_SIDE):
     """(re-)seed `state` from the face box (fx, fy, fw, fh) marked in `frame`, uint8 BGR [h, w, 3] on the HIP device: the
-    template is the reduced grey of the box (include/d3f_hip.h: d3f_track_seed_u8).  Returns the geometry."""
+    template is the reduced grey of the box, the level the seed's own (include/d3f_hip.h: d3f_track_seed_scale_u8, the
+    launch of d3f_track_seed_u8 with the level stored beside the position).  Returns the geometry."""
     if not isinstance(state, TrackState):
         raise ValueError("track_seed: state must be a TrackState")
     if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
@@ -1045,7 +1050,8 @@ def track_seed(state, frame, face, side=TRACK_TEMPLATE_SIDE):
     if _dev(frame) != state.templ.device:
         raise ValueError("track_seed expects the frame on the state's device")
     x = frame.contiguous()
-    check(_lib.lib().d3f_track_seed_u8(ptr(x), h, w, s, tx, ty, tw, th, ptr(state.templ), ptr(state.pos), stream_ptr()))
+    check(_lib.lib().d3f_track_seed_scale_u8(ptr(x), h, w, s, tx, ty, tw, th, ptr(state.templ), ptr(state.pos_level),
+                                             stream_ptr()))
     state.geometry, state.h, state.w, state.seeded = geometry, h, w, True
     return geometry
 
@@ -1079,6 +1085,59 @@ def track_faces(rows, state):
     the frame's row says not found.  state: the TrackState the rows came from, or the geometry it had then"""
     s, _, _, _, _, ox, oy, fw, fh = getattr(state, "geometry", state)
     return [(int(px) * s + ox, int(py) * s + oy, fw, fh) if int(found) else None for px, py, _, found in rows]
+
+
+def track_template_scale_u8(frames, state, search=TRACK_SEARCH, adapt=TRACK_ADAPT, lost=TRACK_LOST, levels=1,
+                            penalty=TRACK_SCALE_PENALTY):
+    """`track_template_u8` with the scale search: the box may change its level, one sample on the template's longer side,
+    by up to `levels` (0 or 1) a frame; `penalty` (0..65535, in 1/4096 grey levels per sample) is what a change of level
+    must win by -> int32 [B, 8] on the device, a row (px, py, tw, th, ncost, found, L, cost) per frame in the reduced image
+    (`track_scale_faces` turns host rows into boxes).  The state's template stays at the seed's size and its level moves;
+    do not mix calls of this and of `track_template_u8` on one state between two seeds.  One device call: the reduced grey
+    of every frame, then the search inside one kernel (include/d3f_hip.h: d3f_track_template_scale_u8)."""
+    if not isinstance(state, TrackState) or not state.seeded:
+        raise ValueError("track_template_scale_u8: state must be a TrackState seeded by track_seed")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError("track_template_scale_u8 expects uint8 frames [B, h, w, 3]")
+    B, h, w, _ = frames.shape
+    if (h, w) != (state.h, state.w):
+        raise ValueError(f"track_template_scale_u8: frames of {h} x {w}, the state was seeded on {state.h} x {state.w}")
+    if _dev(frames) != state.templ.device:
+        raise ValueError("track_template_scale_u8 expects the frames on the state's device")
+    s, _, _, tw, th = state.geometry[:5]
+    out = torch.empty((B, 8), dtype=torch.int32, device=frames.device)
+    if B > 0:
+        x = frames.contiguous()
+        ws = state.workspace(B * (h // s) * (w // s))
+        check(_lib.lib().d3f_track_template_scale_u8(ptr(x), B, h, w, s, tw, th, int(search), int(adapt), int(lost),
+                                                     int(levels), int(penalty), ptr(state.templ), ptr(state.pos_level),
+                                                     ptr(ws), ptr(out), stream_ptr()))
+    return out
+
+
+def track_scale_faces(rows, state, frame=None):
+    """host rows (px, py, tw, th, ncost, found, L, cost) of `track_template_scale_u8` -> a list of face boxes (x, y, w, h) in
+    frame pixels, None where the frame's row says not found: the seed's face scaled by L / L0 about the centre of the
+    reduced box, then moved so that at least one of its pixels lies inside the frame (`track_crop_box` accepts a face that
+    sticks out).  state: the TrackState the rows came from, or the geometry it had then with frame=(h, w) -- a geometry
+    alone says nothing of the frame's size, and the boxes are then left where they fall"""
+    s, _, _, tw0, th0, ox, oy, fw, fh = getattr(state, "geometry", state)
+    if frame is None:
+        frame = (state.h, state.w) if hasattr(state, "h") else None
+    L0 = max(tw0, th0)
+    boxes = []
+    for px, py, tw, th, _, found, L, _ in rows:
+        if not int(found):
+            boxes.append(None)
+            continue
+        px, py, tw, th, L = int(px), int(py), int(tw), int(th), int(L)
+        fw1, fh1 = (fw * L + L0 // 2) // L0, (fh * L + L0 // 2) // L0
+        x = ((2 * px + tw) * s + 2 * ox + fw - tw0 * s - fw1) // 2
+        y = ((2 * py + th) * s + 2 * oy + fh - th0 * s - fh1) // 2
+        if frame is not None:
+            x, y = min(max(x, 1 - fw1), frame[1] - 1), min(max(y, 1 - fh1), frame[0] - 1)
+        boxes.append((x, y, fw1, fh1))
+    return boxes
 
 
 def paste_resize_cubic_u8(patch, frames, box=None, feather=0, out=None, color=None, boxes=None):

@@ -1,11 +1,14 @@
 """Write the face-box track of a video from boxes marked by hand at key frames: the file that
 put_video_through_fake_model --track and video_to_center_cropped_images --track read.  There is no detector: the box of a
 key frame is the template, and the device follows it from frame to frame (ops.track_template_u8: a reduced grey image of
-every frame, then the smallest sum of absolute differences in a search window).  There is no scale search either: where
-the face changes size, where the tracker drifts and behind a cut, mark another key frame -- the tracker is seeded anew
-at every key.
+every frame, then the smallest sum of absolute differences in a search window).  The box keeps the key's size unless
+--scale is given: then the size is searched too, one sample of the template's longer side a frame (about 2 %), and the
+box follows a face that walks towards the camera or away from it (ops.track_template_scale_u8).  What remains: the
+template's longer side stays within 4..64 samples at the key's stride (a third over the default side of 48), and there
+is no rotation search.  Where the face outgrows that, turns, where the tracker drifts and behind a cut, mark another key
+frame -- the tracker is seeded anew at every key.
 
-    python -m d3f.script_tools.track_face_box VIDEO --key K X Y W H [--key ...] [-o FILE]
+    python -m d3f.script_tools.track_face_box VIDEO --key K X Y W H [--key ...] [-o FILE] [--scale]
 """
 import argparse
 from pathlib import Path
@@ -29,6 +32,8 @@ def main():
         adapt=args.adapt,
         lost=args.lost,
         template_side=args.template_side,
+        scale=args.scale,
+        scale_penalty=args.scale_penalty,
         )
     found = sum(box is not None for box in tracker.track)
     print(f"{tracker.output_path}: {len(tracker.track)} frames, the face found in {found}")
@@ -56,9 +61,17 @@ def parse_command_line_arguments(argv=None):
                         help=f"the template's longer side in samples, 4..{_lib.TRACK_MAX_SIDE} (default "
                              f"{ops.TRACK_TEMPLATE_SIDE})")
 
+    parser.add_argument("--scale", action="store_true",
+                        help="search the size of the box too, one level (one sample of the template's longer side) a frame; "
+                             "without it the box keeps the key's size")
+    parser.add_argument("--scale-penalty", type=int, default=ops.TRACK_SCALE_PENALTY, metavar="P",
+                        help=f"with --scale: what a change of size must win by, in 1/4096 grey levels per sample, "
+                             f"0..{_lib.TRACK_MAX_SCALE_PENALTY} (default {ops.TRACK_SCALE_PENALTY})")
+
     args = parser.parse_args(argv)
     try:
-        check_settings(sorted_keys(args.key), args.batch_frames, args.search, args.adapt, args.lost, args.template_side)
+        check_settings(sorted_keys(args.key), args.batch_frames, args.search, args.adapt, args.lost, args.template_side,
+                       args.scale, args.scale_penalty)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -82,12 +95,16 @@ def sorted_keys(keys):
     return out
 
 
-def check_settings(keys, batch_frames, search, adapt, lost, template_side):
+def check_settings(keys, batch_frames, search, adapt, lost, template_side, scale=False,
+                   scale_penalty=ops.TRACK_SCALE_PENALTY):
     if int(batch_frames) < 1:
         raise ValueError("--batch-frames is at least 1")
+    if not isinstance(scale, bool):
+        raise ValueError(f"--scale is True or False, not {scale!r}")
     for name, value, low, high in (("--search", search, 1, _lib.TRACK_MAX_SEARCH), ("--adapt", adapt, 0, 8),
                                    ("--lost", lost, 0, 255),
-                                   ("--template-side", template_side, _lib.TRACK_MIN_SIDE, _lib.TRACK_MAX_SIDE)):
+                                   ("--template-side", template_side, _lib.TRACK_MIN_SIDE, _lib.TRACK_MAX_SIDE),
+                                   ("--scale-penalty", scale_penalty, 0, _lib.TRACK_MAX_SCALE_PENALTY)):
         if isinstance(value, bool) or not isinstance(value, int) or not low <= value <= high:
             raise ValueError(f"{name} is an integer in {low}..{high}, not {value!r}")
     return keys
@@ -108,19 +125,22 @@ class TrackFaceBox():
     video file (cv2 is not needed then); sink=: a callable that takes each frame's box, (x, y, w, h) or None -- without an
     output_path no file is written then.  .track holds the result, entry k for frame k: None before the first key and where
     the face was not found, the key's own box (clipped to the frame) at a key frame.  A batch is one upload, one device call
-    (one more, and a seed, per key frame inside it) and one small copy back; the result does not depend on batch_frames."""
+    (one more, and a seed, per key frame inside it) and one small copy back; the result does not depend on batch_frames.
+    scale=True: the size of the box is searched too (ops.track_template_scale_u8), scale_penalty what a change of size must
+    win by; every key sets the size anew."""
 
     def __init__(self, video_path, keys, output_path=None, batch_frames=8, frames=None, sink=None, device="cuda",
                  search=ops.TRACK_SEARCH, adapt=ops.TRACK_ADAPT, lost=ops.TRACK_LOST,
-                 template_side=ops.TRACK_TEMPLATE_SIDE):
+                 template_side=ops.TRACK_TEMPLATE_SIDE, scale=False, scale_penalty=ops.TRACK_SCALE_PENALTY):
 
         self.video_path = Path(video_path)
-        self.keys = check_settings(sorted_keys(keys), batch_frames, search, adapt, lost, template_side)
+        self.keys = check_settings(sorted_keys(keys), batch_frames, search, adapt, lost, template_side, scale, scale_penalty)
         self.batch_frames = int(batch_frames)
         self.frames = frames
         self.sink = sink
         self.device = device
         self.search, self.adapt, self.lost, self.template_side = search, adapt, lost, template_side
+        self.scale, self.scale_penalty = scale, scale_penalty
         if output_path is not None:
             self.output_path = Path(output_path)
         elif sink is None:
@@ -142,9 +162,12 @@ class TrackFaceBox():
 
     def header(self):
         keys = ", ".join("{} {} {} {} {}".format(k, *box) for k, box in self.keys.items())
-        return (f"track_face_box {self.video_path.name}: x y w h per frame, - where the face was not found",
-                f"keys (frame x y w h): {keys}",
-                f"search {self.search}, adapt {self.adapt}, lost {self.lost}, template side {self.template_side}")
+        lines = (f"track_face_box {self.video_path.name}: x y w h per frame, - where the face was not found",
+                 f"keys (frame x y w h): {keys}",
+                 f"search {self.search}, adapt {self.adapt}, lost {self.lost}, template side {self.template_side}")
+        if self.scale:
+            lines += (f"scale search: one level a frame, penalty {self.scale_penalty}",)
+        return lines
 
     def track_video(self):
 
@@ -174,8 +197,7 @@ class TrackFaceBox():
         start = 0
         for cut in cuts + [n]:
             if cut > start and state.seeded:
-                parts.append((start, ops.track_template_u8(dev[start:cut], state, self.search, self.adapt, self.lost),
-                              state.geometry))
+                parts.append((start, self.follow(dev[start:cut], state), state.geometry))
             if cut < n:
                 geometry = ops.track_seed(state, dev[cut], self.keys[first + cut], self.template_side)
                 s, tx, ty, _, _, ox, oy, fw, fh = geometry
@@ -186,9 +208,17 @@ class TrackFaceBox():
             at = 0
             for index, part, geometry in parts:
                 count = len(part)
-                boxes[index:index + count] = ops.track_faces(rows[at:at + count], geometry)
+                if self.scale:
+                    boxes[index:index + count] = ops.track_scale_faces(rows[at:at + count], geometry, dev.shape[1:3])
+                else:
+                    boxes[index:index + count] = ops.track_faces(rows[at:at + count], geometry)
                 at += count
         return boxes
+
+    def follow(self, dev, state):
+        if self.scale:
+            return ops.track_template_scale_u8(dev, state, self.search, self.adapt, self.lost, 1, self.scale_penalty)
+        return ops.track_template_u8(dev, state, self.search, self.adapt, self.lost)
 
 
 if __name__ == "__main__":

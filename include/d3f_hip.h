@@ -692,7 +692,8 @@ int d3f_temporal_flag_set(int32_t* flag, int value, void* stream);
 /* Template tracker: the face box of a --track file from boxes set by hand at key frames, with no detector.  Integer
  * arithmetic throughout, so the result does not depend on the order of evaluation; tests/track_restatement.py restates it in
  * numpy and Python integers and every comparison is exact.  The defaults (D3F_TRACK_TEMPLATE_SIDE, _SEARCH, _ADAPT, _LOST) are
- * design choices, not measurements.  There is no scale or rotation search: a face that changes size wants another key box.
+ * design choices, not measurements.  The plain entries follow a template of fixed size; the _scale_ entries below search
+ * the size too.  There is no rotation search.
  *
  * d3f_gray_decimate_u8: frames [B][h][w][3] uint8 BGR, packed, any byte address -> out [B][gh][gw] uint8, gh = h / s,
  * gw = w / s (partial blocks at the right and bottom are dropped), out[y][x] = (sum over the s x s block of B + 2 G + R) /
@@ -731,6 +732,47 @@ int d3f_track_search_u8(const uint8_t* gray, int B, int gh, int gw, int tw, int 
                         uint8_t* templ, int32_t* pos, int32_t* out, void* stream);
 int d3f_track_template_u8(const uint8_t* frames, int B, int h, int w, int s, int tw, int th, int search, int adapt, int lost,
                           uint8_t* templ, int32_t* pos, uint8_t* gray_ws, int32_t* out, void* stream);
+
+/* Template tracker, scale search (opt-in; the entries above are untouched by it): the box follows a face that grows or
+ * shrinks, one level a frame.  tests/track_scale_restatement.py restates it; DESIGN.md section 4 holds the specification.
+ * All integers, / is the floor.
+ * Levels: the seed's template is tw0 x th0, L0 = max(tw0, th0); level L has tw(L) = (tw0 L + L0 / 2) / L0 and th(L) likewise
+ * (one level is one sample on the longer side); L is valid when 4 <= tw(L), th(L) <= 64, tw(L) <= gw, th(L) <= gh.  The state:
+ * templ, the template T0, always tw0 x th0, packed as above; pos int32[3] = (x, y, L), (x, y) the corner of the box at L's size.
+ * resample(A, n_in -> n_out) per axis, bilinear at pixel centres, 6-bit weights: num = (2 i + 1) n_in - n_out, den = 2 n_out;
+ * num < 0: i0 = 0, f = 0, else i0 = num / den, f = ((num - i0 den) 64) / den; i1 = min(i0 + 1, n_in - 1), i0 = min(i0, n_in - 1);
+ * v = (A[y0][x0] (64 - fy)(64 - fx) + A[y0][x1] (64 - fy) fx + A[y1][x0] fy (64 - fx) + A[y1][x1] fy fx + 2048) >> 12.
+ * d3f_track_seed_scale_u8: d3f_track_seed_u8 with pos int32[3], pos[2] = L0 (one launch, the same kernel).
+ * d3f_track_search_scale_u8: gray [B][gh][gw]; templ and pos read at the start and written at the end (a level outside the
+ * valid ones, then a position outside the image, is moved inside first).  For each frame in order:
+ *   - candidate levels Lc = L + dL, dL in -levels..levels, the invalid ones dropped; T(Lc) = resample(T0 -> th(Lc) x tw(Lc));
+ *     the anchor keeps the centre, ax = x + (tw(L) - tw(Lc)) / 2 clamped into 0..gw - tw(Lc), ay likewise;
+ *   - candidates (dx, dy) in [-search, search]^2 with the box at (ax + dx, ay + dy) inside the image;
+ *   - cost = sum |gray - T(Lc)| over the box, ncost = (cost << 12) / (tw(Lc) th(Lc)) (1/4096 grey levels per sample);
+ *   - the smallest (ncost + penalty |dL|, |dL|, dL + 1, dx dx + dy dy, dy + search, dx + search) wins: fields of 21, 1, 2, 14, 8
+ *     and 8 bits of one unsigned 64-bit key.  Ties go to no change of size, then to shrinking, then as above;
+ *   - found = cost <= lost tw(Lc) th(Lc), on the winner's own cost.  Found: L = Lc, (x, y) = anchor + (dx, dy),
+ *     W0 = resample(the window at the new box -> th0 x tw0), T0 = (T0 (8 - adapt) + W0 adapt + 4) >> 3.  Not found: x, y, L and
+ *     T0 stay exactly as they were;
+ *   - out[b] = (x, y, tw(L), th(L), ncost, found, L, cost), int32[8], after the update.
+ * levels is 0 (the search of d3f_track_search_u8: the same positions, costs and template) or 1; penalty, in 1/4096 grey
+ * levels, 0..65535, is hysteresis against size jitter on flat content (D3F_TRACK_SCALE_PENALTY, an eighth of a level: a
+ * design choice, not a measurement).  The stride is fixed at the seed, so the longer side can grow to 64 samples and shrink
+ * to 4; beyond that the level stays at its limit, and another key box seeds at a new stride.
+ * Back in the frame, with the seed's geometry: fw' = (fw L + L0 / 2) / L0, x' = ((2 x + tw(L)) s + 2 ox + fw - tw0 s - fw') / 2,
+ * fh' and y' likewise (ops.track_scale_faces); at L0 that is (x s + ox, y s + oy, fw, fh).
+ * d3f_track_template_scale_u8: d3f_gray_decimate_u8 into gray_ws, then d3f_track_search_scale_u8: two launches in one call.
+ * B == 0 touches nothing.  Refused before any device call: what the entries above refuse, levels outside 0..1, penalty
+ * outside 0..65535. */
+#define D3F_TRACK_SCALE_PENALTY 512
+int d3f_track_seed_scale_u8(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, uint8_t* templ,
+                            int32_t* pos, void* stream);
+int d3f_track_search_scale_u8(const uint8_t* gray, int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost,
+                              int levels, int penalty, uint8_t* templ, int32_t* pos /* int32[3]: x, y, L */,
+                              int32_t* out /* [B][8] */, void* stream);
+int d3f_track_template_scale_u8(const uint8_t* frames, int B, int h, int w, int s, int tw0, int th0, int search, int adapt,
+                                int lost, int levels, int penalty, uint8_t* templ, int32_t* pos, uint8_t* gray_ws,
+                                int32_t* out, void* stream);
 
 /* log_batch_as_image_grid of the three LitModules (d3f/train_deep_fake/lit_module.py:235-249,
  * d3f/train_denoiser/lit_module.py:157-171, d3f/balance_training_images/lit_module.py:197-211):

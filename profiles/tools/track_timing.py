@@ -3,7 +3,8 @@
   decimate : d3f_gray_decimate_u8 alone, stride 4 and 8, B = 1 and B = 8, next to its byte bound: every frame byte read
              once and the reduced image written once, 3 h w + gh gw bytes per frame at 6.3 TB/s achievable HBM
   search   : d3f_track_search_u8 alone on a reduced image of 270 x 480, a 48 x 48 template, search 16 (1089 candidates a
-             frame), B = 1 and B = 8: one workgroup, the frames in order inside the kernel
+             frame), B = 1 and B = 8: one workgroup, the frames in order inside the kernel; beside it, in the same rounds,
+             d3f_track_search_scale_u8 at the same shape with levels = 1 (three levels a frame) and levels = 0
   tool     : ops.track_template_u8 (decimate + search, what track_face_box runs per batch once the frames are on the
              device) for a 190 x 190 face (stride 4, a 47 x 47 template), B = 1 and B = 8, next to
              Unet.predict_frames_full_u8 on the same frames (448 x 448, eager): the share the tracking pass is of the render
@@ -38,7 +39,8 @@ def main():
     g = torch.Generator().manual_seed(1)
     h, w = RAW
     result = {"raw": list(RAW), "precision": args.precision, "digest": _lib.built_digest(), "iters": args.iters,
-              "rounds": args.rounds, "decimate_us_per_frame": {}, "search_us_per_frame": {}, "tool_us_per_frame": {}}
+              "rounds": args.rounds, "decimate_us_per_frame": {}, "search_us_per_frame": {}, "search_scale_us_per_frame": {},
+              "search_scale_levels0_us_per_frame": {}, "tool_us_per_frame": {}}
     torch.manual_seed(0)
     net = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
     lib = _lib.lib()
@@ -68,9 +70,29 @@ def main():
             _lib.check(lib.d3f_track_search_u8(_lib.ptr(grey[4]), B, gh, gw, 48, 48, ops.TRACK_SEARCH, ops.TRACK_ADAPT,
                                                ops.TRACK_LOST, _lib.ptr(templ), _lib.ptr(pos), _lib.ptr(rows),
                                                _lib.stream_ptr()))
-        med, lo, hi = compare({"search": search}, args.warmup, args.iters, args.rounds)["search"]
+        # the scale search on the same image and template, next to it in the same rounds: levels = 1 (three levels: 3267
+        # candidates and four resamples a frame) and levels = 0 (the plain search's candidates through the new kernel)
+        # (a state each: the level that levels = 1 ends at must not become the size that levels = 0 is timed at)
+        state_scale = {levels: (templ.clone(), torch.tensor([200, 100, 48], dtype=torch.int32, device="cuda"))
+                       for levels in (0, 1)}
+        rows_scale = {levels: torch.empty((B, 8), dtype=torch.int32, device="cuda") for levels in (0, 1)}
+
+        def search_scale(levels):
+            _lib.check(lib.d3f_track_search_scale_u8(_lib.ptr(grey[4]), B, gh, gw, 48, 48, ops.TRACK_SEARCH, ops.TRACK_ADAPT,
+                                                     ops.TRACK_LOST, levels, ops.TRACK_SCALE_PENALTY,
+                                                     _lib.ptr(state_scale[levels][0]), _lib.ptr(state_scale[levels][1]),
+                                                     _lib.ptr(rows_scale[levels]), _lib.stream_ptr()))
+        forms = {"search": search, "search_scale": lambda: search_scale(1), "search_scale_levels0": lambda: search_scale(0)}
+        t = compare(forms, args.warmup, args.iters, args.rounds)
+        med, lo, hi = t["search"]
         print(f"search 48x48 R16 B{B}: {med / B:8.2f} us per frame (min {lo / B:.2f}, max {hi / B:.2f}); rows {rows[0].tolist()}")
         result["search_us_per_frame"][f"B{B}"] = {"us": round(med / B, 2), "min": round(lo / B, 2), "max": round(hi / B, 2)}
+        for name, levels in (("search_scale", 1), ("search_scale_levels0", 0)):
+            m, lo, hi = t[name]
+            print(f"{name} 48x48 R16 B{B}: {m / B:8.2f} us per frame (min {lo / B:.2f}, max {hi / B:.2f}), {m / med:.2f} times "
+                  f"the plain search; rows {rows_scale[levels][0].tolist()}")
+            result[f"{name}_us_per_frame"][f"B{B}"] = {"us": round(m / B, 2), "min": round(lo / B, 2), "max": round(hi / B, 2),
+                                                       "times_plain": round(m / med, 3)}
         # the tool's device call against the render of the same frames
         state = ops.TrackState()
         geometry = ops.track_seed(state, raw[0], FACE)
