@@ -34,6 +34,25 @@ def color_match_mode(color_match):
     return COLOR_MATCH_MODES[color_match]
 
 
+BLEND_FEATHER, BLEND_MULTIBAND = 0, 1  # D3F_BLEND_*: how the full-frame entry blends the fake into the frame
+BLEND_MODES = {None: BLEND_FEATHER, "feather": BLEND_FEATHER, "multiband": BLEND_MULTIBAND}
+MULTIBAND_MAX_LEVELS = 6  # D3F_MULTIBAND_MAX_LEVELS
+
+
+def blend_mode(blend):
+    """the D3F_BLEND_* code of None / "feather" / "multiband"; anything else is a ValueError"""
+    if not (blend is None or isinstance(blend, str)) or blend not in BLEND_MODES:
+        raise ValueError(f"blend is None, 'feather' or 'multiband', not {blend!r}")
+    return BLEND_MODES[blend]
+
+
+def blend_levels(levels):
+    """the levels of a multiband blend as an int; anything but an integer in 1..D3F_MULTIBAND_MAX_LEVELS is a ValueError"""
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= MULTIBAND_MAX_LEVELS:
+        raise ValueError(f"blend levels: an integer in 1..{MULTIBAND_MAX_LEVELS}, not {levels!r}")
+    return levels
+
+
 TEMPORAL_STRENGTH, TEMPORAL_THRESHOLD = 0.75, 8  # D3F_TEMPORAL_*: design choices, not measurements
 # D3F_TRACK_*: the template tracker's limits, and its defaults (design choices, not measurements)
 TRACK_MAX_SIDE, TRACK_MAX_SEARCH, TRACK_MAX_STRIDE, TRACK_MIN_SIDE = 64, 64, 32, 4
@@ -141,6 +160,8 @@ PROTOTYPES = {
     "d3f_unet_set_frame_temporal": (_i, [_p, _f, _i]),
     "d3f_unet_frame_temporal": (_i, [_p, C.POINTER(_f), C.POINTER(_i)]),
     "d3f_unet_frame_temporal_reset": (_i, [_p, _p]),
+    "d3f_unet_set_frame_blend": (_i, [_p, _i, _i]),
+    "d3f_unet_frame_blend": (_i, [_p, C.POINTER(_i)]),
     "d3f_unet_num_params": (_i, [_p]),
     "d3f_unet_param_info": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(C.c_int32), C.POINTER(_i), C.POINTER(_i64)]),
     "d3f_unet_param_floats": (_i64, [_p]),
@@ -173,6 +194,12 @@ PROTOTYPES = {
     "d3f_channel_sums_u8": (_i, [_p, _i, _i, _i, _i64, _p, _p]),
     "d3f_color_match_coef": (_i, [_p, _p, _i, _i64, _p, _p]),
     "d3f_paste_resize_cubic_color_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "d3f_paste_multiband_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "d3f_paste_multiband_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i64, _p, _p]),
+    "d3f_paste_multiband_color_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i64, _p, _p]),
+    "d3f_paste_multiband_boxes_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, C.POINTER(C.c_int32), _i, _i, _p, _i64, _p, _p]),
+    "d3f_paste_multiband_color_boxes_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, C.POINTER(C.c_int32), _i, _i, _p, _p, _i64, _p,
+                                                _p]),
     "d3f_temporal_filter_u8": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _p, _p, _p, _f, _i, _p]),
     "d3f_color_coef_smooth": (_i, [_p, _p, _i, _i64, _f, _p, _p, _p, _p]),
     "d3f_temporal_flag_set": (_i, [_p, _i, _p]),

@@ -229,6 +229,18 @@ int d3f_unet_frame_temporal_reset(d3f_unet_t h, void* stream) {
   if (int rc = frame_handle(h, "unet_frame_temporal_reset")) return rc;
   return h->e.frame_temporal_reset((hipStream_t)stream);
 }
+static_assert(D3F_BLEND_FEATHER == UnetEngine::FRAME_BLEND_FEATHER && D3F_BLEND_MULTIBAND == UnetEngine::FRAME_BLEND_MULTIBAND &&
+                  D3F_MULTIBAND_MAX_LEVELS == MULTIBAND_MAX_LEVELS,
+              "d3f_hip.h states the blend modes and the most levels");
+int d3f_unet_set_frame_blend(d3f_unet_t h, int mode, int levels) {
+  if (int rc = frame_handle(h, "unet_set_frame_blend")) return rc;
+  return h->e.set_frame_blend(mode, levels);
+}
+int d3f_unet_frame_blend(d3f_unet_t h, int* levels) {
+  if (!h) return -1;
+  if (levels) *levels = h->e.frame_blend_levels();
+  return h->e.frame_blend();
+}
 int d3f_unet_num_params(d3f_unet_t h) { return h ? (int)h->e.params.size() : -1; }
 int d3f_unet_param_info(d3f_unet_t h, int i, char* name, int name_cap, int32_t shape[4], int* ndim,
                         int64_t* offset) {
@@ -862,6 +874,46 @@ int d3f_paste_resize_cubic_color_boxes_u8(const uint8_t* patch, int B, int H, in
   D3F_CHECK(patch && frame && out && coef, "paste_resize_cubic_color_boxes_u8: null argument");
   return paste_resize_cubic_color_boxes_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, boxes,
                                                   feather, coef, out, (hipStream_t)stream);
+}
+
+int64_t d3f_paste_multiband_workspace_bytes(int B, int cw_max, int ch_max, int levels) {
+  return paste_multiband_workspace_bytes(B, cw_max, ch_max, levels);
+}
+
+int d3f_paste_multiband_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes, const uint8_t* frame,
+                           int src_h, int src_w, int x1, int y1, int cw, int ch, int feather, int levels, void* workspace,
+                           int64_t workspace_bytes, uint8_t* out, void* stream) {
+  D3F_CHECK(patch && frame && out, "paste_multiband_u8: null argument");
+  return paste_multiband_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, x1, y1, cw, ch, nullptr,
+                                   feather, levels, nullptr, false, workspace, (long)workspace_bytes, out,
+                                   (hipStream_t)stream);
+}
+
+int d3f_paste_multiband_color_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                 const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather,
+                                 int levels, const float* coef, void* workspace, int64_t workspace_bytes, uint8_t* out,
+                                 void* stream) {
+  D3F_CHECK(patch && frame && out && coef, "paste_multiband_color_u8: null argument");
+  return paste_multiband_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, x1, y1, cw, ch, nullptr,
+                                   feather, levels, coef, true, workspace, (long)workspace_bytes, out, (hipStream_t)stream);
+}
+
+int d3f_paste_multiband_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                 const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather, int levels,
+                                 void* workspace, int64_t workspace_bytes, uint8_t* out, void* stream) {
+  D3F_CHECK(patch && frame && out && boxes, "paste_multiband_boxes_u8: null argument");
+  return paste_multiband_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, 0, 0, 0, 0, boxes,
+                                   feather, levels, nullptr, false, workspace, (long)workspace_bytes, out,
+                                   (hipStream_t)stream);
+}
+
+int d3f_paste_multiband_color_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                       const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
+                                       int levels, const float* coef, void* workspace, int64_t workspace_bytes, uint8_t* out,
+                                       void* stream) {
+  D3F_CHECK(patch && frame && out && coef && boxes, "paste_multiband_color_boxes_u8: null argument");
+  return paste_multiband_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, 0, 0, 0, 0, boxes,
+                                   feather, levels, coef, true, workspace, (long)workspace_bytes, out, (hipStream_t)stream);
 }
 
 int d3f_temporal_filter_u8(const uint8_t* real, int64_t real_row_stride_bytes, uint8_t* fake, int64_t fake_row_stride_bytes,

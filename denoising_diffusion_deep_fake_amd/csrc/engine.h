@@ -115,6 +115,7 @@ class UnetEngine {
   // full_out null is d3f_unet_predict_frames_u8 and ends there.  Otherwise (d3f_unet_predict_frames_full_u8) the fake half
   // is resized back to the box and blended into raw_in over `feather` pixels -> full_out [B][src_h][src_w][3]: one paste
   // launch, or with set_frame_color_match sums -> coefficients -> [their smoothing] -> the paste in its colour form.
+  // With set_frame_blend(FRAME_BLEND_MULTIBAND) the paste is the multiband sequence instead (multiband.hip), in either form.
   // full_out == raw_in pastes in place, eager only: a replay would read frames it has overwritten.
   struct FrameCall {
     const uint8_t* raw_in;
@@ -162,7 +163,7 @@ class UnetEngine {
   // A pair's two networks share the setting.  A change drops the captured graphs, as a pointer change does.
   int set_head_activation(int act);
   int head_activation() const { return head_act_; }
-  // The three settings of predict_frames.  Each default gives exactly the launches of an engine without the setting; a
+  // The settings of predict_frames.  Each default gives exactly the launches of an engine without the setting; a
   // change drops the two captured frame graphs; device memory a setting needs is the engine's own, allocated at its first
   // switch away from the default and freed with the engine.
   // How the crop is resized to the network's size (D3F_RESAMPLE_*): the plain bicubic or the antialiased one
@@ -184,6 +185,14 @@ class UnetEngine {
   float frame_temporal_strength() const { return frame_.strength; }
   int frame_temporal_threshold() const { return frame_.threshold; }
   int frame_temporal_reset(hipStream_t s) const;
+  // How the full entry blends the fake into the frame (D3F_BLEND_*).  FEATHER: the one paste launch.  MULTIBAND: the
+  // launches of paste_multiband_u8_launch (multiband.hip) in its place, with `levels` pyramid levels; the pyramid workspace
+  // is the engine's, grown at the start of a full call that needs more -- before anything is enqueued or captured, never
+  // shrunk -- and a growth drops the full entry's graph.  FEATHER ignores and keeps `levels`.
+  enum { FRAME_BLEND_FEATHER = 0, FRAME_BLEND_MULTIBAND = 1 };
+  int set_frame_blend(int mode, int levels);
+  int frame_blend() const { return frame_.blend; }
+  int frame_blend_levels() const { return frame_.blend_levels; }
   int export_tensor(const char* name, const void* ws, float* out_nchw, hipStream_t s) const;
   int export_shape(const char* name, int32_t dims[3]) const;
 
@@ -251,11 +260,11 @@ class UnetEngine {
                           const float mean255[3], const float std255[3], char* ws, hipStream_t s) const;
   // captured graphs: one slot per entry point; a slot is re-captured when what it baked in changes -- the pointers, the
   // constants and (predict_frames) the raw frame size and crop box, the full entry's full_out, feather and colour match
-  // mode, and the temporal filter setting (strength bits, threshold)
+  // mode, blend mode and levels, and the temporal filter setting (strength bits, threshold)
   struct GraphKey {
     const void* ptr[6];
     float cst[6];
-    int geo[10];
+    int geo[12];
   };
   struct GraphSlot {
     hipGraphExec_t exec = nullptr;
@@ -304,6 +313,12 @@ class UnetEngine {
     DevBuf<float> state_coef;
     DevBuf<uint64_t> state_sum;
     DevBuf<int> valid;
+    // blend: the mode, the multiband form's levels and its pyramid workspace (grown by a const frame call, before it
+    // enqueues anything)
+    int blend = FRAME_BLEND_FEATHER;
+    int blend_levels = 1;
+    mutable DevBuf<char> blend_ws;
+    mutable long blend_ws_bytes = 0;
   };
   FrameOptions frame_;
   // the pair buffer [B][H][2W][3]: where the fake half starts in a row, and the bytes from row to row

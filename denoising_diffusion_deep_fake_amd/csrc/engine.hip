@@ -741,6 +741,19 @@ int UnetEngine::set_frame_temporal(float strength, int threshold) {
   return 0;
 }
 
+int UnetEngine::set_frame_blend(int mode, int levels) {
+  D3F_CHECK(mode == FRAME_BLEND_FEATHER || mode == FRAME_BLEND_MULTIBAND,
+            "frame blend: unknown mode %d (D3F_BLEND_FEATHER, D3F_BLEND_MULTIBAND)", mode);
+  if (mode == FRAME_BLEND_FEATHER) levels = frame_.blend_levels;  // (ignored and kept)
+  D3F_CHECK(levels >= 1 && levels <= MULTIBAND_MAX_LEVELS, "frame blend: levels %d outside 1..%d", levels,
+            MULTIBAND_MAX_LEVELS);
+  if (mode == frame_.blend && levels == frame_.blend_levels) return 0;
+  drop_frame_graphs();
+  frame_.blend = mode;
+  frame_.blend_levels = levels;
+  return 0;
+}
+
 int UnetEngine::frame_temporal_reset(hipStream_t s) const {
   frame_.reset_pending = false;
   int* valid = frame_.valid.p;
@@ -806,6 +819,7 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
   const bool aa = o.resample == FRAME_RESAMPLE_CUBIC_AA;
   const bool color = full && o.color == FRAME_COLOR_MEANSTD;  // (the pair entry has no paste to colour)
   const bool temporal = o.strength != 0.f;
+  const bool multiband = full && o.blend == FRAME_BLEND_MULTIBAND;
   uint8_t* const pair = c.pair_out;
   uint8_t* const fake = pair + pair_fake_off();
   const long stride = pair_stride();
@@ -819,7 +833,38 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
                      : (aa ? crop_resize_cubic_aa_check : crop_resize_cubic_check)(B, c.src_h, c.src_w, c.x1, c.y1, c.cw,
                                                                                   c.ch, H, W, stride))
     return rc;
-  if (full) {
+  if (multiband) {
+    // the pyramid workspace: grown here, in front of every launch and outside any capture
+    int cw_max = c.cw, ch_max = c.ch;
+    if (boxes) {
+      if (int rc = paste_resize_cubic_boxes_check(fake, c.raw_in, c.full_out, B, H, W, stride, c.src_h, c.src_w, boxes,
+                                                  c.feather))
+        return rc;
+      cw_max = ch_max = 1;
+      for (int b = 0; b < B; ++b) {
+        cw_max = cw_max > boxes[4L * b + 2] ? cw_max : boxes[4L * b + 2];
+        ch_max = ch_max > boxes[4L * b + 3] ? ch_max : boxes[4L * b + 3];
+      }
+    }
+    const long need = paste_multiband_workspace_bytes(B, cw_max, ch_max, o.blend_levels);
+    if (need < 0) return -1;
+    if (need > o.blend_ws_bytes) {
+      g_frames_full_.destroy();  // it bakes the old workspace in
+      if (o.blend_ws.p) {
+        D3F_HIP(hipFree(o.blend_ws.p));  // (waits for the device: no earlier call still uses it)
+        o.blend_ws.p = nullptr;
+        o.blend_ws_bytes = 0;
+      }
+      D3F_HIP(o.blend_ws.ensure((size_t)need));
+      o.blend_ws_bytes = need;
+    }
+    if (int rc = paste_multiband_check(fake, c.raw_in, c.full_out, o.color_coef.p, color, B, H, W, stride, c.src_h, c.src_w,
+                                       c.x1, c.y1, c.cw, c.ch, boxes, c.feather, o.blend_levels, o.blend_ws.p,
+                                       o.blend_ws_bytes))
+      return rc;
+    D3F_CHECK(!(use_graph && c.full_out == c.raw_in),
+              "predict_frames_full_u8: full_out == raw_in (in place) cannot be replayed from a graph: pass use_graph = 0");
+  } else if (full) {
     int rc;
     if (boxes)
       rc = color ? paste_resize_cubic_color_boxes_check(fake, c.raw_in, c.full_out, o.color_coef.p, B, H, W, stride, c.src_h,
@@ -863,6 +908,10 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
         return rc;
     if (!full) return 0;
     // the fake half of the pair is the patch
+    if (multiband && !color)
+      return paste_multiband_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, boxes,
+                                       c.feather, o.blend_levels, nullptr, false, o.blend_ws.p, o.blend_ws_bytes, c.full_out,
+                                       ls);
     if (!color)
       return boxes ? paste_resize_cubic_boxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, c.feather,
                                                         c.full_out, ls)
@@ -879,6 +928,10 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
       if (int rc = color_coef_smooth_launch(o.color_coef.p, to, parts, B, (long)H * W, o.strength, o.state_coef.p,
                                             o.state_sum.p, o.valid.p + 1, ls))
         return rc;
+    if (multiband)
+      return paste_multiband_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, boxes,
+                                       c.feather, o.blend_levels, o.color_coef.p, true, o.blend_ws.p, o.blend_ws_bytes,
+                                       c.full_out, ls);
     if (boxes)
       return paste_resize_cubic_color_boxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, c.feather,
                                                       o.color_coef.p, c.full_out, ls);
@@ -891,7 +944,7 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
   const GraphKey key = {{params_, bnstats, c.raw_in, pair, ws_, c.full_out},
                         {k.mean[0], k.mean[1], k.mean[2], k.stdv[0], k.stdv[1], k.stdv[2]},
                         {c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, full ? c.feather : 0, full ? o.color : 0, strength_bits,
-                         temporal ? o.threshold : 0}};
+                         temporal ? o.threshold : 0, multiband ? o.blend : 0, multiband ? o.blend_levels : 0}};
   return graph_replay(full ? g_frames_full_ : g_frames_, key, s, launches);
 }
 
@@ -975,7 +1028,7 @@ int UnetEngine::graph_replay(GraphSlot& slot, const GraphKey& key, hipStream_t s
     D3F_HIP(hipEventCreateWithFlags(&ev_gout_, hipEventDisableTiming));
   }
   // (GraphKey has no padding: pointers, then 4-byte fields filling whole 8-byte units)
-  static_assert(sizeof(GraphKey) == 6 * sizeof(void*) + 6 * sizeof(float) + 10 * sizeof(int), "GraphKey is compared bytewise");
+  static_assert(sizeof(GraphKey) == 6 * sizeof(void*) + 6 * sizeof(float) + 12 * sizeof(int), "GraphKey is compared bytewise");
   const bool same = slot.exec != nullptr && memcmp(&key, &slot.key, sizeof(GraphKey)) == 0;
   if (!same) {
     slot.destroy();

@@ -157,6 +157,71 @@ int paste_resize_cubic_color_u8_launch(const uint8_t* patch, int B, int H, int W
 // frame b with box b.  Refused before anything is launched: null boxes with B > 0, and for any frame what the single-box
 // function refuses of a box (the message names the frame)
 constexpr int FRAME_BOXES_MAX = 64;
+// The boxes of a launch travel BY VALUE in the kernel's arguments: a table of at most FRAME_BOXES_MAX of them (1 KB), filled
+// on the host from host memory after every box has been checked.  No device buffer, no copy, no lifetime, and no device-side
+// read of a box nobody has checked.  A workgroup of frame blockIdx.z reads its own 16-byte entry -- a uniform index into the
+// kernel-argument segment, so one scalar load, and the box stays in SGPRs as the single box of the other form does -- and
+// from there on runs the code of the single-box kernel: the same device functions on the same operands, hence the same
+// bytes.  What a launch decides once (the staged pitch and STAGED, the antialiased form's table strides, the in-place
+// paste's grid) is the maximum over its boxes; each of these says where something sits in LDS or which workgroups exist,
+// none enters a value.  More than FRAME_BOXES_MAX frames are several launches, in order.
+struct alignas(16) FrameBox {
+  int x1, y1, cw, ch;
+};
+struct FrameBoxes {
+  FrameBox box[FRAME_BOXES_MAX];
+};
+// a kernel's geometry argument: G alone (the single-box form: the arguments it always had), or G and the table
+template <typename G, bool BOXES>
+struct BoxedGeom {
+  G g;
+};
+template <typename G>
+struct BoxedGeom<G, true> {
+  G g;
+  FrameBoxes boxes;
+};
+// the geometry of frame b (= blockIdx.z of the launch): a.g, with frame b's own box in the boxes form
+template <typename G, bool BOXES>
+__device__ __forceinline__ G frame_geom(const BoxedGeom<G, BOXES>& a, int b) {
+  G g = a.g;
+  if constexpr (BOXES) {
+    const FrameBox bx = a.boxes.box[b];
+    g.x1 = bx.x1;
+    g.y1 = bx.y1;
+    g.cw = bx.cw;
+    g.ch = bx.ch;
+  }
+  return g;
+}
+// the table of a launch over frames b0 .. b0 + n - 1 of a call's boxes [B][4] (host memory, checked by the caller)
+inline void fill_frame_boxes(FrameBoxes& t, const int32_t* boxes, int b0, int n) {
+  t = FrameBoxes{};
+  for (int i = 0; i < n; ++i) {
+    const int32_t* bx = boxes + 4L * (b0 + i);
+    t.box[i] = FrameBox{bx[0], bx[1], bx[2], bx[3]};
+  }
+}
+// One row of a 32-pixel-wide frame tile outside the box, frame -> out (the paste kernels: a tile lies on the frame's 32 x 8
+// grid): tile_w * 3 contiguous bytes from p to q.  Lane lx (0..31) of the row takes the aligned dword lx: whole where it
+// lies inside the row's bytes, else its bytes that do.
+__device__ __forceinline__ void frame_tile_row_copy(const uint8_t* p, uint8_t* q, int tile_w, int lx) {
+  const int n = tile_w * 3;
+  const int al = (int)(reinterpret_cast<uintptr_t>(p) & 3);
+  if (al == (int)(reinterpret_cast<uintptr_t>(q) & 3)) {
+    const int k = lx * 4 - al;  // offset of the dword's first byte from p
+    if (k >= 0 && k + 4 <= n) {
+      *reinterpret_cast<uint32_t*>(q + k) = *reinterpret_cast<const uint32_t*>(p + k);
+    } else {
+      for (int j = 0; j < 4; ++j)
+        if (k + j >= 0 && k + j < n) q[k + j] = p[k + j];
+    }
+  } else if (lx < tile_w) {  // frame and out a different number of bytes past a dword: bytes
+    q[lx * 3 + 0] = p[lx * 3 + 0];
+    q[lx * 3 + 1] = p[lx * 3 + 1];
+    q[lx * 3 + 2] = p[lx * 3 + 2];
+  }
+}
 int crop_resize_cubic_boxes_check(int B, int src_h, int src_w, const int32_t* boxes, int H, int W, long dst_row_stride);
 int crop_resize_cubic_boxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
                                       int H, int W, long dst_row_stride, hipStream_t stream);
@@ -181,6 +246,40 @@ int paste_resize_cubic_color_boxes_check(const uint8_t* patch, const uint8_t* fr
 int paste_resize_cubic_color_boxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
                                              const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
                                              const float* coef, uint8_t* out, hipStream_t stream);
+
+// Multiband paste (multiband.hip; include/d3f_hip.h: d3f_paste_multiband_u8 is the definition): the paste's byte at
+// feather 0 minus the frame's byte, as a Laplacian pyramid of `levels` levels in int16 planes of a caller's workspace, each
+// band faded over its own ramp, collapsed and added to the frame.
+// The workspace of a call: per frame and byte-in-pixel one slab of planes -- g_0 .. g_N (int16) and R_1 .. R_{N-1} (int32) --
+// laid out for the call's LARGEST box, every row `pitch[l]` elements long (a multiple of 8, so that rows start on 16 bytes)
+// and every plane on a 16-byte boundary.  A frame with a smaller box uses the top-left part of its planes.
+constexpr int MULTIBAND_MAX_LEVELS = 6;
+struct MultibandPlan {
+  int levels, F;                            // F: the ramp's width in samples of every level, ceil(feather / 2^levels)
+  int pitch[MULTIBAND_MAX_LEVELS + 1];      // elements per row of the planes of level l
+  long g_off[MULTIBAND_MAX_LEVELS + 1];     // bytes from a slab's start to g_l
+  long r_off[MULTIBAND_MAX_LEVELS + 1];     // ... and to R_l (levels 1 .. N - 1)
+  long slab_bytes;                          // of one frame and byte-in-pixel
+};
+// the bytes of a workspace for B frames whose boxes are at most cw_max x ch_max; < 0 with the error set for levels outside
+// 1..MULTIBAND_MAX_LEVELS, B < 0 or a non-positive extent
+long paste_multiband_workspace_bytes(int B, int cw_max, int ch_max, int levels);
+// boxes null: the single box (x1, y1, cw, ch); otherwise HOST memory [B][4] and the four are ignored.  coef null: the plain
+// form; otherwise the colour form's coefficients [B][3][2].  _check: everything the launch refuses, for a caller that must
+// refuse before it starts a capture
+int paste_multiband_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef, bool color, int B,
+                          int H, int W, long patch_row_stride, int src_h, int src_w, int x1, int y1, int cw, int ch,
+                          const int32_t* boxes, int feather, int levels, const void* workspace, long workspace_bytes);
+int paste_multiband_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
+                              int src_h, int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes, int feather,
+                              int levels, const float* coef, bool color, void* workspace, long workspace_bytes, uint8_t* out,
+                              hipStream_t stream);
+// the first launch of the sequence (resize.hip, next to the paste kernel whose arithmetic it shares): g_0 = (V - s) << 6 of
+// n frames into their slabs (frame b's first plane at g0 + b * 3 * slab_bytes, byte-in-pixel c's slab_bytes further on each).
+// boxes: null, or the call's table with this launch's frames from b0 (n <= FRAME_BOXES_MAX)
+int multiband_diff_launch(const uint8_t* patch, int n, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
+                          int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes, int b0, const float* coef,
+                          bool color, int16_t* g0, int pitch0, long slab_bytes, hipStream_t stream);
 
 // colour match (color.hip; include/d3f_hip.h: d3f_channel_sums_u8, d3f_color_match_coef).  Sums: per frame and byte-in-pixel
 // S = sum p, Q = sum p^2 as uint64 [B][3][2], exact; at most COLOR_MAX_PIXELS pixels per frame, so that n Q and S^2 stay

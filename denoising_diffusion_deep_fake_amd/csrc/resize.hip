@@ -23,8 +23,12 @@
 // Staging and the two passes are device functions (resize_stage, resize_value): the paste kernel at the end of this file,
 // the inverse of this operator, runs the same arithmetic on a patch instead of a crop.
 //
+// The multiband paste's first launch (multiband_diff_kernel, at the end) shares them too; its pyramid is multiband.hip.
+//
 // The antialiased form (d3f_crop_resize_cubic_aa_u8: Pillow's bicubic, whose window widens with the scale) has a kernel of
 // its own behind the plain one.
+#include <type_traits>
+
 #include "common.h"
 #include "pointwise.h"
 
@@ -40,46 +44,6 @@ struct ResizeGeom {
   long dst_row_stride;
   int pitch;  // bytes of one staged patch row (a multiple of 4)
 };
-
-// ---- a box per frame (include/d3f_hip.h: the _boxes_ operators) ----
-// The boxes of a launch travel BY VALUE in the kernel's arguments: a table of at most FRAME_BOXES_MAX of them (1 KB), filled
-// on the host from host memory after every box has been checked.  No device buffer, no copy, no lifetime, and no device-side
-// read of a box nobody has checked.  A workgroup of frame blockIdx.z reads its own 16-byte entry -- a uniform index into the
-// kernel-argument segment, so one scalar load, and the box stays in SGPRs as the single box of the other form does -- and
-// from there on runs the code of the single-box kernel: the same device functions on the same operands, hence the same
-// bytes.  What a launch decides once (the staged pitch and STAGED, the antialiased form's table strides, the in-place
-// paste's grid) is the maximum over its boxes; each of these says where something sits in LDS or which workgroups exist,
-// none enters a value.  More than FRAME_BOXES_MAX frames are several launches, in order.
-// (FRAME_BOXES_MAX: pointwise.h)
-struct alignas(16) FrameBox {
-  int x1, y1, cw, ch;
-};
-struct FrameBoxes {
-  FrameBox box[FRAME_BOXES_MAX];
-};
-// a kernel's geometry argument: G alone (the single-box form: the arguments it always had), or G and the table
-template <typename G, bool BOXES>
-struct BoxedGeom {
-  G g;
-};
-template <typename G>
-struct BoxedGeom<G, true> {
-  G g;
-  FrameBoxes boxes;
-};
-// the geometry of frame b (= blockIdx.z of the launch): a.g, with frame b's own box in the boxes form
-template <typename G, bool BOXES>
-__device__ __forceinline__ G frame_geom(const BoxedGeom<G, BOXES>& a, int b) {
-  G g = a.g;
-  if constexpr (BOXES) {
-    const FrameBox bx = a.boxes.box[b];
-    g.x1 = bx.x1;
-    g.y1 = bx.y1;
-    g.cw = bx.cw;
-    g.ch = bx.ch;
-  }
-  return g;
-}
 
 // s = floor(f) and the four tap weights of output index d (n_in -> n_out)
 __device__ __forceinline__ int cubic_taps(int d, int n_in, int n_out, float w[4]) {
@@ -263,15 +227,6 @@ static PatchExtent resize_patch_extent(int n_h, int n_w, int out_h, int out_w) {
 }
 static long resize_lds_bytes(int n_h, int n_w, int out_h, int out_w, int* pitch_out) {
   return resize_patch_extent(n_h, n_w, out_h, out_w).lds_bytes(pitch_out);
-}
-
-// the table of a launch over frames b0 .. b0 + n - 1 of a call's boxes [B][4] (host memory, checked by the caller)
-static void fill_frame_boxes(FrameBoxes& t, const int32_t* boxes, int b0, int n) {
-  t = FrameBoxes{};
-  for (int i = 0; i < n; ++i) {
-    const int32_t* bx = boxes + 4L * (b0 + i);
-    t.box[i] = FrameBox{bx[0], bx[1], bx[2], bx[3]};
-  }
 }
 
 // boxes null: the single-box launch with g0's box.  Otherwise frames b0 .. b0 + B - 1 of the table's call: one launch of at
@@ -779,24 +734,7 @@ __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void paste_resize_cubic_kern
   if (bx_f > bx_l || by_f > by_l) {  // (workgroup-uniform) a tile outside the box: a copy
     if (in_place || ly >= tile_h) return;
     const long at = (long)(oy0 + ly) * row_bytes + (long)ox0 * 3;
-    const uint8_t* p = f + at;
-    uint8_t* q = o + at;
-    const int n = tile_w * 3;
-    const int al = (int)(reinterpret_cast<uintptr_t>(p) & 3);
-    if (al == (int)(reinterpret_cast<uintptr_t>(q) & 3)) {
-      // lane lx takes the aligned dword lx of the row: whole where it lies inside the row's n bytes, else its bytes that do
-      const int k = lx * 4 - al;  // offset of the dword's first byte from p
-      if (k >= 0 && k + 4 <= n) {
-        *reinterpret_cast<uint32_t*>(q + k) = *reinterpret_cast<const uint32_t*>(p + k);
-      } else {
-        for (int j = 0; j < 4; ++j)
-          if (k + j >= 0 && k + j < n) q[k + j] = p[k + j];
-      }
-    } else if (lx < tile_w) {  // frame and out a different number of bytes past a dword: bytes
-      q[lx * 3 + 0] = p[lx * 3 + 0];
-      q[lx * 3 + 1] = p[lx * 3 + 1];
-      q[lx * 3 + 2] = p[lx * 3 + 2];
-    }
+    frame_tile_row_copy(f + at, o + at, tile_w, lx);
     return;
   }
   const uint8_t* img = patch + (long)b * g.H * g.patch_row_stride;
@@ -1005,6 +943,123 @@ int paste_resize_cubic_color_u8_launch(const uint8_t* patch, int B, int H, int W
     return rc;
   if (B == 0) return 0;
   return paste_launch<true>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, x1, y1, cw, ch, feather, coef, out, stream);
+}
+
+// ---- multiband paste: the difference image (include/d3f_hip.h: d3f_paste_multiband_u8; the pyramid is multiband.hip) ----
+// g_0 = (V - s) << 6 with V the byte the paste kernel above writes at feather 0 -- resize_stage, resize_value, the clamp, the
+// colour form's two operations and rintf, the same device functions on the same operands -- and s the frame's byte.
+// Tiles lie on the BOX's 32 x 8 grid, so that a tile's row of a plane starts on 64 bytes: a lane computes its pixel's three
+// values into LDS, and 96 lanes then store the tile's three 8 x 32 planes as 16-byte vectors (a vector that crosses the
+// box's right edge ends inside the row's padding; those lanes hold 0).
+struct DiffGeom {
+  int H, W;
+  long patch_row_stride;
+  int src_h, src_w, x1, y1, cw, ch;
+  int pitch;   // bytes of one staged patch row
+  int pitch0;  // int16 per row of g_0
+  long slab_bytes;
+};
+constexpr int DIFF_TILE_BYTES = 3 * RESIZE_TH * RESIZE_TW * 2;
+
+// BOXES: the grid is the largest box's; a frame's workgroups past its own box return at once
+template <bool STAGED, bool COLOR, bool BOXES>
+__global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void multiband_diff_kernel(const uint8_t* __restrict__ patch,
+                                                                              const uint8_t* __restrict__ frame,
+                                                                              int16_t* __restrict__ g0,
+                                                                              const float* __restrict__ coef,
+                                                                              BoxedGeom<DiffGeom, BOXES> geo) {
+  const int b = blockIdx.z;
+  const DiffGeom g = frame_geom(geo, b);
+  const int bx0 = blockIdx.x * RESIZE_TW, by0 = blockIdx.y * RESIZE_TH;
+  if (bx0 >= g.cw || by0 >= g.ch) return;  // (workgroup-uniform)
+  extern __shared__ __attribute__((aligned(16))) uint8_t diff_lds[];
+  int16_t* dtile = reinterpret_cast<int16_t*>(diff_lds);  // [3][RESIZE_TH][RESIZE_TW]
+  uint8_t* staged = diff_lds + DIFF_TILE_BYTES;
+  const int tid = threadIdx.x;
+  const int bx_l = min(bx0 + RESIZE_TW, g.cw) - 1, by_l = min(by0 + RESIZE_TH, g.ch) - 1;
+  const uint8_t* img = patch + (long)b * g.H * g.patch_row_stride;
+  const ResizeSrc rs = {img, g.patch_row_stride, g.H, g.W, g.ch, g.cw, g.pitch};
+  ResizeTile t;
+  if (STAGED) {
+    const uint8_t* hi = patch + ((long)gridDim.z * g.H - 1) * g.patch_row_stride + (long)g.W * 3;
+    t = resize_stage(staged, rs, bx0, bx_l, by0, by_l, patch, hi, tid);
+    __syncthreads();
+  }
+  const int lx = tid % RESIZE_TW, ly = tid / RESIZE_TW;
+  const int j = bx0 + lx, i = by0 + ly;
+  int d[3] = {0, 0, 0};
+  if (j < g.cw && i < g.ch) {
+    float v[3];
+    resize_value<STAGED>(staged, rs, t, j, i, v);
+    const uint8_t* s = frame + (long)b * g.src_h * g.src_w * 3 + ((long)(g.y1 + i) * g.src_w + g.x1 + j) * 3;
+    for (int c = 0; c < 3; ++c) {
+      float vc = fminf(fmaxf(v[c], 0.f), 255.f);
+      if constexpr (COLOR) {
+        const float scaled = coef[((long)b * 3 + c) * 2] * vc;
+        vc = fminf(fmaxf(scaled + coef[((long)b * 3 + c) * 2 + 1], 0.f), 255.f);
+      }
+      d[c] = ((int)rintf(vc) - (int)s[c]) * 64;
+    }
+  }
+  for (int c = 0; c < 3; ++c) dtile[(c * RESIZE_TH + ly) * RESIZE_TW + lx] = (int16_t)d[c];
+  __syncthreads();
+  if (tid < 3 * RESIZE_TH * (RESIZE_TW / 8)) {
+    const int c = tid / (RESIZE_TH * (RESIZE_TW / 8)), r = (tid / (RESIZE_TW / 8)) % RESIZE_TH, k = tid % (RESIZE_TW / 8);
+    if (by0 + r < g.ch && bx0 + 8 * k < g.cw) {
+      int16_t* plane = g0 + ((long)b * 3 + c) * (g.slab_bytes / 2);
+      *reinterpret_cast<int4*>(plane + (long)(by0 + r) * g.pitch0 + bx0 + 8 * k) =
+          *reinterpret_cast<const int4*>(dtile + (c * RESIZE_TH + r) * RESIZE_TW + 8 * k);
+    }
+  }
+}
+
+template <bool COLOR, bool BOXES>
+static int diff_launch_one(const uint8_t* patch, int n, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
+                           int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes, int b0, const float* coef,
+                           int16_t* g0, int pitch0, long slab_bytes, hipStream_t stream) {
+  BoxedGeom<DiffGeom, BOXES> a;
+  DiffGeom& g = a.g;
+  g = DiffGeom{H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, 0, pitch0, slab_bytes};
+  int cw_max = cw, ch_max = ch;
+  long lds;
+  if constexpr (BOXES) {
+    fill_frame_boxes(a.boxes, boxes, b0, n);
+    PatchExtent e;
+    cw_max = ch_max = 1;
+    for (int i = 0; i < n; ++i) {
+      const FrameBox& bx = a.boxes.box[i];
+      e.cover(resize_patch_extent(H, W, bx.ch, bx.cw));
+      cw_max = cw_max > bx.cw ? cw_max : bx.cw;
+      ch_max = ch_max > bx.ch ? ch_max : bx.ch;
+    }
+    lds = e.lds_bytes(&g.pitch);
+  } else {
+    lds = resize_lds_bytes(H, W, ch, cw, &g.pitch);
+  }
+  const dim3 grid((cw_max + RESIZE_TW - 1) / RESIZE_TW, (ch_max + RESIZE_TH - 1) / RESIZE_TH, n), block(RESIZE_TW * RESIZE_TH);
+  if (lds > 0)
+    hipLaunchKernelGGL((multiband_diff_kernel<true, COLOR, BOXES>), grid, block, (size_t)(DIFF_TILE_BYTES + lds), stream, patch,
+                       frame, g0, coef, a);
+  else
+    hipLaunchKernelGGL((multiband_diff_kernel<false, COLOR, BOXES>), grid, block, (size_t)DIFF_TILE_BYTES, stream, patch, frame,
+                       g0, coef, a);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+// (the caller, paste_multiband_u8_launch, has checked everything)
+int multiband_diff_launch(const uint8_t* patch, int n, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
+                          int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes, int b0, const float* coef,
+                          bool color, int16_t* g0, int pitch0, long slab_bytes, hipStream_t stream) {
+  auto go = [&](auto COLOR, auto BOXES) {
+    return diff_launch_one<decltype(COLOR)::value, decltype(BOXES)::value>(patch, n, H, W, patch_row_stride, frame, src_h,
+                                                                           src_w, x1, y1, cw, ch, boxes, b0, coef, g0, pitch0,
+                                                                           slab_bytes, stream);
+  };
+  using T = std::true_type;
+  using F = std::false_type;
+  if (boxes) return color ? go(T{}, T{}) : go(F{}, T{});
+  return color ? go(T{}, F{}) : go(F{}, F{});
 }
 
 }  // namespace d3f

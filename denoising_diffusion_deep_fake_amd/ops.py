@@ -1140,6 +1140,51 @@ def track_scale_faces(rows, state, frame=None):
     return boxes
 
 
+def _paste_args(who, patch, frames, box, out, color, boxes):
+    """the arguments the paste operators share, checked: (patch [B,H,W,3], frames [B,h,w,3] contiguous, out, geo = the box's
+    four integers or (the ctypes boxes table,), coef [B,3,2] or None, single, rows = the boxes as 4-tuples)"""
+    if (box is None) == (boxes is None):
+        raise ValueError(f"{who}: exactly one of box= and boxes=")
+    if (patch.dtype != torch.uint8 or patch.shape[-1] != 3 or patch.dim() not in (3, 4) or frames.dtype != torch.uint8
+            or frames.shape[-1] != 3 or frames.dim() != patch.dim()):
+        raise ValueError(f"{who} expects a uint8 patch [H, W, 3] and frames [h, w, 3], or a batch of both")
+    dev = _dev(frames)
+    single = frames.dim() == 3
+    p = patch.unsqueeze(0) if single else patch
+    in_place = out is frames
+    f = frames.unsqueeze(0) if single else frames
+    if in_place and not f.is_contiguous():
+        raise ValueError("out=frames (in place) needs contiguous frames")
+    f = f.contiguous()
+    B = f.shape[0]
+    H, W = int(p.shape[1]), int(p.shape[2])
+    if (p.shape[0] != B or p.device != dev or p.stride(3) != 1 or p.stride(2) != 3 or p.stride(1) < 3 * W
+            or (B > 1 and p.stride(0) != H * p.stride(1))):
+        raise ValueError(f"patch must be a uint8 tensor [{B}, H, W, 3] on the frames' device with packed pixels and frames "
+                         f"H rows apart")
+    if boxes is not None:
+        table, rows = _boxes_arg(boxes, B, who)
+        geo = (table,)
+    else:
+        geo = tuple(int(v) for v in box)
+        rows = [geo] * B
+    if in_place:
+        o = f
+    elif out is None:
+        o = torch.empty_like(f)
+    else:
+        o = out.unsqueeze(0) if single and out.dim() == 3 else out
+        if tuple(o.shape) != tuple(f.shape) or o.dtype != torch.uint8 or o.device != dev or not o.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(frames.shape)} on the frames' device")
+    coef = None
+    if color is not None:
+        coef = color.unsqueeze(0) if single and color.dim() == 2 else color
+        if tuple(coef.shape) != (B, 3, 2) or coef.dtype != torch.float32 or coef.device != dev:
+            raise ValueError(f"color must be a float32 tensor of shape {(B, 3, 2)} on the frames' device")
+        coef = coef.contiguous()
+    return p, f, o, geo, coef, single, rows
+
+
 def paste_resize_cubic_u8(patch, frames, box=None, feather=0, out=None, color=None, boxes=None):
     """The inverse of `crop_resize_cubic_u8` with a blend: uint8 `patch` [H, W, 3] / [B, H, W, 3] on the HIP device is resized
     to the box (x1, y1, cw, ch) of uint8 `frames` [h, w, 3] / [B, h, w, 3] with the same arithmetic and blended in over a
@@ -1152,49 +1197,52 @@ def paste_resize_cubic_u8(patch, frames, box=None, feather=0, out=None, color=No
     boxes: [B][4] integers in host memory, a box per frame, instead of box= (exactly one of the two); one `feather` for the
     call.  Frame b is byte for byte the single-box call on frame b with boxes[b] (d3f_paste_resize_cubic_boxes_u8 and its
     _color form; one launch per 64 frames)."""
-    if (box is None) == (boxes is None):
-        raise ValueError("paste_resize_cubic_u8: exactly one of box= and boxes=")
-    if (patch.dtype != torch.uint8 or patch.shape[-1] != 3 or patch.dim() not in (3, 4) or frames.dtype != torch.uint8
-            or frames.shape[-1] != 3 or frames.dim() != patch.dim()):
-        raise ValueError("paste_resize_cubic_u8 expects a uint8 patch [H, W, 3] and frames [h, w, 3], or a batch of both")
-    dev = _dev(frames)
-    single = frames.dim() == 3
-    p = patch.unsqueeze(0) if single else patch
-    in_place = out is frames
-    f = frames.unsqueeze(0) if single else frames
-    if in_place and not f.is_contiguous():
-        raise ValueError("out=frames (in place) needs contiguous frames")
-    f = f.contiguous()
+    p, f, o, geo, coef, single, _ = _paste_args("paste_resize_cubic_u8", patch, frames, box, out, color, boxes)
     B, h, w, _ = f.shape
     H, W = int(p.shape[1]), int(p.shape[2])
-    if (p.shape[0] != B or p.device != dev or p.stride(3) != 1 or p.stride(2) != 3 or p.stride(1) < 3 * W
-            or (B > 1 and p.stride(0) != H * p.stride(1))):
-        raise ValueError(f"patch must be a uint8 tensor [{B}, H, W, 3] on the frames' device with packed pixels and frames "
-                         f"H rows apart")
-    if boxes is not None:
-        table, _ = _boxes_arg(boxes, B, "paste_resize_cubic_u8")
-        geo = (table,)
-    else:
-        geo = tuple(int(v) for v in box)
-    if in_place:
-        o = f
-    elif out is None:
-        o = torch.empty_like(f)
-    else:
-        o = out.unsqueeze(0) if single and out.dim() == 3 else out
-        if tuple(o.shape) != tuple(f.shape) or o.dtype != torch.uint8 or o.device != dev or not o.is_contiguous():
-            raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(frames.shape)} on the frames' device")
     L = _lib.lib()
-    if color is None:
+    if coef is None:
         paste = L.d3f_paste_resize_cubic_u8 if boxes is None else L.d3f_paste_resize_cubic_boxes_u8
         check(paste(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, *geo, int(feather), ptr(o), stream_ptr()))
         return o[0] if single else o
-    coef = color.unsqueeze(0) if single and color.dim() == 2 else color
-    if tuple(coef.shape) != (B, 3, 2) or coef.dtype != torch.float32 or coef.device != dev:
-        raise ValueError(f"color must be a float32 tensor of shape {(B, 3, 2)} on the frames' device")
-    coef = coef.contiguous()
     paste = L.d3f_paste_resize_cubic_color_u8 if boxes is None else L.d3f_paste_resize_cubic_color_boxes_u8
     check(paste(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, *geo, int(feather), ptr(coef), ptr(o), stream_ptr()))
+    return o[0] if single else o
+
+
+def multiband_levels(feather):
+    """the pyramid levels of a multiband paste over `feather` pixels when the caller names none -- the one place the default
+    lives: the largest N in 1..5 with (feather >> N) >= 2, else 1, so that the coarsest band's ramp is still at least two of
+    its own samples wide.  A design choice, not a measurement."""
+    feather = int(feather)
+    return max([n for n in range(1, 6) if (feather >> n) >= 2], default=1)
+
+
+def paste_multiband_u8(patch, frames, box=None, feather=0, levels=None, out=None, color=None, boxes=None):
+    """`paste_resize_cubic_u8` with a multiband (Burt & Adelson) blend in place of the single ramp: the difference between the
+    resized patch and the frame is split into `levels` frequency bands, the coarsest fades over about `feather` pixels and
+    every finer band over half the band above, in integer arithmetic throughout (include/d3f_hip.h: d3f_paste_multiband_u8;
+    tests/multiband_restatement.py restates it).  feather=0 is byte for byte `paste_resize_cubic_u8(..., feather=0)`.
+    levels: 1..6, None: `multiband_levels(feather)`; every box needs min(cw, ch) >= 2 ** levels.  patch, out, color and
+    boxes: as `paste_resize_cubic_u8` (the _color, _boxes and _color_boxes forms of the operator).  The pyramid workspace is
+    allocated here, per call."""
+    p, f, o, geo, coef, single, rows = _paste_args("paste_multiband_u8", patch, frames, box, out, color, boxes)
+    B, h, w, _ = f.shape
+    H, W = int(p.shape[1]), int(p.shape[2])
+    levels = multiband_levels(feather) if levels is None else int(levels)
+    L = _lib.lib()
+    need = L.d3f_paste_multiband_workspace_bytes(B, max([r[2] for r in rows], default=1), max([r[3] for r in rows], default=1),
+                                                 levels)
+    if need < 0:
+        check(-1)
+    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=f.device)
+    tail = (ptr(ws), int(need), ptr(o), stream_ptr())
+    if coef is None:
+        paste = L.d3f_paste_multiband_u8 if boxes is None else L.d3f_paste_multiband_boxes_u8
+        check(paste(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, *geo, int(feather), levels, *tail))
+    else:
+        paste = L.d3f_paste_multiband_color_u8 if boxes is None else L.d3f_paste_multiband_color_boxes_u8
+        check(paste(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, *geo, int(feather), levels, ptr(coef), *tail))
     return o[0] if single else o
 
 

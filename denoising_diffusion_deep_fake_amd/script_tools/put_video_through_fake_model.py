@@ -13,7 +13,7 @@ from contextlib import ExitStack, nullcontext
 from pathlib import Path
 
 from .. import ops
-from .._lib import TEMPORAL_STRENGTH, TEMPORAL_THRESHOLD, temporal_setting
+from .._lib import MULTIBAND_MAX_LEVELS, TEMPORAL_STRENGTH, TEMPORAL_THRESHOLD, temporal_setting
 from ..train_deep_fake.lit_module import LitModule
 from .video_writer_context_manager import (VideoWriter, add_track_arguments, batches, check_track_arguments, import_cv2,
                                            load_track, open_video_as_generator, track_setting, video_fps)
@@ -36,6 +36,8 @@ def main():
         color_match=args.color_match,
         temporal=args.temporal,
         temporal_threshold=args.temporal_threshold,
+        blend=args.blend,
+        blend_levels=args.blend_levels,
         track=args.track,
         track_margin=args.track_margin,
         track_smooth=args.track_smooth,
@@ -44,6 +46,7 @@ def main():
 
 OUTPUTS = ("pair", "full")
 COLOR_MATCHES = ("none", "meanstd")
+BLENDS = ("feather", "multiband")
 
 
 def parse_command_line_arguments(argv=None):
@@ -77,6 +80,14 @@ def parse_command_line_arguments(argv=None):
                         help="--temporal: mean absolute change of the crop, in levels per sample over a pixel's 3 x 3 "
                              f"surroundings, from which a pixel counts as moving (1..255, default {TEMPORAL_THRESHOLD})")
 
+    parser.add_argument("--blend", choices=list(BLENDS), default=None,
+                        help="--output full: how the fake fades into the frame; feather: one ramp of --feather pixels; "
+                             "multiband: low frequencies fade over --feather pixels, fine detail over a fraction of it, so "
+                             "that a wide ramp hides the brightness step without ghosting edges (default: feather)")
+    parser.add_argument("--blend-levels", type=int, default=None, metavar="N",
+                        help=f"--blend multiband: frequency bands of the blend (1..{MULTIBAND_MAX_LEVELS}; every crop box "
+                             "must be at least 2^N pixels on its short side; default: from the feather)")
+
     add_track_arguments(parser)
 
     args = parser.parse_args(argv)
@@ -89,6 +100,12 @@ def parse_command_line_arguments(argv=None):
         parser.error(str(e))
     if args.color_match is not None and args.output != "full":
         parser.error("--color-match needs --output full: the real|fake pair is not pasted anywhere")
+    if args.blend == "multiband" and args.output != "full":
+        parser.error("--blend multiband needs --output full: the real|fake pair is not pasted anywhere")
+    if args.blend_levels is not None and args.blend != "multiband":
+        parser.error("--blend-levels needs --blend multiband")
+    if args.blend_levels is not None and not 1 <= args.blend_levels <= MULTIBAND_MAX_LEVELS:
+        parser.error(f"--blend-levels is an integer in 1..{MULTIBAND_MAX_LEVELS}, not {args.blend_levels}")
     return args
 
 
@@ -103,6 +120,10 @@ class RenderFakeVideo():
     replaces, per frame and channel, before the paste; None / "none": the fake is pasted as the network made it.
     temporal=STRENGTH (either output; temporal_threshold=N with it): the fake is filtered against flicker along the video
     (`Unet.predict_frames_u8`, temporal=); the model's filter state is reset once, before the first batch.
+    blend="multiband" (output="full" only; blend_levels=N in 1..6 with it): the fake is blended in per frequency band
+    (`ops.paste_multiband_u8`) instead of over the single ramp; None / "feather": the ramp.  With a track and no
+    blend_levels the levels come from the feather `track_feather` gives, and every box of the track is checked against
+    2 ** N once, before the first batch.
     track=FILE (or a list of (x, y, w, h) boxes; track_margin=M, track_smooth=N with it): frame k is cropped, and with
     output="full" pasted, at `ops.track_crop_box` of the track's entry k instead of the centre box; the frame counter runs
     across batches, and the padding frames of a short last batch repeat the last real frame's box.  output="full" without
@@ -111,7 +132,8 @@ class RenderFakeVideo():
 
     def __init__(self, video_path, checkpoint_path, model_a_or_b, image_width, image_height, batch_frames=1,
                  frames=None, sink=None, model=None, output="pair", feather=None, antialias=False, color_match=None,
-                 temporal=None, temporal_threshold=None, track=None, track_margin=None, track_smooth=None):
+                 temporal=None, temporal_threshold=None, track=None, track_margin=None, track_smooth=None, blend=None,
+                 blend_levels=None):
 
         self.video_path = Path(video_path)
         self.checkpoint_path = Path(checkpoint_path) if checkpoint_path is not None else None
@@ -135,6 +157,17 @@ class RenderFakeVideo():
             raise ValueError("temporal_threshold needs temporal")
         strength, threshold = temporal_setting(temporal, temporal_threshold)
         self.temporal = None if temporal is None or strength == 0.0 else (strength, threshold)
+        if not (blend is None or isinstance(blend, str)) or blend not in (None,) + BLENDS:
+            raise ValueError(f"blend is None or one of {BLENDS}, not {blend!r}")
+        if blend == "multiband" and output != "full":
+            raise ValueError("blend='multiband' needs output='full': the real|fake pair is not pasted anywhere")
+        if blend_levels is not None and blend != "multiband":
+            raise ValueError("blend_levels needs blend='multiband'")
+        if blend_levels is not None and (isinstance(blend_levels, bool) or not isinstance(blend_levels, int)
+                                         or not 1 <= blend_levels <= MULTIBAND_MAX_LEVELS):
+            raise ValueError(f"blend_levels is an integer in 1..{MULTIBAND_MAX_LEVELS}, not {blend_levels!r}")
+        self.blend = blend
+        self.blend_levels = blend_levels
         self.track_margin, track_smooth = track_setting(track, track_margin, track_smooth)
         self.track = None if track is None else load_track(track, self.track_margin, track_smooth)
         self.frame_index = 0  # of the next batch's first frame: the track is followed across batches
@@ -176,6 +209,18 @@ class RenderFakeVideo():
                                      self.track_margin)
         return ops.default_feather(min(b[2] for b in boxes), min(b[3] for b in boxes))
 
+    def track_blend_levels(self, h, w, feather):
+        """blend="multiband" with a track: the levels (blend_levels=, else `ops.multiband_levels` of the call's feather),
+        after every box of the whole track has been checked against 2 ** levels"""
+        levels = self.blend_levels if self.blend_levels is not None else ops.multiband_levels(feather)
+        boxes = ops.track_crop_boxes(self.track, 0, len(self.track), h, w, self.image_width, self.image_height,
+                                     self.track_margin)
+        for k, b in enumerate(boxes):
+            if min(b[2], b[3]) < (1 << levels):
+                raise ValueError(f"blend='multiband' with {levels} levels needs boxes of at least {1 << levels} pixels on "
+                                 f"their short side; frame {k} of the track has {b[2]} x {b[3]}")
+        return levels
+
     def render_real_fake_video(self):
         w = 2 * self.image_width
         h = self.image_height
@@ -202,9 +247,14 @@ class RenderFakeVideo():
         with ExitStack() as stack:
             write = self.sink
             feather = self.feather
+            blend_levels = self.blend_levels
+            track_checked = False
             for batch, real_frames in batches(frames, self.batch_frames):
                 if feather is None and self.track is not None:
                     feather = self.track_feather(*batch.shape[1:3])
+                if self.blend == "multiband" and self.track is not None and not track_checked:
+                    blend_levels = self.track_blend_levels(*batch.shape[1:3], feather)
+                    track_checked = True
                 if write is None:  # the writer takes the source's size, read off the first frame
                     h, w = batch.shape[1:3]
                     write = stack.enter_context(VideoWriter(str(self.get_output_video_path("_full")), w, h,
@@ -213,7 +263,8 @@ class RenderFakeVideo():
                                                            self.image_height, feather=feather,
                                                            antialias=self.antialias, color_match=self.color_match,
                                                            temporal=self.temporal,
-                                                           boxes=self.batch_boxes(batch, real_frames))
+                                                           boxes=self.batch_boxes(batch, real_frames),
+                                                           blend=self.blend, blend_levels=blend_levels)
                 for frame in full[:real_frames]:  # the padding of a short last batch is dropped
                     write(frame)
 

@@ -514,7 +514,8 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
 
     @torch.no_grad()
     def predict_fake_frames_full(self, raw_bgr_batch, model_a_or_b, width, height, feather=None, with_pair=False,
-                                 antialias=False, color_match=None, temporal=None, boxes=None):
+                                 antialias=False, color_match=None, temporal=None, boxes=None, blend=None,
+                                 blend_levels=None):
         """host frames [B, h, w, 3] (uint8 BGR, any size) -> host frames of the same shape with the centre-crop box replaced
         by the fake, resized back to the box and blended in over `feather` source pixels (None: `ops.default_feather`):
         the swapped video at the source's size, in one device call (`Unet.predict_frames_full_u8`).  with_pair: returns
@@ -523,7 +524,8 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         crop-to-network resize only).  color_match: None / "none" / "meanstd", as `Unet.predict_frames_full_u8`: the fake's
         colour statistics matched to the crop it replaces before the paste; the pair is the same either way.  temporal: as
         `predict_fake_frames`; the pair then holds the filtered fake, and with color_match the coefficients are smoothed.
-        boxes: as `predict_fake_frames`; every frame's fake goes back into its own box (`Unet.predict_frames_full_u8`)."""
+        boxes: as `predict_fake_frames`; every frame's fake goes back into its own box (`Unet.predict_frames_full_u8`).
+        blend, blend_levels: as `Unet.predict_frames_full_u8` -- "multiband" fades each frequency band over its own ramp."""
         model, mean, std, raw = self._frame_path_inputs(raw_bgr_batch, model_a_or_b, "predict_fake_frames_full")
         width, height = int(width), int(height)
         if not hasattr(self, "_frames_full_buffers"):
@@ -537,7 +539,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         model.predict_frames_full_u8(dev_in, (height, width), mean, std, feather=feather,
                                      graph=bool(self.hparams.get("inference_graph", False)), out=dev_full,
                                      pair_out=dev_pair, antialias=antialias, color_match=color_match,
-                                     temporal=temporal, boxes=boxes)
+                                     temporal=temporal, boxes=boxes, blend=blend, blend_levels=blend_levels)
         host_full.copy_(dev_full, non_blocking=True)
         if with_pair:
             host_pair.copy_(dev_pair, non_blocking=True)

@@ -871,14 +871,17 @@ class Unet(nn.Module, _NetsRuntime):
         return x, single, geo, eng, pair, rows
 
     @staticmethod
-    def _apply_frame_settings(eng, antialias, color, temporal):
+    def _apply_frame_settings(eng, antialias, color, temporal, blend=None):
         """the frame entries' settings on the plan's handle, in front of every call (the handle returns early on a value it
         already has, and keeps its captured graphs and the filter's state then).  color: a D3F_COLOR_* code, or None: left
-        as it is -- `predict_frames_u8` has no paste to colour.  temporal: what `_lib.temporal_setting` returns."""
+        as it is -- `predict_frames_u8` has no paste to colour.  temporal: what `_lib.temporal_setting` returns.  blend:
+        (D3F_BLEND_* code, levels), or None: left as it is, for the same reason."""
         L = _lib.lib()
         check(L.d3f_unet_set_frame_resample(eng.h, _lib.RESAMPLE_CUBIC_AA if antialias else _lib.RESAMPLE_CUBIC))
         if color is not None:
             check(L.d3f_unet_set_frame_color_match(eng.h, color))
+        if blend is not None:
+            check(L.d3f_unet_set_frame_blend(eng.h, blend[0], blend[1]))
         check(L.d3f_unet_set_frame_temporal(eng.h, temporal[0], temporal[1]))
 
     def reset_frame_temporal(self):
@@ -925,7 +928,8 @@ class Unet(nn.Module, _NetsRuntime):
 
     @torch.no_grad()
     def predict_frames_full_u8(self, raw_bgr, size, mean, std, feather=None, graph=True, out=None, pair_out=None,
-                               antialias=False, color_match=None, temporal=None, boxes=None):
+                               antialias=False, color_match=None, temporal=None, boxes=None, blend=None,
+                               blend_levels=None):
         """`predict_frames_u8`, then the fake pasted back into the source frames: uint8 BGR frames [h,w,3] or [B,h,w,3] on
         the HIP device -> the frames at their own size with the centre-crop box replaced by the fake, resized back
         (`ops.paste_resize_cubic_u8`) and blended in over `feather` source pixels (None: `ops.default_feather` of the
@@ -941,8 +945,18 @@ class Unet(nn.Module, _NetsRuntime):
         and with color_match="meanstd" the coefficients are smoothed across frames too (`ops.color_coef_smooth`).
         boxes: as `predict_frames_u8` -- None, one box (the same C entry, `graph=` honoured) or [B][4], a box per frame
         (d3f_unet_predict_frames_full_boxes_u8: eager whatever `graph=` says); every frame's fake is pasted into its own
-        box, with one feather for the call: None is `ops.default_feather(min cw, min ch)` over the call's boxes."""
+        box, with one feather for the call: None is `ops.default_feather(min cw, min ch)` over the call's boxes.
+        blend: None / "feather": the single ramp above.  "multiband": the paste is `ops.paste_multiband_u8` on the fake half
+        of the pair instead (with color_match its colour form, with boxes its boxes form), still in the one C call (the
+        handle's D3F_BLEND_MULTIBAND mode; its pyramid workspace belongs to the plan and grows with the box): low frequencies
+        fade over `feather` pixels, fine detail over a fraction of it.  blend_levels: the pyramid's levels, 1..6, with
+        "multiband" only; None: `ops.multiband_levels(feather)`.  A change of either re-captures the graph."""
         from . import ops
+        blend_code = _lib.blend_mode(blend)
+        if blend_levels is not None and blend_code != _lib.BLEND_MULTIBAND:
+            raise ValueError("blend_levels needs blend='multiband'")
+        if blend_levels is not None:
+            blend_levels = _lib.blend_levels(blend_levels)
         color_code = _lib.color_match_mode(color_match)
         temporal = _lib.temporal_setting(temporal)
         in_place = out is raw_bgr
@@ -961,7 +975,9 @@ class Unet(nn.Module, _NetsRuntime):
                     or full.device != x.device):
                 raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(raw_bgr.shape)} on the input's device")
         rt = self._rt
-        self._apply_frame_settings(eng, antialias, color_code, temporal)
+        if blend_code == _lib.BLEND_MULTIBAND and blend_levels is None:
+            blend_levels = ops.multiband_levels(feather)
+        self._apply_frame_settings(eng, antialias, color_code, temporal, (blend_code, blend_levels or 1))
         L = _lib.lib()
         per_frame = len(geo) == 3
         entry = L.d3f_unet_predict_frames_full_boxes_u8 if per_frame else L.d3f_unet_predict_frames_full_u8

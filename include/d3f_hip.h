@@ -268,6 +268,25 @@ int d3f_unet_frame_color_match(d3f_unet_t h); /* the mode, or < 0 for a null han
 int d3f_unet_set_frame_temporal(d3f_unet_t h, float strength, int threshold);
 int d3f_unet_frame_temporal(d3f_unet_t h, float* strength, int* threshold);
 int d3f_unet_frame_temporal_reset(d3f_unet_t h, void* stream);
+/* How the full-frame entries (d3f_unet_predict_frames_full_u8, _full_boxes_u8) blend the fake into the frame:
+ *   D3F_BLEND_FEATHER    one ramp of `feather` pixels: d3f_paste_resize_cubic_u8 (with D3F_COLOR_MEANSTD its colour form).  The
+ *                        default after d3f_unet_create; launches, bytes and graphs are exactly those of a handle that never
+ *                        heard of the setting, and `levels` is ignored (and kept).
+ *   D3F_BLEND_MULTIBAND  the last launch -- the paste -- is replaced by the launches of d3f_paste_multiband_u8 (with
+ *                        D3F_COLOR_MEANSTD: sums, coefficients, their smoothing, then d3f_paste_multiband_color_u8; with boxes
+ *                        the boxes forms) with levels in 1..D3F_MULTIBAND_MAX_LEVELS: full_out is byte for byte that
+ *                        operator on pair_out's fake half.  The temporal filter acts on the pair before the paste and is
+ *                        untouched; d3f_unet_predict_frames_u8 ignores the setting.
+ * The pyramid workspace belongs to the handle: sized by d3f_paste_multiband_workspace_bytes for the call's batch and largest
+ * box, grown (never shrunk) at the start of a full-frame call that needs more, before anything is enqueued or captured, and
+ * freed with the handle; a growth waits for the device and drops the full-frame graph.  Mode and levels are part of the
+ * full-frame graph's key.  Setting the values the handle has changes nothing; different values drop the two frame graphs.
+ * Refused: an unknown mode, levels outside 1..6 with D3F_BLEND_MULTIBAND, a pair handle; at the call, whatever the operator
+ * refuses (a box below 1 << levels on a side), before any capture. */
+#define D3F_BLEND_FEATHER 0
+#define D3F_BLEND_MULTIBAND 1
+int d3f_unet_set_frame_blend(d3f_unet_t h, int mode, int levels);
+int d3f_unet_frame_blend(d3f_unet_t h, int* levels); /* the mode (levels, if not null, gets the levels), or < 0 for a null handle */
 /* gradients of every parameter (written, not accumulated) for the preceding training forward.
  * The backward pass is cut into d3f_unet_num_segments() buckets so a data-parallel caller can
  * all-reduce bucket k while bucket k+1 computes: run segments [seg_begin, seg_end) in order 0..n;
@@ -641,6 +660,52 @@ int d3f_paste_resize_cubic_boxes_u8(const uint8_t* patch, int B, int H, int W, i
 int d3f_paste_resize_cubic_color_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
                                           const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
                                           const float* coef, uint8_t* out, void* stream);
+
+/* Multiband paste (Burt & Adelson): d3f_paste_resize_cubic_u8 with the single ramp replaced by a ramp per spatial frequency
+ * band -- low frequencies fade over about `feather` pixels, every finer band over half the band above.  Inputs: those of
+ * d3f_paste_resize_cubic_u8 (with coef: of d3f_paste_resize_cubic_color_u8), levels = N in 1..D3F_MULTIBAND_MAX_LEVELS, and a
+ * workspace in device memory.  Definition (the acceptance contract; tests/multiband_restatement.py restates it in numpy
+ * integers; every comparison is exact), per frame and byte-in-pixel, all in integers:
+ *   - V[i][j], the target byte: what d3f_paste_resize_cubic_u8 (with coef: d3f_paste_resize_cubic_color_u8) writes at box
+ *     pixel (i, j) with feather = 0 -- rintf of the clamped fp32 resize value, from the same device functions;
+ *   - D = V - s in -255..255, s the frame's byte; g_0 = D << 6, held in int16.  Outside the box D is zero by definition;
+ *   - level sizes: h_0 = ch, w_0 = cw, h_{l+1} = (h_l + 1) / 2, w likewise;
+ *   - REDUCE: g_{l+1}[i][j] = (sum over a, b in -2..2 of w_a w_b g_l[clamp(2i + a)][clamp(2j + b)] + 128) >> 8 with
+ *     w = 1 4 6 4 1, indices clamped into level l, the sum exact, the shift arithmetic (floor);
+ *   - EXPAND of a level to h_l x w_l: per axis, output index 2k takes g[k - 1] + 6 g[k] + g[k + 1], output index 2k + 1 takes
+ *     4 g[k] + 4 g[k + 1], indices clamped into the coarse level; the 2-D value is the product form of the two axes (the
+ *     weights sum to 64): (sum + 32) >> 6, arithmetic shift;
+ *   - band masks: F = (feather + (1 << N) - 1) >> N, the ramp's width in SAMPLES of every level.  At level l,
+ *     n_y(i) = min(min(i, h_l - 1 - i) + 1, F + 1), n_x likewise, M = n_y n_x, den = (F + 1)^2 and
+ *     m_l(x) = floor((2 x M + den) / (2 den)) (floor also for negative x; where M == den this is x);
+ *   - collapse: R_N = m_N(g_N); for l = N - 1 .. 0: R_l = EXPAND(R_{l+1}) + m_l(g_l - EXPAND(g_{l+1})), R in int32;
+ *   - E = (R_0 + 32) >> 6; the byte in the box is clamp(s + E, 0, 255), outside the box the frame's byte.
+ * Consequences: feather == 0 gives F == 0, every mask is the identity, each level adds back the very expansion it
+ * subtracted, E == D and out is byte for byte d3f_paste_resize_cubic_u8 with feather = 0; a patch whose resize equals the
+ * frame in the box (D == 0) returns the frame.
+ * workspace: d3f_paste_multiband_workspace_bytes(B, cw_max, ch_max, levels) bytes (cw_max, ch_max: the largest box extents of
+ * the call; < 0 for arguments it refuses) starting on 16 bytes; its contents before the call do not matter and are undefined
+ * after it.  2 N + 1 launches (per 64 frames in the boxes forms).  out == frame runs in place under
+ * d3f_paste_resize_cubic_u8's rules: the last launch reads no frame byte but the three it writes.  The boxes forms: frame b is
+ * byte for byte the single-box call on frame b with box b.  Refused before any device call: everything the plain (colour,
+ * boxes) paste refuses, levels outside 1..6, a box with min(cw, ch) < (1 << N) (the boxes forms name the frame), a null,
+ * misaligned or short workspace, a workspace that overlaps patch, frame, out or coef. */
+#define D3F_MULTIBAND_MAX_LEVELS 6
+int64_t d3f_paste_multiband_workspace_bytes(int B, int cw_max, int ch_max, int levels);
+int d3f_paste_multiband_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes, const uint8_t* frame,
+                           int src_h, int src_w, int x1, int y1, int cw, int ch, int feather, int levels, void* workspace,
+                           int64_t workspace_bytes, uint8_t* out, void* stream);
+int d3f_paste_multiband_color_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                 const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather,
+                                 int levels, const float* coef, void* workspace, int64_t workspace_bytes, uint8_t* out,
+                                 void* stream);
+int d3f_paste_multiband_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                 const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather, int levels,
+                                 void* workspace, int64_t workspace_bytes, uint8_t* out, void* stream);
+int d3f_paste_multiband_color_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                       const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
+                                       int levels, const float* coef, void* workspace, int64_t workspace_bytes, uint8_t* out,
+                                       void* stream);
 
 /* Temporal filter against flicker in the fake video, in two operators.  The definitions are the acceptance contract;
  * tests/temporal_restatement.py restates them in numpy float32 and int64, and every comparison is exact.  All fp32 arithmetic

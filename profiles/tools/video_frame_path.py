@@ -41,10 +41,18 @@
                  library without the boxes entries (the parent's build named through D3F_LIB), or with --off-only, only the
                  single-box forms run: the same sequence of calls on both sides of an A/B of the unchanged path
 
+  --blend      : instead of the above, the multiband paste of the full-frame output: Unet.predict_frames_full_u8 with blend=None
+                 and blend="multiband" (two networks, so that neither handle's mode ever changes inside a timed block), eager,
+                 next to Unet.predict_u8 (the forward pass the paste follows) and the two paste operators alone, out of place:
+                 1080x1920 -> 448x448 and 256x256, centre box, default feather and levels, B = 1 and B = 8; with the byte
+                 bound of the multiband launches -- patch and box read by the first launch, the frame read and written by the
+                 last, every int16 plane g_l written once and read twice (REDUCE, and the collapse of its level; g_N once),
+                 every int32 plane R_l (l = 1 .. N - 1) written once and read once
+
 Back-to-back enqueues on one stream, ITERS iterations after WARMUP, the forms alternating in ROUNDS rounds; the figure is
 the median round's time per call (and per frame).  Host work of the reference's loop (cv2.resize on one CPU thread, the
 concatenate, two PCIe trips) is not part of any figure here.  One JSON line at the end.
-    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N] [--antialias | --color [--off-only] | --temporal [--off-only] | --boxes [--off-only]]
+    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N] [--antialias | --color [--off-only] | --temporal [--off-only] | --boxes [--off-only] | --blend]
 """
 import argparse
 import json
@@ -270,12 +278,76 @@ def boxes_section(args, g):
     print(json.dumps(result))
 
 
+def multiband_bytes(H, W, h, w, cw, ch, levels):
+    """bytes per frame the multiband launches must move (see --blend above)"""
+    plane = [3 * -(-ch // (1 << l)) * -(-cw // (1 << l)) for l in range(levels + 1)]
+    total = H * W * 3 + cw * ch * 3 + 2 * h * w * 3             # patch and box in; frame in, frame out
+    total += sum(2 * p for p in plane)                            # every g_l written
+    total += sum(2 * 2 * p for p in plane[:-1]) + 2 * plane[-1]   # g_l read by REDUCE and by its collapse; g_N once
+    total += sum(2 * 4 * p for p in plane[1:-1])                  # R_l written and read
+    return total
+
+
+def blend_section(args, g):
+    """the multiband paste against the plain one inside the whole call and alone, per frame; one JSON line"""
+    result = {"precision": args.precision, "digest": _lib.built_digest(), "iters": args.iters, "rounds": args.rounds,
+              "blend_us_per_frame": {}}
+    torch.manual_seed(0)
+    net_off = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
+    net_on = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
+    for side in (448, 256):
+        size = (side, side)
+        box = ops.center_crop_box(RAW[0], RAW[1], side, side)
+        feather = ops.default_feather(box[2], box[3])
+        levels = ops.multiband_levels(feather)
+        need = multiband_bytes(side, side, RAW[0], RAW[1], box[2], box[3], levels)
+        bound = need / 6.3e12 * 1e6  # at 6.3 TB/s achievable HBM
+        plain_bound = 2 * RAW[0] * RAW[1] * 3 / 6.3e12 * 1e6
+        for B in (1, 8):
+            raw = torch.randint(0, 256, (B,) + RAW + (3,), generator=g, dtype=torch.uint8).cuda()
+            pair = net_off.predict_frames_u8(raw, size, MEAN, STD, graph=False).clone()
+            small = pair[:, :, :side].contiguous()
+            fake = torch.empty_like(small)
+            bufs = {k: (torch.empty_like(raw), torch.empty_like(pair)) for k in ("off", "on")}
+            full = torch.empty_like(raw)
+            forms = {
+                "full_feather_eager": lambda: net_off.predict_frames_full_u8(raw, size, MEAN, STD, graph=False, out=bufs["off"][0],
+                                                                             pair_out=bufs["off"][1]),
+                "full_multiband_eager": lambda: net_on.predict_frames_full_u8(raw, size, MEAN, STD, graph=False,
+                                                                              out=bufs["on"][0], pair_out=bufs["on"][1],
+                                                                              blend="multiband"),
+                "predict_u8": lambda: net_off.predict_u8(small, MEAN, STD, graph=False, out=fake),
+                "paste_op": lambda: ops.paste_resize_cubic_u8(pair[:, :, side:], raw, box, feather, out=full),
+                "multiband_op": lambda: ops.paste_multiband_u8(pair[:, :, side:], raw, box, feather, levels, out=full),
+            }
+            t = compare(forms, args.warmup, args.iters, args.rounds)
+            key = f"{RAW[0]}x{RAW[1]}_to_{side}_B{B}"
+            row = {}
+            for name, (med, lo, hi) in t.items():
+                print(f"{key:24s} {name:22s} {med / B:9.2f} us per frame (min {lo / B:.2f}, max {hi / B:.2f})")
+                row[name] = [round(med / B, 2), round(lo / B, 2), round(hi / B, 2)]
+            row["added_eager"] = round((t["full_multiband_eager"][0] - t["full_feather_eager"][0]) / B, 2)
+            row["added_share_of_predict_u8"] = round(row["added_eager"] / (t["predict_u8"][0] / B), 4)
+            row["feather"], row["levels"], row["launches"] = feather, levels, 2 * levels + 1
+            row["multiband_bytes"], row["multiband_byte_bound_us"] = need, round(bound, 2)
+            row["multiband_op_times_bound"] = round(t["multiband_op"][0] / B / bound, 1)
+            row["paste_op_times_bound"] = round(t["paste_op"][0] / B / plain_bound, 1)
+            print(f"{key:24s} multiband (feather {feather}, {levels} levels, {2 * levels + 1} launches) adds {row['added_eager']:.2f} "
+                  f"us per frame to the call, {100 * row['added_share_of_predict_u8']:.1f} % of predict_u8; its launches move "
+                  f"{need} bytes per frame, byte bound {bound:.2f} us, the operator at {row['multiband_op_times_bound']:.1f} "
+                  f"times it (the plain paste at {row['paste_op_times_bound']:.1f} times its own)")
+            result["blend_us_per_frame"][key] = row
+            del raw, bufs, full
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--antialias", action="store_true", help="measure the antialiased resize instead (see above)")
     ap.add_argument("--color", action="store_true", help="measure the colour match of the full-frame output instead (see above)")
     ap.add_argument("--temporal", action="store_true", help="measure the temporal filter of the frame entries instead (see above)")
     ap.add_argument("--boxes", action="store_true", help="measure the per-frame-box forms against the single-box ones instead (see above)")
+    ap.add_argument("--blend", action="store_true", help="measure the multiband paste of the full-frame output instead (see above)")
     ap.add_argument("--off-only", action="store_true",
                     help="--color / --temporal / --boxes: only the forms without the mode, as on a library without its entries -- the same "
                          "sequence of allocations and captures on both sides of an A/B of the unchanged path")
@@ -292,6 +364,8 @@ def main():
         return temporal_section(args, torch.Generator().manual_seed(1))
     if args.boxes:
         return boxes_section(args, torch.Generator().manual_seed(1))
+    if args.blend:
+        return blend_section(args, torch.Generator().manual_seed(1))
     torch.manual_seed(0)
     net = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
     g = torch.Generator().manual_seed(1)
