@@ -41,9 +41,48 @@ ah bl + al bh; each is exact in fp32 (8 x 8 significand bits).  Dropped: am bl +
 The term is therefore (6 * ceil(n / 16) + X3_DROPPED) * 2^-24 * sum |a| |b|, capped at the fp32 bound with n + 4 (the
 cap binds below n = 16 only; test_cpu_conv_forms.py asserts it for every case).
 
-Winograd F(2x2, 3x3) is out of scope of the per-element bound: its input, filter and output transforms need an error
-analysis of their own, the form is fp32 only, and the existing rel-L2 gate of 1e-5 already sees a single wrong element.
-The Winograd cases of the table run under guards, poison and the bit-for-bit repeat with that aggregate gate alone.
+Winograd F(2x2, 3x3), fp32 (conv_winograd.hip): Y = A^T [ sum_c (G g G^T) (.) (B^T d B) ] A per 2 x 2 output tile, d the
+4 x 4 input tile at stride 2 on the zero-padded input.  Every term of that sum passes through the roundings of four
+stages, read off the kernel (the library is compiled with -ffp-contract=off: no fused multiply-add outside the MFMAs):
+
+    input transform    tr_col, then tr_row: one addition or subtraction per stage                     2  WINO_INPUT_ROUNDINGS
+    filter transform   winograd_pack_kernel: 0.5f * ((g0 +- g1) + g2) down the columns and again along
+                       the rows -- two additions per stage, the halving exact                         4  WINO_FILTER_ROUNDINGS
+    contraction        C channels per position through v_mfma_f32_32x32x2f32, the accumulator carried
+                       from chunk to chunk: at most one rounding per channel, as for every fp32 MFMA
+                       of this table                                                                  C
+    output transform   (a + b) + c over the rows of positions, then over the columns                  4  WINO_OUTPUT_ROUNDINGS
+
+A stage's error is relative to that stage on absolute values -- |B^T| |d| |B|, |G| |g| |G^T|, the sum of absolute products,
+|A^T| |M| |A| -- so the bound is gamma_n * Ymag with n = C + 10, gamma_n = n * 2^-24 / (1 - n * 2^-24) (the first-order
+n * 2^-24 does not cover the products of the stages' errors) and
+
+    Ymag = |A^T| [ sum_c (|G| |g| |G^T|) (.) (|B^T| |d| |B|) ] |A|
+
+the Winograd algorithm itself in float64 on absolute values with the absolute-value matrices (winograd_eval(...,
+absolute=True)).  It is NOT the direct convolution's magnitude: the transforms add and subtract what the direct form
+never combines (on N(0, 1) data Ymag is about 7 times sum |x| |w|; on inputs with a common offset, where B^T d B cancels,
+far more), and a gate built from sum |x| |w| would be violated by a faultless kernel.  The kernel's eval epilogue
+v = o * sc + sf (+ res), then ReLU: |sc| * E_o + k * 2^-24 * (|o sc| + |sf| + |res|), k = 2 without a residual (the product,
+the addition) and 3 with one; ReLU is 1-Lipschitz and adds nothing.  tests/test_cpu_conv_forms.py restates the whole path
+in torch fp32 in the kernel's operation order, holds it to this bound on N(0, 1) inputs and on the same inputs shifted
+by + 8, and shows that the same path with V rounded to bf16 violates it.
+
+Exact operands (make_exact_data).  x0, x1, w and dy drawn from {-1, 0, 1}: every product is -1, 0 or 1, every partial sum
+of every contraction an integer below 2^24 (exact_conditions, asserted for every case by tests/test_cpu_conv_forms.py),
+every pre-summed up-fold weight an integer of at most 4 (exact in bf16 and in the first plane of f32x3), every Winograd
+transform a quarter-integer: fp32 arithmetic makes no rounding error in any order, and the only acceptable difference
+from float64 is zero.  Every case of the table runs a second time on them and is compared with torch.equal against the
+float64 result passed through the route's STORAGE roundings only (bf16 storage rounds integers above 256):
+
+    forward, a data gradient written at its own resolution   stored(ref)
+    "fullres" route                                          stored(sum2x2(stored(ref_full)))
+    "summed" and "folded" routes                             stored(sum2x2(ref))
+    accumulation into an existing gradient                   stored(base + grad), base in {-1, 0, 1}
+    weight gradient, all parts, class form and slab reduce   ref
+    statistics                                               the float64 total of the partial rows == sum y, sum y^2
+    Winograd eval epilogue                                   scale in {-2, -1, 1, 2}, shift and residual in {-1, 0, 1}:
+                                                             relu?(ref * scale + shift + res), exact as well
 
 Statistics.  In every storage type they are sums of the fp32 accumulators, `rows` of them per partial row in fp32
 (stat_row_pixels), the partial rows added here in float64: bound = the propagated per-element accumulation bound
@@ -93,6 +132,16 @@ SLAB_REDUCE_ADDS = 0
 # D3F_F32X3: dropped products of the truncation split, in units of 2^-24 |a b| (2 * 2^-22 + 2^-30), and the cap
 X3_DROPPED = 8.0 + 2.0 ** -6
 X3_CAP = 4
+# Winograd F(2x2, 3x3) (conv_winograd.hip): roundings of the three transforms (the contraction adds one per channel), and
+# the eval epilogue's v = o * sc + sf (+ res)
+WINO_INPUT_ROUNDINGS = 2
+WINO_FILTER_ROUNDINGS = 4
+WINO_OUTPUT_ROUNDINGS = 4
+WINO_EVAL_ROUNDINGS = 2
+WINO_EVAL_RES_ROUNDINGS = 3
+WINO_BT = ((1, 0, -1, 0), (0, 1, 1, 0), (0, -1, 1, 0), (0, 1, 0, -1))
+WINO_G = ((1, 0, 0), (.5, .5, .5), (.5, -.5, .5), (0, 0, 1))
+WINO_AT = ((1, 1, 1, 0), (0, 1, -1, -1))
 
 Case = namedtuple("Case", "dtype B H W C0 C1 Cout k stride pad up cin_real ws dirs forms why ragged entry",
                   defaults=(None, "conv"))
@@ -207,23 +256,83 @@ def sum2x2(t):
     return t[:, :, 0::2, 0::2] + t[:, :, 0::2, 1::2] + t[:, :, 1::2, 0::2] + t[:, :, 1::2, 1::2]
 
 
-def reference(c, data, dirs=None):
-    """float64 results and magnitude terms (the same contractions on absolute values) of the directions asked for, NCHW:
-    y, y_mag; dx (gradient of the conv input, all channels, full resolution), dx_mag; dw, dw_mag"""
+def make_exact_data(c, seed=0):
+    """make_data's tensors drawn uniformly from {-1, 0, 1}: the operands on which fp32 arithmetic is exact (docstring);
+    a case that broke one of exact_conditions would get more zeros here, not leave the table"""
+    g = torch.Generator().manual_seed(1000 * seed + 17 + c.B + 7 * c.H + 13 * c.Cout)
+    c0 = c.cin_real if c.C1 == 0 else c.C0
+    h0, w0 = (c.H // 2, c.W // 2) if c.up else (c.H, c.W)
+    ho, wo = out_hw(c)
+    tri = lambda *s: torch.randint(-1, 2, s, generator=g).double()  # noqa: E731
+    x0 = tri(c.B, c0, h0, w0)
+    x1 = tri(c.B, c.C1, c.H, c.W) if c.C1 else None
+    return x0, x1, tri(c.Cout, c.cin_real, c.k, c.k), tri(c.B, c.Cout, ho, wo)
+
+
+def exact_conditions(c, plan, data, y=None):
+    """{name: the largest magnitude an fp32 partial sum of that contraction can reach}: each must stay below 2^24 for the
+    exact pass to be exact in any summation order.  y: the float64 forward result (statistics rows)"""
+    x0, x1, w, dy = data
+    mx = max(float(x0.abs().max()), float(x1.abs().max()) if x1 is not None else 0.0)
+    mw, mdy = float(w.abs().max()), float(dy.abs().max())
+    ho, wo = out_hw(c)
+    wino = c.entry == "winograd"
+    out = {}
+    if "fwd" in c.dirs:
+        # (pre-summed up-fold weights: |w1 + .. + w4| <= |w1| + .. + |w4|, the same total; Winograd: |B^T| |d| |B| <= 4 max|x|,
+        # |G| |g| |G^T| <= 2.25 max|w| per position, |A^T| |M| |A| sums 9 positions, all in quarter-integers: x 4)
+        out["forward contraction"] = c.k * c.k * (c.C0 + c.C1) * mx * mw * (4 * 9 * 4 * 2.25 if wino else 1)
+        if y is not None:
+            out["statistics row"] = stat_row_pixels(plan.fwd, wino) * float((y * y).max())
+    if "dgrad" in c.dirs:
+        out["data-gradient contraction"] = (4 if c.up else 1) * dgrad_n(c) * mdy * mw + 1   # + the base of acc0 / acc1
+    if "wgrad" in c.dirs:
+        out["weight-gradient contraction"] = c.B * ho * wo * mx * mdy * (4 if c.up else 1)  # (class form: four taps)
+    return out
+
+
+def reference(c, data, dirs=None, mags=True):
+    """float64 results and (mags) magnitude terms (the same contractions on absolute values) of the directions asked for,
+    NCHW: y, y_mag; dx (gradient of the conv input, all channels, full resolution), dx_mag; dw, dw_mag"""
     x0, x1, w, dy = data
     dirs = c.dirs if dirs is None else dirs
     xin = conv_input(c, x0, x1)
     r = {}
     if "fwd" in dirs:
         r["y"] = F.conv2d(xin, w, None, c.stride, c.pad)
-        r["y_mag"] = F.conv2d(xin.abs(), w.abs(), None, c.stride, c.pad)
+        if mags:
+            r["y_mag"] = F.conv2d(xin.abs(), w.abs(), None, c.stride, c.pad)
     if "dgrad" in dirs:
         r["dx"] = torch.nn.grad.conv2d_input(xin.shape, w, dy, c.stride, c.pad)
-        r["dx_mag"] = torch.nn.grad.conv2d_input(xin.shape, w.abs(), dy.abs(), c.stride, c.pad)
+        if mags:
+            r["dx_mag"] = torch.nn.grad.conv2d_input(xin.shape, w.abs(), dy.abs(), c.stride, c.pad)
     if "wgrad" in dirs:
         r["dw"] = torch.nn.grad.conv2d_weight(xin, w.shape, dy, c.stride, c.pad)
-        r["dw_mag"] = torch.nn.grad.conv2d_weight(xin.abs(), w.shape, dy.abs(), c.stride, c.pad)
+        if mags:
+            r["dw_mag"] = torch.nn.grad.conv2d_weight(xin.abs(), w.shape, dy.abs(), c.stride, c.pad)
     return r
+
+
+# ---- Winograd F(2x2, 3x3) in float64 ---------------------------------------------------------------------------------------
+def winograd_tiles(x):
+    """[B, C, H, W] -> the 4 x 4 input tiles at stride 2 on the zero-padded input, [B, C, 4, 4, H / 2, W / 2]"""
+    H, W = x.shape[2:]
+    xp = F.pad(x, (1, 1, 1, 1))
+    return torch.stack([torch.stack([xp[:, :, a:a + H:2, b:b + W:2] for b in range(4)], 2) for a in range(4)], 2)
+
+
+def winograd_eval(x, w, absolute=False):
+    """A^T [ sum_c (G g G^T) (.) (B^T d B) ] A in float64, [B, K, H, W]; absolute: on |x|, |w| with |B^T|, |G|, |A^T| -- the
+    magnitude term Ymag of the Winograd bound"""
+    bt, g, at = (torch.tensor(m, dtype=torch.float64) for m in (WINO_BT, WINO_G, WINO_AT))
+    x, w = x.double(), w.double()
+    if absolute:
+        x, w, bt, g, at = x.abs(), w.abs(), bt.abs(), g.abs(), at.abs()
+    v = torch.einsum("ia,bcaets,je->bcijts", bt, winograd_tiles(x), bt)
+    u = torch.einsum("ia,kcae,je->kcij", g, w, g)
+    m = torch.einsum("kcij,bcijts->bkijts", u, v)
+    y = torch.einsum("pi,bkijts,qj->bktpsq", at, m, at)
+    return y.reshape(x.shape[0], w.shape[0], x.shape[2], x.shape[3])
 
 
 # ---- bounds --------------------------------------------------------------------------------------------------------------
@@ -314,14 +423,41 @@ def wgrad_bound(c, plan, dw_mag):
     return (acc_roundings(c.dtype, n) + extra) * U24 * dw_mag  # the gradient is fp32 in every storage type
 
 
-def stats_reference(c, plan, y, y_mag, wino=False):
-    """per-channel (sum y, sum y^2) in float64 and their bounds"""
-    acc = fwd_acc_bound(c, plan, y_mag)
+def stats_reference(c, plan, y, y_mag, wino=False, acc=None):
+    """per-channel (sum y, sum y^2) in float64 and their bounds; acc: the accumulator bound where it is not the plain
+    contraction's (Winograd: wino_acc_bound)"""
+    acc = fwd_acc_bound(c, plan, y_mag) if acc is None else acc
     rows = stat_row_pixels(plan.fwd, wino)
     s1, s2 = y.sum((0, 2, 3)), (y * y).sum((0, 2, 3))
     b1 = acc.sum((0, 2, 3)) + rows * U24 * y.abs().sum((0, 2, 3))
     b2 = (2 * y.abs() * acc + acc * acc).sum((0, 2, 3)) + rows * U24 * s2
     return s1, s2, b1, b2
+
+
+def gamma(n):
+    """n roundings compounded: (1 + 2^-24)^n - 1 <= n * 2^-24 / (1 - n * 2^-24)"""
+    return n * U24 / (1.0 - n * U24)
+
+
+def wino_roundings(c):
+    return c.C0 + WINO_INPUT_ROUNDINGS + WINO_FILTER_ROUNDINGS + WINO_OUTPUT_ROUNDINGS
+
+
+def wino_acc_bound(c, wino_mag):
+    """conv_winograd_kernel's output before the epilogue; wino_mag = winograd_eval(x, w, absolute=True)"""
+    return gamma(wino_roundings(c)) * wino_mag
+
+
+def wino_eval_reference(o, o_err, scale, shift, res, relu):
+    """the eval epilogue relu?(o * scale + shift + res?) in float64 and its bound.  o, o_err: the float64 convolution
+    and the bound of the kernel's own o; scale, shift [K]; res like o or None"""
+    sc, sf = scale.double().view(1, -1, 1, 1), shift.double().view(1, -1, 1, 1)
+    ref = o * sc + sf
+    terms = (o * sc).abs() + sf.abs()
+    k = WINO_EVAL_ROUNDINGS
+    if res is not None:
+        ref, terms, k = ref + res, terms + res.abs(), WINO_EVAL_RES_ROUNDINGS
+    return (ref.clamp_min(0.0) if relu else ref), sc.abs() * o_err + k * U24 * terms
 
 
 def violations(got, ref, bound):
@@ -417,6 +553,9 @@ CASES = [
     Case(F32, 1, 16, 16, 16, 0, 64, 3, 1, 1, 0, 16, 0, ('fwd',),
          [(F32, 'fwd', 'wino')],
          'conv_winograd_kernel: one workgroup, every image border inside one patch', None, 'winograd'),
+    Case(F32, 1, 16, 16, 32, 0, 64, 3, 1, 1, 0, 32, 0, ('fwd',),
+         [(F32, 'fwd', 'wino')],
+         'conv_winograd_kernel: two chunks, the last one contracted from V[1] (1 and 3 chunks both end in V[0])', None, 'winograd'),
     Case(F32, 2, 32, 48, 48, 0, 128, 3, 1, 1, 0, 48, 0, ('fwd',),
          [(F32, 'fwd', 'wino')],
          'conv_winograd_kernel: odd chunk count, two filter blocks, non-square', None, 'winograd'),

@@ -8,7 +8,12 @@
 * the 4e-3 rel-L2 gate of the bf16 conv_pres case does NOT see a whole wrong corner pixel: the hole the bound closes;
 * form coverage: every kernel form the whole-network plans take (d3f_unet_conv_layer) is reached by an operator case
   (d3f_conv_layer_plan), and every case still selects the forms it is there for;
-* every persistent weight-gradient kernel has a case whose workgroups take unequal shares.
+* every persistent weight-gradient kernel has a case whose workgroups take unequal shares;
+* Winograd F(2x2, 3x3): the kernel's path restated in torch fp32 stays inside the derived bound of conv_cases.py for every
+  Winograd case, on N(0, 1) inputs and on inputs shifted by + 8; the same path with V rounded to bf16 violates it; on
+  operands in {-1, 0, 1} the fp32 path is exact;
+* exact operands: every case's {-1, 0, 1} data set keeps every fp32 partial sum below 2^24, the condition under which
+  the exact pass of tests/test_gpu_conv_forms.py may demand equality.
 """
 import ctypes as C
 
@@ -16,11 +21,13 @@ import pytest
 import torch
 
 import conv_cases as cc
+import packed_restatement as pr
 from conv_cases import ALL, BF16, CASES, F32, F32X3
 from denoising_diffusion_deep_fake_amd import _lib
 
 CPU_MACS = 2e8  # cases above this many multiply-adds skip the CPU evaluations here (the GPU test runs them all)
 SMALL = [c for c in CASES if cc.macs(c) <= CPU_MACS and c.entry == "conv"]
+WINO = [c for c in CASES if c.entry == "winograd"]
 PRES = next(c for c in CASES if c.dtype == BF16 and (c.B, c.H, c.W, c.C0, c.Cout) == (12, 64, 64, 64, 64))
 
 # What the single-operator entry points cannot express.  None of it selects another kernel instantiation -- a form is
@@ -273,6 +280,129 @@ def test_every_persistent_weight_gradient_kernel_has_a_case_with_unequal_shares(
             seen.setdefault((w.patch, w.cls), cc.case_id(c))
     want = {(1, 0), (1, 1), (2, 0), (3, 0), (4, 0), (7, 0), (0, 0)}
     assert want <= set(seen) and ((5, 0) in seen or (6, 0) in seen), seen
+
+
+# ---- Winograd F(2x2, 3x3) --------------------------------------------------------------------------------------------------
+def winograd_fp32(x, w, v_bf16=False):
+    """conv_winograd_kernel restated in torch fp32, operation for operation: 4 x 4 tiles at stride 2 on the zero-padded
+    input; tr_col then tr_row; the filter transform of winograd_pack_kernel; per position one fused multiply-add per
+    channel into the fp32 accumulator (the product exact in float64, one rounding of the sum), in the kernel's channel
+    order -- chunk of 16, half s2, element e, the MFMA's pair (8 s2 + e, 8 s2 + 4 + e); (a + b) + c down the rows of
+    positions, then along the columns.  v_bf16: V rounded to bf16, the planted fault."""
+    x, w = x.float(), w.float()
+    (B, C, H, W), K = x.shape, w.shape[0]
+    d = cc.winograd_tiles(x)                                            # [B, C, 4, 4, Ty, Tx]
+    t = [[None] * 4 for _ in range(4)]
+    for j in range(4):                                                  # tr_col: B^T d
+        d0, d1, d2, d3 = (d[:, :, a, j] for a in range(4))
+        t[0][j], t[1][j], t[2][j], t[3][j] = d0 - d2, d1 + d2, d2 - d1, d1 - d3
+    v = []
+    for i in range(4):                                                  # tr_row: (B^T d) B, positions 4 i .. 4 i + 3
+        v += [t[i][0] - t[i][2], t[i][1] + t[i][2], t[i][2] - t[i][1], t[i][1] - t[i][3]]
+    v = torch.stack(v, 2)                                               # [B, C, 16, Ty, Tx]
+    if v_bf16:
+        v = v.bfloat16().float()
+    u = pr.winograd_filter_fp32(w).reshape(K, C, 16)
+    acc = torch.zeros(B, K, 16, H // 2, W // 2)
+    for ch in range(C // 16):
+        for s2 in range(2):
+            for e in range(4):
+                for fq in range(2):
+                    ci = 16 * ch + 8 * s2 + 4 * fq + e
+                    acc = (acc.double() + u[:, ci].double()[None, :, :, None, None] * v[:, ci].double()[:, None]).float()
+    a = [acc[:, :, q] for q in range(16)]
+    t0 = [(a[j] + a[4 + j]) + a[8 + j] for j in range(4)]
+    t1 = [(a[4 + j] - a[8 + j]) - a[12 + j] for j in range(4)]
+    o00, o01 = (t0[0] + t0[1]) + t0[2], (t0[1] - t0[2]) - t0[3]
+    o10, o11 = (t1[0] + t1[1]) + t1[2], (t1[1] - t1[2]) - t1[3]
+    y = torch.stack([torch.stack([o00, o01], -1), torch.stack([o10, o11], -1)], 3)   # [B, K, Ty, 2, Tx, 2]
+    return y.reshape(B, K, H, W)
+
+
+@pytest.mark.parametrize("shift", [0.0, 8.0], ids=["N01", "N01+8"])
+@pytest.mark.parametrize("case", WINO, ids=cc.case_id)
+def test_winograd_bound_admits_the_fp32_restatement_and_flags_a_bf16_V(case, shift):
+    """N(0, 1) inputs, and the same inputs shifted by + 8, where B^T d B cancels the offset: Ymag follows |d| and the
+    bound with it.  The same path with V rounded to bf16 (2^-9 per term against (C + 10) * 2^-24) must violate it."""
+    c = case
+    x0, _, w, _ = cc.make_data(c)
+    x = (x0 + shift).float().double()
+    ref = torch.nn.functional.conv2d(x, w, None, 1, 1)
+    direct_mag = torch.nn.functional.conv2d(x.abs(), w.abs(), None, 1, 1)
+    mag = cc.winograd_eval(x, w, absolute=True)
+    assert bool(((cc.winograd_eval(x, w) - ref).abs() <= 64 * 2.0 ** -53 * mag).all()), "float64 Winograd == the convolution"
+    assert bool((mag >= direct_mag * (1 - 1e-12)).all())
+    bound = cc.wino_acc_bound(c, mag)
+    assert cc.wino_roundings(c) == c.C0 + 10
+    got = winograd_fp32(x, w)
+    bad, ratio = cc.violations(got, ref, bound)
+    print(f"error/bound winograd fp32 restatement {cc.case_id(c)} shift {shift}: {ratio:.4f}; "
+          f"Ymag / direct magnitude {float(mag.sum() / direct_mag.sum()):.2f}")
+    assert bad == 0, (bad, ratio)
+    bad16, ratio16 = cc.violations(winograd_fp32(x, w, v_bf16=True), ref, bound)
+    assert bad16 > ref.numel() // 2 and ratio16 > 16, (bad16, ratio16)
+    if shift:
+        return
+    # the statistics and the eval epilogue of the same fp32 values, under their derived bounds
+    plan = cc.plan_of(c)
+    s1, s2, b1, b2 = cc.stats_reference(c, plan, ref, None, wino=True, acc=bound)
+    assert cc.stat_row_pixels(plan.fwd, True) == 256
+    assert cc.violations(got.sum((0, 2, 3)), s1, b1)[0] == 0 and cc.violations((got * got).sum((0, 2, 3)), s2, b2)[0] == 0
+    g = torch.Generator().manual_seed(5)
+    sc, sf = torch.rand(c.Cout, generator=g) + 0.5, torch.randn(c.Cout, generator=g) * 0.3
+    res = torch.randn(ref.shape, generator=g)
+    for with_res in (False, True):
+        for relu in (False, True):
+            v32 = got * sc.view(1, -1, 1, 1) + sf.view(1, -1, 1, 1)
+            v32 = v32 + res if with_res else v32
+            v32 = v32.clamp_min(0) if relu else v32
+            want, bnd = cc.wino_eval_reference(ref, bound, sc, sf, res.double() if with_res else None, relu)
+            assert cc.violations(v32, want, bnd)[0] == 0, (with_res, relu)
+            # a dropped shift is outside it (|shift| ~ 0.3 against ~1e-5)
+            assert cc.violations(v32 - sf.view(1, -1, 1, 1) * (v32 > 0), want, bnd)[0] > want.numel() // 8
+
+
+@pytest.mark.parametrize("case", WINO, ids=cc.case_id)
+def test_winograd_in_fp32_is_exact_on_exact_operands(case):
+    x0, _, w, _ = cc.make_exact_data(case)
+    ref = torch.nn.functional.conv2d(x0, w, None, 1, 1)
+    assert torch.equal(winograd_fp32(x0, w).double(), ref)
+    assert torch.equal(cc.winograd_eval(x0, w), ref)
+
+
+def test_the_winograd_cases_end_in_both_V_buffers():
+    """chunk c is contracted from V[c & 1]: the table has a case that ends in V[1] (an even chunk count) and cases that end
+    in V[0]; one with a single chunk (nothing double-buffered), one with two filter blocks and several workgroups"""
+    chunks = sorted(c.C0 // 16 for c in WINO)
+    assert 1 in chunks and any(n % 2 == 0 for n in chunks) and any(n % 2 == 1 and n > 1 for n in chunks)
+    assert any(c.Cout > 64 and c.B * (c.H // 16) * (c.W // 16) > 1 for c in WINO)
+    assert all(16 <= c.H <= 48 and 16 <= c.W <= 48 for c in WINO)
+
+
+# ---- exact operands --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES, ids=cc.case_id)
+def test_exact_operands_keep_every_fp32_sum_exact(case):
+    """the conditions under which the exact pass of tests/test_gpu_conv_forms.py may demand equality: every operand in
+    {-1, 0, 1}, and every partial sum an fp32 contraction or statistics row can form stays below 2^24 -- B * Ho * Wo *
+    max|x dy| for the weight gradient, the tap and channel count for the others, stat_row_pixels * max(y^2) for a
+    statistics row.  (The forward result is evaluated in fp32 here: exact once the first condition holds.)"""
+    c = case
+    plan = cc.plan_of(c)
+    data = cc.make_exact_data(c)
+    for t in data:
+        assert t is None or (bool(((t == 0) | (t.abs() == 1)).all()) and len(t.unique()) == 3)
+    assert torch.equal(data[0], cc.make_exact_data(c)[0]), "deterministic"
+    first = cc.exact_conditions(c, plan, data)
+    assert first and all(v < 2 ** 24 for v in first.values()), first
+    y = None
+    if "fwd" in c.dirs:
+        x0, x1, w, _ = data
+        y = torch.nn.functional.conv2d(cc.conv_input(c, x0, x1).float(), w.float(), None, c.stride, c.pad).double()
+        if cc.macs(c) <= CPU_MACS:
+            assert torch.equal(y, cc.reference(c, data, dirs=("fwd",), mags=False)["y"])
+    cond = cc.exact_conditions(c, plan, data, y)
+    assert ("statistics row" in cond) == ("fwd" in c.dirs)
+    assert all(v < 2 ** 24 for v in cond.values()), cond
 
 
 def test_f32x3_term_stays_under_the_fp32_bound_with_four_more_roundings():

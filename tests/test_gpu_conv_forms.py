@@ -14,7 +14,16 @@ route needs it), d3f_conv_backward_weight, d3f_conv_winograd_* -- and each call 
   cin_real < C0 as finite garbage (dY pad channels stay zero: d3f_head_activation_backward's contract);
 * every call runs twice from the same poisoned state and must give the same bits (no result path has an atomic);
 * acc0 / acc1: a second data-gradient call accumulates into a random base and is held to base + gradient under the one
-  counted extra addition.
+  counted extra addition;
+* exact operands: every case runs a second time (test_conv_case_exact) on conv_cases.make_exact_data -- operands in
+  {-1, 0, 1}, on which fp32 arithmetic makes no rounding error in any order -- through the same guards, poison, garbage pad
+  channels and repeat, and every result must EQUAL the float64 one passed through the route's storage roundings
+  (conv_cases.py lists them); a failure reports how many elements differ and the first index.
+
+Winograd F(2x2, 3x3) goes through d3f_conv_winograd_pack / d3f_conv_winograd_forward: the raw output under its own
+per-element bound gamma_(C + 10) * Ymag (conv_cases.py has the analysis), both statistics sums under the bounds derived
+from it, and the eval epilogue of the same kernel -- relu?(conv * scale + shift + residual?), all four variants, the
+residual behind guard bands -- under |scale| * E_o + k * 2^-24 * (|o scale| + |shift| + |res|).
 
 What launches what (python tests/conv_cases.py prints it from the plan structs; kernel instantiation, its form tuple --
 (dtype 0 f32 / 1 bf16 / 2 f32x3, launch, patch, tile_bm, tile_bn, par, nz, small_c, fast_addr, sum2, splitk > 1) or
@@ -79,7 +88,9 @@ conv_igemm_kernel<float, 64, 64, FAST 1>
     <- f32-12x64x64-96+0to32-k3s1-up2-ws0
 conv_winograd_kernel
     (0, 'fwd', 'wino')
-    <- f32-1x16x16-16+0to64-k3s1-up0-ws0-wino, f32-2x32x48-48+0to128-k3s1-up0-ws0-wino
+    <- f32-1x16x16-16+0to64-k3s1-up0-ws0-wino, f32-1x16x16-32+0to64-k3s1-up0-ws0-wino, f32-2x32x48-48+0to128-k3s1-up0-ws0-wino
+    (1, 2 and 3 chunks of 16 channels: the last chunk contracted from V[0], V[1], V[0]; raw output + statistics rows,
+    and the eval epilogue {no residual, residual} x {no ReLU, ReLU})
 conv_igemm_kernel<float, 128, 64, FAST 2 (up-folded)>
     (0, 'fwd', 0, 128, 64, 3, 4, 0, 0, 0, 0)
     <- f32-16x16x128-32+32to96-k3s1-up2-ws0
@@ -454,7 +465,8 @@ conv_wgrad_patch_kernel<float, 32, 32, 3, 1, 16> + wgrad_reduce_batch_kernel
     <- f32x3-1x4x4-32+32to32-k3s1-up2-ws0
 
 Reachable only through the whole network (run-time paths of the instantiations above, no instantiation of their own):
-the eval-fused epilogue of d3f_conv_forward's kernels (CONV_EVAL_FUSED) and the head's bias + NCHW epilogue
+the eval-fused epilogue of d3f_conv_forward's kernels (CONV_EVAL_FUSED; conv_winograd_kernel's own is run here, through
+d3f_conv_winograd_forward's scale / shift / residual arguments) and the head's bias + NCHW epilogue
 (CONV_HEAD_NCHW), BatchNorm partial sums riding in a data-gradient epilogue (ConvParams::bn_partial), and two networks
 in one launch (grid.z = nets): tests/test_gpu_unet.py, test_gpu_bf16.py, test_gpu_parity_layers.py, test_gpu_pair.py.
 """
@@ -525,6 +537,17 @@ def check(direction, c, got_nchw, ref, bound, gate):
     assert e < gate, (direction, cc.case_id(c), "rel-L2", e)
 
 
+def same(direction, c, got, want):
+    """the exact pass: equality with the float64 result (after the route's storage roundings), no tolerance"""
+    got = got.double()
+    diff = got != want   # (NaN differs from everything)
+    n = int(diff.sum())
+    first = tuple(diff.nonzero()[0].tolist()) if n else None
+    assert got.shape == want.shape and torch.equal(got, want), \
+        (direction, cc.case_id(c), f"{n} of {want.numel()} elements differ, first at {first}",
+         None if first is None else (float(got[first]), float(want[first])))
+
+
 def gate_of(c):
     return cc.REL_L2_BF16 if c.dtype == BF16 else cc.REL_L2_F32
 
@@ -538,13 +561,16 @@ def device_input(x64, cpad, dtype, gen):
 
 
 class Run:
-    def __init__(self, c):
-        self.c, self.L = c, _lib.lib()
+    def __init__(self, c, exact=False):
+        self.c, self.L, self.exact = c, _lib.lib(), exact
         self.d = cc.desc_of(c)
         self.plan = cc.plan_of(c)
         assert cc.case_forms(c, self.plan) == c.forms, "the planner moved this case: tests/test_cpu_conv_forms.py"
-        self.data = cc.make_data(c)
-        self.ref = cc.reference(c, self.data)
+        self.data = cc.make_exact_data(c) if exact else cc.make_data(c)
+        self.ref = cc.reference(c, self.data, mags=not exact)
+        if exact:   # what makes equality the right demand (tests/test_cpu_conv_forms.py asserts the same without a GPU)
+            cond = cc.exact_conditions(c, self.plan, self.data, self.ref.get("y"))
+            assert all(v < 2 ** 24 for v in cond.values()), cond
         self.gen = torch.Generator().manual_seed(99)
         x0, x1, w, dy = self.data
         self.tt = cc.tdt(c.dtype)
@@ -557,6 +583,15 @@ class Run:
 
     def ok(self, rc):
         assert rc == 0, self.L.d3f_last_error().decode()
+
+    def stored(self, x64):
+        return cc.stored(x64, self.c.dtype)
+
+    def base(self, *shape):
+        """an existing gradient to accumulate into: storage-type N(0, 1), or {-1, 0, 1} in the exact pass"""
+        if self.exact:
+            return torch.randint(-1, 2, shape, generator=self.gen).double()
+        return self.stored(torch.randn(*shape, generator=self.gen, dtype=torch.float64))
 
     # ---- packed weights: NaN bytes before the pack ----
     def pack(self):
@@ -591,13 +626,19 @@ class Run:
                                                      ptr(stats), ptr(ws), stream())), outs, poison)
         assert self.wf.intact()
         got = cc.to_nchw(y.t.cpu().view(c.B, self.ho, self.wo, c.Cout))
-        ref_y, mag = self.ref["y"], self.ref["y_mag"]
-        check("fwd", c, got, ref_y, cc.fwd_bound(c, plan, ref_y, mag), gate_of(c))
+        ref_y = self.ref["y"]
         st = stats.t.cpu().view(rows + SPARE_STAT_ROWS, cpad, 2)
         assert bool(torch.isfinite(st[:rows, :c.Cout]).all()), "statistics rows not written"
         assert bool(torch.isnan(st[rows:]).all()), "statistics written behind the last row the plan names"
-        s1, s2, b1, b2 = cc.stats_reference(c, plan, ref_y, mag)
         sums = st[:rows, :c.Cout].double().sum(0)
+        if self.exact:
+            same("fwd", c, got, self.stored(ref_y))
+            same("stats sum", c, sums[:, 0], ref_y.sum((0, 2, 3)))
+            same("stats sumsq", c, sums[:, 1], (ref_y * ref_y).sum((0, 2, 3)))
+            return
+        mag = self.ref["y_mag"]
+        check("fwd", c, got, ref_y, cc.fwd_bound(c, plan, ref_y, mag), gate_of(c))
+        s1, s2, b1, b2 = cc.stats_reference(c, plan, ref_y, mag)
         for name, got_s, ref_s, bnd in (("sum", sums[:, 0], s1, b1), ("sumsq", sums[:, 1], s2, b2)):
             bad, ratio = cc.violations(got_s, ref_s, bnd)
             note("stats " + name, c, ratio)
@@ -612,10 +653,11 @@ class Run:
         dx1 = Guarded(c.B * c.H * c.W * c.C1, GUARD_ROWS * c.C1, self.tt) if c.C1 else None
         ws = byte_buffer(L.d3f_conv_workspace_bytes(c.dtype, C.byref(d), 1)) if c.ws else None
         outs = [dx0] + ([dx1] if dx1 else []) + ([ws] if ws else [])
-        ref_dx, mag = self.ref["dx"], self.ref["dx_mag"]
-        r0, m0 = ref_dx[:, :c.C0], mag[:, :c.C0]
-        base0 = cc.stored(torch.randn(c.B, c.C0, h0, w0, generator=self.gen, dtype=torch.float64), c.dtype)
-        base1 = cc.stored(torch.randn(c.B, c.C1, c.H, c.W, generator=self.gen, dtype=torch.float64), c.dtype) if c.C1 else None
+        ref_dx, mag = self.ref["dx"], self.ref.get("dx_mag")
+        r0, m0 = ref_dx[:, :c.C0], None if mag is None else mag[:, :c.C0]
+        r1, m1 = ref_dx[:, c.C0:], None if mag is None else mag[:, c.C0:]
+        base0 = self.base(c.B, c.C0, h0, w0)
+        base1 = self.base(c.B, c.C1, c.H, c.W) if c.C1 else None
 
         def call(acc):
             return lambda: self.ok(L.d3f_conv_backward_data(c.dtype, C.byref(d), ptr(self.dy), ptr(self.wd), ptr(dx0), ptr(dx1),
@@ -643,23 +685,33 @@ class Run:
 
         run_twice(call(0), outs, poison(0))
         assert self.wd.intact()
-        if low:
-            want0, err0 = cc.sum2x2(r0), cc.dgrad_low_err(c, plan, r0, m0)
+        want0 = cc.sum2x2(r0) if low else r0
+        if self.exact:
+            same("dgrad " + route, c, read0(), self.stored(want0))
+            if dx1:
+                same("dgrad skip", c, read1(), self.stored(r1))
         else:
-            want0, err0 = r0, cc.dgrad_full_err(c, m0)
-        check("dgrad " + route, c, read0(), want0, cc.store_rounding(c.dtype, want0, err0), gate_of(c))
-        if dx1:
-            r1, m1 = ref_dx[:, c.C0:], mag[:, c.C0:]
-            check("dgrad skip", c, read1(), r1, cc.dgrad_full_bound(c, r1, m1), gate_of(c))
+            err0 = cc.dgrad_low_err(c, plan, r0, m0) if low else cc.dgrad_full_err(c, m0)
+            check("dgrad " + route, c, read0(), want0, cc.store_rounding(c.dtype, want0, err0), gate_of(c))
+            if dx1:
+                check("dgrad skip", c, read1(), r1, cc.dgrad_full_bound(c, r1, m1), gate_of(c))
         if route == "fullres":  # the caller reduces the full-resolution gradient itself
             lowg = Guarded(c.B * (c.H // 2) * (c.W // 2) * c.C0, GUARD_ROWS * c.C0, self.tt)
             run_twice(lambda: self.ok(L.d3f_upsample2x_backward(c.dtype, ptr(dx0), ptr(lowg), c.B, c.H // 2, c.W // 2, c.C0, stream())),
                       [lowg], lambda: lowg.t.fill_(SENTINEL))
             assert dx0.intact()
             got = cc.to_nchw(lowg.t.cpu().view(c.B, c.H // 2, c.W // 2, c.C0))
-            check("dgrad 2x2", c, got, cc.sum2x2(r0), cc.dgrad_low_bound(c, plan, r0, m0), gate_of(c))
+            if self.exact:   # two storage roundings: the full-resolution gradient, then its 2 x 2 sums
+                same("dgrad 2x2", c, got, self.stored(cc.sum2x2(self.stored(r0))))
+            else:
+                check("dgrad 2x2", c, got, cc.sum2x2(r0), cc.dgrad_low_bound(c, plan, r0, m0), gate_of(c))
         # accumulate into an existing gradient
         run_twice(call(1), outs, poison(1))
+        if self.exact:
+            same("dgrad acc", c, read0(), self.stored(base0 + want0))
+            if dx1:
+                same("dgrad acc skip", c, read1(), self.stored(base1 + r1))
+            return
         total, bound = cc.acc_bound(c, base0, want0, err0)
         bad, ratio = cc.violations(read0(), total, bound)
         note("dgrad acc", c, ratio)
@@ -682,11 +734,15 @@ class Run:
         run_twice(lambda: self.ok(L.d3f_conv_backward_weight(c.dtype, C.byref(d), ptr(self.dy), ptr(self.s0), ptr(self.s1), ptr(ws),
                                                              ptr(dw), stream())), [dw, ws], poison)
         got = dw.t.cpu().view(c.Cout, c.cin_real, c.k, c.k)
+        if self.exact:
+            same("wgrad", c, got, self.ref["dw"])
+            return
         check("wgrad", c, got, self.ref["dw"], cc.wgrad_bound(c, plan, self.ref["dw_mag"]), cc.REL_L2_WGRAD)
 
     def winograd(self):
         """conv_winograd_kernel through its own entry: guards, poison, repeat; the aggregate gates of
-        tests/test_gpu_ops.py (the per-element bound leaves Winograd out: conv_cases.py)"""
+        tests/test_gpu_ops.py, and beside them the per-element bound of conv_cases.py on y, the bounds derived from it on
+        both statistics sums, and the four eval-epilogue variants under theirs"""
         c, L, d = self.c, self.L, self.d
         u = byte_buffer(L.d3f_conv_winograd_filter_bytes(C.byref(d)))
         run_twice(lambda: self.ok(L.d3f_conv_winograd_pack(C.byref(d), ptr(self.w), ptr(u), stream())), [u],
@@ -714,12 +770,55 @@ class Run:
         s1, s2 = ref_y.sum((0, 2, 3)), (ref_y * ref_y).sum((0, 2, 3))
         assert float(((sums[:, 1] - s2).abs().max() / s2.abs().max())) < 1e-5
         assert float((sums[:, 0] - s1).abs().max()) < 1e-3 * (1 + float(s2.sqrt().max()))
+        # every element and both sums under the Winograd bound (exact pass: equal)
+        x0, w = self.data[0], self.data[2]
+        if self.exact:
+            same("wino", c, got, ref_y)
+            same("wino stats sum", c, sums[:, 0], s1)
+            same("wino stats sumsq", c, sums[:, 1], s2)
+            acc = None
+        else:
+            acc = cc.wino_acc_bound(c, cc.winograd_eval(x0, w, absolute=True))
+            check("wino", c, got, ref_y, acc, cc.REL_L2_F32)
+            _, _, b1, b2 = cc.stats_reference(c, self.plan, ref_y, None, wino=True, acc=acc)
+            for name, got_s, ref_s, bnd in (("sum", sums[:, 0], s1, b1), ("sumsq", sums[:, 1], s2, b2)):
+                bad, ratio = cc.violations(got_s, ref_s, bnd)
+                note("wino stats " + name, c, ratio)
+                assert bad == 0, ("winograd statistics", name, cc.case_id(c), bad, ratio)
+        # the eval epilogue of the same kernel: relu?(o * scale + shift + residual?)
+        if self.exact:
+            scale = torch.tensor([-2.0, -1.0, 1.0, 2.0])[torch.randint(0, 4, (c.Cout,), generator=self.gen)]
+            shift = torch.randint(-1, 2, (c.Cout,), generator=self.gen).float()
+            res64 = torch.randint(-1, 2, ref_y.shape, generator=self.gen).double()
+        else:
+            scale = torch.rand(c.Cout, generator=self.gen) + 0.5
+            scale[::3] = -scale[::3]
+            shift = torch.randn(c.Cout, generator=self.gen) * 0.3
+            res64 = torch.randn(ref_y.shape, generator=self.gen).double()
+        sc_d, sf_d = scale.cuda(), shift.cuda()
+        res = Guarded(res64.numel(), GUARD_ROWS * c.Cout, self.tt)
+        res_nhwc = cc.to_nhwc(res64).float().reshape(-1)
+        res.t.copy_(res_nhwc)
+        for with_res in (False, True):
+            for relu in (0, 1):
+                run_twice(lambda: self.ok(L.d3f_conv_winograd_forward(C.byref(d), ptr(self.s0), ptr(u), ptr(y), None, ptr(sc_d),
+                                                                      ptr(sf_d), ptr(res) if with_res else None, relu, stream())),
+                          [y], lambda: y.t.fill_(SENTINEL))
+                assert u.intact() and res.intact() and torch.equal(res.t.cpu(), res_nhwc), "the epilogue wrote into an input"
+                out = cc.to_nchw(y.t.cpu().view(c.B, c.H, c.W, c.Cout))
+                name = "wino eval" + ("+res" if with_res else "") + ("+relu" if relu else "")
+                want, bound = cc.wino_eval_reference(ref_y, acc if acc is not None else torch.zeros_like(ref_y), scale, shift,
+                                                     res64 if with_res else None, bool(relu))
+                if self.exact:
+                    same(name, c, out, want)
+                else:
+                    check(name, c, out, want, bound, cc.REL_L2_F32)
+                assert not relu or bool((out >= 0).all())
 
 
-@pytest.mark.parametrize("case", CASES, ids=cc.case_id)
-def test_conv_case(case):
+def run_case(case, exact):
     assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    r = Run(case)
+    r = Run(case, exact)
     if case.entry == "winograd":
         r.winograd()
         return
@@ -730,6 +829,17 @@ def test_conv_case(case):
         r.backward_data()
     if "wgrad" in case.dirs:
         r.backward_weight()
+
+
+@pytest.mark.parametrize("case", CASES, ids=cc.case_id)
+def test_conv_case(case):
+    run_case(case, exact=False)
+
+
+@pytest.mark.parametrize("case", CASES, ids=cc.case_id)
+def test_conv_case_exact(case):
+    """the same case on operands in {-1, 0, 1}: every result equals float64 (conv_cases.py, "Exact operands")"""
+    run_case(case, exact=True)
 
 
 def test_report_worst_ratios():
