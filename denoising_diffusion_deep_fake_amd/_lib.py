@@ -130,7 +130,7 @@ class ConvPlan(C.Structure):
 BN_COEF_ROWS = 7  # D3F_BN_COEF_ROWS: mean invstd scale shift k0 k1 k2
 
 _p, _i, _i64, _f, _sz, _dbl = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_double
-_u64, _u32p = C.c_uint64, C.POINTER(C.c_uint32)
+_u64, _u32p, _i32p = C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
 _desc = C.POINTER(ConvDesc)
 _bnd, _bnp = C.POINTER(BnDesc), C.POINTER(BnPlan)
 _cvp = C.POINTER(ConvPlan)
@@ -214,6 +214,16 @@ PROTOTYPES = {
                                               _p, _i, _p]),
     "d3f_unet_predict_frames_full_boxes_u8": (_i, [_p, _p, _p, _p, _i, _i, C.POINTER(C.c_int32), _i, _p, _p, C.POINTER(_f),
                                                    C.POINTER(_f), _p, _i, _p]),
+    # ... and a rotation per frame: rot is HOST memory, [B][2] int32 (c16, s16)
+    "d3f_crop_resize_cubic_rboxes_u8": (_i, [_p, _i, _i, _i, _i32p, _i32p, _p, _i, _i, _i64, _p]),
+    "d3f_crop_resize_cubic_rboxes_u8_nhwc": (_i, [_i, _p, _i, _i, _i, _i32p, _i32p, _p, _i, _i, _i64, _p, _i, C.POINTER(_f),
+                                                  C.POINTER(_f), _p]),
+    "d3f_paste_resize_cubic_rboxes_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, _i32p, _i32p, _i, _p, _p]),
+    "d3f_paste_resize_cubic_color_rboxes_u8": (_i, [_p, _i, _i, _i, _i64, _p, _i, _i, _i32p, _i32p, _i, _p, _p, _p]),
+    "d3f_unet_predict_frames_rboxes_u8": (_i, [_p, _p, _p, _p, _i, _i, _i32p, _i32p, _p, C.POINTER(_f), C.POINTER(_f), _p, _i,
+                                               _p]),
+    "d3f_unet_predict_frames_full_rboxes_u8": (_i, [_p, _p, _p, _p, _i, _i, _i32p, _i32p, _i, _p, _p, C.POINTER(_f),
+                                                    C.POINTER(_f), _p, _i, _p]),
     "d3f_gray_decimate_u8": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "d3f_track_seed_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "d3f_track_search_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),

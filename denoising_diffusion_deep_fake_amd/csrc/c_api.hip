@@ -298,7 +298,7 @@ int d3f_unet_predict_frames_u8(d3f_unet_t h, const float* params, float* bnstats
                                const float std[3], void* workspace, int use_graph, void* stream) {
   D3F_CHECK(h && params && bnstats && raw_in && pair_out && mean && std && workspace, "predict_frames_u8: null argument");
   if (int rc = single_net(h, "predict_frames_u8", "has no eval-mode forward (run each network alone)")) return rc;
-  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, nullptr, 0, nullptr};
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, nullptr, 0, nullptr, nullptr};
   return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
 }
 
@@ -309,7 +309,7 @@ int d3f_unet_predict_frames_full_u8(d3f_unet_t h, const float* params, float* bn
   D3F_CHECK(h && params && bnstats && raw_in && pair_out && full_out && mean && std && workspace,
             "predict_frames_full_u8: null argument");
   if (int rc = single_net(h, "predict_frames_full_u8", "has no eval-mode forward (run each network alone)")) return rc;
-  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, full_out, feather, nullptr};
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, full_out, feather, nullptr, nullptr};
   return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
 }
 
@@ -320,7 +320,7 @@ int d3f_unet_predict_frames_boxes_u8(d3f_unet_t h, const float* params, float* b
             "predict_frames_boxes_u8: null argument");
   D3F_CHECK(boxes, "predict_frames_boxes_u8: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)");
   if (int rc = single_net(h, "predict_frames_boxes_u8", "has no eval-mode forward (run each network alone)")) return rc;
-  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, nullptr, 0, boxes};
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, nullptr, 0, boxes, nullptr};
   return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
 }
 
@@ -332,7 +332,32 @@ int d3f_unet_predict_frames_full_boxes_u8(d3f_unet_t h, const float* params, flo
             "predict_frames_full_boxes_u8: null argument");
   D3F_CHECK(boxes, "predict_frames_full_boxes_u8: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)");
   if (int rc = single_net(h, "predict_frames_full_boxes_u8", "has no eval-mode forward (run each network alone)")) return rc;
-  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, full_out, feather, boxes};
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, full_out, feather, boxes, nullptr};
+  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
+}
+
+int d3f_unet_predict_frames_rboxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
+                                      int src_w, const int32_t* boxes, const int32_t* rot, uint8_t* pair_out,
+                                      const float mean[3], const float std[3], void* workspace, int use_graph, void* stream) {
+  D3F_CHECK(h && params && bnstats && raw_in && pair_out && mean && std && workspace,
+            "predict_frames_rboxes_u8: null argument");
+  D3F_CHECK(boxes, "predict_frames_rboxes_u8: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)");
+  D3F_CHECK(rot, "predict_frames_rboxes_u8: null rot (host memory [B][2]: c16, s16 per frame)");
+  if (int rc = single_net(h, "predict_frames_rboxes_u8", "has no eval-mode forward (run each network alone)")) return rc;
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, nullptr, 0, boxes, rot};
+  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
+}
+
+int d3f_unet_predict_frames_full_rboxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in,
+                                           int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int feather,
+                                           uint8_t* pair_out, uint8_t* full_out, const float mean[3], const float std[3],
+                                           void* workspace, int use_graph, void* stream) {
+  D3F_CHECK(h && params && bnstats && raw_in && pair_out && full_out && mean && std && workspace,
+            "predict_frames_full_rboxes_u8: null argument");
+  D3F_CHECK(boxes, "predict_frames_full_rboxes_u8: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)");
+  D3F_CHECK(rot, "predict_frames_full_rboxes_u8: null rot (host memory [B][2]: c16, s16 per frame)");
+  if (int rc = single_net(h, "predict_frames_full_rboxes_u8", "has no eval-mode forward (run each network alone)")) return rc;
+  const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, full_out, feather, boxes, rot};
   return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
 }
 
@@ -874,6 +899,42 @@ int d3f_paste_resize_cubic_color_boxes_u8(const uint8_t* patch, int B, int H, in
   D3F_CHECK(patch && frame && out && coef, "paste_resize_cubic_color_boxes_u8: null argument");
   return paste_resize_cubic_color_boxes_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, boxes,
                                                   feather, coef, out, (hipStream_t)stream);
+}
+
+int d3f_crop_resize_cubic_rboxes_u8(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, const int32_t* rot,
+                                    uint8_t* dst, int H, int W, int64_t dst_row_stride_bytes, void* stream) {
+  D3F_CHECK(src && dst, "crop_resize_cubic_rboxes_u8: null argument");
+  return crop_resize_cubic_rboxes_u8_launch(src, B, src_h, src_w, boxes, rot, dst, H, W, (long)dst_row_stride_bytes,
+                                            (hipStream_t)stream);
+}
+
+int d3f_crop_resize_cubic_rboxes_u8_nhwc(int dtype, const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
+                                         const int32_t* rot, uint8_t* dst, int H, int W, int64_t dst_row_stride_bytes,
+                                         void* act, int Cpad, const float mean[3], const float std[3], void* stream) {
+  D3F_CHECK(src && dst && act && mean && std, "crop_resize_cubic_rboxes_u8_nhwc: null argument");
+  D3F_CHECK(dtype == D3F_F32 || dtype == D3F_BF16, "crop_resize_cubic_rboxes_u8_nhwc: dtype %d is neither D3F_F32 nor D3F_BF16",
+            dtype);
+  // (mean * 255, std * 255 in fp32, as the frame entries scale them)
+  const float m[3] = {mean[0] * 255.0f, mean[1] * 255.0f, mean[2] * 255.0f};
+  const float sd[3] = {std[0] * 255.0f, std[1] * 255.0f, std[2] * 255.0f};
+  return crop_resize_cubic_rboxes_u8_nhwc_launch(dtype, src, B, src_h, src_w, boxes, rot, dst, H, W, (long)dst_row_stride_bytes,
+                                                 act, Cpad, m, sd, (hipStream_t)stream);
+}
+
+int d3f_paste_resize_cubic_rboxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                     const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, const int32_t* rot,
+                                     int feather, uint8_t* out, void* stream) {
+  D3F_CHECK(patch && frame && out, "paste_resize_cubic_rboxes_u8: null argument");
+  return paste_resize_cubic_rboxes_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, boxes, rot,
+                                             feather, nullptr, false, out, (hipStream_t)stream);
+}
+
+int d3f_paste_resize_cubic_color_rboxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                           const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, const int32_t* rot,
+                                           int feather, const float* coef, uint8_t* out, void* stream) {
+  D3F_CHECK(patch && frame && out && coef, "paste_resize_cubic_color_rboxes_u8: null argument");
+  return paste_resize_cubic_rboxes_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, boxes, rot,
+                                             feather, coef, true, out, (hipStream_t)stream);
 }
 
 int64_t d3f_paste_multiband_workspace_bytes(int B, int cw_max, int ch_max, int levels) {

@@ -127,6 +127,10 @@ class UnetEngine {
     // above (d3f_unet_predict_frames_boxes_u8 / _full_boxes_u8).  The crop and the paste launches then run in their boxes
     // forms (resize.hip); everything between them works on the pair buffer and is the same.  null: one box, as ever
     const int32_t* boxes;
+    // HOST memory [B][2] (c16, s16 of frame b's angle) next to boxes: the boxes turned about their centres
+    // (d3f_unet_predict_frames_rboxes_u8 / _full_rboxes_u8); the crop and the paste then run in their rotated forms.
+    // null: as today
+    const int32_t* rot;
   };
   // use_graph: captured once per set of pointers, constants, frame size, crop box and settings; a slot per entry.  Refused
   // with boxes: a captured launch bakes its kernel arguments in, the boxes among them, and a key on their values would

@@ -828,7 +828,14 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
             "%s with a box per frame cannot be replayed from a graph: a captured launch bakes its kernel arguments in, the "
             "boxes among them, and a graph keyed on their values would be re-captured on every call; pass use_graph = 0",
             who);
-  if (int rc = boxes ? (aa ? crop_resize_cubic_aa_boxes_check : crop_resize_cubic_boxes_check)(B, c.src_h, c.src_w, boxes, H,
+  const int32_t* const rot = c.rot;
+  D3F_CHECK(!rot || boxes, "%s: rot without boxes", who);
+  D3F_CHECK(!(rot && aa), "%s: D3F_RESAMPLE_CUBIC_AA together with rot: the antialiased crop of a rotated box is out of scope",
+            who);
+  D3F_CHECK(!(rot && multiband),
+            "%s: D3F_BLEND_MULTIBAND together with rot: the multiband pyramid of a rotated box is out of scope", who);
+  if (int rc = rot    ? crop_resize_cubic_rboxes_check(B, c.src_h, c.src_w, boxes, rot, H, W, stride)
+               : boxes ? (aa ? crop_resize_cubic_aa_boxes_check : crop_resize_cubic_boxes_check)(B, c.src_h, c.src_w, boxes, H,
                                                                                               W, stride)
                      : (aa ? crop_resize_cubic_aa_check : crop_resize_cubic_check)(B, c.src_h, c.src_w, c.x1, c.y1, c.cw,
                                                                                   c.ch, H, W, stride))
@@ -866,7 +873,10 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
               "predict_frames_full_u8: full_out == raw_in (in place) cannot be replayed from a graph: pass use_graph = 0");
   } else if (full) {
     int rc;
-    if (boxes)
+    if (rot)
+      rc = paste_resize_cubic_rboxes_check(fake, c.raw_in, c.full_out, o.color_coef.p, color, B, H, W, stride, c.src_h, c.src_w,
+                                           boxes, rot, c.feather);
+    else if (boxes)
       rc = color ? paste_resize_cubic_color_boxes_check(fake, c.raw_in, c.full_out, o.color_coef.p, B, H, W, stride, c.src_h,
                                                         c.src_w, boxes, c.feather)
                  : paste_resize_cubic_boxes_check(fake, c.raw_in, c.full_out, B, H, W, stride, c.src_h, c.src_w, boxes,
@@ -890,7 +900,10 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
   }
   auto launches = [&](hipStream_t ls) {
     // one launch writes the real half of the pair and, from the same rounded bytes, the network input
-    if (int rc = boxes ? (aa ? crop_resize_cubic_aa_boxes_u8_nhwc_launch : crop_resize_cubic_boxes_u8_nhwc_launch)(
+    if (int rc = rot   ? crop_resize_cubic_rboxes_u8_nhwc_launch(dtype, c.raw_in, B, c.src_h, c.src_w, boxes, rot, pair, H, W,
+                                                                 stride, ws + tensors[t_x].off, tensors[t_x].C, k.mean, k.stdv,
+                                                                 ls)
+                 : boxes ? (aa ? crop_resize_cubic_aa_boxes_u8_nhwc_launch : crop_resize_cubic_boxes_u8_nhwc_launch)(
                              dtype, c.raw_in, B, c.src_h, c.src_w, boxes, pair, H, W, stride, ws + tensors[t_x].off,
                              tensors[t_x].C, k.mean, k.stdv, ls)
                        : (aa ? crop_resize_cubic_aa_u8_nhwc_launch : crop_resize_cubic_u8_nhwc_launch)(
@@ -912,6 +925,9 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
       return paste_multiband_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, boxes,
                                        c.feather, o.blend_levels, nullptr, false, o.blend_ws.p, o.blend_ws_bytes, c.full_out,
                                        ls);
+    if (!color && rot)
+      return paste_resize_cubic_rboxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, rot, c.feather,
+                                                 nullptr, false, c.full_out, ls);
     if (!color)
       return boxes ? paste_resize_cubic_boxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, c.feather,
                                                         c.full_out, ls)
@@ -932,6 +948,9 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
       return paste_multiband_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, boxes,
                                        c.feather, o.blend_levels, o.color_coef.p, true, o.blend_ws.p, o.blend_ws_bytes,
                                        c.full_out, ls);
+    if (rot)
+      return paste_resize_cubic_rboxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, rot, c.feather,
+                                                 o.color_coef.p, true, c.full_out, ls);
     if (boxes)
       return paste_resize_cubic_color_boxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, c.feather,
                                                       o.color_coef.p, c.full_out, ls);

@@ -247,6 +247,34 @@ int paste_resize_cubic_color_boxes_u8_launch(const uint8_t* patch, int B, int H,
                                              const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
                                              const float* coef, uint8_t* out, hipStream_t stream);
 
+// Rotated boxes (include/d3f_hip.h: the _rboxes_ operators; DESIGN.md section 4 "Rotated crop"): the _boxes_ functions with
+// one more table, rot: HOST memory [B][2] as c16 = round(cos a * 65536), s16 = round(sin a * 65536) of frame b's angle.  A
+// launch's table holds box and rotation per frame (1.5 KB by value, FRAME_BOXES_MAX frames); the kernels are forms of their
+// own (a sample's 4 x 4 neighbourhood sits per pixel, not per row and column), the 4 x 4 sum and the epilogues are shared.
+// Refused before anything is launched: what the _boxes_ functions refuse, a null rot, and for any frame a rot whose
+// c16^2 + s16^2 lies further than 2^17 from 2^32 (the message names the frame)
+struct alignas(8) FrameRot {
+  int c16, s16;
+};
+struct FrameRBoxes {
+  FrameBox box[FRAME_BOXES_MAX];
+  FrameRot rot[FRAME_BOXES_MAX];
+};
+int crop_resize_cubic_rboxes_check(int B, int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int H, int W,
+                                   long dst_row_stride);
+int crop_resize_cubic_rboxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
+                                       const int32_t* rot, uint8_t* dst, int H, int W, long dst_row_stride, hipStream_t stream);
+int crop_resize_cubic_rboxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
+                                            const int32_t* rot, uint8_t* dst, int H, int W, long dst_row_stride, void* act,
+                                            int Cpad, const float mean255[3], const float std255[3], hipStream_t stream);
+// coef null: the plain form (_check: color says which form is meant)
+int paste_resize_cubic_rboxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef,
+                                    bool color, int B, int H, int W, long patch_row_stride, int src_h, int src_w,
+                                    const int32_t* boxes, const int32_t* rot, int feather);
+int paste_resize_cubic_rboxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
+                                        int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int feather,
+                                        const float* coef, bool color, uint8_t* out, hipStream_t stream);
+
 // Multiband paste (multiband.hip; include/d3f_hip.h: d3f_paste_multiband_u8 is the definition): the paste's byte at
 // feather 0 minus the frame's byte, as a Laplacian pyramid of `levels` levels in int16 planes of a caller's workspace, each
 // band faded over its own ramp, collapsed and added to the frame.

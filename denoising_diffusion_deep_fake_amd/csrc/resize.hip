@@ -27,6 +27,9 @@
 //
 // The antialiased form (d3f_crop_resize_cubic_aa_u8: Pillow's bicubic, whose window widens with the scale) has a kernel of
 // its own behind the plain one.
+//
+// The rotated forms (the _rboxes_ operators: a box per frame, turned about its centre) are at the end of the file: kernels
+// of their own around the same weights, 4 x 4 sum and epilogues.
 #include <type_traits>
 
 #include "common.h"
@@ -45,6 +48,17 @@ struct ResizeGeom {
   int pitch;  // bytes of one staged patch row (a multiple of 4)
 };
 
+// the Keys weights (A = -0.75) of the taps s-1 .. s+2 at the fraction t = f - s
+__device__ __forceinline__ void keys_weights(float t, float w[4]) {
+  const float A = -0.75f;
+  auto inner = [A](float x) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; };       // |x| <= 1
+  auto outer = [A](float x) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; };  // 1 < |x| < 2
+  w[0] = outer(t + 1.f);
+  w[1] = inner(t);
+  w[2] = inner(1.f - t);
+  w[3] = outer(2.f - t);
+}
+
 // s = floor(f) and the four tap weights of output index d (n_in -> n_out)
 __device__ __forceinline__ int cubic_taps(int d, int n_in, int n_out, float w[4]) {
   const int num = (2 * d + 1) * n_in - n_out, den = 2 * n_out;
@@ -53,14 +67,7 @@ __device__ __forceinline__ int cubic_taps(int d, int n_in, int n_out, float w[4]
     rem += den;
     s -= 1;
   }
-  const float t = (float)rem / (float)den;
-  const float A = -0.75f;
-  auto inner = [A](float x) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; };       // |x| <= 1
-  auto outer = [A](float x) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; };  // 1 < |x| < 2
-  w[0] = outer(t + 1.f);
-  w[1] = inner(t);
-  w[2] = inner(1.f - t);
-  w[3] = outer(2.f - t);
+  keys_weights((float)rem / (float)den, w);
   return s;
 }
 
@@ -89,15 +96,13 @@ struct ResizeTile {
   unsigned align0 = 0, align_step = 0;
 };
 
-// stages what the output indices [ox_f, ox_l] x [oy_f, oy_l] read, with aligned dword loads; a dword is loaded whole only
-// inside [lo, hi).  The caller synchronises the workgroup afterwards.
-__device__ __forceinline__ ResizeTile resize_stage(uint8_t* patch, const ResizeSrc& g, int ox_f, int ox_l, int oy_f,
-                                                   int oy_l, const uint8_t* lo, const uint8_t* hi, int tid) {
+// stages columns [cx0, cx1] of rows [ry0, ry1] of the image (all inside it), with aligned dword loads; a dword is loaded
+// whole only inside [lo, hi).  The caller synchronises the workgroup afterwards.
+__device__ __forceinline__ ResizeTile resize_stage_rect(uint8_t* patch, const ResizeSrc& g, int cx0, int cx1, int ry0, int ry1,
+                                                        const uint8_t* lo, const uint8_t* hi, int tid) {
   ResizeTile t;
-  t.cx0 = max(floor_src(ox_f, g.n_w, g.out_w) - 1, 0);
-  t.ry0 = max(floor_src(oy_f, g.n_h, g.out_h) - 1, 0);
-  const int cx1 = min(floor_src(ox_l, g.n_w, g.out_w) + 2, g.n_w - 1);
-  const int ry1 = min(floor_src(oy_l, g.n_h, g.out_h) + 2, g.n_h - 1);
+  t.cx0 = cx0;
+  t.ry0 = ry0;
   const int row_bytes = (cx1 - t.cx0 + 1) * 3, rows = ry1 - t.ry0 + 1, pitch_dw = g.pitch >> 2;
   // patch row r holds the aligned dwords that cover its bytes: byte k of the row sits at r * pitch + align_r + k
   const uint8_t* first = g.img + (long)t.ry0 * g.src_pitch + (long)t.cx0 * 3;
@@ -121,12 +126,20 @@ __device__ __forceinline__ ResizeTile resize_stage(uint8_t* patch, const ResizeS
   return t;
 }
 
-// the fp32 value of output pixel (ox, oy) before rounding: horizontal pass, then vertical pass
+// stages what the output indices [ox_f, ox_l] x [oy_f, oy_l] read
+__device__ __forceinline__ ResizeTile resize_stage(uint8_t* patch, const ResizeSrc& g, int ox_f, int ox_l, int oy_f,
+                                                   int oy_l, const uint8_t* lo, const uint8_t* hi, int tid) {
+  const int cx0 = max(floor_src(ox_f, g.n_w, g.out_w) - 1, 0), ry0 = max(floor_src(oy_f, g.n_h, g.out_h) - 1, 0);
+  const int cx1 = min(floor_src(ox_l, g.n_w, g.out_w) + 2, g.n_w - 1);
+  const int ry1 = min(floor_src(oy_l, g.n_h, g.out_h) + 2, g.n_h - 1);
+  return resize_stage_rect(patch, g, cx0, cx1, ry0, ry1, lo, hi, tid);
+}
+
+// the 4 x 4 sum of the taps sx-1 .. sx+2, sy-1 .. sy+2 (indices clamped inside the image) with the weights wx, wy, in fp32:
+// horizontal pass, then vertical pass
 template <bool STAGED>
-__device__ __forceinline__ void resize_value(const uint8_t* patch, const ResizeSrc& g, const ResizeTile& t, int ox, int oy,
-                                             float v[3]) {
-  float wx[4], wy[4];
-  const int sx = cubic_taps(ox, g.n_w, g.out_w, wx), sy = cubic_taps(oy, g.n_h, g.out_h, wy);
+__device__ __forceinline__ void resize_sum(const uint8_t* patch, const ResizeSrc& g, const ResizeTile& t, int sx, int sy,
+                                           const float wx[4], const float wy[4], float v[3]) {
   int col[4];
   for (int k = 0; k < 4; ++k) col[k] = (clampi(sx - 1 + k, 0, g.n_w - 1) - t.cx0) * 3;
   float hrow[4][3];
@@ -152,6 +165,15 @@ __device__ __forceinline__ void resize_value(const uint8_t* patch, const ResizeS
     a = a + wy[3] * hrow[3][c];
     v[c] = a;
   }
+}
+
+// the fp32 value of output pixel (ox, oy) before rounding
+template <bool STAGED>
+__device__ __forceinline__ void resize_value(const uint8_t* patch, const ResizeSrc& g, const ResizeTile& t, int ox, int oy,
+                                             float v[3]) {
+  float wx[4], wy[4];
+  const int sx = cubic_taps(ox, g.n_w, g.out_w, wx), sy = cubic_taps(oy, g.n_h, g.out_h, wy);
+  resize_sum<STAGED>(patch, g, t, sx, sy, wx, wy, v);
 }
 
 // the epilogue of the crop kernels: rintf and clamp of a pixel's fp32 value v -> its three bytes at o and, ACT, the
@@ -700,6 +722,28 @@ struct PasteArgs<true, BOXES> {
   const float* coef;
 };
 
+// the epilogue of the paste kernels: the clamped patch value v (COLOR: through frame b's gain and offset, clamped again)
+// blended with weight a over the frame's three bytes at f -> the three bytes at o
+template <bool COLOR, class Args>
+__device__ __forceinline__ void paste_blend(const float v[3], float a, const uint8_t* f, uint8_t* o, const Args& args, int b) {
+  const float na = 1.f - a;
+  const float s[3] = {(float)f[0], (float)f[1], (float)f[2]};
+  uint8_t px[3];
+  for (int c = 0; c < 3; ++c) {
+    float vc = fminf(fmaxf(v[c], 0.f), 255.f);
+    if constexpr (COLOR) {
+      const float scaled = args.coef[((long)b * 3 + c) * 2] * vc;
+      vc = fminf(fmaxf(scaled + args.coef[((long)b * 3 + c) * 2 + 1], 0.f), 255.f);
+    }
+    const float pv = a * vc, ps = na * s[c];
+    const float r = rintf(pv + ps);
+    px[c] = (uint8_t)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r));
+  }
+  o[0] = px[0];
+  o[1] = px[1];
+  o[2] = px[2];
+}
+
 // COLOR (include/d3f_hip.h: d3f_paste_resize_cubic_color_u8): the clamped patch value goes through gain * v + offset of its
 // frame and channel (product and sum rounded separately) and a second clamp before the blend
 // BOXES: frame b takes box b of the table; g.pitch (and STAGED) are the launch's, sized for its largest staged part.  In
@@ -764,22 +808,7 @@ __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void paste_resize_cubic_kern
   const int dy = min(i, g.ch - 1 - i), dx = min(j, g.cw - 1 - j);
   const float ay = (float)min(dy + 1, g.feather + 1) / (float)(g.feather + 1);
   const float ax = (float)min(dx + 1, g.feather + 1) / (float)(g.feather + 1);
-  const float a = ay * ax, na = 1.f - a;
-  const float s[3] = {(float)f[at], (float)f[at + 1], (float)f[at + 2]};
-  uint8_t px[3];
-  for (int c = 0; c < 3; ++c) {
-    float vc = fminf(fmaxf(v[c], 0.f), 255.f);
-    if constexpr (COLOR) {
-      const float scaled = args.coef[((long)b * 3 + c) * 2] * vc;
-      vc = fminf(fmaxf(scaled + args.coef[((long)b * 3 + c) * 2 + 1], 0.f), 255.f);
-    }
-    const float pv = a * vc, ps = na * s[c];
-    const float r = rintf(pv + ps);
-    px[c] = (uint8_t)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r));
-  }
-  o[at] = px[0];
-  o[at + 1] = px[1];
-  o[at + 2] = px[2];
+  paste_blend<COLOR>(v, ay * ax, f + at, o + at, args, b);
 }
 
 int paste_resize_cubic_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, int B, int H, int W,
@@ -1060,6 +1089,441 @@ int multiband_diff_launch(const uint8_t* patch, int n, int H, int W, long patch_
   using F = std::false_type;
   if (boxes) return color ? go(T{}, T{}) : go(F{}, T{});
   return color ? go(T{}, F{}) : go(F{}, F{});
+}
+
+// ---- rotated boxes (include/d3f_hip.h: the _rboxes_ operators; DESIGN.md section 4 "Rotated crop") ----
+// Frame b's box turned by its angle about its centre; the angle arrives as c16 = round(cos a * 65536), s16 = round(sin a *
+// 65536), computed on the host.  Every coordinate is formed EXACTLY in 64-bit integers over one denominator and reduced once,
+// by a floor division, to a fixed-point position with ROT_FRAC_BITS fractional bits: its integer part is s, its fraction
+// t = (float)frac / 65536 is exact in fp32.  With extents up to RESIZE_MAX_EXTENT = 2^14 and |c16|, |s16| <= 65537:
+//   crop:  num = (2 x1 + cw - 1) 2^16 W H + c16 cw (2 ox + 1 - W) H - s16 ch (2 oy + 1 - H) W over 2^17 W H; the first term is
+//          below 2^15 2^16 2^28 = 2^59, the other two together below (|c16| + |s16|) 2^42 < 2^58.6: |num| < 2^60;
+//   paste: n_j = (cw - 1) 2^16 + c16 dx2 + s16 dy2 over 2^17 with |dx2|, |dy2| < 2^16: |n_j| < 2^34; the patch position
+//          (n_j + 2^16) W - 2^16 cw over 2^17 cw stays below 2^49.
+// From s and t on it is the arithmetic of the plain forms: keys_weights, resize_sum, resize_store / paste_blend.  A tile
+// stages the axis-aligned bounding box of its footprint (the map is affine: the extremes sit at the tile's four corners),
+// clipped to the image; the crop's image is the whole FRAME, so its taps clamp to the frame and not to the box.
+constexpr int ROT_FRAC_BITS = 16;
+constexpr long ROT_ONE = 1L << ROT_FRAC_BITS;
+
+struct RotBox {
+  int x1, y1, cw, ch, c16, s16;
+};
+
+// floor(a / b), b > 0, exactly.  On the device the quotient is first taken in fp64: the conversion of a and the division
+// are each off by 2^-53 of the quotient, which stays below 2^48 here (the crop's positions below 2^33, the paste's patch
+// positions below 2^48), so its floor is off by at most one; the exact 64-bit remainder then corrects it.  The same integer
+// as the host's division, without the 64-bit integer division's long expansion -- a lane needs up to ten of them
+__host__ __device__ inline long floor_div64(long a, long b) {  // b > 0
+#if defined(__HIP_DEVICE_COMPILE__)
+  long q = (long)floor((double)a / (double)b);
+  const long r = a - q * b;
+  if (r < 0) q -= 1;
+  if (r >= b) q += 1;
+  return q;
+#else
+  long q = a / b;
+  if (a - q * b < 0) q -= 1;
+  return q;
+#endif
+}
+__host__ __device__ inline long clampl(long v, long lo, long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the fixed-point frame position of output pixel (ox, oy) of an H x W crop of the rotated box
+__host__ __device__ inline void rot_crop_pos(const RotBox& r, int H, int W, int ox, int oy, long& px, long& py) {
+  const long nu = (long)r.cw * (2 * ox + 1 - W), nv = (long)r.ch * (2 * oy + 1 - H);
+  const long base = ROT_ONE * W * H;
+  const long numx = (2L * r.x1 + r.cw - 1) * base + (long)r.c16 * nu * H - (long)r.s16 * nv * W;
+  const long numy = (2L * r.y1 + r.ch - 1) * base + (long)r.s16 * nu * H + (long)r.c16 * nv * W;
+  const long den = 2L * W * H;  // (num / (2^17 W H)) 2^16
+  px = floor_div64(numx, den);
+  py = floor_div64(numy, den);
+}
+
+// the numerators over 2^17 of the box-local position (j', i') of frame pixel (x, y)
+__host__ __device__ inline void rot_local(const RotBox& r, int x, int y, long& nj, long& ni) {
+  const long dx2 = 2L * x - 2L * r.x1 - r.cw + 1, dy2 = 2L * y - 2L * r.y1 - r.ch + 1;
+  nj = (r.cw - 1) * ROT_ONE + r.c16 * dx2 + r.s16 * dy2;
+  ni = (r.ch - 1) * ROT_ONE - r.s16 * dx2 + r.c16 * dy2;
+}
+// -0.5 <= position < extent - 0.5
+__host__ __device__ inline bool rot_inside(long n, int extent) { return n >= -ROT_ONE && n < (2L * extent - 1) * ROT_ONE; }
+// the fixed-point position in a patch of n_out samples of the local position n / 2^17 on an axis of `extent` pixels:
+// (j' + 0.5) n_out / extent - 0.5
+__host__ __device__ inline long rot_patch_pos(long n, int extent, int n_out) {
+  return floor_div64((n + ROT_ONE) * n_out - ROT_ONE * extent, 2L * extent);
+}
+// the ramp of one axis on the continuous distance: min(d' + 1, feather + 1) / (feather + 1), d' = min(j', extent - 1 - j')
+// in fixed point (two integers converted to fp32, one division)
+__host__ __device__ inline float rot_ramp(long n, int extent, int feather) {
+  const long fx = n >> 1;  // floor, ROT_FRAC_BITS fractional bits
+  const long other = (extent - 1) * ROT_ONE - fx;
+  const long d = fx < other ? fx : other;
+  const long full = (feather + 1) * ROT_ONE;
+  return (float)(d + ROT_ONE < full ? d + ROT_ONE : full) / (float)full;
+}
+// the frame pixels [bx0, bx1] x [by0, by1] that hold the rotated rectangle (a pixel more on every side: c16, s16 are a
+// rotation to 2^-15 only), clipped to the frame; the box's centre lies inside the frame, so none is empty
+__host__ __device__ inline void rot_bbox(const RotBox& r, int src_h, int src_w, int& bx0, int& bx1, int& by0, int& by1) {
+  const long ac = r.c16 < 0 ? -(long)r.c16 : r.c16, as = r.s16 < 0 ? -(long)r.s16 : r.s16;
+  const long ax = (2L * r.x1 + r.cw - 1) * ROT_ONE, ay = (2L * r.y1 + r.ch - 1) * ROT_ONE;
+  const long hx = ac * r.cw + as * r.ch, hy = as * r.cw + ac * r.ch;  // over 2^17, as ax and ay
+  bx0 = (int)clampl(((ax - hx) >> 17) - 1, 0, src_w - 1);
+  bx1 = (int)clampl(((ax + hx) >> 17) + 2, 0, src_w - 1);
+  by0 = (int)clampl(((ay - hy) >> 17) - 1, 0, src_h - 1);
+  by1 = (int)clampl(((ay + hy) >> 17) + 2, 0, src_h - 1);
+}
+
+__device__ __forceinline__ RotBox rot_box(const FrameRBoxes& t, int b) {
+  const FrameBox bx = t.box[b];
+  const FrameRot r = t.rot[b];
+  return RotBox{bx.x1, bx.y1, bx.cw, bx.ch, r.c16, r.s16};
+}
+
+// stages the bounding box of the positions pos(x, y) of x in [x_f, x_l], y in [y_f, y_l] with their taps, clipped to the
+// image -- and to the launch's LDS (rows_max rows of g.pitch bytes: the host's bound holds it; the clip keeps a wrong bound
+// from writing past the allocation)
+template <class Pos>
+__device__ __forceinline__ ResizeTile rot_stage(uint8_t* patch, const ResizeSrc& g, int rows_max, Pos pos, int x_f, int x_l,
+                                                int y_f, int y_l, const uint8_t* lo, const uint8_t* hi, int tid) {
+  long lox, hix, loy, hiy;
+  pos(x_f, y_f, lox, loy);
+  hix = lox;
+  hiy = loy;
+  for (int k = 1; k < 4; ++k) {
+    long px, py;
+    pos(k & 1 ? x_l : x_f, k & 2 ? y_l : y_f, px, py);
+    lox = px < lox ? px : lox;
+    hix = px > hix ? px : hix;
+    loy = py < loy ? py : loy;
+    hiy = py > hiy ? py : hiy;
+  }
+  const int cx0 = (int)clampl((lox >> ROT_FRAC_BITS) - 1, 0, g.n_w - 1), ry0 = (int)clampl((loy >> ROT_FRAC_BITS) - 1, 0, g.n_h - 1);
+  int cx1 = (int)clampl((hix >> ROT_FRAC_BITS) + 2, 0, g.n_w - 1), ry1 = (int)clampl((hiy >> ROT_FRAC_BITS) + 2, 0, g.n_h - 1);
+  cx1 = min(cx1, cx0 + (g.pitch - 3) / 3 - 1);
+  ry1 = min(ry1, ry0 + rows_max - 1);
+  return resize_stage_rect(patch, g, cx0, cx1, ry0, ry1, lo, hi, tid);
+}
+
+// the value at a fixed-point position of the image
+template <bool STAGED>
+__device__ __forceinline__ void rot_value(const uint8_t* patch, const ResizeSrc& g, const ResizeTile& t, long px, long py,
+                                          float v[3]) {
+  float wx[4], wy[4];
+  keys_weights((float)(int)(px & (ROT_ONE - 1)) / (float)ROT_ONE, wx);
+  keys_weights((float)(int)(py & (ROT_ONE - 1)) / (float)ROT_ONE, wy);
+  resize_sum<STAGED>(patch, g, t, (int)(px >> ROT_FRAC_BITS), (int)(py >> ROT_FRAC_BITS), wx, wy, v);
+}
+
+struct RotCropGeom {
+  int src_h, src_w, H, W;
+  long dst_row_stride;
+  int pitch, rows_max;  // the launch's staged rows: their pitch in bytes and their count
+};
+struct RotCropArgs {
+  RotCropGeom g;
+  FrameRBoxes t;
+};
+
+template <typename T, bool ACT, bool STAGED>
+__global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void crop_resize_cubic_rot_kernel(
+    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, T* __restrict__ act, RotCropArgs a, int Cpad, float m0,
+    float m1, float m2, float s0, float s1, float s2) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t patch[];
+  const int tid = threadIdx.x;
+  const int ox0 = blockIdx.x * RESIZE_TW, oy0 = blockIdx.y * RESIZE_TH, b = blockIdx.z;
+  const RotCropGeom& g = a.g;
+  const RotBox r = rot_box(a.t, b);
+  const long frame_bytes = (long)g.src_h * g.src_w * 3;
+  // the image is the whole frame: a tap index clamps to the frame
+  const ResizeSrc rs = {src + b * frame_bytes, (long)g.src_w * 3, g.src_h, g.src_w, g.H, g.W, g.pitch};
+  auto pos = [&](int ox, int oy, long& px, long& py) { rot_crop_pos(r, g.H, g.W, ox, oy, px, py); };
+  ResizeTile t;
+  if (STAGED) {
+    t = rot_stage(patch, rs, g.rows_max, pos, ox0, min(ox0 + RESIZE_TW, g.W) - 1, oy0, min(oy0 + RESIZE_TH, g.H) - 1, src,
+                  src + (long)gridDim.z * frame_bytes, tid);
+    __syncthreads();
+  }
+  const int ox = ox0 + (tid % RESIZE_TW), oy = oy0 + (tid / RESIZE_TW);
+  if (ox >= g.W || oy >= g.H) return;
+  long px, py;
+  pos(ox, oy, px, py);
+  float v[3];
+  rot_value<STAGED>(patch, rs, t, px, py, v);
+  resize_store<T, ACT>(v, dst + ((long)b * g.H + oy) * g.dst_row_stride + (long)ox * 3,
+                       ACT ? act + (((long)b * g.H + oy) * g.W + ox) * Cpad : nullptr, Cpad, m0, m1, m2, s0, s1, s2);
+}
+
+// what a tile may stage of an n_h x n_w image when its footprint spans xext x yext samples (floors): floor(a + e) - floor(a)
+// <= floor(e) + 1 steps, the three taps around them and one sample for the count; the pitch as resize_patch_extent's
+static PatchExtent rot_patch_extent(long xext, long yext, int n_h, int n_w) {
+  long cols = xext + 5, rows = yext + 5;
+  cols = cols < n_w ? cols : n_w;
+  rows = rows < n_h ? rows : n_h;
+  return PatchExtent{rows, (cols * 3 + 3 + 3) / 4 * 4};
+}
+static long labs64(long v) { return v < 0 ? -v : v; }
+
+static void fill_frame_rboxes(FrameRBoxes& t, const int32_t* boxes, const int32_t* rot, int b0, int n) {
+  t = FrameRBoxes{};
+  for (int i = 0; i < n; ++i) {
+    const int32_t* bx = boxes + 4L * (b0 + i);
+    t.box[i] = FrameBox{bx[0], bx[1], bx[2], bx[3]};
+    t.rot[i] = FrameRot{rot[2L * (b0 + i)], rot[2L * (b0 + i) + 1]};
+  }
+}
+
+// frames b0 .. b0 + B - 1 of the call's tables: one launch of at most FRAME_BOXES_MAX frames
+template <typename T, bool ACT>
+static int rot_crop_launch_one(const uint8_t* src, uint8_t* dst, T* act, RotCropArgs& a, const int32_t* boxes,
+                               const int32_t* rot, int b0, int B, int Cpad, const float mean255[3], const float std255[3],
+                               hipStream_t stream) {
+  RotCropGeom& g = a.g;
+  fill_frame_rboxes(a.t, boxes, rot, b0, B);
+  PatchExtent e;
+  for (int i = 0; i < B; ++i) {
+    // a tile's footprint: (RESIZE_TW - 1) cw / W along the crop's columns and (RESIZE_TH - 1) ch / H along its rows, turned
+    const long ac = labs64(a.t.rot[i].c16), as = labs64(a.t.rot[i].s16);
+    const long du = (long)(RESIZE_TW - 1) * a.t.box[i].cw * g.H, dv = (long)(RESIZE_TH - 1) * a.t.box[i].ch * g.W;
+    const long den = ROT_ONE * g.W * g.H;
+    e.cover(rot_patch_extent((ac * du + as * dv) / den, (as * du + ac * dv) / den, g.src_h, g.src_w));
+  }
+  const long lds = e.lds_bytes(&g.pitch);
+  g.rows_max = (int)e.rows;
+  const dim3 grid((g.W + RESIZE_TW - 1) / RESIZE_TW, (g.H + RESIZE_TH - 1) / RESIZE_TH, B), block(RESIZE_TW * RESIZE_TH);
+  const float z[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
+  const float* m = mean255 ? mean255 : z;
+  const float* s = std255 ? std255 : one;
+  if (lds > 0)
+    hipLaunchKernelGGL((crop_resize_cubic_rot_kernel<T, ACT, true>), grid, block, (size_t)lds, stream, src, dst, act, a, Cpad,
+                       m[0], m[1], m[2], s[0], s[1], s[2]);
+  else
+    hipLaunchKernelGGL((crop_resize_cubic_rot_kernel<T, ACT, false>), grid, block, 0, stream, src, dst, act, a, Cpad, m[0],
+                       m[1], m[2], s[0], s[1], s[2]);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+template <typename T, bool ACT>
+static int rot_crop_launch(const uint8_t* src, uint8_t* dst, T* act, const ResizeGeom& g, const int32_t* boxes,
+                           const int32_t* rot, int B, int Cpad, const float mean255[3], const float std255[3],
+                           hipStream_t stream) {
+  RotCropArgs a;
+  a.g = RotCropGeom{g.src_h, g.src_w, g.H, g.W, g.dst_row_stride, 0, 0};
+  const long frame_bytes = (long)g.src_h * g.src_w * 3, out_bytes = (long)g.H * g.dst_row_stride;
+  for (int b0 = 0; b0 < B; b0 += FRAME_BOXES_MAX) {
+    const int n = B - b0 < FRAME_BOXES_MAX ? B - b0 : FRAME_BOXES_MAX;
+    if (int rc = rot_crop_launch_one<T, ACT>(src + b0 * frame_bytes, dst + b0 * out_bytes,
+                                             ACT ? act + (long)b0 * g.H * g.W * Cpad : nullptr, a, boxes, rot, b0, n, Cpad,
+                                             mean255, std255, stream))
+      return rc;
+  }
+  return 0;
+}
+
+// every frame's rotation: null, or no rotation (a table that would scale)
+static int frame_rot_check(const char* op, const int32_t* rot, int B) {
+  D3F_CHECK(rot != nullptr, "%s: null rot (host memory [B][2]: c16, s16 per frame)", op);
+  for (int b = 0; b < B; ++b) {
+    const long c = rot[2L * b], s = rot[2L * b + 1];
+    const bool small = labs64(c) <= 2 * ROT_ONE && labs64(s) <= 2 * ROT_ONE;
+    D3F_CHECK(small && labs64(c * c + s * s - (1L << 32)) <= (1L << 17),
+              "%s: frame %d: rot (c16 %ld, s16 %ld) is no rotation: c16^2 + s16^2 lies further than 2^17 from 2^32 (such a "
+              "table would scale)", op, b, c, s);
+  }
+  return 0;
+}
+
+static int rot_crop_geometry(ResizeGeom& g, int B, int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int H, int W,
+                             long dst_row_stride) {
+  if (int rc = resize_geometry(g, B, src_h, src_w, 0, 0, 1, 1, H, W, dst_row_stride)) return rc;
+  if (int rc = frame_boxes_check("crop_resize_cubic_rboxes", boxes, B, src_h, src_w)) return rc;
+  return frame_rot_check("crop_resize_cubic_rboxes", rot, B);
+}
+
+int crop_resize_cubic_rboxes_check(int B, int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int H, int W,
+                                   long dst_row_stride) {
+  ResizeGeom g;
+  return rot_crop_geometry(g, B, src_h, src_w, boxes, rot, H, W, dst_row_stride);
+}
+
+int crop_resize_cubic_rboxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
+                                       const int32_t* rot, uint8_t* dst, int H, int W, long dst_row_stride,
+                                       hipStream_t stream) {
+  ResizeGeom g;
+  if (int rc = rot_crop_geometry(g, B, src_h, src_w, boxes, rot, H, W, dst_row_stride)) return rc;
+  return rot_crop_launch<float, false>(src, dst, nullptr, g, boxes, rot, B, 0, nullptr, nullptr, stream);
+}
+
+int crop_resize_cubic_rboxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
+                                            const int32_t* rot, uint8_t* dst, int H, int W, long dst_row_stride, void* act,
+                                            int Cpad, const float mean255[3], const float std255[3], hipStream_t stream) {
+  ResizeGeom g;
+  if (int rc = rot_crop_geometry(g, B, src_h, src_w, boxes, rot, H, W, dst_row_stride)) return rc;
+  D3F_CHECK(Cpad >= 3, "crop_resize_cubic_rboxes: activation of %d channels", Cpad);
+  if (dtype == D3F_F32)
+    return rot_crop_launch<float, true>(src, dst, (float*)act, g, boxes, rot, B, Cpad, mean255, std255, stream);
+  return rot_crop_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, boxes, rot, B, Cpad, mean255, std255, stream);
+}
+
+// the paste of a rotated box: tiles on the FRAME's 32 x 8 grid, as the plain form's.  A tile that misses the rectangle's
+// bounding box is a copy (out == frame: not launched); inside it a pixel belongs to the box when its centre lies in the
+// rotated rectangle, and every other pixel is the frame's
+struct RotPasteGeom {
+  int H, W;
+  long patch_row_stride;
+  int src_h, src_w, feather;
+  int pitch, rows_max;
+};
+template <bool COLOR>
+struct RotPasteArgs {
+  RotPasteGeom g;
+  FrameRBoxes t;
+};
+template <>
+struct RotPasteArgs<true> {
+  RotPasteGeom g;
+  FrameRBoxes t;
+  const float* coef;
+};
+
+template <bool STAGED, bool COLOR>
+__global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void paste_resize_cubic_rot_kernel(const uint8_t* __restrict__ patch,
+                                                                                      const uint8_t* frame, uint8_t* out,
+                                                                                      RotPasteArgs<COLOR> args) {
+  const int b = blockIdx.z;
+  const RotPasteGeom& g = args.g;
+  const RotBox r = rot_box(args.t, b);
+  const bool in_place = frame == out;
+  int bx0, bx1, by0, by1;
+  rot_bbox(r, g.src_h, g.src_w, bx0, bx1, by0, by1);
+  int tx0 = 0, ty0 = 0;
+  if (in_place) {  // (workgroup-uniform) the launch's grid is the most tiles any frame's bounding box meets
+    tx0 = bx0 / RESIZE_TW;
+    ty0 = by0 / RESIZE_TH;
+    if ((int)blockIdx.x > bx1 / RESIZE_TW - tx0 || (int)blockIdx.y > by1 / RESIZE_TH - ty0) return;
+  }
+  extern __shared__ __attribute__((aligned(16))) uint8_t staged[];
+  const int tid = threadIdx.x;
+  const int ox0 = ((int)blockIdx.x + tx0) * RESIZE_TW, oy0 = ((int)blockIdx.y + ty0) * RESIZE_TH;
+  const long frame_bytes = (long)g.src_h * g.src_w * 3, row_bytes = (long)g.src_w * 3;
+  const uint8_t* f = frame + b * frame_bytes;
+  uint8_t* o = out + b * frame_bytes;
+  const int tile_w = min(RESIZE_TW, g.src_w - ox0), tile_h = min(RESIZE_TH, g.src_h - oy0);
+  const int lx = tid % RESIZE_TW, ly = tid / RESIZE_TW;
+  if (ox0 > bx1 || ox0 + tile_w - 1 < bx0 || oy0 > by1 || oy0 + tile_h - 1 < by0) {  // (workgroup-uniform) a copy
+    if (in_place || ly >= tile_h) return;
+    const long at = (long)(oy0 + ly) * row_bytes + (long)ox0 * 3;
+    frame_tile_row_copy(f + at, o + at, tile_w, lx);
+    return;
+  }
+  const uint8_t* img = patch + (long)b * g.H * g.patch_row_stride;
+  const ResizeSrc rs = {img, g.patch_row_stride, g.H, g.W, r.ch, r.cw, g.pitch};
+  // the patch position of frame pixel (x, y): taps clamp inside the patch
+  auto pos = [&](int x, int y, long& px, long& py) {
+    long nj, ni;
+    rot_local(r, x, y, nj, ni);
+    px = rot_patch_pos(nj, r.cw, g.W);
+    py = rot_patch_pos(ni, r.ch, g.H);
+  };
+  ResizeTile t;
+  if (STAGED) {
+    const uint8_t* hi = patch + ((long)gridDim.z * g.H - 1) * g.patch_row_stride + (long)g.W * 3;
+    t = rot_stage(staged, rs, g.rows_max, pos, ox0, ox0 + tile_w - 1, oy0, oy0 + tile_h - 1, patch, hi, tid);
+    __syncthreads();
+  }
+  if (lx >= tile_w || ly >= tile_h) return;
+  const long at = (long)(oy0 + ly) * row_bytes + (long)(ox0 + lx) * 3;
+  long nj, ni;
+  rot_local(r, ox0 + lx, oy0 + ly, nj, ni);
+  if (!rot_inside(nj, r.cw) || !rot_inside(ni, r.ch)) {  // a pixel of the tile outside the rectangle
+    if (!in_place) {
+      const uint8_t q0 = f[at], q1 = f[at + 1], q2 = f[at + 2];
+      o[at] = q0;
+      o[at + 1] = q1;
+      o[at + 2] = q2;
+    }
+    return;
+  }
+  float v[3];
+  rot_value<STAGED>(staged, rs, t, rot_patch_pos(nj, r.cw, g.W), rot_patch_pos(ni, r.ch, g.H), v);
+  const float ay = rot_ramp(ni, r.ch, g.feather), ax = rot_ramp(nj, r.cw, g.feather);
+  paste_blend<COLOR>(v, ay * ax, f + at, o + at, args, b);
+}
+
+template <bool COLOR>
+static int rot_paste_launch_one(const uint8_t* patch, int B, const uint8_t* frame, RotPasteArgs<COLOR>& args,
+                                const int32_t* boxes, const int32_t* rot, int b0, uint8_t* out, hipStream_t stream) {
+  RotPasteGeom& g = args.g;
+  fill_frame_rboxes(args.t, boxes, rot, b0, B);
+  dim3 grid((g.src_w + RESIZE_TW - 1) / RESIZE_TW, (g.src_h + RESIZE_TH - 1) / RESIZE_TH, B);
+  PatchExtent e;
+  unsigned tiles_x = 1, tiles_y = 1;  // in place: the most tiles any frame's bounding box meets
+  for (int i = 0; i < B; ++i) {
+    const FrameBox& bx = args.t.box[i];
+    // a tile's footprint in the box: 31 and 7 frame pixels, turned; in the patch: times W / cw and H / ch
+    const long ac = labs64(args.t.rot[i].c16), as = labs64(args.t.rot[i].s16);
+    const long xext = (ac * (RESIZE_TW - 1) + as * (RESIZE_TH - 1)) * g.W / (ROT_ONE * bx.cw);
+    const long yext = (as * (RESIZE_TW - 1) + ac * (RESIZE_TH - 1)) * g.H / (ROT_ONE * bx.ch);
+    e.cover(rot_patch_extent(xext, yext, g.H, g.W));
+    int bx0, bx1, by0, by1;
+    rot_bbox(RotBox{bx.x1, bx.y1, bx.cw, bx.ch, args.t.rot[i].c16, args.t.rot[i].s16}, g.src_h, g.src_w, bx0, bx1, by0, by1);
+    const unsigned nx = bx1 / RESIZE_TW - bx0 / RESIZE_TW + 1, ny = by1 / RESIZE_TH - by0 / RESIZE_TH + 1;
+    tiles_x = tiles_x > nx ? tiles_x : nx;
+    tiles_y = tiles_y > ny ? tiles_y : ny;
+  }
+  const long lds = e.lds_bytes(&g.pitch);
+  g.rows_max = (int)e.rows;
+  if (frame == out) {  // (the kernel derives each frame's first tile)
+    grid.x = tiles_x;
+    grid.y = tiles_y;
+  }
+  const dim3 block(RESIZE_TW * RESIZE_TH);
+  if (lds > 0)
+    hipLaunchKernelGGL((paste_resize_cubic_rot_kernel<true, COLOR>), grid, block, (size_t)lds, stream, patch, frame, out, args);
+  else
+    hipLaunchKernelGGL((paste_resize_cubic_rot_kernel<false, COLOR>), grid, block, 0, stream, patch, frame, out, args);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+template <bool COLOR>
+static int rot_paste_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
+                            int src_w, const int32_t* boxes, const int32_t* rot, int feather, const float* coef, uint8_t* out,
+                            hipStream_t stream) {
+  RotPasteArgs<COLOR> args;
+  args.g = RotPasteGeom{H, W, patch_row_stride, src_h, src_w, feather, 0, 0};
+  const long frame_bytes = (long)src_h * src_w * 3, patch_bytes = (long)H * patch_row_stride;
+  for (int b0 = 0; b0 < B; b0 += FRAME_BOXES_MAX) {
+    const int n = B - b0 < FRAME_BOXES_MAX ? B - b0 : FRAME_BOXES_MAX;
+    if constexpr (COLOR) args.coef = coef + 6L * b0;
+    if (int rc = rot_paste_launch_one<COLOR>(patch + b0 * patch_bytes, n, frame + b0 * frame_bytes, args, boxes, rot, b0,
+                                             out + b0 * frame_bytes, stream))
+      return rc;
+  }
+  return 0;
+}
+
+int paste_resize_cubic_rboxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef,
+                                    bool color, int B, int H, int W, long patch_row_stride, int src_h, int src_w,
+                                    const int32_t* boxes, const int32_t* rot, int feather) {
+  const char* op = color ? "paste_resize_cubic_color_rboxes" : "paste_resize_cubic_rboxes";
+  if (int rc = color ? paste_resize_cubic_color_check(patch, frame, out, coef, B, H, W, patch_row_stride, src_h, src_w, 0, 0, 1,
+                                                      1, feather)
+                     : paste_resize_cubic_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, 0, 0, 1, 1, feather))
+    return rc;
+  if (int rc = frame_boxes_check(op, boxes, B, src_h, src_w)) return rc;
+  return frame_rot_check(op, rot, B);
+}
+
+int paste_resize_cubic_rboxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
+                                        int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int feather,
+                                        const float* coef, bool color, uint8_t* out, hipStream_t stream) {
+  if (int rc = paste_resize_cubic_rboxes_check(patch, frame, out, coef, color, B, H, W, patch_row_stride, src_h, src_w, boxes,
+                                               rot, feather))
+    return rc;
+  if (color) return rot_paste_launch<true>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, boxes, rot, feather, coef, out, stream);
+  return rot_paste_launch<false>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, boxes, rot, feather, nullptr, out, stream);
 }
 
 }  // namespace d3f

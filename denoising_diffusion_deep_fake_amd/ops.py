@@ -6,6 +6,7 @@ parity tests and for callers that want one kernel at a time; the training path g
 `Unet` (one C call per forward / backward).  No fallbacks: every function launches a HIP kernel.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -753,6 +754,91 @@ def smooth_box_track(faces, n):
     return out
 
 
+def angle_hundredths(angle_degrees):
+    """an angle in degrees -> integer hundredths of a degree, wrapped to (-18000, 18000]"""
+    a = float(angle_degrees)
+    if not math.isfinite(a):
+        raise ValueError(f"angle {angle_degrees!r} is not a finite number of degrees")
+    h = int(round(a * 100.0)) % 36000
+    return h - 36000 if h > 18000 else h
+
+
+def box_rotation(angle_degrees):
+    """(c16, s16) = (round(cos a * 65536), round(sin a * 65536)) of an angle in degrees, first rounded to hundredths of a degree
+    and wrapped to (-180, 180]: the rotation of a box as the _rboxes_ operators take it (include/d3f_hip.h; the device does
+    no trigonometry).  x right, y down: a positive angle turns the box clockwise on the screen about its centre."""
+    a = math.radians(angle_hundredths(angle_degrees) / 100.0)
+    return int(round(math.cos(a) * 65536.0)), int(round(math.sin(a) * 65536.0))
+
+
+def read_rbox_track(path):
+    """`read_box_track` for a track with head roll -> a list of (fx, fy, fw, fh, a), entry k for frame k.  A line is
+    `x y w h` or `x y w h a` with a the box's angle in decimal degrees (`box_rotation`'s convention; a missing a is 0; it is
+    rounded to hundredths and wrapped to (-180, 180]); comments, blank lines, `-` and gaps as in `read_box_track`, which
+    itself keeps refusing a fifth field."""
+    faces = []
+    with open(path) as f:
+        for number, line in enumerate(f, 1):
+            fields = line.split("#", 1)[0].replace(",", " ").split()
+            if not fields:
+                continue
+            if fields == ["-"]:
+                faces.append(None)
+                continue
+            try:
+                if len(fields) not in (4, 5):
+                    raise ValueError
+                angle = angle_hundredths(fields[4]) / 100.0 if len(fields) == 5 else 0.0
+                faces.append(tuple(int(v) for v in fields[:4]) + (angle,))
+            except ValueError:
+                raise ValueError(f"{path}, line {number}: expected `x y w h` (integers), `x y w h a` (a in degrees) or `-`, "
+                                 f"got {line.strip()!r}") from None
+    first = next((face for face in faces if face is not None), None)
+    if first is None:
+        raise ValueError(f"{path}: no detection in the track")
+    last = first
+    for k, face in enumerate(faces):
+        if face is None:
+            faces[k] = last
+        else:
+            last = face
+    return faces
+
+
+def smooth_rbox_track(faces, n):
+    """`smooth_box_track` of a track with angles: the box of (fx, fy, fw, fh, a) is smoothed as there, the angle is the mean
+    of the window's angles in integer hundredths of a degree with floor division (no wrap-around handling: a head does not
+    roll past 180 degrees).  n = 0 returns its input."""
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"smooth_rbox_track: n = {n} is negative")
+    if n == 0:
+        return list(faces)
+    boxes = smooth_box_track([face[:4] for face in faces], n)
+    hundredths = [angle_hundredths(face[4]) for face in faces]
+    out = []
+    for k, box in enumerate(boxes):
+        window = hundredths[max(k - n, 0):k + n + 1]
+        out.append(tuple(box) + ((sum(window) // len(window)) / 100.0,))
+    return out
+
+
+def _rot_arg(angles, B, who):
+    """angles = B numbers of degrees -> (a ctypes int32 array [B * 2] in host memory holding `box_rotation` of each, or None
+    when every angle is zero after rounding to hundredths: the caller then takes the axis-aligned entries)"""
+    if isinstance(angles, torch.Tensor):
+        angles = angles.tolist()
+    try:
+        hundredths = [angle_hundredths(a) for a in angles]
+    except TypeError:
+        raise ValueError(f"{who}: angles must be {B} numbers of degrees, one per frame") from None
+    if len(hundredths) != B:
+        raise ValueError(f"{who}: angles must be {B} numbers of degrees, one per frame")
+    if not any(hundredths):
+        return None
+    return (C.c_int32 * (2 * B))(*[v for h in hundredths for v in box_rotation(h / 100.0)])
+
+
 def box_of_frame(track, k):
     """entry k of a track; frames past its last line keep the last box"""
     return track[min(int(k), len(track) - 1)]
@@ -762,6 +848,13 @@ def track_crop_boxes(track, first, count, h, w, width, height, margin=TRACK_MARG
     """`track_crop_box` of frames first .. first + count - 1 of a track (what `read_box_track` returns) in h x w frames: the
     [count][4] boxes of one batch of a frame loop"""
     return [track_crop_box(h, w, width, height, box_of_frame(track, first + i), margin) for i in range(count)]
+
+
+def track_crop_rboxes(track, first, count, h, w, width, height, margin=TRACK_MARGIN):
+    """`track_crop_boxes` of a track with angles (what `read_rbox_track` returns) -> (the [count][4] boxes, the count angles
+    in degrees): the box is `track_crop_box` of the entry's (fx, fy, fw, fh), the angle the entry's own"""
+    entries = [box_of_frame(track, first + i) for i in range(count)]
+    return ([track_crop_box(h, w, width, height, e[:4], margin) for e in entries], [float(e[4]) for e in entries])
 
 
 def _boxes_arg(boxes, B, who):
@@ -778,7 +871,7 @@ def _boxes_arg(boxes, B, who):
     return flat, rows
 
 
-def crop_resize_cubic_u8(frames, size, box=None, out=None, antialias=False, boxes=None):
+def crop_resize_cubic_u8(frames, size, box=None, out=None, antialias=False, boxes=None, angles=None):
     """uint8 frames [h, w, 3] or [B, h, w, 3] on the HIP device -> the crop box (x1, y1, cw, ch) resized to size = (H, W)
     as cv2.resize(..., INTER_CUBIC) defines it in float arithmetic (include/d3f_hip.h: d3f_crop_resize_cubic_u8).
     box=None: the reference's centre crop to the target aspect.  out: a uint8 tensor [B, H, W, 3] whose pixels are packed
@@ -788,11 +881,20 @@ def crop_resize_cubic_u8(frames, size, box=None, out=None, antialias=False, boxe
     times the size of the output, where four taps per axis skip most of the source pixels.
     boxes: [B][4] integers in host memory, a box per frame, instead of box= (one of the two at most): frame b is byte for
     byte the single-box call on frame b with boxes[b], still one device call (d3f_crop_resize_cubic_boxes_u8 and its _aa
-    form; one launch per 64 frames)."""
+    form; one launch per 64 frames).
+    angles: B angles in degrees next to boxes=, a rotation of each box about its centre (`box_rotation`): the crop's columns
+    run along (cos a, sin a) of the frame, and taps clamp to the frame (d3f_crop_resize_cubic_rboxes_u8).  None, or all zero
+    after rounding to hundredths, is the boxes= call, byte for byte and launch for launch.  Not with antialias=True."""
     if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or frames.dim() not in (3, 4):
         raise ValueError("crop_resize_cubic_u8 expects uint8 frames [h, w, 3] or [B, h, w, 3]")
     if box is not None and boxes is not None:
         raise ValueError("crop_resize_cubic_u8: box= and boxes= exclude each other")
+    if angles is not None and boxes is None:
+        raise ValueError("crop_resize_cubic_u8: angles= needs boxes=")
+    rot = None if angles is None else _rot_arg(angles, 1 if frames.dim() == 3 else int(frames.shape[0]), "crop_resize_cubic_u8")
+    if rot is not None and antialias:
+        raise ValueError("crop_resize_cubic_u8: antialias=True with non-zero angles: the antialiased crop of a rotated box "
+                         "is out of scope")
     dev = _dev(frames)
     single = frames.dim() == 3
     x = (frames.unsqueeze(0) if single else frames).contiguous()
@@ -809,6 +911,9 @@ def crop_resize_cubic_u8(frames, size, box=None, out=None, antialias=False, boxe
         raise ValueError(f"out must be a uint8 tensor of shape {(B, H, W, 3)} on the input's device with packed pixels "
                          f"and frames H rows apart")
     L = _lib.lib()
+    if rot is not None:
+        check(L.d3f_crop_resize_cubic_rboxes_u8(ptr(x), B, h, w, table, rot, ptr(out), H, W, out.stride(1), stream_ptr()))
+        return out[0] if single else out
     if boxes is not None:
         resize = L.d3f_crop_resize_cubic_aa_boxes_u8 if antialias else L.d3f_crop_resize_cubic_boxes_u8
         check(resize(ptr(x), B, h, w, table, ptr(out), H, W, out.stride(1), stream_ptr()))
@@ -1185,7 +1290,7 @@ def _paste_args(who, patch, frames, box, out, color, boxes):
     return p, f, o, geo, coef, single, rows
 
 
-def paste_resize_cubic_u8(patch, frames, box=None, feather=0, out=None, color=None, boxes=None):
+def paste_resize_cubic_u8(patch, frames, box=None, feather=0, out=None, color=None, boxes=None, angles=None):
     """The inverse of `crop_resize_cubic_u8` with a blend: uint8 `patch` [H, W, 3] / [B, H, W, 3] on the HIP device is resized
     to the box (x1, y1, cw, ch) of uint8 `frames` [h, w, 3] / [B, h, w, 3] with the same arithmetic and blended in over a
     ramp of `feather` pixels; outside the box the result is the frame (include/d3f_hip.h: d3f_paste_resize_cubic_u8).
@@ -1196,11 +1301,25 @@ def paste_resize_cubic_u8(patch, frames, box=None, feather=0, out=None, color=No
     the blend (d3f_paste_resize_cubic_color_u8).  None: the plain call.
     boxes: [B][4] integers in host memory, a box per frame, instead of box= (exactly one of the two); one `feather` for the
     call.  Frame b is byte for byte the single-box call on frame b with boxes[b] (d3f_paste_resize_cubic_boxes_u8 and its
-    _color form; one launch per 64 frames)."""
+    _color form; one launch per 64 frames).
+    angles: B angles in degrees next to boxes=, as `crop_resize_cubic_u8` takes them: the patch goes back into the rotated
+    rectangle -- a frame pixel belongs to the box when its centre lies in it, the ramp runs on the distance to the
+    rectangle's sides (d3f_paste_resize_cubic_rboxes_u8 and its _color form).  None or all zero: the boxes= call."""
+    if angles is not None and boxes is None:
+        raise ValueError("paste_resize_cubic_u8: angles= needs boxes=")
+    rot = None if angles is None else _rot_arg(angles, 1 if frames.dim() == 3 else int(frames.shape[0]), "paste_resize_cubic_u8")
     p, f, o, geo, coef, single, _ = _paste_args("paste_resize_cubic_u8", patch, frames, box, out, color, boxes)
     B, h, w, _ = f.shape
     H, W = int(p.shape[1]), int(p.shape[2])
     L = _lib.lib()
+    if rot is not None:
+        if coef is None:
+            check(L.d3f_paste_resize_cubic_rboxes_u8(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, geo[0], rot, int(feather),
+                                                     ptr(o), stream_ptr()))
+        else:
+            check(L.d3f_paste_resize_cubic_color_rboxes_u8(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, geo[0], rot,
+                                                           int(feather), ptr(coef), ptr(o), stream_ptr()))
+        return o[0] if single else o
     if coef is None:
         paste = L.d3f_paste_resize_cubic_u8 if boxes is None else L.d3f_paste_resize_cubic_boxes_u8
         check(paste(ptr(p), B, H, W, p.stride(1), ptr(f), h, w, *geo, int(feather), ptr(o), stream_ptr()))

@@ -16,7 +16,8 @@ from .. import ops
 from .._lib import MULTIBAND_MAX_LEVELS, TEMPORAL_STRENGTH, TEMPORAL_THRESHOLD, temporal_setting
 from ..train_deep_fake.lit_module import LitModule
 from .video_writer_context_manager import (VideoWriter, add_track_arguments, batches, check_track_arguments, import_cv2,
-                                           load_track, open_video_as_generator, track_setting, video_fps)
+                                           load_rtrack, load_track, open_video_as_generator, track_rotate_setting,
+                                           track_setting, video_fps)
 
 
 def main():
@@ -41,6 +42,7 @@ def main():
         track=args.track,
         track_margin=args.track_margin,
         track_smooth=args.track_smooth,
+        track_rotate=args.track_rotate,
         )
 
 
@@ -128,12 +130,16 @@ class RenderFakeVideo():
     output="full" pasted, at `ops.track_crop_box` of the track's entry k instead of the centre box; the frame counter runs
     across batches, and the padding frames of a short last batch repeat the last real frame's box.  output="full" without
     feather= takes `ops.default_feather` of the smallest box of the whole track once, so the ramp does not change from
-    batch to batch.  A tracked call runs eager (`Unet.predict_frames_u8`, boxes=)."""
+    batch to batch.  A tracked call runs eager (`Unet.predict_frames_u8`, boxes=).
+    track_rotate=True: the track's entries carry an angle in degrees (`ops.read_rbox_track`; a list's entries may be
+    (x, y, w, h, a)) and every box is turned by it about its centre, in the crop and in the paste
+    (`Unet.predict_frames_u8`, angles=); the padding frames repeat the last real frame's angle too.  Not with antialias=True or
+    blend="multiband"."""
 
     def __init__(self, video_path, checkpoint_path, model_a_or_b, image_width, image_height, batch_frames=1,
                  frames=None, sink=None, model=None, output="pair", feather=None, antialias=False, color_match=None,
                  temporal=None, temporal_threshold=None, track=None, track_margin=None, track_smooth=None, blend=None,
-                 blend_levels=None):
+                 blend_levels=None, track_rotate=False):
 
         self.video_path = Path(video_path)
         self.checkpoint_path = Path(checkpoint_path) if checkpoint_path is not None else None
@@ -169,7 +175,11 @@ class RenderFakeVideo():
         self.blend = blend
         self.blend_levels = blend_levels
         self.track_margin, track_smooth = track_setting(track, track_margin, track_smooth)
-        self.track = None if track is None else load_track(track, self.track_margin, track_smooth)
+        self.track_rotate = track_rotate_setting(track, track_rotate, self.antialias, blend)
+        if self.track_rotate:
+            self.track = load_rtrack(track, track_smooth)
+        else:
+            self.track = None if track is None else load_track(track, self.track_margin, track_smooth)
         self.frame_index = 0  # of the next batch's first frame: the track is followed across batches
         self.frames = frames
         self.sink = sink
@@ -194,27 +204,35 @@ class RenderFakeVideo():
         return model
 
     def batch_boxes(self, batch, real_frames):
-        """the boxes [B][4] of a batch of frames, or None without a track; the padding frames repeat the last real frame's"""
+        """(the boxes [B][4] of a batch of frames, or None without a track; their B angles, or None without track_rotate); the
+        padding frames repeat the last real frame's"""
         if self.track is None:
-            return None
+            return None, None
         h, w = batch.shape[1:3]
-        boxes = ops.track_crop_boxes(self.track, self.frame_index, real_frames, h, w, self.image_width, self.image_height,
-                                     self.track_margin)
+        geometry = (self.track, self.frame_index, real_frames, h, w, self.image_width, self.image_height, self.track_margin)
+        pad = len(batch) - real_frames
         self.frame_index += real_frames
-        return boxes + [boxes[-1]] * (len(batch) - real_frames)
+        if self.track_rotate:
+            boxes, angles = ops.track_crop_rboxes(*geometry)
+            return boxes + [boxes[-1]] * pad, angles + [angles[-1]] * pad
+        boxes = ops.track_crop_boxes(*geometry)
+        return boxes + [boxes[-1]] * pad, None
+
+    def whole_track_boxes(self, h, w):
+        """the crop box of every entry of the track"""
+        faces = [face[:4] for face in self.track]
+        return ops.track_crop_boxes(faces, 0, len(faces), h, w, self.image_width, self.image_height, self.track_margin)
 
     def track_feather(self, h, w):
         """output="full" with a track and no feather=: `ops.default_feather` of the smallest box of the whole track"""
-        boxes = ops.track_crop_boxes(self.track, 0, len(self.track), h, w, self.image_width, self.image_height,
-                                     self.track_margin)
+        boxes = self.whole_track_boxes(h, w)
         return ops.default_feather(min(b[2] for b in boxes), min(b[3] for b in boxes))
 
     def track_blend_levels(self, h, w, feather):
         """blend="multiband" with a track: the levels (blend_levels=, else `ops.multiband_levels` of the call's feather),
         after every box of the whole track has been checked against 2 ** levels"""
         levels = self.blend_levels if self.blend_levels is not None else ops.multiband_levels(feather)
-        boxes = ops.track_crop_boxes(self.track, 0, len(self.track), h, w, self.image_width, self.image_height,
-                                     self.track_margin)
+        boxes = self.whole_track_boxes(h, w)
         for k, b in enumerate(boxes):
             if min(b[2], b[3]) < (1 << levels):
                 raise ValueError(f"blend='multiband' with {levels} levels needs boxes of at least {1 << levels} pixels on "
@@ -234,10 +252,10 @@ class RenderFakeVideo():
         with writer as video_writer:
             write = self.sink if self.sink is not None else video_writer.write
             for batch, real_frames in batches(frames, self.batch_frames):
+                boxes, angles = self.batch_boxes(batch, real_frames)
                 real_and_fake = self.model.predict_fake_frames(batch, self.model_a_or_b, self.image_width,
                                                                self.image_height, antialias=self.antialias,
-                                                               temporal=self.temporal,
-                                                               boxes=self.batch_boxes(batch, real_frames))
+                                                               temporal=self.temporal, boxes=boxes, angles=angles)
                 for frame in real_and_fake[:real_frames]:  # the padding of a short last batch is dropped
                     write(frame)
 
@@ -259,11 +277,11 @@ class RenderFakeVideo():
                     h, w = batch.shape[1:3]
                     write = stack.enter_context(VideoWriter(str(self.get_output_video_path("_full")), w, h,
                                                             self.get_input_video_properties())).write
+                boxes, angles = self.batch_boxes(batch, real_frames)
                 full = self.model.predict_fake_frames_full(batch, self.model_a_or_b, self.image_width,
                                                            self.image_height, feather=feather,
                                                            antialias=self.antialias, color_match=self.color_match,
-                                                           temporal=self.temporal,
-                                                           boxes=self.batch_boxes(batch, real_frames),
+                                                           temporal=self.temporal, boxes=boxes, angles=angles,
                                                            blend=self.blend, blend_levels=blend_levels)
                 for frame in full[:real_frames]:  # the padding of a short last batch is dropped
                     write(frame)

@@ -6,9 +6,10 @@ every frame, then the smallest sum of absolute differences in a search window). 
 box follows a face that walks towards the camera or away from it (ops.track_template_scale_u8).  What remains: the
 template's longer side stays within 4..64 samples at the key's stride (a third over the default side of 48), and there
 is no rotation search.  Where the face outgrows that, turns, where the tracker drifts and behind a cut, mark another key
-frame -- the tracker is seeded anew at every key.
+frame -- the tracker is seeded anew at every key.  Head roll is marked by hand as well: --key-angle K A (repeatable) writes
+a fifth column, the key angles interpolated linearly, which the two tools read with --track-rotate.
 
-    python -m d3f.script_tools.track_face_box VIDEO --key K X Y W H [--key ...] [-o FILE] [--scale]
+    python -m d3f.script_tools.track_face_box VIDEO --key K X Y W H [--key ...] [-o FILE] [--scale] [--key-angle K A ...]
 """
 import argparse
 from pathlib import Path
@@ -34,6 +35,7 @@ def main():
         template_side=args.template_side,
         scale=args.scale,
         scale_penalty=args.scale_penalty,
+        key_angles=args.key_angle,
         )
     found = sum(box is not None for box in tracker.track)
     print(f"{tracker.output_path}: {len(tracker.track)} frames, the face found in {found}")
@@ -68,8 +70,14 @@ def parse_command_line_arguments(argv=None):
                         help=f"with --scale: what a change of size must win by, in 1/4096 grey levels per sample, "
                              f"0..{_lib.TRACK_MAX_SCALE_PENALTY} (default {ops.TRACK_SCALE_PENALTY})")
 
+    parser.add_argument("--key-angle", nargs=2, action="append", metavar=("K", "A"), default=None,
+                        help="the head's roll at frame K, A in decimal degrees (positive: clockwise on the screen); repeat "
+                             "it.  The file gains a fifth column, the linear interpolation of the key angles (constant "
+                             "before the first and after the last), for --track-rotate; the tracker does not search rotation")
+
     args = parser.parse_args(argv)
     try:
+        sorted_key_angles(args.key_angle)
         check_settings(sorted_keys(args.key), args.batch_frames, args.search, args.adapt, args.lost, args.template_side,
                        args.scale, args.scale_penalty)
     except ValueError as e:
@@ -95,6 +103,43 @@ def sorted_keys(keys):
     return out
 
 
+def sorted_key_angles(pairs):
+    """pairs: (k, a) each, a in degrees -> {k: a in integer hundredths of a degree, wrapped to (-18000, 18000]} in the order
+    of k, or None for no pair; a ValueError for a negative or a repeated frame index and an angle that is no finite number"""
+    if not pairs:
+        return None
+    out = {}
+    try:
+        rows = sorted((int(k), ops.angle_hundredths(a)) for k, a in pairs)
+    except (TypeError, ValueError):
+        raise ValueError("--key-angle: `K A`, a frame index and an angle in decimal degrees") from None
+    for k, a in rows:
+        if k < 0:
+            raise ValueError(f"--key-angle: frame index {k} is negative")
+        if k in out:
+            raise ValueError(f"--key-angle: frame {k} has two angles")
+        out[k] = a
+    return out
+
+
+def interpolate_key_angles(key_angles, frames):
+    """{k: hundredths} -> the angle of frames 0 .. frames - 1 in integer hundredths: linear between two keys (floor division),
+    constant before the first key and after the last"""
+    ks = list(key_angles)
+    out = []
+    for k in range(frames):
+        if k <= ks[0]:
+            out.append(key_angles[ks[0]])
+        elif k >= ks[-1]:
+            out.append(key_angles[ks[-1]])
+        else:
+            k1 = next(q for q in ks if q >= k)
+            k0 = ks[ks.index(k1) - 1]
+            a0, a1 = key_angles[k0], key_angles[k1]
+            out.append(a0 + (a1 - a0) * (k - k0) // (k1 - k0))
+    return out
+
+
 def check_settings(keys, batch_frames, search, adapt, lost, template_side, scale=False,
                    scale_penalty=ops.TRACK_SCALE_PENALTY):
     if int(batch_frames) < 1:
@@ -110,14 +155,20 @@ def check_settings(keys, batch_frames, search, adapt, lost, template_side, scale
     return keys
 
 
-def write_track(path, track, header=()):
+def write_track(path, track, header=(), angles=None):
     """line k for frame k: `x y w h`, or `-` where track[k] is None, behind `# ` comment lines -- what ops.read_box_track
-    parses"""
+    parses.  angles (integer hundredths of a degree, one per frame): a fifth column in decimal degrees -- what
+    ops.read_rbox_track parses"""
     with open(path, "w") as f:
         for line in header:
             f.write(f"# {line}\n")
-        for box in track:
-            f.write("-\n" if box is None else "{} {} {} {}\n".format(*box))
+        for k, box in enumerate(track):
+            if box is None:
+                f.write("-\n")
+            elif angles is None:
+                f.write("{} {} {} {}\n".format(*box))
+            else:
+                f.write("{} {} {} {} {:.2f}\n".format(*box, angles[k] / 100.0))
 
 
 class TrackFaceBox():
@@ -127,11 +178,14 @@ class TrackFaceBox():
     the face was not found, the key's own box (clipped to the frame) at a key frame.  A batch is one upload, one device call
     (one more, and a seed, per key frame inside it) and one small copy back; the result does not depend on batch_frames.
     scale=True: the size of the box is searched too (ops.track_template_scale_u8), scale_penalty what a change of size must
-    win by; every key sets the size anew."""
+    win by; every key sets the size anew.
+    key_angles: (k, a) each, the head's roll in degrees at frame k: the file gains a fifth column, .angles holds it in integer
+    hundredths of a degree (`interpolate_key_angles`); None: the file is the four-column one.  The tracker itself does not
+    search rotation."""
 
     def __init__(self, video_path, keys, output_path=None, batch_frames=8, frames=None, sink=None, device="cuda",
                  search=ops.TRACK_SEARCH, adapt=ops.TRACK_ADAPT, lost=ops.TRACK_LOST,
-                 template_side=ops.TRACK_TEMPLATE_SIDE, scale=False, scale_penalty=ops.TRACK_SCALE_PENALTY):
+                 template_side=ops.TRACK_TEMPLATE_SIDE, scale=False, scale_penalty=ops.TRACK_SCALE_PENALTY, key_angles=None):
 
         self.video_path = Path(video_path)
         self.keys = check_settings(sorted_keys(keys), batch_frames, search, adapt, lost, template_side, scale, scale_penalty)
@@ -141,6 +195,8 @@ class TrackFaceBox():
         self.device = device
         self.search, self.adapt, self.lost, self.template_side = search, adapt, lost, template_side
         self.scale, self.scale_penalty = scale, scale_penalty
+        self.key_angles = sorted_key_angles(key_angles)
+        self.angles = None
         if output_path is not None:
             self.output_path = Path(output_path)
         elif sink is None:
@@ -154,8 +210,10 @@ class TrackFaceBox():
 
         self.track_video()
 
+        if self.key_angles is not None:
+            self.angles = interpolate_key_angles(self.key_angles, len(self.track))
         if self.output_path is not None:
-            write_track(self.output_path, self.track, self.header())
+            write_track(self.output_path, self.track, self.header(), self.angles)
         late = [k for k in self.keys if k >= len(self.track)]
         if late:
             raise ValueError(f"--key: frame {late[0]} is past the video's last frame, {len(self.track) - 1}")
@@ -167,6 +225,9 @@ class TrackFaceBox():
                  f"search {self.search}, adapt {self.adapt}, lost {self.lost}, template side {self.template_side}")
         if self.scale:
             lines += (f"scale search: one level a frame, penalty {self.scale_penalty}",)
+        if self.key_angles is not None:
+            angles = ", ".join(f"{k} {a / 100.0:.2f}" for k, a in self.key_angles.items())
+            lines += (f"fifth column: the box's angle in degrees, interpolated between the key angles (frame angle): {angles}",)
         return lines
 
     def track_video(self):

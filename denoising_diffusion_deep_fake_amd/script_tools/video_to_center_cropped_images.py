@@ -9,8 +9,8 @@ from pathlib import Path
 import torch
 
 from .. import ops
-from .video_writer_context_manager import (add_track_arguments, batches, check_track_arguments, import_cv2, load_track,
-                                           open_video_as_generator, track_setting)
+from .video_writer_context_manager import (add_track_arguments, batches, check_track_arguments, import_cv2, load_rtrack,
+                                           load_track, open_video_as_generator, track_rotate_setting, track_setting)
 
 
 def main():
@@ -26,6 +26,7 @@ def main():
         track=args.track,
         track_margin=args.track_margin,
         track_smooth=args.track_smooth,
+        track_rotate=args.track_rotate,
         )
 
 
@@ -51,10 +52,14 @@ class VideoToImages():
     """frames=: an iterable of decoded BGR frames instead of the video file (cv2 is not needed then); the output folder
     is still named after video_path.  antialias=True: ops.crop_resize_cubic_u8(..., antialias=True).
     track=FILE (or a list of (x, y, w, h) boxes; track_margin=M, track_smooth=N with it): frame k is cut at
-    `ops.track_crop_box` of the track's entry k, the frame counter running across batches, as RenderFakeVideo(track=) does"""
+    `ops.track_crop_box` of the track's entry k, the frame counter running across batches, as RenderFakeVideo(track=) does.
+    track_rotate=True: the track's entries carry an angle (`ops.read_rbox_track`) and every box is turned by it about its
+    centre (`ops.crop_resize_cubic_u8`, angles=); not with antialias=True"""
+
+    track_rotate = False  # the track's entries are (x, y, w, h, a)
 
     def __init__(self, video_path, image_width, image_height, batch_frames=16, frames=None, device="cuda",
-                 antialias=False, track=None, track_margin=None, track_smooth=None):
+                 antialias=False, track=None, track_margin=None, track_smooth=None, track_rotate=False):
 
         self.video_path = Path(video_path)
         self.image_width = int(image_width)
@@ -66,7 +71,11 @@ class VideoToImages():
         self.device = device
         self.antialias = bool(antialias)
         self.track_margin, track_smooth = track_setting(track, track_margin, track_smooth)
-        self.track = None if track is None else load_track(track, self.track_margin, track_smooth)
+        self.track_rotate = track_rotate_setting(track, track_rotate, self.antialias)
+        if self.track_rotate:
+            self.track = load_rtrack(track, track_smooth)
+        else:
+            self.track = None if track is None else load_track(track, self.track_margin, track_smooth)
         self.frame_index = 0  # of the next batch's first frame: the track is followed across batches
 
         if frames is None:
@@ -98,16 +107,20 @@ class VideoToImages():
         """[n, h, w, 3] host BGR frames -> [n, height, width, 3] host BGR frames, cropped at the centre -- with a track, each
         at its own box (the first real_frames of the batch are frames of the video, the rest padding) -- and resized"""
         dev = torch.from_numpy(batch).to(self.device)
-        boxes = None
+        boxes = angles = None
         if self.track is not None:
             real = len(batch) if real_frames is None else real_frames
             h, w = batch.shape[1:3]
-            boxes = ops.track_crop_boxes(self.track, self.frame_index, real, h, w, self.image_width, self.image_height,
-                                         self.track_margin)
+            geometry = (self.track, self.frame_index, real, h, w, self.image_width, self.image_height, self.track_margin)
+            if self.track_rotate:
+                boxes, angles = ops.track_crop_rboxes(*geometry)
+                angles += [angles[-1]] * (len(batch) - real)
+            else:
+                boxes = ops.track_crop_boxes(*geometry)
             self.frame_index += real
             boxes += [boxes[-1]] * (len(batch) - real)
         return ops.crop_resize_cubic_u8(dev, (self.image_height, self.image_width), antialias=self.antialias,
-                                        boxes=boxes).cpu().numpy()
+                                        boxes=boxes, angles=angles).cpu().numpy()
 
     def save_frame_to_disk(self, frame, frame_index):
         from PIL import Image

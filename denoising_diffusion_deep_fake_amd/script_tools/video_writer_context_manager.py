@@ -85,13 +85,31 @@ def add_track_arguments(parser):
                         help=f"--track: the crop is M times the face box (default {ops.TRACK_MARGIN})")
     parser.add_argument("--track-smooth", type=int, default=None, metavar="N",
                         help="--track: average the track over 2 N + 1 frames against detector jitter (default 0: off)")
+    parser.add_argument("--track-rotate", action="store_true",
+                        help="--track: a line may carry a fifth field, the box's angle in decimal degrees (positive turns "
+                             "the box clockwise on the screen; missing: 0), and every crop box is turned by it about its "
+                             "centre; not with --antialias or --blend multiband")
 
 
 def check_track_arguments(parser, args):
     try:
         track_setting(args.track, args.track_margin, args.track_smooth)
+        track_rotate_setting(args.track, args.track_rotate, args.antialias, getattr(args, "blend", None))
     except ValueError as e:
         parser.error(str(e))
+
+
+def track_rotate_setting(track, rotate, antialias, blend=None):
+    """track_rotate= / --track-rotate, checked against what a rotated box does not have -> bool"""
+    if not rotate:
+        return False
+    if track is None:
+        raise ValueError("--track-rotate needs --track")
+    if antialias:
+        raise ValueError("--track-rotate with --antialias: the antialiased crop of a rotated box is out of scope")
+    if blend == "multiband":
+        raise ValueError("--track-rotate with --blend multiband: the multiband pyramid of a rotated box is out of scope")
+    return True
 
 
 def track_setting(track, margin, smooth):
@@ -108,6 +126,18 @@ def track_setting(track, margin, smooth):
     if smooth < 0:
         raise ValueError(f"--track-smooth {smooth} is negative")
     return margin, smooth
+
+
+def load_rtrack(track, smooth):
+    """track: a track file's path with an optional fifth field, or the entries themselves (a list of (x, y, w, h) or
+    (x, y, w, h, a), a in degrees) -> the smoothed track of (x, y, w, h, a)"""
+    if isinstance(track, (str, Path)):
+        faces = ops.read_rbox_track(track)
+    else:
+        faces = [tuple(int(v) for v in f[:4]) + (ops.angle_hundredths(f[4]) / 100.0 if len(f) > 4 else 0.0,) for f in track]
+    if not faces:
+        raise ValueError("track: no detection in the track")
+    return ops.smooth_rbox_track(faces, smooth)
 
 
 def load_track(track, margin, smooth):

@@ -449,7 +449,8 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
 
     # ---- raw frames to real|fake frames (script_tools/put_video_through_fake_model.py:111-119, 68) ----
     @torch.no_grad()
-    def predict_fake_frames(self, raw_bgr_batch, model_a_or_b, width, height, antialias=False, temporal=None, boxes=None):
+    def predict_fake_frames(self, raw_bgr_batch, model_a_or_b, width, height, antialias=False, temporal=None, boxes=None,
+                            angles=None):
         """host frames [B, h, w, 3] (uint8 BGR, any size) -> host real|fake frames [B, height, 2 * width, 3]: centre crop,
         bicubic resize, `predict_fake` and the side-by-side concatenate of the reference's frame loop in one device call
         (`Unet.predict_frames_u8`).  Mean / std as in `predict_fake`: a model is fed the other domain's statistics.
@@ -457,7 +458,8 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         antialias=True: the antialiased bicubic resize (`ops.crop_resize_cubic_u8(..., antialias=True)`) -- prepare the
         training images the same way.  temporal: None, a strength or (strength, threshold), as `Unet.predict_frames_u8`: the
         fake half filtered against flicker; successive calls are then consecutive in time (`reset_frame_temporal` starts a
-        new sequence).  boxes: None (the centre crop), one box or a box per frame [B][4], as `Unet.predict_frames_u8`."""
+        new sequence).  boxes: None (the centre crop), one box or a box per frame [B][4], as `Unet.predict_frames_u8`.
+        angles: None, or B angles in degrees next to a box per frame: the boxes turned about their centres."""
         model, mean, std, raw = self._frame_path_inputs(raw_bgr_batch, model_a_or_b, "predict_fake_frames")
         width, height = int(width), int(height)
         key = (raw.shape, id(model), width, height)
@@ -475,7 +477,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         host_in.copy_(torch.from_numpy(raw))
         dev_in.copy_(host_in, non_blocking=True)
         model.predict_frames_u8(dev_in, (height, width), mean, std, graph=bool(self.hparams.get("inference_graph", False)),
-                                out=dev_out, antialias=antialias, temporal=temporal, boxes=boxes)
+                                out=dev_out, antialias=antialias, temporal=temporal, boxes=boxes, angles=angles)
         host_out.copy_(dev_out, non_blocking=True)
         torch.cuda.current_stream().synchronize()
         return host_out.numpy().copy()
@@ -515,7 +517,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
     @torch.no_grad()
     def predict_fake_frames_full(self, raw_bgr_batch, model_a_or_b, width, height, feather=None, with_pair=False,
                                  antialias=False, color_match=None, temporal=None, boxes=None, blend=None,
-                                 blend_levels=None):
+                                 blend_levels=None, angles=None):
         """host frames [B, h, w, 3] (uint8 BGR, any size) -> host frames of the same shape with the centre-crop box replaced
         by the fake, resized back to the box and blended in over `feather` source pixels (None: `ops.default_feather`):
         the swapped video at the source's size, in one device call (`Unet.predict_frames_full_u8`).  with_pair: returns
@@ -525,7 +527,8 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         colour statistics matched to the crop it replaces before the paste; the pair is the same either way.  temporal: as
         `predict_fake_frames`; the pair then holds the filtered fake, and with color_match the coefficients are smoothed.
         boxes: as `predict_fake_frames`; every frame's fake goes back into its own box (`Unet.predict_frames_full_u8`).
-        blend, blend_levels: as `Unet.predict_frames_full_u8` -- "multiband" fades each frequency band over its own ramp."""
+        blend, blend_levels: as `Unet.predict_frames_full_u8` -- "multiband" fades each frequency band over its own ramp.
+        angles: as `predict_fake_frames`; every frame's fake goes back into its own rotated rectangle."""
         model, mean, std, raw = self._frame_path_inputs(raw_bgr_batch, model_a_or_b, "predict_fake_frames_full")
         width, height = int(width), int(height)
         if not hasattr(self, "_frames_full_buffers"):
@@ -539,7 +542,7 @@ class LitModule(ValidationMixin, ImageLoggingMixin, LightningModule):
         model.predict_frames_full_u8(dev_in, (height, width), mean, std, feather=feather,
                                      graph=bool(self.hparams.get("inference_graph", False)), out=dev_full,
                                      pair_out=dev_pair, antialias=antialias, color_match=color_match,
-                                     temporal=temporal, boxes=boxes, blend=blend, blend_levels=blend_levels)
+                                     temporal=temporal, boxes=boxes, blend=blend, blend_levels=blend_levels, angles=angles)
         host_full.copy_(dev_full, non_blocking=True)
         if with_pair:
             host_pair.copy_(dev_pair, non_blocking=True)

@@ -871,6 +871,26 @@ class Unet(nn.Module, _NetsRuntime):
         return x, single, geo, eng, pair, rows
 
     @staticmethod
+    def _frame_rot(who, angles, boxes, raw_bgr, antialias, multiband=False):
+        """angles= of the two raw-frame entries -> the host int32 table [B][2] the rboxes entries take, or None for the
+        axis-aligned call (angles None, or all zero after rounding to hundredths).  Checked before anything touches the
+        device"""
+        from . import ops
+        if angles is None:
+            return None
+        rows = boxes.tolist() if isinstance(boxes, torch.Tensor) else (None if boxes is None else list(boxes))
+        if rows is None or (len(rows) == 4 and not any(hasattr(v, "__len__") for v in rows)):
+            raise ValueError(f"{who}: angles= needs boxes= with a box per frame")
+        rot = ops._rot_arg(angles, 1 if raw_bgr.dim() == 3 else int(raw_bgr.shape[0]), who)
+        if rot is not None and antialias:
+            raise ValueError(f"{who}: antialias=True with non-zero angles: the antialiased crop of a rotated box is out of "
+                             f"scope")
+        if rot is not None and multiband:
+            raise ValueError(f"{who}: blend='multiband' with non-zero angles: the multiband pyramid of a rotated box is out "
+                             f"of scope")
+        return rot
+
+    @staticmethod
     def _apply_frame_settings(eng, antialias, color, temporal, blend=None):
         """the frame entries' settings on the plan's handle, in front of every call (the handle returns early on a value it
         already has, and keeps its captured graphs and the filter's state then).  color: a D3F_COLOR_* code, or None: left
@@ -895,7 +915,7 @@ class Unet(nn.Module, _NetsRuntime):
 
     @torch.no_grad()
     def predict_frames_u8(self, raw_bgr, size, mean, std, graph=True, out=None, antialias=False, temporal=None,
-                          boxes=None):
+                          boxes=None, angles=None):
         """The frame path of d3f/script_tools/put_video_through_fake_model.py:111-119, 68 on decoded frames of any
         size: uint8 BGR frames [h,w,3] or [B,h,w,3] on the HIP device -> centre crop to the aspect of size = (H, W)
         (`ops.center_crop_box`) -> bicubic resize (`ops.crop_resize_cubic_u8`) -> `predict_u8` -> the real|fake frames
@@ -913,14 +933,20 @@ class Unet(nn.Module, _NetsRuntime):
         face that moves (`ops.track_crop_box`) -- through d3f_unet_predict_frames_boxes_u8: still one C call, the left half
         byte for byte `ops.crop_resize_cubic_u8(..., boxes=)`, and it runs EAGER whatever `graph=` says: a captured launch
         bakes the boxes in, so a moving box would re-capture on every call.  The temporal filter reads the resized crop: a
-        box that moves is motion to it."""
+        box that moves is motion to it.
+        angles: B angles in degrees next to a box per frame -- a head that rolls (`ops.box_rotation`) -- through
+        d3f_unet_predict_frames_rboxes_u8: the left half is byte for byte `ops.crop_resize_cubic_u8(..., boxes=, angles=)`.
+        None, or all zero after rounding to hundredths, is the boxes= call.  Not with antialias=True."""
         temporal = _lib.temporal_setting(temporal)
+        rot = self._frame_rot("predict_frames_u8", angles, boxes, raw_bgr, antialias)
         x, single, geo, eng, out, _ = self._frame_inputs("predict_frames_u8", raw_bgr, size, out, "out", boxes=boxes)
         rt = self._rt
         self._apply_frame_settings(eng, antialias, None, temporal)
         L = _lib.lib()
         per_frame = len(geo) == 3
         entry = L.d3f_unet_predict_frames_boxes_u8 if per_frame else L.d3f_unet_predict_frames_u8
+        if rot is not None:
+            entry, geo = L.d3f_unet_predict_frames_rboxes_u8, geo + (rot,)
         check(entry(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), *geo, ptr(out), _float3(mean), _float3(std),
                     ptr(eng.workspace), 1 if graph and not per_frame else 0, stream_ptr()))
         eng.keep = (x, out)  # the captured graph bakes these pointers in: keep them alive with the engine
@@ -929,7 +955,7 @@ class Unet(nn.Module, _NetsRuntime):
     @torch.no_grad()
     def predict_frames_full_u8(self, raw_bgr, size, mean, std, feather=None, graph=True, out=None, pair_out=None,
                                antialias=False, color_match=None, temporal=None, boxes=None, blend=None,
-                               blend_levels=None):
+                               blend_levels=None, angles=None):
         """`predict_frames_u8`, then the fake pasted back into the source frames: uint8 BGR frames [h,w,3] or [B,h,w,3] on
         the HIP device -> the frames at their own size with the centre-crop box replaced by the fake, resized back
         (`ops.paste_resize_cubic_u8`) and blended in over `feather` source pixels (None: `ops.default_feather` of the
@@ -950,7 +976,10 @@ class Unet(nn.Module, _NetsRuntime):
         of the pair instead (with color_match its colour form, with boxes its boxes form), still in the one C call (the
         handle's D3F_BLEND_MULTIBAND mode; its pyramid workspace belongs to the plan and grows with the box): low frequencies
         fade over `feather` pixels, fine detail over a fraction of it.  blend_levels: the pyramid's levels, 1..6, with
-        "multiband" only; None: `ops.multiband_levels(feather)`.  A change of either re-captures the graph."""
+        "multiband" only; None: `ops.multiband_levels(feather)`.  A change of either re-captures the graph.
+        angles: as `predict_frames_u8` (d3f_unet_predict_frames_full_rboxes_u8): every frame's fake is pasted into its own
+        rotated rectangle (`ops.paste_resize_cubic_u8(..., boxes=, angles=)`).  Not with antialias=True or
+        blend="multiband"."""
         from . import ops
         blend_code = _lib.blend_mode(blend)
         if blend_levels is not None and blend_code != _lib.BLEND_MULTIBAND:
@@ -960,6 +989,7 @@ class Unet(nn.Module, _NetsRuntime):
         color_code = _lib.color_match_mode(color_match)
         temporal = _lib.temporal_setting(temporal)
         in_place = out is raw_bgr
+        rot = self._frame_rot("predict_frames_full_u8", angles, boxes, raw_bgr, antialias, blend_code == _lib.BLEND_MULTIBAND)
         x, single, geo, eng, pair_out, rows = self._frame_inputs("predict_frames_full_u8", raw_bgr, size, pair_out,
                                                                  "pair_out", in_place, boxes=boxes)
         if feather is None:
@@ -981,6 +1011,8 @@ class Unet(nn.Module, _NetsRuntime):
         L = _lib.lib()
         per_frame = len(geo) == 3
         entry = L.d3f_unet_predict_frames_full_boxes_u8 if per_frame else L.d3f_unet_predict_frames_full_u8
+        if rot is not None:
+            entry, geo = L.d3f_unet_predict_frames_full_rboxes_u8, geo + (rot,)
         check(entry(eng.h, ptr(rt["flat"]), ptr(rt["flat_bn"]), ptr(x), *geo, feather, ptr(pair_out), ptr(full),
                     _float3(mean), _float3(std), ptr(eng.workspace), 1 if graph and not per_frame else 0, stream_ptr()))
         eng.keep_full = (x, pair_out, full)  # the captured graph bakes these pointers in: keep them alive with the engine

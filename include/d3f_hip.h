@@ -216,6 +216,21 @@ int d3f_unet_predict_frames_full_boxes_u8(d3f_unet_t h, const float* params, flo
                                           int src_h, int src_w, const int32_t* boxes, int feather, uint8_t* pair_out,
                                           uint8_t* full_out, const float mean[3], const float std[3], void* workspace,
                                           int use_graph, void* stream);
+/* The two boxes entries with a rotation per frame (a head that rolls): rot is HOST memory, [B][2] int32 as c16, s16 of frame
+ * b (the _rboxes_ operators below define them), read before the call returns.  The same launch sequence with the crop and the
+ * paste in their rotated forms (d3f_crop_resize_cubic_rboxes_u8_nhwc, d3f_paste_resize_cubic_rboxes_u8 / _color_rboxes_u8):
+ * pair_out and full_out are byte for byte the composition of those operators; colour sums, coefficients, their smoothing and
+ * the temporal filter work on pair_out and do not change.  Refused before any device call: what the boxes entries refuse
+ * (use_graph != 0 among it, for their reason), a null rot, a rot that is no rotation (the frame is named), and
+ * D3F_RESAMPLE_CUBIC_AA or D3F_BLEND_MULTIBAND on the handle -- the antialiased crop and the multiband pyramid of a rotated
+ * box are out of scope. */
+int d3f_unet_predict_frames_rboxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
+                                      int src_w, const int32_t* boxes, const int32_t* rot, uint8_t* pair_out,
+                                      const float mean[3], const float std[3], void* workspace, int use_graph, void* stream);
+int d3f_unet_predict_frames_full_rboxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in,
+                                           int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int feather,
+                                           uint8_t* pair_out, uint8_t* full_out, const float mean[3], const float std[3],
+                                           void* workspace, int use_graph, void* stream);
 /* How d3f_unet_predict_frames_u8 and d3f_unet_predict_frames_full_u8 resize the crop box to the handle's H x W:
  *   D3F_RESAMPLE_CUBIC     d3f_crop_resize_cubic_u8 (cv2.INTER_CUBIC: four taps per axis whatever the scale).  The default
  *                          after d3f_unet_create; its launches are exactly those of a handle that never heard of the setting.
@@ -660,6 +675,52 @@ int d3f_paste_resize_cubic_boxes_u8(const uint8_t* patch, int B, int H, int W, i
 int d3f_paste_resize_cubic_color_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
                                           const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
                                           const float* coef, uint8_t* out, void* stream);
+
+/* Rotated boxes: a face whose head rolls.  Each operator below is its _boxes_ operator with one more table, rot: HOST memory,
+ * [B][2] int32 as c16 = round(cos a * 65536), s16 = round(sin a * 65536) of frame b's angle a, read before the call returns.
+ * Coordinates are x right, y down; a positive angle turns the box clockwise on the screen about its centre: in frame
+ * coordinates the crop's column direction is (cos a, sin a), its row direction (-sin a, cos a).  No trigonometry on the
+ * device: the two integers are the rotation (ops.box_rotation computes them from an angle in degrees).  Definition (the
+ * acceptance contract; tests/rotation_restatement.py restates it), with c = c16 / 65536, s = s16 / 65536 and the box's centre
+ * (X, Y) = (x1 + (cw - 1) / 2, y1 + (ch - 1) / 2) in tap-index units:
+ *   crop: output pixel (ox, oy) of the H x W crop reads the FRAME at (X + c u - s v, Y + s u + c v) with
+ *     u = cw (2 ox + 1 - W) / (2 W), v = ch (2 oy + 1 - H) / (2 H).  Each coordinate is formed exactly in 64-bit integers over
+ *     the denominator 2^17 W H and reduced once, by a floor, to a fixed-point position with 16 fractional bits: its integer
+ *     part is s, its fraction t = frac / 65536 exact in fp32.  Taps s - 1 .. s + 2 per axis, Keys weights (A = -0.75) of t as
+ *     in d3f_crop_resize_cubic_u8, horizontal then vertical pass in fp32 without contraction, rintf, clamp.  Tap indices are
+ *     clamped to the FRAME (replicate), not to the box: a rotated box's corners may leave the frame, and no read ever does.
+ *     This is a stated difference from the plain form, and angle 0 is therefore (and for the 16-bit fraction) not promised
+ *     byte-equal to d3f_crop_resize_cubic_boxes_u8: it differs by at most one level away from the box's border ring.
+ *   paste: for frame pixel p = (x, y), dx2 = 2 x - 2 x1 - cw + 1, dy2 = 2 y - 2 y1 - ch + 1, the box-local position is
+ *     j' = n_j / 2^17, i' = n_i / 2^17 with n_j = (cw - 1) 2^16 + c16 dx2 + s16 dy2, n_i = (ch - 1) 2^16 - s16 dx2 + c16 dy2
+ *     (exact integers).  The pixel belongs to the box when -0.5 <= j' < cw - 0.5 and -0.5 <= i' < ch - 0.5 (tested on n_j,
+ *     n_i); every other byte of out is the frame's.  The patch is sampled at (j' + 0.5) W / cw - 0.5 -- exactly
+ *     ((n_j + 2^16) W - 2^16 cw) / (2^17 cw), reduced by a floor to 16 fractional bits -- and likewise for i'; taps clamped
+ *     inside the patch; value, clamp, colour form and blend exactly as d3f_paste_resize_cubic_u8 / _color_u8.  The ramp of an
+ *     axis: f = floor(n_j / 2), d = min(f, (cw - 1) 2^16 - f), a_x = (float)min(d + 2^16, (feather + 1) 2^16) /
+ *     (float)((feather + 1) 2^16) (two integers converted to fp32, one division), a = a_y * a_x.  At angle 0 it is the plain
+ *     form's ramp.
+ * The tables travel by value (box and rotation: 1.5 KB per launch of at most D3F_FRAME_BOXES_MAX frames; a longer call is
+ * several launches, in order).  A tile stages the axis-aligned bounding box of its footprint, clipped to the image; a launch
+ * whose largest footprint passes 32 KB reads its taps from global memory with the same arithmetic, and both routes give the
+ * same bytes.  The in-place paste launches only the tiles that meet the rotated rectangle's bounding box.
+ * Refused before any device call: whatever the _boxes_ operator refuses (the box itself lies inside the frame), a null rot,
+ * and for any frame a rot with |c16^2 + s16^2 - 2^32| > 2^17 -- such a table would scale, not rotate -- with the frame's index
+ * in the message.  Extents up to 16384 as ever: no intermediate passes 2^60. */
+int d3f_crop_resize_cubic_rboxes_u8(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, const int32_t* rot,
+                                    uint8_t* dst, int H, int W, int64_t dst_row_stride_bytes, void* stream);
+/* the fused form the frame entries launch: dst as above and, from the same rounded bytes, the normalised activation
+ * act [B][H][W][Cpad] (dtype D3F_F32 or D3F_BF16, device memory, Cpad >= 3) in RGB order: ((float)byte - mean[c] * 255.f) /
+ * (std[c] * 255.f) in fp32, channels from 3 on zero; mean, std: 3 host floats (RGB order) */
+int d3f_crop_resize_cubic_rboxes_u8_nhwc(int dtype, const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
+                                         const int32_t* rot, uint8_t* dst, int H, int W, int64_t dst_row_stride_bytes,
+                                         void* act, int Cpad, const float mean[3], const float std[3], void* stream);
+int d3f_paste_resize_cubic_rboxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                     const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, const int32_t* rot,
+                                     int feather, uint8_t* out, void* stream);
+int d3f_paste_resize_cubic_color_rboxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
+                                           const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, const int32_t* rot,
+                                           int feather, const float* coef, uint8_t* out, void* stream);
 
 /* Multiband paste (Burt & Adelson): d3f_paste_resize_cubic_u8 with the single ramp replaced by a ramp per spatial frequency
  * band -- low frequencies fade over about `feather` pixels, every finer band over half the band above.  Inputs: those of

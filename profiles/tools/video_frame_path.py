@@ -49,10 +49,16 @@
                  last, every int16 plane g_l written once and read twice (REDUCE, and the collapse of its level; g_N once),
                  every int32 plane R_l (l = 1 .. N - 1) written once and read once
 
+  --rotate     : instead of the above, the rotated crop and paste: the _rboxes_ forms at 0.01 and at 20 degrees next to the
+                 _boxes_ forms on the same boxes (every box the centre box) in the same run -- the crop alone (out=) and the paste
+                 alone (out of place, default feather): 1080x1920 -> 448x448 and 256x256, B = 1 and B = 8; with the LDS bytes a
+                 workgroup's tile may stage in each form (the launch's bound: rows times pitch), which is what the rotated
+                 forms pay for first.  With --off-only only the _boxes_ forms run
+
 Back-to-back enqueues on one stream, ITERS iterations after WARMUP, the forms alternating in ROUNDS rounds; the figure is
 the median round's time per call (and per frame).  Host work of the reference's loop (cv2.resize on one CPU thread, the
 concatenate, two PCIe trips) is not part of any figure here.  One JSON line at the end.
-    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N] [--antialias | --color [--off-only] | --temporal [--off-only] | --boxes [--off-only] | --blend]
+    python profiles/tools/video_frame_path.py [--precision f32|bf16] [--iters N] [--antialias | --color [--off-only] | --temporal [--off-only] | --boxes [--off-only] | --blend | --rotate [--off-only]]
 """
 import argparse
 import json
@@ -341,6 +347,65 @@ def blend_section(args, g):
     print(json.dumps(result))
 
 
+def staged_bytes(n_h, n_w, out_h, out_w, angle=None, clip=None):
+    """the LDS bytes a tile of a resize n_h x n_w -> out_h x out_w may stage (csrc/resize.hip: resize_patch_extent; with an
+    angle rot_patch_extent on the turned footprint, clipped to the image clip = (h, w)), 0 past 32 KB (taps from global memory)"""
+    du, dv = 31 * n_w * out_h, 7 * n_h * out_w
+    if angle is None:
+        cols, rows = 31 * n_w // out_w + 5, 7 * n_h // out_h + 5
+    else:
+        c16, s16 = (abs(v) for v in ops.box_rotation(angle))
+        den = 65536 * out_w * out_h
+        cols, rows = min((c16 * du + s16 * dv) // den + 5, clip[1]), min((s16 * du + c16 * dv) // den + 5, clip[0])
+    total = rows * ((cols * 3 + 6) // 4 * 4)
+    return total if total <= 32 * 1024 else 0
+
+
+def rotate_section(args, g):
+    """the rotated crop and paste against the boxes forms on the same boxes, per frame; one JSON line"""
+    has_rot = hasattr(_lib.lib(), "d3f_crop_resize_cubic_rboxes_u8") and not args.off_only
+    result = {"precision": args.precision, "digest": _lib.built_digest(), "iters": args.iters, "rounds": args.rounds,
+              "has_rot": has_rot, "rotate_us_per_frame": {}}
+    for side in (448, 256):
+        size = (side, side)
+        box = ops.center_crop_box(RAW[0], RAW[1], side, side)
+        feather = ops.default_feather(box[2], box[3])
+        for B in (1, 8):
+            raw = torch.randint(0, 256, (B,) + RAW + (3,), generator=g, dtype=torch.uint8).cuda()
+            small = ops.crop_resize_cubic_u8(raw, size)
+            resized, full = torch.empty_like(small), torch.empty_like(raw)
+            many = [box] * B
+            forms = {"crop_boxes": lambda: ops.crop_resize_cubic_u8(raw, size, boxes=many, out=resized),
+                     "paste_boxes": lambda: ops.paste_resize_cubic_u8(small, raw, boxes=many, feather=feather, out=full)}
+            if has_rot:
+                for angle in (0.01, 20.0):
+                    turn = [angle] * B
+                    forms[f"crop_rboxes_{angle}"] = lambda turn=turn: ops.crop_resize_cubic_u8(raw, size, boxes=many, angles=turn,
+                                                                                             out=resized)
+                    forms[f"paste_rboxes_{angle}"] = lambda turn=turn: ops.paste_resize_cubic_u8(small, raw, boxes=many, angles=turn,
+                                                                                               feather=feather, out=full)
+            t = compare(forms, args.warmup, args.iters, args.rounds)
+            key = f"{RAW[0]}x{RAW[1]}_to_{side}_B{B}"
+            row = {}
+            for name, (med, lo, hi) in t.items():
+                print(f"{key:24s} {name:20s} {med / B:9.2f} us per frame (min {lo / B:.2f}, max {hi / B:.2f})")
+                row[name] = [round(med / B, 2), round(lo / B, 2), round(hi / B, 2)]
+            row["crop_staged_bytes"] = {"boxes": staged_bytes(box[3], box[2], side, side)}
+            row["paste_staged_bytes"] = {"boxes": staged_bytes(side, side, box[3], box[2])}
+            if has_rot:
+                for angle in (0.01, 20.0):
+                    row["crop_staged_bytes"][str(angle)] = staged_bytes(box[3], box[2], side, side, angle, RAW)
+                    row["paste_staged_bytes"][str(angle)] = staged_bytes(side, side, box[3], box[2], angle, size)
+                    for what in ("crop", "paste"):
+                        row[f"{what}_ratio_{angle}"] = round(t[f"{what}_rboxes_{angle}"][0] / t[f"{what}_boxes"][0], 3)
+                print(f"{key:24s} rotated / boxes: crop {row['crop_ratio_0.01']:.2f} (0.01 deg) {row['crop_ratio_20.0']:.2f} (20 deg), "
+                      f"paste {row['paste_ratio_0.01']:.2f} {row['paste_ratio_20.0']:.2f}; staged bytes per tile: crop "
+                      f"{row['crop_staged_bytes']}, paste {row['paste_staged_bytes']}")
+            result["rotate_us_per_frame"][key] = row
+            del raw, full
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--antialias", action="store_true", help="measure the antialiased resize instead (see above)")
@@ -348,6 +413,7 @@ def main():
     ap.add_argument("--temporal", action="store_true", help="measure the temporal filter of the frame entries instead (see above)")
     ap.add_argument("--boxes", action="store_true", help="measure the per-frame-box forms against the single-box ones instead (see above)")
     ap.add_argument("--blend", action="store_true", help="measure the multiband paste of the full-frame output instead (see above)")
+    ap.add_argument("--rotate", action="store_true", help="measure the rotated crop and paste against the boxes forms instead (see above)")
     ap.add_argument("--off-only", action="store_true",
                     help="--color / --temporal / --boxes: only the forms without the mode, as on a library without its entries -- the same "
                          "sequence of allocations and captures on both sides of an A/B of the unchanged path")
@@ -366,6 +432,8 @@ def main():
         return boxes_section(args, torch.Generator().manual_seed(1))
     if args.blend:
         return blend_section(args, torch.Generator().manual_seed(1))
+    if args.rotate:
+        return rotate_section(args, torch.Generator().manual_seed(1))
     torch.manual_seed(0)
     net = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
     g = torch.Generator().manual_seed(1)
