@@ -293,72 +293,67 @@ int d3f_unet_predict_u8(d3f_unet_t h, const float* params, float* bnstats, const
   return h->e.predict_u8(params, bnstats, bgr_in, bgr_out, mean, std, workspace, use_graph, (hipStream_t)stream);
 }
 
+// the six frame entries: what an entry requires of its arguments, then the engine's one path.  who: the entry's name
+enum { FRAMES_FULL = 1, FRAMES_BOXES = 2, FRAMES_ROT = 4 };
+static int predict_frames_entry(const char* who, int needs, d3f_unet_t h, const float* params, float* bnstats,
+                                const UnetEngine::FrameCall& c, const float* mean, const float* std, void* workspace,
+                                int use_graph, void* stream) {
+  D3F_CHECK(h && params && bnstats && c.raw_in && c.pair_out && (c.full_out || !(needs & FRAMES_FULL)) && mean && std && workspace,
+            "%s: null argument", who);
+  D3F_CHECK(c.boxes || !(needs & FRAMES_BOXES), "%s: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)", who);
+  D3F_CHECK(c.rot || !(needs & FRAMES_ROT), "%s: null rot (host memory [B][2]: c16, s16 per frame)", who);
+  if (int rc = single_net(h, who, "has no eval-mode forward (run each network alone)")) return rc;
+  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
+}
+
 int d3f_unet_predict_frames_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
                                int src_w, int x1, int y1, int cw, int ch, uint8_t* pair_out, const float mean[3],
                                const float std[3], void* workspace, int use_graph, void* stream) {
-  D3F_CHECK(h && params && bnstats && raw_in && pair_out && mean && std && workspace, "predict_frames_u8: null argument");
-  if (int rc = single_net(h, "predict_frames_u8", "has no eval-mode forward (run each network alone)")) return rc;
   const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, nullptr, 0, nullptr, nullptr};
-  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
+  return predict_frames_entry("predict_frames_u8", 0, h, params, bnstats, c, mean, std, workspace, use_graph, stream);
 }
 
 int d3f_unet_predict_frames_full_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
                                     int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* pair_out,
                                     uint8_t* full_out, const float mean[3], const float std[3], void* workspace,
                                     int use_graph, void* stream) {
-  D3F_CHECK(h && params && bnstats && raw_in && pair_out && full_out && mean && std && workspace,
-            "predict_frames_full_u8: null argument");
-  if (int rc = single_net(h, "predict_frames_full_u8", "has no eval-mode forward (run each network alone)")) return rc;
   const UnetEngine::FrameCall c = {raw_in, src_h, src_w, x1, y1, cw, ch, pair_out, full_out, feather, nullptr, nullptr};
-  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
+  return predict_frames_entry("predict_frames_full_u8", FRAMES_FULL, h, params, bnstats, c, mean, std, workspace, use_graph,
+                              stream);
 }
 
 int d3f_unet_predict_frames_boxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
                                      int src_w, const int32_t* boxes, uint8_t* pair_out, const float mean[3],
                                      const float std[3], void* workspace, int use_graph, void* stream) {
-  D3F_CHECK(h && params && bnstats && raw_in && pair_out && mean && std && workspace,
-            "predict_frames_boxes_u8: null argument");
-  D3F_CHECK(boxes, "predict_frames_boxes_u8: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)");
-  if (int rc = single_net(h, "predict_frames_boxes_u8", "has no eval-mode forward (run each network alone)")) return rc;
   const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, nullptr, 0, boxes, nullptr};
-  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
+  return predict_frames_entry("predict_frames_boxes_u8", FRAMES_BOXES, h, params, bnstats, c, mean, std, workspace, use_graph,
+                              stream);
 }
 
 int d3f_unet_predict_frames_full_boxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in,
                                           int src_h, int src_w, const int32_t* boxes, int feather, uint8_t* pair_out,
                                           uint8_t* full_out, const float mean[3], const float std[3], void* workspace,
                                           int use_graph, void* stream) {
-  D3F_CHECK(h && params && bnstats && raw_in && pair_out && full_out && mean && std && workspace,
-            "predict_frames_full_boxes_u8: null argument");
-  D3F_CHECK(boxes, "predict_frames_full_boxes_u8: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)");
-  if (int rc = single_net(h, "predict_frames_full_boxes_u8", "has no eval-mode forward (run each network alone)")) return rc;
   const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, full_out, feather, boxes, nullptr};
-  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
+  return predict_frames_entry("predict_frames_full_boxes_u8", FRAMES_FULL | FRAMES_BOXES, h, params, bnstats, c, mean, std,
+                              workspace, use_graph, stream);
 }
 
 int d3f_unet_predict_frames_rboxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in, int src_h,
                                       int src_w, const int32_t* boxes, const int32_t* rot, uint8_t* pair_out,
                                       const float mean[3], const float std[3], void* workspace, int use_graph, void* stream) {
-  D3F_CHECK(h && params && bnstats && raw_in && pair_out && mean && std && workspace,
-            "predict_frames_rboxes_u8: null argument");
-  D3F_CHECK(boxes, "predict_frames_rboxes_u8: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)");
-  D3F_CHECK(rot, "predict_frames_rboxes_u8: null rot (host memory [B][2]: c16, s16 per frame)");
-  if (int rc = single_net(h, "predict_frames_rboxes_u8", "has no eval-mode forward (run each network alone)")) return rc;
   const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, nullptr, 0, boxes, rot};
-  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
+  return predict_frames_entry("predict_frames_rboxes_u8", FRAMES_BOXES | FRAMES_ROT, h, params, bnstats, c, mean, std, workspace,
+                              use_graph, stream);
 }
 
 int d3f_unet_predict_frames_full_rboxes_u8(d3f_unet_t h, const float* params, float* bnstats, const uint8_t* raw_in,
                                            int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int feather,
                                            uint8_t* pair_out, uint8_t* full_out, const float mean[3], const float std[3],
                                            void* workspace, int use_graph, void* stream) {
-  D3F_CHECK(h && params && bnstats && raw_in && pair_out && full_out && mean && std && workspace,
-            "predict_frames_full_rboxes_u8: null argument");
-  D3F_CHECK(boxes, "predict_frames_full_rboxes_u8: null boxes (host memory [B][4]: x1, y1, cw, ch per frame)");
-  D3F_CHECK(rot, "predict_frames_full_rboxes_u8: null rot (host memory [B][2]: c16, s16 per frame)");
-  if (int rc = single_net(h, "predict_frames_full_rboxes_u8", "has no eval-mode forward (run each network alone)")) return rc;
   const UnetEngine::FrameCall c = {raw_in, src_h, src_w, 0, 0, 0, 0, pair_out, full_out, feather, boxes, rot};
-  return h->e.predict_frames(c, params, bnstats, mean, std, workspace, use_graph, (hipStream_t)stream);
+  return predict_frames_entry("predict_frames_full_rboxes_u8", FRAMES_FULL | FRAMES_BOXES | FRAMES_ROT, h, params, bnstats, c,
+                              mean, std, workspace, use_graph, stream);
 }
 
 int d3f_unet_num_segments(d3f_unet_t h) { return h ? h->e.num_segments : -1; }
@@ -830,27 +825,41 @@ int d3f_u8rgb_normalise(const uint8_t* in_hwc, float* out_nchw, int B, int H, in
   return u8rgb_to_nchw_launch(in_hwc, out_nchw, B, (long)H * W, mean, std, (hipStream_t)stream);
 }
 
+// The frame path's crop and paste operators: each keeps its own null-argument check, then fills the call's descriptor
+// (pointwise.h: CropCall, PasteCall) and takes the one entry point.  The paste operators' common arguments:
+static PasteCall paste_call(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes, const uint8_t* frame,
+                            int src_h, int src_w, FrameBoxForm form, int feather, uint8_t* out) {
+  return {.patch = patch, .B = B, .H = H, .W = W, .patch_row_stride = (long)patch_row_stride_bytes, .frame = frame,
+          .src_h = src_h, .src_w = src_w, .form = form, .feather = feather, .out = out};
+}
+static void set_box(PasteCall& c, int x1, int y1, int cw, int ch) { c.x1 = x1, c.y1 = y1, c.cw = cw, c.ch = ch; }
+static void set_color(PasteCall& c, const float* coef) { c.color = true, c.coef = coef; }
+
 int d3f_crop_resize_cubic_u8(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch, uint8_t* dst,
                              int H, int W, int64_t dst_row_stride_bytes, void* stream) {
   D3F_CHECK(src && dst, "crop_resize_cubic_u8: null argument");
-  return crop_resize_cubic_u8_launch(src, B, src_h, src_w, x1, y1, cw, ch, dst, H, W, (long)dst_row_stride_bytes,
-                                     (hipStream_t)stream);
+  return crop_resize_launch({.src = src, .B = B, .src_h = src_h, .src_w = src_w, .x1 = x1, .y1 = y1, .cw = cw, .ch = ch,
+                             .dst = dst, .H = H, .W = W, .dst_row_stride = (long)dst_row_stride_bytes},
+                            (hipStream_t)stream);
 }
 
 int d3f_crop_resize_cubic_aa_u8(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch,
                                 uint8_t* dst, int H, int W, int64_t dst_row_stride_bytes, void* stream) {
   D3F_CHECK(src && dst, "crop_resize_cubic_aa_u8: null argument");
-  return crop_resize_cubic_aa_u8_launch(src, B, src_h, src_w, x1, y1, cw, ch, dst, H, W, (long)dst_row_stride_bytes,
-                                        (hipStream_t)stream);
+  return crop_resize_launch({.src = src, .B = B, .src_h = src_h, .src_w = src_w, .x1 = x1, .y1 = y1, .cw = cw, .ch = ch,
+                             .antialias = true, .dst = dst, .H = H, .W = W, .dst_row_stride = (long)dst_row_stride_bytes},
+                            (hipStream_t)stream);
 }
 
 int d3f_paste_resize_cubic_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
                               const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather,
                               uint8_t* out, void* stream) {
   D3F_CHECK(patch && frame && out, "paste_resize_cubic_u8: null argument");
-  return paste_resize_cubic_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, x1, y1, cw, ch,
-                                      feather, out, (hipStream_t)stream);
+  PasteCall c = paste_call(patch, B, H, W, patch_row_stride_bytes, frame, src_h, src_w, FRAME_BOX_ONE, feather, out);
+  set_box(c, x1, y1, cw, ch);
+  return paste_resize_launch(c, (hipStream_t)stream);
 }
+
 
 int d3f_channel_sums_u8(const uint8_t* img, int B, int H, int W, int64_t row_stride_bytes, uint64_t* sums, void* stream) {
   D3F_CHECK(img && sums, "channel_sums_u8: null argument");
@@ -866,46 +875,54 @@ int d3f_paste_resize_cubic_color_u8(const uint8_t* patch, int B, int H, int W, i
                                     const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather,
                                     const float* coef, uint8_t* out, void* stream) {
   D3F_CHECK(patch && frame && out && coef, "paste_resize_cubic_color_u8: null argument");
-  return paste_resize_cubic_color_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, x1, y1, cw, ch,
-                                            feather, coef, out, (hipStream_t)stream);
+  PasteCall c = paste_call(patch, B, H, W, patch_row_stride_bytes, frame, src_h, src_w, FRAME_BOX_ONE, feather, out);
+  set_box(c, x1, y1, cw, ch);
+  set_color(c, coef);
+  return paste_resize_launch(c, (hipStream_t)stream);
 }
 
 static_assert(D3F_FRAME_BOXES_MAX == FRAME_BOXES_MAX, "d3f_hip.h states the boxes of a launch");
 int d3f_crop_resize_cubic_boxes_u8(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst, int H,
                                    int W, int64_t dst_row_stride_bytes, void* stream) {
   D3F_CHECK(src && dst, "crop_resize_cubic_boxes_u8: null argument");
-  return crop_resize_cubic_boxes_u8_launch(src, B, src_h, src_w, boxes, dst, H, W, (long)dst_row_stride_bytes,
-                                           (hipStream_t)stream);
+  return crop_resize_launch({.src = src, .B = B, .src_h = src_h, .src_w = src_w, .form = FRAME_BOX_PER_FRAME, .boxes = boxes,
+                             .dst = dst, .H = H, .W = W, .dst_row_stride = (long)dst_row_stride_bytes},
+                            (hipStream_t)stream);
 }
 
 int d3f_crop_resize_cubic_aa_boxes_u8(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
                                       int H, int W, int64_t dst_row_stride_bytes, void* stream) {
   D3F_CHECK(src && dst, "crop_resize_cubic_aa_boxes_u8: null argument");
-  return crop_resize_cubic_aa_boxes_u8_launch(src, B, src_h, src_w, boxes, dst, H, W, (long)dst_row_stride_bytes,
-                                              (hipStream_t)stream);
+  return crop_resize_launch({.src = src, .B = B, .src_h = src_h, .src_w = src_w, .form = FRAME_BOX_PER_FRAME, .boxes = boxes,
+                             .antialias = true, .dst = dst, .H = H, .W = W, .dst_row_stride = (long)dst_row_stride_bytes},
+                            (hipStream_t)stream);
 }
 
 int d3f_paste_resize_cubic_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
                                     const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
                                     uint8_t* out, void* stream) {
   D3F_CHECK(patch && frame && out, "paste_resize_cubic_boxes_u8: null argument");
-  return paste_resize_cubic_boxes_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, boxes, feather,
-                                            out, (hipStream_t)stream);
+  PasteCall c = paste_call(patch, B, H, W, patch_row_stride_bytes, frame, src_h, src_w, FRAME_BOX_PER_FRAME, feather, out);
+  c.boxes = boxes;
+  return paste_resize_launch(c, (hipStream_t)stream);
 }
 
 int d3f_paste_resize_cubic_color_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
                                           const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
                                           const float* coef, uint8_t* out, void* stream) {
   D3F_CHECK(patch && frame && out && coef, "paste_resize_cubic_color_boxes_u8: null argument");
-  return paste_resize_cubic_color_boxes_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, boxes,
-                                                  feather, coef, out, (hipStream_t)stream);
+  PasteCall c = paste_call(patch, B, H, W, patch_row_stride_bytes, frame, src_h, src_w, FRAME_BOX_PER_FRAME, feather, out);
+  c.boxes = boxes;
+  set_color(c, coef);
+  return paste_resize_launch(c, (hipStream_t)stream);
 }
 
 int d3f_crop_resize_cubic_rboxes_u8(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, const int32_t* rot,
                                     uint8_t* dst, int H, int W, int64_t dst_row_stride_bytes, void* stream) {
   D3F_CHECK(src && dst, "crop_resize_cubic_rboxes_u8: null argument");
-  return crop_resize_cubic_rboxes_u8_launch(src, B, src_h, src_w, boxes, rot, dst, H, W, (long)dst_row_stride_bytes,
-                                            (hipStream_t)stream);
+  return crop_resize_launch({.src = src, .B = B, .src_h = src_h, .src_w = src_w, .form = FRAME_BOX_ROTATED, .boxes = boxes,
+                             .rot = rot, .dst = dst, .H = H, .W = W, .dst_row_stride = (long)dst_row_stride_bytes},
+                            (hipStream_t)stream);
 }
 
 int d3f_crop_resize_cubic_rboxes_u8_nhwc(int dtype, const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
@@ -917,25 +934,31 @@ int d3f_crop_resize_cubic_rboxes_u8_nhwc(int dtype, const uint8_t* src, int B, i
   // (mean * 255, std * 255 in fp32, as the frame entries scale them)
   const float m[3] = {mean[0] * 255.0f, mean[1] * 255.0f, mean[2] * 255.0f};
   const float sd[3] = {std[0] * 255.0f, std[1] * 255.0f, std[2] * 255.0f};
-  return crop_resize_cubic_rboxes_u8_nhwc_launch(dtype, src, B, src_h, src_w, boxes, rot, dst, H, W, (long)dst_row_stride_bytes,
-                                                 act, Cpad, m, sd, (hipStream_t)stream);
+  return crop_resize_launch({.src = src, .B = B, .src_h = src_h, .src_w = src_w, .form = FRAME_BOX_ROTATED, .boxes = boxes,
+                             .rot = rot, .dst = dst, .H = H, .W = W, .dst_row_stride = (long)dst_row_stride_bytes, .act = act,
+                             .dtype = dtype, .Cpad = Cpad, .mean255 = m, .std255 = sd},
+                            (hipStream_t)stream);
 }
 
 int d3f_paste_resize_cubic_rboxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
                                      const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, const int32_t* rot,
                                      int feather, uint8_t* out, void* stream) {
   D3F_CHECK(patch && frame && out, "paste_resize_cubic_rboxes_u8: null argument");
-  return paste_resize_cubic_rboxes_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, boxes, rot,
-                                             feather, nullptr, false, out, (hipStream_t)stream);
+  PasteCall c = paste_call(patch, B, H, W, patch_row_stride_bytes, frame, src_h, src_w, FRAME_BOX_ROTATED, feather, out);
+  c.boxes = boxes, c.rot = rot;
+  return paste_resize_launch(c, (hipStream_t)stream);
 }
 
 int d3f_paste_resize_cubic_color_rboxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
                                            const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, const int32_t* rot,
                                            int feather, const float* coef, uint8_t* out, void* stream) {
   D3F_CHECK(patch && frame && out && coef, "paste_resize_cubic_color_rboxes_u8: null argument");
-  return paste_resize_cubic_rboxes_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, boxes, rot,
-                                             feather, coef, true, out, (hipStream_t)stream);
+  PasteCall c = paste_call(patch, B, H, W, patch_row_stride_bytes, frame, src_h, src_w, FRAME_BOX_ROTATED, feather, out);
+  c.boxes = boxes, c.rot = rot;
+  set_color(c, coef);
+  return paste_resize_launch(c, (hipStream_t)stream);
 }
+
 
 int64_t d3f_paste_multiband_workspace_bytes(int B, int cw_max, int ch_max, int levels) {
   return paste_multiband_workspace_bytes(B, cw_max, ch_max, levels);
@@ -945,9 +968,9 @@ int d3f_paste_multiband_u8(const uint8_t* patch, int B, int H, int W, int64_t pa
                            int src_h, int src_w, int x1, int y1, int cw, int ch, int feather, int levels, void* workspace,
                            int64_t workspace_bytes, uint8_t* out, void* stream) {
   D3F_CHECK(patch && frame && out, "paste_multiband_u8: null argument");
-  return paste_multiband_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, x1, y1, cw, ch, nullptr,
-                                   feather, levels, nullptr, false, workspace, (long)workspace_bytes, out,
-                                   (hipStream_t)stream);
+  PasteCall c = paste_call(patch, B, H, W, patch_row_stride_bytes, frame, src_h, src_w, FRAME_BOX_ONE, feather, out);
+  set_box(c, x1, y1, cw, ch);
+  return paste_multiband_u8_launch(c, levels, workspace, (long)workspace_bytes, (hipStream_t)stream);
 }
 
 int d3f_paste_multiband_color_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
@@ -955,17 +978,19 @@ int d3f_paste_multiband_color_u8(const uint8_t* patch, int B, int H, int W, int6
                                  int levels, const float* coef, void* workspace, int64_t workspace_bytes, uint8_t* out,
                                  void* stream) {
   D3F_CHECK(patch && frame && out && coef, "paste_multiband_color_u8: null argument");
-  return paste_multiband_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, x1, y1, cw, ch, nullptr,
-                                   feather, levels, coef, true, workspace, (long)workspace_bytes, out, (hipStream_t)stream);
+  PasteCall c = paste_call(patch, B, H, W, patch_row_stride_bytes, frame, src_h, src_w, FRAME_BOX_ONE, feather, out);
+  set_box(c, x1, y1, cw, ch);
+  set_color(c, coef);
+  return paste_multiband_u8_launch(c, levels, workspace, (long)workspace_bytes, (hipStream_t)stream);
 }
 
 int d3f_paste_multiband_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
                                  const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather, int levels,
                                  void* workspace, int64_t workspace_bytes, uint8_t* out, void* stream) {
   D3F_CHECK(patch && frame && out && boxes, "paste_multiband_boxes_u8: null argument");
-  return paste_multiband_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, 0, 0, 0, 0, boxes,
-                                   feather, levels, nullptr, false, workspace, (long)workspace_bytes, out,
-                                   (hipStream_t)stream);
+  PasteCall c = paste_call(patch, B, H, W, patch_row_stride_bytes, frame, src_h, src_w, FRAME_BOX_PER_FRAME, feather, out);
+  c.boxes = boxes;
+  return paste_multiband_u8_launch(c, levels, workspace, (long)workspace_bytes, (hipStream_t)stream);
 }
 
 int d3f_paste_multiband_color_boxes_u8(const uint8_t* patch, int B, int H, int W, int64_t patch_row_stride_bytes,
@@ -973,9 +998,12 @@ int d3f_paste_multiband_color_boxes_u8(const uint8_t* patch, int B, int H, int W
                                        int levels, const float* coef, void* workspace, int64_t workspace_bytes, uint8_t* out,
                                        void* stream) {
   D3F_CHECK(patch && frame && out && coef && boxes, "paste_multiband_color_boxes_u8: null argument");
-  return paste_multiband_u8_launch(patch, B, H, W, (long)patch_row_stride_bytes, frame, src_h, src_w, 0, 0, 0, 0, boxes,
-                                   feather, levels, coef, true, workspace, (long)workspace_bytes, out, (hipStream_t)stream);
+  PasteCall c = paste_call(patch, B, H, W, patch_row_stride_bytes, frame, src_h, src_w, FRAME_BOX_PER_FRAME, feather, out);
+  c.boxes = boxes;
+  set_color(c, coef);
+  return paste_multiband_u8_launch(c, levels, workspace, (long)workspace_bytes, (hipStream_t)stream);
 }
+
 
 int d3f_temporal_filter_u8(const uint8_t* real, int64_t real_row_stride_bytes, uint8_t* fake, int64_t fake_row_stride_bytes,
                            int B, int H, int W, float* state_fake, uint8_t* state_real, int32_t* state_valid, float strength,

@@ -834,59 +834,38 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
             who);
   D3F_CHECK(!(rot && multiband),
             "%s: D3F_BLEND_MULTIBAND together with rot: the multiband pyramid of a rotated box is out of scope", who);
-  if (int rc = rot    ? crop_resize_cubic_rboxes_check(B, c.src_h, c.src_w, boxes, rot, H, W, stride)
-               : boxes ? (aa ? crop_resize_cubic_aa_boxes_check : crop_resize_cubic_boxes_check)(B, c.src_h, c.src_w, boxes, H,
-                                                                                              W, stride)
-                     : (aa ? crop_resize_cubic_aa_check : crop_resize_cubic_check)(B, c.src_h, c.src_w, c.x1, c.y1, c.cw,
-                                                                                  c.ch, H, W, stride))
-    return rc;
-  if (multiband) {
-    // the pyramid workspace: grown here, in front of every launch and outside any capture
-    int cw_max = c.cw, ch_max = c.ch;
-    if (boxes) {
-      if (int rc = paste_resize_cubic_boxes_check(fake, c.raw_in, c.full_out, B, H, W, stride, c.src_h, c.src_w, boxes,
-                                                  c.feather))
-        return rc;
-      cw_max = ch_max = 1;
-      for (int b = 0; b < B; ++b) {
-        cw_max = cw_max > boxes[4L * b + 2] ? cw_max : boxes[4L * b + 2];
-        ch_max = ch_max > boxes[4L * b + 3] ? ch_max : boxes[4L * b + 3];
+  // the call's crop and its paste (resize.hip): one descriptor each, whatever the form
+  // one launch writes the real half of the pair and, from the same rounded bytes, the network input
+  const CropCall crop = {.src = c.raw_in, .B = B, .src_h = c.src_h, .src_w = c.src_w, .form = frame_box_form(boxes, rot),
+                         .x1 = c.x1, .y1 = c.y1, .cw = c.cw, .ch = c.ch, .boxes = boxes, .rot = rot, .antialias = aa,
+                         .dst = pair, .H = H, .W = W, .dst_row_stride = stride, .act = ws + tensors[t_x].off, .dtype = dtype,
+                         .Cpad = tensors[t_x].C, .mean255 = k.mean, .std255 = k.stdv};
+  // the fake half of the pair is the patch; coef: written by the colour branch below, in front of the paste
+  const PasteCall paste = {.patch = fake, .B = B, .H = H, .W = W, .patch_row_stride = stride, .frame = c.raw_in,
+                           .src_h = c.src_h, .src_w = c.src_w, .form = crop.form, .x1 = c.x1, .y1 = c.y1, .cw = c.cw,
+                           .ch = c.ch, .boxes = boxes, .rot = rot, .feather = c.feather, .out = c.full_out, .color = color,
+                           .coef = color ? o.color_coef.p : nullptr};
+  if (int rc = crop_resize_check(crop)) return rc;
+  if (full) {
+    if (int rc = paste_resize_check(paste)) return rc;
+    if (multiband) {
+      // the pyramid workspace: grown here, in front of every launch and outside any capture
+      int cw_max, ch_max;
+      frame_boxes_max_extent(boxes, B, c.cw, c.ch, &cw_max, &ch_max);
+      const long need = paste_multiband_workspace_bytes(B, cw_max, ch_max, o.blend_levels);
+      if (need < 0) return -1;
+      if (need > o.blend_ws_bytes) {
+        g_frames_full_.destroy();  // it bakes the old workspace in
+        if (o.blend_ws.p) {
+          D3F_HIP(hipFree(o.blend_ws.p));  // (waits for the device: no earlier call still uses it)
+          o.blend_ws.p = nullptr;
+          o.blend_ws_bytes = 0;
+        }
+        D3F_HIP(o.blend_ws.ensure((size_t)need));
+        o.blend_ws_bytes = need;
       }
+      if (int rc = paste_multiband_check(paste, o.blend_levels, o.blend_ws.p, o.blend_ws_bytes)) return rc;
     }
-    const long need = paste_multiband_workspace_bytes(B, cw_max, ch_max, o.blend_levels);
-    if (need < 0) return -1;
-    if (need > o.blend_ws_bytes) {
-      g_frames_full_.destroy();  // it bakes the old workspace in
-      if (o.blend_ws.p) {
-        D3F_HIP(hipFree(o.blend_ws.p));  // (waits for the device: no earlier call still uses it)
-        o.blend_ws.p = nullptr;
-        o.blend_ws_bytes = 0;
-      }
-      D3F_HIP(o.blend_ws.ensure((size_t)need));
-      o.blend_ws_bytes = need;
-    }
-    if (int rc = paste_multiband_check(fake, c.raw_in, c.full_out, o.color_coef.p, color, B, H, W, stride, c.src_h, c.src_w,
-                                       c.x1, c.y1, c.cw, c.ch, boxes, c.feather, o.blend_levels, o.blend_ws.p,
-                                       o.blend_ws_bytes))
-      return rc;
-    D3F_CHECK(!(use_graph && c.full_out == c.raw_in),
-              "predict_frames_full_u8: full_out == raw_in (in place) cannot be replayed from a graph: pass use_graph = 0");
-  } else if (full) {
-    int rc;
-    if (rot)
-      rc = paste_resize_cubic_rboxes_check(fake, c.raw_in, c.full_out, o.color_coef.p, color, B, H, W, stride, c.src_h, c.src_w,
-                                           boxes, rot, c.feather);
-    else if (boxes)
-      rc = color ? paste_resize_cubic_color_boxes_check(fake, c.raw_in, c.full_out, o.color_coef.p, B, H, W, stride, c.src_h,
-                                                        c.src_w, boxes, c.feather)
-                 : paste_resize_cubic_boxes_check(fake, c.raw_in, c.full_out, B, H, W, stride, c.src_h, c.src_w, boxes,
-                                                  c.feather);
-    else
-      rc = color ? paste_resize_cubic_color_check(fake, c.raw_in, c.full_out, o.color_coef.p, B, H, W, stride, c.src_h,
-                                                  c.src_w, c.x1, c.y1, c.cw, c.ch, c.feather)
-                 : paste_resize_cubic_check(fake, c.raw_in, c.full_out, B, H, W, stride, c.src_h, c.src_w, c.x1, c.y1, c.cw,
-                                            c.ch, c.feather);
-    if (rc) return rc;
     D3F_CHECK(!(use_graph && c.full_out == c.raw_in),
               "predict_frames_full_u8: full_out == raw_in (in place) cannot be replayed from a graph: pass use_graph = 0");
   }
@@ -899,17 +878,7 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
       if (int rc = frame_temporal_reset(s)) return rc;
   }
   auto launches = [&](hipStream_t ls) {
-    // one launch writes the real half of the pair and, from the same rounded bytes, the network input
-    if (int rc = rot   ? crop_resize_cubic_rboxes_u8_nhwc_launch(dtype, c.raw_in, B, c.src_h, c.src_w, boxes, rot, pair, H, W,
-                                                                 stride, ws + tensors[t_x].off, tensors[t_x].C, k.mean, k.stdv,
-                                                                 ls)
-                 : boxes ? (aa ? crop_resize_cubic_aa_boxes_u8_nhwc_launch : crop_resize_cubic_boxes_u8_nhwc_launch)(
-                             dtype, c.raw_in, B, c.src_h, c.src_w, boxes, pair, H, W, stride, ws + tensors[t_x].off,
-                             tensors[t_x].C, k.mean, k.stdv, ls)
-                       : (aa ? crop_resize_cubic_aa_u8_nhwc_launch : crop_resize_cubic_u8_nhwc_launch)(
-                             dtype, c.raw_in, B, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, pair, H, W, stride,
-                             ws + tensors[t_x].off, tensors[t_x].C, k.mean, k.stdv, ls))
-      return rc;
+    if (int rc = crop_resize_launch(crop, ls)) return rc;
     float* head_out = reinterpret_cast<float*>(ws + head_nchw_off);
     if (int rc = forward_body(params_, bnstats, head_out, ws, 0, ls, nullptr, false)) return rc;
     head_z_live_ = false;
@@ -920,42 +889,21 @@ int UnetEngine::predict_frames(const FrameCall& c, const float* params_, float* 
                                              o.strength, o.threshold, ls))
         return rc;
     if (!full) return 0;
-    // the fake half of the pair is the patch
-    if (multiband && !color)
-      return paste_multiband_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, boxes,
-                                       c.feather, o.blend_levels, nullptr, false, o.blend_ws.p, o.blend_ws_bytes, c.full_out,
-                                       ls);
-    if (!color && rot)
-      return paste_resize_cubic_rboxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, rot, c.feather,
-                                                 nullptr, false, c.full_out, ls);
-    if (!color)
-      return boxes ? paste_resize_cubic_boxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, c.feather,
-                                                        c.full_out, ls)
-                   : paste_resize_cubic_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch,
-                                                  c.feather, c.full_out, ls);
-    // colour match: the sums of both halves (set 0 the real crop = `to`, set 1 the fake = `from`), the coefficients, and
-    // the paste in its colour form
-    int parts = 0;
-    if (int rc = channel_sums_pair_slabs_launch(pair, pair_fake_off(), B, H, W, stride, o.color_slabs.p, &parts, ls)) return rc;
-    const uint64_t* to = o.color_slabs.p;
-    const uint64_t* from = to + (size_t)B * parts * 6;
-    if (int rc = color_match_coef_launch(from, to, parts, B, (long)H * W, o.color_coef.p, ls)) return rc;
-    if (temporal)
-      if (int rc = color_coef_smooth_launch(o.color_coef.p, to, parts, B, (long)H * W, o.strength, o.state_coef.p,
-                                            o.state_sum.p, o.valid.p + 1, ls))
-        return rc;
-    if (multiband)
-      return paste_multiband_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, boxes,
-                                       c.feather, o.blend_levels, o.color_coef.p, true, o.blend_ws.p, o.blend_ws_bytes,
-                                       c.full_out, ls);
-    if (rot)
-      return paste_resize_cubic_rboxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, rot, c.feather,
-                                                 o.color_coef.p, true, c.full_out, ls);
-    if (boxes)
-      return paste_resize_cubic_color_boxes_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, boxes, c.feather,
-                                                      o.color_coef.p, c.full_out, ls);
-    return paste_resize_cubic_color_u8_launch(fake, B, H, W, stride, c.raw_in, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch,
-                                              c.feather, o.color_coef.p, c.full_out, ls);
+    if (color) {
+      // colour match: the sums of both halves (set 0 the real crop = `to`, set 1 the fake = `from`), the coefficients, and
+      // the paste in its colour form
+      int parts = 0;
+      if (int rc = channel_sums_pair_slabs_launch(pair, pair_fake_off(), B, H, W, stride, o.color_slabs.p, &parts, ls)) return rc;
+      const uint64_t* to = o.color_slabs.p;
+      const uint64_t* from = to + (size_t)B * parts * 6;
+      if (int rc = color_match_coef_launch(from, to, parts, B, (long)H * W, o.color_coef.p, ls)) return rc;
+      if (temporal)
+        if (int rc = color_coef_smooth_launch(o.color_coef.p, to, parts, B, (long)H * W, o.strength, o.state_coef.p,
+                                              o.state_sum.p, o.valid.p + 1, ls))
+          return rc;
+    }
+    if (multiband) return paste_multiband_u8_launch(paste, o.blend_levels, o.blend_ws.p, o.blend_ws_bytes, ls);
+    return paste_resize_launch(paste, ls);
   };
   if (!use_graph) return launches(s);
   int strength_bits;

@@ -308,144 +308,109 @@ long paste_multiband_workspace_bytes(int B, int cw_max, int ch_max, int levels) 
   return (long)B * 3 * p.slab_bytes;
 }
 
-// the largest box extents of a call
-static void mb_max_box(const int32_t* boxes, int B, int cw, int ch, int* cw_max, int* ch_max) {
-  *cw_max = cw;
-  *ch_max = ch;
-  if (!boxes) return;
-  *cw_max = *ch_max = 1;
-  for (int b = 0; b < B; ++b) {
-    *cw_max = *cw_max > boxes[4L * b + 2] ? *cw_max : boxes[4L * b + 2];
-    *ch_max = *ch_max > boxes[4L * b + 3] ? *ch_max : boxes[4L * b + 3];
-  }
-}
-
 static bool mb_overlap(const void* a, long a_bytes, const void* b, long b_bytes) {
   const char* p = reinterpret_cast<const char*>(a);
   const char* q = reinterpret_cast<const char*>(b);
   return a_bytes > 0 && b_bytes > 0 && p < q + b_bytes && q < p + a_bytes;
 }
 
-int paste_multiband_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef, bool color, int B,
-                          int H, int W, long patch_row_stride, int src_h, int src_w, int x1, int y1, int cw, int ch,
-                          const int32_t* boxes, int feather, int levels, const void* workspace, long workspace_bytes) {
+int paste_multiband_check(const PasteCall& c, int levels, const void* workspace, long workspace_bytes) {
   if (int rc = mb_levels_check(levels)) return rc;
+  D3F_CHECK(c.form != FRAME_BOX_ROTATED, "paste_multiband: the multiband paste has no rotated form");
   // the plain paste's refusals: sizes, the box(es), strides, feather, overlaps
-  int rc;
-  if (boxes)
-    rc = color ? paste_resize_cubic_color_boxes_check(patch, frame, out, coef, B, H, W, patch_row_stride, src_h, src_w, boxes,
-                                                      feather)
-               : paste_resize_cubic_boxes_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, boxes, feather);
-  else
-    rc = color ? paste_resize_cubic_color_check(patch, frame, out, coef, B, H, W, patch_row_stride, src_h, src_w, x1, y1, cw,
-                                                ch, feather)
-               : paste_resize_cubic_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather);
-  if (rc) return rc;
+  if (int rc = paste_resize_check(c)) return rc;
+  const int32_t* boxes = c.form == FRAME_BOX_PER_FRAME ? c.boxes : nullptr;
   if (boxes) {
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0; b < c.B; ++b) {
       const int bw = boxes[4L * b + 2], bh = boxes[4L * b + 3];
       D3F_CHECK((bw < bh ? bw : bh) >= (1 << levels), "paste_multiband: frame %d: box %d x %d below %d on a side (%d levels)", b,
                 bw, bh, 1 << levels, levels);
     }
   } else {
-    D3F_CHECK((cw < ch ? cw : ch) >= (1 << levels), "paste_multiband: box %d x %d below %d on a side (%d levels)", cw, ch,
-              1 << levels, levels);
+    D3F_CHECK((c.cw < c.ch ? c.cw : c.ch) >= (1 << levels), "paste_multiband: box %d x %d below %d on a side (%d levels)", c.cw,
+              c.ch, 1 << levels, levels);
   }
-  if (B == 0) return 0;
+  if (c.B == 0) return 0;
   int cw_max, ch_max;
-  mb_max_box(boxes, B, cw, ch, &cw_max, &ch_max);
-  const long need = paste_multiband_workspace_bytes(B, cw_max, ch_max, levels);
+  frame_boxes_max_extent(boxes, c.B, c.cw, c.ch, &cw_max, &ch_max);
+  const long need = paste_multiband_workspace_bytes(c.B, cw_max, ch_max, levels);
   D3F_CHECK(workspace != nullptr, "paste_multiband: null workspace");
   D3F_CHECK((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "paste_multiband: the workspace must start on 16 bytes");
   D3F_CHECK(workspace_bytes >= need,
             "paste_multiband: workspace of %ld bytes, %ld needed (d3f_paste_multiband_workspace_bytes(%d, %d, %d, %d))",
-            workspace_bytes, need, B, cw_max, ch_max, levels);
-  const long bytes = (long)B * src_h * src_w * 3, patch_bytes = ((long)B * H - 1) * patch_row_stride + 3L * W;
-  D3F_CHECK(!mb_overlap(workspace, need, out, bytes) && !mb_overlap(workspace, need, frame, bytes) &&
-                !mb_overlap(workspace, need, patch, patch_bytes) &&
-                !(color && mb_overlap(workspace, need, coef, (long)B * 6 * sizeof(float))),
+            workspace_bytes, need, c.B, cw_max, ch_max, levels);
+  const long bytes = (long)c.B * c.src_h * c.src_w * 3, patch_bytes = ((long)c.B * c.H - 1) * c.patch_row_stride + 3L * c.W;
+  D3F_CHECK(!mb_overlap(workspace, need, c.out, bytes) && !mb_overlap(workspace, need, c.frame, bytes) &&
+                !mb_overlap(workspace, need, c.patch, patch_bytes) &&
+                !(c.color && mb_overlap(workspace, need, c.coef, (long)c.B * 6 * sizeof(float))),
             "paste_multiband: the workspace overlaps patch, frame, out or coef");
   return 0;
 }
 
-// the sequence for frames b0 .. b0 + n - 1 of a call (their patch, frame, out, coef and slabs are passed)
+// the sequence for a chunk of a call (c: its frames, paste_chunk; its boxes from b0; ws: its slabs)
 template <bool BOXES>
-static int mb_launch_frames(const MultibandPlan& p, const uint8_t* patch, int n, int H, int W, long patch_row_stride,
-                            const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes,
-                            int b0, const float* coef, bool color, char* ws, uint8_t* out, hipStream_t stream) {
-  if (int rc = multiband_diff_launch(patch, n, H, W, patch_row_stride, frame, src_h, src_w, x1, y1, cw, ch, boxes, b0, coef,
-                                     color, reinterpret_cast<int16_t*>(ws + p.g_off[0]), p.pitch[0], p.slab_bytes, stream))
+static int mb_launch_frames(const MultibandPlan& p, const PasteCall& c, int b0, char* ws, hipStream_t stream) {
+  if (int rc = multiband_diff_launch(c, b0, reinterpret_cast<int16_t*>(ws + p.g_off[0]), p.pitch[0], p.slab_bytes, stream))
     return rc;
+  const int n = c.B;
   BoxedGeom<MbGeom, BOXES> a;
-  a.g = MbGeom{src_h, src_w, x1, y1, cw, ch, 0, 0};
-  int cw_max = cw, ch_max = ch;
-  dim3 fin((src_w + FIN_TW - 1) / FIN_TW, (src_h + FIN_TH - 1) / FIN_TH, n);
+  a.g = MbGeom{c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, 0, 0};
+  int cw_max, ch_max;
+  frame_boxes_max_extent(BOXES ? c.boxes + 4L * b0 : nullptr, n, c.cw, c.ch, &cw_max, &ch_max);
+  InPlaceTiles tiles{FIN_TW, FIN_TH};
   if constexpr (BOXES) {
-    fill_frame_boxes(a.boxes, boxes, b0, n);
-    mb_max_box(boxes + 4L * b0, n, 0, 0, &cw_max, &ch_max);
-    if (frame == out) {  // in place: the most tiles any frame's box meets (the kernel derives each frame's first tile)
-      fin.x = fin.y = 1;
-      for (int i = 0; i < n; ++i) {
-        const FrameBox& bx = a.boxes.box[i];
-        const unsigned nx = (bx.x1 + bx.cw - 1) / FIN_TW - bx.x1 / FIN_TW + 1;
-        const unsigned ny = (bx.y1 + bx.ch - 1) / FIN_TH - bx.y1 / FIN_TH + 1;
-        fin.x = fin.x > nx ? fin.x : nx;
-        fin.y = fin.y > ny ? fin.y : ny;
-      }
+    fill_frame_boxes(a.boxes, c.boxes, b0, n);
+    for (int i = 0; i < n; ++i) tiles.cover(a.boxes.box[i]);
+  } else {
+    tiles.cover(FrameBox{c.x1, c.y1, c.cw, c.ch});
+  }
+  dim3 fin((c.src_w + FIN_TW - 1) / FIN_TW, (c.src_h + FIN_TH - 1) / FIN_TH, n);
+  if (c.frame == c.out) {  // in place: the tiles that meet a box (BOXES: the kernel derives each frame's first tile)
+    fin.x = tiles.nx;
+    fin.y = tiles.ny;
+    if constexpr (!BOXES) {
+      a.g.tx0 = c.x1 / FIN_TW;
+      a.g.ty0 = c.y1 / FIN_TH;
     }
-  } else if (frame == out) {  // in place: the tiles that meet the box
-    a.g.tx0 = x1 / FIN_TW;
-    a.g.ty0 = y1 / FIN_TH;
-    fin.x = (x1 + cw - 1) / FIN_TW - a.g.tx0 + 1;
-    fin.y = (y1 + ch - 1) / FIN_TH - a.g.ty0 + 1;
   }
   const int N = p.levels;
-  auto tiles = [&](int l) {
+  auto tiles_of = [&](int l) {
     return dim3((mb_dim(cw_max, l) + MB_TW - 1) / MB_TW, (mb_dim(ch_max, l) + MB_TH - 1) / MB_TH, 3 * n);
   };
   for (int l = 0; l < N; ++l)
-    hipLaunchKernelGGL((multiband_reduce_kernel<BOXES>), tiles(l + 1), dim3(MB_THREADS), 0, stream, ws, p, a, l);
+    hipLaunchKernelGGL((multiband_reduce_kernel<BOXES>), tiles_of(l + 1), dim3(MB_THREADS), 0, stream, ws, p, a, l);
   for (int l = N - 1; l >= 1; --l) {
     if (l == N - 1)
-      hipLaunchKernelGGL((multiband_collapse_kernel<true, BOXES>), tiles(l), dim3(MB_THREADS), 0, stream, ws, p, a, l);
+      hipLaunchKernelGGL((multiband_collapse_kernel<true, BOXES>), tiles_of(l), dim3(MB_THREADS), 0, stream, ws, p, a, l);
     else
-      hipLaunchKernelGGL((multiband_collapse_kernel<false, BOXES>), tiles(l), dim3(MB_THREADS), 0, stream, ws, p, a, l);
+      hipLaunchKernelGGL((multiband_collapse_kernel<false, BOXES>), tiles_of(l), dim3(MB_THREADS), 0, stream, ws, p, a, l);
   }
   if (N == 1)
-    hipLaunchKernelGGL((multiband_final_kernel<true, BOXES>), fin, dim3(FIN_TW * FIN_TH), 0, stream, frame, out, ws, p, a);
+    hipLaunchKernelGGL((multiband_final_kernel<true, BOXES>), fin, dim3(FIN_TW * FIN_TH), 0, stream, c.frame, c.out, ws, p, a);
   else
-    hipLaunchKernelGGL((multiband_final_kernel<false, BOXES>), fin, dim3(FIN_TW * FIN_TH), 0, stream, frame, out, ws, p, a);
+    hipLaunchKernelGGL((multiband_final_kernel<false, BOXES>), fin, dim3(FIN_TW * FIN_TH), 0, stream, c.frame, c.out, ws, p, a);
   D3F_HIP(hipGetLastError());
   return 0;
 }
 
-int paste_multiband_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
-                              int src_h, int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes, int feather,
-                              int levels, const float* coef, bool color, void* workspace, long workspace_bytes, uint8_t* out,
-                              hipStream_t stream) {
-  if (int rc = paste_multiband_check(patch, frame, out, coef, color, B, H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch,
-                                     boxes, feather, levels, workspace, workspace_bytes))
-    return rc;
-  if (B == 0) return 0;
+int paste_multiband_u8_launch(const PasteCall& c, int levels, void* workspace, long workspace_bytes, hipStream_t stream) {
+  if (int rc = paste_multiband_check(c, levels, workspace, workspace_bytes)) return rc;
+  if (c.B == 0) return 0;
+  const bool boxes = c.form == FRAME_BOX_PER_FRAME;
   int cw_max, ch_max;
-  mb_max_box(boxes, B, cw, ch, &cw_max, &ch_max);
+  frame_boxes_max_extent(boxes ? c.boxes : nullptr, c.B, c.cw, c.ch, &cw_max, &ch_max);
   MultibandPlan p;
-  mb_plan(p, cw_max, ch_max, levels, feather);
-  const long frame_bytes = (long)src_h * src_w * 3, patch_bytes = (long)H * patch_row_stride;
-  const int step = boxes ? FRAME_BOXES_MAX : MB_FRAMES_MAX;
-  for (int b0 = 0; b0 < B; b0 += step) {  // launches of at most `step` frames each, in order
-    const int n = B - b0 < step ? B - b0 : step;
-    char* ws = reinterpret_cast<char*>(workspace) + (long)b0 * 3 * p.slab_bytes;
-    const float* cf = color ? coef + 6L * b0 : nullptr;
-    const int rc = boxes ? mb_launch_frames<true>(p, patch + b0 * patch_bytes, n, H, W, patch_row_stride,
-                                                  frame + b0 * frame_bytes, src_h, src_w, 0, 0, 0, 0, boxes, b0, cf, color, ws,
-                                                  out + b0 * frame_bytes, stream)
-                         : mb_launch_frames<false>(p, patch + b0 * patch_bytes, n, H, W, patch_row_stride,
-                                                   frame + b0 * frame_bytes, src_h, src_w, x1, y1, cw, ch, nullptr, 0, cf,
-                                                   color, ws, out + b0 * frame_bytes, stream);
-    if (rc) return rc;
-  }
-  return 0;
+  mb_plan(p, cw_max, ch_max, levels, c.feather);
+  const long frame_bytes = (long)c.src_h * c.src_w * 3, patch_bytes = (long)c.H * c.patch_row_stride;
+  return for_frame_chunks(
+      c.B, boxes ? FRAME_BOXES_MAX : MB_FRAMES_MAX,
+      [&](int b0, int n, const uint8_t* patch, const uint8_t* frame, uint8_t* out, const float* coef, char* ws) {
+        const PasteCall k = paste_chunk(c, n, patch, frame, out, coef);
+        return boxes ? mb_launch_frames<true>(p, k, b0, ws, stream) : mb_launch_frames<false>(p, k, b0, ws, stream);
+      },
+      FramePtr<const uint8_t>{c.patch, patch_bytes}, FramePtr<const uint8_t>{c.frame, frame_bytes},
+      FramePtr<uint8_t>{c.out, frame_bytes}, FramePtr<const float>{c.color ? c.coef : nullptr, 6},
+      FramePtr<char>{reinterpret_cast<char*>(workspace), 3 * p.slab_bytes});
 }
 
 }  // namespace d3f

@@ -114,44 +114,18 @@ int u8bgr_to_nhwc_launch(int dtype, const uint8_t* in, void* out, long npix, int
 int nchw_to_u8bgr_launch(const float* in, uint8_t* out, int B, int H, int W, long out_row_stride, const float mean255[3],
                          const float std255[3], hipStream_t stream);
 
-// script_tools frame path (resize.hip): crop box (x1, y1, cw, ch) of uint8 BGR frames [B][src_h][src_w][3] -> bicubic
-// (cv2.INTER_CUBIC in float arithmetic) -> [B][H][W][3] with rows dst_row_stride bytes apart; the _nhwc form also writes
-// the K16 normalisation of the rounded bytes, [B][H][W][Cpad] in RGB order, as u8bgr_to_nhwc_launch would
-// (the host-side argument check of both, for a caller that must refuse before it starts a capture)
-int crop_resize_cubic_check(int B, int src_h, int src_w, int x1, int y1, int cw, int ch, int H, int W, long dst_row_stride);
-int crop_resize_cubic_u8_launch(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch,
-                                uint8_t* dst, int H, int W, long dst_row_stride, hipStream_t stream);
-int crop_resize_cubic_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw,
-                                     int ch, uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
-                                     const float mean255[3], const float std255[3], hipStream_t stream);
-// the antialiased form of the three above (Pillow's bicubic: the window widens with the scale; include/d3f_hip.h:
-// d3f_crop_resize_cubic_aa_u8); refuses what they refuse and a crop above 32 times the output on an axis
-int crop_resize_cubic_aa_check(int B, int src_h, int src_w, int x1, int y1, int cw, int ch, int H, int W,
-                               long dst_row_stride);
-int crop_resize_cubic_aa_u8_launch(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch,
-                                   uint8_t* dst, int H, int W, long dst_row_stride, hipStream_t stream);
-int crop_resize_cubic_aa_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw,
-                                        int ch, uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
-                                        const float mean255[3], const float std255[3], hipStream_t stream);
-// full-frame output (resize.hip): patch [B][H][W][3], rows patch_row_stride bytes apart, resized to the box (x1, y1, cw, ch)
-// of frame [B][src_h][src_w][3] with the same arithmetic and blended in over a ramp of `feather` pixels; the rest of out
-// is the frame.  out == frame runs in place.  (_check: the host-side argument check, for a caller that must refuse
-// before it starts a capture)
-int paste_resize_cubic_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, int B, int H, int W,
-                             long patch_row_stride, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather);
-int paste_resize_cubic_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
-                                 int src_h, int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* out,
-                                 hipStream_t stream);
-// the colour form (include/d3f_hip.h: d3f_paste_resize_cubic_color_u8): the clamped patch value times coef[b][c][0] plus
-// coef[b][c][1], clamped again, in front of the blend; coef [B][3][2] fp32 in device memory.  The same kernel with one more
-// template parameter; refuses what the plain form refuses and a coef that overlaps out
-int paste_resize_cubic_color_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef, int B,
-                                   int H, int W, long patch_row_stride, int src_h, int src_w, int x1, int y1, int cw, int ch,
-                                   int feather);
-int paste_resize_cubic_color_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
-                                       const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch,
-                                       int feather, const float* coef, uint8_t* out, hipStream_t stream);
-// A box per frame (include/d3f_hip.h: the _boxes_ operators): each function above with (x1, y1, cw, ch) replaced by boxes,
+// script_tools frame path (resize.hip).  Crop: box (x1, y1, cw, ch) of uint8 BGR frames [B][src_h][src_w][3] -> bicubic
+// (cv2.INTER_CUBIC in float arithmetic) -> [B][H][W][3] with rows dst_row_stride bytes apart, optionally with the K16
+// normalisation of the rounded bytes, [B][H][W][Cpad] in RGB order, as u8bgr_to_nhwc_launch would write it.  The antialiased
+// form is Pillow's bicubic (the window widens with the scale; include/d3f_hip.h: d3f_crop_resize_cubic_aa_u8): it refuses
+// what the plain form refuses and a crop above 32 times the output on an axis.
+// Paste, the full-frame output: patch [B][H][W][3], rows patch_row_stride bytes apart, resized to the box of frame
+// [B][src_h][src_w][3] with the same arithmetic and blended in over a ramp of `feather` pixels; the rest of out is the
+// frame.  out == frame runs in place.  The colour form (include/d3f_hip.h: d3f_paste_resize_cubic_color_u8): the clamped
+// patch value times coef[b][c][0] plus coef[b][c][1], clamped again, in front of the blend; coef [B][3][2] fp32 in device
+// memory.  The same kernel with one more template parameter; refuses what the plain form refuses and a coef that overlaps out.
+// Both in three forms of the box -- one for the call, one per frame, one per frame and turned: CropCall and PasteCall below.
+// A box per frame (include/d3f_hip.h: the _boxes_ operators): crop and paste with (x1, y1, cw, ch) replaced by boxes,
 // HOST memory [B][4] as x1, y1, cw, ch, read before the call returns.  The boxes travel by value in the kernels' arguments,
 // FRAME_BOXES_MAX per launch; a longer call is several launches, in order.  Frame b is byte for byte the single-box call on
 // frame b with box b.  Refused before anything is launched: null boxes with B > 0, and for any frame what the single-box
@@ -222,36 +196,12 @@ __device__ __forceinline__ void frame_tile_row_copy(const uint8_t* p, uint8_t* q
     q[lx * 3 + 2] = p[lx * 3 + 2];
   }
 }
-int crop_resize_cubic_boxes_check(int B, int src_h, int src_w, const int32_t* boxes, int H, int W, long dst_row_stride);
-int crop_resize_cubic_boxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
-                                      int H, int W, long dst_row_stride, hipStream_t stream);
-int crop_resize_cubic_boxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
-                                           uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
-                                           const float mean255[3], const float std255[3], hipStream_t stream);
-int crop_resize_cubic_aa_boxes_check(int B, int src_h, int src_w, const int32_t* boxes, int H, int W, long dst_row_stride);
-int crop_resize_cubic_aa_boxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
-                                         int H, int W, long dst_row_stride, hipStream_t stream);
-int crop_resize_cubic_aa_boxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w,
-                                              const int32_t* boxes, uint8_t* dst, int H, int W, long dst_row_stride,
-                                              void* act, int Cpad, const float mean255[3], const float std255[3],
-                                              hipStream_t stream);
-int paste_resize_cubic_boxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, int B, int H, int W,
-                                   long patch_row_stride, int src_h, int src_w, const int32_t* boxes, int feather);
-int paste_resize_cubic_boxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
-                                       const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
-                                       uint8_t* out, hipStream_t stream);
-int paste_resize_cubic_color_boxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef,
-                                         int B, int H, int W, long patch_row_stride, int src_h, int src_w,
-                                         const int32_t* boxes, int feather);
-int paste_resize_cubic_color_boxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
-                                             const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
-                                             const float* coef, uint8_t* out, hipStream_t stream);
 
-// Rotated boxes (include/d3f_hip.h: the _rboxes_ operators; DESIGN.md section 4 "Rotated crop"): the _boxes_ functions with
-// one more table, rot: HOST memory [B][2] as c16 = round(cos a * 65536), s16 = round(sin a * 65536) of frame b's angle.  A
+// Rotated boxes (include/d3f_hip.h: the _rboxes_ operators; DESIGN.md section 4 "Rotated crop"): the boxes form with one
+// more table, rot: HOST memory [B][2] as c16 = round(cos a * 65536), s16 = round(sin a * 65536) of frame b's angle.  A
 // launch's table holds box and rotation per frame (1.5 KB by value, FRAME_BOXES_MAX frames); the kernels are forms of their
 // own (a sample's 4 x 4 neighbourhood sits per pixel, not per row and column), the 4 x 4 sum and the epilogues are shared.
-// Refused before anything is launched: what the _boxes_ functions refuse, a null rot, and for any frame a rot whose
+// Refused before anything is launched: what the boxes form refuses, a null rot, and for any frame a rot whose
 // c16^2 + s16^2 lies further than 2^17 from 2^32 (the message names the frame)
 struct alignas(8) FrameRot {
   int c16, s16;
@@ -260,20 +210,111 @@ struct FrameRBoxes {
   FrameBox box[FRAME_BOXES_MAX];
   FrameRot rot[FRAME_BOXES_MAX];
 };
-int crop_resize_cubic_rboxes_check(int B, int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int H, int W,
-                                   long dst_row_stride);
-int crop_resize_cubic_rboxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
-                                       const int32_t* rot, uint8_t* dst, int H, int W, long dst_row_stride, hipStream_t stream);
-int crop_resize_cubic_rboxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
-                                            const int32_t* rot, uint8_t* dst, int H, int W, long dst_row_stride, void* act,
-                                            int Cpad, const float mean255[3], const float std255[3], hipStream_t stream);
-// coef null: the plain form (_check: color says which form is meant)
-int paste_resize_cubic_rboxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef,
-                                    bool color, int B, int H, int W, long patch_row_stride, int src_h, int src_w,
-                                    const int32_t* boxes, const int32_t* rot, int feather);
-int paste_resize_cubic_rboxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
-                                        int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int feather,
-                                        const float* coef, bool color, uint8_t* out, hipStream_t stream);
+
+// Which box a frame takes.  A field of its own in the two descriptors: "a box per frame, and no table" is a refusal of the
+// _boxes_ and _rboxes_ operators (null boxes with B > 0; a null rot with any B) that the tables' pointers alone cannot tell
+// from the single-box call.
+enum FrameBoxForm {
+  FRAME_BOX_ONE,        // (x1, y1, cw, ch) for every frame; boxes and rot are ignored
+  FRAME_BOX_PER_FRAME,  // boxes: HOST memory [B][4] as x1, y1, cw, ch, read before the call returns; the four are ignored
+  FRAME_BOX_ROTATED,    // boxes and rot (HOST memory [B][2])
+};
+inline FrameBoxForm frame_box_form(const int32_t* boxes, const int32_t* rot) {
+  return rot ? FRAME_BOX_ROTATED : boxes ? FRAME_BOX_PER_FRAME : FRAME_BOX_ONE;
+}
+// One crop call and one paste call, in every form.  In the two per-frame forms frame b is byte for byte the single-box call on
+// frame b with box b; a call of more than FRAME_BOXES_MAX frames is several launches, in order.  _check is everything the
+// launch refuses, on the host (for a caller that must refuse before it starts a capture); the operator's name in a message
+// is the form's (crop_resize_cubic_aa_boxes: frame 2: ...).  B == 0 launches nothing.
+struct CropCall {
+  const uint8_t* src = nullptr;
+  int B = 0, src_h = 0, src_w = 0;
+  FrameBoxForm form = FRAME_BOX_ONE;
+  int x1 = 0, y1 = 0, cw = 0, ch = 0;
+  const int32_t* boxes = nullptr;
+  const int32_t* rot = nullptr;
+  bool antialias = false;  // (not with FRAME_BOX_ROTATED)
+  uint8_t* dst = nullptr;
+  int H = 0, W = 0;
+  long dst_row_stride = 0;
+  // the fused network input; act null: bytes only, and the four below are ignored
+  void* act = nullptr;
+  int dtype = D3F_F32, Cpad = 0;
+  const float* mean255 = nullptr;  // null: 0
+  const float* std255 = nullptr;   // null: 1
+};
+struct PasteCall {
+  const uint8_t* patch = nullptr;
+  int B = 0, H = 0, W = 0;
+  long patch_row_stride = 0;
+  const uint8_t* frame = nullptr;
+  int src_h = 0, src_w = 0;
+  FrameBoxForm form = FRAME_BOX_ONE;
+  int x1 = 0, y1 = 0, cw = 0, ch = 0;
+  const int32_t* boxes = nullptr;
+  const int32_t* rot = nullptr;
+  int feather = 0;
+  uint8_t* out = nullptr;
+  bool color = false;  // the colour form; a field of its own: the colour form with a null coef is refused
+  const float* coef = nullptr;
+};
+int crop_resize_check(const CropCall& c);
+int crop_resize_launch(const CropCall& c, hipStream_t stream);
+int paste_resize_check(const PasteCall& c);
+int paste_resize_launch(const PasteCall& c, hipStream_t stream);
+
+// A pointer of a call that advances with the frame: its first frame's address (null stays null) and its elements per frame.
+template <typename T>
+struct FramePtr {
+  T* p;
+  long per_frame;
+};
+// Cuts a call of B frames into chunks of at most `step`, in order: fn(b0, n, pointers advanced to frame b0...) for each; the
+// first non-zero answer ends the walk.  Every launch sequence of a per-frame form goes through here (step FRAME_BOXES_MAX),
+// and the single-box forms with their one launch (step B).
+template <class Fn, typename... T>
+int for_frame_chunks(int B, int step, Fn fn, FramePtr<T>... ptr) {
+  for (int b0 = 0; b0 < B; b0 += step) {
+    const int n = B - b0 < step ? B - b0 : step;
+    if (int rc = fn(b0, n, (ptr.p ? ptr.p + b0 * ptr.per_frame : nullptr)...)) return rc;
+  }
+  return 0;
+}
+// frames b0 .. b0 + n - 1 of a paste call as a call of their own (boxes and rot stay the call's: index them from b0)
+inline PasteCall paste_chunk(const PasteCall& c, int n, const uint8_t* patch, const uint8_t* frame, uint8_t* out,
+                             const float* coef) {
+  PasteCall k = c;
+  k.B = n;
+  k.patch = patch;
+  k.frame = frame;
+  k.out = out;
+  k.coef = coef;
+  return k;
+}
+// the largest box extents of a call's boxes [B][4] (checked by the caller); boxes null: the single box cw x ch
+inline void frame_boxes_max_extent(const int32_t* boxes, int B, int cw, int ch, int* cw_max, int* ch_max) {
+  *cw_max = cw;
+  *ch_max = ch;
+  if (!boxes) return;
+  *cw_max = *ch_max = 1;
+  for (int b = 0; b < B; ++b) {
+    *cw_max = *cw_max > boxes[4L * b + 2] ? *cw_max : boxes[4L * b + 2];
+    *ch_max = *ch_max > boxes[4L * b + 3] ? *ch_max : boxes[4L * b + 3];
+  }
+}
+// In place (out == frame) a paste launches only the tiles of the frame's tw x th grid that a box meets; with a box per frame
+// the grid is the most any frame needs, and the kernel derives each frame's first tile.  cover: a box's pixels
+// [px0, px1] x [py0, py1]
+struct InPlaceTiles {
+  int tw, th;
+  unsigned nx = 1, ny = 1;
+  void cover(int px0, int px1, int py0, int py1) {
+    const unsigned x = px1 / tw - px0 / tw + 1, y = py1 / th - py0 / th + 1;
+    nx = nx > x ? nx : x;
+    ny = ny > y ? ny : y;
+  }
+  void cover(const FrameBox& b) { cover(b.x1, b.x1 + b.cw - 1, b.y1, b.y1 + b.ch - 1); }
+};
 
 // Multiband paste (multiband.hip; include/d3f_hip.h: d3f_paste_multiband_u8 is the definition): the paste's byte at
 // feather 0 minus the frame's byte, as a Laplacian pyramid of `levels` levels in int16 planes of a caller's workspace, each
@@ -292,22 +333,14 @@ struct MultibandPlan {
 // the bytes of a workspace for B frames whose boxes are at most cw_max x ch_max; < 0 with the error set for levels outside
 // 1..MULTIBAND_MAX_LEVELS, B < 0 or a non-positive extent
 long paste_multiband_workspace_bytes(int B, int cw_max, int ch_max, int levels);
-// boxes null: the single box (x1, y1, cw, ch); otherwise HOST memory [B][4] and the four are ignored.  coef null: the plain
-// form; otherwise the colour form's coefficients [B][3][2].  _check: everything the launch refuses, for a caller that must
-// refuse before it starts a capture
-int paste_multiband_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef, bool color, int B,
-                          int H, int W, long patch_row_stride, int src_h, int src_w, int x1, int y1, int cw, int ch,
-                          const int32_t* boxes, int feather, int levels, const void* workspace, long workspace_bytes);
-int paste_multiband_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
-                              int src_h, int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes, int feather,
-                              int levels, const float* coef, bool color, void* workspace, long workspace_bytes, uint8_t* out,
-                              hipStream_t stream);
+// c: the paste call, in the single-box or the per-frame form, plain or colour (no rotated form).  _check: everything the
+// launch refuses, for a caller that must refuse before it starts a capture
+int paste_multiband_check(const PasteCall& c, int levels, const void* workspace, long workspace_bytes);
+int paste_multiband_u8_launch(const PasteCall& c, int levels, void* workspace, long workspace_bytes, hipStream_t stream);
 // the first launch of the sequence (resize.hip, next to the paste kernel whose arithmetic it shares): g_0 = (V - s) << 6 of
-// n frames into their slabs (frame b's first plane at g0 + b * 3 * slab_bytes, byte-in-pixel c's slab_bytes further on each).
-// boxes: null, or the call's table with this launch's frames from b0 (n <= FRAME_BOXES_MAX)
-int multiband_diff_launch(const uint8_t* patch, int n, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
-                          int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes, int b0, const float* coef,
-                          bool color, int16_t* g0, int pitch0, long slab_bytes, hipStream_t stream);
+// a chunk's frames into their slabs (frame b's first plane at g0 + b * 3 * slab_bytes, byte-in-pixel c's slab_bytes further
+// on each).  c: the chunk (paste_chunk), at most FRAME_BOXES_MAX frames in the per-frame form; its boxes from b0
+int multiband_diff_launch(const PasteCall& c, int b0, int16_t* g0, int pitch0, long slab_bytes, hipStream_t stream);
 
 // colour match (color.hip; include/d3f_hip.h: d3f_channel_sums_u8, d3f_color_match_coef).  Sums: per frame and byte-in-pixel
 // S = sum p, Q = sum p^2 as uint64 [B][3][2], exact; at most COLOR_MAX_PIXELS pixels per frame, so that n Q and S^2 stay

@@ -247,102 +247,74 @@ static PatchExtent resize_patch_extent(int n_h, int n_w, int out_h, int out_w) {
   const long cols = (long)(RESIZE_TW - 1) * n_w / out_w + 1 + 4, rows = (long)(RESIZE_TH - 1) * n_h / out_h + 1 + 4;
   return PatchExtent{rows, (cols * 3 + 3 + 3) / 4 * 4};
 }
-static long resize_lds_bytes(int n_h, int n_w, int out_h, int out_w, int* pitch_out) {
-  return resize_patch_extent(n_h, n_w, out_h, out_w).lds_bytes(pitch_out);
+
+// ---- host: what the launches of every form share (the entry points are at the end of the file) ----
+// the operator's name in a refusal: the call's form
+static const char* crop_op(const CropCall& c) {
+  if (c.form == FRAME_BOX_ROTATED) return "crop_resize_cubic_rboxes";
+  if (c.form == FRAME_BOX_PER_FRAME) return c.antialias ? "crop_resize_cubic_aa_boxes" : "crop_resize_cubic_boxes";
+  return c.antialias ? "crop_resize_cubic_aa" : "crop_resize_cubic";
 }
 
-// boxes null: the single-box launch with g0's box.  Otherwise frames b0 .. b0 + B - 1 of the table's call: one launch of at
-// most FRAME_BOXES_MAX frames (resize_boxes_launch cuts a call up)
-template <typename T, bool ACT, bool BOXES>
-static int resize_launch_one(const uint8_t* src, uint8_t* dst, T* act, const ResizeGeom& g0, const int32_t* boxes, int b0,
-                             int B, int Cpad, const float mean255[3], const float std255[3], hipStream_t stream) {
-  BoxedGeom<ResizeGeom, BOXES> a;
-  a.g = g0;
-  ResizeGeom& g = a.g;
-  long lds;
-  if constexpr (BOXES) {
-    fill_frame_boxes(a.boxes, boxes, b0, B);
-    PatchExtent e;
-    for (int i = 0; i < B; ++i) e.cover(resize_patch_extent(a.boxes.box[i].ch, a.boxes.box[i].cw, g.H, g.W));
-    lds = e.lds_bytes(&g.pitch);
-  } else {
-    lds = resize_lds_bytes(g.ch, g.cw, g.H, g.W, &g.pitch);
+// the crop kernels' mean and std arguments: null is 0 and 1
+struct Norm255 {
+  float m[3], s[3];
+  Norm255(const float* mean255, const float* std255) {
+    for (int i = 0; i < 3; ++i) {
+      m[i] = mean255 ? mean255[i] : 0.f;
+      s[i] = std255 ? std255[i] : 1.f;
+    }
   }
-  const bool staged = lds > 0;
-  const dim3 grid((g.W + RESIZE_TW - 1) / RESIZE_TW, (g.H + RESIZE_TH - 1) / RESIZE_TH, B), block(RESIZE_TW * RESIZE_TH);
-  const float z[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
-  const float* m = mean255 ? mean255 : z;
-  const float* s = std255 ? std255 : one;
-  if (staged)
-    hipLaunchKernelGGL((crop_resize_cubic_kernel<T, ACT, true, BOXES>), grid, block, (size_t)lds, stream, src, dst, act,
-                       a, Cpad, m[0], m[1], m[2], s[0], s[1], s[2]);
+};
+
+static dim3 tile_grid(int w, int h, int frames) {
+  return dim3((w + RESIZE_TW - 1) / RESIZE_TW, (h + RESIZE_TH - 1) / RESIZE_TH, frames);
+}
+
+// A kernel's STAGED instantiation with `lds` bytes of staged patch behind `fixed` bytes of LDS, or, lds == 0
+// (PatchExtent::lds_bytes: the patch does not fit), the instantiation that reads its taps from global memory
+template <typename... P, typename... A>
+static int launch_staged(void (*staged)(P...), void (*unstaged)(P...), dim3 grid, long lds, size_t fixed, hipStream_t stream,
+                         const A&... args) {
+  const dim3 block(RESIZE_TW * RESIZE_TH);
+  if (lds > 0)
+    hipLaunchKernelGGL(staged, grid, block, fixed + (size_t)lds, stream, args...);
   else
-    hipLaunchKernelGGL((crop_resize_cubic_kernel<T, ACT, false, BOXES>), grid, block, 0, stream, src, dst, act, a, Cpad,
-                       m[0], m[1], m[2], s[0], s[1], s[2]);
+    hipLaunchKernelGGL(unstaged, grid, block, fixed, stream, args...);
   D3F_HIP(hipGetLastError());
   return 0;
 }
 
-template <typename T, bool ACT>
-static int resize_launch(const uint8_t* src, uint8_t* dst, T* act, const ResizeGeom& g, int B, int Cpad,
-                         const float mean255[3], const float std255[3], hipStream_t stream) {
-  return resize_launch_one<T, ACT, false>(src, dst, act, g, nullptr, 0, B, Cpad, mean255, std255, stream);
-}
-
-// a call with a box per frame: launches of at most FRAME_BOXES_MAX frames each, in order
-template <typename T, bool ACT>
-static int resize_boxes_launch(const uint8_t* src, uint8_t* dst, T* act, const ResizeGeom& g, const int32_t* boxes, int B,
-                               int Cpad, const float mean255[3], const float std255[3], hipStream_t stream) {
-  const long frame_bytes = (long)g.src_h * g.src_w * 3, out_bytes = (long)g.H * g.dst_row_stride;
-  for (int b0 = 0; b0 < B; b0 += FRAME_BOXES_MAX) {
-    const int n = B - b0 < FRAME_BOXES_MAX ? B - b0 : FRAME_BOXES_MAX;
-    if (int rc = resize_launch_one<T, ACT, true>(src + b0 * frame_bytes, dst + b0 * out_bytes,
-                                                 ACT ? act + (long)b0 * g.H * g.W * Cpad : nullptr, g, boxes, b0, n, Cpad,
-                                                 mean255, std255, stream))
-      return rc;
+// The boxes one launch decides its LDS and its grid for: the table of a chunk's frames b0 .. b0 + n - 1, filled here from the
+// call's boxes, or the call's single box
+struct LaunchBoxes {
+  FrameBox one;
+  const FrameBox* box = &one;
+  int n = 1;
+  template <typename G, bool BOXES>
+  LaunchBoxes(BoxedGeom<G, BOXES>& a, const int32_t* boxes, int b0, int frames, FrameBox single) : one(single) {
+    if constexpr (BOXES) {
+      fill_frame_boxes(a.boxes, boxes, b0, frames);
+      box = a.boxes.box;
+      n = frames;
+    }
   }
-  return 0;
-}
+  LaunchBoxes(const LaunchBoxes&) = delete;
+};
 
-static int resize_geometry(ResizeGeom& g, int B, int src_h, int src_w, int x1, int y1, int cw, int ch, int H, int W,
-                           long dst_row_stride) {
-  D3F_CHECK(B >= 0 && src_h > 0 && src_w > 0 && cw > 0 && ch > 0 && H > 0 && W > 0,
-            "crop_resize_cubic: non-positive size (B %d, frame %dx%d, crop %dx%d, output %dx%d)", B, src_h, src_w, ch, cw,
-            H, W);
-  D3F_CHECK(x1 >= 0 && y1 >= 0 && (long)x1 + cw <= src_w && (long)y1 + ch <= src_h,
-            "crop_resize_cubic: crop box (x1 %d, y1 %d, %d x %d) outside the %d x %d frame", x1, y1, cw, ch, src_w, src_h);
-  D3F_CHECK(src_h <= RESIZE_MAX_EXTENT && src_w <= RESIZE_MAX_EXTENT && H <= RESIZE_MAX_EXTENT && W <= RESIZE_MAX_EXTENT,
-            "crop_resize_cubic: extents up to %d (32-bit source coordinates)", RESIZE_MAX_EXTENT);
-  D3F_CHECK(B <= 65535, "crop_resize_cubic: at most 65535 frames per call (B %d)", B);
-  D3F_CHECK(dst_row_stride >= 3L * W, "crop_resize_cubic: output row stride %ld below 3 * W = %ld bytes", dst_row_stride,
-            3L * W);
-  g = ResizeGeom{src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride, 0};
-  return 0;
-}
-
-int crop_resize_cubic_check(int B, int src_h, int src_w, int x1, int y1, int cw, int ch, int H, int W, long dst_row_stride) {
-  ResizeGeom g;
-  return resize_geometry(g, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride);
-}
-
-int crop_resize_cubic_u8_launch(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch,
-                                uint8_t* dst, int H, int W, long dst_row_stride, hipStream_t stream) {
-  ResizeGeom g;
-  if (int rc = resize_geometry(g, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride)) return rc;
-  if (B == 0) return 0;
-  return resize_launch<float, false>(src, dst, nullptr, g, B, 0, nullptr, nullptr, stream);
-}
-
-int crop_resize_cubic_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw,
-                                     int ch, uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
-                                     const float mean255[3], const float std255[3], hipStream_t stream) {
-  ResizeGeom g;
-  if (int rc = resize_geometry(g, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride)) return rc;
-  D3F_CHECK(Cpad >= 3, "crop_resize_cubic: activation of %d channels", Cpad);
-  if (B == 0) return 0;
-  if (dtype == D3F_F32)
-    return resize_launch<float, true>(src, dst, (float*)act, g, B, Cpad, mean255, std255, stream);
-  return resize_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, B, Cpad, mean255, std255, stream);
+// one launch of the plain crop: a single-box call, or a chunk of a per-frame call (c: its frames; its boxes from b0)
+template <typename T, bool ACT, bool BOXES>
+static int resize_launch_one(const CropCall& c, int b0, const Norm255& k, hipStream_t stream) {
+  BoxedGeom<ResizeGeom, BOXES> a;
+  ResizeGeom& g = a.g;
+  g = ResizeGeom{c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, c.H, c.W, c.dst_row_stride, 0};
+  const LaunchBoxes bx(a, c.boxes, b0, c.B, FrameBox{c.x1, c.y1, c.cw, c.ch});
+  PatchExtent e;
+  for (int i = 0; i < bx.n; ++i) e.cover(resize_patch_extent(bx.box[i].ch, bx.box[i].cw, g.H, g.W));
+  const long lds = e.lds_bytes(&g.pitch);
+  return launch_staged(crop_resize_cubic_kernel<T, ACT, true, BOXES>, crop_resize_cubic_kernel<T, ACT, false, BOXES>,
+                       tile_grid(g.W, g.H, c.B), lds, 0, stream, c.src, c.dst, (T*)c.act, a, c.Cpad, k.m[0], k.m[1], k.m[2],
+                       k.s[0], k.s[1], k.s[2]);
 }
 
 // What the single-box operators refuse of a box, for every frame of a boxes call, before anything is launched; the message
@@ -359,37 +331,6 @@ static int frame_boxes_check(const char* op, const int32_t* boxes, int B, int sr
               aa_H);
   }
   return 0;
-}
-
-// the geometry of a boxes call: everything of resize_geometry that is not the box (checked with a box every frame has),
-// then every frame's box
-static int resize_boxes_geometry(ResizeGeom& g, int B, int src_h, int src_w, const int32_t* boxes, int H, int W,
-                                 long dst_row_stride) {
-  if (int rc = resize_geometry(g, B, src_h, src_w, 0, 0, 1, 1, H, W, dst_row_stride)) return rc;
-  return frame_boxes_check("crop_resize_cubic_boxes", boxes, B, src_h, src_w);
-}
-
-int crop_resize_cubic_boxes_check(int B, int src_h, int src_w, const int32_t* boxes, int H, int W, long dst_row_stride) {
-  ResizeGeom g;
-  return resize_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride);
-}
-
-int crop_resize_cubic_boxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
-                                      int H, int W, long dst_row_stride, hipStream_t stream) {
-  ResizeGeom g;
-  if (int rc = resize_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride)) return rc;
-  return resize_boxes_launch<float, false>(src, dst, nullptr, g, boxes, B, 0, nullptr, nullptr, stream);
-}
-
-int crop_resize_cubic_boxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
-                                           uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
-                                           const float mean255[3], const float std255[3], hipStream_t stream) {
-  ResizeGeom g;
-  if (int rc = resize_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride)) return rc;
-  D3F_CHECK(Cpad >= 3, "crop_resize_cubic_boxes: activation of %d channels", Cpad);
-  if (dtype == D3F_F32)
-    return resize_boxes_launch<float, true>(src, dst, (float*)act, g, boxes, B, Cpad, mean255, std255, stream);
-  return resize_boxes_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, boxes, B, Cpad, mean255, std255, stream);
 }
 
 // ---- antialiased form: Pillow's bicubic (torch's interpolate(mode="bicubic", antialias=True)) ----
@@ -571,7 +512,7 @@ static size_t aa_lds_bytes(const AaGeom& g) {
   return (floats + 2 * RESIZE_TW + 2 * RESIZE_TH) * 4 + (size_t)AA_ROWS * g.pitch;
 }
 
-// the table strides and the staged pitch of one box (aa_geometry), and of a launch: the most of its boxes
+// the table strides and the staged pitch of one box, and of a launch: the most of its boxes
 static void aa_strides(AaGeom& g, int cw, int ch) {
   const int ntx = aa_max_taps(cw, g.W) | 1, nty = aa_max_taps(ch, g.H) | 1;
   const int pitch = (aa_max_cols(cw, g.W) * 3 + 3 + 3) / 4 * 4;  // up to 3 bytes of dword alignment in front
@@ -580,118 +521,22 @@ static void aa_strides(AaGeom& g, int cw, int ch) {
   g.pitch = g.pitch > pitch ? g.pitch : pitch;
 }
 
-static int aa_geometry(AaGeom& g, int B, int src_h, int src_w, int x1, int y1, int cw, int ch, int H, int W,
-                       long dst_row_stride) {
-  ResizeGeom r;
-  if (int rc = resize_geometry(r, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride)) return rc;
-  D3F_CHECK((long)cw <= (long)AA_MAX_RATIO * W && (long)ch <= (long)AA_MAX_RATIO * H,
-            "crop_resize_cubic_aa: crop %d x %d above %d times the output %d x %d on an axis (at most %d taps per axis)", cw,
-            ch, AA_MAX_RATIO, W, H, 4 * AA_MAX_RATIO + 1);
-  g = AaGeom{src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride, 0, 0, 0};
-  aa_strides(g, cw, ch);
-  D3F_CHECK(aa_lds_bytes(g) <= (size_t)AA_LDS_LIMIT, "crop_resize_cubic_aa: %zu bytes of LDS", aa_lds_bytes(g));
-  return 0;
-}
-
-int crop_resize_cubic_aa_check(int B, int src_h, int src_w, int x1, int y1, int cw, int ch, int H, int W,
-                               long dst_row_stride) {
-  AaGeom g;
-  return aa_geometry(g, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride);
-}
-
-// boxes null: the single-box launch of g0.  Otherwise frames b0 .. b0 + B - 1 of the table's call, at most FRAME_BOXES_MAX
+// one launch of the antialiased crop: a single-box call, or a chunk of a per-frame call (c: its frames; its boxes from b0).
+// (The LDS of a launch -- its boxes' largest strides together -- stays below AA_LDS_LIMIT whatever the boxes: at the ratio
+// limit on both axes it is 52 KB.)
 template <typename T, bool ACT, bool BOXES>
-static int aa_launch_one(const uint8_t* src, uint8_t* dst, T* act, const AaGeom& g0, const int32_t* boxes, int b0, int B,
-                         int Cpad, const float mean255[3], const float std255[3], hipStream_t stream) {
+static int aa_launch_one(const CropCall& c, int b0, const Norm255& k, hipStream_t stream) {
   BoxedGeom<AaGeom, BOXES> a;
-  a.g = g0;
   AaGeom& g = a.g;
-  if constexpr (BOXES) {
-    fill_frame_boxes(a.boxes, boxes, b0, B);
-    g.ntx = g.nty = g.pitch = 0;
-    for (int i = 0; i < B; ++i) aa_strides(g, a.boxes.box[i].cw, a.boxes.box[i].ch);
-    D3F_CHECK(aa_lds_bytes(g) <= (size_t)AA_LDS_LIMIT, "crop_resize_cubic_aa_boxes: %zu bytes of LDS", aa_lds_bytes(g));
-  }
-  const dim3 grid((g.W + RESIZE_TW - 1) / RESIZE_TW, (g.H + RESIZE_TH - 1) / RESIZE_TH, B), block(RESIZE_TW * RESIZE_TH);
-  const float z[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
-  const float* m = mean255 ? mean255 : z;
-  const float* s = std255 ? std255 : one;
-  hipLaunchKernelGGL((crop_resize_cubic_aa_kernel<T, ACT, BOXES>), grid, block, aa_lds_bytes(g), stream, src, dst, act, a,
-                     Cpad, m[0], m[1], m[2], s[0], s[1], s[2]);
+  g = AaGeom{c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, c.H, c.W, c.dst_row_stride, 0, 0, 0};
+  const LaunchBoxes bx(a, c.boxes, b0, c.B, FrameBox{c.x1, c.y1, c.cw, c.ch});
+  for (int i = 0; i < bx.n; ++i) aa_strides(g, bx.box[i].cw, bx.box[i].ch);
+  D3F_CHECK(aa_lds_bytes(g) <= (size_t)AA_LDS_LIMIT, "%s: %zu bytes of LDS", crop_op(c), aa_lds_bytes(g));
+  hipLaunchKernelGGL((crop_resize_cubic_aa_kernel<T, ACT, BOXES>), tile_grid(g.W, g.H, c.B), dim3(RESIZE_TW * RESIZE_TH),
+                     aa_lds_bytes(g), stream, c.src, c.dst, (T*)c.act, a, c.Cpad, k.m[0], k.m[1], k.m[2], k.s[0], k.s[1],
+                     k.s[2]);
   D3F_HIP(hipGetLastError());
   return 0;
-}
-
-template <typename T, bool ACT>
-static int aa_launch(const uint8_t* src, uint8_t* dst, T* act, const AaGeom& g, int B, int Cpad, const float mean255[3],
-                     const float std255[3], hipStream_t stream) {
-  return aa_launch_one<T, ACT, false>(src, dst, act, g, nullptr, 0, B, Cpad, mean255, std255, stream);
-}
-
-// a call with a box per frame: launches of at most FRAME_BOXES_MAX frames each, in order
-template <typename T, bool ACT>
-static int aa_boxes_launch(const uint8_t* src, uint8_t* dst, T* act, const AaGeom& g, const int32_t* boxes, int B, int Cpad,
-                           const float mean255[3], const float std255[3], hipStream_t stream) {
-  const long frame_bytes = (long)g.src_h * g.src_w * 3, out_bytes = (long)g.H * g.dst_row_stride;
-  for (int b0 = 0; b0 < B; b0 += FRAME_BOXES_MAX) {
-    const int n = B - b0 < FRAME_BOXES_MAX ? B - b0 : FRAME_BOXES_MAX;
-    if (int rc = aa_launch_one<T, ACT, true>(src + b0 * frame_bytes, dst + b0 * out_bytes,
-                                             ACT ? act + (long)b0 * g.H * g.W * Cpad : nullptr, g, boxes, b0, n, Cpad,
-                                             mean255, std255, stream))
-      return rc;
-  }
-  return 0;
-}
-
-// the geometry of a boxes call: aa_geometry's checks with a box every frame has, then every frame's box.  (The LDS of a
-// launch -- its boxes' largest strides together -- stays below AA_LDS_LIMIT whatever the boxes: at the ratio limit on both
-// axes it is 52 KB.)
-static int aa_boxes_geometry(AaGeom& g, int B, int src_h, int src_w, const int32_t* boxes, int H, int W,
-                             long dst_row_stride) {
-  if (int rc = aa_geometry(g, B, src_h, src_w, 0, 0, 1, 1, H, W, dst_row_stride)) return rc;
-  return frame_boxes_check("crop_resize_cubic_aa_boxes", boxes, B, src_h, src_w, H, W);
-}
-
-int crop_resize_cubic_aa_boxes_check(int B, int src_h, int src_w, const int32_t* boxes, int H, int W, long dst_row_stride) {
-  AaGeom g;
-  return aa_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride);
-}
-
-int crop_resize_cubic_aa_boxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes, uint8_t* dst,
-                                         int H, int W, long dst_row_stride, hipStream_t stream) {
-  AaGeom g;
-  if (int rc = aa_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride)) return rc;
-  return aa_boxes_launch<float, false>(src, dst, nullptr, g, boxes, B, 0, nullptr, nullptr, stream);
-}
-
-int crop_resize_cubic_aa_boxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w,
-                                              const int32_t* boxes, uint8_t* dst, int H, int W, long dst_row_stride,
-                                              void* act, int Cpad, const float mean255[3], const float std255[3],
-                                              hipStream_t stream) {
-  AaGeom g;
-  if (int rc = aa_boxes_geometry(g, B, src_h, src_w, boxes, H, W, dst_row_stride)) return rc;
-  D3F_CHECK(Cpad >= 3, "crop_resize_cubic_aa_boxes: activation of %d channels", Cpad);
-  if (dtype == D3F_F32) return aa_boxes_launch<float, true>(src, dst, (float*)act, g, boxes, B, Cpad, mean255, std255, stream);
-  return aa_boxes_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, boxes, B, Cpad, mean255, std255, stream);
-}
-
-int crop_resize_cubic_aa_u8_launch(const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw, int ch,
-                                   uint8_t* dst, int H, int W, long dst_row_stride, hipStream_t stream) {
-  AaGeom g;
-  if (int rc = aa_geometry(g, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride)) return rc;
-  if (B == 0) return 0;
-  return aa_launch<float, false>(src, dst, nullptr, g, B, 0, nullptr, nullptr, stream);
-}
-
-int crop_resize_cubic_aa_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, int x1, int y1, int cw,
-                                        int ch, uint8_t* dst, int H, int W, long dst_row_stride, void* act, int Cpad,
-                                        const float mean255[3], const float std255[3], hipStream_t stream) {
-  AaGeom g;
-  if (int rc = aa_geometry(g, B, src_h, src_w, x1, y1, cw, ch, H, W, dst_row_stride)) return rc;
-  D3F_CHECK(Cpad >= 3, "crop_resize_cubic_aa: activation of %d channels", Cpad);
-  if (B == 0) return 0;
-  if (dtype == D3F_F32) return aa_launch<float, true>(src, dst, (float*)act, g, B, Cpad, mean255, std255, stream);
-  return aa_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, B, Cpad, mean255, std255, stream);
 }
 
 // ---- full-frame output: the inverse of crop_resize_cubic (the plain form) with a blend in the epilogue ----
@@ -811,167 +656,42 @@ __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void paste_resize_cubic_kern
   paste_blend<COLOR>(v, ay * ax, f + at, o + at, args, b);
 }
 
-int paste_resize_cubic_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, int B, int H, int W,
-                             long patch_row_stride, int src_h, int src_w, int x1, int y1, int cw, int ch, int feather) {
-  D3F_CHECK(B >= 0 && B <= 65535, "paste_resize_cubic: B %d outside 0..65535 frames per call", B);
-  D3F_CHECK(src_h > 0 && src_w > 0 && cw > 0 && ch > 0 && H > 0 && W > 0,
-            "paste_resize_cubic: non-positive size (frame %dx%d, box %dx%d, patch %dx%d)", src_h, src_w, ch, cw, H, W);
-  D3F_CHECK(x1 >= 0 && y1 >= 0 && (long)x1 + cw <= src_w && (long)y1 + ch <= src_h,
-            "paste_resize_cubic: box (x1 %d, y1 %d, %d x %d) outside the %d x %d frame", x1, y1, cw, ch, src_w, src_h);
-  D3F_CHECK(src_h <= RESIZE_MAX_EXTENT && src_w <= RESIZE_MAX_EXTENT && H <= RESIZE_MAX_EXTENT && W <= RESIZE_MAX_EXTENT,
-            "paste_resize_cubic: extents up to %d (32-bit source coordinates)", RESIZE_MAX_EXTENT);
-  D3F_CHECK(feather >= 0 && feather <= RESIZE_MAX_EXTENT, "paste_resize_cubic: feather %d outside 0..%d", feather,
-            RESIZE_MAX_EXTENT);
-  D3F_CHECK(patch_row_stride >= 3L * W, "paste_resize_cubic: patch row stride %ld below 3 * W = %ld bytes",
-            patch_row_stride, 3L * W);
-  const long bytes = (long)B * src_h * src_w * 3;
-  D3F_CHECK(frame == out || out + bytes <= frame || frame + bytes <= out,
-            "paste_resize_cubic: frame and out overlap in part (out == frame runs in place)");
-  // other workgroups write out while a tile stages its part of the patch: the patches' bytes must lie outside out
-  const long patch_bytes = B > 0 ? ((long)B * H - 1) * patch_row_stride + 3L * W : 0;
-  D3F_CHECK(patch_bytes == 0 || patch + patch_bytes <= out || out + bytes <= patch,
-            "paste_resize_cubic: patch overlaps out");
-  return 0;
+// color -> COLOR and the form -> BOXES as types, for the paste kernels and the multiband difference: fn(COLOR, BOXES)
+template <class Fn>
+static int paste_forms(const PasteCall& c, Fn fn) {
+  using T = std::true_type;
+  using F = std::false_type;
+  if (c.form != FRAME_BOX_ONE) return c.color ? fn(T{}, T{}) : fn(F{}, T{});
+  return c.color ? fn(T{}, F{}) : fn(F{}, F{});
 }
 
-int paste_resize_cubic_color_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef, int B,
-                                   int H, int W, long patch_row_stride, int src_h, int src_w, int x1, int y1, int cw, int ch,
-                                   int feather) {
-  if (int rc = paste_resize_cubic_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather))
-    return rc;
-  D3F_CHECK(coef != nullptr, "paste_resize_cubic_color: null coef");
-  // a tile reads its frame's coefficients while other tiles write out
-  const long bytes = (long)B * src_h * src_w * 3, coef_bytes = (long)B * 6 * sizeof(float);
-  const uint8_t* cb = reinterpret_cast<const uint8_t*>(coef);
-  D3F_CHECK(cb + coef_bytes <= out || out + bytes <= cb, "paste_resize_cubic_color: coef overlaps out");
-  return 0;
-}
-
-// one launch of both forms; coef is read by the colour form only.  boxes null: the single box (x1, y1, cw, ch).  Otherwise
-// frames b0 .. b0 + B - 1 of the table's call, at most FRAME_BOXES_MAX (patch, frame, out and coef are those frames')
+// one launch of the paste, plain or colour: a single-box call, or a chunk of a per-frame call (c: its frames; its boxes from
+// b0).  coef is read by the colour form only
 template <bool COLOR, bool BOXES>
-static int paste_launch_one(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
-                            int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes, int b0, int feather,
-                            const float* coef, uint8_t* out, hipStream_t stream) {
+static int paste_launch_one(const PasteCall& c, int b0, hipStream_t stream) {
   PasteArgs<COLOR, BOXES> args;
   PasteGeom& g = args.geo.g;
-  g = PasteGeom{H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather, 0, 0, 0};
-  if constexpr (COLOR) args.coef = coef;
-  dim3 grid((src_w + RESIZE_TW - 1) / RESIZE_TW, (src_h + RESIZE_TH - 1) / RESIZE_TH, B);
-  long lds;
-  if constexpr (BOXES) {
-    fill_frame_boxes(args.geo.boxes, boxes, b0, B);
-    PatchExtent e;
-    unsigned tiles_x = 1, tiles_y = 1;  // in place: the most tiles any frame's box meets
-    for (int i = 0; i < B; ++i) {
-      const FrameBox& bx = args.geo.boxes.box[i];
-      e.cover(resize_patch_extent(H, W, bx.ch, bx.cw));
-      const unsigned nx = (bx.x1 + bx.cw - 1) / RESIZE_TW - bx.x1 / RESIZE_TW + 1;
-      const unsigned ny = (bx.y1 + bx.ch - 1) / RESIZE_TH - bx.y1 / RESIZE_TH + 1;
-      tiles_x = tiles_x > nx ? tiles_x : nx;
-      tiles_y = tiles_y > ny ? tiles_y : ny;
-    }
-    lds = e.lds_bytes(&g.pitch);
-    if (frame == out) {  // (the kernel derives each frame's tx0, ty0)
-      grid.x = tiles_x;
-      grid.y = tiles_y;
-    }
-  } else {
-    lds = resize_lds_bytes(H, W, ch, cw, &g.pitch);
-    if (frame == out) {  // in place: the tiles that meet the box
-      g.tx0 = x1 / RESIZE_TW;
-      g.ty0 = y1 / RESIZE_TH;
-      grid.x = (x1 + cw - 1) / RESIZE_TW - g.tx0 + 1;
-      grid.y = (y1 + ch - 1) / RESIZE_TH - g.ty0 + 1;
+  g = PasteGeom{c.H, c.W, c.patch_row_stride, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, c.feather, 0, 0, 0};
+  if constexpr (COLOR) args.coef = c.coef;
+  const LaunchBoxes bx(args.geo, c.boxes, b0, c.B, FrameBox{c.x1, c.y1, c.cw, c.ch});
+  PatchExtent e;
+  InPlaceTiles tiles{RESIZE_TW, RESIZE_TH};
+  for (int i = 0; i < bx.n; ++i) {
+    e.cover(resize_patch_extent(c.H, c.W, bx.box[i].ch, bx.box[i].cw));
+    tiles.cover(bx.box[i]);
+  }
+  const long lds = e.lds_bytes(&g.pitch);
+  dim3 grid = tile_grid(c.src_w, c.src_h, c.B);
+  if (c.frame == c.out) {  // in place: the tiles that meet a box (BOXES: the kernel derives each frame's tx0, ty0)
+    grid.x = tiles.nx;
+    grid.y = tiles.ny;
+    if constexpr (!BOXES) {
+      g.tx0 = c.x1 / RESIZE_TW;
+      g.ty0 = c.y1 / RESIZE_TH;
     }
   }
-  const dim3 block(RESIZE_TW * RESIZE_TH);
-  if (lds > 0)
-    hipLaunchKernelGGL((paste_resize_cubic_kernel<true, COLOR, BOXES>), grid, block, (size_t)lds, stream, patch, frame, out,
-                       args);
-  else
-    hipLaunchKernelGGL((paste_resize_cubic_kernel<false, COLOR, BOXES>), grid, block, 0, stream, patch, frame, out, args);
-  D3F_HIP(hipGetLastError());
-  return 0;
-}
-
-template <bool COLOR>
-static int paste_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
-                        int src_w, int x1, int y1, int cw, int ch, int feather, const float* coef, uint8_t* out,
-                        hipStream_t stream) {
-  return paste_launch_one<COLOR, false>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, x1, y1, cw, ch, nullptr, 0,
-                                        feather, coef, out, stream);
-}
-
-// a call with a box per frame: launches of at most FRAME_BOXES_MAX frames each, in order
-template <bool COLOR>
-static int paste_boxes_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
-                              int src_h, int src_w, const int32_t* boxes, int feather, const float* coef, uint8_t* out,
-                              hipStream_t stream) {
-  const long frame_bytes = (long)src_h * src_w * 3, patch_bytes = (long)H * patch_row_stride;
-  for (int b0 = 0; b0 < B; b0 += FRAME_BOXES_MAX) {
-    const int n = B - b0 < FRAME_BOXES_MAX ? B - b0 : FRAME_BOXES_MAX;
-    if (int rc = paste_launch_one<COLOR, true>(patch + b0 * patch_bytes, n, H, W, patch_row_stride, frame + b0 * frame_bytes,
-                                               src_h, src_w, 0, 0, 0, 0, boxes, b0, feather, COLOR ? coef + 6L * b0 : nullptr,
-                                               out + b0 * frame_bytes, stream))
-      return rc;
-  }
-  return 0;
-}
-
-// the checks of a boxes call: the single-box operator's with a box every frame has, then every frame's box
-int paste_resize_cubic_boxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, int B, int H, int W,
-                                   long patch_row_stride, int src_h, int src_w, const int32_t* boxes, int feather) {
-  if (int rc = paste_resize_cubic_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, 0, 0, 1, 1, feather))
-    return rc;
-  return frame_boxes_check("paste_resize_cubic_boxes", boxes, B, src_h, src_w);
-}
-
-int paste_resize_cubic_color_boxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef,
-                                         int B, int H, int W, long patch_row_stride, int src_h, int src_w,
-                                         const int32_t* boxes, int feather) {
-  if (int rc = paste_resize_cubic_color_check(patch, frame, out, coef, B, H, W, patch_row_stride, src_h, src_w, 0, 0, 1, 1,
-                                              feather))
-    return rc;
-  return frame_boxes_check("paste_resize_cubic_color_boxes", boxes, B, src_h, src_w);
-}
-
-int paste_resize_cubic_boxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
-                                       const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
-                                       uint8_t* out, hipStream_t stream) {
-  if (int rc = paste_resize_cubic_boxes_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, boxes, feather))
-    return rc;
-  return paste_boxes_launch<false>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, boxes, feather, nullptr, out,
-                                   stream);
-}
-
-int paste_resize_cubic_color_boxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
-                                             const uint8_t* frame, int src_h, int src_w, const int32_t* boxes, int feather,
-                                             const float* coef, uint8_t* out, hipStream_t stream) {
-  if (int rc = paste_resize_cubic_color_boxes_check(patch, frame, out, coef, B, H, W, patch_row_stride, src_h, src_w, boxes,
-                                                    feather))
-    return rc;
-  return paste_boxes_launch<true>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, boxes, feather, coef, out, stream);
-}
-
-int paste_resize_cubic_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
-                                 int src_h, int src_w, int x1, int y1, int cw, int ch, int feather, uint8_t* out,
-                                 hipStream_t stream) {
-  if (int rc = paste_resize_cubic_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, feather))
-    return rc;
-  if (B == 0) return 0;
-  return paste_launch<false>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, x1, y1, cw, ch, feather, nullptr, out,
-                             stream);
-}
-
-int paste_resize_cubic_color_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride,
-                                       const uint8_t* frame, int src_h, int src_w, int x1, int y1, int cw, int ch,
-                                       int feather, const float* coef, uint8_t* out, hipStream_t stream) {
-  if (int rc = paste_resize_cubic_color_check(patch, frame, out, coef, B, H, W, patch_row_stride, src_h, src_w, x1, y1, cw,
-                                              ch, feather))
-    return rc;
-  if (B == 0) return 0;
-  return paste_launch<true>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, x1, y1, cw, ch, feather, coef, out, stream);
+  return launch_staged(paste_resize_cubic_kernel<true, COLOR, BOXES>, paste_resize_cubic_kernel<false, COLOR, BOXES>, grid, lds,
+                       0, stream, c.patch, c.frame, c.out, args);
 }
 
 // ---- multiband paste: the difference image (include/d3f_hip.h: d3f_paste_multiband_u8; the pyramid is multiband.hip) ----
@@ -1043,52 +763,28 @@ __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void multiband_diff_kernel(c
 }
 
 template <bool COLOR, bool BOXES>
-static int diff_launch_one(const uint8_t* patch, int n, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
-                           int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes, int b0, const float* coef,
-                           int16_t* g0, int pitch0, long slab_bytes, hipStream_t stream) {
+static int diff_launch_one(const PasteCall& c, int b0, int16_t* g0, int pitch0, long slab_bytes, hipStream_t stream) {
   BoxedGeom<DiffGeom, BOXES> a;
   DiffGeom& g = a.g;
-  g = DiffGeom{H, W, patch_row_stride, src_h, src_w, x1, y1, cw, ch, 0, pitch0, slab_bytes};
-  int cw_max = cw, ch_max = ch;
-  long lds;
-  if constexpr (BOXES) {
-    fill_frame_boxes(a.boxes, boxes, b0, n);
-    PatchExtent e;
-    cw_max = ch_max = 1;
-    for (int i = 0; i < n; ++i) {
-      const FrameBox& bx = a.boxes.box[i];
-      e.cover(resize_patch_extent(H, W, bx.ch, bx.cw));
-      cw_max = cw_max > bx.cw ? cw_max : bx.cw;
-      ch_max = ch_max > bx.ch ? ch_max : bx.ch;
-    }
-    lds = e.lds_bytes(&g.pitch);
-  } else {
-    lds = resize_lds_bytes(H, W, ch, cw, &g.pitch);
+  g = DiffGeom{c.H, c.W, c.patch_row_stride, c.src_h, c.src_w, c.x1, c.y1, c.cw, c.ch, 0, pitch0, slab_bytes};
+  const LaunchBoxes bx(a, c.boxes, b0, c.B, FrameBox{c.x1, c.y1, c.cw, c.ch});
+  PatchExtent e;
+  int cw_max = 1, ch_max = 1;
+  for (int i = 0; i < bx.n; ++i) {
+    e.cover(resize_patch_extent(c.H, c.W, bx.box[i].ch, bx.box[i].cw));
+    cw_max = cw_max > bx.box[i].cw ? cw_max : bx.box[i].cw;
+    ch_max = ch_max > bx.box[i].ch ? ch_max : bx.box[i].ch;
   }
-  const dim3 grid((cw_max + RESIZE_TW - 1) / RESIZE_TW, (ch_max + RESIZE_TH - 1) / RESIZE_TH, n), block(RESIZE_TW * RESIZE_TH);
-  if (lds > 0)
-    hipLaunchKernelGGL((multiband_diff_kernel<true, COLOR, BOXES>), grid, block, (size_t)(DIFF_TILE_BYTES + lds), stream, patch,
-                       frame, g0, coef, a);
-  else
-    hipLaunchKernelGGL((multiband_diff_kernel<false, COLOR, BOXES>), grid, block, (size_t)DIFF_TILE_BYTES, stream, patch, frame,
-                       g0, coef, a);
-  D3F_HIP(hipGetLastError());
-  return 0;
+  const long lds = e.lds_bytes(&g.pitch);
+  return launch_staged(multiband_diff_kernel<true, COLOR, BOXES>, multiband_diff_kernel<false, COLOR, BOXES>,
+                       tile_grid(cw_max, ch_max, c.B), lds, DIFF_TILE_BYTES, stream, c.patch, c.frame, g0, c.coef, a);
 }
 
 // (the caller, paste_multiband_u8_launch, has checked everything)
-int multiband_diff_launch(const uint8_t* patch, int n, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
-                          int src_w, int x1, int y1, int cw, int ch, const int32_t* boxes, int b0, const float* coef,
-                          bool color, int16_t* g0, int pitch0, long slab_bytes, hipStream_t stream) {
-  auto go = [&](auto COLOR, auto BOXES) {
-    return diff_launch_one<decltype(COLOR)::value, decltype(BOXES)::value>(patch, n, H, W, patch_row_stride, frame, src_h,
-                                                                           src_w, x1, y1, cw, ch, boxes, b0, coef, g0, pitch0,
-                                                                           slab_bytes, stream);
-  };
-  using T = std::true_type;
-  using F = std::false_type;
-  if (boxes) return color ? go(T{}, T{}) : go(F{}, T{});
-  return color ? go(T{}, F{}) : go(F{}, F{});
+int multiband_diff_launch(const PasteCall& c, int b0, int16_t* g0, int pitch0, long slab_bytes, hipStream_t stream) {
+  return paste_forms(c, [&](auto COLOR, auto BOXES) {
+    return diff_launch_one<decltype(COLOR)::value, decltype(BOXES)::value>(c, b0, g0, pitch0, slab_bytes, stream);
+  });
 }
 
 // ---- rotated boxes (include/d3f_hip.h: the _rboxes_ operators; DESIGN.md section 4 "Rotated crop") ----
@@ -1273,15 +969,15 @@ static void fill_frame_rboxes(FrameRBoxes& t, const int32_t* boxes, const int32_
   }
 }
 
-// frames b0 .. b0 + B - 1 of the call's tables: one launch of at most FRAME_BOXES_MAX frames
+// one launch of the rotated crop: a chunk of at most FRAME_BOXES_MAX frames (c: its frames; its boxes and rotations from b0)
 template <typename T, bool ACT>
-static int rot_crop_launch_one(const uint8_t* src, uint8_t* dst, T* act, RotCropArgs& a, const int32_t* boxes,
-                               const int32_t* rot, int b0, int B, int Cpad, const float mean255[3], const float std255[3],
-                               hipStream_t stream) {
+static int rot_crop_launch_one(const CropCall& c, int b0, const Norm255& k, hipStream_t stream) {
+  RotCropArgs a;
   RotCropGeom& g = a.g;
-  fill_frame_rboxes(a.t, boxes, rot, b0, B);
+  g = RotCropGeom{c.src_h, c.src_w, c.H, c.W, c.dst_row_stride, 0, 0};
+  fill_frame_rboxes(a.t, c.boxes, c.rot, b0, c.B);
   PatchExtent e;
-  for (int i = 0; i < B; ++i) {
+  for (int i = 0; i < c.B; ++i) {
     // a tile's footprint: (RESIZE_TW - 1) cw / W along the crop's columns and (RESIZE_TH - 1) ch / H along its rows, turned
     const long ac = labs64(a.t.rot[i].c16), as = labs64(a.t.rot[i].s16);
     const long du = (long)(RESIZE_TW - 1) * a.t.box[i].cw * g.H, dv = (long)(RESIZE_TH - 1) * a.t.box[i].ch * g.W;
@@ -1290,35 +986,9 @@ static int rot_crop_launch_one(const uint8_t* src, uint8_t* dst, T* act, RotCrop
   }
   const long lds = e.lds_bytes(&g.pitch);
   g.rows_max = (int)e.rows;
-  const dim3 grid((g.W + RESIZE_TW - 1) / RESIZE_TW, (g.H + RESIZE_TH - 1) / RESIZE_TH, B), block(RESIZE_TW * RESIZE_TH);
-  const float z[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
-  const float* m = mean255 ? mean255 : z;
-  const float* s = std255 ? std255 : one;
-  if (lds > 0)
-    hipLaunchKernelGGL((crop_resize_cubic_rot_kernel<T, ACT, true>), grid, block, (size_t)lds, stream, src, dst, act, a, Cpad,
-                       m[0], m[1], m[2], s[0], s[1], s[2]);
-  else
-    hipLaunchKernelGGL((crop_resize_cubic_rot_kernel<T, ACT, false>), grid, block, 0, stream, src, dst, act, a, Cpad, m[0],
-                       m[1], m[2], s[0], s[1], s[2]);
-  D3F_HIP(hipGetLastError());
-  return 0;
-}
-
-template <typename T, bool ACT>
-static int rot_crop_launch(const uint8_t* src, uint8_t* dst, T* act, const ResizeGeom& g, const int32_t* boxes,
-                           const int32_t* rot, int B, int Cpad, const float mean255[3], const float std255[3],
-                           hipStream_t stream) {
-  RotCropArgs a;
-  a.g = RotCropGeom{g.src_h, g.src_w, g.H, g.W, g.dst_row_stride, 0, 0};
-  const long frame_bytes = (long)g.src_h * g.src_w * 3, out_bytes = (long)g.H * g.dst_row_stride;
-  for (int b0 = 0; b0 < B; b0 += FRAME_BOXES_MAX) {
-    const int n = B - b0 < FRAME_BOXES_MAX ? B - b0 : FRAME_BOXES_MAX;
-    if (int rc = rot_crop_launch_one<T, ACT>(src + b0 * frame_bytes, dst + b0 * out_bytes,
-                                             ACT ? act + (long)b0 * g.H * g.W * Cpad : nullptr, a, boxes, rot, b0, n, Cpad,
-                                             mean255, std255, stream))
-      return rc;
-  }
-  return 0;
+  return launch_staged(crop_resize_cubic_rot_kernel<T, ACT, true>, crop_resize_cubic_rot_kernel<T, ACT, false>,
+                       tile_grid(g.W, g.H, c.B), lds, 0, stream, c.src, c.dst, (T*)c.act, a, c.Cpad, k.m[0], k.m[1], k.m[2],
+                       k.s[0], k.s[1], k.s[2]);
 }
 
 // every frame's rotation: null, or no rotation (a table that would scale)
@@ -1332,38 +1002,6 @@ static int frame_rot_check(const char* op, const int32_t* rot, int B) {
               "table would scale)", op, b, c, s);
   }
   return 0;
-}
-
-static int rot_crop_geometry(ResizeGeom& g, int B, int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int H, int W,
-                             long dst_row_stride) {
-  if (int rc = resize_geometry(g, B, src_h, src_w, 0, 0, 1, 1, H, W, dst_row_stride)) return rc;
-  if (int rc = frame_boxes_check("crop_resize_cubic_rboxes", boxes, B, src_h, src_w)) return rc;
-  return frame_rot_check("crop_resize_cubic_rboxes", rot, B);
-}
-
-int crop_resize_cubic_rboxes_check(int B, int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int H, int W,
-                                   long dst_row_stride) {
-  ResizeGeom g;
-  return rot_crop_geometry(g, B, src_h, src_w, boxes, rot, H, W, dst_row_stride);
-}
-
-int crop_resize_cubic_rboxes_u8_launch(const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
-                                       const int32_t* rot, uint8_t* dst, int H, int W, long dst_row_stride,
-                                       hipStream_t stream) {
-  ResizeGeom g;
-  if (int rc = rot_crop_geometry(g, B, src_h, src_w, boxes, rot, H, W, dst_row_stride)) return rc;
-  return rot_crop_launch<float, false>(src, dst, nullptr, g, boxes, rot, B, 0, nullptr, nullptr, stream);
-}
-
-int crop_resize_cubic_rboxes_u8_nhwc_launch(int dtype, const uint8_t* src, int B, int src_h, int src_w, const int32_t* boxes,
-                                            const int32_t* rot, uint8_t* dst, int H, int W, long dst_row_stride, void* act,
-                                            int Cpad, const float mean255[3], const float std255[3], hipStream_t stream) {
-  ResizeGeom g;
-  if (int rc = rot_crop_geometry(g, B, src_h, src_w, boxes, rot, H, W, dst_row_stride)) return rc;
-  D3F_CHECK(Cpad >= 3, "crop_resize_cubic_rboxes: activation of %d channels", Cpad);
-  if (dtype == D3F_F32)
-    return rot_crop_launch<float, true>(src, dst, (float*)act, g, boxes, rot, B, Cpad, mean255, std255, stream);
-  return rot_crop_launch<bf16_t, true>(src, dst, (bf16_t*)act, g, boxes, rot, B, Cpad, mean255, std255, stream);
 }
 
 // the paste of a rotated box: tiles on the FRAME's 32 x 8 grid, as the plain form's.  A tile that misses the rectangle's
@@ -1451,15 +1089,17 @@ __global__ __launch_bounds__(RESIZE_TW * RESIZE_TH) void paste_resize_cubic_rot_
   paste_blend<COLOR>(v, ay * ax, f + at, o + at, args, b);
 }
 
+// one launch of the rotated paste: a chunk of at most FRAME_BOXES_MAX frames (c: its frames; its boxes and rotations from b0)
 template <bool COLOR>
-static int rot_paste_launch_one(const uint8_t* patch, int B, const uint8_t* frame, RotPasteArgs<COLOR>& args,
-                                const int32_t* boxes, const int32_t* rot, int b0, uint8_t* out, hipStream_t stream) {
+static int rot_paste_launch_one(const PasteCall& c, int b0, hipStream_t stream) {
+  RotPasteArgs<COLOR> args;
   RotPasteGeom& g = args.g;
-  fill_frame_rboxes(args.t, boxes, rot, b0, B);
-  dim3 grid((g.src_w + RESIZE_TW - 1) / RESIZE_TW, (g.src_h + RESIZE_TH - 1) / RESIZE_TH, B);
+  g = RotPasteGeom{c.H, c.W, c.patch_row_stride, c.src_h, c.src_w, c.feather, 0, 0};
+  if constexpr (COLOR) args.coef = c.coef;
+  fill_frame_rboxes(args.t, c.boxes, c.rot, b0, c.B);
   PatchExtent e;
-  unsigned tiles_x = 1, tiles_y = 1;  // in place: the most tiles any frame's bounding box meets
-  for (int i = 0; i < B; ++i) {
+  InPlaceTiles tiles{RESIZE_TW, RESIZE_TH};  // in place: the most tiles any frame's bounding box meets
+  for (int i = 0; i < c.B; ++i) {
     const FrameBox& bx = args.t.box[i];
     // a tile's footprint in the box: 31 and 7 frame pixels, turned; in the patch: times W / cw and H / ch
     const long ac = labs64(args.t.rot[i].c16), as = labs64(args.t.rot[i].s16);
@@ -1468,62 +1108,145 @@ static int rot_paste_launch_one(const uint8_t* patch, int B, const uint8_t* fram
     e.cover(rot_patch_extent(xext, yext, g.H, g.W));
     int bx0, bx1, by0, by1;
     rot_bbox(RotBox{bx.x1, bx.y1, bx.cw, bx.ch, args.t.rot[i].c16, args.t.rot[i].s16}, g.src_h, g.src_w, bx0, bx1, by0, by1);
-    const unsigned nx = bx1 / RESIZE_TW - bx0 / RESIZE_TW + 1, ny = by1 / RESIZE_TH - by0 / RESIZE_TH + 1;
-    tiles_x = tiles_x > nx ? tiles_x : nx;
-    tiles_y = tiles_y > ny ? tiles_y : ny;
+    tiles.cover(bx0, bx1, by0, by1);
   }
   const long lds = e.lds_bytes(&g.pitch);
   g.rows_max = (int)e.rows;
-  if (frame == out) {  // (the kernel derives each frame's first tile)
-    grid.x = tiles_x;
-    grid.y = tiles_y;
+  dim3 grid = tile_grid(g.src_w, g.src_h, c.B);
+  if (c.frame == c.out) {  // (the kernel derives each frame's first tile)
+    grid.x = tiles.nx;
+    grid.y = tiles.ny;
   }
-  const dim3 block(RESIZE_TW * RESIZE_TH);
-  if (lds > 0)
-    hipLaunchKernelGGL((paste_resize_cubic_rot_kernel<true, COLOR>), grid, block, (size_t)lds, stream, patch, frame, out, args);
-  else
-    hipLaunchKernelGGL((paste_resize_cubic_rot_kernel<false, COLOR>), grid, block, 0, stream, patch, frame, out, args);
-  D3F_HIP(hipGetLastError());
+  return launch_staged(paste_resize_cubic_rot_kernel<true, COLOR>, paste_resize_cubic_rot_kernel<false, COLOR>, grid, lds, 0,
+                       stream, c.patch, c.frame, c.out, args);
+}
+
+// ---- the entry points: one check and one launch sequence for every form of the crop, and of the paste ----
+// A per-frame form is checked as the single-box call with a box every frame has (so that everything that is not the box is
+// refused in the single-box operator's words), then every frame's box, then every frame's rotation.
+int crop_resize_check(const CropCall& c) {
+  const bool one = c.form == FRAME_BOX_ONE;
+  const char* op = crop_op(c);
+  const int x1 = one ? c.x1 : 0, y1 = one ? c.y1 : 0, cw = one ? c.cw : 1, ch = one ? c.ch : 1;
+  D3F_CHECK(c.B >= 0 && c.src_h > 0 && c.src_w > 0 && cw > 0 && ch > 0 && c.H > 0 && c.W > 0,
+            "crop_resize_cubic: non-positive size (B %d, frame %dx%d, crop %dx%d, output %dx%d)", c.B, c.src_h, c.src_w, ch, cw,
+            c.H, c.W);
+  D3F_CHECK(x1 >= 0 && y1 >= 0 && (long)x1 + cw <= c.src_w && (long)y1 + ch <= c.src_h,
+            "crop_resize_cubic: crop box (x1 %d, y1 %d, %d x %d) outside the %d x %d frame", x1, y1, cw, ch, c.src_w, c.src_h);
+  D3F_CHECK(c.src_h <= RESIZE_MAX_EXTENT && c.src_w <= RESIZE_MAX_EXTENT && c.H <= RESIZE_MAX_EXTENT && c.W <= RESIZE_MAX_EXTENT,
+            "crop_resize_cubic: extents up to %d (32-bit source coordinates)", RESIZE_MAX_EXTENT);
+  D3F_CHECK(c.B <= 65535, "crop_resize_cubic: at most 65535 frames per call (B %d)", c.B);
+  D3F_CHECK(c.dst_row_stride >= 3L * c.W, "crop_resize_cubic: output row stride %ld below 3 * W = %ld bytes", c.dst_row_stride,
+            3L * c.W);
+  if (c.antialias && one) {
+    D3F_CHECK((long)cw <= (long)AA_MAX_RATIO * c.W && (long)ch <= (long)AA_MAX_RATIO * c.H,
+              "crop_resize_cubic_aa: crop %d x %d above %d times the output %d x %d on an axis (at most %d taps per axis)", cw,
+              ch, AA_MAX_RATIO, c.W, c.H, 4 * AA_MAX_RATIO + 1);
+    AaGeom g = {};
+    g.H = c.H;
+    g.W = c.W;
+    aa_strides(g, cw, ch);
+    D3F_CHECK(aa_lds_bytes(g) <= (size_t)AA_LDS_LIMIT, "crop_resize_cubic_aa: %zu bytes of LDS", aa_lds_bytes(g));
+  }
+  if (!one)
+    if (int rc = frame_boxes_check(op, c.boxes, c.B, c.src_h, c.src_w, c.antialias ? c.H : 0, c.antialias ? c.W : 0)) return rc;
+  if (c.form == FRAME_BOX_ROTATED) {
+    if (int rc = frame_rot_check(op, c.rot, c.B)) return rc;
+    D3F_CHECK(!c.antialias, "%s: the rotated crop has no antialiased form", op);
+  }
+  D3F_CHECK(!c.act || c.Cpad >= 3, "%s: activation of %d channels", op, c.Cpad);
   return 0;
 }
 
-template <bool COLOR>
-static int rot_paste_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame, int src_h,
-                            int src_w, const int32_t* boxes, const int32_t* rot, int feather, const float* coef, uint8_t* out,
-                            hipStream_t stream) {
-  RotPasteArgs<COLOR> args;
-  args.g = RotPasteGeom{H, W, patch_row_stride, src_h, src_w, feather, 0, 0};
-  const long frame_bytes = (long)src_h * src_w * 3, patch_bytes = (long)H * patch_row_stride;
-  for (int b0 = 0; b0 < B; b0 += FRAME_BOXES_MAX) {
-    const int n = B - b0 < FRAME_BOXES_MAX ? B - b0 : FRAME_BOXES_MAX;
-    if constexpr (COLOR) args.coef = coef + 6L * b0;
-    if (int rc = rot_paste_launch_one<COLOR>(patch + b0 * patch_bytes, n, frame + b0 * frame_bytes, args, boxes, rot, b0,
-                                             out + b0 * frame_bytes, stream))
-      return rc;
+int crop_resize_launch(const CropCall& c, hipStream_t stream) {
+  if (int rc = crop_resize_check(c)) return rc;
+  const bool one = c.form == FRAME_BOX_ONE;
+  const Norm255 k(c.mean255, c.std255);
+  const long frame_bytes = (long)c.src_h * c.src_w * 3, out_bytes = (long)c.H * c.dst_row_stride;
+  // dtype -> T and act -> ACT as types, then the form's launch for every chunk
+  auto go = [&](auto* type, auto ACT) {
+    using T = std::remove_pointer_t<decltype(type)>;
+    constexpr bool A = decltype(ACT)::value;
+    int (*launch_one)(const CropCall&, int, const Norm255&, hipStream_t) =
+        c.form == FRAME_BOX_ROTATED ? rot_crop_launch_one<T, A>
+        : c.antialias               ? (one ? aa_launch_one<T, A, false> : aa_launch_one<T, A, true>)
+                                    : (one ? resize_launch_one<T, A, false> : resize_launch_one<T, A, true>);
+    return for_frame_chunks(
+        c.B, one ? c.B : FRAME_BOXES_MAX,
+        [&](int b0, int n, const uint8_t* src, uint8_t* dst, T* act) {
+          CropCall chunk = c;
+          chunk.B = n;
+          chunk.src = src;
+          chunk.dst = dst;
+          chunk.act = act;
+          return launch_one(chunk, b0, k, stream);
+        },
+        FramePtr<const uint8_t>{c.src, frame_bytes}, FramePtr<uint8_t>{c.dst, out_bytes},
+        FramePtr<T>{(T*)c.act, (long)c.H * c.W * c.Cpad});
+  };
+  if (!c.act) return go((float*)nullptr, std::false_type{});
+  if (c.dtype == D3F_F32) return go((float*)nullptr, std::true_type{});
+  return go((bf16_t*)nullptr, std::true_type{});
+}
+
+static const char* paste_op(const PasteCall& c) {
+  if (c.form == FRAME_BOX_ROTATED) return c.color ? "paste_resize_cubic_color_rboxes" : "paste_resize_cubic_rboxes";
+  if (c.form == FRAME_BOX_PER_FRAME) return c.color ? "paste_resize_cubic_color_boxes" : "paste_resize_cubic_boxes";
+  return c.color ? "paste_resize_cubic_color" : "paste_resize_cubic";
+}
+
+int paste_resize_check(const PasteCall& c) {
+  const bool one = c.form == FRAME_BOX_ONE;
+  const char* op = paste_op(c);
+  const int x1 = one ? c.x1 : 0, y1 = one ? c.y1 : 0, cw = one ? c.cw : 1, ch = one ? c.ch : 1;
+  D3F_CHECK(c.B >= 0 && c.B <= 65535, "paste_resize_cubic: B %d outside 0..65535 frames per call", c.B);
+  D3F_CHECK(c.src_h > 0 && c.src_w > 0 && cw > 0 && ch > 0 && c.H > 0 && c.W > 0,
+            "paste_resize_cubic: non-positive size (frame %dx%d, box %dx%d, patch %dx%d)", c.src_h, c.src_w, ch, cw, c.H, c.W);
+  D3F_CHECK(x1 >= 0 && y1 >= 0 && (long)x1 + cw <= c.src_w && (long)y1 + ch <= c.src_h,
+            "paste_resize_cubic: box (x1 %d, y1 %d, %d x %d) outside the %d x %d frame", x1, y1, cw, ch, c.src_w, c.src_h);
+  D3F_CHECK(c.src_h <= RESIZE_MAX_EXTENT && c.src_w <= RESIZE_MAX_EXTENT && c.H <= RESIZE_MAX_EXTENT && c.W <= RESIZE_MAX_EXTENT,
+            "paste_resize_cubic: extents up to %d (32-bit source coordinates)", RESIZE_MAX_EXTENT);
+  D3F_CHECK(c.feather >= 0 && c.feather <= RESIZE_MAX_EXTENT, "paste_resize_cubic: feather %d outside 0..%d", c.feather,
+            RESIZE_MAX_EXTENT);
+  D3F_CHECK(c.patch_row_stride >= 3L * c.W, "paste_resize_cubic: patch row stride %ld below 3 * W = %ld bytes",
+            c.patch_row_stride, 3L * c.W);
+  const long bytes = (long)c.B * c.src_h * c.src_w * 3;
+  D3F_CHECK(c.frame == c.out || c.out + bytes <= c.frame || c.frame + bytes <= c.out,
+            "paste_resize_cubic: frame and out overlap in part (out == frame runs in place)");
+  // other workgroups write out while a tile stages its part of the patch: the patches' bytes must lie outside out
+  const long patch_bytes = c.B > 0 ? ((long)c.B * c.H - 1) * c.patch_row_stride + 3L * c.W : 0;
+  D3F_CHECK(patch_bytes == 0 || c.patch + patch_bytes <= c.out || c.out + bytes <= c.patch,
+            "paste_resize_cubic: patch overlaps out");
+  if (c.color) {
+    D3F_CHECK(c.coef != nullptr, "paste_resize_cubic_color: null coef");
+    // a tile reads its frame's coefficients while other tiles write out
+    const long coef_bytes = (long)c.B * 6 * sizeof(float);
+    const uint8_t* cb = reinterpret_cast<const uint8_t*>(c.coef);
+    D3F_CHECK(cb + coef_bytes <= c.out || c.out + bytes <= cb, "paste_resize_cubic_color: coef overlaps out");
   }
+  if (!one)
+    if (int rc = frame_boxes_check(op, c.boxes, c.B, c.src_h, c.src_w)) return rc;
+  if (c.form == FRAME_BOX_ROTATED) return frame_rot_check(op, c.rot, c.B);
   return 0;
 }
 
-int paste_resize_cubic_rboxes_check(const uint8_t* patch, const uint8_t* frame, const uint8_t* out, const float* coef,
-                                    bool color, int B, int H, int W, long patch_row_stride, int src_h, int src_w,
-                                    const int32_t* boxes, const int32_t* rot, int feather) {
-  const char* op = color ? "paste_resize_cubic_color_rboxes" : "paste_resize_cubic_rboxes";
-  if (int rc = color ? paste_resize_cubic_color_check(patch, frame, out, coef, B, H, W, patch_row_stride, src_h, src_w, 0, 0, 1,
-                                                      1, feather)
-                     : paste_resize_cubic_check(patch, frame, out, B, H, W, patch_row_stride, src_h, src_w, 0, 0, 1, 1, feather))
-    return rc;
-  if (int rc = frame_boxes_check(op, boxes, B, src_h, src_w)) return rc;
-  return frame_rot_check(op, rot, B);
+int paste_resize_launch(const PasteCall& c, hipStream_t stream) {
+  if (int rc = paste_resize_check(c)) return rc;
+  const bool one = c.form == FRAME_BOX_ONE;
+  const long frame_bytes = (long)c.src_h * c.src_w * 3, patch_bytes = (long)c.H * c.patch_row_stride;
+  return paste_forms(c, [&](auto COLOR, auto BOXES) {
+    constexpr bool C = decltype(COLOR)::value, BX = decltype(BOXES)::value;
+    int (*launch_one)(const PasteCall&, int, hipStream_t) =
+        c.form == FRAME_BOX_ROTATED ? rot_paste_launch_one<C> : paste_launch_one<C, BX>;
+    return for_frame_chunks(
+        c.B, one ? c.B : FRAME_BOXES_MAX,
+        [&](int b0, int n, const uint8_t* patch, const uint8_t* frame, uint8_t* out, const float* coef) {
+          return launch_one(paste_chunk(c, n, patch, frame, out, coef), b0, stream);
+        },
+        FramePtr<const uint8_t>{c.patch, patch_bytes}, FramePtr<const uint8_t>{c.frame, frame_bytes},
+        FramePtr<uint8_t>{c.out, frame_bytes}, FramePtr<const float>{C ? c.coef : nullptr, 6});
+  });
 }
 
-int paste_resize_cubic_rboxes_u8_launch(const uint8_t* patch, int B, int H, int W, long patch_row_stride, const uint8_t* frame,
-                                        int src_h, int src_w, const int32_t* boxes, const int32_t* rot, int feather,
-                                        const float* coef, bool color, uint8_t* out, hipStream_t stream) {
-  if (int rc = paste_resize_cubic_rboxes_check(patch, frame, out, coef, color, B, H, W, patch_row_stride, src_h, src_w, boxes,
-                                               rot, feather))
-    return rc;
-  if (color) return rot_paste_launch<true>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, boxes, rot, feather, coef, out, stream);
-  return rot_paste_launch<false>(patch, B, H, W, patch_row_stride, frame, src_h, src_w, boxes, rot, feather, nullptr, out, stream);
-}
 
 }  // namespace d3f

@@ -18,7 +18,7 @@ RESIZE_LDS_BYTES, TW, TH = 32 * 1024, 32, 8
 
 
 def _patch_extent(n_h, n_w, out_h, out_w):
-    """resize_lds_bytes' formula (csrc/resize.hip): rows and pitch of the largest staged part of a tile"""
+    """resize_patch_extent's formula (csrc/resize.hip): rows and pitch of the largest staged part of a tile"""
     cols, rows = (TW - 1) * n_w // out_w + 1 + 4, (TH - 1) * n_h // out_h + 1 + 4
     return rows, (cols * 3 + 3 + 3) // 4 * 4
 

@@ -125,6 +125,47 @@ def test_fused_activation_form_equals_the_u8_form_then_the_normalisation(dtype):
     assert torch.equal(fused(mean, std).cpu(), expect)
 
 
+def _moving_boxes(B, hw=(24, 32)):
+    """a box and an angle per frame, drawn as the 70-frame test draws them"""
+    rng = np.random.default_rng(922)
+    boxes, angles = [], []
+    for b in range(B):
+        cw, ch = int(rng.integers(6, 20)), int(rng.integers(6, 20))
+        boxes.append((int(rng.integers(0, hw[1] - cw + 1)), int(rng.integers(0, hw[0] - ch + 1)), cw, ch))
+        angles.append(float(rng.integers(-17999, 18001)) / 100.0)
+    return boxes, angles
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_fused_activation_form_behind_the_first_launch_of_a_call(dtype):
+    """65 frames are two launches: frame 64 is the second one's first, where the source, the bytes and the activation have
+    each advanced by 64 frames.  It equals the call on frame 64 alone with box 64, and not the one with box 0."""
+    from denoising_diffusion_deep_fake_amd import _lib, ops
+    B, hw, size, cpad = 65, (24, 32), (8, 8), 4
+    frames = _frames(920, B, hw)
+    boxes, angles = _moving_boxes(B)
+    tdt = torch.float32 if dtype == "f32" else torch.bfloat16
+    m, s = (C.c_float * 3)(0.4, 0.5, 0.6), (C.c_float * 3)(0.5, 0.45, 0.55)
+
+    def fused(fr, bx, an):
+        n = fr.shape[0]
+        dst = torch.zeros((n,) + size + (3,), dtype=torch.uint8, device="cuda")
+        act = torch.full((n,) + size + (cpad,), 3.0, dtype=tdt, device="cuda")
+        table, _ = ops._boxes_arg(bx, n, "test")
+        _lib.check(_lib.lib().d3f_crop_resize_cubic_rboxes_u8_nhwc(_lib.F32 if dtype == "f32" else _lib.BF16, _lib.ptr(fr), n,
+                                                                   hw[0], hw[1], table, ops._rot_arg(an, n, "test"),
+                                                                   _lib.ptr(dst), size[0], size[1], 3 * size[1], _lib.ptr(act),
+                                                                   cpad, m, s, _lib.stream_ptr()))
+        return dst, act
+
+    dst, act = fused(frames, boxes, angles)
+    last = frames[64:].contiguous()
+    dst_own, act_own = fused(last, boxes[64:], angles[64:])
+    assert torch.equal(dst[64:], dst_own) and torch.equal(act[64:], act_own)
+    dst_first, act_first = fused(last, boxes[:1], angles[:1])
+    assert not torch.equal(dst[64:], dst_first) and not torch.equal(act[64:], act_first)
+
+
 @pytest.mark.parametrize("angle, k", [(90.0, 1), (180.0, 2), (270.0, 3), (-90.0, 3)])
 def test_quarter_turns_are_rot90_of_the_axis_aligned_kernel_s_crop(angle, k):
     """cw = 2 W, ch = 2 H, a square box: every t is 0.5, all weights and sums are dyadic, so fp32 is exact in either pass
