@@ -58,6 +58,8 @@ TEMPORAL_STRENGTH, TEMPORAL_THRESHOLD = 0.75, 8  # D3F_TEMPORAL_*: design choice
 TRACK_MAX_SIDE, TRACK_MAX_SEARCH, TRACK_MAX_STRIDE, TRACK_MIN_SIDE = 64, 64, 32, 4
 TRACK_TEMPLATE_SIDE, TRACK_SEARCH, TRACK_ADAPT, TRACK_LOST = 48, 16, 1, 16
 TRACK_SCALE_PENALTY, TRACK_MAX_SCALE_PENALTY = 512, 65535  # D3F_TRACK_SCALE_PENALTY, in 1/4096 grey levels
+# D3F_TRACK_ROT_*: the rotation search's step in hundredths of a degree, its range in degrees, its penalty, the largest index
+TRACK_ROT_STEP, TRACK_ROT_MAX, TRACK_ROT_PENALTY, TRACK_ROT_MAX_INDEX = 200, 60, 512, 64
 
 
 def temporal_setting(temporal, threshold=None):
@@ -231,6 +233,10 @@ PROTOTYPES = {
     "d3f_track_seed_scale_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "d3f_track_search_scale_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "d3f_track_template_scale_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    # table is HOST memory, [2 amax + 1][2] int32
+    "d3f_track_seed_rot_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "d3f_track_search_rot_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i32p, _p, _p, _p, _p]),
+    "d3f_track_template_rot_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i32p, _p, _p, _p, _p, _p]),
     "d3f_image_grid_shape": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
     "d3f_image_grid_u8": (_i, [C.POINTER(_p), _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _p, _p]),
     "d3f_unet_num_segments": (_i, [_p]),

@@ -1056,6 +1056,28 @@ int d3f_track_template_scale_u8(const uint8_t* frames, int B, int h, int w, int 
                                         out, (hipStream_t)stream);
 }
 
+int d3f_track_seed_rot_u8(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, int a0, int c16, int s16,
+                          uint8_t* templ, int32_t* pos, void* stream) {
+  D3F_CHECK(frame && templ && pos, "track_seed_rot_u8: null argument");
+  return track_seed_rot_u8_launch(frame, h, w, s, tx, ty, tw, th, a0, c16, s16, templ, pos, (hipStream_t)stream);
+}
+
+int d3f_track_search_rot_u8(const uint8_t* gray, int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost,
+                            int steps, int penalty, int amax, const int32_t* table, uint8_t* templ, int32_t* pos, int32_t* out,
+                            void* stream) {
+  D3F_CHECK(gray && templ && pos && out, "track_search_rot_u8: null argument");
+  return track_search_rot_u8_launch(gray, B, gh, gw, tw0, th0, search, adapt, lost, steps, penalty, amax, table, templ, pos, out,
+                                    (hipStream_t)stream);
+}
+
+int d3f_track_template_rot_u8(const uint8_t* frames, int B, int h, int w, int s, int tw0, int th0, int search, int adapt,
+                              int lost, int steps, int penalty, int amax, const int32_t* table, uint8_t* templ, int32_t* pos,
+                              uint8_t* gray_ws, int32_t* out, void* stream) {
+  D3F_CHECK(frames && templ && pos && gray_ws && out, "track_template_rot_u8: null argument");
+  return track_template_rot_u8_launch(frames, B, h, w, s, tw0, th0, search, adapt, lost, steps, penalty, amax, table, templ, pos,
+                                      gray_ws, out, (hipStream_t)stream);
+}
+
 int d3f_track_search_u8(const uint8_t* gray, int B, int gh, int gw, int tw, int th, int search, int adapt, int lost,
                         uint8_t* templ, int32_t* pos, int32_t* out, void* stream) {
   D3F_CHECK(gray && templ && pos && out, "track_search_u8: null argument");

@@ -394,6 +394,18 @@ int track_search_scale_u8_launch(const uint8_t* gray, int B, int gh, int gw, int
 int track_template_scale_u8_launch(const uint8_t* frames, int B, int h, int w, int s, int tw0, int th0, int search, int adapt,
                                    int lost, int levels, int penalty, uint8_t* templ, int* pos, uint8_t* gray_ws, int* out,
                                    hipStream_t stream);
+// the rotation search (d3f_track_search_rot_u8): templ is the upright tw0 x th0 template, pos int32[3] = x, y, angle index,
+// out int32 [B][8]; table is HOST memory, (c16, s16) of the angle indices -amax..amax, checked and then passed by value
+int track_seed_rot_u8_launch(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, int a0, int c16, int s16,
+                             uint8_t* templ, int* pos, hipStream_t stream);
+int track_search_rot_check(int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost, int steps, int penalty,
+                           int amax, const int* table, const int* pos, const int* out);
+int track_search_rot_u8_launch(const uint8_t* gray, int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost,
+                               int steps, int penalty, int amax, const int* table, uint8_t* templ, int* pos, int* out,
+                               hipStream_t stream);
+int track_template_rot_u8_launch(const uint8_t* frames, int B, int h, int w, int s, int tw0, int th0, int search, int adapt,
+                                 int lost, int steps, int penalty, int amax, const int* table, uint8_t* templ, int* pos,
+                                 uint8_t* gray_ws, int* out, hipStream_t stream);
 
 // training image grids (image_grid.hip): make_grid + scale + clamp + uint8 of up to 8 fp32 NCHW batches in one launch;
 // `batches` is a host array of n device pointers, out [n][GH][GW][3] with {GH, GW} from image_grid_shape

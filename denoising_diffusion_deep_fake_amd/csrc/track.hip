@@ -24,6 +24,10 @@
 //
 // track_search_scale_kernel (d3f_track_search_scale_u8, opt-in): the same search over the neighbouring sizes too; its own
 // comment stands in front of it, tests/track_scale_restatement.py restates it.
+//
+// track_search_rot_kernel and track_seed_rot_kernel (d3f_track_search_rot_u8, d3f_track_seed_rot_u8, opt-in): the same
+// search over the neighbouring angles of the box too, the cost on a disc; their comment stands in front of them,
+// tests/track_rot_restatement.py restates them.
 #include "../../include/d3f_hip.h"
 #include "common.h"
 #include "pointwise.h"
@@ -538,6 +542,252 @@ __global__ __launch_bounds__(TS_THREADS) void track_search_scale_kernel(const ui
   if (tid == 0) pos[0] = px, pos[1] = py, pos[2] = L;
 }
 
+// ---- the rotation search (include/d3f_hip.h: d3f_track_search_rot_u8; tests/track_rot_restatement.py) ----
+// track_search_rot_kernel keeps the shape of track_search_kernel: ONE workgroup, the loop over the call's frames inside,
+// the position and the angle index uniform for the workgroup (read back from the reduced key through readfirstlane, so
+// they stay in scalar registers).  The state's template T0 is the upright face, tw0 x th0, in LDS for the call; the cost is
+// taken on the disc of diameter min(tw0, th0) about the box's centre, which a rotation maps onto itself, every row of it one
+// span (lo, n).  Per frame T0 is turned to the (up to three) candidate angles -- row j of a turned template holds the
+// span's n(j) samples left-aligned, zero behind them, rows RS_TPITCH_DW dwords apart: the odd pitch puts the rows that the
+// parts of a group read at once on different banks -- the window is staged as track_search_kernel stages it (the
+// candidates' boxes are the un-rotated ones, the same for every angle), and the candidates of all angles are spread over
+// the lanes as work items of four dx and a part of the rows.  A row's walk starts lo(j) bytes into the window's row and
+// takes n(j) >> 2 whole dwords and a masked tail.  The winner's window is turned back and blended into T0 on the disc.
+// The rotations arrive as a table of (c16, s16) per angle index BY VALUE in the kernel's arguments (the host has checked
+// every entry; the device does no trigonometry) and are copied to LDS once, where a lane indexes them.
+constexpr int RS_ANGLES = 3;                             // dA = -1, 0, 1
+constexpr int RS_MAX_INDEX = D3F_TRACK_ROT_MAX_INDEX;    // the angle indices are -amax..amax, amax at most this
+constexpr int RS_TABLE = 2 * RS_MAX_INDEX + 1;
+constexpr int RS_TPITCH_DW = TS_TDW + 1;                 // dwords between the rows of a turned template
+static_assert((TS_WMAX * TS_PITCH_DW + TRACK_MAX_SIDE * TS_TDW + RS_ANGLES * TRACK_MAX_SIDE * RS_TPITCH_DW + TRACK_MAX_SIDE +
+               2 * RS_TABLE) * 4 + TS_THREADS / 64 * 8 <= 64 * 1024,
+              "track_search_rot_kernel's static LDS");
+static_assert(RS_MAX_INDEX < 128 && TRACK_MAX_SIDE <= 64, "the angle index is a byte of the key's decode; a span is lo | n << 8");
+
+struct RotGeom {
+  int B, gh, gw, tw0, th0, R, adapt, lost, steps, penalty, amax;
+  FrameRot rot[RS_TABLE];  // index a + amax: the rotation by a * step
+};
+
+// the disc: sample (i, j) of tw0 x th0 belongs when u u + v v <= D D, u = 2 i + 1 - tw0, v = 2 j + 1 - th0, D = min(tw0, th0)
+__device__ __forceinline__ bool track_disc(int i, int j, int tw0, int th0) {
+  const int u = 2 * i + 1 - tw0, v = 2 * j + 1 - th0, D = min(tw0, th0);
+  return u * u + v * v <= D * D;
+}
+
+// Output sample (i, j) of rot(A, c, s): the position in A turned about the centre, in 1/131072 of a sample (below 2^24 in
+// magnitude: |u|, |v| < 64, |c|, |s| <= 65536), its two taps per axis clamped to the array and the 6-bit weights
+struct RotTap {
+  int x0, x1, y0, y1, fx, fy;
+};
+__device__ __forceinline__ RotTap track_rot_tap(int i, int j, int tw0, int th0, int c, int s) {
+  const int u = 2 * i + 1 - tw0, v = 2 * j + 1 - th0;
+  const int X = c * u + s * v + (tw0 - 1) * 65536, Y = -s * u + c * v + (th0 - 1) * 65536;
+  const int x0 = X >> 17, y0 = Y >> 17;
+  return RotTap{min(max(x0, 0), tw0 - 1), min(max(x0 + 1, 0), tw0 - 1), min(max(y0, 0), th0 - 1), min(max(y0 + 1, 0), th0 - 1),
+                (X >> 11) & 63,          (Y >> 11) & 63};
+}
+
+// The seed with an angle: templ holds the grey of the axis-aligned key box (track_seed_kernel); on the disc it becomes that
+// grey turned back by the key angle, rot(grey, c, -s), and pos[2] the angle's index.  One workgroup: every read through LDS
+// before the first write.
+__global__ __launch_bounds__(TS_THREADS) void track_seed_rot_kernel(uint8_t* __restrict__ templ, int tw0, int th0, int a0, int c,
+                                                                   int s, int* __restrict__ pos) {
+  __shared__ uint8_t src[TRACK_MAX_SIDE * TRACK_MAX_SIDE];
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < tw0 * th0; idx += TS_THREADS) src[idx] = templ[idx];
+  if (tid == 0) pos[2] = a0;
+  __syncthreads();
+  for (int idx = tid; idx < tw0 * th0; idx += TS_THREADS) {
+    const int j = idx / tw0, i = idx - j * tw0;
+    if (!track_disc(i, j, tw0, th0)) continue;
+    const RotTap t = track_rot_tap(i, j, tw0, th0, c, -s);
+    const uint8_t* r0 = src + t.y0 * tw0;
+    const uint8_t* r1 = src + t.y1 * tw0;
+    templ[idx] = (uint8_t)track_bilinear(r0[t.x0], r0[t.x1], r1[t.x0], r1[t.x1], t.fx, t.fy);
+  }
+}
+
+__global__ __launch_bounds__(TS_THREADS) void track_search_rot_kernel(const uint8_t* __restrict__ gray, RotGeom g,
+                                                                     uint8_t* __restrict__ templ, int* __restrict__ pos,
+                                                                     int* __restrict__ out) {
+  __shared__ uint32_t win[TS_WMAX * TS_PITCH_DW];
+  __shared__ uint32_t t0[TRACK_MAX_SIDE * TS_TDW];                     // T0, rows 64 bytes apart
+  __shared__ uint32_t tl[RS_ANGLES * TRACK_MAX_SIDE * RS_TPITCH_DW];  // T(a + dA): a row's span left-aligned, zero behind it
+  __shared__ uint32_t span[TRACK_MAX_SIDE];                            // row j of the disc: lo | n << 8
+  __shared__ int tab[2 * RS_TABLE];                                    // (c16, s16) of index a at 2 (a + amax)
+  __shared__ u64 red[TS_THREADS / 64];
+  uint8_t* t0b = reinterpret_cast<uint8_t*>(t0);
+  const uint8_t* wb = reinterpret_cast<const uint8_t*>(win);
+  const int tid = threadIdx.x, tw0 = g.tw0, th0 = g.th0, R = g.R, amax = g.amax;
+  for (int i = tid; i < tw0 * th0; i += TS_THREADS) t0b[(i / tw0) * TRACK_MAX_SIDE + i % tw0] = templ[i];
+  if (tid < 2 * (2 * amax + 1)) tab[tid] = reinterpret_cast<const int*>(g.rot)[tid];
+  if (tid < th0) {
+    int lo = 0;
+    while (lo < tw0 && !track_disc(lo, tid, tw0, th0)) ++lo;
+    span[tid] = lo < tw0 ? (uint32_t)lo | (uint32_t)(tw0 - 2 * lo) << 8 : 0u;  // (the disc is symmetric in i)
+  }
+  // an angle or a position the host never saw: kept valid, so that no candidate reads outside the table or the image
+  int a = __builtin_amdgcn_readfirstlane(min(max(pos[2], -amax), amax));
+  int px = __builtin_amdgcn_readfirstlane(min(max(pos[0], 0), g.gw - tw0));
+  int py = __builtin_amdgcn_readfirstlane(min(max(pos[1], 0), g.gh - th0));
+  const uint8_t* lo = gray;
+  const uint8_t* hi = gray + (long)g.B * g.gh * g.gw;
+  __syncthreads();
+  int n = 0;  // the disc's samples
+  for (int j = 0; j < th0; ++j) n += (int)(span[j] >> 8);
+  for (int b = 0; b < g.B; ++b) {
+    const int dx_lo = max(-R, -px), dx_hi = min(R, g.gw - tw0 - px);
+    const int dy_lo = max(-R, -py), dy_hi = min(R, g.gh - th0 - py);
+    const int ncx = dx_hi - dx_lo + 1, ncy = dy_hi - dy_lo + 1;
+    const int wx0 = px + dx_lo, wy0 = py + dy_lo, ww = ncx - 1 + tw0, wh = ncy - 1 + th0;
+    const uint8_t* seg0 = gray + ((long)b * g.gh + wy0) * g.gw + wx0;
+    const int a0 = (int)(reinterpret_cast<uintptr_t>(seg0) & 3);  // row r of the window starts (a0 + r gw) mod 4 past a dword
+    const int items = wh * TS_STAGE_DW;
+    for (int i0 = tid; i0 < items; i0 += TS_UNROLL * TS_THREADS) {
+      uint32_t v[TS_UNROLL];
+      int at[TS_UNROLL];
+#pragma unroll
+      for (int u = 0; u < TS_UNROLL; ++u) {
+        const int i = i0 + u * TS_THREADS;
+        at[u] = -1;
+        v[u] = 0;
+        if (i >= items) continue;
+        const int r = i / TS_STAGE_DW, k = i - r * TS_STAGE_DW;
+        const int al = (a0 + r * g.gw) & 3;
+        if (4 * k >= al + ww) continue;
+        at[u] = r * TS_PITCH_DW + k;
+        v[u] = track_load_dword(seg0 + (long)r * g.gw - al + 4 * k, lo, hi);
+      }
+#pragma unroll
+      for (int u = 0; u < TS_UNROLL; ++u)
+        if (at[u] >= 0) win[at[u]] = v[u];
+    }
+    // the candidate angles: k = dA + 1 for a + dA inside the table, always a run kfirst .. kfirst + nk - 1 around k = 1
+    const int kfirst = g.steps > 0 && a - 1 >= -amax ? 0 : 1, nk = 2 - kfirst + (g.steps > 0 && a + 1 <= amax ? 1 : 0);
+    // T(a + dA) = rot(T0): a lane a dword of a row's span, the bytes behind n(j) as 0 (the tail's mask relies on it)
+    for (int idx = tid; idx < nk * th0 * TS_TDW; idx += TS_THREADS) {
+      const int kk = idx / (th0 * TS_TDW), rest = idx - kk * (th0 * TS_TDW), j = rest / TS_TDW, m4 = rest - j * TS_TDW;
+      const int k = kfirst + kk, lo_j = (int)(span[j] & 255u), n_j = (int)(span[j] >> 8);
+      if (4 * m4 >= n_j) continue;
+      const int c = tab[2 * (a + k - 1 + amax)], s = tab[2 * (a + k - 1 + amax) + 1];
+      uint32_t d = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (4 * m4 + q >= n_j) continue;
+        const RotTap t = track_rot_tap(lo_j + 4 * m4 + q, j, tw0, th0, c, s);
+        const uint8_t* r0 = t0b + t.y0 * TRACK_MAX_SIDE;
+        const uint8_t* r1 = t0b + t.y1 * TRACK_MAX_SIDE;
+        d |= (uint32_t)track_bilinear(r0[t.x0], r0[t.x1], r1[t.x0], r1[t.x1], t.fx, t.fy) << (8 * q);
+      }
+      tl[(k * TRACK_MAX_SIDE + j) * RS_TPITCH_DW + m4] = d;
+    }
+    __syncthreads();
+    // work items as in track_search_kernel, over the groups of all angles
+    const int ngx = (ncx + 3) >> 2, per = ngx * ncy, ngroups = nk * per;
+    int p = 1, units = ((ngroups + TS_THREADS - 1) / TS_THREADS) * th0;
+    for (int q = 2; q <= 64; q <<= 1) {
+      const int u = ((ngroups * q + TS_THREADS - 1) / TS_THREADS) * ((th0 + q - 1) / q);
+      if (u < units) p = q, units = u;
+    }
+    const int rpp = (th0 + p - 1) / p;
+    u64 best = ~0ull;
+    for (int it0 = 0; it0 < ngroups * p; it0 += TS_THREADS) {
+      const int item = it0 + tid, grp = item / p, part = item - grp * p;
+      const bool live = grp < ngroups;
+      const int kk = live ? grp / per : 0, local = live ? grp - kk * per : 0, k = kfirst + kk;
+      const int cyr = local / ngx, cxr = (local - cyr * ngx) * 4;
+      uint32_t cost[4] = {0, 0, 0, 0};
+      if (live) {
+        const int j1 = min(th0, (part + 1) * rpp);
+        for (int j = part * rpp; j < j1; ++j) {
+          const int lo_j = (int)(span[j] & 255u), n_j = (int)(span[j] >> 8), nfull = n_j >> 2;
+          const int r = cyr + j;
+          const int o = ((a0 + r * g.gw) & 3) + cxr + lo_j, ph = o & 3;
+          const uint32_t* row = win + r * TS_PITCH_DW + (o >> 2);
+          const uint32_t* trow = tl + (k * TRACK_MAX_SIDE + j) * RS_TPITCH_DW;
+          uint32_t d0 = row[0], d1 = row[1];
+          u64 acc = 0;  // four 16-bit sums: at most 16 dwords of 4 * 255 a row
+          for (int m = 0; m < nfull; ++m) {
+            const uint32_t d2 = row[m + 2];
+            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
+            acc = __builtin_amdgcn_qsad_pk_u16_u8((u64)w1 << 32 | w0, trow[m], acc);
+            d0 = d1, d1 = d2;
+          }
+          if (n_j & 3) {  // the span's last, partial dword: the window's bytes behind n(j) masked, the template's are 0
+            const uint32_t tail = (1u << (8 * (n_j & 3))) - 1u;
+            const uint32_t d2 = row[nfull + 2];
+            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
+            const uint32_t t = trow[nfull];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) cost[i] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, i) & tail, t, cost[i]);
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) cost[i] += (uint32_t)(acc >> (16 * i)) & 0xffffu;
+        }
+      }
+      for (int off = 1; off < p; off <<= 1)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cost[i] += __shfl_xor(cost[i], off, 64);
+      if (live && part == 0) {
+        const int dy = dy_lo + cyr, ada = k != 1;
+        const uint32_t bias = ada ? (uint32_t)g.penalty : 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int dx = dx_lo + cxr + i;
+          if (cxr + i >= ncx) continue;
+          const uint32_t ncost = (cost[i] << 12) / (uint32_t)n;  // cost << 12 <= 255 * 4096 * 4096 < 2^32
+          const u64 key = (u64)(ncost + bias) << 33 | (u64)ada << 32 | (u64)k << 30 | (u64)(dx * dx + dy * dy) << 16 |
+                          (u64)(dy + R) << 8 | (u64)(dx + R);
+          best = key < best ? key : best;
+        }
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const u64 other = __shfl_xor(best, off, 64);
+      best = other < best ? other : best;
+    }
+    if ((tid & 63) == 0) red[tid >> 6] = best;
+    __syncthreads();
+    best = red[0];
+    for (int k = 1; k < TS_THREADS / 64; ++k) best = red[k] < best ? red[k] : best;
+    const uint32_t best_lo = __builtin_amdgcn_readfirstlane((uint32_t)best), best_hi = __builtin_amdgcn_readfirstlane((uint32_t)(best >> 32));
+    // the winner: its angle, its displacement, and its cost back from cost << 12 over n (n is at most 4096, so one multiple
+    // of 4096 lies in ncost * n .. ncost * n + n - 1)
+    const int kb = (int)((best_lo >> 30) & 3u), dx = (int)(best_lo & 255u) - R, dy = (int)((best_lo >> 8) & 255u) - R;
+    const uint32_t ncost = (best_hi >> 1) - (kb != 1 ? (uint32_t)g.penalty : 0u);
+    const int cost = (int)((ncost * (uint32_t)n + 4095u) >> 12);
+    const int found = cost <= g.lost * n;
+    if (found) {
+      a += kb - 1, px += dx, py += dy;
+      if (g.adapt > 0) {
+        // W0 = the window at the new box turned back, blended into T0 on the disc
+        const int c = tab[2 * (a + amax)], s = -tab[2 * (a + amax) + 1];
+        for (int idx = tid; idx < th0 * TRACK_MAX_SIDE; idx += TS_THREADS) {
+          const int j = idx >> 6, m = idx & 63, lo_j = (int)(span[j] & 255u), n_j = (int)(span[j] >> 8);
+          if (m >= n_j) continue;
+          const int i = lo_j + m;
+          const RotTap t = track_rot_tap(i, j, tw0, th0, c, s);
+          const int ra = py - wy0 + t.y0, rb = py - wy0 + t.y1;
+          const uint8_t* r0 = wb + ra * (TS_PITCH_DW * 4) + ((a0 + ra * g.gw) & 3) + (px - wx0);
+          const uint8_t* r1 = wb + rb * (TS_PITCH_DW * 4) + ((a0 + rb * g.gw) & 3) + (px - wx0);
+          const int wv = track_bilinear(r0[t.x0], r0[t.x1], r1[t.x0], r1[t.x1], t.fx, t.fy);
+          uint8_t* tp = t0b + j * TRACK_MAX_SIDE + i;
+          *tp = (uint8_t)((*tp * (8 - g.adapt) + wv * g.adapt + 4) >> 3);
+        }
+      }
+    }
+    if (tid == 0) {
+      int* o = out + 8L * b;
+      o[0] = px, o[1] = py, o[2] = tw0, o[3] = th0, o[4] = (int)ncost, o[5] = found, o[6] = a, o[7] = cost;
+    }
+    __syncthreads();  // the window, the templates and red are the next frame's
+  }
+  for (int i = tid; i < tw0 * th0; i += TS_THREADS) templ[i] = t0b[(i / tw0) * TRACK_MAX_SIDE + i % tw0];
+  if (tid == 0) pos[0] = px, pos[1] = py, pos[2] = a;
+}
+
 static int track_frame_check(const char* who, int h, int w, int s) {
   D3F_CHECK(h > 0 && w > 0 && h <= 16384 && w <= 16384, "%s: size %d x %d outside 1..16384", who, h, w);
   D3F_CHECK(s >= 1 && s <= TRACK_MAX_STRIDE, "%s: stride %d outside 1..%d", who, s, TRACK_MAX_STRIDE);
@@ -656,6 +906,56 @@ int track_template_scale_u8_launch(const uint8_t* frames, int B, int h, int w, i
   if (int rc = gray_decimate_u8_launch(frames, B, h, w, s, gray_ws, stream)) return rc;
   return track_search_scale_u8_launch(gray_ws, B, h / s, w / s, tw0, th0, search, adapt, lost, levels, penalty, templ, pos, out,
                                       stream);
+}
+
+int track_seed_rot_u8_launch(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, int a0, int c16, int s16,
+                             uint8_t* templ, int* pos, hipStream_t stream) {
+  D3F_CHECK(a0 >= -RS_MAX_INDEX && a0 <= RS_MAX_INDEX, "track_seed_rot: angle index %d outside -%d..%d", a0, RS_MAX_INDEX,
+            RS_MAX_INDEX);
+  D3F_CHECK(abs(c16) <= 65536 && abs(s16) <= 65536, "track_seed_rot: rot (c16 %d, s16 %d) outside -65536..65536", c16, s16);
+  // the plain seed's launch (it refuses what it refuses, before anything runs), then the turn and pos[2]
+  if (int rc = track_seed_u8_launch(frame, h, w, s, tx, ty, tw, th, templ, pos, false, stream)) return rc;
+  hipLaunchKernelGGL(track_seed_rot_kernel, dim3(1), dim3(TS_THREADS), 0, stream, templ, tw, th, a0, c16, s16, pos);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+int track_search_rot_check(int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost, int steps, int penalty,
+                           int amax, const int* table, const int* pos, const int* out) {
+  if (int rc = track_search_check(B, gh, gw, tw0, th0, search, adapt, lost, pos, out)) return rc;
+  D3F_CHECK(steps >= 0 && steps <= 1, "track_search_rot: steps %d outside 0..1", steps);
+  D3F_CHECK(penalty >= 0 && penalty <= 65535, "track_search_rot: penalty %d outside 0..65535", penalty);
+  D3F_CHECK(amax >= 0 && amax <= RS_MAX_INDEX, "track_search_rot: amax %d outside 0..%d", amax, RS_MAX_INDEX);
+  D3F_CHECK(table != nullptr, "track_search_rot: null table (host memory [2 amax + 1][2]: c16, s16 per angle index)");
+  for (int i = 0; i < 2 * (2 * amax + 1); ++i)
+    D3F_CHECK(table[i] >= -65536 && table[i] <= 65536, "track_search_rot: table entry %d (angle index %d) is %d, outside "
+              "-65536..65536", i, i / 2 - amax, table[i]);
+  return 0;
+}
+
+int track_search_rot_u8_launch(const uint8_t* gray, int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost,
+                               int steps, int penalty, int amax, const int* table, uint8_t* templ, int* pos, int* out,
+                               hipStream_t stream) {
+  if (int rc = track_search_rot_check(B, gh, gw, tw0, th0, search, adapt, lost, steps, penalty, amax, table, pos, out)) return rc;
+  if (B == 0) return 0;
+  RotGeom g = {B, gh, gw, tw0, th0, search, adapt, lost, steps, penalty, amax, {}};
+  for (int i = 0; i < 2 * amax + 1; ++i) g.rot[i] = FrameRot{table[2 * i], table[2 * i + 1]};
+  hipLaunchKernelGGL(track_search_rot_kernel, dim3(1), dim3(TS_THREADS), 0, stream, gray, g, templ, pos, out);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+int track_template_rot_u8_launch(const uint8_t* frames, int B, int h, int w, int s, int tw0, int th0, int search, int adapt,
+                                 int lost, int steps, int penalty, int amax, const int* table, uint8_t* templ, int* pos,
+                                 uint8_t* gray_ws, int* out, hipStream_t stream) {
+  // both refusals before either launch
+  if (int rc = gray_decimate_check(B, h, w, s)) return rc;
+  D3F_CHECK(h / s > 0 && w / s > 0, "track_template_rot: stride %d leaves nothing of %d x %d", s, h, w);
+  if (int rc = track_search_rot_check(B, h / s, w / s, tw0, th0, search, adapt, lost, steps, penalty, amax, table, pos, out))
+    return rc;
+  if (int rc = gray_decimate_u8_launch(frames, B, h, w, s, gray_ws, stream)) return rc;
+  return track_search_rot_u8_launch(gray_ws, B, h / s, w / s, tw0, th0, search, adapt, lost, steps, penalty, amax, table, templ,
+                                    pos, out, stream);
 }
 
 }  // namespace d3f

@@ -1062,6 +1062,7 @@ def color_coef_smooth(coef, sums_to, n, state, strength=_lib.TEMPORAL_STRENGTH):
 TRACK_TEMPLATE_SIDE, TRACK_SEARCH, TRACK_ADAPT, TRACK_LOST = (_lib.TRACK_TEMPLATE_SIDE, _lib.TRACK_SEARCH, _lib.TRACK_ADAPT,
                                                               _lib.TRACK_LOST)
 TRACK_SCALE_PENALTY = _lib.TRACK_SCALE_PENALTY
+TRACK_ROT_STEP, TRACK_ROT_MAX, TRACK_ROT_PENALTY = _lib.TRACK_ROT_STEP, _lib.TRACK_ROT_MAX, _lib.TRACK_ROT_PENALTY
 
 
 def gray_decimate_u8(frames, s, out=None):
@@ -1121,7 +1122,9 @@ class TrackState:
     and `pos` int32 [2], both on the device; `geometry`, what `track_template_geometry` gave at the seed, and the frame
     size (h, w) it was given for, on the host; a grey workspace grown on demand; `seeded`.  `pos_level` int32 [3] is `pos`
     with the scale search's level behind it (`pos` is a view of its front): the seed sets it to L0 = max(tw, th), only
-    `track_template_scale_u8` reads and moves it, and with it `templ` stays at the seed's size."""
+    `track_template_scale_u8` reads and moves it, and with it `templ` stays at the seed's size.  A seed with `angle=`
+    makes the state one of the rotation search instead: the third entry is the angle index, `rot` = (step, max_degrees) of
+    the seed (None otherwise), `templ` the upright face; only `track_template_rot_u8` follows such a state."""
 
     def __init__(self, device="cuda"):
         device = torch.device(device)
@@ -1134,6 +1137,7 @@ class TrackState:
         self.h = self.w = 0
         self.gray = None
         self.seeded = False
+        self.rot = None
 
     def workspace(self, n):
         if self.gray is None or self.gray.numel() < n:
@@ -1141,10 +1145,39 @@ class TrackState:
         return self.gray
 
 
-def track_seed(state, frame, face, side=TRACK_TEMPLATE_SIDE):
+def track_rot_table(step=TRACK_ROT_STEP, max_degrees=TRACK_ROT_MAX):
+    """the rotation search's table: [(c16, s16)] = `box_rotation(a * step / 100)` for the angle indices a = -amax..amax (entry
+    a + amax), index a the angle a * step hundredths of a degree, amax = floor(max_degrees * 100 / step).  A ValueError: a
+    step that is no positive integer, a range that is negative, beyond 180 degrees or of more than 64 steps."""
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError(f"track_rot_table: the step is a positive integer of hundredths of a degree, not {step!r}")
+    try:
+        reach = float(max_degrees)
+    except (TypeError, ValueError):
+        reach = -1.0
+    if not 0.0 <= reach <= 180.0:  # (a NaN fails both comparisons)
+        raise ValueError(f"track_rot_table: the range is a number of degrees in 0..180, not {max_degrees!r}")
+    amax = int(reach * 100.0) // step
+    if amax > _lib.TRACK_ROT_MAX_INDEX:
+        raise ValueError(f"track_rot_table: {max_degrees} degrees in steps of {step / 100.0:.2f} are {amax} indices, above "
+                         f"{_lib.TRACK_ROT_MAX_INDEX}")
+    return [box_rotation(a * step / 100.0) for a in range(-amax, amax + 1)]
+
+
+def _rot_table_arg(step, max_degrees):
+    """(amax, the table as a ctypes int32 array in host memory)"""
+    table = track_rot_table(step, max_degrees)
+    flat = [v for pair in table for v in pair]
+    return len(table) // 2, (C.c_int32 * len(flat))(*flat)
+
+
+def track_seed(state, frame, face, side=TRACK_TEMPLATE_SIDE, angle=None, step=TRACK_ROT_STEP, max_degrees=TRACK_ROT_MAX):
     """(re-)seed `state` from the face box (fx, fy, fw, fh) marked in `frame`, uint8 BGR [h, w, 3] on the HIP device: the
     template is the reduced grey of the box, the level the seed's own (include/d3f_hip.h: d3f_track_seed_scale_u8, the
-    launch of d3f_track_seed_u8 with the level stored beside the position).  Returns the geometry."""
+    launch of d3f_track_seed_u8 with the level stored beside the position).  Returns the geometry.
+    angle: the head's roll in the key frame in degrees (0: the tracked angle is relative to the key frame's pose): the seed of
+    the rotation search with `step` and `max_degrees` (`track_rot_table`) -- the angle index a0 = round(angle / step), a
+    ValueError outside the table; the template is the box's grey turned back by that angle on the disc (d3f_track_seed_rot_u8)."""
     if not isinstance(state, TrackState):
         raise ValueError("track_seed: state must be a TrackState")
     if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
@@ -1155,9 +1188,22 @@ def track_seed(state, frame, face, side=TRACK_TEMPLATE_SIDE):
     if _dev(frame) != state.templ.device:
         raise ValueError("track_seed expects the frame on the state's device")
     x = frame.contiguous()
-    check(_lib.lib().d3f_track_seed_scale_u8(ptr(x), h, w, s, tx, ty, tw, th, ptr(state.templ), ptr(state.pos_level),
-                                             stream_ptr()))
-    state.geometry, state.h, state.w, state.seeded = geometry, h, w, True
+    if angle is None:
+        check(_lib.lib().d3f_track_seed_scale_u8(ptr(x), h, w, s, tx, ty, tw, th, ptr(state.templ), ptr(state.pos_level),
+                                                 stream_ptr()))
+        rot = None
+    else:
+        table = track_rot_table(step, max_degrees)
+        hundredths = angle_hundredths(angle)
+        a0 = (2 * abs(hundredths) + step) // (2 * step) * (1 if hundredths >= 0 else -1)  # halves away from zero
+        if abs(a0) > len(table) // 2:
+            raise ValueError(f"track_seed: the angle {angle} is index {a0} at step {step}, outside the table of "
+                             f"+-{len(table) // 2}")
+        c16, s16 = table[a0 + len(table) // 2]
+        check(_lib.lib().d3f_track_seed_rot_u8(ptr(x), h, w, s, tx, ty, tw, th, a0, c16, s16, ptr(state.templ),
+                                               ptr(state.pos_level), stream_ptr()))
+        rot = (step, max_degrees)
+    state.geometry, state.h, state.w, state.seeded, state.rot = geometry, h, w, True, rot
     return geometry
 
 
@@ -1243,6 +1289,47 @@ def track_scale_faces(rows, state, frame=None):
             x, y = min(max(x, 1 - fw1), frame[1] - 1), min(max(y, 1 - fh1), frame[0] - 1)
         boxes.append((x, y, fw1, fh1))
     return boxes
+
+
+def track_template_rot_u8(frames, state, search=TRACK_SEARCH, adapt=TRACK_ADAPT, lost=TRACK_LOST, steps=1,
+                          penalty=TRACK_ROT_PENALTY, step=TRACK_ROT_STEP, max_degrees=TRACK_ROT_MAX):
+    """`track_template_u8` with the rotation search: the box may turn about its centre by up to `steps` (0 or 1) angle
+    indices a frame, an index `step` hundredths of a degree, within +-`max_degrees`; `penalty` (0..65535, in 1/4096 grey
+    levels per sample) is what a turn must win by -> int32 [B, 8] on the device, a row (px, py, tw0, th0, ncost, found, a,
+    cost) per frame in the reduced image (`track_rot_faces` turns host rows into boxes and angles).  The state is one that
+    `track_seed(..., angle=)` seeded with the same step and range: its template is the upright face, its third entry the
+    angle index.  One device call: the reduced grey of every frame, then the search inside one kernel (include/d3f_hip.h:
+    d3f_track_template_rot_u8)."""
+    if not isinstance(state, TrackState) or not state.seeded:
+        raise ValueError("track_template_rot_u8: state must be a TrackState seeded by track_seed")
+    if state.rot != (step, max_degrees):
+        raise ValueError(f"track_template_rot_u8: step {step} and range {max_degrees}, the state was seeded "
+                         + ("without angle=" if state.rot is None else f"with {state.rot}"))
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError("track_template_rot_u8 expects uint8 frames [B, h, w, 3]")
+    B, h, w, _ = frames.shape
+    if (h, w) != (state.h, state.w):
+        raise ValueError(f"track_template_rot_u8: frames of {h} x {w}, the state was seeded on {state.h} x {state.w}")
+    if _dev(frames) != state.templ.device:
+        raise ValueError("track_template_rot_u8 expects the frames on the state's device")
+    s, _, _, tw, th = state.geometry[:5]
+    amax, table = _rot_table_arg(step, max_degrees)
+    out = torch.empty((B, 8), dtype=torch.int32, device=frames.device)
+    if B > 0:
+        x = frames.contiguous()
+        ws = state.workspace(B * (h // s) * (w // s))
+        check(_lib.lib().d3f_track_template_rot_u8(ptr(x), B, h, w, s, tw, th, int(search), int(adapt), int(lost), int(steps),
+                                                   int(penalty), amax, table, ptr(state.templ), ptr(state.pos_level), ptr(ws),
+                                                   ptr(out), stream_ptr()))
+    return out
+
+
+def track_rot_faces(rows, state, step=TRACK_ROT_STEP):
+    """host rows (px, py, tw0, th0, ncost, found, a, cost) of `track_template_rot_u8` -> a list of (x, y, w, h, hundredths),
+    None where the frame's row says not found: the box is `track_faces`' box, which turns about its centre, the angle
+    a * step in hundredths of a degree.  state: the TrackState the rows came from, or the geometry it had then"""
+    s, _, _, _, _, ox, oy, fw, fh = getattr(state, "geometry", state)
+    return [(int(r[0]) * s + ox, int(r[1]) * s + oy, fw, fh, int(r[6]) * int(step)) if int(r[5]) else None for r in rows]
 
 
 def _paste_args(who, patch, frames, box, out, color, boxes):

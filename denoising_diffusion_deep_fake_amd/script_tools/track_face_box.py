@@ -4,12 +4,16 @@ key frame is the template, and the device follows it from frame to frame (ops.tr
 every frame, then the smallest sum of absolute differences in a search window).  The box keeps the key's size unless
 --scale is given: then the size is searched too, one sample of the template's longer side a frame (about 2 %), and the
 box follows a face that walks towards the camera or away from it (ops.track_template_scale_u8).  What remains: the
-template's longer side stays within 4..64 samples at the key's stride (a third over the default side of 48), and there
-is no rotation search.  Where the face outgrows that, turns, where the tracker drifts and behind a cut, mark another key
-frame -- the tracker is seeded anew at every key.  Head roll is marked by hand as well: --key-angle K A (repeatable) writes
-a fifth column, the key angles interpolated linearly, which the two tools read with --track-rotate.
+template's longer side stays within 4..64 samples at the key's stride (a third over the default side of 48).  Where
+the face outgrows that, where the tracker drifts and behind a cut, mark another key frame -- the tracker is seeded anew
+at every key.  Head roll: --rotate searches the box's angle too, one step (--rotate-step, 2 degrees) a frame, up to
+--rotate-max degrees either way (ops.track_template_rot_u8), and writes it as a fifth column, which the two tools read with
+--track-rotate; the angle is relative to the key frame's pose unless --key-angle K A gives the roll at that key.  Without
+--rotate the roll is marked by hand: --key-angle K A (repeatable) writes the fifth column from the key angles, interpolated
+linearly.  --rotate and --scale cannot be combined: the rotation search keeps the key's size.
 
-    python -m d3f.script_tools.track_face_box VIDEO --key K X Y W H [--key ...] [-o FILE] [--scale] [--key-angle K A ...]
+    python -m d3f.script_tools.track_face_box VIDEO --key K X Y W H [--key ...] [-o FILE] [--scale | --rotate]
+                                              [--key-angle K A ...]
 """
 import argparse
 from pathlib import Path
@@ -36,6 +40,10 @@ def main():
         scale=args.scale,
         scale_penalty=args.scale_penalty,
         key_angles=args.key_angle,
+        rotate=args.rotate,
+        rotate_step=args.rotate_step,
+        rotate_max=args.rotate_max,
+        rotate_penalty=args.rotate_penalty,
         )
     found = sum(box is not None for box in tracker.track)
     print(f"{tracker.output_path}: {len(tracker.track)} frames, the face found in {found}")
@@ -73,13 +81,25 @@ def parse_command_line_arguments(argv=None):
     parser.add_argument("--key-angle", nargs=2, action="append", metavar=("K", "A"), default=None,
                         help="the head's roll at frame K, A in decimal degrees (positive: clockwise on the screen); repeat "
                              "it.  The file gains a fifth column, the linear interpolation of the key angles (constant "
-                             "before the first and after the last), for --track-rotate; the tracker does not search rotation")
+                             "before the first and after the last), for --track-rotate.  With --rotate: the roll at the key "
+                             "frame K, which must have a --key; the tracker follows it from there")
+    parser.add_argument("--rotate", action="store_true",
+                        help="search the angle of the box too, one step a frame, and write it as the fifth column; without "
+                             "it the tracker does not search rotation")
+    parser.add_argument("--rotate-step", type=int, default=ops.TRACK_ROT_STEP, metavar="H",
+                        help=f"with --rotate: the angle of one step in hundredths of a degree (default {ops.TRACK_ROT_STEP})")
+    parser.add_argument("--rotate-max", type=int, default=ops.TRACK_ROT_MAX, metavar="D",
+                        help=f"with --rotate: the angle stays within +-D degrees, at most {_lib.TRACK_ROT_MAX_INDEX} steps "
+                             f"(default {ops.TRACK_ROT_MAX})")
+    parser.add_argument("--rotate-penalty", type=int, default=ops.TRACK_ROT_PENALTY, metavar="P",
+                        help=f"with --rotate: what a turn must win by, in 1/4096 grey levels per sample, "
+                             f"0..{_lib.TRACK_MAX_SCALE_PENALTY} (default {ops.TRACK_ROT_PENALTY})")
 
     args = parser.parse_args(argv)
     try:
-        sorted_key_angles(args.key_angle)
         check_settings(sorted_keys(args.key), args.batch_frames, args.search, args.adapt, args.lost, args.template_side,
-                       args.scale, args.scale_penalty)
+                       args.scale, args.scale_penalty, args.rotate, args.rotate_step, args.rotate_max, args.rotate_penalty,
+                       sorted_key_angles(args.key_angle))
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -141,17 +161,37 @@ def interpolate_key_angles(key_angles, frames):
 
 
 def check_settings(keys, batch_frames, search, adapt, lost, template_side, scale=False,
-                   scale_penalty=ops.TRACK_SCALE_PENALTY):
+                   scale_penalty=ops.TRACK_SCALE_PENALTY, rotate=False, rotate_step=ops.TRACK_ROT_STEP,
+                   rotate_max=ops.TRACK_ROT_MAX, rotate_penalty=ops.TRACK_ROT_PENALTY, key_angles=None):
+    """keys: what `sorted_keys` gave; key_angles: what `sorted_key_angles` gave.  A ValueError for a setting out of range,
+    --rotate with --scale, and with --rotate a step and range `ops.track_rot_table` refuses, a key angle at a frame without
+    a key or beyond the range"""
     if int(batch_frames) < 1:
         raise ValueError("--batch-frames is at least 1")
     if not isinstance(scale, bool):
         raise ValueError(f"--scale is True or False, not {scale!r}")
+    if not isinstance(rotate, bool):
+        raise ValueError(f"--rotate is True or False, not {rotate!r}")
+    if rotate and scale:
+        raise ValueError("--rotate with --scale: the rotation search keeps the key's size, the two cannot be combined")
     for name, value, low, high in (("--search", search, 1, _lib.TRACK_MAX_SEARCH), ("--adapt", adapt, 0, 8),
                                    ("--lost", lost, 0, 255),
                                    ("--template-side", template_side, _lib.TRACK_MIN_SIDE, _lib.TRACK_MAX_SIDE),
-                                   ("--scale-penalty", scale_penalty, 0, _lib.TRACK_MAX_SCALE_PENALTY)):
+                                   ("--scale-penalty", scale_penalty, 0, _lib.TRACK_MAX_SCALE_PENALTY),
+                                   ("--rotate-penalty", rotate_penalty, 0, _lib.TRACK_MAX_SCALE_PENALTY),
+                                   ("--rotate-step", rotate_step, 1, 18000), ("--rotate-max", rotate_max, 0, 180)):
         if isinstance(value, bool) or not isinstance(value, int) or not low <= value <= high:
             raise ValueError(f"{name} is an integer in {low}..{high}, not {value!r}")
+    if rotate:
+        try:
+            amax = len(ops.track_rot_table(rotate_step, rotate_max)) // 2
+        except ValueError as e:
+            raise ValueError(f"--rotate-step {rotate_step} with --rotate-max {rotate_max}: {e}") from None
+        for k, a in (key_angles or {}).items():
+            if k not in keys:
+                raise ValueError(f"--key-angle: with --rotate the angle of frame {k} seeds the tracker, and frame {k} has no --key")
+            if (2 * abs(a) + rotate_step) // (2 * rotate_step) > amax:
+                raise ValueError(f"--key-angle: {a / 100.0:.2f} degrees at frame {k} is beyond --rotate-max {rotate_max}")
     return keys
 
 
@@ -180,23 +220,32 @@ class TrackFaceBox():
     scale=True: the size of the box is searched too (ops.track_template_scale_u8), scale_penalty what a change of size must
     win by; every key sets the size anew.
     key_angles: (k, a) each, the head's roll in degrees at frame k: the file gains a fifth column, .angles holds it in integer
-    hundredths of a degree (`interpolate_key_angles`); None: the file is the four-column one.  The tracker itself does not
-    search rotation."""
+    hundredths of a degree (`interpolate_key_angles`); None: the file is the four-column one.
+    rotate=True: the angle of the box is searched too (ops.track_template_rot_u8; not together with scale=True), rotate_step
+    hundredths of a degree a step, within +-rotate_max degrees, rotate_penalty what a turn must win by.  The fifth column
+    and .angles (0 where the track has None; the sink still takes x y w h) are then the tracked angle, a multiple of the step; a key angle seeds the
+    angle at its key frame -- a frame without a key there is a ValueError -- and a key without one seeds angle 0: the
+    tracked angle is then relative to that key frame's pose."""
 
     def __init__(self, video_path, keys, output_path=None, batch_frames=8, frames=None, sink=None, device="cuda",
                  search=ops.TRACK_SEARCH, adapt=ops.TRACK_ADAPT, lost=ops.TRACK_LOST,
-                 template_side=ops.TRACK_TEMPLATE_SIDE, scale=False, scale_penalty=ops.TRACK_SCALE_PENALTY, key_angles=None):
+                 template_side=ops.TRACK_TEMPLATE_SIDE, scale=False, scale_penalty=ops.TRACK_SCALE_PENALTY, key_angles=None,
+                 rotate=False, rotate_step=ops.TRACK_ROT_STEP, rotate_max=ops.TRACK_ROT_MAX,
+                 rotate_penalty=ops.TRACK_ROT_PENALTY):
 
         self.video_path = Path(video_path)
-        self.keys = check_settings(sorted_keys(keys), batch_frames, search, adapt, lost, template_side, scale, scale_penalty)
+        self.keys = sorted_keys(keys)
+        self.key_angles = sorted_key_angles(key_angles)
+        self.keys = check_settings(self.keys, batch_frames, search, adapt, lost, template_side, scale, scale_penalty,
+                                   rotate, rotate_step, rotate_max, rotate_penalty, self.key_angles)
         self.batch_frames = int(batch_frames)
         self.frames = frames
         self.sink = sink
         self.device = device
         self.search, self.adapt, self.lost, self.template_side = search, adapt, lost, template_side
         self.scale, self.scale_penalty = scale, scale_penalty
-        self.key_angles = sorted_key_angles(key_angles)
-        self.angles = None
+        self.rotate, self.rotate_step, self.rotate_max, self.rotate_penalty = rotate, rotate_step, rotate_max, rotate_penalty
+        self.angles = [] if rotate else None
         if output_path is not None:
             self.output_path = Path(output_path)
         elif sink is None:
@@ -210,7 +259,7 @@ class TrackFaceBox():
 
         self.track_video()
 
-        if self.key_angles is not None:
+        if not self.rotate and self.key_angles is not None:
             self.angles = interpolate_key_angles(self.key_angles, len(self.track))
         if self.output_path is not None:
             write_track(self.output_path, self.track, self.header(), self.angles)
@@ -225,7 +274,13 @@ class TrackFaceBox():
                  f"search {self.search}, adapt {self.adapt}, lost {self.lost}, template side {self.template_side}")
         if self.scale:
             lines += (f"scale search: one level a frame, penalty {self.scale_penalty}",)
-        if self.key_angles is not None:
+        if self.rotate:
+            lines += (f"rotation search: one step of {self.rotate_step / 100.0:.2f} degrees a frame within +-{self.rotate_max}, "
+                      f"penalty {self.rotate_penalty}; fifth column: the box's angle in degrees",)
+            if self.key_angles is not None:
+                angles = ", ".join(f"{k} {a / 100.0:.2f}" for k, a in self.key_angles.items())
+                lines += (f"key angles (frame angle): {angles}",)
+        elif self.key_angles is not None:
             angles = ", ".join(f"{k} {a / 100.0:.2f}" for k, a in self.key_angles.items())
             lines += (f"fifth column: the box's angle in degrees, interpolated between the key angles (frame angle): {angles}",)
         return lines
@@ -244,6 +299,9 @@ class TrackFaceBox():
                     state = ops.TrackState(self.device)
                 boxes = self.track_batch(torch.from_numpy(batch).to(self.device)[:real_frames], first, state)
             for box in boxes:
+                if self.rotate:  # (x, y, w, h, hundredths): the track stays x y w h, the angle goes beside it
+                    self.angles.append(0 if box is None else box[4])
+                    box = None if box is None else box[:4]
                 self.track.append(box)
                 if self.sink is not None:
                     self.sink(box)
@@ -260,16 +318,26 @@ class TrackFaceBox():
             if cut > start and state.seeded:
                 parts.append((start, self.follow(dev[start:cut], state), state.geometry))
             if cut < n:
-                geometry = ops.track_seed(state, dev[cut], self.keys[first + cut], self.template_side)
+                if self.rotate:
+                    angle = (self.key_angles or {}).get(first + cut, 0)
+                    geometry = ops.track_seed(state, dev[cut], self.keys[first + cut], self.template_side, angle / 100.0,
+                                              self.rotate_step, self.rotate_max)
+                else:
+                    geometry = ops.track_seed(state, dev[cut], self.keys[first + cut], self.template_side)
                 s, tx, ty, _, _, ox, oy, fw, fh = geometry
                 boxes[cut] = (tx * s + ox, ty * s + oy, fw, fh)  # the key's box, clipped
+                if self.rotate:  # and the angle of the seed's index
+                    boxes[cut] += ((2 * abs(angle) + self.rotate_step) // (2 * self.rotate_step) * self.rotate_step
+                                   * (1 if angle >= 0 else -1),)
             start = cut + 1
         if parts:
             rows = torch.cat([part[1] for part in parts]).cpu().tolist()  # one copy back
             at = 0
             for index, part, geometry in parts:
                 count = len(part)
-                if self.scale:
+                if self.rotate:
+                    boxes[index:index + count] = ops.track_rot_faces(rows[at:at + count], geometry, self.rotate_step)
+                elif self.scale:
                     boxes[index:index + count] = ops.track_scale_faces(rows[at:at + count], geometry, dev.shape[1:3])
                 else:
                     boxes[index:index + count] = ops.track_faces(rows[at:at + count], geometry)
@@ -277,6 +345,9 @@ class TrackFaceBox():
         return boxes
 
     def follow(self, dev, state):
+        if self.rotate:
+            return ops.track_template_rot_u8(dev, state, self.search, self.adapt, self.lost, 1, self.rotate_penalty,
+                                             self.rotate_step, self.rotate_max)
         if self.scale:
             return ops.track_template_scale_u8(dev, state, self.search, self.adapt, self.lost, 1, self.scale_penalty)
         return ops.track_template_u8(dev, state, self.search, self.adapt, self.lost)

@@ -819,7 +819,7 @@ int d3f_temporal_flag_set(int32_t* flag, int value, void* stream);
  * arithmetic throughout, so the result does not depend on the order of evaluation; tests/track_restatement.py restates it in
  * numpy and Python integers and every comparison is exact.  The defaults (D3F_TRACK_TEMPLATE_SIDE, _SEARCH, _ADAPT, _LOST) are
  * design choices, not measurements.  The plain entries follow a template of fixed size; the _scale_ entries below search
- * the size too.  There is no rotation search.
+ * the size too, the _rot_ entries below them head roll.
  *
  * d3f_gray_decimate_u8: frames [B][h][w][3] uint8 BGR, packed, any byte address -> out [B][gh][gw] uint8, gh = h / s,
  * gw = w / s (partial blocks at the right and bottom are dropped), out[y][x] = (sum over the s x s block of B + 2 G + R) /
@@ -899,6 +899,51 @@ int d3f_track_search_scale_u8(const uint8_t* gray, int B, int gh, int gw, int tw
 int d3f_track_template_scale_u8(const uint8_t* frames, int B, int h, int w, int s, int tw0, int th0, int search, int adapt,
                                 int lost, int levels, int penalty, uint8_t* templ, int32_t* pos, uint8_t* gray_ws,
                                 int32_t* out, void* stream);
+
+/* Template tracker, rotation search (opt-in; the entries above are untouched by it): the box follows head roll, one angle
+ * index a frame, and writes the angle that the _rboxes_ operators read.  tests/track_rot_restatement.py restates it; DESIGN.md
+ * section 4 holds the specification.  All integers, / is the floor, >> of a negative number too.  It does not search the size.
+ * The state: templ, the template T0 of the UPRIGHT face, tw0 x th0, packed as above; pos int32[3] = (x, y, a): (x, y) the corner
+ * of the un-rotated tw0 x th0 box, which turns about its centre as the _rboxes_ boxes do, a the angle index in -amax..amax.
+ * Index a is the angle a * step hundredths of a degree; step is the host's choice (D3F_TRACK_ROT_STEP = 200, D3F_TRACK_ROT_MAX =
+ * 60 degrees).  table: HOST memory, int32 [2 amax + 1][2], entry a + amax = (c16, s16) = round(65536 cos), round(65536 sin) of
+ * that angle (ops.box_rotation; x right, y down, positive clockwise on the screen); amax <= D3F_TRACK_ROT_MAX_INDEX.  The table
+ * is checked (every entry within -65536..65536) and passed by value; the device does no trigonometry.
+ * The disc: with u = 2 i + 1 - tw0, v = 2 j + 1 - th0, D = min(tw0, th0), sample (i, j) belongs when u u + v v <= D D; n is
+ * their number.  Costs are summed and T0 is blended on the disc only.
+ * rot(A, c, s), A of th0 x tw0, per sample of the disc: X = c u + s v + (tw0 - 1) 65536, Y = -s u + c v + (th0 - 1) 65536 (units
+ * of 1/131072 sample); x0 = X >> 17, fx = (X >> 11) & 63, x1 = x0 + 1, both clamped to 0..tw0 - 1, y likewise; the value is the
+ * scale search's bilinear form, (A[y0][x0] (64 - fy)(64 - fx) + ... + 2048) >> 12.  At angle 0 it is the identity.  (A tap of a
+ * sample on the disc's rim may be a sample just outside the disc.)
+ * d3f_track_seed_rot_u8: d3f_track_seed_u8's launch, then one more: on the disc templ = rot(the grey, c16, -s16), the key box's
+ * content turned back by the key angle, and pos[2] = a0.  With a0 = 0, c16 = 65536, s16 = 0 templ is the plain seed's bytes.
+ * d3f_track_search_rot_u8: gray [B][gh][gw]; templ and pos read at the start and written at the end (an a outside -amax..amax
+ * and a position outside the image are moved inside first).  For each frame in order:
+ *   - candidate indices a + dA, dA in -steps..steps, those outside -amax..amax dropped; T(a + dA) = rot(T0, c, s) of the index;
+ *   - candidates (dx, dy) in [-search, search]^2 with the un-rotated box inside the image, as d3f_track_search_u8 has them;
+ *   - cost = sum over the disc of |gray - T(a + dA)|, ncost = (cost << 12) / n;
+ *   - the smallest (ncost + penalty |dA|, |dA|, dA + 1, dx dx + dy dy, dy + search, dx + search) wins: the scale search's 64-bit
+ *     key with dA in the place of dL.  Ties go to no turn, then to the smaller index, then as above;
+ *   - found = cost <= lost n, on the winner's own cost.  Found: a += dA, (x, y) += (dx, dy), W0 = rot(the window at the new box,
+ *     c, -s) of the new index, T0 = (T0 (8 - adapt) + W0 adapt + 4) >> 3 on the disc.  Not found: x, y, a and T0 stay;
+ *   - out[b] = (x, y, tw0, th0, ncost, found, a, cost), int32[8], after the update.
+ * The box in the frame is d3f_track_search_u8's, (x s + ox, y s + oy, fw, fh); its angle is a * step hundredths of a degree.
+ * d3f_track_template_rot_u8: d3f_gray_decimate_u8 into gray_ws, then d3f_track_search_rot_u8: two launches in one call.
+ * B == 0 touches nothing.  Refused before any device call: what d3f_track_search_u8 refuses, steps outside 0..1, penalty outside
+ * 0..65535, amax outside 0..D3F_TRACK_ROT_MAX_INDEX, a null table or an entry outside -65536..65536; by the seed an a0 outside
+ * -D3F_TRACK_ROT_MAX_INDEX..D3F_TRACK_ROT_MAX_INDEX and c16, s16 outside -65536..65536. */
+#define D3F_TRACK_ROT_MAX_INDEX 64
+#define D3F_TRACK_ROT_STEP 200
+#define D3F_TRACK_ROT_MAX 60
+#define D3F_TRACK_ROT_PENALTY 512
+int d3f_track_seed_rot_u8(const uint8_t* frame, int h, int w, int s, int tx, int ty, int tw, int th, int a0, int c16, int s16,
+                          uint8_t* templ, int32_t* pos /* int32[3]: x, y, a */, void* stream);
+int d3f_track_search_rot_u8(const uint8_t* gray, int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost,
+                            int steps, int penalty, int amax, const int32_t* table /* host [2 amax + 1][2] */, uint8_t* templ,
+                            int32_t* pos /* int32[3]: x, y, a */, int32_t* out /* [B][8] */, void* stream);
+int d3f_track_template_rot_u8(const uint8_t* frames, int B, int h, int w, int s, int tw0, int th0, int search, int adapt,
+                              int lost, int steps, int penalty, int amax, const int32_t* table, uint8_t* templ, int32_t* pos,
+                              uint8_t* gray_ws, int32_t* out, void* stream);
 
 /* log_batch_as_image_grid of the three LitModules (d3f/train_deep_fake/lit_module.py:235-249,
  * d3f/train_denoiser/lit_module.py:157-171, d3f/balance_training_images/lit_module.py:197-211):

@@ -4,7 +4,8 @@
              once and the reduced image written once, 3 h w + gh gw bytes per frame at 6.3 TB/s achievable HBM
   search   : d3f_track_search_u8 alone on a reduced image of 270 x 480, a 48 x 48 template, search 16 (1089 candidates a
              frame), B = 1 and B = 8: one workgroup, the frames in order inside the kernel; beside it, in the same rounds,
-             d3f_track_search_scale_u8 at the same shape with levels = 1 (three levels a frame) and levels = 0
+             d3f_track_search_scale_u8 at the same shape with levels = 1 (three levels a frame) and levels = 0, and
+             d3f_track_search_rot_u8 with steps = 1 (three angles a frame, on the disc) and steps = 0
   tool     : ops.track_template_u8 (decimate + search, what track_face_box runs per batch once the frames are on the
              device) for a 190 x 190 face (stride 4, a 47 x 47 template), B = 1 and B = 8, next to
              Unet.predict_frames_full_u8 on the same frames (448 x 448, eager): the share the tracking pass is of the render
@@ -15,6 +16,7 @@ key frame and nothing in the others, and neither kernel's work depends on the da
     python profiles/tools/track_timing.py [--precision f32|bf16] [--iters N]
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -40,7 +42,8 @@ def main():
     h, w = RAW
     result = {"raw": list(RAW), "precision": args.precision, "digest": _lib.built_digest(), "iters": args.iters,
               "rounds": args.rounds, "decimate_us_per_frame": {}, "search_us_per_frame": {}, "search_scale_us_per_frame": {},
-              "search_scale_levels0_us_per_frame": {}, "tool_us_per_frame": {}}
+              "search_scale_levels0_us_per_frame": {}, "search_rot_us_per_frame": {}, "search_rot_steps0_us_per_frame": {},
+              "tool_us_per_frame": {}}
     torch.manual_seed(0)
     net = Unet("resnet34", None, 3, 3, None, compute_dtype=args.precision).cuda().eval()
     lib = _lib.lib()
@@ -82,7 +85,20 @@ def main():
                                                      ops.TRACK_LOST, levels, ops.TRACK_SCALE_PENALTY,
                                                      _lib.ptr(state_scale[levels][0]), _lib.ptr(state_scale[levels][1]),
                                                      _lib.ptr(rows_scale[levels]), _lib.stream_ptr()))
-        forms = {"search": search, "search_scale": lambda: search_scale(1), "search_scale_levels0": lambda: search_scale(0)}
+        # the rotation search likewise: steps = 1 (three angles: 3267 candidates on the disc and four turns of the template a
+        # frame) and steps = 0, a state each
+        table = [v for pair in ops.track_rot_table() for v in pair]
+        amax, table = len(table) // 4, (ctypes.c_int32 * len(table))(*table)
+        state_rot = {steps: (templ.clone(), torch.tensor([200, 100, 0], dtype=torch.int32, device="cuda")) for steps in (0, 1)}
+        rows_rot = {steps: torch.empty((B, 8), dtype=torch.int32, device="cuda") for steps in (0, 1)}
+
+        def search_rot(steps):
+            _lib.check(lib.d3f_track_search_rot_u8(_lib.ptr(grey[4]), B, gh, gw, 48, 48, ops.TRACK_SEARCH, ops.TRACK_ADAPT,
+                                                   ops.TRACK_LOST, steps, ops.TRACK_ROT_PENALTY, amax, table,
+                                                   _lib.ptr(state_rot[steps][0]), _lib.ptr(state_rot[steps][1]),
+                                                   _lib.ptr(rows_rot[steps]), _lib.stream_ptr()))
+        forms = {"search": search, "search_scale": lambda: search_scale(1), "search_scale_levels0": lambda: search_scale(0),
+                 "search_rot": lambda: search_rot(1), "search_rot_steps0": lambda: search_rot(0)}
         t = compare(forms, args.warmup, args.iters, args.rounds)
         med, lo, hi = t["search"]
         print(f"search 48x48 R16 B{B}: {med / B:8.2f} us per frame (min {lo / B:.2f}, max {hi / B:.2f}); rows {rows[0].tolist()}")
@@ -91,6 +107,12 @@ def main():
             m, lo, hi = t[name]
             print(f"{name} 48x48 R16 B{B}: {m / B:8.2f} us per frame (min {lo / B:.2f}, max {hi / B:.2f}), {m / med:.2f} times "
                   f"the plain search; rows {rows_scale[levels][0].tolist()}")
+            result[f"{name}_us_per_frame"][f"B{B}"] = {"us": round(m / B, 2), "min": round(lo / B, 2), "max": round(hi / B, 2),
+                                                       "times_plain": round(m / med, 3)}
+        for name, steps in (("search_rot", 1), ("search_rot_steps0", 0)):
+            m, lo, hi = t[name]
+            print(f"{name} 48x48 R16 B{B}: {m / B:8.2f} us per frame (min {lo / B:.2f}, max {hi / B:.2f}), {m / med:.2f} times "
+                  f"the plain search; rows {rows_rot[steps][0].tolist()}")
             result[f"{name}_us_per_frame"][f"B{B}"] = {"us": round(m / B, 2), "min": round(lo / B, 2), "max": round(hi / B, 2),
                                                        "times_plain": round(m / med, 3)}
         # the tool's device call against the render of the same frames
