@@ -57,6 +57,7 @@ TEMPORAL_STRENGTH, TEMPORAL_THRESHOLD = 0.75, 8  # D3F_TEMPORAL_*: design choice
 # D3F_TRACK_*: the template tracker's limits, and its defaults (design choices, not measurements)
 TRACK_MAX_SIDE, TRACK_MAX_SEARCH, TRACK_MAX_STRIDE, TRACK_MIN_SIDE = 64, 64, 32, 4
 TRACK_TEMPLATE_SIDE, TRACK_SEARCH, TRACK_ADAPT, TRACK_LOST = 48, 16, 1, 16
+TRACK_RELOST = 8  # D3F_TRACK_RELOST: the whole-frame search's threshold, half of TRACK_LOST (a design choice too)
 TRACK_SCALE_PENALTY, TRACK_MAX_SCALE_PENALTY = 512, 65535  # D3F_TRACK_SCALE_PENALTY, in 1/4096 grey levels
 # D3F_TRACK_ROT_*: the rotation search's step in hundredths of a degree, its range in degrees, its penalty, the largest index
 TRACK_ROT_STEP, TRACK_ROT_MAX, TRACK_ROT_PENALTY, TRACK_ROT_MAX_INDEX = 200, 60, 512, 64
@@ -230,6 +231,10 @@ PROTOTYPES = {
     "d3f_track_seed_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "d3f_track_search_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "d3f_track_template_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    # keys: uint64 [B] on the device
+    "d3f_track_global_u8": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "d3f_track_search_reacq_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "d3f_track_template_reacq_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "d3f_track_seed_scale_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "d3f_track_search_scale_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "d3f_track_template_scale_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),

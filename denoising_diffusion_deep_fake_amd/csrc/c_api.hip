@@ -1091,6 +1091,29 @@ int d3f_track_template_u8(const uint8_t* frames, int B, int h, int w, int s, int
                                   (hipStream_t)stream);
 }
 
+int d3f_track_global_u8(const uint8_t* gray, int B, int gh, int gw, int tw, int th, const uint8_t* key_templ, uint64_t* keys,
+                        void* stream) {
+  D3F_CHECK(gray && key_templ && keys, "track_global_u8: null argument");
+  return track_global_u8_launch(gray, B, gh, gw, tw, th, key_templ, reinterpret_cast<unsigned long long*>(keys),
+                                (hipStream_t)stream);
+}
+
+int d3f_track_search_reacq_u8(const uint8_t* gray, int B, int gh, int gw, int tw, int th, int search, int adapt, int lost,
+                              int relost, uint8_t* templ, const uint8_t* key_templ, int32_t* pos, const uint64_t* keys,
+                              int32_t* out, void* stream) {
+  D3F_CHECK(gray && templ && key_templ && pos && keys && out, "track_search_reacq_u8: null argument");
+  return track_search_reacq_u8_launch(gray, B, gh, gw, tw, th, search, adapt, lost, relost, templ, key_templ, pos,
+                                      reinterpret_cast<const unsigned long long*>(keys), out, (hipStream_t)stream);
+}
+
+int d3f_track_template_reacq_u8(const uint8_t* frames, int B, int h, int w, int s, int tw, int th, int search, int adapt,
+                                int lost, int relost, uint8_t* templ, const uint8_t* key_templ, int32_t* pos, uint8_t* gray_ws,
+                                uint64_t* keys_ws, int32_t* out, void* stream) {
+  D3F_CHECK(frames && templ && key_templ && pos && gray_ws && keys_ws && out, "track_template_reacq_u8: null argument");
+  return track_template_reacq_u8_launch(frames, B, h, w, s, tw, th, search, adapt, lost, relost, templ, key_templ, pos, gray_ws,
+                                        reinterpret_cast<unsigned long long*>(keys_ws), out, (hipStream_t)stream);
+}
+
 int d3f_image_grid_shape(int images, int nrow, int padding, int H, int W, int32_t dims[2]) {
   D3F_CHECK(dims != nullptr, "image_grid_shape: null argument");
   return image_grid_shape(images, nrow, padding, H, W, dims);

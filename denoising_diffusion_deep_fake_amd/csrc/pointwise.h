@@ -406,6 +406,19 @@ int track_search_rot_u8_launch(const uint8_t* gray, int B, int gh, int gw, int t
 int track_template_rot_u8_launch(const uint8_t* frames, int B, int h, int w, int s, int tw0, int th0, int search, int adapt,
                                  int lost, int steps, int penalty, int amax, const int* table, uint8_t* templ, int* pos,
                                  uint8_t* gray_ws, int* out, hipStream_t stream);
+// re-acquisition (d3f_track_global_u8, d3f_track_search_reacq_u8): key_templ is packed as templ is and never written, keys
+// uint64 [B] = cost << 32 | y << 16 | x of the key template's best position in each frame
+int track_global_check(int B, int gh, int gw, int tw, int th, const void* keys);
+int track_global_u8_launch(const uint8_t* gray, int B, int gh, int gw, int tw, int th, const uint8_t* key_templ,
+                           unsigned long long* keys, hipStream_t stream);
+int track_search_reacq_check(int B, int gh, int gw, int tw, int th, int search, int adapt, int lost, int relost,
+                             const uint8_t* templ, const uint8_t* key_templ, const int* pos, const void* keys, const int* out);
+int track_search_reacq_u8_launch(const uint8_t* gray, int B, int gh, int gw, int tw, int th, int search, int adapt, int lost,
+                                 int relost, uint8_t* templ, const uint8_t* key_templ, int* pos,
+                                 const unsigned long long* keys, int* out, hipStream_t stream);
+int track_template_reacq_u8_launch(const uint8_t* frames, int B, int h, int w, int s, int tw, int th, int search, int adapt,
+                                   int lost, int relost, uint8_t* templ, const uint8_t* key_templ, int* pos, uint8_t* gray_ws,
+                                   unsigned long long* keys_ws, int* out, hipStream_t stream);
 
 // training image grids (image_grid.hip): make_grid + scale + clamp + uint8 of up to 8 fp32 NCHW batches in one launch;
 // `batches` is a host array of n device pointers, out [n][GH][GW][3] with {GH, GW} from image_grid_shape

@@ -28,6 +28,11 @@
 // track_search_rot_kernel and track_seed_rot_kernel (d3f_track_search_rot_u8, d3f_track_seed_rot_u8, opt-in): the same
 // search over the neighbouring angles of the box too, the cost on a disc; their comment stands in front of them,
 // tests/track_rot_restatement.py restates them.
+//
+// track_global_kernel and track_search_reacq_kernel (d3f_track_global_u8, d3f_track_search_reacq_u8, opt-in): the key template
+// against every position of the reduced image, over all CUs, and the serial search that takes a frame it does not find from
+// there; their comments stand in front of them, tests/track_reacq_restatement.py restates them.  The row walk of all five
+// search kernels is one device function, track_row_sad4.
 #include "../../include/d3f_hip.h"
 #include "common.h"
 #include "pointwise.h"
@@ -161,9 +166,42 @@ struct SearchGeom {
   int B, gh, gw, tw, th, R, adapt, lost;
 };
 
-__global__ __launch_bounds__(TS_THREADS) void track_search_kernel(const uint8_t* __restrict__ gray, SearchGeom g,
-                                                                 uint8_t* __restrict__ templ, int* __restrict__ pos,
-                                                                 int* __restrict__ out) {
+// One row of a template against one staged window row for four candidates next to each other: row, the window row's dword
+// that holds the first candidate's first byte, ph that byte's place in it; trow, the template row's dwords (zero behind its
+// n bytes); nfull = n >> 2 whole dwords, each three of the window's dwords rotated into 64 bits and one v_qsad_pk_u16_u8
+// (four sums of absolute differences, the window at byte offsets 0..3; 16-bit sums: at most 16 dwords of 4 * 255 a row);
+// with has_tail (n & 3 != 0) the last, partial dword through v_sad_u8, the window's bytes behind n masked by tail.  The
+// four sums are added to cost.  Reads row[0 .. nfull + 1], and row[nfull + 2] with has_tail.
+__device__ __forceinline__ void track_row_sad4(const uint32_t* row, int ph, const uint32_t* trow, int nfull, bool has_tail,
+                                               uint32_t tail, uint32_t (&cost)[4]) {
+  uint32_t d0 = row[0], d1 = row[1];
+  u64 acc = 0;
+  for (int m = 0; m < nfull; ++m) {
+    const uint32_t d2 = row[m + 2];
+    const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
+    acc = __builtin_amdgcn_qsad_pk_u16_u8((u64)w1 << 32 | w0, trow[m], acc);
+    d0 = d1, d1 = d2;
+  }
+  if (has_tail) {
+    const uint32_t d2 = row[nfull + 2];
+    const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
+    const uint32_t t = trow[nfull];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cost[i] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, i) & tail, t, cost[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) cost[i] += (uint32_t)(acc >> (16 * i)) & 0xffffu;
+}
+
+// The serial search in its two forms.  REACQ false: track_search_kernel, what d3f_track_search_u8 specifies.  REACQ true:
+// track_search_reacq_kernel (d3f_track_search_reacq_u8): a frame that the window does not find takes the whole-frame
+// search's keys[b] (track_global_kernel, below) -- at a cost of at most relost a sample the position becomes the key's,
+// the template the key template's bytes and the row (x, y, gcost, 2); otherwise the frame is lost as in the plain form.
+template <bool REACQ>
+__device__ __forceinline__ void track_search_body(const uint8_t* __restrict__ gray, const SearchGeom& g,
+                                                  uint8_t* __restrict__ templ, int* __restrict__ pos, int* __restrict__ out,
+                                                  const uint8_t* __restrict__ key_templ, const u64* __restrict__ keys,
+                                                  int relost) {
   __shared__ uint32_t win[TS_WMAX * TS_PITCH_DW];
   __shared__ uint32_t tl[TRACK_MAX_SIDE * TS_TDW];
   __shared__ u64 red[TS_THREADS / 64];
@@ -229,25 +267,8 @@ __global__ __launch_bounds__(TS_THREADS) void track_search_kernel(const uint8_t*
         for (int j = part * rpp; j < j1; ++j) {
           const int r = cyr + j;
           const int o = ((a0 + r * g.gw) & 3) + cxr, ph = o & 3;
-          const uint32_t* row = win + r * TS_PITCH_DW + (o >> 2);
-          const uint32_t* trow = tl + j * TS_TDW;
-          uint32_t d0 = row[0], d1 = row[1];
-          u64 acc = 0;  // four 16-bit sums: at most 16 dwords of 4 * 255 a row
-          for (int m = 0; m < nfull; ++m) {
-            const uint32_t d2 = row[m + 2];
-            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
-            acc = __builtin_amdgcn_qsad_pk_u16_u8((u64)w1 << 32 | w0, trow[m], acc);
-            d0 = d1, d1 = d2;
-          }
-          if (tw & 3) {  // the row's last, partial dword: the window's bytes behind tw masked, the template's are 0
-            const uint32_t d2 = row[nfull + 2];
-            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
-            const uint32_t t = trow[nfull];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) cost[i] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, i) & tail, t, cost[i]);
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) cost[i] += (uint32_t)(acc >> (16 * i)) & 0xffffu;
+          // (the row's last, partial dword: the window's bytes behind tw masked, the template's are 0)
+          track_row_sad4(win + r * TS_PITCH_DW + (o >> 2), ph, tl + j * TS_TDW, nfull, (tw & 3) != 0, tail, cost);
         }
       }
       for (int off = 1; off < p; off <<= 1)
@@ -275,6 +296,7 @@ __global__ __launch_bounds__(TS_THREADS) void track_search_kernel(const uint8_t*
     for (int k = 1; k < TS_THREADS / 64; ++k) best = red[k] < best ? red[k] : best;
     const int cost = (int)(best >> 32), dx = (int)(best & 255) - R, dy = (int)((best >> 8) & 255) - R;
     const int found = cost <= g.lost * tw * th;
+    int row_cost = cost, row_found = found;  // what the output row says: the whole-frame search may change both
     if (found) {
       px += dx, py += dy;
       if (g.adapt > 0)
@@ -285,14 +307,159 @@ __global__ __launch_bounds__(TS_THREADS) void track_search_kernel(const uint8_t*
           *t = (uint8_t)((*t * (8 - g.adapt) + wv * g.adapt + 4) >> 3);
         }
     }
+    if constexpr (REACQ) {
+      if (!found) {
+        const u64 gkey = keys[b];  // the same for every lane
+        const uint32_t gcost = (uint32_t)(gkey >> 32);
+        if (gcost <= (uint32_t)(relost * tw * th)) {
+          // (a key the whole-frame search never wrote: kept inside the image, as the position at the start is)
+          px = min((int)(gkey & 0xffffu), g.gw - tw), py = min((int)((gkey >> 16) & 0xffffu), g.gh - th);
+          for (int idx = tid; idx < tw * th; idx += TS_THREADS) tb[(idx / tw) * TRACK_MAX_SIDE + idx % tw] = key_templ[idx];
+          row_cost = (int)gcost, row_found = 2;
+        }
+      }
+    }
     if (tid == 0) {
       int* o = out + 4L * b;
-      o[0] = px, o[1] = py, o[2] = cost, o[3] = found;
+      o[0] = px, o[1] = py, o[2] = row_cost, o[3] = row_found;
     }
     __syncthreads();  // the window, the template and red are the next frame's
   }
   for (int i = tid; i < tw * th; i += TS_THREADS) templ[i] = tb[(i / tw) * TRACK_MAX_SIDE + i % tw];
   if (tid == 0) pos[0] = px, pos[1] = py;
+}
+
+__global__ __launch_bounds__(TS_THREADS) void track_search_kernel(const uint8_t* __restrict__ gray, SearchGeom g,
+                                                                 uint8_t* __restrict__ templ, int* __restrict__ pos,
+                                                                 int* __restrict__ out) {
+  track_search_body<false>(gray, g, templ, pos, out, nullptr, nullptr, 0);
+}
+
+__global__ __launch_bounds__(TS_THREADS) void track_search_reacq_kernel(const uint8_t* __restrict__ gray, SearchGeom g,
+                                                                       uint8_t* __restrict__ templ, int* __restrict__ pos,
+                                                                       int* __restrict__ out,
+                                                                       const uint8_t* __restrict__ key_templ,
+                                                                       const u64* __restrict__ keys, int relost) {
+  track_search_body<true>(gray, g, templ, pos, out, key_templ, keys, relost);
+}
+
+// ---- the whole-frame search (include/d3f_hip.h: d3f_track_global_u8; tests/track_reacq_restatement.py) ----
+// track_global_kernel: the key template K against EVERY position of the reduced image, the frames independent of each other:
+// the grid is (tiles of TG_X x TG_Y candidate positions, B), a workgroup of TG_THREADS lanes a tile.  It stages K (rows 64
+// bytes apart, zero behind tw) and the (TG_Y - 1 + th) x (TG_X - 1 + tw) window its tile needs as aligned dwords, a row at
+// whatever byte phase its address has, as track_search_kernel stages its window; a lane takes four candidates next to each
+// other in x and one of TG_PARTS parts of the template's rows (track_row_sad4, the serial search's walk), the parts are
+// added with shuffles, the tile's keys cost << 32 | y << 16 | x reduced with shuffles and through LDS, and lane 0 takes the
+// minimum into keys[b] with ONE 64-bit atomicMin (a vector atomic, global_atomic_umin_x2) -- on keys that
+// track_keys_fill_kernel, the launch before it on the stream, set to all-ones.  A minimum: exact in any order.
+// 16 x 8 candidates a tile: a 1080 x 1920 frame at stride 5 (216 x 384, a 48 x 48 template: 337 x 169 candidates) is
+// 22 x 22 = 484 tiles, nearly two for each of the 256 CUs at B = 1.  LDS: 71 x 24 dwords of window (6816 bytes), 4096 bytes
+// of template and 32 bytes of keys, 10 944 bytes in all.
+constexpr int TG_THREADS = 256;
+constexpr int TG_X = 16, TG_Y = 8;                            // candidate positions of a tile
+constexpr int TG_GROUPS = TG_X / 4 * TG_Y;                    // groups of four candidates
+constexpr int TG_PARTS = TG_THREADS / TG_GROUPS;              // lanes of a group, next to each other: parts of the rows
+constexpr int TG_WROWS = TG_Y - 1 + TRACK_MAX_SIDE;           // rows and bytes per row of the widest window
+constexpr int TG_WBYTES = TG_X - 1 + TRACK_MAX_SIDE;
+constexpr int TG_STAGE_DW = (TG_WBYTES + 3 + 3) / 4;          // dwords that can hold bytes of a window row
+constexpr int TG_PITCH_DW = TG_STAGE_DW + 3;                  // and the dwords a lane's last rotation reads behind them
+static_assert(TG_X % 4 == 0 && TG_GROUPS * TG_PARTS == TG_THREADS && TG_PARTS <= 64 && (TG_PARTS & (TG_PARTS - 1)) == 0,
+              "a group's parts are a power of two of neighbouring lanes of one wave");
+static_assert((3 + TG_X - 4) / 4 + TRACK_MAX_SIDE / 4 + 1 < TG_PITCH_DW, "the last dword a lane reads lies in its row");
+
+struct GlobalGeom {
+  int B, gh, gw, tw, th, ntx;  // ntx: tiles in a row of tiles
+};
+
+__global__ __launch_bounds__(256) void track_keys_fill_kernel(u64* __restrict__ keys, int B) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < B) keys[i] = ~0ull;
+}
+
+__global__ __launch_bounds__(TG_THREADS) void track_global_kernel(const uint8_t* __restrict__ gray, GlobalGeom g,
+                                                                 const uint8_t* __restrict__ key_templ,
+                                                                 u64* __restrict__ keys) {
+  __shared__ uint32_t win[TG_WROWS * TG_PITCH_DW];
+  __shared__ uint32_t tl[TRACK_MAX_SIDE * TS_TDW];
+  __shared__ u64 red[TG_THREADS / 64];
+  const int tid = threadIdx.x, tw = g.tw, th = g.th, b = blockIdx.y;
+  const int tile_y = blockIdx.x / g.ntx, tile_x = blockIdx.x - tile_y * g.ntx;
+  const int x0 = tile_x * TG_X, y0 = tile_y * TG_Y;
+  const int ncx = min(TG_X, g.gw - tw + 1 - x0), ncy = min(TG_Y, g.gh - th + 1 - y0);  // the tile's candidates: both >= 1
+  const int ww = ncx - 1 + tw, wh = ncy - 1 + th;                                      // its window, inside the image
+  // K: a lane a dword of a row, the bytes behind tw as 0 (the tail's mask relies on it)
+  for (int idx = tid; idx < th * TS_TDW; idx += TG_THREADS) {
+    const int j = idx / TS_TDW, m4 = idx - j * TS_TDW;
+    uint32_t d = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (4 * m4 + q < tw) d |= (uint32_t)key_templ[j * tw + 4 * m4 + q] << (8 * q);
+    tl[idx] = d;
+  }
+  const uint8_t* lo = gray;
+  const uint8_t* hi = gray + (long)g.B * g.gh * g.gw;
+  const uint8_t* seg0 = gray + ((long)b * g.gh + y0) * g.gw + x0;
+  const int a0 = (int)(reinterpret_cast<uintptr_t>(seg0) & 3);  // row r of the window starts (a0 + r gw) mod 4 past a dword
+  const int items = wh * TG_STAGE_DW;
+  for (int i0 = tid; i0 < items; i0 += TS_UNROLL * TG_THREADS) {
+    uint32_t v[TS_UNROLL];
+    int at[TS_UNROLL];
+#pragma unroll
+    for (int u = 0; u < TS_UNROLL; ++u) {
+      const int i = i0 + u * TG_THREADS;
+      at[u] = -1;
+      v[u] = 0;
+      if (i >= items) continue;
+      const int r = i / TG_STAGE_DW, k = i - r * TG_STAGE_DW;
+      const int al = (a0 + r * g.gw) & 3;
+      if (4 * k >= al + ww) continue;
+      at[u] = r * TG_PITCH_DW + k;
+      v[u] = track_load_dword(seg0 + (long)r * g.gw - al + 4 * k, lo, hi);
+    }
+#pragma unroll
+    for (int u = 0; u < TS_UNROLL; ++u)
+      if (at[u] >= 0) win[at[u]] = v[u];
+  }
+  __syncthreads();
+  const int grp = tid / TG_PARTS, part = tid - grp * TG_PARTS;
+  const int cyr = grp / (TG_X / 4), cxr = (grp - cyr * (TG_X / 4)) * 4;
+  const bool live = cyr < ncy && cxr < ncx;
+  const int nfull = tw >> 2;  // whole dwords of a template row
+  const uint32_t tail = (tw & 3) ? (1u << (8 * (tw & 3))) - 1u : 0xffffffffu;
+  const int rpp = (th + TG_PARTS - 1) / TG_PARTS;
+  uint32_t cost[4] = {0, 0, 0, 0};
+  if (live) {
+    const int j1 = min(th, (part + 1) * rpp);
+    for (int j = part * rpp; j < j1; ++j) {
+      const int r = cyr + j;
+      const int o = ((a0 + r * g.gw) & 3) + cxr, ph = o & 3;
+      track_row_sad4(win + r * TG_PITCH_DW + (o >> 2), ph, tl + j * TS_TDW, nfull, (tw & 3) != 0, tail, cost);
+    }
+  }
+#pragma unroll
+  for (int off = 1; off < TG_PARTS; off <<= 1)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cost[i] += __shfl_xor(cost[i], off, 64);
+  u64 best = ~0ull;
+  if (live && part == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (cxr + i >= ncx) continue;
+      const u64 key = (u64)cost[i] << 32 | (u64)(y0 + cyr) << 16 | (u64)(x0 + cxr + i);
+      best = key < best ? key : best;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const u64 other = __shfl_xor(best, off, 64);
+    best = other < best ? other : best;
+  }
+  if ((tid & 63) == 0) red[tid >> 6] = best;
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < TG_THREADS / 64; ++k) best = red[k] < best ? red[k] : best;
+    atomicMin(keys + b, best);
+  }
 }
 
 // ---- the scale search (include/d3f_hip.h: d3f_track_search_scale_u8; tests/track_scale_restatement.py) ----
@@ -455,25 +622,9 @@ __global__ __launch_bounds__(TS_THREADS) void track_search_scale_kernel(const ui
         for (int j = part * rpp; j < j1; ++j) {
           const int r = yo + j;
           const int o = ((a0 + r * g.gw) & 3) + xo, ph = o & 3;
-          const uint32_t* row = win + r * SS_PITCH_DW + (o >> 2);
-          const uint32_t* trow = tl + (k * TRACK_MAX_SIDE + j) * TS_TDW;
-          uint32_t d0 = row[0], d1 = row[1];
-          u64 acc = 0;  // four 16-bit sums: at most 16 dwords of 4 * 255 a row
-          for (int m = 0; m < nfull; ++m) {
-            const uint32_t d2 = row[m + 2];
-            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
-            acc = __builtin_amdgcn_qsad_pk_u16_u8((u64)w1 << 32 | w0, trow[m], acc);
-            d0 = d1, d1 = d2;
-          }
-          if (twc & 3) {  // the row's last, partial dword: the window's bytes behind tw(Lc) masked, the template's are 0
-            const uint32_t d2 = row[nfull + 2];
-            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
-            const uint32_t t = trow[nfull];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) cost[i] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, i) & tail, t, cost[i]);
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) cost[i] += (uint32_t)(acc >> (16 * i)) & 0xffffu;
+          // (the row's last, partial dword: the window's bytes behind tw(Lc) masked, the template's are 0)
+          track_row_sad4(win + r * SS_PITCH_DW + (o >> 2), ph, tl + (k * TRACK_MAX_SIDE + j) * TS_TDW, nfull, (twc & 3) != 0, tail,
+                         cost);
         }
       }
       for (int off = 1; off < p; off <<= 1)
@@ -704,26 +855,9 @@ __global__ __launch_bounds__(TS_THREADS) void track_search_rot_kernel(const uint
           const int lo_j = (int)(span[j] & 255u), n_j = (int)(span[j] >> 8), nfull = n_j >> 2;
           const int r = cyr + j;
           const int o = ((a0 + r * g.gw) & 3) + cxr + lo_j, ph = o & 3;
-          const uint32_t* row = win + r * TS_PITCH_DW + (o >> 2);
-          const uint32_t* trow = tl + (k * TRACK_MAX_SIDE + j) * RS_TPITCH_DW;
-          uint32_t d0 = row[0], d1 = row[1];
-          u64 acc = 0;  // four 16-bit sums: at most 16 dwords of 4 * 255 a row
-          for (int m = 0; m < nfull; ++m) {
-            const uint32_t d2 = row[m + 2];
-            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
-            acc = __builtin_amdgcn_qsad_pk_u16_u8((u64)w1 << 32 | w0, trow[m], acc);
-            d0 = d1, d1 = d2;
-          }
-          if (n_j & 3) {  // the span's last, partial dword: the window's bytes behind n(j) masked, the template's are 0
-            const uint32_t tail = (1u << (8 * (n_j & 3))) - 1u;
-            const uint32_t d2 = row[nfull + 2];
-            const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, ph), w1 = __builtin_amdgcn_alignbyte(d2, d1, ph);
-            const uint32_t t = trow[nfull];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) cost[i] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(w1, w0, i) & tail, t, cost[i]);
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) cost[i] += (uint32_t)(acc >> (16 * i)) & 0xffffu;
+          // (the span's last, partial dword: the window's bytes behind n(j) masked, the template's are 0)
+          track_row_sad4(win + r * TS_PITCH_DW + (o >> 2), ph, tl + (k * TRACK_MAX_SIDE + j) * RS_TPITCH_DW, nfull, (n_j & 3) != 0,
+                         (1u << (8 * (n_j & 3))) - 1u, cost);
         }
       }
       for (int off = 1; off < p; off <<= 1)
@@ -866,6 +1000,68 @@ int track_template_u8_launch(const uint8_t* frames, int B, int h, int w, int s, 
   if (int rc = track_search_check(B, h / s, w / s, tw, th, search, adapt, lost, pos, out)) return rc;
   if (int rc = gray_decimate_u8_launch(frames, B, h, w, s, gray_ws, stream)) return rc;
   return track_search_u8_launch(gray_ws, B, h / s, w / s, tw, th, search, adapt, lost, templ, pos, out, stream);
+}
+
+int track_global_check(int B, int gh, int gw, int tw, int th, const void* keys) {
+  if (int rc = track_batch_check("track_global", B)) return rc;
+  D3F_CHECK(gh > 0 && gw > 0 && gh <= 16384 && gw <= 16384, "track_global: reduced size %d x %d outside 1..16384", gh, gw);
+  if (int rc = track_side_check("track_global", tw, th)) return rc;
+  D3F_CHECK(gh >= th && gw >= tw, "track_global: template %d x %d larger than the reduced image %d x %d", tw, th, gw, gh);
+  D3F_CHECK((reinterpret_cast<uintptr_t>(keys) & 7) == 0, "track_global: keys must be aligned to 8 bytes");
+  return 0;
+}
+
+// two launches: the keys set to all-ones, then the tiles' minima taken into them
+int track_global_u8_launch(const uint8_t* gray, int B, int gh, int gw, int tw, int th, const uint8_t* key_templ,
+                           unsigned long long* keys, hipStream_t stream) {
+  if (int rc = track_global_check(B, gh, gw, tw, th, keys)) return rc;
+  if (B == 0) return 0;
+  const int ntx = (gw - tw + TG_X) / TG_X, nty = (gh - th + TG_Y) / TG_Y;  // gw - tw + 1 candidates in a row
+  const GlobalGeom g = {B, gh, gw, tw, th, ntx};
+  hipLaunchKernelGGL(track_keys_fill_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, keys, B);
+  D3F_HIP(hipGetLastError());
+  hipLaunchKernelGGL(track_global_kernel, dim3(ntx * nty, B), dim3(TG_THREADS), 0, stream, gray, g, key_templ, keys);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+int track_search_reacq_check(int B, int gh, int gw, int tw, int th, int search, int adapt, int lost, int relost,
+                             const uint8_t* templ, const uint8_t* key_templ, const int* pos, const void* keys, const int* out) {
+  if (int rc = track_search_check(B, gh, gw, tw, th, search, adapt, lost, pos, out)) return rc;
+  D3F_CHECK(relost >= 0 && relost <= 255, "track_search_reacq: relost %d outside 0..255", relost);
+  D3F_CHECK((reinterpret_cast<uintptr_t>(keys) & 7) == 0, "track_search_reacq: keys must be aligned to 8 bytes");
+  // the tw * th bytes each kernel touches of either template
+  D3F_CHECK(key_templ + tw * th <= templ || templ + tw * th <= key_templ,
+            "track_search_reacq: key_templ overlaps templ (the key template is never adapted: a buffer of its own)");
+  return 0;
+}
+
+int track_search_reacq_u8_launch(const uint8_t* gray, int B, int gh, int gw, int tw, int th, int search, int adapt, int lost,
+                                 int relost, uint8_t* templ, const uint8_t* key_templ, int* pos,
+                                 const unsigned long long* keys, int* out, hipStream_t stream) {
+  if (int rc = track_search_reacq_check(B, gh, gw, tw, th, search, adapt, lost, relost, templ, key_templ, pos, keys, out))
+    return rc;
+  if (B == 0) return 0;
+  const SearchGeom g = {B, gh, gw, tw, th, search, adapt, lost};
+  hipLaunchKernelGGL(track_search_reacq_kernel, dim3(1), dim3(TS_THREADS), 0, stream, gray, g, templ, pos, out, key_templ, keys,
+                     relost);
+  D3F_HIP(hipGetLastError());
+  return 0;
+}
+
+// four launches: the reduced image, the keys' fill, the whole-frame search, the serial search
+int track_template_reacq_u8_launch(const uint8_t* frames, int B, int h, int w, int s, int tw, int th, int search, int adapt,
+                                   int lost, int relost, uint8_t* templ, const uint8_t* key_templ, int* pos, uint8_t* gray_ws,
+                                   unsigned long long* keys_ws, int* out, hipStream_t stream) {
+  // every refusal before any launch
+  if (int rc = gray_decimate_check(B, h, w, s)) return rc;
+  D3F_CHECK(h / s > 0 && w / s > 0, "track_template_reacq: stride %d leaves nothing of %d x %d", s, h, w);
+  if (int rc = track_search_reacq_check(B, h / s, w / s, tw, th, search, adapt, lost, relost, templ, key_templ, pos, keys_ws, out))
+    return rc;
+  if (int rc = gray_decimate_u8_launch(frames, B, h, w, s, gray_ws, stream)) return rc;
+  if (int rc = track_global_u8_launch(gray_ws, B, h / s, w / s, tw, th, key_templ, keys_ws, stream)) return rc;
+  return track_search_reacq_u8_launch(gray_ws, B, h / s, w / s, tw, th, search, adapt, lost, relost, templ, key_templ, pos,
+                                      keys_ws, out, stream);
 }
 
 int track_search_scale_check(int B, int gh, int gw, int tw0, int th0, int search, int adapt, int lost, int levels, int penalty,

@@ -1062,6 +1062,7 @@ def color_coef_smooth(coef, sums_to, n, state, strength=_lib.TEMPORAL_STRENGTH):
 TRACK_TEMPLATE_SIDE, TRACK_SEARCH, TRACK_ADAPT, TRACK_LOST = (_lib.TRACK_TEMPLATE_SIDE, _lib.TRACK_SEARCH, _lib.TRACK_ADAPT,
                                                               _lib.TRACK_LOST)
 TRACK_SCALE_PENALTY = _lib.TRACK_SCALE_PENALTY
+TRACK_RELOST = _lib.TRACK_RELOST
 TRACK_ROT_STEP, TRACK_ROT_MAX, TRACK_ROT_PENALTY = _lib.TRACK_ROT_STEP, _lib.TRACK_ROT_MAX, _lib.TRACK_ROT_PENALTY
 
 
@@ -1124,7 +1125,10 @@ class TrackState:
     with the scale search's level behind it (`pos` is a view of its front): the seed sets it to L0 = max(tw, th), only
     `track_template_scale_u8` reads and moves it, and with it `templ` stays at the seed's size.  A seed with `angle=`
     makes the state one of the rotation search instead: the third entry is the angle index, `rot` = (step, max_degrees) of
-    the seed (None otherwise), `templ` the upright face; only `track_template_rot_u8` follows such a state."""
+    the seed (None otherwise), `templ` the upright face; only `track_template_rot_u8` follows such a state.  A seed with
+    `reacquire=True` keeps `key_templ`, a copy of the template's bytes as the seed wrote them, which nothing adapts and the
+    next seed replaces (None otherwise): what `track_template_reacq_u8` looks for in the whole frame; its keys live in a
+    workspace of their own, grown on demand."""
 
     def __init__(self, device="cuda"):
         device = torch.device(device)
@@ -1138,11 +1142,18 @@ class TrackState:
         self.gray = None
         self.seeded = False
         self.rot = None
+        self.key_templ = None
+        self.keys = None
 
     def workspace(self, n):
         if self.gray is None or self.gray.numel() < n:
             self.gray = torch.empty((n,), dtype=torch.uint8, device=self.templ.device)
         return self.gray
+
+    def keys_workspace(self, n):
+        if self.keys is None or self.keys.numel() < n:
+            self.keys = torch.empty((n,), dtype=torch.int64, device=self.templ.device)
+        return self.keys
 
 
 def track_rot_table(step=TRACK_ROT_STEP, max_degrees=TRACK_ROT_MAX):
@@ -1171,15 +1182,22 @@ def _rot_table_arg(step, max_degrees):
     return len(table) // 2, (C.c_int32 * len(flat))(*flat)
 
 
-def track_seed(state, frame, face, side=TRACK_TEMPLATE_SIDE, angle=None, step=TRACK_ROT_STEP, max_degrees=TRACK_ROT_MAX):
+def track_seed(state, frame, face, side=TRACK_TEMPLATE_SIDE, angle=None, step=TRACK_ROT_STEP, max_degrees=TRACK_ROT_MAX,
+               reacquire=False):
     """(re-)seed `state` from the face box (fx, fy, fw, fh) marked in `frame`, uint8 BGR [h, w, 3] on the HIP device: the
     template is the reduced grey of the box, the level the seed's own (include/d3f_hip.h: d3f_track_seed_scale_u8, the
     launch of d3f_track_seed_u8 with the level stored beside the position).  Returns the geometry.
     angle: the head's roll in the key frame in degrees (0: the tracked angle is relative to the key frame's pose): the seed of
     the rotation search with `step` and `max_degrees` (`track_rot_table`) -- the angle index a0 = round(angle / step), a
-    ValueError outside the table; the template is the box's grey turned back by that angle on the disc (d3f_track_seed_rot_u8)."""
+    ValueError outside the table; the template is the box's grey turned back by that angle on the disc (d3f_track_seed_rot_u8).
+    reacquire: True keeps the seed's template bytes in `state.key_templ` as well, the key template of
+    `track_template_reacq_u8`; every seed replaces it (a seed without reacquire=True by None).  Not together with angle=:
+    the whole-frame search looks for one size at one angle."""
     if not isinstance(state, TrackState):
         raise ValueError("track_seed: state must be a TrackState")
+    if reacquire and angle is not None:
+        raise ValueError("track_seed: reacquire=True with angle=: the whole-frame search looks for the key template at one "
+                         "angle and cannot restore the one the rotation search keeps")
     if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
         raise ValueError("track_seed expects one uint8 frame [h, w, 3]")
     h, w = int(frame.shape[0]), int(frame.shape[1])
@@ -1204,6 +1222,7 @@ def track_seed(state, frame, face, side=TRACK_TEMPLATE_SIDE, angle=None, step=TR
                                                ptr(state.pos_level), stream_ptr()))
         rot = (step, max_degrees)
     state.geometry, state.h, state.w, state.seeded, state.rot = geometry, h, w, True, rot
+    state.key_templ = state.templ.clone() if reacquire else None  # (on the current stream, behind the seed's launch)
     return geometry
 
 
@@ -1231,9 +1250,67 @@ def track_template_u8(frames, state, search=TRACK_SEARCH, adapt=TRACK_ADAPT, los
     return out
 
 
+def track_global_u8(gray, key_templ, tw, th, out=None):
+    """the whole-frame search: the key template (uint8 on the HIP device, th rows of tw bytes packed at the front, as
+    `TrackState.key_templ` holds them) against EVERY position of the reduced grey image(s) [gh, gw] / [B, gh, gw] uint8
+    (contiguous, at any byte address) -> the smallest key of each frame, int64 [B] on the device ([1] for one image).  A key
+    is the C entry's unsigned 64 bits carried in an int64 (never negative: the cost is below 2^20):
+    cost = key >> 32, y = (key >> 16) & 0xffff, x = key & 0xffff -- the smallest sum of absolute differences, and among equal
+    sums the top-most, then the left-most position (include/d3f_hip.h: d3f_track_global_u8).  out: a contiguous int64 tensor
+    [B] to write into."""
+    if gray.dtype != torch.uint8 or gray.dim() not in (2, 3):
+        raise ValueError("track_global_u8 expects a uint8 grey image [gh, gw] or [B, gh, gw]")
+    tw, th = int(tw), int(th)
+    dev = _dev(gray)
+    if key_templ.dtype != torch.uint8 or key_templ.numel() < tw * th or key_templ.device != dev or not key_templ.is_contiguous():
+        raise ValueError(f"track_global_u8: key_templ must be contiguous uint8 of at least {tw} x {th} bytes on the image's device")
+    g = (gray.unsqueeze(0) if gray.dim() == 2 else gray).contiguous()
+    B, gh, gw = g.shape
+    if out is None:
+        keys = torch.empty((B,), dtype=torch.int64, device=dev)
+    else:
+        keys = out
+        if tuple(keys.shape) != (B,) or keys.dtype != torch.int64 or keys.device != dev or not keys.is_contiguous():
+            raise ValueError(f"out must be a contiguous int64 tensor of shape ({B},) on the image's device")
+    if B > 0:
+        check(_lib.lib().d3f_track_global_u8(ptr(g), B, gh, gw, tw, th, ptr(key_templ), ptr(keys), stream_ptr()))
+    return keys
+
+
+def track_template_reacq_u8(frames, state, search=TRACK_SEARCH, adapt=TRACK_ADAPT, lost=TRACK_LOST, relost=TRACK_RELOST):
+    """`track_template_u8` with re-acquisition: a frame that the search window does not find is looked for in the whole
+    frame with the state's key template, and taken from there when that costs at most `relost` (0..255) grey levels a
+    sample -- the position becomes the whole-frame winner's, the template the key template's bytes -> int32 [B, 4] on the
+    device, a row (px, py, cost, found) per frame, found 1 by the window, 2 re-acquired (cost: the whole-frame winner's),
+    0 lost (`track_faces` takes 1 and 2 alike).  The state is one that `track_seed(..., reacquire=True)` seeded.  One device
+    call: the reduced grey of every frame, the whole-frame search of every frame over all CUs, then the serial search
+    (include/d3f_hip.h: d3f_track_template_reacq_u8)."""
+    if not isinstance(state, TrackState) or not state.seeded:
+        raise ValueError("track_template_reacq_u8: state must be a TrackState seeded by track_seed")
+    if state.key_templ is None:
+        raise ValueError("track_template_reacq_u8: the state was seeded without reacquire=True and holds no key template")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError("track_template_reacq_u8 expects uint8 frames [B, h, w, 3]")
+    B, h, w, _ = frames.shape
+    if (h, w) != (state.h, state.w):
+        raise ValueError(f"track_template_reacq_u8: frames of {h} x {w}, the state was seeded on {state.h} x {state.w}")
+    if _dev(frames) != state.templ.device:
+        raise ValueError("track_template_reacq_u8 expects the frames on the state's device")
+    s, _, _, tw, th = state.geometry[:5]
+    out = torch.empty((B, 4), dtype=torch.int32, device=frames.device)
+    if B > 0:
+        x = frames.contiguous()
+        ws = state.workspace(B * (h // s) * (w // s))
+        check(_lib.lib().d3f_track_template_reacq_u8(ptr(x), B, h, w, s, tw, th, int(search), int(adapt), int(lost), int(relost),
+                                                     ptr(state.templ), ptr(state.key_templ), ptr(state.pos), ptr(ws),
+                                                     ptr(state.keys_workspace(B)), ptr(out), stream_ptr()))
+    return out
+
+
 def track_faces(rows, state):
-    """host rows (px, py, cost, found) of `track_template_u8` -> a list of face boxes (x, y, w, h) in frame pixels, None where
-    the frame's row says not found.  state: the TrackState the rows came from, or the geometry it had then"""
+    """host rows (px, py, cost, found) of `track_template_u8` or `track_template_reacq_u8` -> a list of face boxes (x, y, w, h)
+    in frame pixels, None where the frame's row says not found (found 0; 1 and 2, a re-acquired frame, are boxes alike).
+    state: the TrackState the rows came from, or the geometry it had then"""
     s, _, _, _, _, ox, oy, fw, fh = getattr(state, "geometry", state)
     return [(int(px) * s + ox, int(py) * s + oy, fw, fh) if int(found) else None for px, py, _, found in rows]
 

@@ -11,11 +11,17 @@ at every key.  Head roll: --rotate searches the box's angle too, one step (--rot
 --track-rotate; the angle is relative to the key frame's pose unless --key-angle K A gives the roll at that key.  Without
 --rotate the roll is marked by hand: --key-angle K A (repeatable) writes the fifth column from the key angles, interpolated
 linearly.  --rotate and --scale cannot be combined: the rotation search keeps the key's size.
+A face that leaves the search window -- out of the frame and back on the other side, a cut away and back, a hand in front
+of it -- is lost for good without --reacquire [RELOST]: with it, a frame that the window does not find is looked for in the
+whole frame with the key box's own template, and taken from there when that costs at most RELOST (default 8) grey levels
+a sample (ops.track_template_reacq_u8); the frame is written as an ordinary `x y w h` line, and one line on stderr counts
+the found, re-acquired and lost frames.  --reacquire cannot be combined with --scale or --rotate.
 
-    python -m d3f.script_tools.track_face_box VIDEO --key K X Y W H [--key ...] [-o FILE] [--scale | --rotate]
-                                              [--key-angle K A ...]
+    python -m d3f.script_tools.track_face_box VIDEO --key K X Y W H [--key ...] [-o FILE]
+                                              [--scale | --rotate | --reacquire [RELOST]] [--key-angle K A ...]
 """
 import argparse
+import sys
 from pathlib import Path
 
 import torch
@@ -44,9 +50,12 @@ def main():
         rotate_step=args.rotate_step,
         rotate_max=args.rotate_max,
         rotate_penalty=args.rotate_penalty,
+        reacquire=args.reacquire,
         )
     found = sum(box is not None for box in tracker.track)
     print(f"{tracker.output_path}: {len(tracker.track)} frames, the face found in {found}")
+    if args.reacquire is not None:
+        print(tracker.summary(), file=sys.stderr)
 
 
 def parse_command_line_arguments(argv=None):
@@ -95,11 +104,17 @@ def parse_command_line_arguments(argv=None):
                         help=f"with --rotate: what a turn must win by, in 1/4096 grey levels per sample, "
                              f"0..{_lib.TRACK_MAX_SCALE_PENALTY} (default {ops.TRACK_ROT_PENALTY})")
 
+    parser.add_argument("--reacquire", type=int, nargs="?", const=ops.TRACK_RELOST, default=None, metavar="RELOST",
+                        help=f"look for a face that the search window lost in the whole frame, with the key box's own "
+                             f"template, and take it from there at a mean absolute difference of at most RELOST grey "
+                             f"levels, 0..255 (default {ops.TRACK_RELOST}, half of --lost's default: a whole frame has far "
+                             f"more candidates than the window); not with --scale or --rotate")
+
     args = parser.parse_args(argv)
     try:
         check_settings(sorted_keys(args.key), args.batch_frames, args.search, args.adapt, args.lost, args.template_side,
                        args.scale, args.scale_penalty, args.rotate, args.rotate_step, args.rotate_max, args.rotate_penalty,
-                       sorted_key_angles(args.key_angle))
+                       sorted_key_angles(args.key_angle), args.reacquire)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -162,10 +177,10 @@ def interpolate_key_angles(key_angles, frames):
 
 def check_settings(keys, batch_frames, search, adapt, lost, template_side, scale=False,
                    scale_penalty=ops.TRACK_SCALE_PENALTY, rotate=False, rotate_step=ops.TRACK_ROT_STEP,
-                   rotate_max=ops.TRACK_ROT_MAX, rotate_penalty=ops.TRACK_ROT_PENALTY, key_angles=None):
-    """keys: what `sorted_keys` gave; key_angles: what `sorted_key_angles` gave.  A ValueError for a setting out of range,
-    --rotate with --scale, and with --rotate a step and range `ops.track_rot_table` refuses, a key angle at a frame without
-    a key or beyond the range"""
+                   rotate_max=ops.TRACK_ROT_MAX, rotate_penalty=ops.TRACK_ROT_PENALTY, key_angles=None, reacquire=None):
+    """keys: what `sorted_keys` gave; key_angles: what `sorted_key_angles` gave; reacquire: None, or the threshold relost.
+    A ValueError for a setting out of range, --rotate with --scale, --reacquire with either, and with --rotate a step and
+    range `ops.track_rot_table` refuses, a key angle at a frame without a key or beyond the range"""
     if int(batch_frames) < 1:
         raise ValueError("--batch-frames is at least 1")
     if not isinstance(scale, bool):
@@ -174,6 +189,14 @@ def check_settings(keys, batch_frames, search, adapt, lost, template_side, scale
         raise ValueError(f"--rotate is True or False, not {rotate!r}")
     if rotate and scale:
         raise ValueError("--rotate with --scale: the rotation search keeps the key's size, the two cannot be combined")
+    if reacquire is not None:
+        if isinstance(reacquire, bool) or not isinstance(reacquire, int) or not 0 <= reacquire <= 255:
+            raise ValueError(f"--reacquire is an integer in 0..255, not {reacquire!r}")
+        if scale or rotate:
+            which = "--scale" if scale else "--rotate"
+            kept = "a level" if scale else "an angle"
+            raise ValueError(f"--reacquire with {which}: that search keeps {kept}, which a whole-frame search of one size and "
+                             f"one angle cannot restore, the two cannot be combined")
     for name, value, low, high in (("--search", search, 1, _lib.TRACK_MAX_SEARCH), ("--adapt", adapt, 0, 8),
                                    ("--lost", lost, 0, 255),
                                    ("--template-side", template_side, _lib.TRACK_MIN_SIDE, _lib.TRACK_MAX_SIDE),
@@ -225,19 +248,25 @@ class TrackFaceBox():
     hundredths of a degree a step, within +-rotate_max degrees, rotate_penalty what a turn must win by.  The fifth column
     and .angles (0 where the track has None; the sink still takes x y w h) are then the tracked angle, a multiple of the step; a key angle seeds the
     angle at its key frame -- a frame without a key there is a ValueError -- and a key without one seeds angle 0: the
-    tracked angle is then relative to that key frame's pose."""
+    tracked angle is then relative to that key frame's pose.
+    reacquire: None, or the threshold relost in grey levels a sample (ops.TRACK_RELOST is the tool's default): a frame that
+    the window does not find is looked for in the whole frame with the key's own template (ops.track_template_reacq_u8; not
+    together with scale=True or rotate=True) and is an ordinary box in .track; .reacquired counts them, `summary()` is the
+    line of counts."""
 
     def __init__(self, video_path, keys, output_path=None, batch_frames=8, frames=None, sink=None, device="cuda",
                  search=ops.TRACK_SEARCH, adapt=ops.TRACK_ADAPT, lost=ops.TRACK_LOST,
                  template_side=ops.TRACK_TEMPLATE_SIDE, scale=False, scale_penalty=ops.TRACK_SCALE_PENALTY, key_angles=None,
                  rotate=False, rotate_step=ops.TRACK_ROT_STEP, rotate_max=ops.TRACK_ROT_MAX,
-                 rotate_penalty=ops.TRACK_ROT_PENALTY):
+                 rotate_penalty=ops.TRACK_ROT_PENALTY, reacquire=None):
 
         self.video_path = Path(video_path)
         self.keys = sorted_keys(keys)
         self.key_angles = sorted_key_angles(key_angles)
         self.keys = check_settings(self.keys, batch_frames, search, adapt, lost, template_side, scale, scale_penalty,
-                                   rotate, rotate_step, rotate_max, rotate_penalty, self.key_angles)
+                                   rotate, rotate_step, rotate_max, rotate_penalty, self.key_angles, reacquire)
+        self.reacquire = reacquire
+        self.reacquired = 0
         self.batch_frames = int(batch_frames)
         self.frames = frames
         self.sink = sink
@@ -283,7 +312,17 @@ class TrackFaceBox():
         elif self.key_angles is not None:
             angles = ", ".join(f"{k} {a / 100.0:.2f}" for k, a in self.key_angles.items())
             lines += (f"fifth column: the box's angle in degrees, interpolated between the key angles (frame angle): {angles}",)
+        if self.reacquire is not None:
+            lines += (f"re-acquisition: a frame the window loses is taken from a whole-frame search of the key's template at "
+                      f"a cost of at most {self.reacquire} a sample",)
         return lines
+
+    def summary(self):
+        """the counts of the run in one line: found (by the window, the key frames among them), re-acquired, lost (written as
+        `-`, the frames before the first key among them)"""
+        lost = sum(box is None for box in self.track)
+        return (f"{len(self.track)} frames: {len(self.track) - lost - self.reacquired} found, {self.reacquired} re-acquired, "
+                f"{lost} lost")
 
     def track_video(self):
 
@@ -323,7 +362,8 @@ class TrackFaceBox():
                     geometry = ops.track_seed(state, dev[cut], self.keys[first + cut], self.template_side, angle / 100.0,
                                               self.rotate_step, self.rotate_max)
                 else:
-                    geometry = ops.track_seed(state, dev[cut], self.keys[first + cut], self.template_side)
+                    geometry = ops.track_seed(state, dev[cut], self.keys[first + cut], self.template_side,
+                                              reacquire=self.reacquire is not None)
                 s, tx, ty, _, _, ox, oy, fw, fh = geometry
                 boxes[cut] = (tx * s + ox, ty * s + oy, fw, fh)  # the key's box, clipped
                 if self.rotate:  # and the angle of the seed's index
@@ -341,6 +381,7 @@ class TrackFaceBox():
                     boxes[index:index + count] = ops.track_scale_faces(rows[at:at + count], geometry, dev.shape[1:3])
                 else:
                     boxes[index:index + count] = ops.track_faces(rows[at:at + count], geometry)
+                    self.reacquired += sum(int(row[3]) == 2 for row in rows[at:at + count])
                 at += count
         return boxes
 
@@ -350,6 +391,8 @@ class TrackFaceBox():
                                              self.rotate_step, self.rotate_max)
         if self.scale:
             return ops.track_template_scale_u8(dev, state, self.search, self.adapt, self.lost, 1, self.scale_penalty)
+        if self.reacquire is not None:
+            return ops.track_template_reacq_u8(dev, state, self.search, self.adapt, self.lost, self.reacquire)
         return ops.track_template_u8(dev, state, self.search, self.adapt, self.lost)
 
 

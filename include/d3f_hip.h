@@ -945,6 +945,48 @@ int d3f_track_template_rot_u8(const uint8_t* frames, int B, int h, int w, int s,
                               int lost, int steps, int penalty, int amax, const int32_t* table, uint8_t* templ, int32_t* pos,
                               uint8_t* gray_ws, int32_t* out, void* stream);
 
+/* Template tracker, re-acquisition (opt-in; the entries above are untouched by it): a face that the search window loses --
+ * it left the frame and came back elsewhere, a cut away and back, a hand in front of it -- is looked for in the whole
+ * frame.  tests/track_reacq_restatement.py restates it; DESIGN.md section 4 holds the specification.  All integers, unsigned
+ * where a key is formed.  It searches neither the size nor the angle: the state is the plain entries'.
+ * The key template K (key_templ: packed as templ is, tw bytes a row, th rows) holds the bytes the seed wrote into templ; it is
+ * never adapted and never written by these entries, and the next seed replaces it.  An adapted template drifts; the key box
+ * was marked by hand.
+ * d3f_track_global_u8: gray [B][gh][gw], any byte address; per frame b, independent of every other frame and of the tracker's
+ * state:
+ *   - every position (x, y) with 0 <= x <= gw - tw and 0 <= y <= gh - th is a candidate;
+ *   - cost = sum over the template of |gray[b][y + j][x + i] - K[j][i]|, below 2^20;
+ *   - key = cost << 32 | y << 16 | x, unsigned 64 bits (sizes are at most 16384: each coordinate fits its field);
+ *   - keys[b] = the smallest key: equal costs go to the top-most position, then the left-most; a constant image gives
+ *     (cost, 0, 0).  A minimum: exact in any order of evaluation.
+ * Two launches: keys[0..B) set to all-ones, then a grid of (tiles of 16 x 8 candidate positions, B) workgroups, each taking
+ * its tile's smallest key into keys[b] with one 64-bit atomicMin (an ordinary vector atomic).  No dword is loaded whole
+ * outside gray's B gh gw bytes, and nothing outside keys[0..B) is written.
+ * d3f_track_search_reacq_u8: d3f_track_search_u8 with keys [B] of the same gray and K.  For each frame in order:
+ *   - the step of d3f_track_search_u8 exactly as it is.  Found: pos and templ are updated as there, out[b] = (x, y, cost, 1);
+ *   - not found: gcost = keys[b] >> 32.  gcost <= relost * tw * th: pos = (keys[b] & 0xffff, (keys[b] >> 16) & 0xffff), templ = K
+ *     byte for byte, out[b] = (pos.x, pos.y, gcost, 2).  Otherwise pos and templ stay, out[b] = (pos.x, pos.y, cost, 0) as there;
+ *   - the next frame searches its window from wherever this one ended.
+ * keys[b] depends on frame b and K alone, so cutting a call anywhere changes nothing.  relost, 0..255 grey levels a sample:
+ * D3F_TRACK_RELOST = 8, half of D3F_TRACK_LOST -- a whole frame has tens of thousands of candidates where the window has a
+ * thousand, so it gets the stricter threshold: a design choice, not a measurement (on the tests' recipe K costs 2.4 .. 2.9
+ * levels a sample where the patch is and 30 .. 33 at the best place of a frame without it).  relost = 0 re-acquires only an
+ * exact copy of K.
+ * d3f_track_template_reacq_u8: d3f_gray_decimate_u8 of the frames into gray_ws [B][gh][gw], d3f_track_global_u8 of it into
+ * keys_ws [B], then d3f_track_search_reacq_u8: four launches in one call.
+ * B == 0 touches nothing.  Refused before any device call: what d3f_track_search_u8 refuses (d3f_track_global_u8: of that, what
+ * it has arguments for), relost outside 0..255, a null key_templ or keys, keys not 8-byte aligned, key_templ overlapping templ
+ * (the tw * th bytes of each). */
+#define D3F_TRACK_RELOST 8
+int d3f_track_global_u8(const uint8_t* gray, int B, int gh, int gw, int tw, int th, const uint8_t* key_templ,
+                        uint64_t* keys /* uint64 [B] */, void* stream);
+int d3f_track_search_reacq_u8(const uint8_t* gray, int B, int gh, int gw, int tw, int th, int search, int adapt, int lost,
+                              int relost, uint8_t* templ, const uint8_t* key_templ, int32_t* pos, const uint64_t* keys,
+                              int32_t* out /* [B][4] */, void* stream);
+int d3f_track_template_reacq_u8(const uint8_t* frames, int B, int h, int w, int s, int tw, int th, int search, int adapt,
+                                int lost, int relost, uint8_t* templ, const uint8_t* key_templ, int32_t* pos, uint8_t* gray_ws,
+                                uint64_t* keys_ws, int32_t* out, void* stream);
+
 /* log_batch_as_image_grid of the three LitModules (d3f/train_deep_fake/lit_module.py:235-249,
  * d3f/train_denoiser/lit_module.py:157-171, d3f/balance_training_images/lit_module.py:197-211):
  * torchvision.utils.make_grid(batch[:images], nrow, padding, pad_value), the whole grid -- padding included -- taken
